@@ -3,13 +3,18 @@
 on synthetic particle x (parameter | metric) matrices, with the inputs resident in HBM.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR               (also writes the last timed step's outputs as DIR/<name>.npy)
+  python bench.py ... --full                           (also every measurement outside the timed region, listed below)
 
 A "step" is one generation: abc_generation_dev on one GPU, or the row-sharded driver (RCCL collectives) on N GPUs.
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, higher_is_better, dtype,
+ms_per_step); the fields below are measured by runs of their own after the timed region, only with --full (null without it).
 Default partitioning is STRONG scaling of the stated configuration: the set has the BASELINE.json size whatever N is
 (configs[2]: 1e6 particles, K = K' = 1e5), its rows and the rows of the next set are split evenly over the ranks.
 --scaling weak keeps the particles per GPU fixed instead (K = K' = 0.1 x all particles then grow with N, and the pair sums
 of the weight stage, K K' / N per GPU, with them).
-Prints ONE JSON line on rank 0 carrying the driver contract plus
+Prints ONE JSON line on rank 0 carrying the driver contract plus, with --full,
+  stage_ms_per_step   a separate pass of at most five steps with every stage timer on
   roofline            the kernel that dominates the step (the pair sums of the importance weights, k_kde_split):
                       achieved = ALGORITHMIC flops, K K' (3 P + 1) per launch, / HIP-event time measured live,
                       against the dense f16 MFMA peak (the pipe the dot products run on); the matrix work actually ISSUED
@@ -19,6 +24,7 @@ Prints ONE JSON line on rank 0 carrying the driver contract plus
   sustained           >= 2 s of back-to-back steps after the timed region (the dominant kernel power-limits the chip)
   extra               legs outside the timed region: fp64 pair-sum kernel, INDEPENDENT noise (the reference's default),
                       particle_ranking_simple, the host-pointer drop-in call, the host alias build on log-normal weights
+  set0, scaling_model the first set's step (no weight stage); the predicted strong-scaling curve (N = 1 only)
   cpu_baseline        the single-threaded CPU oracle on a bounded sample of the same workload (rank 0, N = 1 only).
 """
 import argparse
@@ -104,8 +110,14 @@ def parse_args(argv=None):
                     help="PLS component rule of the timed generation (AbcUtil.cpp:447-449): wilcoxon = argmin PRESS reduced by the "
                          "Wilcoxon signed-rank test (SURVEY A.2; the default of the drop-in: C++ facade, shell, Python mirrors), "
                          "press = plain argmin PRESS; the other rule is timed in `extra`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the legs outside the timed region (sustained run, fp64 "
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline does not need: per-stage times, rooflines, set 0, "
+                         "and at N = 1 the legs below and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0's buffers) as DIR/<name>.npy in float64; arrays of more "
+                         "than 2^20 entries as a fixed sample of their columns")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the legs outside the timed region (sustained run, fp64 "
                     "kernel, INDEPENDENT noise, Wilcoxon rule, simple ranking, host-pointer call, log-normal alias build, scaling model)")
     ap.add_argument("--kde-mode", choices=["auto", "fp64"], default="auto",
                     help="weight kernel: auto = split-operand kernel where it applies (default), fp64 = the fp64 vector kernel (A/B runs)")
@@ -324,6 +336,9 @@ def main(argv=None):
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        return 2
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.single_process:
         return run_threads(args)
@@ -401,182 +416,185 @@ def run_rank(args, env):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    stages = ctx.timing_read(reset=True)
-    # per-stage breakdown (informational): a separate short pass with every stage timer on, outside the timed region
-    nb = min(args.steps, 5)
-    ctx.timing_enable(1)
-    for _ in range(nb):
-        step()
-    barrier()
-    stages_all = ctx.timing_read(reset=True)
-    ctx.timing_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(gen, args.dump_outputs)
     elapsed = env.max_over_ranks(elapsed)
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = N / (elapsed / args.steps)
-
-    def per_launch_ms(stage, st=None, steps=None):
-        """average HIP-event bracket of one launch of a stage (ms) and launches per step, from the recorded counts"""
-        ms, _, cnt = (st or stages)[stage]
-        steps = steps or args.steps
-        assert cnt % steps == 0 and cnt > 0, "stage %s: %d samples over %d steps (timer ring lost samples?)" % (stage, cnt, steps)
-        return ms / cnt, cnt // steps
-
-    event_overhead_ms = ctx.timing_overhead(50)      # what an event pair reports beyond the kernel itself (empty-kernel calibration)
-    stage_ms = {k: round((v[0] + v[1]) / nb, 5) for k, v in stages_all.items()}
-    stage_launches = {k: v[2] // nb for k, v in stages_all.items()}
-
-    # ---- roofline of the DOMINANT kernel: the pair sums of the importance weights (k_kde_split / k_kde) ------------------
-    # ALGORITHMIC work (SURVEY 8d): K K' pairs x (3 P flops of the scaled squared distance + 1 exponential) -- `achieved`.
-    # How it is done (DESIGN.md section 4): k_kde_split takes the pair dot products as exact f16 limb products on the matrix
-    # pipe -- 6 ceil(P/16) + 3 v_mfma_f32_32x32x16_{f16,bf16} per 32 x 32 pairs = 32 ISSUED flop per pair and MFMA
-    # (`mfma_issue_frac`) -- and 2 vector instructions per pair (v_exp_f32 [8 issue cycles], f32 add) + 18 per batch of 16
-    # pairs = 4.3 issue slots per pair.  k_kde (fp64 fallback): 1 add + PP FMAs + 13 for 2^x per pair, no matrix work.
-    kde_bracket_ms, kde_launches = per_launch_ms("k_kde") if Kp else (0.0, 0)
-    kde_ms = max(kde_bracket_ms - event_overhead_ms, 0.0)
-    pairs = float(split(K, world, rank)[1]) * Kp
-    flops_alg = pairs * (3.0 * P + 1.0)
-    PPad = 2
-    while PPad < P:
-        PPad *= 2
     which = ctx.kde_last_kernel() if Kp else _lib.KDE_RAN_NONE
-    issue_peak = 256 * 4 * 2.4e9 / 4.0                # wave-instructions per second: 1024 SIMDs, 4 cycles each, 2.4 GHz
-    alg_tf = flops_alg / (kde_ms * 1e-3) / 1e12 if kde_ms > 0 else 0.0
-    if which == _lib.KDE_RAN_SPLIT:
-        nch_ = 1 if P <= 16 else (2 if P <= 32 else 4)          # 16-parameter chunks of the split kernel
-        # (norm steps folded into spare K-slots where the last chunk has three; else, from 4e9 pairs, tiles in the order of the norm
-        # tops and one step for top and batch reference)
-        mfma_per_block = 6 * nch_ + (1 if P + 3 <= 16 * nch_ else (2 if pairs >= 4.0e9 else 3))
-        flops_issued = pairs * mfma_per_block * 32.0   # 32 x 32 x 16 x 2 flop per MFMA over 1024 pairs
-        # vector issue slots of 4 cycles per pair besides the MFMAs, counted in the kernel's ISA at 16 parameters: 52.5 vector
-        # instructions per 1024 pairs (16 v_exp_f32 at two slots each, 15 f32 adds, 8 v_max3_f32, 13.5 others) = 68.5 slots / 16
-        slots_per_pair = 4.28
-        issued_tf = flops_issued / (kde_ms * 1e-3) / 1e12 if kde_ms > 0 else 0.0
-        roofline = {"kernel": "k_kde_split", "bound": "mfma", "achieved": round(alg_tf, 1), "peak": MFMA_F16_PEAK_TF,
-                    "unit": "TFLOP/s", "frac": round(alg_tf / MFMA_F16_PEAK_TF, 4),
-                    "traffic": pmc_traffic("k_kde_split", args.config, world),
-                    "flops_algorithmic": flops_alg, "frac_algorithmic": round(alg_tf / MFMA_F16_PEAK_TF, 4),
-                    "flops_issued_mfma": flops_issued, "achieved_issued_mfma": round(issued_tf, 1),
-                    "mfma_issue_frac": round(issued_tf / MFMA_F16_PEAK_TF, 4),
-                    "issued_per_algorithmic_flop": round(flops_issued / flops_alg, 2),
-                    # what bare bf16 MFMA loops sustain on random operands on this chip (the clock gives way under matrix load:
-                    # /opt/skills/guides/MI355X_MICROARCH.md, 'DVFS give-back' item 1): the practical ceiling of issued matrix work
-                    "mfma_sustained_random_data_TFLOPs": MFMA_SUSTAINED_TF,
-                    "mfma_issue_vs_sustained": round(issued_tf / MFMA_SUSTAINED_TF, 4),
-                    "algorithmic_vs_fp64_vector_peak": round(alg_tf / FP64_VALU_PEAK_TF, 3),
-                    "mfma_32x32x16_per_1024_pairs": mfma_per_block,
-                    "pairs_per_launch": pairs, "pairs_per_s": pairs / (kde_ms * 1e-3) if kde_ms > 0 else 0.0,
-                    "valu_issue_slots_per_pair": slots_per_pair,
-                    "valu_issue_frac": round((pairs / 64.0) * (slots_per_pair + mfma_per_block * 2.0 / 16.0) / (kde_ms * 1e-3) / issue_peak, 4)
-                    if kde_ms > 0 else 0.0,
-                    "note": "achieved / frac = ALGORITHMIC flops K K' (3P + 1) (SURVEY 8d) against the dense f16 MFMA peak, the pipe "
-                            "the dot products run on; the fp64 operands travel as three f16 limbs, so the matrix pipe ISSUES "
-                            "issued_per_algorithmic_flop times that (mfma_issue_frac); the exponentials run as v_exp_f32 on the "
-                            "vector pipe (valu_issue_frac); weights within 5e-7 of the fp64 oracle by the kernel's error budget, largest seen 3.1e-7 (profiles/history/r03_kde_accuracy.json, r03_generation_fuzz.json).  The chip clocks down "
-                            "under this kernel (profiles/: clock from GRBM_GUI_ACTIVE)"}
-    else:
-        instr_pair = 1 + PPad + 13
-        roofline = {"kernel": "k_kde", "bound": "fp64_valu", "achieved": round(alg_tf, 2), "peak": FP64_VALU_PEAK_TF, "unit": "TFLOP/s",
-                    "frac": round(alg_tf / FP64_VALU_PEAK_TF, 4), "traffic": pmc_traffic("k_kde<", args.config, world),
-                    "flops_algorithmic": flops_alg, "frac_algorithmic": round(alg_tf / FP64_VALU_PEAK_TF, 4),
-                    "pairs_per_launch": pairs, "valu_instr_per_pair": instr_pair,
-                    "valu_issue_frac": round((pairs / 64.0) * instr_pair / (kde_ms * 1e-3) / issue_peak, 4) if kde_ms > 0 else 0.0}
-    roofline.update({"kernel_ms": round(kde_ms, 5), "launches_per_step": kde_launches, "event_bracket_ms": round(kde_bracket_ms, 5),
-                     "event_overhead_ms": round(event_overhead_ms, 5), "share_of_step": round(kde_ms * kde_launches / ms_per_step, 4)})
 
-    # ---- the dominant HBM kernel (k_gram): one launch per step reads X and Y (local rows) exactly once ---------------------
-    gram_bracket_ms, gram_launches = per_launch_ms("k_gram")
-    gram_ms = max(gram_bracket_ms - event_overhead_ms, 0.0)
-    # (beyond 160 columns the set goes through column-group pairs, several launches: the algorithmic bytes of the set are
-    # spread over them, i.e. `achieved` is then bytes of the set / total time of those launches)
-    gram_bytes = 8.0 * n_loc * (M + P) / gram_launches
-    gram_gbs = gram_bytes / (gram_ms * 1e-3) / 1e9 if gram_ms > 0 else 0.0
-    roofline_hbm = {"kernel": "k_gram", "bound": "hbm", "achieved": round(gram_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(gram_gbs / HBM_PEAK_GBS, 4), "traffic": pmc_traffic("k_gram", args.config, world),
-                    "algorithmic_bytes_per_launch": gram_bytes, "kernel_ms": round(gram_ms, 5), "launches_per_step": gram_launches,
-                    "event_bracket_ms": round(gram_bracket_ms, 5),
-                    "achieved_event_bracket": round(gram_bytes / (gram_bracket_ms * 1e-3) / 1e9, 1) if gram_bracket_ms > 0 else 0.0}
-
-    # ---- SURVEY 8(d): all streaming stages together = the step without the pair-sum kernel ------------------------------
-    # Under the Wilcoxon rule the reference's path reads the validation rows once more (SURVEY A.2: "an extra pass over the test rows":
-    # per-observation residuals of every candidate count): + 8 N_v (M + P) bytes, N_v = the rows behind the training fraction.  The
-    # scores this implementation writes and re-reads between its kernels are NOT algorithmic bytes.
-    nv_loc = (n_loc - int(round(n_loc * 0.5))) if RULE == _lib.RULE_WILCOXON else 0
-
-    def alg_bytes(kp, rule_pass=True):
-        nn, k = nn_loc, K
-        return (8.0 * n_loc * (M + P) + 8.0 * n_loc * M + 8.0 * n_loc + 16.0 * n_loc + 16.0 * k * P + nn * (16.0 * P + 8.0)
-                + 8.0 * kp * P + 8.0 * (k + kp) + (8.0 * nv_loc * (M + P) if rule_pass else 0.0))
-    stream_ms = ms_per_step - kde_ms * kde_launches
-    # `achieved` / `frac`: SURVEY 8(d)'s formula AS WRITTEN (ADVICE round 5: the implementation does not read the validation half of
-    # X a second time -- the ranking's projection leaves the scores in the same pass -- so the rule's pass is not in the headline
-    # bytes; the variant with it stays beside it under its own key, as rounds 4 and 5 reported it)
-    stream_gbs = alg_bytes(Kp, False) / (stream_ms * 1e-3) / 1e9
-    roofline_streaming = {"bound": "hbm", "algorithmic_bytes_per_step": alg_bytes(Kp, False), "bytes_per_particle": round(alg_bytes(Kp, False) / n_loc, 1),
-                          "ms": round(stream_ms, 5), "achieved": round(stream_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": round(stream_gbs / HBM_PEAK_GBS, 4),
-                          "frac_without_the_rules_pass": round(stream_gbs / HBM_PEAK_GBS, 4),
-                          "algorithmic_bytes_with_the_rules_pass": alg_bytes(Kp),
-                          "frac_with_the_rules_pass": round(alg_bytes(Kp) / (stream_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                          "note": "SURVEY 8(d) as written: B_alg / (wall time of a step minus the pair-sum kernel), per GPU; host work "
-                                  "and launch gaps included.  frac_with_the_rules_pass adds 8 N_v (M + P) bytes under the Wilcoxon "
-                                  "component rule -- the pass over the validation rows SURVEY A.2 names for the reference's path, which "
-                                  "this implementation does not make (rounds 4-5 quoted that variant as `frac`)"}
-
-    # set 0 (uniform weights, AbcUtil.cpp:539-545) has no O(K K') stage: reported separately, outside the timed region
-    set0 = None
-    sustained = None
-    extra = None
-    scaling_model = None
-    if world == 1:
-        rng0 = abcutil.rng(67890)
-        gen0 = device.Generation(N, M, P, K, 0, nn_loc, 0.5, A, rule=RULE, multivariate=True, device=dev, ctx=ctx)
-        for _ in range(2):
-            gen0.run(dX, dY, dobs, dpri, rng0)
+    # ---- --full: what the headline does not need, each measured by runs of its own after the timed region ------------------
+    stage_ms, stage_launches = None, {}
+    roofline = roofline_hbm = roofline_streaming = set0 = sustained = extra = scaling_model = None
+    if args.full:
+        stages = ctx.timing_read(reset=True)
+        # per-stage breakdown (informational): a separate short pass with every stage timer on, outside the timed region
+        nb = min(args.steps, 5)
+        ctx.timing_enable(1)
+        for _ in range(nb):
+            step()
         barrier()
-        t1 = time.perf_counter()
-        for _ in range(5):
-            gen0.run(dX, dY, dobs, dpri, rng0)
-        barrier()
-        dt0 = (time.perf_counter() - t1) / 5
-        g0 = alg_bytes(0, False) / dt0 / 1e9
-        set0 = {"value": N / dt0, "unit": "particles/s", "ms_per_step": 1e3 * dt0,
-                "roofline_streaming": {"algorithmic_bytes_per_step": alg_bytes(0, False), "achieved": round(g0, 1), "peak": HBM_PEAK_GBS,
-                                       "unit": "GB/s", "frac": round(g0 / HBM_PEAK_GBS, 4)},
-                "note": "first SMC set: rank + uniform weights + resample/perturb (no importance-weight stage)"}
-
-    if world == 1 and not args.no_extra:
-        # ---- sustained: back-to-back steps for >= --sustained-s seconds (the pair-sum kernel power-limits the chip: the timed
-        # region above is 20 steps on a chip that was idle a moment ago) ---------------------------------------------------------
-        ctx.timing_enable(2)
-        ctx.timing_read(reset=True)
-        ns = 0
-        barrier()
-        t1 = time.perf_counter()
-        while True:
-            for _ in range(25):
-                step()
-            ns += 25
-            torch.cuda.synchronize()
-            if time.perf_counter() - t1 >= args.sustained_s:
-                break
-        dts = time.perf_counter() - t1
-        st_s = ctx.timing_read(reset=True)
+        stages_all = ctx.timing_read(reset=True)
         ctx.timing_enable(False)
-        k_ms = (st_s["k_kde"][0] / st_s["k_kde"][2] - event_overhead_ms) if (Kp and st_s["k_kde"][2]) else 0.0
-        g_ms = st_s["k_gram"][0] / max(st_s["k_gram"][2], 1) - event_overhead_ms
-        sustained = {"seconds": round(dts, 3), "steps": ns, "ms_per_step": round(1e3 * dts / ns, 5), "value": N / (dts / ns),
-                     "pair_sum_kernel_ms": round(k_ms, 5), "k_gram_ms": round(g_ms, 5),
-                     "pair_sum_ms_vs_timed_region": round(k_ms / kde_ms, 4) if kde_ms > 0 else None,
-                     "note": "same step, run back to back for >= %.1f s right after the timed region; the ratio of the pair-sum "
-                             "brackets is the clock the chip holds under sustained load relative to the timed region" % args.sustained_s}
-        extra = extra_legs(args, ctx, wl, dX, dY, dobs, dpri, dtp, dwp, ddvp, N, M, P, K, Kp, A, dev, event_overhead_ms)
-        scaling_model = scaling_model_leg(args, dX, dY, dobs, dpri, dtp, dwp, ddvp, N, M, P, K, Kp, A, dev, RULE,
-                                          ms_per_step, kde_ms * kde_launches, stage_ms, stage_launches, event_overhead_ms, step,
-                                          min_press_step_ms=(extra or {}).get("min_press_rule_step_ms"))
+
+        def per_launch_ms(stage, st=None, steps=None):
+            """average HIP-event bracket of one launch of a stage (ms) and launches per step, from the recorded counts"""
+            ms, _, cnt = (st or stages)[stage]
+            steps = steps or args.steps
+            assert cnt % steps == 0 and cnt > 0, "stage %s: %d samples over %d steps (timer ring lost samples?)" % (stage, cnt, steps)
+            return ms / cnt, cnt // steps
+
+        event_overhead_ms = ctx.timing_overhead(50)      # what an event pair reports beyond the kernel itself (empty-kernel calibration)
+        stage_ms = {k: round((v[0] + v[1]) / nb, 5) for k, v in stages_all.items()}
+        stage_launches = {k: v[2] // nb for k, v in stages_all.items()}
+
+        # ---- roofline of the DOMINANT kernel: the pair sums of the importance weights (k_kde_split / k_kde) ------------------
+        # ALGORITHMIC work (SURVEY 8d): K K' pairs x (3 P flops of the scaled squared distance + 1 exponential) -- `achieved`.
+        # How it is done (DESIGN.md section 4): k_kde_split takes the pair dot products as exact f16 limb products on the matrix
+        # pipe -- 6 ceil(P/16) + 3 v_mfma_f32_32x32x16_{f16,bf16} per 32 x 32 pairs = 32 ISSUED flop per pair and MFMA
+        # (`mfma_issue_frac`) -- and 2 vector instructions per pair (v_exp_f32 [8 issue cycles], f32 add) + 18 per batch of 16
+        # pairs = 4.3 issue slots per pair.  k_kde (fp64 fallback): 1 add + PP FMAs + 13 for 2^x per pair, no matrix work.
+        kde_bracket_ms, kde_launches = per_launch_ms("k_kde") if Kp else (0.0, 0)
+        kde_ms = max(kde_bracket_ms - event_overhead_ms, 0.0)
+        pairs = float(split(K, world, rank)[1]) * Kp
+        flops_alg = pairs * (3.0 * P + 1.0)
+        PPad = 2
+        while PPad < P:
+            PPad *= 2
+        issue_peak = 256 * 4 * 2.4e9 / 4.0                # wave-instructions per second: 1024 SIMDs, 4 cycles each, 2.4 GHz
+        alg_tf = flops_alg / (kde_ms * 1e-3) / 1e12 if kde_ms > 0 else 0.0
+        if which == _lib.KDE_RAN_SPLIT:
+            nch_ = 1 if P <= 16 else (2 if P <= 32 else 4)          # 16-parameter chunks of the split kernel
+            # (norm steps folded into spare K-slots where the last chunk has three; else, from 4e9 pairs, tiles in the order of the norm
+            # tops and one step for top and batch reference)
+            mfma_per_block = 6 * nch_ + (1 if P + 3 <= 16 * nch_ else (2 if pairs >= 4.0e9 else 3))
+            flops_issued = pairs * mfma_per_block * 32.0   # 32 x 32 x 16 x 2 flop per MFMA over 1024 pairs
+            # vector issue slots of 4 cycles per pair besides the MFMAs, counted in the kernel's ISA at 16 parameters: 52.5 vector
+            # instructions per 1024 pairs (16 v_exp_f32 at two slots each, 15 f32 adds, 8 v_max3_f32, 13.5 others) = 68.5 slots / 16
+            slots_per_pair = 4.28
+            issued_tf = flops_issued / (kde_ms * 1e-3) / 1e12 if kde_ms > 0 else 0.0
+            roofline = {"kernel": "k_kde_split", "bound": "mfma", "achieved": round(alg_tf, 1), "peak": MFMA_F16_PEAK_TF,
+                        "unit": "TFLOP/s", "frac": round(alg_tf / MFMA_F16_PEAK_TF, 4),
+                        "traffic": pmc_traffic("k_kde_split", args.config, world),
+                        "flops_algorithmic": flops_alg, "frac_algorithmic": round(alg_tf / MFMA_F16_PEAK_TF, 4),
+                        "flops_issued_mfma": flops_issued, "achieved_issued_mfma": round(issued_tf, 1),
+                        "mfma_issue_frac": round(issued_tf / MFMA_F16_PEAK_TF, 4),
+                        "issued_per_algorithmic_flop": round(flops_issued / flops_alg, 2),
+                        # what bare bf16 MFMA loops sustain on random operands on this chip (the clock gives way under matrix load:
+                        # the MI355X microarchitecture guide, 'DVFS give-back' item 1): the practical ceiling of issued matrix work
+                        "mfma_sustained_random_data_TFLOPs": MFMA_SUSTAINED_TF,
+                        "mfma_issue_vs_sustained": round(issued_tf / MFMA_SUSTAINED_TF, 4),
+                        "algorithmic_vs_fp64_vector_peak": round(alg_tf / FP64_VALU_PEAK_TF, 3),
+                        "mfma_32x32x16_per_1024_pairs": mfma_per_block,
+                        "pairs_per_launch": pairs, "pairs_per_s": pairs / (kde_ms * 1e-3) if kde_ms > 0 else 0.0,
+                        "valu_issue_slots_per_pair": slots_per_pair,
+                        "valu_issue_frac": round((pairs / 64.0) * (slots_per_pair + mfma_per_block * 2.0 / 16.0) / (kde_ms * 1e-3) / issue_peak, 4)
+                        if kde_ms > 0 else 0.0,
+                        "note": "achieved / frac = ALGORITHMIC flops K K' (3P + 1) (SURVEY 8d) against the dense f16 MFMA peak, the pipe "
+                                "the dot products run on; the fp64 operands travel as three f16 limbs, so the matrix pipe ISSUES "
+                                "issued_per_algorithmic_flop times that (mfma_issue_frac); the exponentials run as v_exp_f32 on the "
+                                "vector pipe (valu_issue_frac); weights within 5e-7 of the fp64 oracle by the kernel's error budget, largest seen 3.1e-7 (profiles/history/r03_kde_accuracy.json, r03_generation_fuzz.json).  The chip clocks down "
+                                "under this kernel (profiles/: clock from GRBM_GUI_ACTIVE)"}
+        else:
+            instr_pair = 1 + PPad + 13
+            roofline = {"kernel": "k_kde", "bound": "fp64_valu", "achieved": round(alg_tf, 2), "peak": FP64_VALU_PEAK_TF, "unit": "TFLOP/s",
+                        "frac": round(alg_tf / FP64_VALU_PEAK_TF, 4), "traffic": pmc_traffic("k_kde<", args.config, world),
+                        "flops_algorithmic": flops_alg, "frac_algorithmic": round(alg_tf / FP64_VALU_PEAK_TF, 4),
+                        "pairs_per_launch": pairs, "valu_instr_per_pair": instr_pair,
+                        "valu_issue_frac": round((pairs / 64.0) * instr_pair / (kde_ms * 1e-3) / issue_peak, 4) if kde_ms > 0 else 0.0}
+        roofline.update({"kernel_ms": round(kde_ms, 5), "launches_per_step": kde_launches, "event_bracket_ms": round(kde_bracket_ms, 5),
+                         "event_overhead_ms": round(event_overhead_ms, 5), "share_of_step": round(kde_ms * kde_launches / ms_per_step, 4)})
+
+        # ---- the dominant HBM kernel (k_gram): one launch per step reads X and Y (local rows) exactly once ---------------------
+        gram_bracket_ms, gram_launches = per_launch_ms("k_gram")
+        gram_ms = max(gram_bracket_ms - event_overhead_ms, 0.0)
+        # (beyond 160 columns the set goes through column-group pairs, several launches: the algorithmic bytes of the set are
+        # spread over them, i.e. `achieved` is then bytes of the set / total time of those launches)
+        gram_bytes = 8.0 * n_loc * (M + P) / gram_launches
+        gram_gbs = gram_bytes / (gram_ms * 1e-3) / 1e9 if gram_ms > 0 else 0.0
+        roofline_hbm = {"kernel": "k_gram", "bound": "hbm", "achieved": round(gram_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(gram_gbs / HBM_PEAK_GBS, 4), "traffic": pmc_traffic("k_gram", args.config, world),
+                        "algorithmic_bytes_per_launch": gram_bytes, "kernel_ms": round(gram_ms, 5), "launches_per_step": gram_launches,
+                        "event_bracket_ms": round(gram_bracket_ms, 5),
+                        "achieved_event_bracket": round(gram_bytes / (gram_bracket_ms * 1e-3) / 1e9, 1) if gram_bracket_ms > 0 else 0.0}
+
+        # ---- SURVEY 8(d): all streaming stages together = the step without the pair-sum kernel ------------------------------
+        # Under the Wilcoxon rule the reference's path reads the validation rows once more (SURVEY A.2: "an extra pass over the test rows":
+        # per-observation residuals of every candidate count): + 8 N_v (M + P) bytes, N_v = the rows behind the training fraction.  The
+        # scores this implementation writes and re-reads between its kernels are NOT algorithmic bytes.
+        nv_loc = (n_loc - int(round(n_loc * 0.5))) if RULE == _lib.RULE_WILCOXON else 0
+
+        def alg_bytes(kp, rule_pass=True):
+            nn, k = nn_loc, K
+            return (8.0 * n_loc * (M + P) + 8.0 * n_loc * M + 8.0 * n_loc + 16.0 * n_loc + 16.0 * k * P + nn * (16.0 * P + 8.0)
+                    + 8.0 * kp * P + 8.0 * (k + kp) + (8.0 * nv_loc * (M + P) if rule_pass else 0.0))
+        stream_ms = ms_per_step - kde_ms * kde_launches
+        # `achieved` / `frac`: SURVEY 8(d)'s formula AS WRITTEN (ADVICE round 5: the implementation does not read the validation half of
+        # X a second time -- the ranking's projection leaves the scores in the same pass -- so the rule's pass is not in the headline
+        # bytes; the variant with it stays beside it under its own key, as rounds 4 and 5 reported it)
+        stream_gbs = alg_bytes(Kp, False) / (stream_ms * 1e-3) / 1e9
+        roofline_streaming = {"bound": "hbm", "algorithmic_bytes_per_step": alg_bytes(Kp, False), "bytes_per_particle": round(alg_bytes(Kp, False) / n_loc, 1),
+                              "ms": round(stream_ms, 5), "achieved": round(stream_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(stream_gbs / HBM_PEAK_GBS, 4),
+                              "frac_without_the_rules_pass": round(stream_gbs / HBM_PEAK_GBS, 4),
+                              "algorithmic_bytes_with_the_rules_pass": alg_bytes(Kp),
+                              "frac_with_the_rules_pass": round(alg_bytes(Kp) / (stream_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                              "note": "SURVEY 8(d) as written: B_alg / (wall time of a step minus the pair-sum kernel), per GPU; host work "
+                                      "and launch gaps included.  frac_with_the_rules_pass adds 8 N_v (M + P) bytes under the Wilcoxon "
+                                      "component rule -- the pass over the validation rows SURVEY A.2 names for the reference's path, which "
+                                      "this implementation does not make (rounds 4-5 quoted that variant as `frac`)"}
+
+        # set 0 (uniform weights, AbcUtil.cpp:539-545) has no O(K K') stage: reported separately, outside the timed region
+        if world == 1:
+            rng0 = abcutil.rng(67890)
+            gen0 = device.Generation(N, M, P, K, 0, nn_loc, 0.5, A, rule=RULE, multivariate=True, device=dev, ctx=ctx)
+            for _ in range(2):
+                gen0.run(dX, dY, dobs, dpri, rng0)
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(5):
+                gen0.run(dX, dY, dobs, dpri, rng0)
+            barrier()
+            dt0 = (time.perf_counter() - t1) / 5
+            g0 = alg_bytes(0, False) / dt0 / 1e9
+            set0 = {"value": N / dt0, "unit": "particles/s", "ms_per_step": 1e3 * dt0,
+                    "roofline_streaming": {"algorithmic_bytes_per_step": alg_bytes(0, False), "achieved": round(g0, 1), "peak": HBM_PEAK_GBS,
+                                           "unit": "GB/s", "frac": round(g0 / HBM_PEAK_GBS, 4)},
+                    "note": "first SMC set: rank + uniform weights + resample/perturb (no importance-weight stage)"}
+
+        if world == 1 and not args.no_extra:
+            # ---- sustained: back-to-back steps for >= --sustained-s seconds (the pair-sum kernel power-limits the chip: the timed
+            # region above is 20 steps on a chip that was idle a moment ago) ---------------------------------------------------------
+            ctx.timing_enable(2)
+            ctx.timing_read(reset=True)
+            ns = 0
+            barrier()
+            t1 = time.perf_counter()
+            while True:
+                for _ in range(25):
+                    step()
+                ns += 25
+                torch.cuda.synchronize()
+                if time.perf_counter() - t1 >= args.sustained_s:
+                    break
+            dts = time.perf_counter() - t1
+            st_s = ctx.timing_read(reset=True)
+            ctx.timing_enable(False)
+            k_ms = (st_s["k_kde"][0] / st_s["k_kde"][2] - event_overhead_ms) if (Kp and st_s["k_kde"][2]) else 0.0
+            g_ms = st_s["k_gram"][0] / max(st_s["k_gram"][2], 1) - event_overhead_ms
+            sustained = {"seconds": round(dts, 3), "steps": ns, "ms_per_step": round(1e3 * dts / ns, 5), "value": N / (dts / ns),
+                         "pair_sum_kernel_ms": round(k_ms, 5), "k_gram_ms": round(g_ms, 5),
+                         "pair_sum_ms_vs_timed_region": round(k_ms / kde_ms, 4) if kde_ms > 0 else None,
+                         "note": "same step, run back to back for >= %.1f s right after the timed region; the ratio of the pair-sum "
+                                 "brackets is the clock the chip holds under sustained load relative to the timed region" % args.sustained_s}
+            extra = extra_legs(args, ctx, wl, dX, dY, dobs, dpri, dtp, dwp, ddvp, N, M, P, K, Kp, A, dev, event_overhead_ms)
+            scaling_model = scaling_model_leg(args, dX, dY, dobs, dpri, dtp, dwp, ddvp, N, M, P, K, Kp, A, dev, RULE,
+                                              ms_per_step, kde_ms * kde_launches, stage_ms, stage_launches, event_overhead_ms, step,
+                                              min_press_step_ms=(extra or {}).get("min_press_rule_step_ms"))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         X, Y = dX.cpu().numpy().T, dY.cpu().numpy().T
         th_prev, w_prev, dv_prev = dtp.cpu().numpy().T, dwp.cpu().numpy(), ddvp.cpu().numpy()
         cpu = cpu_baseline(cfg, wl, X, Y, obs, spec, th_prev, w_prev, dv_prev, K, A, args.cpu_budget_s)
@@ -598,8 +616,8 @@ def run_rank(args, env):
                        "ncomp_chosen": int(gen.ncomp if use_sharded else gen.ncomp.value),
                        "pls_component_rule": "wilcoxon" if args.rule == "wilcoxon" else "min_press",
                        "parallelism": "row-sharded x%d" % world, "launcher": env.launcher, "collectives": comm_kind,
-                       "collectives_per_step": stage_launches.get("collectives", 0) if use_sharded else 0,
-                       "collectives_ms_per_step": stage_ms.get("collectives", 0.0) if use_sharded else 0.0},
+                       "collectives_per_step": (stage_launches.get("collectives", 0) if use_sharded else 0) if args.full else None,
+                       "collectives_ms_per_step": (stage_ms.get("collectives", 0.0) if use_sharded else 0.0) if args.full else None},
             "roofline": roofline,
             "roofline_hbm": roofline_hbm,
             "roofline_streaming": roofline_streaming,
@@ -612,6 +630,28 @@ def run_rank(args, env):
         }
         print(json.dumps(out))
     env.finish()
+
+
+DUMP_MAX_ENTRIES = 1 << 20       # per array (8 MB of float64): the ten arrays of a generation stay under 64 MB
+
+
+def dump_outputs(gen, out_dir):
+    """--dump-outputs: the output buffers of the generation's last run, i.e. what abc_generation_dev hands its caller (selected rows,
+    distances, parameters, weights, doubled variances, Cholesky factor, proposals, parents, simulator seeds, component count), one
+    float64 .npy each (the integer outputs are below 2^53).  An array of more than DUMP_MAX_ENTRIES entries is cut to a sample of its
+    columns (particles) drawn from a generator seeded by the column count: the same columns in every run of the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    ncomp = gen.ncomp if isinstance(gen.ncomp, int) else gen.ncomp.value
+    arrays = {"idx": gen.idx, "dist": gen.dist, "theta": gen.theta, "w": gen.w, "dv": gen.dv, "L": gen.L, "next": gen.next,
+              "parent": gen.parent, "seeds": gen.seeds, "ncomp": torch.tensor([ncomp])}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_MAX_ENTRIES:
+            cols = t.shape[-1]
+            keep = np.sort(np.random.default_rng(cols).choice(cols, DUMP_MAX_ENTRIES // (t.numel() // cols), replace=False))
+            t = t.index_select(t.dim() - 1, torch.from_numpy(keep).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float64).cpu().numpy())
 
 
 def extra_legs(args, ctx, wl, dX, dY, dobs, dpri, dtp, dwp, ddvp, N, M, P, K, Kp, A, dev, event_overhead_ms):

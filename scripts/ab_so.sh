@@ -4,7 +4,7 @@
 REPS="$1"; STAGE="$2"; shift; shift
 for r in $(seq 1 $REPS); do
   for SO in "$@"; do
-    ABCSMC_HIP_SO="$PWD/$SO" python3 bench.py --no-cpu-baseline --no-extra 2>/dev/null | python3 -c "
+    ABCSMC_HIP_SO="$PWD/$SO" python3 bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('[%-28s] step %.4f kde %.4f stream %.4f set0 %.4f $STAGE %.4f' % ('$SO'.split('/')[-1], d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline_streaming']['ms'], d['set0']['ms_per_step'], d['stage_ms_per_step'].get('$STAGE', 0.0)))"

@@ -7,8 +7,7 @@ CFG="$1"; REPS="$2"; shift 2
 mkdir -p gpurun_out
 for r in $(seq 1 $REPS); do
   for e in "$@"; do
-    env $e python3 bench.py --config $CFG --steps 30 --warmup 5 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > gpurun_out/envab.json
-    python3 -c "
-import json; d=json.loads(open('gpurun_out/envab.json').read()); print('%-40s step %.4f ms  streaming %.4f ms  set0 %.4f' % ('$e', d['ms_per_step'], d['roofline_streaming']['ms'], d['set0']['ms_per_step']))"
+    env $e python3 bench.py --full --config $CFG --steps 30 --warmup 5 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python3 -c "
+import json, sys; d=json.loads(sys.stdin.read()); print('%-40s step %.4f ms  streaming %.4f ms  set0 %.4f' % ('$e', d['ms_per_step'], d['roofline_streaming']['ms'], d['set0']['ms_per_step']))"
   done
 done

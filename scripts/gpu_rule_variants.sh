@@ -8,9 +8,8 @@ CFG="$1"; REPS="${2:-2}"
 mkdir -p gpurun_out
 run() {   # label, rule, env assignments...
   local label="$1" rule="$2"; shift 2
-  env "$@" python3 bench.py --config $CFG --rule $rule --steps 40 --warmup 5 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > gpurun_out/variant.json
-  python3 -c "
-import json; d=json.loads(open('gpurun_out/variant.json').read()); print('%-34s step %.4f ms  streaming %.4f ms' % ('$label', d['ms_per_step'], d['roofline_streaming']['ms']))"
+  env "$@" python3 bench.py --full --config $CFG --rule $rule --steps 40 --warmup 5 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python3 -c "
+import json, sys; d=json.loads(sys.stdin.read()); print('%-34s step %.4f ms  streaming %.4f ms' % ('$label', d['ms_per_step'], d['roofline_streaming']['ms']))"
 }
 for r in $(seq 1 $REPS); do
   run "press" press A=1

@@ -14,6 +14,6 @@ for v in off on; do
       python3 "$ROOT/scripts/wx_time.py" $SHAPE 5) > "$OUT/$name.log" 2>&1
   echo "== $VAR $v: $(grep ranking $OUT/$name.log)"
   python3 scripts/kstats.py $(find "$OUT/prof_$name" -name "*kernel_stats.csv" | head -1) k_wx_sweep k_wx_bounds k_wx_totals
-  python3 bench.py --config $CFG --steps 30 --warmup 5 --no-cpu-baseline --no-extra > "$OUT/$name.bench.json" 2> "$OUT/$name.bench.err" &&
+  python3 bench.py --full --config $CFG --steps 30 --warmup 5 --no-cpu-baseline --no-extra > "$OUT/$name.bench.json" 2> "$OUT/$name.bench.err" &&
     python3 -c "import json,sys; d=json.loads(open('$OUT/$name.bench.json').read().strip().splitlines()[-1]); print('bench', d['ms_per_step'], d['roofline']['frac'])"
 done

@@ -63,6 +63,9 @@ def test_argument_errors_exit_non_zero_without_a_json_line():
     # a launcher that started a different number of ranks than --gpus says
     p = _run(["--gpus", "2"], {"WORLD_SIZE": "3", "RANK": "0"})
     assert p.returncode == 2 and not _json_lines(p.stdout) and "WORLD_SIZE" in p.stderr
+    # no timed step: nothing to divide the time by
+    p = _run(["--steps", "0"])
+    assert p.returncode == 2 and not _json_lines(p.stdout) and "--steps" in p.stderr
 
 
 def test_bare_multi_gpu_launch_starts_its_ranks_and_fails_loudly_without_a_gpu():
@@ -84,7 +87,7 @@ def test_bare_two_rank_launch_on_one_gpu():
     """`python bench.py --gpus 2` with no launcher around it: bench.py starts torch.distributed.run itself (a child process, before
     any GPU call), both ranks share cuda:0 and the C++ sharded driver's collectives go through gloo callbacks; ONE JSON line with
     n_gpus == 2 comes back through the parent, exit status 0"""
-    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "2", "--no-extra", "--no-cpu-baseline"],
+    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "2", "--full", "--no-extra", "--no-cpu-baseline"],
              {"ABC_BENCH_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = _json_lines(p.stdout)
@@ -102,7 +105,7 @@ def test_single_process_route_on_one_gpu():
     """--single-process: abc_ctx_create_multi (ncclCommInitAll) + one host thread per GPU driving abc_generation_sharded_dev on
     its device-resident shard -- with the one GPU of this box: one thread on the one context of abc_ctx_create_multi (which
     joins contexts by RCCL only when there are several), the sharded driver's protocol at world size 1"""
-    p = _run(["--gpus", "1", "--single-process", "--steps", "2", "--warmup", "1", "--config", "2", "--no-extra", "--no-cpu-baseline"])
+    p = _run(["--gpus", "1", "--single-process", "--steps", "2", "--warmup", "1", "--config", "2", "--full", "--no-extra", "--no-cpu-baseline"])
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = _json_lines(p.stdout)
     assert len(lines) == 1
@@ -117,7 +120,7 @@ def test_n1_line_carries_both_component_rules_and_a_scaling_prediction():
     """the default N = 1 run at the small configuration: the timed region runs the drop-in's default rule (Wilcoxon), `extra` times
     the other one (argmin PRESS: whole generation and ranking alone), `scaling_model` predicts 2 / 4 / 8 GPUs from the measured
     stages and the world-1 RCCL collective latency, with the rule's all-reduces counted"""
-    p = _run(["--config", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sustained-s", "0.2"])
+    p = _run(["--config", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--sustained-s", "0.2"])
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     j = _json_lines(p.stdout)[0]
     ex = j["extra"]
@@ -132,3 +135,36 @@ def test_n1_line_carries_both_component_rules_and_a_scaling_prediction():
     f = sm["from"]
     t8 = f["pair_sums_ms"] / 8 + f["row_sharded_streaming_ms"] / 8 + f["replicated_ms"] + f["collectives_per_step"] * f["collective_price_ms"]
     assert abs(sm["predicted"]["8"]["ms_per_step"] - t8) < 2e-3 and sm["predicted"]["8"]["ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline of the timed steps only; --dump-outputs writes the last timed step's outputs
+    (float64, 64 MB at most), and a second run with the same arguments computes the same outputs from the same inputs"""
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = _run(["--config", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+        lines = _json_lines(p.stdout)
+        assert len(lines) == 1
+        j = lines[0]
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["higher_is_better"] is True and j["unit"] == "particles/s"
+        assert abs(j["value"] - j["config"]["particles_total"] / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+        assert j["dtype"].startswith("f64")
+        for k in ("roofline", "roofline_hbm", "roofline_streaming", "set0", "sustained", "extra", "scaling_model", "cpu_baseline",
+                  "stage_ms_per_step"):
+            assert j[k] is None, k
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in ("idx", "dist", "theta", "w", "dv", "L", "next", "parent", "seeds", "ncomp"))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        a = {f[:-4]: np.load(d / f) for f in files}
+        assert all(v.dtype == np.float64 for v in a.values())
+        c = j["config"]
+        assert a["ncomp"][0] == c["ncomp_chosen"] and a["theta"].shape == (c["params"], c["pred_prior_size"])
+        assert a["next"].shape[0] == c["params"] and np.isfinite(a["next"]).all()
+        assert (a["idx"] >= 0).all() and (a["idx"] < c["particles_total"]).all() and (a["idx"] == np.round(a["idx"])).all()
+        outs.append(a)
+    for k in outs[0]:
+        assert np.array_equal(outs[0][k], outs[1][k]), k
