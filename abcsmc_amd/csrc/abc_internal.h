@@ -20,6 +20,38 @@ inline const char* abc_diag_env(const char* name) {
     return on ? getenv(name) : nullptr;
 }
 
+// The context's pinned, device-visible status block (ctx->status_pin).  A generation's status words go here: into pinned memory
+// the small copies at its end are queued back to back behind ONE synchronisation; into pageable memory each one is a blocking
+// round trip (17 + 50 us of gaps at the end of a generation, rocprofv3 timeline).  Kernels receive the members' addresses.
+struct abc_wx_words {              // the Wilcoxon cascade's words (wilcoxon.hip); the kernels index them as pin_words[0..7]
+    int left;                      // [0] tests left after a level: k_wx_bounds' last work-group, the host spins on it (preset to -1)
+    int vmax_lo, vmax_hi;          // [1] [2] k_wx_bounds: the largest validation-row count of a rank, 31 bits each
+    int ncomp;                     // [3] k_wx_bounds / k_wx_decide: the final component count
+    int changed;                   // [4] ... and whether it differs from the fit's
+    int decided;                   // [5] k_wx_bounds: the cascade needs no further level
+    int n_rest;                    // [6] k_wx_bounds of the first half: the tests outside it
+    int n_level;                   // [7] k_wx_bounds: the tests of this level's list
+};
+struct abc_status_block {
+    double model_hdr[4];           // the model header (component count first): k_post_tail or k_status_words
+    int spd;                       // Cholesky status
+    int sel_fail;                  // the bin selection gave up (k_status_words, or the host from gather_sel_fail)
+    int gather_sel_fail;           // ... as the gather behind the selection stores it
+    int alias_fail;                // the device build of the resampling table did not verify (alias_dev.hip)
+    unsigned long long giveups;    // the proposals' give-up counter, read back at a generation's end
+    unsigned giveup_flag;          // raised by a proposal kernel that gives up (note_giveup, resample.hip)
+    int spare;
+    abc_wx_words wx;
+    int repeat_sel_fail;           // the repeated selection's give-up flag (the first gather may still be writing gather_sel_fail)
+};
+static_assert(offsetof(abc_status_block, model_hdr) == 0 && offsetof(abc_status_block, spd) == 32 &&
+              offsetof(abc_status_block, sel_fail) == 36 && offsetof(abc_status_block, gather_sel_fail) == 40 &&
+              offsetof(abc_status_block, alias_fail) == 44 && offsetof(abc_status_block, giveups) == 48 &&
+              offsetof(abc_status_block, giveup_flag) == 56 && offsetof(abc_status_block, wx) == 64 &&
+              offsetof(abc_status_block, repeat_sel_fail) == 96, "status block layout");
+static_assert(sizeof(abc_wx_words) == 8 * sizeof(int) && offsetof(abc_wx_words, n_level) == 7 * sizeof(int), "cascade words");
+static_assert(sizeof(abc_status_block) <= 128, "status block size");
+
 // timed stages (abc_timing_names in api.hip must match)
 enum { ST_GRAM = 0, ST_STATS_REDUCE, ST_PLS_MODEL, ST_PROJECT, ST_SELECT, ST_SORT, ST_GATHER_DV, ST_KDE,
        ST_WEIGHTS_MISC, ST_MVN, ST_ALIAS_HOST, ST_RESAMPLE, ST_PERTURB, ST_COMM, ABC_NSTAGE };
@@ -36,11 +68,7 @@ struct abc_ctx {
     // pinned host scratch
     char* pin;
     size_t pin_bytes;
-    // 128 pinned bytes.  [0, 64): the status words a generation reads back at its end (component count, Cholesky status, selection
-    // flag): into pinned memory the three small copies are queued back to back behind ONE synchronisation; into pageable
-    // memory each one is a blocking round trip (17 + 50 us of gaps at the end of a generation, rocprofv3 timeline).
-    // [64, 128): the words of the Wilcoxon cascade (tests left after a level, the largest validation-row count of a rank: wilcoxon.hip)
-    char* status_pin;
+    abc_status_block* status_pin;      // pinned (above)
     // cached alias table (device) for the last weights vector handed to abc_resample_dev
     double* alias_F;
     uint32_t* alias_A;
@@ -83,7 +111,6 @@ struct abc_ctx {
     bool sel_bins_ran;       // the last launch_select_smallest took the bin path and has not been checked yet
     bool sel_force_radix;    // set by a caller that repeats its work after a failed bin selection
     unsigned long long wx_moved_counts, generation_repeats;      // abc_generation_repeats
-    bool wx_force_inline;    // set by a generation that repeats itself after its speculation on the component count failed: the Wilcoxon reduction in stream order
     bool wx_gather_rows;     // diagnostic (ABC_DIAG=1 ABC_WX_GATHER=1, set at context creation): the sharded generation's Wilcoxon rule by
                              // gathering the validation rows on every rank (rounds 1-4) instead of the sharded cascade
     bool in_mvn;   // the covariance pass reuses k_gram: keep it out of the k_gram stage timer
@@ -361,7 +388,7 @@ int launch_resample(abc_ctx*, const abc_rng* rng, const double* w, size_t K, uin
                     bool uniform_weights = false, const uint32_t* raw_ready = nullptr, bool weights_on_host = false,
                     const volatile int* abort_flag = nullptr, bool parents_ready = false, int* alias_check_deferred = nullptr);
 // alias_check_deferred (optional): with the table built on the device (ctx->alias_mode) nothing waits for the build's verdict
-// here; *alias_check_deferred = 1 then tells the caller to read the pinned flag (ctx->status_pin + 44) at its next
+// here; *alias_check_deferred = 1 then tells the caller to read the pinned flag (ctx->status_pin->alias_fail) at its next
 // synchronisation and, if it is set, to call launch_resample again with ctx->alias_mode = ABC_ALIAS_HOST.  NULL: this
 // function synchronises and falls back by itself.
 // parents_ready (uniform weights only): abc_rng_streams_early has drawn the parents on the side stream already

@@ -646,10 +646,6 @@ int launch_alias_build_dev_i2(abc_ctx* ctx, const double* w, size_t K, double* F
                               const int** verdict_src);
 int launch_alias_build_dev_i4(abc_ctx* ctx, const double* w, size_t K, double* F, uint32_t* A, int* fail_dev, int* fail_pin,
                               const int** verdict_src);
-static size_t alias_small_k() {             // tables up to this size: two elements per thread
-    static const size_t k = abc_diag_env("ABC_ALIAS_SMALL_K") ? (size_t)atoll(abc_diag_env("ABC_ALIAS_SMALL_K")) : ABC_ALIAS_DEV_SMALL_K;
-    return k;
-}
 size_t abc_alias_dev_need(size_t K) {       // (the larger of the two variants' needs: the smaller work-groups')
     constexpr size_t B = AL_T * 2;
     const size_t nblk = (K + B - 1) / B + 1, nblk2 = (2 * K + B - 1) / B + 1;
@@ -657,7 +653,7 @@ size_t abc_alias_dev_need(size_t K) {       // (the larger of the two variants' 
 }
 int launch_alias_build_dev(abc_ctx* ctx, const double* w, size_t K, double* F, uint32_t* A, int* fail_dev, int* fail_pin,
                            const int** verdict_src) {
-    if (K <= alias_small_k()) return launch_alias_build_dev_i2(ctx, w, K, F, A, fail_dev, fail_pin, verdict_src);
+    if (K <= ABC_ALIAS_DEV_SMALL_K) return launch_alias_build_dev_i2(ctx, w, K, F, A, fail_dev, fail_pin, verdict_src);
     return launch_alias_build_dev_i4(ctx, w, K, F, A, fail_dev, fail_pin, verdict_src);
 }
 #endif

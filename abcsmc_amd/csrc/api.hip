@@ -82,7 +82,7 @@ extern "C" int abc_ctx_create(int device, abc_ctx** out) {
     memset(ctx, 0, sizeof(*ctx));
     ctx->device = device;
     if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return ABC_ERR_HIP; }
-    if (hipHostMalloc((void**)&ctx->status_pin, 128, hipHostMallocDefault) != hipSuccess) { (void)hipStreamDestroy(ctx->own_stream); delete ctx; return ABC_ERR_HIP; }
+    if (hipHostMalloc((void**)&ctx->status_pin, sizeof(abc_status_block), hipHostMallocDefault) != hipSuccess) { (void)hipStreamDestroy(ctx->own_stream); delete ctx; return ABC_ERR_HIP; }
     ctx->stream = ctx->own_stream;
     ctx->wx_gather_rows = abc_diag_env("ABC_WX_GATHER") != nullptr;
     ctx->gram_mode = abc_diag_env("ABC_GRAM_FP64") ? ABC_GRAM_FP64 : (abc_diag_env("ABC_GRAM_I8") ? ABC_GRAM_I8 : ABC_GRAM_AUTO);      // (the diagnostic switch of round 4: the initial mode)
@@ -539,8 +539,7 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     // previous set's prologue alone is 0.74 ms there at configs[3] (0.2 ms on an idle chip): 2.34 ms for the statistics pass against
     // 1.6 stand-alone.  Forked behind it the side stream's work runs beside the model fit and the projection instead: everything
     // but the pair sums 6.80 -> 6.57 ms at configs[3], 1.408 -> 1.387 at configs[4].
-    static const int fork_late_env = abc_diag_env("ABC_FORK_LATE") ? 1 : (abc_diag_env("ABC_FORK_EARLY") ? -1 : 0);     // A/B switches
-    const int fork_late = fork_late_env > 0 || (fork_late_env == 0 && !simple && abc_gram_takes_i8(ctx, io->X, Yp, N, N, N, M, Pstat, ntrain, N));
+    const bool fork_late = !simple && abc_gram_takes_i8(ctx, io->X, Yp, N, N, N, M, Pstat, ntrain, N);
     ctx->side_forked = false;
     if (!fork_late) ABC_TRY(abc_side_fork(ctx));
     ABC_TRY(launch_stats_shift(ctx, io->X, Yp, N, N, N, M, Pstat, stats));
@@ -548,8 +547,7 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     if (fork_late) ABC_TRY(abc_side_fork(ctx));
     // (the cascade's stream is forked behind the fit: where the generation will speculate -- the condition is restated below --
     // the fork's event rides on the fit kernel's completion signal)
-    static const int wx_inline = abc_diag_env("ABC_WX_INLINE") ? 1 : 0;                  // A/B switch for measurements
-    const bool wx_spec = !simple && cfg->rule == ABC_RULE_WILCOXON && io->w && K && !wx_inline && !ctx->wx_force_inline &&
+    const bool wx_spec = !simple && cfg->rule == ABC_RULE_WILCOXON && io->w && K &&
                          abc_wx_cascade_applies(N > (size_t)ntrain ? N - (size_t)ntrain : 0, P, A);
     if (wx_spec && !ctx->wx_stream) {
         // (stream priorities were tried for it, highest and lowest: no effect on any config beyond the runs' spread)
@@ -574,10 +572,8 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     // need it ~0.3 ms into the generation), THEN the seeds (an output nobody reads before the call returns): the moments' event,
     // which the main stream waits for in front of the resampling table, is recorded behind all of them on the same stream
     const bool weighted = io->w && K && Kp && io->theta_prev;
-    static const int moments_main = abc_diag_env("ABC_MOMENTS_MAIN") ? 1 : 0;             // A/B switches for measurements
-    const bool moments_side_possible = Nn && P <= 64 && K >= 2 && !uniform_w && !moments_main && ctx->side;
-    static const int seeds_first = abc_diag_env("ABC_SEEDS_FIRST") ? 1 : 0;              // A/B switch for measurements
-    const bool seeds_late = early && weighted && !seeds_first && moments_side_possible;
+    const bool moments_side_possible = Nn && P <= 64 && K >= 2 && !uniform_w && ctx->side;
+    const bool seeds_late = early && weighted && moments_side_possible;
     if (early) ABC_TRY(abc_rng_streams_early(ctx, rng, 0, Nn, seeds_late ? nullptr : io->seeds, Nn, &raw_early, parent_early, K));
     abc_wprev wprev;
     memset(&wprev, 0, sizeof(wprev));
@@ -601,14 +597,11 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     // the per-response counts are committed, the generation goes on) or the decision is committed and the three stages run again.
     // Whole generations on sets the cascade takes only (ranking-only calls and small sets: in stream order, as before).
     const bool wx_rule = !simple && cfg->rule == ABC_RULE_WILCOXON;
-    const size_t nvalid = N > (size_t)ntrain ? N - (size_t)ntrain : 0;
     // ROUND 6: the host LOOKS at the reduction in front of the weight stage again (round 5's first form), because the look has become
     // cheap: the cascade takes the LARGEST COUNT FIRST (wilcoxon.hip, k_wx_plan) -- level 0 over the tests of two to four responses
     // that hold it instead of all P (A - 1) --, so its verdict is there before the selection and the gather beside it have ended, and
     // a moved count costs the cascade's second half and the three ranking stages once more instead of the whole generation
-    // (round 5's default queued everything up to the proposals on the fit's count first and repeated the generation: ABC_WX_DEFER,
-    // kept for A/B runs).
-    static const int wx_defer_env = abc_diag_env("ABC_WX_DEFER") ? 1 : 0;
+    // (round 5's default queued everything up to the proposals on the fit's count first and repeated the generation).
     double* wx_dec = nullptr;
     abc_wx_run* wx_run = nullptr;
     struct WxGuard {          // an error return between the cascade's halves: its kernels still write into this call's arena
@@ -629,10 +622,9 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         hipStream_t main_stream = ctx->stream;
         // (round 6: the pass leaves the scores of EVERY row, not only the validation half -- N x A doubles of this call's arena: should
         // the reduction lower the largest count, the distances are taken again from them, N x count x 8 bytes instead of X once more)
-        static const int scores_valid_only = abc_diag_env("ABC_SCORES_VALID_ONLY") ? 1 : 0;      // A/B switch: round 5's half
         struct ScoresArg { abc_ctx* ctx; hipStream_t main; const double* X; size_t N, M, P, A, ntrain; const double* model; double* dist; double* S_all; }
             sarg = {ctx, main_stream, io->X, N, M, P, A, (size_t)ntrain, model, dist, nullptr};
-        if (!scores_valid_only && !(N & 1)) sarg.S_all = (double*)abc_ws_alloc(ctx, N * A * 8);
+        if (!(N & 1)) sarg.S_all = (double*)abc_ws_alloc(ctx, N * A * 8);
         abc_wx_scores_hook hook = {
             [](void* a, double** S, size_t* sld) -> int {
                 ScoresArg* q = (ScoresArg*)a;
@@ -686,61 +678,38 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     double* theta = io->theta ? io->theta : (double*)abc_ws_alloc(ctx, K * P * 8);
     if (!theta) ABC_FAIL(ctx, ABC_ERR_NOMEM, "generation: workspace exhausted");
     // (the gather is the first kernel behind the selection: it also stores the selection's give-up flag into the pinned block)
-    int* pfail_early = (int*)(ctx->status_pin + 40);
+    int* pfail_early = &ctx->status_pin->gather_sel_fail;
     *pfail_early = 0;
-    volatile unsigned* pgaveup = (volatile unsigned*)(ctx->status_pin + 56);       // raised by a proposal kernel that gives up (note_giveup)
+    volatile unsigned* pgaveup = &ctx->status_pin->giveup_flag;       // raised by a proposal kernel that gives up (note_giveup)
     *pgaveup = 0u;
     // the status words the host reads at the generation's end (model header, Cholesky status): zeroed here, written by the
     // posterior's k_post_tail where that kernel runs -- the copy kernel behind the proposals is then not launched
-    double* const hdr_pin = (double*)ctx->status_pin;
-    int* const spd_pin = (int*)(ctx->status_pin + 32);
+    double* const hdr_pin = ctx->status_pin->model_hdr;
+    int* const spd_pin = &ctx->status_pin->spd;
     hdr_pin[0] = 0.0; *spd_pin = 0;
     bool status_early = false;
-    static const int status_late = abc_diag_env("ABC_STATUS_KERNEL") ? 1 : 0;           // A/B switch for measurements
     bool bins_deferred = ctx->sel_bins_ran && ctx->sel_fail_dev && !ctx->sel_force_radix;
     // The main stream needs what the side stream queued early (the previous set's tiles, the taus2 outputs) only behind the
     // gather, and those kernels ended long ago: the wait goes IN FRONT of the gather, where the event is certain to have fired
     // (a wait that still has to be resolved between the gather and the new set's tiles cost ~12 us of the critical path there)
-    static const int wait_late = abc_diag_env("ABC_WAIT_LATE") ? 1 : 0;
     ctx->side_early_waited = false;
-    if (wprev.ready && !wait_late) {
+    if (wprev.ready) {
         ABC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_prev, 0));
         ctx->side_early_waited = true;                 // (ev_prev was recorded behind ev_side on the same stream)
     }
     // (weighted generations hand the gathered rows to the side stream, for the posterior's moments: the event that orders the two
     // is the gather's own completion signal, not a record behind it)
-    static const int side_moments_on = abc_diag_env("ABC_MOMENTS_MAIN") ? 0 : 1;        // A/B switches for measurements
-    static const int ev_marker = abc_diag_env("ABC_EV_MARKER") ? 1 : 0;
     const bool defer_moments = Nn && P <= 64 && K >= 2;
-    const bool moments_side_planned = defer_moments && !uniform_w && side_moments_on && ctx->side && ctx->noise_mode != ABC_NOISE_REFERENCE_STREAM;
+    const bool moments_side_planned = defer_moments && !uniform_w && ctx->side && ctx->noise_mode != ABC_NOISE_REFERENCE_STREAM;
     if (moments_side_planned && !ctx->ev_theta) {
         ABC_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_theta, abc_xstream_event_flags()));
         ABC_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_moments, abc_xstream_event_flags()));
     }
-    const bool theta_ev_bound = moments_side_planned && !ev_marker;
+    const bool theta_ev_bound = moments_side_planned;
     ABC_TRY(launch_gather_rows(ctx, io->Y, N, N, P, io->idx, K, 0, theta, K, bins_deferred ? ctx->sel_fail_dev : nullptr, pfail_early,
                                theta_ev_bound ? ctx->ev_theta : nullptr));
     if (wx_run) {                                        // level 0 of the cascade, behind the ranking's launches in host order
         hipStream_t main_stream = ctx->stream;
-        // ... and, where its sweep is short enough to fit beside the resampling table and the proposals at the generation's end, behind
-        // the gather ON THE DEVICE too: a level sweep fills every CU with a 1024-thread work-group, the selection's kernels beside it
-        // waited for CUs (configs[3]: the 80 MB histogram pass took 1.4 ms beside a 1.4 ms sweep), and once the pair sums run the
-        // sweep gets no CU until they end -- so a held-back sweep runs behind the pair sums.  Estimates: ~1e9 keys per ms at up to
-        // 8 components (0.8e9 to 16, 0.5e9 to 32); the proposals ~16 P bytes per row at 4 TB/s behind ~0.15 ms of table build.
-        // configs[3]: 359.9 -> 358.8 ms (everything but the pair sums 8.4 -> 7.1 ms), configs[2]: the same within the runs' spread,
-        // configs[4] (a 0.5 ms sweep against 0.2 ms of proposals: not held back; forced, 3.71 -> 3.90 ms)
-        static const int l0_force = abc_diag_env("ABC_WX_L0_AFTER_GATHER") ? atoi(abc_diag_env("ABC_WX_L0_AFTER_GATHER")) : -1;   // A/B switch: 0 / 1
-        const double sweep_ms = (double)nvalid * (double)(P * (A - 1)) / (A <= 8 ? 1.0e9 : (A <= 16 ? 0.8e9 : 0.5e9));
-        const double tail_ms = 0.15 + (double)Nn * (double)P * 16.0 / 4.0e9;
-        // ... and only where there are pair sums to speak of (~4.8e9 pairs per ms): the cascade is a chain of short dependent steps
-        // (sweep, totals, bounds, the host's look), and started behind the gather it outlasts a generation whose weight stage is
-        // over in 0.04 ms (configs[1], K = K' = 1e4: 0.336 -> 0.361 ms held)
-        const double pairs_ms = (double)K * (double)Kp / 4.8e9;
-        const bool l0_after = (l0_force >= 0 ? l0_force != 0 : (sweep_ms <= tail_ms && pairs_ms >= 0.25)) && wx_defer_env;
-        if (l0_after && wx_spec && weighted) {
-            if (!theta_ev_bound) ABC_HIP(ctx, hipEventRecord(ctx->ev_wx_scores, ctx->stream));
-            ABC_HIP(ctx, hipStreamWaitEvent(ctx->wx_stream, theta_ev_bound ? ctx->ev_theta : ctx->ev_wx_scores, 0));
-        }
         ctx->stream = ctx->wx_stream;
         const int rc0 = launch_wilcoxon_level0(ctx, wx_run);
         ctx->stream = main_stream;
@@ -749,11 +718,9 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     // Where the host looks at the cascade: HERE, in front of the weight stage (round 6; round 5's first form).  The verdict of the
     // cascade's first half -- the tests of a few responses that hold the largest count -- is there by the time the gather ends; a count
     // that stands costs nothing, a count that moved costs the cascade's second half and the ranking once more (distances from the
-    // kept scores, selection, gather).  ABC_WX_DEFER: round 5's default -- the weight stage and the proposals queued first on the
-    // fit's count, the looks beside the pair sums, a moved count throwing the generation away (kept for A/B runs).
-    const bool wx_defer = wx_spec && wx_defer_env;
+    // kept scores, selection, gather).
     bool wx_tail_pending = false;
-    if (wx_spec && !wx_defer) {
+    if (wx_spec) {
         // the reduction itself, on its own stream, while the ranking queued above runs (the host's looks at the cascade's level
         // counts happen here, beside GPU work that does not depend on them)
         hipStream_t main_stream = ctx->stream;
@@ -786,7 +753,7 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
             ctx->wx_moved_counts++;
             // (the second selection's give-up flag goes to a word of its own in the pinned block: the first gather may still be
             // running -- resetting ITS word would need a wait for the stream here, ~15 us of idle GPU in front of the repeat)
-            pfail_early = (int*)(ctx->status_pin + 96);
+            pfail_early = &ctx->status_pin->repeat_sel_fail;
             *pfail_early = 0;
             if (scores_all) ABC_TRY(launch_distance_from_scores(ctx, scores_all, N, N, M, P, A, model, dist));
             else ABC_TRY(launch_project_distance(ctx, io->X, N, N, M, P, A, model, 0, dist));
@@ -800,7 +767,7 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     // the radix select.  Weighted generations learn of it at the host's wait for the weights (launch_resample's abort flag),
     // before the alias table, the draws and the proposals of the placeholder are queued; set 0 has no host wait before its
     // end and finds out there.  Either way the proposals' give-up counter is put back to its snapshot.
-    auto repeat_generation = [&](bool radix, bool wx_in_order) -> int {
+    auto repeat_with_radix = [&]() -> int {
         ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->side) ABC_HIP(ctx, hipStreamSynchronize(ctx->side));
         if (ctx->wx_stream) ABC_HIP(ctx, hipStreamSynchronize(ctx->wx_stream));
@@ -810,15 +777,12 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         ctx->ws_off = ws_entry;
         if (rng) *rng = rng_entry;
         ctx->generation_repeats++;
-        const bool radix0 = ctx->sel_force_radix, inline0 = ctx->wx_force_inline;      // (a repeat inside a repeat keeps the outer one's reason)
-        ctx->sel_force_radix = radix0 || radix;
-        ctx->wx_force_inline = inline0 || wx_in_order;
+        const bool radix0 = ctx->sel_force_radix;      // (a repeat inside a repeat keeps the outer one's reason)
+        ctx->sel_force_radix = true;
         const int rc = generation_core(ctx, cfg, io, rng, ncomp_host, simple, model_out);
         ctx->sel_force_radix = radix0;
-        ctx->wx_force_inline = inline0;
         return rc;
     };
-    auto repeat_with_radix = [&]() -> int { return repeat_generation(true, false); };
     double* dv = io->dv ? io->dv : (double*)abc_ws_alloc(ctx, P * 8);
     double* theta_stats = nullptr;        // moments of the posterior: shared by dv and the MVN factor
     // Weighted generations with proposals: the kernel density of the weights uses the PREVIOUS set's variance, so the new set's
@@ -870,7 +834,8 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         }
         const int PPr = abc_perturb_pp(P);
         side_out.dv = dv; side_out.L = L_early; side_out.spd = spd_dev;
-        if (!status_late) { side_out.model_hdr = simple ? nullptr : model; side_out.hdr_pin = hdr_pin; side_out.spd_pin = L_early ? spd_pin : nullptr; status_early = true; }
+        side_out.model_hdr = simple ? nullptr : model; side_out.hdr_pin = hdr_pin; side_out.spd_pin = L_early ? spd_pin : nullptr;
+        status_early = true;
         side_out.rows = (double*)abc_ws_alloc(ctx, K * (size_t)PPr * sizeof(double));
         if (L_early) side_out.Lpad = (double*)abc_ws_alloc(ctx, (size_t)PPr * PPr * sizeof(double));
         if (!side_out.rows || (L_early && !side_out.Lpad)) ABC_FAIL(ctx, ABC_ERR_NOMEM, "generation: workspace exhausted");
@@ -914,7 +879,7 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         const bool hook_moments = defer_moments && !moments_on_side;
         PrepArg pa = {ctx, rng, theta, theta_stats, K, P, Nn, io->seeds, &prep, moments_on_side ? nullptr : L, spd_dev, dv,
                       hook_moments, nullptr, nullptr, nullptr};
-        if (hook_moments && !status_late) {
+        if (hook_moments) {
             pa.model_hdr = simple ? nullptr : model; pa.hdr_pin = hdr_pin; pa.spd_pin = L ? spd_pin : nullptr;
             status_early = true;
         }
@@ -970,42 +935,17 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
             taus2_jump(rng, 2 * (uint64_t)Nn);   // Nnext resampling draws + Nnext seeds
         }
     }
-    if (wx_defer) {
-        // the cascade's second half (see above): EVERYTHING of this generation is queued by now, the pair sums run.  (Queued in
-        // front of the resampling stage, first version, the host's waits for the cascade's levels -- whose kernels get hardly any
-        // CU while the pair sums' work-groups hold them all -- kept the resampling table from being queued in time: 0.34 ms of
-        // idle main stream behind the weights at configs[4], rocprofv3 timeline)
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->wx_stream;
-        int changed = 2;
-        int rc = launch_wilcoxon_finish(ctx, wx_run, &changed);
-        wx_run = nullptr;
-        if (rc == ABC_OK && hipEventRecord(ctx->ev_wx_done, ctx->wx_stream) != hipSuccess) rc = ABC_ERR_HIP;
-        ctx->stream = main_stream;
-        // the largest count moved (or a bin of the exact step outgrew LDS: massive ties): what was queued ranked on the wrong count
-        if (rc == ABC_INTERNAL_RETRY || (rc == ABC_OK && changed)) return repeat_generation(false, true);
-        if (rc != ABC_OK) { if (!ctx->err[0]) snprintf(ctx->err, sizeof(ctx->err), "generation: the component rule's reduction failed"); return rc; }
-        // the per-response counts into the model record, on the cascade's own stream: nothing this generation still queues reads
-        // them (the largest count, which everything used, is the fit's), and on the main stream the launch sat between the
-        // normalised weights and the resampling table -- 16 us of the critical path (rocprofv3 timeline).  The host waits for that
-        // stream at the generation's end.
-        ctx->stream = ctx->wx_stream;
-        rc = launch_wilcoxon_commit(ctx, model, M, P, A, wx_dec, 0);
-        ctx->stream = main_stream;
-        ABC_TRY(rc);
-        wx_tail_pending = true;
-    }
     {
-        // status words into the pinned block: [0..31] model header (component count), [32] Cholesky status, [36] selection flag
-        double* hdr = (double*)ctx->status_pin;
-        int* pspd = (int*)(ctx->status_pin + 32);
-        int* pfail = (int*)(ctx->status_pin + 36);
+        // status words into the pinned block: model header (component count), Cholesky status, selection flag
+        double* hdr = ctx->status_pin->model_hdr;
+        int* pspd = &ctx->status_pin->spd;
+        int* pfail = &ctx->status_pin->sel_fail;
         if (!status_early) { hdr[0] = 0.0; *pspd = 0; }
         *pfail = 0;
         if (seeds_late && !seeds_waited) ABC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));     // (never in practice: see below)
         // ONE tiny kernel stores the three words into the (device-visible) pinned block: three copies were three blit launches
         const int* fail_dev = (ctx->sel_bins_ran && ctx->sel_fail_dev) ? (const int*)ctx->sel_fail_dev : nullptr;
-        unsigned long long* pgive = (unsigned long long*)(ctx->status_pin + 48);
+        unsigned long long* pgive = &ctx->status_pin->giveups;
         *pgive = 0;
         if (!status_early) {
             hipLaunchKernelGGL(k_status_words, dim3(1), dim3(64), 0, ctx->stream, simple ? (const double*)nullptr : (const double*)model,
@@ -1031,7 +971,7 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         if (failed && !ctx->sel_force_radix) return repeat_with_radix();
         // the device build of the resampling table did not verify: the draws and the proposals once more, with the table from the
         // host (the weights are final; only what depends on the table is repeated)
-        if (alias_deferred && *(volatile int*)(ctx->status_pin + 44) && parent_used) {
+        if (alias_deferred && *(volatile int*)&ctx->status_pin->alias_fail && parent_used) {
             ctx->alias_dev_fallbacks++;
             const int mode = ctx->alias_mode;
             ctx->alias_mode = ABC_ALIAS_HOST;
@@ -1059,9 +999,9 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
                 ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 ctx->giveups_dev_known = now;
             }
-            *(volatile unsigned long long*)(ctx->status_pin + 48) = ctx->giveups_dev_known;
+            *(volatile unsigned long long*)&ctx->status_pin->giveups = ctx->giveups_dev_known;
         }
-        const unsigned long long gv = *(volatile unsigned long long*)(ctx->status_pin + 48) + ctx->giveups_host;
+        const unsigned long long gv = *(volatile unsigned long long*)&ctx->status_pin->giveups + ctx->giveups_host;
         const unsigned long long before = ctx->giveups_seen;
         ctx->giveups_seen = gv;
         // (status stays ABC_OK: a C caller's `if (rc)` must not read a finished generation as a failure; abc_generation_giveups)

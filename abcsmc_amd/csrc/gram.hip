@@ -11,8 +11,6 @@
 // 16x16 blocks (fp64 in, fp64 accumulate).  HBM-bound: 8*(M+P) bytes per particle, read once.
 #include <stdlib.h>
 
-#include <vector>
-
 #include "abc_internal.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -428,7 +426,7 @@ __global__ __launch_bounds__((GramDimsDma<C, CY, NW>::NT)) void k_gram_dma(
 // neighbouring wave of the same work-group at the same time: the loads are therefore NOT non-temporal, see run_gram_dma8); in LDS that is element (column c, row r) of block i at
 // 128 i + 2 c + 32 (r >> 1) + (r & 1), so the operand read of k-step s (lane (cl, q) -> row 4 s + q) covers 64 consecutive
 // doubles: conflict-free without a swizzle.  Everything else (shift at operand read, masks, column sums, epilogue) as above.
-template <int C, int CY, bool NTL = true>
+template <int C, int CY>
 __global__ __launch_bounds__(512) void k_gram_dma8(const double* __restrict__ X, const double* __restrict__ Y, size_t ldx, size_t ldy,
                                                   int M, int P, long long n, long long split, const double* __restrict__ shift,
                                                   double* __restrict__ partial) {
@@ -453,7 +451,7 @@ __global__ __launch_bounds__(512) void k_gram_dma8(const double* __restrict__ X,
         long long r = t0 + tile * TRK + 8 * wave + 2 * (lane >> 4);
         r = r > rmax ? rmax : r;                         // rows past the end are masked later; keep the address legal
 #pragma unroll
-        for (int i = 0; i < C; i++) dma16<NTL>(cptr[i] + r, wring + slot * CH + i * 128);
+        for (int i = 0; i < C; i++) dma16<false>(cptr[i] + r, wring + slot * CH + i * 128);
     };
     const int cl = lane & 15, q = lane >> 4;
     double sh[C], keep[C];
@@ -789,7 +787,7 @@ __global__ __launch_bounds__(1024) void k_pilot_scale(const double* __restrict__
 // rows of a column (the DMA lanes fetch the even row pairs into the first half of a column's 256 bytes and the odd ones into the
 // second, so a thread's two 16-byte reads are 16-byte strided across the lanes: conflict-free), the 4 x 4 byte transpose is eight
 // v_perm_b32, every plane store one ds_write_b32; the sums stay in registers: 360 us -- and the phases taken out one at a time
-// (ABC_GRAM_ABL) said why: the refills alone 222 us (5.2 TB/s, what this access pattern gets), conversion + products WITHOUT
+// said why: the refills alone 222 us (5.2 TB/s, what this access pattern gets), conversion + products WITHOUT
 // refills 290 us, i.e. ~5000 cycles per tile of which the byte products own 1664 (four tile pairs x 13 MFMAs x 32 cycles on the
 // busier SIMDs) and the conversion ~2500 (two waves of ~260 vector instructions per SIMD), one after the other between barriers.
 // Round 5, second: the two run TOGETHER.  Two sets of byte planes; in the step of tile i the four waves 0..3 (one per SIMD) multiply
@@ -803,8 +801,7 @@ __global__ __launch_bounds__(512) void k_gram_i8(const double* __restrict__ X, c
                                                  const int* __restrict__ escale, double* __restrict__ partial,
                                                  unsigned long long* __restrict__ far_mask /* [2][tmax]: far rows of every 32-row tile */,
                                                  unsigned long long* __restrict__ far_sum /* [2][(tmax + 63) / 64]: tiles with any; then one word: any at all */,
-                                                 long long tmax, int nraw /* raw tiles in LDS: 3, or 2 */,
-                                                 int abl /* diagnostic (ABC_GRAM_ABL): 1 no conversion, 2 no products, 4 no refills */) {
+                                                 long long tmax, int nraw /* raw tiles in LDS: 3, or 2 */) {
     using D = GramI8<C, CY>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds8[];
     const int ncols = M + P, ndma = (ncols + 3) / 4, rawb = ndma * 1024;
@@ -1003,7 +1000,7 @@ __global__ __launch_bounds__(512) void k_gram_i8(const double* __restrict__ X, c
     if (nmine > 0) {                                                           // tile 0 -> plane set 0
         wait_in_flight(npre - 1);
         __syncthreads();
-        if (!(abl & 1)) convert(0, 0, 0);
+        convert(0, 0, 0);
     }
     int slot_i = 0, fset_i = 0;                                                // i % nraw, i % 3
     // (two loops: the accumulators are flushed between runs of FLUSH tiles -- the flush stays out of the inner loop's register budget)
@@ -1044,7 +1041,7 @@ __global__ __launch_bounds__(512) void k_gram_i8(const double* __restrict__ X, c
                 // conversion of tile i + 2, next step) have to pass the next one
                 if (lane < 12) reinterpret_cast<unsigned int*>(rowfar0 + ((fset_n == 2) ? 0 : fset_n + 1) * 48)[lane] = 0u;
             }
-            if (i + nraw < nmine && !(abl & 4)) stage(i + nraw, slot_i);
+            if (i + nraw < nmine) stage(i + nraw, slot_i);
             if (any_far) {                                                     // (uniform) rare: zero the far rows' bytes
                 unsigned char* planes = planes0 + (i & 1) * 4 * D::PLANE;
                 for (int e2 = t; e2 < 4 * D::C32 * 32; e2 += D::NT) {
@@ -1054,9 +1051,9 @@ __global__ __launch_bounds__(512) void k_gram_i8(const double* __restrict__ X, c
                 __syncthreads();
             }
             // (3) the byte products of tile i and the conversion of tile i + 1, in opposite orders on the two waves of a SIMD
-            const bool conv = i + 1 < nmine && !(abl & 1);
+            const bool conv = i + 1 < nmine;
             if (conv && wave >= 4) convert(i + 1, slot_n, fset_n);
-            if (!(abl & 2)) products(i & 1);                                   // (one call site: the accumulators stay in their registers)
+            products(i & 1);                                                   // (one call site: the accumulators stay in their registers)
             if (conv && wave < 4) convert(i + 1, slot_n, fset_n);
             slot_i = slot_n; fset_i = fset_n;
         }
@@ -1313,18 +1310,12 @@ int run_gram_dma8(abc_ctx* ctx, const double* X, const double* Y, size_t n, size
     // line, the other half going to the neighbouring wave at about the same time --, and a line fetched with the hint is not kept
     // for the neighbour: FETCH_SIZE showed 13.5 GB for the 7.68 GB of configs[3]'s set (1.76 x), 8.25 GB without the hint, and the
     // kernel 2.25 -> 2.09 ms (it is bound by the fp64 matrix pipe first, so the doubled traffic cost 7 %, not 76 %).  The kernels
-    // whose pieces are whole lines (k_gram_dma: 16 rows, k_gram_i8: 32 rows of a column) keep the hint.  ABC_GRAM_DMA8_NT: A/B.
-    static const bool nont = abc_diag_env("ABC_GRAM_DMA8_NT") == nullptr;
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram_dma8<C, CY, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram_dma8<C, CY, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    // whose pieces are whole lines (k_gram_dma: 16 rows, k_gram_i8: 32 rows of a column) keep the hint.
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram_dma8<C, CY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     {
         StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_GRAM);
-        if (nont)
-            hipLaunchKernelGGL((k_gram_dma8<C, CY, false>), dim3((unsigned)G, 2), dim3(512), lds_bytes, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P,
-                               (long long)n, split, stats + L.off_shift, partial);
-        else
-            hipLaunchKernelGGL((k_gram_dma8<C, CY, true>), dim3((unsigned)G, 2), dim3(512), lds_bytes, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P,
-                               (long long)n, split, stats + L.off_shift, partial);
+        hipLaunchKernelGGL((k_gram_dma8<C, CY>), dim3((unsigned)G, 2), dim3(512), lds_bytes, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P,
+                           (long long)n, split, stats + L.off_shift, partial);
     }
     ABC_HIP(ctx, hipGetLastError());
     StageTimer tm2(ctx, ctx->in_mvn ? -1 : ST_STATS_REDUCE);
@@ -1383,25 +1374,18 @@ int run_gram_i8(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t
     if (!partial || !escale || !far_mask || !far_sum) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted (%zu B)", pbytes);
     const int lds_b = D::lds_bytes((int)(M + P)), nraw = D::raw_tiles((int)(M + P));
     ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram_i8<C, CY>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b));
-    static const int abl = abc_diag_env("ABC_GRAM_ABL") ? atoi(abc_diag_env("ABC_GRAM_ABL")) : 0;      // (phases left out: timings only)
     {
         StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_GRAM);
         hipLaunchKernelGGL(k_pilot_scale, dim3((unsigned)D::C16), dim3(1024), 0, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P, (long long)n,
                            (const double*)(stats + L.off_shift), escale);
         ABC_HIP(ctx, hipMemsetAsync(far_sum, 0, (2 * sumw + 1) * 8, ctx->stream));
         hipLaunchKernelGGL((k_gram_i8<C, CY>), dim3((unsigned)G, 2), dim3(D::NT), (size_t)lds_b, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P,
-                           (long long)n, split, (const double*)(stats + L.off_shift), (const int*)escale, partial, far_mask, far_sum, tmax, nraw, abl);
+                           (long long)n, split, (const double*)(stats + L.off_shift), (const int*)escale, partial, far_mask, far_sum, tmax, nraw);
         hipLaunchKernelGGL((k_gram_far<C, CY>), dim3((unsigned)(D::NBLK + 1), 2), dim3(256), 0, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P,
                            (long long)n, split, (const double*)(stats + L.off_shift), partial, (int)G, (const unsigned long long*)far_mask,
                            (const unsigned long long*)far_sum, tmax);
     }
     ABC_HIP(ctx, hipGetLastError());
-    if (abc_diag_env("ABC_GRAM_DEBUG")) {        // (diagnostic: the columns' fixed-point binades)
-        std::vector<int> he(D::C32);
-        ABC_HIP(ctx, hipMemcpy(he.data(), escale, D::C16 * sizeof(int), hipMemcpyDeviceToHost));
-        for (int c = 0; c < (int)(M + P); c++) fprintf(stderr, "%d%s", he[c], (c + 1) % 32 ? " " : "\n");
-        fprintf(stderr, "\n");
-    }
     StageTimer tm2(ctx, ctx->in_mvn ? -1 : ST_STATS_REDUCE);
     hipLaunchKernelGGL((k_stats_reduce<C, CY>), dim3((D::PSZ + 63) / 64, 2), dim3(64 * SR_SL), 0, ctx->stream, partial, (int)(G + 1),
                        stats, ntr, nte);
@@ -1502,90 +1486,103 @@ int launch_stats_shift(abc_ctx* ctx, const double* X, const double* Y, size_t n,
     return ABC_OK;
 }
 
-// Will launch_stats_accumulate take the byte-limb kernel for this set?  (The same conditions as below, for a caller that arranges its
-// streams around that kernel: one 512-thread work-group per CU with 150-160 KB of LDS -- anything resident beside it costs it CUs.)
-bool abc_gram_takes_i8(const abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
-                       uint64_t n_train_global, size_t n_set) {
-    const size_t C = (M + P + 15) / 16;
-    size_t CY = C - (M + 15) / 16;
-    if (CY > 2) CY = 2;
+// ---- which statistics kernel a set takes ------------------------------------------------------------------------------------------
+// ONE decision, for launch_stats_accumulate and for a caller that arranges its streams around the byte-limb kernel (abc_gram_takes_i8).
+// Up to 48 columns (C <= 3) the VGPR-staged k_gram is the default since its loads carry the non-temporal policy: 75 us against 84 us
+// for the LDS-DMA kernel at N = 1e6, M = 32, P = 16 (0.68 against 0.60 of the HBM peak inside a generation); 49..96 columns run the
+// eight-wave LDS-DMA variant (0.29 against 0.68 ms on the configs[3] shape).  LDS-DMA staging (dma_ok) needs 16-B aligned columns and
+// an even row count (row pairs never straddle the array end).
+// 4..6 column blocks (49..96 columns, e.g. BASELINE configs[3]: 64 metrics + 32 parameters): k_gram_dma8, EIGHT waves of
+// wave-private staging in 8-row chunks (two waves per SIMD keep the fp64 matrix pipe busy: 0.36 -> 0.29 ms on the configs[3]
+// shard against the four-wave, 16-row-chunk variant, which stays for the column-pointer-table mode of the grouped path).
+// (6, 0) needs 172 KB for its epilogue and stays on the VGPR-staged kernel.
+// 81..96 columns of a LARGE set (configs[3]: 64 metrics + 32 parameters, 1e7 rows) go through the byte-limb kernel of the wide
+// sets (k_gram_i8): 1.59 ms against k_gram_dma8's 1.99 at 1e7 rows x 96 columns (0.60 against 0.48 of HBM: the fp64
+// matrix pipe is 0.62 busy there), the same statistics to the byte products' error (section 4).  From 2e6 rows: where it was measured.
+// WHERE THE BYTE-LIMB KERNEL IS THE DEFAULT (round 6).  Its noise -- every value rounded to a 32-bit grid -- is harmless at the
+// Gram's own scale (4e-11 of sqrt(G_aa G_bb)) but not always at the LOADINGS: a component that fits noise works on cross
+// products sqrt(rows) below that scale, with close eigenvalues, and tests/fuzz/wide_model_fuzz.py found a used loading column
+// 4.3e-6 off the oracle's (fp64 kernels: 4e-10) at 66 000 training rows x 29 responses x 30 components -- BASELINE.json allows
+// 1e-6.  The error falls faster than 1 / rows: 64 fuzzed sets whose partitions hold 450 000 rows and more stay within 2.6e-7
+// (profiles/r06_wide_model_fuzz_big.json).  So ABC_GRAM_AUTO takes the kernel only where EVERY non-empty partition of the
+// WHOLE set (training / validation rows: ntr_set, nte_set) has at least 400 000 rows -- configs[4] (5e5 + 5e5), configs[3]
+// (5e6 + 5e6) -- and the fp64 kernels below that; ABC_GRAM_I8 is round 5's rule (200 000 rows in the whole set) for A/B runs and tests.
+// 8..10 column blocks: one launch, the Gram blocks dealt out to the waves of a work-group -- large sets on the byte-limb kernel on the
+// i8 matrix pipe (sums and the diagonal exact, off-diagonal products to ~1e-10 of sqrt(G_aa G_bb)); small ones, and all with
+// ABC_GRAM_FP64 (A/B runs, tests), on the fp64 matrix pipe (k_gram_wide).  (LDS-DMA staging: 16-byte aligned columns, an even row
+// count; from 200000 rows: the values are rounded to a 32-bit grid of 10 .. 19 sigma, noise of 3e-9 sigma per value that averages
+// out with the square root of the rows -- 1e-10 of sqrt(G_aa G_bb) at 35000 rows per partition, which the 32nd loading of a
+// 128-metric model amplifies to 2e-7; 4e-8 at 1e6 rows.)  7 blocks, 97..112 columns: the byte-limb kernel where it applies -- round
+// 5; the fp64 one-launch kernel spills at that width, so small sets of it stay on the grouped path, which reads every column twice.
+// (A rank whose shard the byte-limb kernel cannot take -- an odd row count, columns that are not 16-byte aligned, fewer than 4096
+// rows -- runs the fp64 kernel on ITS rows: the rows' rule is the same on every rank, dma_ok and n are about what can run.)
+// Wider sets, and the shapes without an instantiation ((1, 1), (2, 2): sets without metrics): column groups of 48, one launch per
+// pair of groups (every column is read ceil(columns / 48) - 1 times).
+enum GramKernel { GRAM_VGPR, GRAM_DMA8, GRAM_WIDE, GRAM_I8, GRAM_GROUPED };
+static GramKernel gram_kernel(size_t C, size_t CY, bool dma_ok, size_t n, size_t ntr_set, size_t nte_set, int gram_mode) {
+    const size_t rows_set = ntr_set + nte_set;
+    const size_t part_min = (ntr_set && nte_set) ? (ntr_set < nte_set ? ntr_set : nte_set) : (ntr_set ? ntr_set : nte_set);
+    const bool i8_rows = gram_mode == ABC_GRAM_I8 ? rows_set >= 200000 : (gram_mode == ABC_GRAM_AUTO && part_min >= 400000);
+    const bool i8_ok = i8_rows && dma_ok && n >= 4096;
+    if (C >= 7) return C > 10 ? GRAM_GROUPED : i8_ok ? GRAM_I8 : C == 7 ? GRAM_GROUPED : GRAM_WIDE;
+    if (C == 6 && CY >= 1 && i8_ok && rows_set >= 2000000) return GRAM_I8;
+    if (C >= 4 && dma_ok && !(C == 6 && CY == 0)) return GRAM_DMA8;
+    return (C >= 3 || (C >= 1 && CY < C)) ? GRAM_VGPR : GRAM_GROUPED;
+}
+
+// n_set (0: n): the rows of the whole set these n are a shard of; n_train_global: its training rows
+static GramKernel gram_kernel_for(const abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
+                                  uint64_t n_train_global, size_t n_set, size_t* C, size_t* CY) {
+    *C = (M + P + 15) / 16;
+    *CY = *C - (M + 15) / 16;           // trailing blocks without any metric column
+    if (*CY > 2) *CY = 2;
     const bool dma_ok = (ldx % 2 == 0) && (ldy % 2 == 0) && (n % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)Y & 15) == 0) && n >= 2;
     const size_t rows_set = n_set ? n_set : n;
-    const size_t ntr_set = n_train_global < rows_set ? (size_t)n_train_global : rows_set, nte_set = rows_set - ntr_set;
-    const size_t part_min = (ntr_set && nte_set) ? (ntr_set < nte_set ? ntr_set : nte_set) : (ntr_set ? ntr_set : nte_set);
-    const bool i8_rows = ctx->gram_mode == ABC_GRAM_I8 ? rows_set >= 200000 : (ctx->gram_mode == ABC_GRAM_AUTO && part_min >= 400000);
-    if (!i8_rows || !dma_ok || n < 4096) return false;
-    if (C == 6) return rows_set >= 2000000 && CY >= 1 && !abc_diag_env("ABC_GRAM_DMA8_96");
-    return C >= 7 && C <= 10;
+    const size_t ntr_set = n_train_global < rows_set ? (size_t)n_train_global : rows_set;
+    return gram_kernel(*C, *CY, dma_ok, n, ntr_set, rows_set - ntr_set, ctx->gram_mode);
+}
+
+bool abc_gram_takes_i8(const abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
+                       uint64_t n_train_global, size_t n_set) {
+    size_t C, CY;
+    return gram_kernel_for(ctx, X, Y, n, ldx, ldy, M, P, n_train_global, n_set, &C, &CY) == GRAM_I8;
 }
 
 int launch_stats_accumulate(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy,
                             size_t M, size_t P, uint64_t row0, uint64_t n_train_global, double* stats, size_t n_set) {
     long long split = 0;
     if (n_train_global > row0) split = (long long)((n_train_global - row0) < n ? (n_train_global - row0) : n);
-    const size_t C = (M + P + 15) / 16;
-    size_t CY = C - (M + 15) / 16;      // trailing blocks without any metric column
-    if (CY > 2) CY = 2;
-    // Two kernels.  Up to 48 columns (C <= 3) the VGPR-staged k_gram is the default since its loads carry the non-temporal
-    // policy: 75 us against 84 us for the LDS-DMA kernel at N = 1e6, M = 32, P = 16 (0.68 against 0.60 of the HBM peak inside
-    // a generation); 49..96 columns run the eight-wave LDS-DMA variant (0.29 against 0.68 ms on the configs[3] shape).
-    // LDS-DMA staging needs 16-B aligned columns and an even row count (row pairs never straddle the array end).
-    const bool dma_ok = (ldx % 2 == 0) && (ldy % 2 == 0) && (n % 2 == 0) && (((uintptr_t)X & 15) == 0) &&
-                        (((uintptr_t)Y & 15) == 0) && n >= 2;
-    // 4..6 column blocks (49..96 columns, e.g. BASELINE configs[3]: 64 metrics + 32 parameters): k_gram_dma8, EIGHT waves of
-    // wave-private staging in 8-row chunks (two waves per SIMD keep the fp64 matrix pipe busy: 0.36 -> 0.29 ms on the configs[3]
-    // shard against the four-wave, 16-row-chunk variant, which stays for the column-pointer-table mode of the grouped path).
-    // (6, 0) needs 172 KB for its epilogue and stays on the VGPR-staged kernel.
-    // 81..96 columns of a LARGE set (configs[3]: 64 metrics + 32 parameters, 1e7 rows) go through the byte-limb kernel of the wide
-    // sets (k_gram_i8, below): 1.59 ms against k_gram_dma8's 1.99 at 1e7 rows x 96 columns (0.60 against 0.48 of HBM: the fp64
-    // matrix pipe is 0.62 busy there), the same statistics to the byte products' error (section 4).  From 2e6 rows: where it was measured.
-    static const bool dma8_96 = abc_diag_env("ABC_GRAM_DMA8_96") != nullptr;              // A/B switch: the fp64 kernel as before
-    // WHERE THE BYTE-LIMB KERNEL IS THE DEFAULT (round 6).  Its noise -- every value rounded to a 32-bit grid -- is harmless at the
-    // Gram's own scale (4e-11 of sqrt(G_aa G_bb)) but not always at the LOADINGS: a component that fits noise works on cross
-    // products sqrt(rows) below that scale, with close eigenvalues, and tests/fuzz/wide_model_fuzz.py found a used loading column
-    // 4.3e-6 off the oracle's (fp64 kernels: 4e-10) at 66 000 training rows x 29 responses x 30 components -- BASELINE.json allows
-    // 1e-6.  The error falls faster than 1 / rows: 64 fuzzed sets whose partitions hold 450 000 rows and more stay within 2.6e-7
-    // (profiles/r06_wide_model_fuzz_big.json).  So ABC_GRAM_AUTO takes the kernel only where EVERY non-empty partition of the
-    // WHOLE set (training / validation rows: n_train_global, n_set) has at least 400 000 rows -- configs[4] (5e5 + 5e5), configs[3]
-    // (5e6 + 5e6) -- and the fp64 kernels below that; ABC_GRAM_I8 is round 5's rule (200 000 rows in the whole set) for A/B runs and tests.
-    const size_t rows_set = n_set ? n_set : n;
-    const size_t ntr_set = n_train_global < rows_set ? (size_t)n_train_global : rows_set, nte_set = rows_set - ntr_set;
-    const size_t part_min = (ntr_set && nte_set) ? (ntr_set < nte_set ? ntr_set : nte_set) : (ntr_set ? ntr_set : nte_set);
-    const bool i8_rows = ctx->gram_mode == ABC_GRAM_I8 ? rows_set >= 200000 : (ctx->gram_mode == ABC_GRAM_AUTO && part_min >= 400000);
-    if (!dma8_96 && C == 6 && dma_ok && i8_rows && rows_set >= 2000000 && n >= 4096) {
-        if (CY == 2) return run_gram_i8<6, 2>(ctx, X, Y, n, ldx, ldy, M, P, split, stats);
-        if (CY == 1) return run_gram_i8<6, 1>(ctx, X, Y, n, ldx, ldy, M, P, split, stats);
+    size_t C, CY;
+    const GramKernel kind = gram_kernel_for(ctx, X, Y, n, ldx, ldy, M, P, n_train_global, n_set, &C, &CY);
+#define GRAM_RUN(run, c, cy) if (C == c && CY == cy) return run<c, cy>(ctx, X, Y, n, ldx, ldy, M, P, split, stats)
+    switch (kind) {
+        case GRAM_I8:
+            GRAM_RUN(run_gram_i8, 6, 1); GRAM_RUN(run_gram_i8, 6, 2);
+            GRAM_RUN(run_gram_i8, 7, 0); GRAM_RUN(run_gram_i8, 7, 1); GRAM_RUN(run_gram_i8, 7, 2);
+            GRAM_RUN(run_gram_i8, 8, 0); GRAM_RUN(run_gram_i8, 8, 1); GRAM_RUN(run_gram_i8, 8, 2);
+            GRAM_RUN(run_gram_i8, 9, 0); GRAM_RUN(run_gram_i8, 9, 1); GRAM_RUN(run_gram_i8, 9, 2);
+            GRAM_RUN(run_gram_i8, 10, 0); GRAM_RUN(run_gram_i8, 10, 1); GRAM_RUN(run_gram_i8, 10, 2);
+            break;
+        case GRAM_DMA8:
+            GRAM_RUN(run_gram_dma8, 4, 0); GRAM_RUN(run_gram_dma8, 4, 1); GRAM_RUN(run_gram_dma8, 4, 2);
+            GRAM_RUN(run_gram_dma8, 5, 0); GRAM_RUN(run_gram_dma8, 5, 1); GRAM_RUN(run_gram_dma8, 5, 2);
+            GRAM_RUN(run_gram_dma8, 6, 1); GRAM_RUN(run_gram_dma8, 6, 2);
+            break;
+        case GRAM_WIDE:
+            GRAM_RUN(run_gram_wide, 8, 0); GRAM_RUN(run_gram_wide, 8, 1); GRAM_RUN(run_gram_wide, 8, 2);
+            GRAM_RUN(run_gram_wide, 9, 0); GRAM_RUN(run_gram_wide, 9, 1); GRAM_RUN(run_gram_wide, 9, 2);
+            GRAM_RUN(run_gram_wide, 10, 0); GRAM_RUN(run_gram_wide, 10, 1); GRAM_RUN(run_gram_wide, 10, 2);
+            break;
+        case GRAM_VGPR:
+            GRAM_RUN(run_gram, 1, 0); GRAM_RUN(run_gram, 2, 0); GRAM_RUN(run_gram, 2, 1);
+            GRAM_RUN(run_gram, 3, 0); GRAM_RUN(run_gram, 3, 1); GRAM_RUN(run_gram, 3, 2);
+            GRAM_RUN(run_gram, 4, 0); GRAM_RUN(run_gram, 4, 1); GRAM_RUN(run_gram, 4, 2);
+            GRAM_RUN(run_gram, 5, 0); GRAM_RUN(run_gram, 5, 1); GRAM_RUN(run_gram, 5, 2);
+            GRAM_RUN(run_gram, 6, 0); GRAM_RUN(run_gram, 6, 1); GRAM_RUN(run_gram, 6, 2);
+            break;
+        case GRAM_GROUPED:
+            break;
     }
-#define GRAM_DMA4_CASE(c, cy) if (C == c && CY == cy && dma_ok) return run_gram_dma8<c, cy>(ctx, X, Y, n, ldx, ldy, M, P, split, stats)
-    GRAM_DMA4_CASE(4, 0); GRAM_DMA4_CASE(4, 1); GRAM_DMA4_CASE(4, 2); GRAM_DMA4_CASE(5, 0); GRAM_DMA4_CASE(5, 1); GRAM_DMA4_CASE(5, 2);
-    GRAM_DMA4_CASE(6, 1); GRAM_DMA4_CASE(6, 2);
-#undef GRAM_DMA4_CASE
-#define GRAM_CASE(c, cy) if (C == c && CY == cy) return run_gram<c, cy>(ctx, X, Y, n, ldx, ldy, M, P, split, stats)
-    GRAM_CASE(1, 0); GRAM_CASE(2, 0); GRAM_CASE(2, 1); GRAM_CASE(3, 0); GRAM_CASE(3, 1); GRAM_CASE(3, 2);
-    GRAM_CASE(4, 0); GRAM_CASE(4, 1); GRAM_CASE(4, 2); GRAM_CASE(5, 0); GRAM_CASE(5, 1); GRAM_CASE(5, 2);
-    GRAM_CASE(6, 0); GRAM_CASE(6, 1); GRAM_CASE(6, 2);
-#undef GRAM_CASE
-    // 8..10 column blocks: one launch, the Gram blocks dealt out to the waves of a work-group (7 blocks: the compiler spills
-    // that instantiation; it stays on the grouped path)
-    // ... large sets on the byte-limb kernel on the i8 matrix pipe (k_gram_i8: sums and the diagonal exact, off-diagonal products
-    // to ~1e-10 of sqrt(G_aa G_bb)); small ones, and all with ABC_GRAM_FP64 (A/B runs, tests), on the fp64 matrix pipe
-    const bool gram_fp64 = ctx->gram_mode == ABC_GRAM_FP64;      // (abc_ctx_set_gram_mode; ABC_DIAG=1 ABC_GRAM_FP64=1 presets it)
-    // (LDS-DMA staging: 16-byte aligned columns, an even row count; from 200000 rows: the values are rounded to a 32-bit grid of
-    // 10 .. 19 sigma, noise of 3e-9 sigma per value that averages out with the square root of the rows -- 1e-10 of sqrt(G_aa G_bb) at
-    // 35000 rows per partition, which the 32nd loading of a 128-metric model amplifies to 2e-7; 4e-8 at 1e6 rows)
-    // (a rank whose shard the kernel cannot take -- an odd row count, columns that are not 16-byte aligned, fewer than 4096 rows --
-    // runs the fp64 kernel on ITS rows: the decision above is the same on every rank, this one is about what can run)
-    const bool i8_ok = !gram_fp64 && i8_rows && n >= 4096 && dma_ok;
-#define GRAM_WIDE_CASE(c, cy) if (C == c && CY == cy) return i8_ok ? run_gram_i8<c, cy>(ctx, X, Y, n, ldx, ldy, M, P, split, stats) \
-                                                                    : run_gram_wide<c, cy>(ctx, X, Y, n, ldx, ldy, M, P, split, stats)
-    // (7 blocks, 97..112 columns: the byte-limb kernel where it applies -- round 5; the fp64 one-launch kernel spills at that width, so
-    // small sets of it stay on the grouped path below, which reads every column twice)
-#define GRAM_I8_ONLY_CASE(c, cy) if (C == c && CY == cy && i8_ok) return run_gram_i8<c, cy>(ctx, X, Y, n, ldx, ldy, M, P, split, stats)
-    GRAM_I8_ONLY_CASE(7, 0); GRAM_I8_ONLY_CASE(7, 1); GRAM_I8_ONLY_CASE(7, 2);
-#undef GRAM_I8_ONLY_CASE
-    GRAM_WIDE_CASE(8, 0); GRAM_WIDE_CASE(8, 1); GRAM_WIDE_CASE(8, 2);
-    GRAM_WIDE_CASE(9, 0); GRAM_WIDE_CASE(9, 1); GRAM_WIDE_CASE(9, 2); GRAM_WIDE_CASE(10, 0); GRAM_WIDE_CASE(10, 1); GRAM_WIDE_CASE(10, 2);
-#undef GRAM_WIDE_CASE
-    // wider sets: column groups of 48, one launch per pair of groups (every column is read ceil(columns / 48) - 1 times)
+#undef GRAM_RUN
     return run_gram_grouped(ctx, X, Y, n, ldx, ldy, M, P, split, stats);
 }

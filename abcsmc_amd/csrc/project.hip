@@ -416,8 +416,7 @@ int launch_project_distance(abc_ctx* ctx, const double* X, size_t n, size_t ldx,
     // goes through the scalar kernel below)
     bool mfma_kernel = false;
     size_t mfma_lb = 0, mfma_main = 0;
-    static const bool valu_only = abc_diag_env("ABC_PROJECT_VALU") != nullptr;          // A/B switch for measurements
-    if (KC == 32 && npairs && !valu_only) {       // (16 components: the vector kernel is 5-10 % faster, measured)
+    if (KC == 32 && npairs) {       // (16 components: the vector kernel is 5-10 % faster, measured)
         const size_t M4 = (M + 3) & ~(size_t)3;
         mfma_main = (M4 * KC + 2 * M4 > (size_t)4 * 64 * (KC + 1)) ? M4 * KC + 2 * M4 : (size_t)4 * 64 * (KC + 1);
         mfma_lb = (mfma_main + KC) * sizeof(double);
@@ -525,21 +524,19 @@ size_t launch_project_scores(abc_ctx* ctx, const double* X, size_t n, size_t ldx
 // packet the selection's first kernel would wait for: ~7 us of the critical path)
 int launch_project_distance_scores(abc_ctx* ctx, const double* X, size_t n, size_t ldx, size_t M, size_t P, size_t A, const double* model,
                                    double* dist, double* S, size_t sld, size_t row_test, hipEvent_t done) {
-    static const bool off = abc_diag_env("ABC_PROJECT_SEPARATE") != nullptr;              // A/B switch for measurements
     const ModelLayout ML = model_layout(M, P, A);
     int KC = 1;
     while (KC < (int)A) KC *= 2;
     const bool vec_ok = (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)dist & 15) == 0) && (((uintptr_t)S & 15) == 0) &&
                         n >= 2 && !(n & 1) && !(row_test & 1) && !(sld & 1) && row_test < n;
-    if (off || !vec_ok || (KC != 8 && KC != 16 && KC != 32)) return 1;
+    if (!vec_ok || (KC != 8 && KC != 16 && KC != 32)) return 1;
     StageTimer tm(ctx, ST_PROJECT);
     const size_t npairs = n / 2;
     if (KC == 32) {
         const size_t M4 = (M + 3) & ~(size_t)3;
         const size_t mfma_main = (M4 * KC + 2 * M4 > (size_t)4 * 64 * (KC + 1)) ? M4 * KC + 2 * M4 : (size_t)4 * 64 * (KC + 1);
         const size_t lb = (mfma_main + KC) * sizeof(double);
-        static const bool valu_only = abc_diag_env("ABC_PROJECT_VALU") != nullptr;
-        if (lb > 150 * 1024 || valu_only) return 1;
+        if (lb > 150 * 1024) return 1;
         const unsigned gb = (unsigned)((n + 255) / 256);
         ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_project_mfma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
         hipExtLaunchKernelGGL(k_project_mfma<2>, dim3(gb), dim3(256), lb, ctx->stream, nullptr, done, 0, X, n, ldx, (int)M, model + ML.off_mean,

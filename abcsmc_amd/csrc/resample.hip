@@ -619,8 +619,7 @@ int abc_side_fork(abc_ctx* ctx) {
     // The side stream must start behind everything queued on the main one so far.  When the main stream is idle -- the usual
     // case at the start of a generation: the previous call ended with a synchronisation -- that holds without an event, and the
     // record + wait pair (~15 us of host time in front of the generation's first launch, the GPU idle meanwhile) is skipped.
-    static const int always = abc_diag_env("ABC_FORK_ALWAYS") ? 1 : 0;           // A/B switch for measurements
-    if (always || hipStreamQuery(ctx->stream) != hipSuccess) {
+    if (hipStreamQuery(ctx->stream) != hipSuccess) {
         (void)hipGetLastError();                                           // (hipErrorNotReady is not an error here)
         ABC_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
         ABC_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
@@ -709,7 +708,7 @@ int launch_resample(abc_ctx* ctx, const abc_rng* rng, const double* w, size_t K,
     // ---- the table built on the device (alias_dev.hip): no copy of the weights to the host, no host wait ------------------------
     if (ctx->alias_mode == ABC_ALIAS_DEVICE && K >= ABC_ALIAS_DEV_MIN_K && K <= ABC_ALIAS_DEV_MAX_K && ctx->ws_off + abc_alias_dev_need(K) <= ctx->ws_bytes) {
         if (!ctx->alias_fail_dev) ABC_HIP(ctx, hipMalloc((void**)&ctx->alias_fail_dev, sizeof(int)));
-        int* fail_pin = (int*)(ctx->status_pin + 44);
+        int* fail_pin = &ctx->status_pin->alias_fail;
         *fail_pin = 0;
         const int* verdict = nullptr;
         uint32_t* raw = const_cast<uint32_t*>(raw_ready);
@@ -848,7 +847,7 @@ int launch_perturb_prepare(abc_ctx* ctx, const abc_rng* rng, const double* theta
 int abc_giveups_ensure(abc_ctx* ctx) {
     if (ctx->giveups_dev) return ABC_OK;
     ABC_HIP(ctx, hipMalloc((void**)&ctx->giveups_dev, 3 * sizeof(unsigned long long)));
-    const unsigned long long init[3] = {0ull, 0ull, (unsigned long long)(size_t)(ctx->status_pin + 56)};
+    const unsigned long long init[3] = {0ull, 0ull, (unsigned long long)(size_t)&ctx->status_pin->giveup_flag};
     ABC_HIP(ctx, hipMemcpy(ctx->giveups_dev, init, sizeof(init), hipMemcpyHostToDevice));
     return ABC_OK;
 }

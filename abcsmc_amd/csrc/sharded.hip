@@ -494,7 +494,7 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
     // stream costs its critical path 6-7 us, the first packet of an idle queue nothing)
     ctx->side_early_waited = false;
     ctx->side_forked = false;
-    *(volatile unsigned*)(ctx->status_pin + 56) = 0u;          // (raised by a proposal kernel that gives up: read at the call's end)
+    *(volatile unsigned*)&ctx->status_pin->giveup_flag = 0u;          // (raised by a proposal kernel that gives up: read at the call's end)
     // (... except beside the byte-limb statistics kernel of wide sets, which wants every CU to itself: forked behind it, api.hip)
     const bool fork_late = abc_gram_takes_i8(ctx, io->X, io->Y, n, n, n, M, P, ntrain, N);
     if (!fork_late) ABC_TRY(abc_side_fork(ctx));
@@ -644,7 +644,7 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
         ABC_TRY(launch_select_smallest(ctx, dist, n, K, row0, io->idx, io->dist, true));
         const bool bins_deferred = ctx->sel_bins_ran && ctx->sel_fail_dev && !ctx->sel_force_radix;
         ctx->sel_bins_ran = false;
-        pfail_early = (int*)(ctx->status_pin + 40);
+        pfail_early = &ctx->status_pin->gather_sel_fail;
         *pfail_early = 0;
         if (bins_deferred) ds_fail_dev = ctx->sel_fail_dev;
         ABC_TRY(launch_gather_rows(ctx, io->Y, n, n, P, io->idx, K, row0, theta, K, bins_deferred ? ctx->sel_fail_dev : nullptr, pfail_early,
@@ -680,7 +680,7 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
                            (unsigned long long)n, bins_deferred ? (const int*)ctx->sel_fail_dev : (const int*)nullptr);
         if (ls_n) ABC_TRY(launch_gather_rows(ctx, io->Y, n, n, P, (const uint64_t*)R.idx(rec_mine, 0), ls_n, row0, (double*)R.rows(rec_mine, 0), ls_cap));
         ABC_TRY(comm_all_gather(ctx, rec_mine, rec_all, R.rec_bytes));
-        pfail_early = (int*)(ctx->status_pin + 40);
+        pfail_early = &ctx->status_pin->gather_sel_fail;
         *pfail_early = 0;
         ds_fail_dev = ds_fail;
         hipLaunchKernelGGL(k_ls_unpack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, (const char*)rec_all, R, W, cand_dist,
@@ -786,8 +786,8 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
         side_out.dv = dv; side_out.L = L_early; side_out.spd = spd_dev;
         // (as the fused driver: the generation's status words go straight into the pinned block from k_post_tail -- no copies behind
         // the proposals)
-        side_out.model_hdr = model; side_out.hdr_pin = (double*)ctx->status_pin; side_out.spd_pin = L_early ? (int*)(ctx->status_pin + 32) : nullptr;
-        ((double*)ctx->status_pin)[0] = 0.0; *(int*)(ctx->status_pin + 32) = 0;
+        side_out.model_hdr = model; side_out.hdr_pin = ctx->status_pin->model_hdr; side_out.spd_pin = L_early ? &ctx->status_pin->spd : nullptr;
+        ctx->status_pin->model_hdr[0] = 0.0; ctx->status_pin->spd = 0;
         status_early = true;
         side_out.rows = (double*)abc_ws_alloc(ctx, K * (size_t)PPr * sizeof(double));
         if (L_early) side_out.Lpad = (double*)abc_ws_alloc(ctx, (size_t)PPr * PPr * sizeof(double));
@@ -885,8 +885,8 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
     }
     taus2_jump(rng, 2 * (uint64_t)cfg->Nnext_total);          // Nnext resampling draws + Nnext seeds of the whole set
     {
-        double* hdr = (double*)ctx->status_pin;             // pinned, device-visible
-        int* pspd = (int*)(ctx->status_pin + 32);
+        double* hdr = ctx->status_pin->model_hdr;             // pinned, device-visible
+        int* pspd = &ctx->status_pin->spd;
         if (!status_early) {                                // (first sets, generations without proposals: the two words by copies)
             hdr[0] = 0.0; *pspd = 0;
             ABC_HIP(ctx, hipMemcpyAsync(hdr, model, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -898,7 +898,7 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
         if (ds_fail_dev && pfail_early && *pfail_early) return repeat_with_radix();      // (no host wait before this one)
         // the device build of the resampling table did not verify (every rank builds the same table from the same weights, so
         // every rank lands here alike): this rank's draws and proposals once more, with the table from the host
-        if (alias_deferred && *(volatile int*)(ctx->status_pin + 44) && parent_used) {
+        if (alias_deferred && *(volatile int*)&ctx->status_pin->alias_fail && parent_used) {
             ctx->alias_dev_fallbacks++;
             const int mode = ctx->alias_mode;
             ctx->alias_mode = ABC_ALIAS_HOST;
@@ -915,7 +915,7 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
     // left the count of the context's last fused generation standing): the pinned word a proposal kernel raises when it gives up
     // tells whether the device counter has to be fetched at all
     {
-        volatile unsigned* pgaveup = (volatile unsigned*)(ctx->status_pin + 56);
+        volatile unsigned* pgaveup = &ctx->status_pin->giveup_flag;
         if (Nn && *pgaveup && ctx->giveups_dev) {
             unsigned long long now = 0;
             ABC_HIP(ctx, hipMemcpyAsync(&now, ctx->giveups_dev, sizeof(now), hipMemcpyDeviceToHost, ctx->stream));

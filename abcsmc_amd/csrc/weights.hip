@@ -1387,20 +1387,12 @@ static bool ks_topn_on(size_t P, bool split, bool fold, size_t pairs) {
     return (double)pairs >= minp;
 }
 
-// 33..64 parameters: the previous tiles staged in LDS (k_kde_split_lds; ABC_KDE_LDS=0 under ABC_DIAG: the register-resident kernel of
-// rounds 3-5), and with it three stored chunks instead of four at 33..48 parameters (ABC_KDE_CHUNKS3=0: four)
-static bool ks_lds_on() {
-    static const bool on = [] { const char* e = abc_diag_env("ABC_KDE_LDS"); return !e || atoi(e) != 0; }();
-    return on;
-}
-static int ks_chunks(size_t P) {
-    static const bool three = [] { const char* e = abc_diag_env("ABC_KDE_CHUNKS3"); return !e || atoi(e) != 0; }();
-    return (P <= 16) ? 1 : (P <= 32) ? 2 : (P <= 48 && three && ks_lds_on()) ? 3 : 4;
-}
+// 33..64 parameters: the previous tiles staged in LDS (k_kde_split_lds), and with it three stored chunks instead of four at 33..48
+// parameters
+static int ks_chunks(size_t P) { return (P <= 16) ? 1 : (P <= 32) ? 2 : (P <= 48) ? 3 : 4; }
 // up to 13 / 17..29 / 33..45 / 49..61 parameters: the variants of the split kernel with two MFMAs fewer (norm pieces in the spare K-slots: KS_FOLD)
 static bool ks_fold_on(size_t P, bool split) {
-    static const bool off = abc_diag_env("ABC_KDE_NOFOLD") != nullptr;              // A/B switch for measurements
-    return split && P + 3 <= (size_t)16 * ks_chunks(P) && !off;               // three spare K-slots in the last chunk
+    return split && P + 3 <= (size_t)16 * ks_chunks(P);                       // three spare K-slots in the last chunk
 }
 
 int launch_weights_prev(abc_ctx* ctx, size_t P, size_t kn_max, const double* theta_prev, size_t Kp, const double* w_prev,
@@ -1588,7 +1580,6 @@ int launch_weights_raw(abc_ctx* ctx, const abc_prior* priors, const double* thet
 #undef LAUNCH_EPAN
     } else {
         StageTimer tk(ctx, ST_KDE);
-        const bool kde_lds = ks_lds_on();
         if (split) {
             // three waves per SIMD at 16 parameters (129 VGPRs; four, with two spills: no faster), two at 32 (192)
             // ... one at 64 on this kernel (more than 256 registers: the two resident column operand sets alone are 128) -- which is
@@ -1608,11 +1599,8 @@ int launch_weights_raw(abc_ctx* ctx, const abc_prior* priors, const double* thet
             else if (fold && NCH == 3)      // (33..45: three chunks, nineteen MFMAs per 1024 pairs; previous tiles in LDS, two waves per SIMD)
                 hipLaunchKernelGGL((k_kde_split_lds<KS_FOLD + 3, KDE_LDS_W3, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
                                    (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (fold && kde_lds)       // (49..61 with the previous tiles in LDS: twenty-five)
+            else if (fold)                  // (49..61 with the previous tiles in LDS: twenty-five)
                 hipLaunchKernelGGL((k_kde_split_lds<KS_FOLD + 4, 2, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (fold)                  // (33..61: twenty-five instead of twenty-seven)
-                hipLaunchKernelGGL((k_kde_split<KS_FOLD + 4, 1, true, 0>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
                                    (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
             else if (prev->tmin && NCH == 1)      // (14..16 parameters, tiles in the order of the norm tops: eight MFMAs instead of nine)
                 hipLaunchKernelGGL((k_kde_split<KS_TOPN + 1, 3, true, 1>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
@@ -1623,11 +1611,8 @@ int launch_weights_raw(abc_ctx* ctx, const abc_prior* priors, const double* thet
             else if (prev->tmin && NCH == 3)      // (46..48: twenty)
                 hipLaunchKernelGGL((k_kde_split_lds<KS_TOPN + 3, KDE_LDS_W3, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
                                    (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (prev->tmin && kde_lds)       // (62..64: twenty-six)
+            else if (prev->tmin)                  // (62..64: twenty-six)
                 hipLaunchKernelGGL((k_kde_split_lds<KS_TOPN + 4, 2, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (prev->tmin)                  // (62..64: twenty-six instead of twenty-seven)
-                hipLaunchKernelGGL((k_kde_split<KS_TOPN + 4, 1, true, 0>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
                                    (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
             else if (NCH == 1)
                 hipLaunchKernelGGL((k_kde_split<1, 3, true, 1>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
@@ -1638,11 +1623,8 @@ int launch_weights_raw(abc_ctx* ctx, const abc_prior* priors, const double* thet
             else if (NCH == 3)
                 hipLaunchKernelGGL((k_kde_split_lds<3, KDE_LDS_W3, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
                                    (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (kde_lds)
-                hipLaunchKernelGGL((k_kde_split_lds<4, 2, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
             else
-                hipLaunchKernelGGL((k_kde_split<4, 1>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
+                hipLaunchKernelGGL((k_kde_split_lds<4, 2, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
                                    (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
         }
         if (PP > 64)

@@ -386,8 +386,7 @@ __device__ __forceinline__ void wx_wave_table(const unsigned int* __restrict__ c
 //   (all keys in the low, positive differences in the high half of a 32-bit counter: a work-group's rows stay below 2^16)
 //   MODE 2: the key itself (sign of d in bit 63) to keys[slot][row] -- the exact step.
 // The work-groups of one run of tiles (one per group of tests) follow each other on ONE XCD (blockIdx % 8), so the scores come
-// from HBM once and from that XCD's L2 for the other groups.  TT threads: 1024 (four waves per SIMD, <= 128 registers), or 768 with two
-// rows per thread at 17..32 components (three waves per SIMD, <= 170 registers: the 2 x 32 scores of a thread's rows alone are 128).
+// from HBM once and from that XCD's L2 for the other groups.  TT threads: 1024 (four waves per SIMD, <= 128 registers).
 template <int AM, int R, int MODE, int TT>
 __global__ __launch_bounds__(TT) void k_wx_sweep(const double* __restrict__ Y, size_t ldy, size_t row_test, size_t nt, int M, int P, int A,
                                                    const double* __restrict__ model, const double* __restrict__ S, size_t sld,
@@ -1382,16 +1381,14 @@ WxLevel wx_level_one(size_t nt, size_t A, int want, int NBX, size_t per_test_lds
     g.G = (int)(((size_t)WX_LDS - 1024) / per_test_lds);          // (1 KB: the spare counters of the sweep)
     if (g.G < 1) g.G = 1;
     if (g.G > want) g.G = want;
-    static const bool t768 = abc_diag_env("ABC_WX_T768") != nullptr;          // A/B switch: 17..32 components on 768 threads x 2 rows
-    const int rmax = A <= 8 ? 4 : (A <= 16 ? 2 : (t768 ? 2 : 1));
+    const int rmax = A <= 8 ? 4 : (A <= 16 ? 2 : 1);
     int ns = fixed_slots > 0 ? fixed_slots : want;
     for (int it = 0; it < 8; it++) {
         g.nslots = ns;
         g.TG = (ns + g.G - 1) / g.G;
         g.R = rmax;
-        auto threads = [&](int R) { return (A > 16 && R == 2) ? 768 : WX_T; };
-        while (g.R > 1 && ((nt + (size_t)threads(g.R) * g.R - 1) / ((size_t)threads(g.R) * g.R)) * (size_t)g.TG < 192) g.R >>= 1;
-        g.TT = threads(g.R);
+        while (g.R > 1 && ((nt + (size_t)WX_T * g.R - 1) / ((size_t)WX_T * g.R)) * (size_t)g.TG < 192) g.R >>= 1;
+        g.TT = WX_T;
         g.tiles = (int)((nt + (size_t)g.TT * g.R - 1) / ((size_t)g.TT * g.R));
         const int limit = 65535 / (g.TT * g.R);
         int rr_target = 256 / g.TG;
@@ -1433,12 +1430,6 @@ size_t wx_bc_bytes(size_t nv, size_t nseg_max) {           // the sweeps' counte
 // sigma, and a test that reaches a fine level has its statistic near the threshold, where |W| / sigma has density ~0.2: about
 // 126 / B sqrt(m / 5e5) of them stay open.  Rounds 4-5 took 16384 / 8192 / 4096 / 2048 bins by the number of tests alone.
 int wx_pick_bins(int nact, size_t nvt) {
-    static const char* fixed = abc_diag_env("ABC_WX_BINS_BY_COUNT");          // A/B switch: the rule of rounds 4-5
-    if (fixed) {
-        int nb = nact <= 8 ? 16384 : (nact <= 32 ? 8192 : (nact <= 96 ? 4096 : 2048));
-        while (nb > 1024 && (size_t)nb * 4 > nvt) nb >>= 1;                // (at least four keys to the bin)
-        return nb;
-    }
     const double open_per_bin = 126.0 * sqrt((double)nvt / 5.0e5);
     int best = 1024;
     double best_cost = 1e300;
@@ -1532,7 +1523,6 @@ static void wx_sweep(abc_ctx* ctx, size_t A, int mode, const WxLevel& g, size_t 
                                                     kbase, c0, NBX, blockcnt, keys, kld)
     if (A <= 8) { if (g.R == 4) WX_GO(8, 4, 1024); else if (g.R == 2) WX_GO(8, 2, 1024); else WX_GO(8, 1, 1024); }
     else if (A <= 16) { if (g.R == 2) WX_GO(16, 2, 1024); else WX_GO(16, 1, 1024); }
-    else if (g.R == 2) WX_GO(32, 2, 768);
     else WX_GO(32, 1, 1024);
 #undef WX_GO
 }
@@ -1542,8 +1532,7 @@ static void wx_scores(abc_ctx* ctx, const double* X, size_t ldx, size_t row_test
     // the projection's kernels where the shape is theirs (row pairs with 16-byte loads; 17..32 components on the fp64 matrix pipe: the
     // vector kernel below took 605 us at 5e5 rows x 128 metrics x 32 components, k_project_mfma does twice the rows in 270), the
     // vector kernel for what they leave (an odd last row, unaligned or narrow sets)
-    static const bool plain = abc_diag_env("ABC_WX_PLAIN_SCORES") != nullptr;
-    const size_t took = plain ? 0 : launch_project_scores(ctx, X + row_test, nt, ldx, M, P, A, model, S);
+    const size_t took = launch_project_scores(ctx, X + row_test, nt, ldx, M, P, A, model, S);
     if (took >= nt) return;
     const size_t nt_all = nt;
     X += took; S += took; nt -= took;
@@ -1571,7 +1560,7 @@ struct abc_wx_run {
     int Wr; bool sharded; size_t nvt, nseg_max, bc_bytes;
     WxPlan* plan; int *seg_j, *seg_a, *astar, *segbase, *fail; unsigned long long* nz; double* W; int* v3; unsigned int* kbase;
     int *actA, *actB, *nactv; unsigned int* tickets; int* slotmap; unsigned char* passb; double* S; size_t S_ld; unsigned int *c0, *blockcnt;
-    volatile int* pin; const double* nv_ranks; size_t nv_stride;
+    volatile abc_wx_words* pin; const double* nv_ranks; size_t nv_stride;
     unsigned int* cl_fine; size_t cl_fine_ld;
     // the largest count first (k_wx_plan): the tests of first_r picked responses (actA, at most first_bound of them), then -- only
     // if none of those responses keeps its optimum -- the rest (act_rest)
@@ -1584,7 +1573,7 @@ struct abc_wx_run {
                     size_t cl_ld, int cl_by_test, bool first_half) {
         hipStream_t st = ctx->stream;
         const size_t per_test = (size_t)NBX * 4 + (mode == 1 ? WX_NC0 * 4 : 0) + 7 * 4 + 16;
-        pin[0] = -1;
+        pin->left = -1;
         const size_t blds = ((size_t)NBX + 1024) * 8;
         if (blds > (48u << 10)) ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_wx_bounds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds));
         for (int lo = 0; lo < nact_host;) {
@@ -1611,8 +1600,8 @@ struct abc_wx_run {
         return ABC_OK;
     }
     int level_wait(int* left, bool* decided) {
-        ABC_TRY(wx_wait_word(ctx, pin, left));
-        *decided = pin[5] != 0;                 // (written in front of the word the wait saw)
+        ABC_TRY(wx_wait_word(ctx, &pin->left, left));
+        *decided = pin->decided != 0;                 // (written in front of the word the wait saw)
         return ABC_OK;
     }
 
@@ -1638,12 +1627,10 @@ struct abc_wx_run {
         nactv = (int*)abc_ws_alloc(ctx, WX_NWORDS * sizeof(int));
         tickets = (unsigned int*)abc_ws_alloc(ctx, WX_NWORDS * sizeof(int));
         // the largest count first: where the caller only uses the largest per-response count and there are more responses than picks
-        static const char* first_env = abc_diag_env("ABC_WX_FIRST");            // A/B switch and tests: 0 = every test at level 0, as round 5
         first_r = 0;
         if (stop_at_max && P <= 1024 && A >= 2) {
             first_r = 32 / (int)(A - 1);
             first_r = first_r < 2 ? 2 : (first_r > 4 ? 4 : first_r);
-            if (first_env) first_r = atoi(first_env) < WX_FIRST_MAX ? atoi(first_env) : WX_FIRST_MAX;
             if ((size_t)first_r >= P) first_r = 0;
         }
         first_bound = first_r ? first_r * (int)(A - 1) : (int)nseg_max;
@@ -1659,7 +1646,7 @@ struct abc_wx_run {
         if (!plan || !seg_j || !seg_a || !astar || !segbase || !fail || !nz || !W || !v3 || !kbase || !actA || !actB || !nactv || !tickets || !slotmap ||
             !passb || !c0 || !blockcnt || !act_rest || !in_first)
             ABC_FAIL(ctx, ABC_ERR_NOMEM, "wilcoxon: workspace exhausted (%zu tests x %zu rows)", nseg_max, nt);
-        pin = (volatile int*)(ctx->status_pin + 64);
+        pin = &ctx->status_pin->wx;
         nv_ranks = has_sh ? shv.nv_ranks : nullptr;
         nv_stride = has_sh ? shv.nv_stride : 0;
         cl_fine = nullptr;
@@ -1740,10 +1727,10 @@ struct abc_wx_run {
             // most of their tests, 4 of 83 left instead of 50)
             ABC_TRY(fine_levels(0, true));
             if (!decided) {
-                // (the host sizes the launch for the tests there are -- pin[6], left by the first half's bounds kernels; sized for all
+                // (the host sizes the launch for the tests there are -- pin->n_rest, left by the first half's bounds kernels; sized for all
                 // P (A - 1) that a set could have, two thirds of the work-groups of a 77-test level found nothing to do and the rest
                 // had a third of the chip: 216 us at 1e6 x 128 x 16 x 32.  A level without tests still runs its decision.)
-                int n_rest = pin[6];
+                int n_rest = pin->n_rest;
                 if (n_rest < 1) n_rest = 1;
                 if (n_rest > (int)nseg_max) n_rest = (int)nseg_max;
                 ABC_TRY(level_queue(4, 0, WX_NC0, act_rest, nactv + 4, n_rest, actB, nactv + 5, c0, WX_NC0, 1, false));
@@ -1761,7 +1748,7 @@ struct abc_wx_run {
             const unsigned int target = wx_target(nvt);
             const int nbcap = (int)(nvt / target) + 2;
             size_t vmax = nt;
-            if (sharded) vmax = (size_t)pin[1] | ((size_t)pin[2] << 31);
+            if (sharded) vmax = (size_t)pin->vmax_lo | ((size_t)pin->vmax_hi << 31);
             if (vmax < nt) ABC_FAIL(ctx, ABC_ERR_COMM, "wilcoxon: %zu validation rows on this rank, %zu at most on any", nt, vmax);
             unsigned long long* keys_loc = (unsigned long long*)abc_ws_alloc(ctx, (size_t)XB * (vmax ? vmax : 1) * 8);
             unsigned long long* keysx = (unsigned long long*)abc_ws_alloc(ctx, (size_t)XB * nvt * 8);
@@ -1823,7 +1810,7 @@ struct abc_wx_run {
             ABC_HIP(ctx, hipMemcpyAsync(fail_host, fail, sizeof(int), hipMemcpyDeviceToHost, st));
             ABC_HIP(ctx, hipStreamSynchronize(st));
         }
-        if (changed_host) *changed_host = pin[4];          // (visible: written in front of the word the last wait / the synchronisation saw)
+        if (changed_host) *changed_host = pin->changed;          // (visible: written in front of the word the last wait / the synchronisation saw)
         if (abc_diag_env("ABC_WX_DEBUG")) {          // (diagnostic: how the tests were settled)
             std::vector<int> hv(nseg_max);
             WxPlan hp;

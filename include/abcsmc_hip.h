@@ -24,7 +24,7 @@
  *   - one context per GPU and per host thread; calls on one context are serialised.
  *   - Diagnostic environment switches: the library reads NO environment variable unless ABC_DIAG=1 is set; beside it, the
  *     test / A-B switches listed in INTEGRATION.md section 6 act (ABC_WS_POISON: workspace pre-filled with a byte;
- *     ABC_ALIAS_FORCE_FAIL: the device alias build reports failure; kernel-variant and stream-orchestration A/B switches).
+ *     ABC_ALIAS_FORCE_FAIL: the device alias build reports failure; kernel-path and fault-injection switches of the tests).
  *     None changes a result except by forcing a documented fall-back path.
  */
 #ifndef ABCSMC_HIP_H

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs on the GPU box: the bench line of one config without / with a diagnostic switch, alternating, REPS times each
-#   gpurun -- 'bash scripts/gpu_env_ab_bench.sh ABC_PROJECT_SEPARATE 3 3'
+#   bash scripts/gpu_env_ab_bench.sh ABC_GRAM_FP64 4 3
 set -u
 export TMPDIR=/tmp ABC_DIAG=1
 VAR="$1"; CFG="$2"; REPS="${3:-3}"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6: the bench line of one config under a list of environment settings (diagnostic switches), alternating, REPS times
-#   gpurun -- 'bash scripts/gpu_r6_envab.sh 5 2 "A=1" "ABC_WX_FIRST=3" "ABC_WX_FIRST=4"'
+#   bash scripts/gpu_r6_envab.sh 5 2 "A=1" "ABC_GRAM_FP64=1" "ABC_GRAM_I8=1"
 set -u
 export TMPDIR=/tmp ABC_DIAG=1
 CFG="$1"; REPS="$2"; shift 2

@@ -1,6 +1,5 @@
 #!/bin/bash
-# Runs on the GPU box: the bench line of one config under argmin PRESS, under the Wilcoxon rule, and under the rule with this round's
-# orchestration changes switched off one at a time (diagnostic switches), alternating, REPS times
+# Runs on the GPU box: the bench line of one config under argmin PRESS and under the Wilcoxon rule, alternating, REPS times
 #   gpurun -- 'bash scripts/gpu_rule_variants.sh 3 2'
 set -u
 export TMPDIR=/tmp ABC_DIAG=1
@@ -14,8 +13,4 @@ import json, sys; d=json.loads(sys.stdin.read()); print('%-34s step %.4f ms  str
 for r in $(seq 1 $REPS); do
   run "press" press A=1
   run "wilcoxon" wilcoxon A=1
-  run "wilcoxon, look deferred (round 5)" wilcoxon ABC_WX_DEFER=1
-  run "wilcoxon, scores separate" wilcoxon ABC_PROJECT_SEPARATE=1
-  run "wilcoxon, all tests at level 0" wilcoxon ABC_WX_FIRST=0
-  run "wilcoxon, in stream order" wilcoxon ABC_WX_INLINE=1
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs on the GPU box: one diagnostic switch of the Wilcoxon reduction A/B-ed on one shape -- kernel statistics of the sweeps, then
 # the bench line of the given config, each without and with the switch
-#   gpurun -- 'bash scripts/gpu_wx_envab.sh ABC_WX_T768 "1000000 128 16 32" 4'
+#   bash scripts/gpu_wx_envab.sh ABC_WX_NOBOUNDS "1000000 128 16 32" 4
 set -u
 ROOT=$(pwd); OUT=$ROOT/gpurun_out; export TMPDIR=/tmp ABC_DIAG=1
 VAR="$1"; SHAPE="$2"; CFG="$3"

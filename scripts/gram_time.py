@@ -1,5 +1,4 @@
-"""Times the one-pass statistics kernel alone (abc_stats_accumulate_dev) on random resident data; used for A/B runs
-of k_gram variants (ABC_GRAM_DMA, ABC_GRAM_ABL) without running later stages on possibly invalid statistics.
+"""Times the one-pass statistics kernel alone (abc_stats_accumulate_dev) on random resident data, without the later stages.
     python scripts/gram_time.py [N] [M] [P]"""
 import os
 import sys

@@ -1,5 +1,5 @@
 """Times the PLS ranking (device resident) at a given shape; the stage timers give the projection kernel's share.
-    python scripts/project_time.py N M P A        (ABC_PROJECT_VALU=1: the vector-pipe projection for 16 / 32 components)"""
+    python scripts/project_time.py N M P A"""
 import os
 os.environ.setdefault("ABC_DIAG", "1")     # the library reads its diagnostic switches only beside this
 import sys

@@ -1,8 +1,7 @@
 """The same generation many times over (inputs resident, outputs hashed each time): every output must be bit-identical from run
 to run -- the two streams of a generation, the side stream's early work and the events between them leave room for races that a
-single comparison against the oracle would not show.  The printed hash must also be the same with the streams' orchestration
-switches flipped (ABC_FORK_ALWAYS, ABC_WAIT_LATE, ABC_SEEDS_FIRST, ABC_MOMENTS_MAIN, ABC_STATUS_KERNEL) and with the runtime serialising
-every launch (AMD_SERIALIZE_KERNEL=3): a dependency the streams' events do not express would show as a different hash there.
+single comparison against the oracle would not show.  The printed hash must also be the same with the runtime serialising every
+launch (AMD_SERIALIZE_KERNEL=3): a dependency the streams' events do not express would show as a different hash there.
     python scripts/repeat_check.py [repeats]"""
 import hashlib
 import os

@@ -1,6 +1,5 @@
 """Worker of test_weight_split_kernel_staging_does_not_change_the_sums: the importance weights of fixed sets at the parameter counts
-given on the command line, one line per count: P, sha256 of the K weights' bytes, and the weights' sum to 17 digits.  The switches
-that pick the kernel (ABC_KDE_LDS, ABC_KDE_CHUNKS3 under ABC_DIAG) are read once per process, hence a process per setting."""
+given on the command line, one line per count: P, sha256 of the K weights' bytes, and the weights' sum to 17 digits."""
 import hashlib
 import os
 import sys

@@ -572,30 +572,35 @@ def test_weight_split_kernel_accuracy_at_33_to_64_parameters(gpu_ctx, oracle, P,
 def test_weight_split_kernel_staging_does_not_change_the_sums():
     """33..64 parameters since round 6: the previous tiles are staged in LDS (k_kde_split_lds, two or three waves per SIMD) instead
     of being held in registers (k_kde_split, one wave per SIMD), and up to 48 parameters three chunks are stored and multiplied
-    instead of four.  The staging changes where an operand comes from, not one matrix step: at 49..64 parameters the weights are the
-    register kernel's BIT FOR BIT, and so are the four-chunk LDS kernel's at 33..48; the three-chunk kernels (the fourth chunk's
+    instead of four.  The staging changes where an operand comes from, not one matrix step: at 49..64 parameters the weights were the
+    register kernel's BIT FOR BIT, and so were the four-chunk LDS kernel's at 33..48; the three-chunk kernels (the fourth chunk's
     products were exact zeros; the norm pieces ride in another chunk's spare slots up to 45 parameters, and 46..48 lose the folded
-    variant) agree with them far inside the kernel's error budget.  One process per setting: the switches are read once."""
+    variant) agreed with them far inside the kernel's error budget.  The register kernel and the four-chunk setting at 33..48 are
+    retired: the sha256 of the weights the LDS kernels gave when they were checked against them are pinned here, and the kernels
+    must still give exactly those bits."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    counts = ["33", "45", "46", "48", "49", "61", "62", "64"]
-
-    def run(**env):
-        p = subprocess.run([sys.executable, os.path.join(root, "tests", "_kde_worker.py")] + counts, capture_output=True, text=True, timeout=600,
-                           env=dict(os.environ, ABC_DIAG="1", **env), cwd=root)
-        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
-        rows = [l.split() for l in p.stdout.splitlines() if l.startswith("KDE ")]
-        assert [r[1] for r in rows] == counts
-        return {int(r[1]): (r[2], float(r[3])) for r in rows}
-    built, four, regs = run(), run(ABC_KDE_CHUNKS3="0"), run(ABC_KDE_LDS="0")
-    for P in (int(c) for c in counts):
-        assert four[P][0] == regs[P][0], P                                  # LDS staging alone: the same bits
-        if P > 48:
-            assert built[P][0] == regs[P][0], P
-        else:
-            assert abs(built[P][1] / regs[P][1] - 1.0) < 1e-7, (P, built[P][1], regs[P][1])
+    pinned = {
+        33: ("96a2168854e07ecad9ce4d478bddd7a6b694f7de6e9a375764b592fe766d6eb2", 1.87226878815456246e+01),
+        45: ("00386d60c187b095d648f980c35ec568d192ded136e25727728b59a875fee828", 1.19730772430102377e+01),
+        46: ("1442f5bca7a83db2aaeb35bf2a152af7fd163edb6283af18ec22a4049000de35", 7.47766780147603427e+00),
+        48: ("a7aba27b0a5648ed4076a363f59983f2b2a31f981a1f5d6fdf22b9adbd7550d0", 1.13914449815631329e+01),
+        49: ("e11ac59afd1b850fae4789d48b3592add83b08183967ba3162fa38ef663f259b", 3.82582272153152703e+00),
+        61: ("7112143a4faeab0a5ad7af2b132e5320ac1e9afae9f8c817f4941a954d485e9f", 1.77819062987579901e+00),
+        62: ("3eb48bcaad21ce3aa96e824f2b0cee95525f450afe489767a6896ac81ca6f39f", 2.32794576292930167e+00),
+        64: ("6e1abd4e257763a792fd7fe5f55b6c92938550ab6f68809661d5daafb3e5639f", 1.00941719085734221e+01),
+    }
+    counts = [str(P) for P in pinned]
+    p = subprocess.run([sys.executable, os.path.join(root, "tests", "_kde_worker.py")] + counts, capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ABC_DIAG="1"), cwd=root)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    rows = [l.split() for l in p.stdout.splitlines() if l.startswith("KDE ")]
+    assert [r[1] for r in rows] == counts
+    for r in rows:
+        P = int(r[1])
+        assert r[2] == pinned[P][0], (P, float(r[3]), pinned[P][1])
 
 
 @pytest.mark.parametrize("P", [16, 11])
@@ -1930,7 +1935,7 @@ def test_generation_speculates_on_the_component_count(gpu_ctx, oracle, M, P, A, 
     validation rows' go to the cascade) and takes the distance over the fit's count.  The host looks at the cascade -- which takes the
     tests of a few responses that hold the largest count first (round 6) -- in front of the weight stage.  With noisy responses the
     reduction lowers the largest count: the distances are taken again from the kept scores, selection and gather run once more
-    (round 5's default had queued everything up to the proposals by then and repeated the whole generation: ABC_WX_DEFER).
+    (round 5's default had queued everything up to the proposals by then and repeated the whole generation).
     With clean responses the count stands.  Either way every output equals the oracle's generation under the rule -- the parents too,
     so the repeat starts from the generator's state at entry -- and the count equals the oracle's, which in the noisy cases is below
     the argmin-PRESS count (checked: the speculation is wrong there and has to be repaired).  8 / 10 components: the vector
@@ -1958,10 +1963,10 @@ def test_generation_speculates_on_the_component_count(gpu_ctx, oracle, M, P, A, 
     if noise:
         assert ref["ncomp"] < press            # (the case the test is for: the count the ranking speculated on is wrong)
     # what the repair cost (abc_generation_repeats): a moved count = the three ranking stages ONCE more, a count that stands = nothing;
-    # the generation itself is never repeated (round 5's default did that).  Under the diagnostic switches that force the cascade to
-    # fail or defer its look the counts are those switches' own.
+    # the generation itself is never repeated (round 5's default did that).  Under the diagnostic switch that forces the cascade to
+    # fail the counts are that switch's own.
     import os
-    if not any(os.environ.get(k) for k in ("ABC_WX_FORCE_FAIL", "ABC_WX_DEFER", "ABC_WX_INLINE")):
+    if not os.environ.get("ABC_WX_FORCE_FAIL"):
         assert (ranking_repeats, generation_repeats) == ((1, 0) if ref["ncomp"] < press else (0, 0))
     assert gen.ncomp.value == ref["ncomp"]
     assert np.array_equal(gen.idx.cpu().numpy().astype(np.uint64), ref["idx"])
@@ -1986,13 +1991,6 @@ def test_generation_repeats_itself_when_the_cascade_gives_up(gpu_ctx):
                        timeout=900, env=env, cwd=root)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
     assert "3 passed" in p.stdout, p.stdout[-500:]
-    # ... and round 5's default, kept behind a switch: everything up to the proposals queued on the fit's count, the look at the
-    # cascade behind them, a moved count repeating the whole generation -- one weighted case with noisy responses
-    env = dict(os.environ, ABC_DIAG="1", ABC_WX_DEFER="1")
-    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", ids[0]], capture_output=True, text=True,
-                       timeout=900, env=env, cwd=root)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
-    assert "1 passed" in p.stdout, p.stdout[-500:]
 
 
 def test_wilcoxon_reduction_at_config4_stated_size(gpu_ctx, oracle):
