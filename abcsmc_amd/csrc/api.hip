@@ -319,12 +319,29 @@ static size_t default_A(size_t M, size_t P, int max_comp) {
 }
 
 // ---- stage-level device entry points -----------------------------------------------------------
+// Column-major arguments of the stage entry points: a leading dimension below the row count would make columns overlap, and a
+// set without columns has no record.  The statistics also need a metric column: with M == 0 the record has no X'X block, and
+// the column-group path (run_gram_grouped) that such a set would reach covers pairs of groups only, so it would leave the
+// record unwritten.  Leading dimensions of an empty side (M == 0 / P == 0) are not looked at.
+#define CHECK_COLS(ctx, fn, n, ldx, ldy, M, P)                                                                          \
+    do {                                                                                                                \
+        if ((M) + (P) == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no columns (M + P == 0)", fn);                         \
+        if ((M) > 0 && (ldx) < (n)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < n %zu", fn, (size_t)(ldx), (size_t)(n)); \
+        if ((P) > 0 && (ldy) < (n)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < n %zu", fn, (size_t)(ldy), (size_t)(n)); \
+    } while (0)
+#define CHECK_STATS_COLS(ctx, fn, n, ldx, ldy, M, P)                                                                    \
+    do {                                                                                                                \
+        CHECK_COLS(ctx, fn, n, ldx, ldy, M, P);                                                                         \
+        if ((M) == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: the statistics record needs at least one metric (M == 0)", fn); \
+    } while (0)
+
 extern "C" size_t abc_stats_len(size_t M, size_t P) { return stats_layout(M, P).len; }
 extern "C" size_t abc_model_len(size_t M, size_t P, size_t A) { return model_layout(M, P, A).len; }
 
 extern "C" int abc_stats_shift_dev(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy,
                                    size_t M, size_t P, double* stats) {
     CHECK_CTX(ctx);
+    CHECK_STATS_COLS(ctx, "abc_stats_shift_dev", n, ldx, ldy, M, P);
     return launch_stats_shift(ctx, X, Y, n, ldx, ldy, M, P, stats);
 }
 
@@ -332,6 +349,7 @@ extern "C" int abc_stats_accumulate_dev(abc_ctx* ctx, const double* X, const dou
                                         size_t ldy, size_t M, size_t P, uint64_t row0, uint64_t n_train_global,
                                         double* stats) {
     CHECK_CTX(ctx);
+    CHECK_STATS_COLS(ctx, "abc_stats_accumulate_dev", n, ldx, ldy, M, P);
     ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(0, M, P, 1, 0, 0, 0)));
     return launch_stats_accumulate(ctx, X, Y, n, ldx, ldy, M, P, row0, n_train_global, stats);
 }
@@ -349,6 +367,7 @@ extern "C" int abc_pls_model_dev(abc_ctx* ctx, const double* stats, const double
 extern "C" int abc_pls_wilcoxon_dev(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy,
                                     size_t M, size_t P, size_t A, size_t row_test, double* model) {
     CHECK_CTX(ctx);
+    CHECK_COLS(ctx, "abc_pls_wilcoxon_dev", n, ldx, ldy, M, P);
     const size_t nt = row_test < n ? n - row_test : 0;
     ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(0, M, P, A, 0, 0, 0) + abc_wx_need(nt, P, A)));
     return launch_wilcoxon(ctx, X, Y, n, ldx, ldy, M, P, A, row_test, model);
@@ -372,6 +391,7 @@ extern "C" int abc_model_ncomp(abc_ctx* ctx, const double* model, size_t M, size
 extern "C" int abc_project_distance_dev(abc_ctx* ctx, const double* X, size_t n, size_t ldx, size_t M, size_t P,
                                         size_t A, const double* model, int simple, double* dist) {
     CHECK_CTX(ctx);
+    CHECK_COLS(ctx, "abc_project_distance_dev", n, ldx, n, M, P);      // (X only: the ldy slot gets n, which always passes)
     ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(0, M, P, A, 0, 0, 0)));
     return launch_project_distance(ctx, X, n, ldx, M, P, A, model, simple, dist);
 }
@@ -425,6 +445,8 @@ extern "C" int abc_merge_sorted_runs_dev(abc_ctx* ctx, const double* key, const 
 extern "C" int abc_gather_rows_dev(abc_ctx* ctx, const double* Y, size_t n_local, size_t ldy, size_t P,
                                    const uint64_t* idx, size_t K, uint64_t idx_base, double* theta, size_t ldt) {
     CHECK_CTX(ctx);
+    if (P > 0 && ldy < n_local) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_gather_rows_dev: ldy %zu < n_local %zu", ldy, n_local);
+    if (P > 0 && ldt < K) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_gather_rows_dev: ldt %zu < K %zu", ldt, K);
     return launch_gather_rows(ctx, Y, n_local, ldy, P, idx, K, idx_base, theta, ldt);
 }
 

@@ -1432,6 +1432,9 @@ int run_gram_grouped(abc_ctx* ctx, const double* X, const double* Y, size_t n, s
     const double** tab = (const double**)abc_ws_alloc(ctx, 96 * sizeof(double*));
     int* gmap = (int*)abc_ws_alloc(ctx, 96 * sizeof(int));
     if (!loc || !tab || !gmap) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted");
+    // k_group_scatter writes the columns of the set only: the padding columns M+P .. C16 of the sums and Gram stay zero from here,
+    // as every single-launch path leaves them (tests/test_gpu_stats.py fills the record with NaN first)
+    ABC_HIP(ctx, hipMemsetAsync(stats + LB.off_sum[0], 0, (LB.len - LB.off_sum[0]) * sizeof(double), ctx->stream));
     const size_t ws_mark = ctx->ws_off;
     for (int ga = 0; ga < ng; ga++)
         for (int gb = ga + 1; gb < ng; gb++) {

@@ -278,6 +278,13 @@ int abc_generation_dev(abc_ctx* ctx, const abc_generation_cfg* cfg, const abc_ge
  * combined by plain addition of everything after shift[]; records about different shifts are re-centred first
  * (abc_generation_sharded_dev all-gathers the ranks' records, each about its own pilot shift, and merges them). */
 size_t abc_stats_len(size_t M, size_t P);
+/* Column-major arguments of the stage entry points below (statistics, Wilcoxon reduction, projection, gather): every call with
+ * M + P == 0, with a leading dimension below the row count (ldx < n with M > 0, ldy < n with P > 0, ldt < K with P > 0)
+ * returns ABC_ERR_INVALID with a message (the gather has no M: P == 0 is a no-op there); rows [n, ld) of a column take no part
+ * in any result.  The statistics calls refuse M == 0 (ABC_ERR_INVALID): the record is built around the metrics' X'X block.
+ * n == 0 gives an all-zero record.
+ * Record entries: padding columns (M+P .. C16) are 0 in the shift, the sums and both Grams; the off-diagonal Y'Y entries
+ * are either the products or 0 (the fp64 kernels skip whole 16-column blocks that hold parameters only). */
 /* pilot shift (mean of the first min(n,256) local rows) -> stats record's shift[] */
 int abc_stats_shift_dev(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx,
                         size_t ldy, size_t M, size_t P, double* stats);

@@ -72,8 +72,22 @@ def _near_tie_ok(idx_a, idx_b, dist_full, tol=1e-9):
     (130, 128, 30, 30, 0.5),     # ... fewer rows than one work-group, 128 metrics
 ])
 def test_particle_ranking_pls(gpu_ctx, oracle, N, M, P, A, f):
-    from abcsmc_amd import abcutil
     wl, X, Y, obs = _wl(M, P, N)
+    _ranking_pls_against_oracle(gpu_ctx, oracle, X, Y, obs, f, A)
+
+
+def test_particle_ranking_pls_unrepresentative_pilot(gpu_ctx, oracle):
+    """the first 256 rows -- the rows the statistics' shift is taken from -- 1e3 sigma away from the rest (a grid-ordered first
+    set): the one-pass record then carries every value ~1e3 sigma off centre (tests/test_gpu_stats.py bounds its centred
+    covariance); the model must still hold the oracle's loadings to 1e-6"""
+    wl, X, Y, obs = _wl(32, 16, 4000)
+    X[:256] += 1e3 * X.std(axis=0)
+    Y[:256] += 1e3 * Y.std(axis=0)
+    _ranking_pls_against_oracle(gpu_ctx, oracle, np.asfortranarray(X), np.asfortranarray(Y), obs, 0.5, 8)
+
+
+def _ranking_pls_against_oracle(gpu_ctx, oracle, X, Y, obs, f, A):
+    from abcsmc_amd import abcutil
     g = abcutil.particle_ranking_PLS(X, Y, obs, f, max_comp=A, details=True, ctx=gpu_ctx)
     o = oracle.particle_ranking_pls(X, Y, obs, f, A)
     assert g["ncomp"] == o["ncomp"]
@@ -1586,7 +1600,11 @@ def _stats_record(gpu_ctx, X, Y, ntrain):
 
 @pytest.mark.parametrize("N,M,P,kind", [(200_000, 128, 16, "plain"), (400_000, 120, 8, "plain"), (231_073, 140, 20, "plain"),
                                         (240_000, 128, 16, "spikes"), (240_000, 128, 16, "heavy"), (220_000, 113, 16, "constant"),
-                                        (200_000, 144, 16, "plain"), (210_000, 112, 16, "spikes"), (2_000_000, 64, 32, "heavy"), (220_000, 100, 8, "heavy"), (240_000, 90, 20, "plain")])
+                                        (200_000, 144, 16, "plain"), (210_000, 112, 16, "spikes"), (2_000_000, 64, 32, "heavy"), (220_000, 100, 8, "heavy"), (240_000, 90, 20, "plain"),
+                                        # the (C, CY) instantiations no case above reaches: (7, 2), (8, 2), (9, 0), (9, 2), (10, 0), (10, 2), (6, 1)
+                                        (200_000, 73, 36, "plain"), (200_000, 89, 36, "plain"), (200_000, 131, 6, "plain"),
+                                        (200_000, 105, 36, "plain"), (200_000, 147, 6, "plain"), (200_000, 121, 36, "plain"),
+                                        (2_000_000, 69, 23, "plain")])
 def test_wide_gram_on_the_i8_matrix_pipe(gpu_ctx, N, M, P, kind):
     """k_gram_i8 (round 4; round 5: four rows per thread in the conversion, two sets of byte planes, one barrier per tile -- 160 columns
     leave LDS for two raw tiles instead of three, 128 columns are two whole conversion rounds; 81..96 columns take it from 2e6 rows -- the
@@ -1597,6 +1615,9 @@ def test_wide_gram_on_the_i8_matrix_pipe(gpu_ctx, N, M, P, kind):
     range (their rows go through k_gram_far in fp64), heavy tails, a column of tiny variance and a constant one; an odd row count
     (no 16-byte row pairs for the LDS-DMA staging) stays on the fp64 matrix pipe"""
     from abcsmc_amd import _lib
+    from _gram_dispatch import GRAM_I8, kernel_for
+    fam = kernel_for(M, P, N, N // 2, mode=GRAM_I8)
+    assert fam[0] == ("i8" if N % 2 == 0 else "wide"), fam
     gpu_ctx.set_gram_mode(_lib.GRAM_I8)        # (round 6: ABC_GRAM_AUTO takes this kernel from 400 000 rows per partition only)
     wl, X, Y, obs = _wl(M, P, N, 21)
     rng = np.random.default_rng(3)
@@ -2210,5 +2231,55 @@ def test_error_codes_and_messages(gpu_ctx):
                                     _lib.RULE_WILCOXON, 10, idx70.ctypes.data, None, None, None, None, None)
     assert rc == -1 and b"components" in L.abc_last_error(h)
     th = np.asfortranarray(np.random.default_rng(2).normal(size=(20, 70)))
+    _stage_argument_checks(gpu_ctx)
     # a later valid call on the same context still works
     assert abcutil.calculate_doubled_variance(th[:, :3], ctx=gpu_ctx).shape == (3,)
+
+
+def _stage_argument_checks(gpu_ctx):
+    """the stage entry points that take a leading dimension refuse one below the row count, a set without columns and (the
+    statistics) a set without metrics -- ABC_ERR_INVALID with a message, the caller's buffers untouched; n == 0 is an all-zero
+    record (tests/test_gpu_stats.py::test_stats_record_of_no_rows)"""
+    import torch
+    from abcsmc_amd import _lib
+    L = _lib.lib()
+    h = gpu_ctx.handle
+    n, M, P, A, K = 64, 4, 2, 2, 16
+    X = torch.ones(n * M + n, dtype=torch.float64, device="cuda:0")
+    Y = torch.ones(n * P + n, dtype=torch.float64, device="cuda:0")
+    stats = torch.full((L.abc_stats_len(M, P),), float("nan"), dtype=torch.float64, device="cuda:0")
+    model = torch.zeros(L.abc_model_len(M, P, A) + 8, dtype=torch.float64, device="cuda:0")
+    dist = torch.full((n,), float("nan"), dtype=torch.float64, device="cuda:0")
+    idx = torch.zeros(K, dtype=torch.int64, device="cuda:0")
+    theta = torch.full((K * P + K,), -1.0, dtype=torch.float64, device="cuda:0")
+    x, y, s = X.data_ptr(), Y.data_ptr(), stats.data_ptr()
+    torch.cuda.synchronize()
+    mp, dp, ip, tp = model.data_ptr(), dist.data_ptr(), idx.data_ptr(), theta.data_ptr()
+    bad = [
+        (lambda: L.abc_stats_shift_dev(h, x, y, n, n - 1, n, M, P, s), b"ldx"),
+        (lambda: L.abc_stats_shift_dev(h, x, y, n, n, n - 1, M, P, s), b"ldy"),
+        (lambda: L.abc_stats_shift_dev(h, x, y, n, n, n, 0, 0, s), b"no columns"),
+        (lambda: L.abc_stats_shift_dev(h, x, y, n, n, n, 0, P, s), b"M == 0"),
+        (lambda: L.abc_stats_accumulate_dev(h, x, y, n, n - 1, n, M, P, 0, n // 2, s), b"ldx"),
+        (lambda: L.abc_stats_accumulate_dev(h, x, y, n, n, 1, M, P, 0, n // 2, s), b"ldy"),
+        (lambda: L.abc_stats_accumulate_dev(h, x, y, n, n, n, 0, 0, 0, n // 2, s), b"no columns"),
+        (lambda: L.abc_stats_accumulate_dev(h, x, y, n, n, n, 0, P, 0, n // 2, s), b"M == 0"),   # (was ABC_OK, record unwritten)
+        (lambda: L.abc_pls_wilcoxon_dev(h, x, y, n, n - 1, n, M, P, A, n // 2, mp), b"ldx"),
+        (lambda: L.abc_pls_wilcoxon_dev(h, x, y, n, n, n - 2, M, P, A, n // 2, mp), b"ldy"),
+        (lambda: L.abc_pls_wilcoxon_dev(h, x, y, n, n, n, 0, 0, A, n // 2, mp), b"no columns"),
+        (lambda: L.abc_project_distance_dev(h, x, n, n - 1, M, P, A, mp, 0, dp), b"ldx"),
+        (lambda: L.abc_project_distance_dev(h, x, n, 0, M, P, A, mp, 1, dp), b"ldx"),
+        (lambda: L.abc_project_distance_dev(h, x, n, n, 0, 0, A, mp, 0, dp), b"no columns"),
+        (lambda: L.abc_gather_rows_dev(h, y, n, n - 1, P, ip, K, 0, tp, K), b"ldy"),
+        (lambda: L.abc_gather_rows_dev(h, y, n, n, P, ip, K, 0, tp, K - 1), b"ldt"),
+    ]
+    for k, (call, word) in enumerate(bad):
+        assert call() == -1, k
+        msg = L.abc_last_error(h)
+        assert word in msg, (k, msg)
+    torch.cuda.synchronize()
+    assert torch.isnan(stats).all() and torch.isnan(dist).all() and (theta == -1.0).all()
+    # leading dimensions of an empty side are not looked at (P == 0: Y unused; M == 0 with P > 0: a projection of nothing)
+    gpu_ctx.check(L.abc_stats_shift_dev(h, x, None, n, n, 0, M, 0, s))
+    gpu_ctx.check(L.abc_gather_rows_dev(h, y, n, 0, 0, idx.data_ptr(), K, 0, theta.data_ptr(), 0))
+    torch.cuda.synchronize()
