@@ -114,6 +114,9 @@ SIGNATURES = {
     "abc_rng_get": (C.c_uint32, [_vp]),
     "abc_rng_jump": (None, [_vp, _u64]),
     "abc_particle_ranking_pls": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _d, _i, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "abc_particle_ranking_pls_targets": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "abc_rank_targets_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "abc_targets_fallbacks": (_i, [_vp, _vp, _i]),
     "abc_particle_ranking_simple": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_calculate_doubled_variance": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "abc_weight_predictive_prior_uniform": (_i, [_vp, _sz, _vp]),
@@ -286,6 +289,12 @@ class Context:
         """proposals the perturbation gave up on (abc_perturb_giveups)"""
         n = C.c_uint64(0)
         self.check(lib().abc_perturb_giveups(self._h, C.byref(n), int(reset)))
+        return n.value
+
+    def targets_fallbacks(self, reset=False):
+        """targets the batched ranking recomputed by the exact single-target path (abc_targets_fallbacks)"""
+        n = C.c_uint64(0)
+        self.check(lib().abc_targets_fallbacks(self._h, C.byref(n), int(reset)))
         return n.value
 
     def set_alias_mode(self, mode):

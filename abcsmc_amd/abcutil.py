@@ -64,6 +64,65 @@ def particle_ranking_PLS(X_orig, Y_orig, target_values, training_fraction, K=Non
     return idx
 
 
+def particle_ranking_PLS_targets(X_orig, Y_orig, targets, training_fraction, K, exclude=None, max_comp=0,
+                                 rule=_lib.RULE_DEFAULT, details=False, ctx=None):
+    """particle_ranking_PLS for B observed targets at once (abc_particle_ranking_pls_targets): ONE fit shared by all of
+    them.  targets: (B, M); exclude: B row numbers (or None; -1 / 2**64 - 1 = none) never ranked for their target (the row
+    still takes part in the fit).  Returns idx (B, K): row b = the first K of particle_ranking_PLS(X, Y, targets[b]).
+    details=True: dict(idx, dist (B, K), post_mean (B, P): mean parameter row of each target's K rows, ncomp)."""
+    ctx = _ctx(ctx)
+    X, Y = _f(X_orig), _f(Y_orig)
+    T = _f(np.atleast_2d(np.asarray(targets, dtype=np.float64)))
+    N, M = X.shape
+    P = Y.shape[1]
+    B = T.shape[0]
+    if Y.shape[0] != N or T.shape[1] != M:
+        raise ValueError("shape mismatch")
+    if not (0 < training_fraction <= 1):
+        raise ValueError("training_fraction must be in (0,1]")
+    K = int(K)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude, dtype=np.int64).astype(np.uint64)
+        if ex.shape != (B,):
+            raise ValueError("exclude needs one entry per target")
+    idx = np.empty((B, K), dtype=np.uint64)
+    dist = np.empty((B, K))
+    pm = np.empty((B, P))
+    ncomp = C.c_int32(0)
+    ctx.check(lib().abc_particle_ranking_pls_targets(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
+                                                     int(max_comp), int(rule), _p(ex), K, _p(idx), _p(dist), _p(pm),
+                                                     C.addressof(ncomp)))
+    if details:
+        return dict(idx=idx, dist=dist, post_mean=pm, ncomp=ncomp.value)
+    return idx
+
+
+def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
+                       ctx=None):
+    """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
+    without replacement (numpy Generator seeded with `seed`) serve as pseudo-observed data, each ranked against the set with
+    itself excluded (the fit is shared: the row stays in it), and the posterior mean of its K nearest rows estimates its
+    parameters.  Returns dict(rows, theta (true parameters, (n_targets, P)), post_mean, pred_error (P,): per parameter
+    sum_b (post_mean_bj - theta_bj)^2 / (n_targets * Var_j(theta)), Var with n - 1 in the denominator as R's var; NaN where
+    the true values do not vary)."""
+    X, Y = _f(X_orig), _f(Y_orig)
+    N = X.shape[0]
+    n_targets = int(n_targets)
+    if not (1 <= n_targets <= N):
+        raise ValueError("n_targets must be in [1, N]")
+    rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
+    r = particle_ranking_PLS_targets(X, Y, X[rows], training_fraction, K, exclude=rows, max_comp=max_comp, rule=rule,
+                                     details=True, ctx=ctx)
+    theta = np.ascontiguousarray(Y[rows])
+    pm = r["post_mean"]
+    var = theta.var(axis=0, ddof=1) if n_targets > 1 else np.zeros(theta.shape[1])
+    sse = ((pm - theta) ** 2).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        err = np.where(var > 0, sse / (n_targets * np.where(var > 0, var, 1.0)), np.nan)
+    return dict(rows=rows, theta=theta, post_mean=pm, pred_error=err, idx=r["idx"], ncomp=r["ncomp"])
+
+
 def particle_ranking_simple(X_orig, Y_orig, target_values, K=None, details=False, ctx=None):
     """ABC::particle_ranking_simple (AbcUtil.cpp:408-421); Y_orig is unused, as in the reference."""
     ctx = _ctx(ctx)

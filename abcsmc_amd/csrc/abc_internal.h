@@ -110,6 +110,7 @@ struct abc_ctx {
     int* sel_fail_dev;       // device: the sampled-range bin selection gave up (select.hip); read by abc_select_check
     bool sel_bins_ran;       // the last launch_select_smallest took the bin path and has not been checked yet
     bool sel_force_radix;    // set by a caller that repeats its work after a failed bin selection
+    unsigned long long targets_fallbacks;   // targets of abc_rank_targets_dev that took the exact single-target path
     unsigned long long wx_moved_counts, generation_repeats;      // abc_generation_repeats
     bool wx_gather_rows;     // diagnostic (ABC_DIAG=1 ABC_WX_GATHER=1, set at context creation): the sharded generation's Wilcoxon rule by
                              // gathering the validation rows on every rank (rounds 1-4) instead of the sharded cascade
@@ -256,6 +257,11 @@ int launch_project_distance_scores(abc_ctx*, const double* X, size_t n, size_t l
 // the distances again from the scores of all rows that pass has left (S[i + sld k], row_test = 0): a repeat of the ranking on a
 // lowered component count (model[0]) without a second pass over X
 int launch_distance_from_scores(abc_ctx*, const double* S, size_t n, size_t sld, size_t M, size_t P, size_t A, const double* model, double* dist);
+// batched ranking of B targets against one fitted model (targets.hip); any_excl: exclude is given and names a row for some target
+size_t abc_targets_need(size_t N, size_t A, size_t B, size_t K, bool any_excl);
+int launch_rank_targets(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
+                        const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
+                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

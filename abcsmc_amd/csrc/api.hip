@@ -1265,3 +1265,100 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
     CHECK_CTX(ctx);
     return sample_host(ctx, rng, n, w, theta, K, P, priors, dv, 0, out, parent, seeds);
 }
+
+// ---- batched ranking of many observed targets against one fitted set (targets.hip) ------------------------------------------
+// Argument checks shared by the device and the host entry.  ex: the exclusions in host memory (NULL: none).
+static int targets_check(abc_ctx* ctx, const char* fn, size_t N, size_t M, size_t B, size_t K, const uint64_t* ex, bool* any_excl) {
+    if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
+    if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
+    if (M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no metrics (M == 0)", fn);
+    if (K > N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N = %zu", fn, K, N);
+    if (N >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: N = %zu rows (at most 2^32 - 1)", fn, N);
+    *any_excl = false;
+    if (ex)
+        for (size_t b = 0; b < B; b++) {
+            if (ex[b] == UINT64_MAX) continue;
+            if (ex[b] >= N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: exclude[%zu] = %llu is not a row (N = %zu)", fn, b,
+                                     (unsigned long long)ex[b], N);
+            *any_excl = true;
+        }
+    if (*any_excl && K > N - 1) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N - 1 = %zu with an excluded row", fn, K, N - 1);
+    return ABC_OK;
+}
+
+extern "C" int abc_rank_targets_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                    size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                    const uint64_t* exclude, size_t K, uint64_t* idx, double* dist, double* post_mean) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_rank_targets_dev";
+    if (!X || !model || !targets || !idx) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, model, targets and idx are required)", fn);
+    if (post_mean && P && !Y) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: post_mean needs Y", fn);
+    if (A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
+    if (ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, ldx, N);
+    if (ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, ldt, B);
+    if (post_mean && P && ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, ldy, N);
+    std::vector<uint64_t> ex;
+    if (exclude && B) {
+        ex.resize(B);
+        ABC_HIP(ctx, hipMemcpyAsync(ex.data(), exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    bool any_excl = false;
+    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude ? ex.data() : nullptr, &any_excl));
+    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, 1, 1, 1, K + 1, 0, 0) + abc_targets_need(N, A, B, K, any_excl)));
+    return launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, idx, dist, post_mean);
+}
+
+extern "C" int abc_particle_ranking_pls_targets(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                const uint64_t* exclude, size_t K, uint64_t* idx, double* dist, double* post_mean,
+                                                int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_particle_ranking_pls_targets";
+    if (!X || !Y || !targets || !idx) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, Y, targets and idx are required)", fn);
+    bool any_excl = false;
+    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude, &any_excl));
+    const size_t A = default_A(M, P, max_comp);
+    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, M, P, A, K + 1, 0, 0) + (N * (M + P) + M + 4) * 8 +
+                                    (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0) +
+                                    (B * M + B + 2 * B * K + B * P) * 8 + 8 * 256 + abc_targets_need(N, A, B, K, any_excl)));
+    Stage s{ctx};
+    // the fit: the single-target ranking's own path (generation_core) on an all-zero observation, whose scores are not used
+    abc_generation_io io;
+    memset(&io, 0, sizeof(io));
+    io.X = s.up(X, N * M);
+    io.Y = s.up(Y, N * P);
+    double* zobs = s.dev<double>(M);
+    io.obs = zobs;
+    io.idx = s.dev<uint64_t>(1);
+    io.dist = s.dev<double>(1);
+    if (!io.X || !io.Y || !zobs || !io.idx || !io.dist) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_HIP(ctx, hipMemsetAsync(zobs, 0, M * sizeof(double), ctx->stream));
+    abc_generation_cfg cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.N = N; cfg.M = M; cfg.P = P; cfg.K = 1; cfg.train_frac = train_frac;
+    cfg.max_comp = max_comp; cfg.rule = rule;
+    const double* model = nullptr;
+    ABC_TRY(generation_core(ctx, &cfg, &io, nullptr, ncomp, 0, &model));
+    const double* t_d = s.up(targets, B * M);
+    const uint64_t* ex_d = exclude ? s.up(exclude, B) : nullptr;
+    uint64_t* idx_d = s.dev<uint64_t>(B * K);
+    double* dist_d = dist ? s.dev<double>(B * K) : nullptr;
+    double* pm_d = (post_mean && P) ? s.dev<double>(B * P) : nullptr;
+    if (!t_d || (exclude && !ex_d) || !idx_d || (dist && !dist_d) || (post_mean && P && !pm_d))
+        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_TRY(launch_rank_targets(ctx, io.X, N, io.Y, N, N, M, P, model, A, t_d, B, B, ex_d, any_excl, K, idx_d, dist_d, pm_d));
+    s.down(idx, idx_d, B * K);
+    s.down(dist, dist_d, B * K);
+    s.down(post_mean, pm_d, B * P);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+extern "C" int abc_targets_fallbacks(abc_ctx* ctx, uint64_t* count, int reset) {
+    if (!ctx || !count) return ABC_ERR_INVALID;
+    *count = (uint64_t)ctx->targets_fallbacks;
+    if (reset) ctx->targets_fallbacks = 0;
+    return ABC_OK;
+}

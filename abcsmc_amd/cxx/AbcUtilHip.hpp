@@ -335,6 +335,19 @@ inline std::vector<size_t> particle_ranking_PLS(const Mat2D& X_orig, const Mat2D
                                                 const float_type training_fraction) {
     return particle_ranking_PLS(X_orig, Y_orig, target_values, training_fraction, component_rule(), max_components_ref());
 }
+// Many observed targets against one set (abc_particle_ranking_pls_targets): targets is B x M, one target per row.  One fit shared by
+// all targets; returns, per target, the K best rows in ascending distance -- the first K of particle_ranking_PLS for that target.
+inline std::vector<std::vector<size_t>> particle_ranking_PLS_targets(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                    const float_type train_frac, size_t K) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows();
+    std::vector<uint64_t> idx(B * K);
+    check(abc_particle_ranking_pls_targets(context(), X.data(), Y.data(), X.rows(), X.cols(), Y.cols(), targets.data(), B, train_frac,
+                                           max_components_ref(), component_rule(), nullptr, K, idx.data(), nullptr, nullptr, nullptr));
+    std::vector<std::vector<size_t>> out(B);
+    for (size_t b = 0; b < B; b++) out[b].assign(idx.begin() + b * K, idx.begin() + (b + 1) * K);
+    return out;
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

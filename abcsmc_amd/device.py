@@ -92,3 +92,30 @@ class Generation:
         if cfg.Nnext:
             self.ctx.warn_generation_giveups()
         return self
+
+
+def rank_targets(X, model, A, targets, K, Y=None, exclude=None, post_mean=False, dist=True, ctx=None):
+    """Batched ranking on the device (abc_rank_targets_dev).  X: (M, N) column-major holder (a column-slice view with a row
+    stride >= N is fine: ldx = X.stride(0)); model: a finished model record (abc_pls_model_dev [+ abc_pls_wilcoxon_dev]) for
+    (M, P, A); targets: (M, B) holder (ldt = targets.stride(0)); Y: (P, N) holder, needed for post_mean; exclude: int64 (B,)
+    (-1: none).  Returns (idx (B, K) int64, dist (B, K) or None, post_mean (B, P) or None) as device tensors."""
+    assert X.dim() == 2 and X.stride(1) == 1 and targets.dim() == 2 and targets.stride(1) == 1
+    M, N = X.shape
+    B = targets.shape[1]
+    assert targets.shape[0] == M
+    dev = X.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    P = Y.shape[0] if Y is not None else 0
+    if Y is not None:
+        assert Y.dim() == 2 and Y.shape[1] == N and (Y.stride(1) == 1 or P <= 1)
+    idx = torch.empty((B, K), dtype=torch.int64, device=dev)
+    d = torch.empty((B, K), dtype=torch.float64, device=dev) if dist else None
+    pm = torch.empty((B, P), dtype=torch.float64, device=dev) if post_mean else None
+    if exclude is not None:
+        exclude = exclude.to(device=dev, dtype=torch.int64).contiguous()
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ldy = Y.stride(0) if (Y is not None and P > 1) else N
+    ctx.check(lib().abc_rank_targets_dev(ctx.handle, X.data_ptr(), X.stride(0) if M > 1 else N, _ptr(Y), ldy, N, M, P,
+                                         model.data_ptr(), A, targets.data_ptr(), targets.stride(0) if M > 1 else B, B,
+                                         _ptr(exclude), K, idx.data_ptr(), _ptr(d), _ptr(pm)))
+    return idx, d, pm

@@ -351,6 +351,37 @@ int abc_perturb_dev(abc_ctx* ctx, const abc_rng* rng, const double* theta, size_
                     int multivariate, const double* L_or_dv, double* out, uint64_t* seeds,
                     uint64_t seed_stream_offset);
 
+/* ---- batched ranking: one fitted set, many observed targets -------------------------------------------------------------
+ * Ranks the same N rows against B observed metric vectors with ONE statistics pass, ONE fit and ONE projection (cross-validation
+ * of the ABC setup as cv4abc does it; one reference table against many data sets).  Target b's result equals, bit for bit
+ * (indices and dist bits), the first K entries of abc_particle_ranking_pls(X, Y, targets[b], ...) with the same train_frac,
+ * max_comp and rule: ascending (dist, row), ties by row, dist = sqrt(sum_{k < ncomp} (s_k - o_k)^2) as one fma chain in component
+ * order, ncomp from the model header.
+ * exclude (optional, B entries; UINT64_MAX = none): row exclude[b] is never ranked for target b, so its result equals the
+ * single call's first K + 1 rows with that row removed.  DEVIATION from a leave-one-out refit: the fit is shared by all targets
+ * and the excluded row still takes part in it (statistics, loadings, component choice); it only drops out of the ranking.
+ * Non-finite target entries are refused (ABC_ERR_INVALID).  Both calls synchronise the context's stream. */
+/* Device pointers, column-major.  model: a finished record of abc_pls_model_dev (+ abc_pls_wilcoxon_dev) for (M, P, A); its own
+ * observed scores are ignored.  targets: B x M, leading dimension ldt >= B.  idx, dist: K x B (target b's K rows contiguous at
+ * b K).  post_mean (optional): B x P row-major, post_mean[b P + j] = fp64 mean of Y[idx[b K + e], j] over e < K; Y (leading
+ * dimension ldy) is read only for it.  exclude, dist, post_mean and Y may be NULL.  ABC_ERR_INVALID (with a message) for B == 0,
+ * K == 0, K > N, K > N - 1 when a target excludes a row, an excluded row >= N other than UINT64_MAX, ldx < N, ldt < B, ldy < N
+ * (with post_mean), M == 0, A == 0, and NULL X / model / targets / idx (Y with post_mean); ABC_ERR_NOMEM when the workspace cannot
+ * be had; ABC_ERR_UNSUPPORTED for N >= 2^32. */
+int abc_rank_targets_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
+                         const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
+                         size_t K, uint64_t* idx, double* dist, double* post_mean);
+/* HOST-pointer drop-in: X N x M, Y N x P, targets B x M (ld = B), exclude B (optional); one upload, the fit of
+ * abc_particle_ranking_pls, the batched ranking, one download.  idx / dist K x B, post_mean B x P (optional), ncomp (optional). */
+int abc_particle_ranking_pls_targets(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                     const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                     const uint64_t* exclude, size_t K, uint64_t* idx, double* dist, double* post_mean,
+                                     int32_t* ncomp);
+/* Targets of the two calls above whose batched selection gave up (its sampled threshold let through fewer than K rows or more
+ * than the candidate segment holds, or a bin of the exact step outgrew LDS) and that the exact single-target path recomputed,
+ * since the context was created or the last reset.  Never changes a result. */
+int abc_targets_fallbacks(abc_ctx* ctx, uint64_t* count, int reset);
+
 /* ======================================================================================== */
 /* Multi-GPU: rows (particles) sharded over several GPUs of one node             */
 /* ======================================================================================== */
