@@ -21,6 +21,8 @@ COMM_NONE, COMM_RCCL, COMM_CALLBACKS = 0, 1, 2
 NOISE_DEVICE, NOISE_REFERENCE_STREAM = 0, 1
 WEIGHT_GAUSSIAN, WEIGHT_EPANECHNIKOV = 0, 1
 ALIAS_DEVICE, ALIAS_HOST = 0, 1
+KERNEL_EPANECHNIKOV, KERNEL_RECTANGULAR = 0, 1
+ADJ_STATUS_SKIPPED, ADJ_STATUS_RECTANGULAR = 1, 2
 
 
 class LibraryMissing(ImportError):
@@ -67,6 +69,12 @@ class ShardedCfg(C.Structure):
                 ("nnext_local", C.c_size_t), ("next0", C.c_size_t), ("Nnext_total", C.c_size_t),
                 ("train_frac", C.c_double),
                 ("max_comp", C.c_int32), ("rule", C.c_int32), ("multivariate", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AdjustOut(C.Structure):
+    """abc_adjust_out: every pointer optional (None: not written)"""
+    _fields_ = [("theta", C.c_void_p), ("weight", C.c_void_p), ("coef", C.c_void_p), ("rank", C.c_void_p),
+                ("status", C.c_void_p)]
 
 
 ALL_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -117,6 +125,10 @@ SIGNATURES = {
     "abc_particle_ranking_pls_targets": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "abc_rank_targets_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
     "abc_targets_fallbacks": (_i, [_vp, _vp, _i]),
+    "abc_rank_targets_adjust_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _vp, _vp,
+                                         _vp]),
+    "abc_particle_ranking_pls_targets_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _vp, _vp,
+                                                     _vp, _vp]),
     "abc_particle_ranking_simple": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_calculate_doubled_variance": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "abc_weight_predictive_prior_uniform": (_i, [_vp, _sz, _vp]),

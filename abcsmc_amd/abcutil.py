@@ -98,22 +98,74 @@ def particle_ranking_PLS_targets(X_orig, Y_orig, targets, training_fraction, K, 
     return idx
 
 
+_KERNELS = {"epanechnikov": _lib.KERNEL_EPANECHNIKOV, "rectangular": _lib.KERNEL_RECTANGULAR}
+
+
+def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fraction, K, exclude=None, kernel="epanechnikov",
+                                        max_comp=0, rule=_lib.RULE_DEFAULT, theta=True, ctx=None):
+    """particle_ranking_PLS_targets followed by the local-linear regression adjustment of every target's K rows on their PLS
+    scores (abc_particle_ranking_pls_targets_adjust; Beaumont, Zhang & Balding 2002; the definition is in the header).  kernel:
+    "epanechnikov" (default) or "rectangular".  Returns dict(idx (B, K), dist (B, K), theta (B, K, P): the adjusted rows, or None
+    with theta=False, weight (B, K), coef (B, A + 1, P): [b, 0] = alpha, [b, 1 + k] = beta_k, post_mean = coef[:, 0]: the
+    adjusted posterior means, rank (B,), status (B,): bit 0 a component skipped, bit 1 rectangular fallback, ncomp)."""
+    ctx = _ctx(ctx)
+    if kernel not in _KERNELS:
+        raise ValueError("kernel must be one of %s" % sorted(_KERNELS))
+    X, Y = _f(X_orig), _f(Y_orig)
+    T = _f(np.atleast_2d(np.asarray(targets, dtype=np.float64)))
+    N, M = X.shape
+    P = Y.shape[1]
+    B = T.shape[0]
+    if Y.shape[0] != N or T.shape[1] != M:
+        raise ValueError("shape mismatch")
+    if not (0 < training_fraction <= 1):
+        raise ValueError("training_fraction must be in (0,1]")
+    K = int(K)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude, dtype=np.int64).astype(np.uint64)
+        if ex.shape != (B,):
+            raise ValueError("exclude needs one entry per target")
+    A = max_comp if max_comp > 0 else min(M, P)
+    idx = np.empty((B, K), dtype=np.uint64)
+    dist = np.empty((B, K))
+    th = np.empty((B, K, P)) if theta else None
+    w = np.empty((B, K))
+    coef = np.empty((B, A + 1, P))
+    rank = np.empty(B, dtype=np.int32)
+    status = np.empty(B, dtype=np.int32)
+    out = _lib.AdjustOut(_p(th), _p(w), _p(coef), _p(rank), _p(status))
+    ncomp = C.c_int32(0)
+    ctx.check(lib().abc_particle_ranking_pls_targets_adjust(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
+                                                            int(max_comp), int(rule), _p(ex), K, _KERNELS[kernel], _p(idx),
+                                                            _p(dist), C.byref(out), C.addressof(ncomp)))
+    return dict(idx=idx, dist=dist, theta=th, weight=w, coef=coef, post_mean=coef[:, 0], rank=rank, status=status,
+                ncomp=ncomp.value)
+
+
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
-                       ctx=None):
+                       ctx=None, method="rejection", kernel="epanechnikov"):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
     without replacement (numpy Generator seeded with `seed`) serve as pseudo-observed data, each ranked against the set with
     itself excluded (the fit is shared: the row stays in it), and the posterior mean of its K nearest rows estimates its
     parameters.  Returns dict(rows, theta (true parameters, (n_targets, P)), post_mean, pred_error (P,): per parameter
     sum_b (post_mean_bj - theta_bj)^2 / (n_targets * Var_j(theta)), Var with n - 1 in the denominator as R's var; NaN where
-    the true values do not vary)."""
+    the true values do not vary).  method="loclinear": the estimate is instead the local-linear adjusted posterior mean alpha of
+    particle_ranking_PLS_targets_adjust (kernel as there), the comparison cv4abc makes between "rejection" and "loclinear"."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
     if not (1 <= n_targets <= N):
         raise ValueError("n_targets must be in [1, N]")
+    if method not in ("rejection", "loclinear"):
+        raise ValueError("method must be 'rejection' or 'loclinear'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
-    r = particle_ranking_PLS_targets(X, Y, X[rows], training_fraction, K, exclude=rows, max_comp=max_comp, rule=rule,
-                                     details=True, ctx=ctx)
+    if method == "rejection":
+        r = particle_ranking_PLS_targets(X, Y, X[rows], training_fraction, K, exclude=rows, max_comp=max_comp, rule=rule,
+                                         details=True, ctx=ctx)
+    else:
+        r = particle_ranking_PLS_targets_adjust(X, Y, X[rows], training_fraction, K, exclude=rows, kernel=kernel,
+                                                max_comp=max_comp, rule=rule, theta=False, ctx=ctx)
     theta = np.ascontiguousarray(Y[rows])
     pm = r["post_mean"]
     var = theta.var(axis=0, ddof=1) if n_targets > 1 else np.zeros(theta.shape[1])

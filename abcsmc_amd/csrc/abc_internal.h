@@ -259,9 +259,18 @@ int launch_project_distance_scores(abc_ctx*, const double* X, size_t n, size_t l
 int launch_distance_from_scores(abc_ctx*, const double* S, size_t n, size_t sld, size_t M, size_t P, size_t A, const double* model, double* dist);
 // batched ranking of B targets against one fitted model (targets.hip); any_excl: exclude is given and names a row for some target
 size_t abc_targets_need(size_t N, size_t A, size_t B, size_t K, bool any_excl);
+// keep (optional): where the ranking left the scores of every row (S[i + sld k], all A components) and the targets' scores
+// (O[b KCO + k], 0 for k >= ncomp); both stay in the arena after the return, below the caller's next allocation
+struct abc_tg_scores { const double* S; size_t sld; const double* O; int KCO; };
 int launch_rank_targets(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                         const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean);
+                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean, abc_tg_scores* keep = nullptr);
+// local-linear adjustment of the batched ranking (adjust.hip): the ranking of launch_rank_targets, then the regression of every
+// target's K retained rows on their scores; out: device pointers (abc_adjust_out), dist may be NULL
+size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K);
+int launch_rank_targets_adjust(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
+                               const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
+                               bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

@@ -69,7 +69,7 @@ size_t abc_ws_need(size_t N, size_t M, size_t P, size_t A, size_t K, size_t Kp, 
 }
 
 // ---- context ---------------------------------------------------------------------------------
-extern "C" int abc_version(void) { return 100; }
+extern "C" int abc_version(void) { return 101; }
 
 extern "C" int abc_ctx_create(int device, abc_ctx** out) {
     if (!out) return ABC_ERR_INVALID;
@@ -1351,6 +1351,104 @@ extern "C" int abc_particle_ranking_pls_targets(abc_ctx* ctx, const double* X, c
     s.down(idx, idx_d, B * K);
     s.down(dist, dist_d, B * K);
     s.down(post_mean, pm_d, B * P);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+// ---- local-linear adjustment of the batched ranking (adjust.hip) -----------------------------------------------------------
+static int adjust_check(abc_ctx* ctx, const char* fn, const double* Y, size_t ldy, size_t N, size_t A, size_t P, int kernel,
+                        const abc_adjust_out* out) {
+    if (!Y) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (Y is required)", fn);
+    if (!out) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (out is required)", fn);
+    if (kernel != ABC_KERNEL_EPANECHNIKOV && kernel != ABC_KERNEL_RECTANGULAR)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: kernel %d (0 = Epanechnikov, 1 = rectangular)", fn, kernel);
+    if (P > 0 && ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, ldy, N);
+    if (A > 64) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: A = %zu components (at most 64)", fn, A);
+    if (P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, P);
+    return ABC_OK;
+}
+
+extern "C" int abc_rank_targets_adjust_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                           size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                           const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
+                                           const abc_adjust_out* out) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_rank_targets_adjust_dev";
+    if (!X || !model || !targets || !idx) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, model, targets and idx are required)", fn);
+    if (A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
+    if (ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, ldx, N);
+    if (ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, ldt, B);
+    ABC_TRY(adjust_check(ctx, fn, Y, ldy, N, A, P, kernel, out));
+    std::vector<uint64_t> ex;
+    if (exclude && B) {
+        ex.resize(B);
+        ABC_HIP(ctx, hipMemcpyAsync(ex.data(), exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    bool any_excl = false;
+    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude ? ex.data() : nullptr, &any_excl));
+    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, 1, 1, 1, K + 1, 0, 0) + abc_targets_need(N, A, B, K, any_excl) +
+                                    abc_adjust_need(N, A, P, B, K)));
+    return launch_rank_targets_adjust(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, kernel, idx, dist,
+                                      out);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                       const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                       const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
+                                                       const abc_adjust_out* out, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_particle_ranking_pls_targets_adjust";
+    if (!X || !targets || !idx) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, Y, targets and idx are required)", fn);
+    const size_t A = default_A(M, P, max_comp);
+    ABC_TRY(adjust_check(ctx, fn, Y, N, N, A, P, kernel, out));
+    bool any_excl = false;
+    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude, &any_excl));
+    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, M, P, A, K + 1, 0, 0) + (N * (M + P) + M + 4) * 8 +
+                                    (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0) +
+                                    (B * M + B + 2 * B * K + B * (A + 1) * P + B * K * P + B * K + B) * 8 + 16 * 256 +
+                                    abc_targets_need(N, A, B, K, any_excl) + abc_adjust_need(N, A, P, B, K)));
+    Stage s{ctx};
+    // the fit: as abc_particle_ranking_pls_targets
+    abc_generation_io io;
+    memset(&io, 0, sizeof(io));
+    io.X = s.up(X, N * M);
+    io.Y = s.up(Y, N * P);
+    double* zobs = s.dev<double>(M);
+    io.obs = zobs;
+    io.idx = s.dev<uint64_t>(1);
+    io.dist = s.dev<double>(1);
+    if (!io.X || !io.Y || !zobs || !io.idx || !io.dist) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_HIP(ctx, hipMemsetAsync(zobs, 0, M * sizeof(double), ctx->stream));
+    abc_generation_cfg cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.N = N; cfg.M = M; cfg.P = P; cfg.K = 1; cfg.train_frac = train_frac;
+    cfg.max_comp = max_comp; cfg.rule = rule;
+    const double* model = nullptr;
+    ABC_TRY(generation_core(ctx, &cfg, &io, nullptr, ncomp, 0, &model));
+    const double* t_d = s.up(targets, B * M);
+    const uint64_t* ex_d = exclude ? s.up(exclude, B) : nullptr;
+    uint64_t* idx_d = s.dev<uint64_t>(B * K);
+    double* dist_d = dist ? s.dev<double>(B * K) : nullptr;
+    abc_adjust_out od;
+    od.theta = out->theta ? s.dev<double>(B * K * P + 1) : nullptr;
+    od.weight = out->weight ? s.dev<double>(B * K) : nullptr;
+    od.coef = out->coef ? s.dev<double>(B * (A + 1) * P + 1) : nullptr;
+    od.rank = out->rank ? s.dev<int32_t>(B) : nullptr;
+    od.status = out->status ? s.dev<int32_t>(B) : nullptr;
+    if (!t_d || (exclude && !ex_d) || !idx_d || (dist && !dist_d) || (out->theta && !od.theta) || (out->weight && !od.weight) ||
+        (out->coef && !od.coef) || (out->rank && !od.rank) || (out->status && !od.status))
+        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_TRY(launch_rank_targets_adjust(ctx, io.X, N, io.Y, N, N, M, P, model, A, t_d, B, B, ex_d, any_excl, K, kernel, idx_d, dist_d,
+                                       &od));
+    s.down(idx, idx_d, B * K);
+    s.down(dist, dist_d, B * K);
+    s.down(out->theta, od.theta, B * K * P);
+    s.down(out->weight, od.weight, B * K);
+    s.down(out->coef, od.coef, B * (A + 1) * P);
+    s.down(out->rank, od.rank, B);
+    s.down(out->status, od.status, B);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;

@@ -463,7 +463,7 @@ size_t abc_targets_need(size_t N, size_t A, size_t B, size_t K, bool any_excl) {
 
 int launch_rank_targets(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                         const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean) {
+                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean, abc_tg_scores* keep) {
     const ModelLayout ML = model_layout(M, P, A);
     const int kc = tg_kc(A);
     const int KCO = kc ? kc : (int)A;
@@ -479,6 +479,7 @@ int launch_rank_targets(abc_ctx* ctx, const double* X, size_t ldx, const double*
     double* dtmp = (double*)abc_ws_alloc(ctx, N * 8);
     double* Ss = (double*)abc_ws_alloc(ctx, (size_t)TG_S * KCO * 8);
     if (!O || !info || !fail || !cnt || !bad || !S || !dtmp || !Ss) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets: workspace exhausted");
+    if (keep) { keep->S = S; keep->sld = N; keep->O = O; keep->KCO = KCO; }     // (the arena keeps them past the return)
 
     // target scores; non-finite targets are refused before anything else runs
     ABC_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));

@@ -348,6 +348,42 @@ inline std::vector<std::vector<size_t>> particle_ranking_PLS_targets(const Mat2D
     for (size_t b = 0; b < B; b++) out[b].assign(idx.begin() + b * K, idx.begin() + (b + 1) * K);
     return out;
 }
+// The same ranking followed by the local-linear regression adjustment of every target's K rows on their PLS scores
+// (abc_particle_ranking_pls_targets_adjust; kernel 0 Epanechnikov, 1 rectangular).  Per target: the rows, the adjusted parameter
+// rows (K x P) and the coefficients ((A + 1) x P: row 0 = alpha, the adjusted posterior mean; row 1 + k = beta_k).
+struct TargetAdjustment {
+    std::vector<size_t> idx;
+    Mat2D theta;
+    Mat2D coef;
+    int rank = 0, status = 0;
+};
+inline std::vector<TargetAdjustment> particle_ranking_PLS_targets_adjust(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                        const float_type train_frac, size_t K, int kernel = 0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols();
+    const int mc = max_components_ref();
+    const size_t A = mc > 0 ? (size_t)mc : (M < P ? M : P);
+    std::vector<uint64_t> idx(B * K);
+    std::vector<double> th(B * K * P), cf(B * (A + 1) * P);
+    std::vector<int32_t> rank(B), status(B);
+    abc_adjust_out out = {th.data(), nullptr, cf.data(), rank.data(), status.data()};
+    check(abc_particle_ranking_pls_targets_adjust(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac, mc,
+                                                  component_rule(), nullptr, K, kernel, idx.data(), nullptr, &out, nullptr));
+    std::vector<TargetAdjustment> res(B);
+    for (size_t b = 0; b < B; b++) {
+        TargetAdjustment& r = res[b];
+        r.idx.assign(idx.begin() + b * K, idx.begin() + (b + 1) * K);
+        r.theta = Mat2D(K, P);
+        for (size_t e = 0; e < K; e++)
+            for (size_t j = 0; j < P; j++) r.theta(e, j) = th[(b * K + e) * P + j];
+        r.coef = Mat2D(A + 1, P);
+        for (size_t k = 0; k <= A; k++)
+            for (size_t j = 0; j < P; j++) r.coef(k, j) = cf[(b * (A + 1) + k) * P + j];
+        r.rank = rank[b];
+        r.status = status[b];
+    }
+    return res;
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

@@ -119,3 +119,36 @@ def rank_targets(X, model, A, targets, K, Y=None, exclude=None, post_mean=False,
                                          model.data_ptr(), A, targets.data_ptr(), targets.stride(0) if M > 1 else B, B,
                                          _ptr(exclude), K, idx.data_ptr(), _ptr(d), _ptr(pm)))
     return idx, d, pm
+
+
+def rank_targets_adjust(X, model, A, targets, K, Y, exclude=None, kernel=_lib.KERNEL_EPANECHNIKOV, theta=True, weight=True,
+                        dist=True, ctx=None):
+    """rank_targets followed by the local-linear adjustment (abc_rank_targets_adjust_dev); Y: (P, N) holder (required).
+    Returns dict(idx (B, K) int64, dist (B, K) or None, theta (B, K, P) or None, weight (B, K) or None, coef (B, A + 1, P),
+    rank (B,) int32, status (B,) int32) as device tensors."""
+    assert X.dim() == 2 and (X.stride(1) == 1 or X.shape[1] == 1)
+    assert targets.dim() == 2 and (targets.stride(1) == 1 or targets.shape[1] == 1)
+    assert Y is not None and Y.dim() == 2 and Y.shape[1] == X.shape[1] and (Y.stride(1) == 1 or Y.shape[0] <= 1)
+    M, N = X.shape
+    B = targets.shape[1]
+    P = Y.shape[0]
+    assert targets.shape[0] == M
+    dev = X.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    f64 = torch.float64
+    r = dict(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
+             dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None,
+             theta=torch.empty((B, K, P), dtype=f64, device=dev) if theta else None,
+             weight=torch.empty((B, K), dtype=f64, device=dev) if weight else None,
+             coef=torch.empty((B, A + 1, P), dtype=f64, device=dev),
+             rank=torch.empty(B, dtype=torch.int32, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev))
+    out = _lib.AdjustOut(*(r[k].data_ptr() if r[k] is not None else None for k in ("theta", "weight", "coef", "rank", "status")))
+    if exclude is not None:
+        exclude = exclude.to(device=dev, dtype=torch.int64).contiguous()
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ldy = Y.stride(0) if P > 1 else N
+    ctx.check(lib().abc_rank_targets_adjust_dev(ctx.handle, X.data_ptr(), X.stride(0) if M > 1 else N, Y.data_ptr(), ldy, N, M, P,
+                                                model.data_ptr(), A, targets.data_ptr(), targets.stride(0) if M > 1 else B, B,
+                                                _ptr(exclude), K, int(kernel), r["idx"].data_ptr(), _ptr(r["dist"]),
+                                                C.byref(out)))
+    return r

@@ -382,6 +382,45 @@ int abc_particle_ranking_pls_targets(abc_ctx* ctx, const double* X, const double
  * since the context was created or the last reset.  Never changes a result. */
 int abc_targets_fallbacks(abc_ctx* ctx, uint64_t* count, int reset);
 
+/* ---- local-linear regression adjustment of the batched ranking (Beaumont, Zhang & Balding 2002) ------------------------------
+ * The ranking of the two calls above (idx and dist bit for bit the same for the same arguments; dist may be NULL here), then for
+ * every target b a weighted regression of its K retained rows' parameters on their PLS scores.  Definition, per target:
+ *   rows e = 0..K-1 in ranking order (exclusion applied), distances d_e ascending, row numbers i_e; nc = the model's component
+ *   count; o = the target's observed scores (abc_rank_targets_dev's formula); S[i, k] = score k of row i (the ranking's own).
+ *   bandwidth   h = d_{K-1}
+ *   weights     kernel 0 (Epanechnikov): w_e = 1 - (d_e / h)^2, computed as t = d_e / h, 1 - t * t (a row at distance h weighs 0);
+ *               kernel 1 (rectangular): w_e = 1.  Kernel 0 takes the rectangular weights when h == 0 or every weight is 0 (K = 1,
+ *               for example), and sets status bit 1.
+ *   covariates  x_e[k] = S[i_e, k] - o_k, k < nc;  response theta_e = Y[i_e, :]
+ *   fit         weighted means xbar, thetabar; centred moments C = sum w (x - xbar)(x - xbar)' (nc x nc) and
+ *               c = sum w (x - xbar)(theta - thetabar)' (nc x P), from one pass shifted by the first retained row; beta = C^-1 c by
+ *               the regression sweep operator (Goodnight 1979) in component order.  Pivot k is skipped (beta_k = 0) when C_kk after
+ *               the earlier sweeps is <= 1e-10 x the original C_kk, or the original C_kk is <= 0; rank = the pivots kept.
+ *               alpha = thetabar - beta' xbar: the fitted value at the observation, the adjusted posterior mean.
+ *   adjusted    theta*_e[j] = theta_e[j] - sum_k beta_kj x_e[k], one fma chain in k order.
+ * Every reduction's order depends on (K, nc, P) only: target b's outputs are the same bits alone (B = 1), inside any batch and
+ * through either entry point (with the same model).  Limits: A <= 64, P <= 1024 (ABC_ERR_UNSUPPORTED beyond).  Argument checks
+ * are those of the ranking plus ABC_ERR_INVALID for kernel not 0 / 1, NULL Y, ldy < N and NULL out. */
+typedef struct {            /* every pointer optional (NULL: not written); device or host memory per the entry point          */
+    double*  theta;         /* (B*K) x P row-major: row b*K + e = theta*_e of target b                                        */
+    double*  weight;        /* B*K: w_e                                                                                       */
+    double*  coef;          /* B x (A+1) x P row-major: [b][0][j] = alpha_j, [b][1+k][j] = beta_kj (0 for k >= nc or skipped) */
+    int32_t* rank;          /* B: pivots kept                                                                                 */
+    int32_t* status;        /* B: bit 0 = some pivot skipped, bit 1 = rectangular fallback                                    */
+} abc_adjust_out;
+enum { ABC_KERNEL_EPANECHNIKOV = 0, ABC_KERNEL_RECTANGULAR = 1 };
+/* Device pointers (as abc_rank_targets_dev; Y required), out's members in device memory. */
+int abc_rank_targets_adjust_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
+                                const abc_adjust_out* out);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets), out's members in host memory; A = max_comp if it is positive,
+ * otherwise min(M, P). */
+int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                            const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                            const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
+                                            const abc_adjust_out* out, int32_t* ncomp);
+
 /* ======================================================================================== */
 /* Multi-GPU: rows (particles) sharded over several GPUs of one node             */
 /* ======================================================================================== */
