@@ -23,6 +23,7 @@ WEIGHT_GAUSSIAN, WEIGHT_EPANECHNIKOV = 0, 1
 ALIAS_DEVICE, ALIAS_HOST = 0, 1
 KERNEL_EPANECHNIKOV, KERNEL_RECTANGULAR = 0, 1
 ADJ_STATUS_SKIPPED, ADJ_STATUS_RECTANGULAR = 1, 2
+POSTERIOR_REJECTION, POSTERIOR_LOCLINEAR = 0, 1
 
 
 class LibraryMissing(ImportError):
@@ -77,6 +78,11 @@ class AdjustOut(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class Summary(C.Structure):
+    """abc_summary: probs (host, nq levels), truth / quant / cdf optional (memory as the entry point's other arrays)"""
+    _fields_ = [("probs", C.c_void_p), ("nq", C.c_size_t), ("truth", C.c_void_p), ("quant", C.c_void_p), ("cdf", C.c_void_p)]
+
+
 ALL_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 BROADCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -129,6 +135,12 @@ SIGNATURES = {
                                          _vp]),
     "abc_particle_ranking_pls_targets_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _vp, _vp,
                                                      _vp, _vp]),
+    "abc_rank_targets_summary_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _i, _vp,
+                                          _vp, _vp, _vp]),
+    "abc_particle_ranking_pls_targets_summary": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _i, _vp,
+                                                      _vp, _vp, _vp, _vp]),
+    "abc_weighted_summary_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    "abc_weighted_summary": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "abc_particle_ranking_simple": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_calculate_doubled_variance": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "abc_weight_predictive_prior_uniform": (_i, [_vp, _sz, _vp]),

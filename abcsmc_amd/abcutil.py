@@ -143,15 +143,92 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
                 ncomp=ncomp.value)
 
 
+_METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_LOCLINEAR}
+
+
+def _summary_arg(probs, truth, quant, cdf):
+    pr = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    return _lib.Summary(pr.ctypes.data, pr.size, _p(truth), _p(quant), _p(cdf)), pr
+
+
+def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fraction, K, probs=(0.025, 0.5, 0.975), truth=None,
+                                         method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
+                                         rule=_lib.RULE_DEFAULT, ctx=None):
+    """particle_ranking_PLS_targets followed by weighted posterior quantiles of every target's K retained rows and, with truth
+    (B, P), the posterior CDF at the truth (abc_particle_ranking_pls_targets_summary; the definition is in the header).
+    method "rejection": the rows' parameters, equal weights; "loclinear": the local-linear adjusted rows with the kernel's weights
+    (as particle_ranking_PLS_targets_adjust).  Returns dict(quant (B, nq, P): [b, q, j], cdf (B, P) or None, probs, idx (B, K),
+    dist (B, K), ncomp)."""
+    ctx = _ctx(ctx)
+    if method not in _METHODS:
+        raise ValueError("method must be one of %s" % sorted(_METHODS))
+    if kernel not in _KERNELS:
+        raise ValueError("kernel must be one of %s" % sorted(_KERNELS))
+    X, Y = _f(X_orig), _f(Y_orig)
+    T = _f(np.atleast_2d(np.asarray(targets, dtype=np.float64)))
+    N, M = X.shape
+    P = Y.shape[1]
+    B = T.shape[0]
+    if Y.shape[0] != N or T.shape[1] != M:
+        raise ValueError("shape mismatch")
+    if not (0 < training_fraction <= 1):
+        raise ValueError("training_fraction must be in (0,1]")
+    K = int(K)
+    ex = None
+    if exclude is not None:
+        ex = np.asarray(exclude, dtype=np.int64).astype(np.uint64)
+        if ex.shape != (B,):
+            raise ValueError("exclude needs one entry per target")
+    tr = None
+    if truth is not None:
+        tr = np.ascontiguousarray(np.asarray(truth, dtype=np.float64).reshape(B, P))
+    nq = np.atleast_1d(probs).size
+    idx = np.empty((B, K), dtype=np.uint64)
+    dist = np.empty((B, K))
+    quant = np.empty((B, nq, P))
+    cdf = np.empty((B, P)) if tr is not None else None
+    s, pr = _summary_arg(probs, tr, quant, cdf)
+    ncomp = C.c_int32(0)
+    ctx.check(lib().abc_particle_ranking_pls_targets_summary(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
+                                                             int(max_comp), int(rule), _p(ex), K, _METHODS[method], _KERNELS[kernel],
+                                                             _p(idx), _p(dist), None, C.byref(s), C.addressof(ncomp)))
+    return dict(quant=quant, cdf=cdf, probs=pr, idx=idx, dist=dist, ncomp=ncomp.value)
+
+
+def weighted_summary(values, weights=None, probs=(0.025, 0.5, 0.975), truth=None, ctx=None):
+    """Weighted quantiles (and the CDF at truth) of every column of values (K, P) on the device (abc_weighted_summary; the
+    definition is in the header): equal weights when weights is None; with equal weights the quantiles are NumPy's "hazen".
+    Returns dict(quant (nq, P), cdf (P,) or None)."""
+    ctx = _ctx(ctx)
+    V = _f(values)
+    if V.ndim == 1:
+        V = _f(V.reshape(-1, 1))
+    K, P = V.shape
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    if w is not None and w.size != K:
+        raise ValueError("weights needs one entry per row")
+    tr = None if truth is None else np.ascontiguousarray(np.asarray(truth, dtype=np.float64).reshape(P))
+    nq = np.atleast_1d(probs).size
+    quant = np.empty((nq, P))
+    cdf = np.empty(P) if tr is not None else None
+    s, pr = _summary_arg(probs, tr, quant, cdf)
+    ctx.check(lib().abc_weighted_summary(ctx.handle, _p(V), K, P, _p(w), C.byref(s)))
+    return dict(quant=quant, cdf=cdf)
+
+
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
-                       ctx=None, method="rejection", kernel="epanechnikov"):
+                       ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
     without replacement (numpy Generator seeded with `seed`) serve as pseudo-observed data, each ranked against the set with
     itself excluded (the fit is shared: the row stays in it), and the posterior mean of its K nearest rows estimates its
     parameters.  Returns dict(rows, theta (true parameters, (n_targets, P)), post_mean, pred_error (P,): per parameter
     sum_b (post_mean_bj - theta_bj)^2 / (n_targets * Var_j(theta)), Var with n - 1 in the denominator as R's var; NaN where
     the true values do not vary).  method="loclinear": the estimate is instead the local-linear adjusted posterior mean alpha of
-    particle_ranking_PLS_targets_adjust (kernel as there), the comparison cv4abc makes between "rejection" and "loclinear"."""
+    particle_ranking_PLS_targets_adjust (kernel as there), the comparison cv4abc makes between "rejection" and "loclinear".
+    statistic="median": the estimate (post_median instead of post_mean) and pred_error come from the posterior median (weighted
+    for loclinear), cv4abc's default.  coverage=True adds truth_cdf (n_targets, P): each left-out row's true parameter's place in
+    its own posterior (roughly uniform when calibrated), and ci95 (P,): the fraction of targets whose truth lies in
+    [Q(0.025), Q(0.975)]."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -159,20 +236,34 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
         raise ValueError("n_targets must be in [1, N]")
     if method not in ("rejection", "loclinear"):
         raise ValueError("method must be 'rejection' or 'loclinear'")
+    if statistic not in ("mean", "median"):
+        raise ValueError("statistic must be 'mean' or 'median'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
-    if method == "rejection":
+    theta = np.ascontiguousarray(Y[rows])
+    sm = None
+    if statistic == "median" or coverage:
+        sm = particle_ranking_PLS_targets_summary(X, Y, X[rows], training_fraction, K, probs=(0.5, 0.025, 0.975),
+                                                  truth=theta if coverage else None, method=method, kernel=kernel, exclude=rows,
+                                                  max_comp=max_comp, rule=rule, ctx=ctx)
+    if statistic == "median":
+        r = sm
+    elif method == "rejection":
         r = particle_ranking_PLS_targets(X, Y, X[rows], training_fraction, K, exclude=rows, max_comp=max_comp, rule=rule,
                                          details=True, ctx=ctx)
     else:
         r = particle_ranking_PLS_targets_adjust(X, Y, X[rows], training_fraction, K, exclude=rows, kernel=kernel,
                                                 max_comp=max_comp, rule=rule, theta=False, ctx=ctx)
-    theta = np.ascontiguousarray(Y[rows])
-    pm = r["post_mean"]
+    pm = sm["quant"][:, 0, :] if statistic == "median" else r["post_mean"]
     var = theta.var(axis=0, ddof=1) if n_targets > 1 else np.zeros(theta.shape[1])
     sse = ((pm - theta) ** 2).sum(axis=0)
     with np.errstate(divide="ignore", invalid="ignore"):
         err = np.where(var > 0, sse / (n_targets * np.where(var > 0, var, 1.0)), np.nan)
-    return dict(rows=rows, theta=theta, post_mean=pm, pred_error=err, idx=r["idx"], ncomp=r["ncomp"])
+    out = dict(rows=rows, theta=theta, pred_error=err, idx=r["idx"], ncomp=r["ncomp"])
+    out["post_median" if statistic == "median" else "post_mean"] = pm
+    if coverage:
+        out["truth_cdf"] = sm["cdf"]
+        out["ci95"] = ((sm["quant"][:, 1, :] <= theta) & (theta <= sm["quant"][:, 2, :])).mean(axis=0)
+    return out
 
 
 def particle_ranking_simple(X_orig, Y_orig, target_values, K=None, details=False, ctx=None):

@@ -270,7 +270,27 @@ int launch_rank_targets(abc_ctx*, const double* X, size_t ldx, const double* Y, 
 size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K);
 int launch_rank_targets_adjust(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                               bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out);
+                               bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
+                               struct abc_adj_keep* keep = nullptr);
+// weighted posterior quantiles and CDF (summary.hip).  abc_summary_need: workspace of launch_summary for B segment groups of P
+// segments of K values.  SmValues: how the values and weights of segment (b, j) are made (method 0 / 1: the ranking's rows,
+// method 2: V and w); sum: probs in host memory, truth / quant / cdf in device memory.
+struct SmValues {
+    int method;                  // 0 rejection, 1 loclinear, 2 generic
+    const uint64_t* idx;         // B x K (methods 0 and 1)
+    const double* Y;             // method 0: Y[i + ldy j]
+    size_t ldy;
+    const struct abc_adj_keep* adj;  // method 1
+    int A;
+    int kernel;
+    const double* V;             // method 2: V[e + ldv j], w[e] (NULL: 1)
+    size_t ldv;
+    const double* w;
+};
+size_t abc_summary_need(size_t B, size_t K, size_t P);
+int launch_summary(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_summary* sum);
+// generic weights (device): ABC_ERR_INVALID when one is negative or non-finite or all are zero (synchronises)
+int abc_summary_check_weights(abc_ctx*, const double* w, size_t K, const char* fn);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "abc_internal.h"
+#include "adjust_dev.h"
 
 namespace {
 
@@ -28,34 +29,6 @@ constexpr int AJ_APPLY_DBL = 4096;                          // doubles of k_adj_
 constexpr size_t AJ_PART_BYTES = (size_t)256 << 20;         // moment blocks of one batch of targets
 constexpr size_t AJ_TABLE_MAX_BYTES = (size_t)2 << 30;      // largest row-major table
 constexpr unsigned AJ_MAX_GRID_Y = 65535;
-
-// where the retained rows are read from: the table (T != NULL, row i at T + i W) or the scores and Y directly (same bits)
-struct AjSrc {
-    const double* T;
-    size_t W;
-    const double* S;
-    size_t sld;
-    const double* Y;
-    size_t ldy;
-};
-
-__device__ __forceinline__ double aj_val(const AjSrc& s, size_t i, int c, int nc) {
-    if (s.T) return s.T[i * s.W + (size_t)c];
-    return (c < nc) ? s.S[i + s.sld * (size_t)c] : s.Y[i + s.ldy * (size_t)(c - nc)];
-}
-
-// the Epanechnikov weights of a target are all 0 exactly when its first one is (d ascending, w non-increasing in d)
-__device__ __forceinline__ bool aj_fallback(const double* d, size_t K) {
-    const double h = d[K - 1];
-    if (h == 0.0) return true;
-    const double t = d[0] / h;
-    return 1.0 - t * t == 0.0;
-}
-__device__ __forceinline__ double aj_weight(double de, double h, bool rect) {
-    if (rect) return 1.0;
-    const double t = de / h;
-    return 1.0 - t * t;
-}
 
 // T[i W + c] = c < nc ? S[i + sld c] : Y[i + ldy (c - nc)]: 64 rows x 32 columns at a time through LDS
 __global__ __launch_bounds__(256) void k_adj_table(const double* __restrict__ S, size_t sld, const double* __restrict__ Y, size_t ldy,
@@ -312,10 +285,7 @@ __global__ __launch_bounds__(256) void k_adj_apply(AjSrc src, const uint64_t* __
     for (int q = t; q < nr * P; q += 256) {
         const int r = q / P, j = q % P;
         const double* x = tv + r * Wv;
-        double a = x[nc + j];
-#pragma unroll 8
-        for (int k = 0; k < nc; k++) a = fma(-bt[k * P + j], x[k], a);
-        theta[(b * K + e0 + r) * (size_t)P + j] = a;
+        theta[(b * K + e0 + r) * (size_t)P + j] = aj_adjusted(x[nc + j], [&](int k) { return x[k]; }, bt + j, (size_t)P, nc);
     }
 }
 
@@ -379,12 +349,13 @@ size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K) {
 
 int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                               bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out) {
+                               bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
+                               abc_adj_keep* keep) {
     double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
     if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
     abc_tg_scores sc;
     ABC_TRY(launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, idx, d, nullptr, &sc));
-    if (!out->theta && !out->weight && !out->coef && !out->rank && !out->status) return ABC_OK;
+    if (!keep && !out->theta && !out->weight && !out->coef && !out->rank && !out->status) return ABC_OK;
 
     double hdr = 0.0;
     ABC_HIP(ctx, hipMemcpyAsync(&hdr, model, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -429,6 +400,14 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
         ABC_HIP(ctx, hipGetLastError());
     }
 
+    if (keep) {
+        keep->src = src;
+        keep->O = sc.O;
+        keep->KCO = sc.KCO;
+        keep->nc = nc;
+        keep->coef = coef;
+        keep->dist = d;
+    }
     if (out->theta || out->weight) {
         const int Wv = nc + Pi;
         int TR = Wv > 0 ? AJ_APPLY_DBL / Wv : 64;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "abc_internal.h"
+#include "adjust_dev.h"
 
 // ---- workspace -------------------------------------------------------------------------------
 int abc_ws_reserve(abc_ctx* ctx, size_t bytes) {
@@ -69,7 +70,7 @@ size_t abc_ws_need(size_t N, size_t M, size_t P, size_t A, size_t K, size_t Kp, 
 }
 
 // ---- context ---------------------------------------------------------------------------------
-extern "C" int abc_version(void) { return 101; }
+extern "C" int abc_version(void) { return 102; }
 
 extern "C" int abc_ctx_create(int device, abc_ctx** out) {
     if (!out) return ABC_ERR_INVALID;
@@ -1449,6 +1450,224 @@ extern "C" int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const doubl
     s.down(out->coef, od.coef, B * (A + 1) * P);
     s.down(out->rank, od.rank, B);
     s.down(out->status, od.status, B);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+// ---- weighted posterior quantiles and CDF (summary.hip) -------------------------------------------------------------------
+static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
+    if (!sum) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (sum is required)", fn);
+    if (sum->nq == 0 || sum->nq > 64) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: nq = %zu levels (1 to 64)", fn, sum->nq);
+    if (!sum->probs) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (probs is required)", fn);
+    for (size_t q = 0; q < sum->nq; q++)
+        if (!(sum->probs[q] >= 0.0 && sum->probs[q] <= 1.0))
+            ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: probs[%zu] = %g is not a level in [0, 1]", fn, q, sum->probs[q]);
+    if (sum->cdf && !sum->truth) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: cdf requires truth", fn);
+    return ABC_OK;
+}
+
+static int summary_method_check(abc_ctx* ctx, const char* fn, int method) {
+    if (method != ABC_POSTERIOR_REJECTION && method != ABC_POSTERIOR_LOCLINEAR)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: method %d (0 = rejection, 1 = loclinear)", fn, method);
+    return ABC_OK;
+}
+
+// workspace of rank_summary beyond the ranking's own
+static size_t rank_summary_need(size_t N, size_t A, size_t P, size_t B, size_t K, int method) {
+    return 2 * B * K * 8 + 16 * 256 + (method == ABC_POSTERIOR_LOCLINEAR ? abc_adjust_need(N, A, P, B, K) : 0) +
+           abc_summary_need(B, K, P);
+}
+
+// the ranking (method 0) or the adjustment (method 1), then the summaries; device pointers, the workspace reserved
+static int rank_summary(abc_ctx* ctx, const char* fn, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                        size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
+                        bool any_excl, size_t K, int method, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* adj,
+                        const abc_summary* sum) {
+    uint64_t* ix = idx ? idx : (uint64_t*)abc_ws_alloc(ctx, B * K * 8);
+    double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
+    if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    SmValues sv;
+    memset(&sv, 0, sizeof(sv));
+    sv.method = method;
+    sv.idx = ix;
+    sv.Y = Y;
+    sv.ldy = ldy;
+    sv.A = (int)A;
+    sv.kernel = kernel;
+    abc_adj_keep keep;
+    if (method == ABC_POSTERIOR_REJECTION) {
+        ABC_TRY(launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, ix, d, nullptr));
+    } else {
+        abc_adjust_out od;
+        memset(&od, 0, sizeof(od));
+        if (adj) od = *adj;
+        ABC_TRY(launch_rank_targets_adjust(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, kernel, ix, d,
+                                           &od, &keep));
+        sv.adj = &keep;
+    }
+    return launch_summary(ctx, sv, B, K, P, sum);
+}
+
+extern "C" int abc_rank_targets_summary_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                            size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                            const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                            const abc_adjust_out* adj, const abc_summary* sum) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_rank_targets_summary_dev";
+    if (!X || !model || !targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, Y, model and targets are required)", fn);
+    if (A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
+    if (ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, ldx, N);
+    if (ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, ldt, B);
+    ABC_TRY(summary_method_check(ctx, fn, method));
+    const abc_adjust_out none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ABC_TRY(adjust_check(ctx, fn, Y, ldy, N, A, P, kernel, &none));
+    ABC_TRY(summary_check(ctx, fn, sum));
+    std::vector<uint64_t> ex;
+    if (exclude && B) {
+        ex.resize(B);
+        ABC_HIP(ctx, hipMemcpyAsync(ex.data(), exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    bool any_excl = false;
+    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude ? ex.data() : nullptr, &any_excl));
+    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, 1, 1, 1, K + 1, 0, 0) + abc_targets_need(N, A, B, K, any_excl) +
+                                    rank_summary_need(N, A, P, B, K, method)));
+    return rank_summary(ctx, fn, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, method, kernel, idx, dist,
+                        method == ABC_POSTERIOR_LOCLINEAR ? adj : nullptr, sum);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_summary(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                        const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                        const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                                        double* dist, const abc_adjust_out* adj, const abc_summary* sum,
+                                                        int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_particle_ranking_pls_targets_summary";
+    if (!X || !targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, Y and targets are required)", fn);
+    ABC_TRY(summary_method_check(ctx, fn, method));
+    const size_t A = default_A(M, P, max_comp);
+    const abc_adjust_out none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ABC_TRY(adjust_check(ctx, fn, Y, N, N, A, P, kernel, &none));
+    ABC_TRY(summary_check(ctx, fn, sum));
+    bool any_excl = false;
+    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude, &any_excl));
+    const bool ll = method == ABC_POSTERIOR_LOCLINEAR;
+    const abc_adjust_out* ah = ll ? adj : nullptr;
+    const size_t nq = sum->nq;
+    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, M, P, A, K + 1, 0, 0) + (N * (M + P) + M + 4) * 8 +
+                                    (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0) +
+                                    (B * M + B + 2 * B * K + B * (A + 1) * P + B * K * P + B * K + B + B * P * (nq + 2)) * 8 +
+                                    32 * 256 + abc_targets_need(N, A, B, K, any_excl) + rank_summary_need(N, A, P, B, K, method)));
+    Stage s{ctx};
+    // the fit: as abc_particle_ranking_pls_targets
+    abc_generation_io io;
+    memset(&io, 0, sizeof(io));
+    io.X = s.up(X, N * M);
+    io.Y = s.up(Y, N * P);
+    double* zobs = s.dev<double>(M);
+    io.obs = zobs;
+    io.idx = s.dev<uint64_t>(1);
+    io.dist = s.dev<double>(1);
+    if (!io.X || !io.Y || !zobs || !io.idx || !io.dist) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_HIP(ctx, hipMemsetAsync(zobs, 0, M * sizeof(double), ctx->stream));
+    abc_generation_cfg cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.N = N; cfg.M = M; cfg.P = P; cfg.K = 1; cfg.train_frac = train_frac;
+    cfg.max_comp = max_comp; cfg.rule = rule;
+    const double* model = nullptr;
+    ABC_TRY(generation_core(ctx, &cfg, &io, nullptr, ncomp, 0, &model));
+    const double* t_d = s.up(targets, B * M);
+    const uint64_t* ex_d = exclude ? s.up(exclude, B) : nullptr;
+    uint64_t* idx_d = idx ? s.dev<uint64_t>(B * K) : nullptr;
+    double* dist_d = dist ? s.dev<double>(B * K) : nullptr;
+    abc_adjust_out od;
+    memset(&od, 0, sizeof(od));
+    if (ah) {
+        od.theta = ah->theta ? s.dev<double>(B * K * P + 1) : nullptr;
+        od.weight = ah->weight ? s.dev<double>(B * K) : nullptr;
+        od.coef = ah->coef ? s.dev<double>(B * (A + 1) * P + 1) : nullptr;
+        od.rank = ah->rank ? s.dev<int32_t>(B) : nullptr;
+        od.status = ah->status ? s.dev<int32_t>(B) : nullptr;
+    }
+    abc_summary sd = *sum;
+    sd.truth = sum->truth ? s.up(sum->truth, B * P) : nullptr;
+    sd.quant = sum->quant ? s.dev<double>(B * nq * P) : nullptr;
+    sd.cdf = sum->cdf ? s.dev<double>(B * P) : nullptr;
+    if (!t_d || (exclude && !ex_d) || (idx && !idx_d) || (dist && !dist_d) || (ah && ah->theta && !od.theta) ||
+        (ah && ah->weight && !od.weight) || (ah && ah->coef && !od.coef) || (ah && ah->rank && !od.rank) ||
+        (ah && ah->status && !od.status) || (sum->truth && !sd.truth) || (sum->quant && !sd.quant) || (sum->cdf && !sd.cdf))
+        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_TRY(rank_summary(ctx, fn, io.X, N, io.Y, N, N, M, P, model, A, t_d, B, B, ex_d, any_excl, K, method, kernel, idx_d, dist_d,
+                         ah ? &od : nullptr, &sd));
+    s.down(idx, idx_d, B * K);
+    s.down(dist, dist_d, B * K);
+    if (ah) {
+        s.down(ah->theta, od.theta, B * K * P);
+        s.down(ah->weight, od.weight, B * K);
+        s.down(ah->coef, od.coef, B * (A + 1) * P);
+        s.down(ah->rank, od.rank, B);
+        s.down(ah->status, od.status, B);
+    }
+    s.down(sum->quant, sd.quant, B * nq * P);
+    s.down(sum->cdf, sd.cdf, B * P);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+static int weighted_summary_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P,
+                                  const abc_summary* sum) {
+    if (!V) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (V is required)", fn);
+    if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
+    if (P == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: P == 0", fn);
+    if (ldv < K) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldv %zu < K %zu", fn, ldv, K);
+    if (P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, P);
+    if (K >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: K = %zu values (at most 2^32 - 1)", fn, K);
+    return summary_check(ctx, fn, sum);
+}
+
+extern "C" int abc_weighted_summary_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
+                                        const abc_summary* sum) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_weighted_summary_dev";
+    ABC_TRY(weighted_summary_check(ctx, fn, V, ldv, K, P, sum));
+    ABC_TRY(abc_ws_reserve(ctx, abc_summary_need(1, K, P) + 16 * 256));
+    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
+    SmValues sv;
+    memset(&sv, 0, sizeof(sv));
+    sv.method = 2;
+    sv.V = V;
+    sv.ldv = ldv;
+    sv.w = w;
+    return launch_summary(ctx, sv, 1, K, P, sum);
+}
+
+extern "C" int abc_weighted_summary(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_summary* sum) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_weighted_summary";
+    ABC_TRY(weighted_summary_check(ctx, fn, V, K, K, P, sum));
+    const size_t nq = sum->nq;
+    ABC_TRY(abc_ws_reserve(ctx, abc_summary_need(1, K, P) + (K * P + K + P * (nq + 2)) * 8 + 32 * 256));
+    Stage s{ctx};
+    const double* V_d = s.up(V, K * P);
+    const double* w_d = w ? s.up(w, K) : nullptr;
+    abc_summary sd = *sum;
+    sd.truth = sum->truth ? s.up(sum->truth, P) : nullptr;
+    sd.quant = sum->quant ? s.dev<double>(nq * P) : nullptr;
+    sd.cdf = sum->cdf ? s.dev<double>(P) : nullptr;
+    if (!V_d || (w && !w_d) || (sum->truth && !sd.truth) || (sum->quant && !sd.quant) || (sum->cdf && !sd.cdf))
+        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
+    SmValues sv;
+    memset(&sv, 0, sizeof(sv));
+    sv.method = 2;
+    sv.V = V_d;
+    sv.ldv = K;
+    sv.w = w_d;
+    ABC_TRY(launch_summary(ctx, sv, 1, K, P, &sd));
+    s.down(sum->quant, sd.quant, nq * P);
+    s.down(sum->cdf, sd.cdf, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;

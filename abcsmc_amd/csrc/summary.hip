@@ -1,0 +1,453 @@
+// Weighted posterior quantiles and CDF of segments (abc_rank_targets_summary_dev, abc_weighted_summary_dev; the definition is in
+// the header).  A segment is one (target b, parameter j): K values made in registers from the ranking's rows (Y, or the adjusted
+// value theta* of adjust_dev.h, which k_adj_apply computes with the same function), or read from a given matrix.
+//
+// The key of a value is its order-preserving 64-bit image (IEEE totalOrder); an entry of weight 0 gets the key ~0 and sorts
+// behind every finite value.  A segment's entries are sorted by (key, e), then one pass in tiles of SM_TILE sorted entries makes
+// the running weight sums and the knots' numerators H_r = fma(-0.5, om_r, W_r), and the CDF's sums L and E; every level q is
+// then one binary search over the knots.
+//   LDS path    (K <= SM_LDS_MAX)  k_sm_lds: one work-group per segment; keys and e sorted by a bitonic sort in LDS, the knots
+//                                  written over the sorted e
+//   global path (larger K)         k_sm_chunk sorts chunks of SM_LDS_MAX entries in LDS the same way and writes them out,
+//                                  k_sm_merge merges runs pairwise (an entry's place is its rank in its own run plus its rank in
+//                                  the partner run: (key, e) is unique within a segment), k_sm_eval_global evaluates as above
+// The sums run in an order fixed by the tile (SM_TILE entries, SM_PER consecutive ones per thread, a fixed scan and tree over the
+// threads, tiles in order) and nothing else, so both paths give the same bits for any weights, a target's bits do not depend on the
+// batch, and no floating-point atomics are involved.
+#include <math.h>
+
+#include "abc_internal.h"
+#include "adjust_dev.h"
+
+namespace {
+
+constexpr int SM_BS = 512;                                  // threads of every summary work-group
+constexpr int SM_PER = 16;                                  // consecutive sorted entries per thread and tile
+constexpr int SM_TILE = SM_BS * SM_PER;                     // 8192
+constexpr int SM_LDS_MAX = 8192;                            // largest K of the LDS path; also the chunk of the global path
+constexpr int SM_MAXQ = 64;
+constexpr size_t SM_WS_BYTES = (size_t)256 << 20;           // sort buffers of one batch of targets (global path)
+constexpr unsigned SM_MAX_GRID_Y = 65535;
+constexpr unsigned long long SM_PAD_KEY = ~0ull;
+constexpr unsigned SM_PAD_ID = 0xFFFFFFFFu;
+
+struct SmProbs {
+    double q[SM_MAXQ];
+    int nq;
+};
+
+// what a kernel needs to make the values and weights of segment (b0 + blockIdx.y, j) and to write its outputs
+struct SmArgs {
+    int method;                 // 0 rejection, 1 loclinear, 2 generic
+    const uint64_t* idx;        // B x K
+    const double* Y;
+    size_t ldy;
+    AjSrc src;                  // method 1: as launch_rank_targets_adjust read the rows
+    const double* O;
+    int KCO, nc, A, P, kernel;
+    const double* coef;
+    const double* dist;
+    const double* V;            // method 2
+    size_t ldv;
+    const double* w;
+    size_t K;
+    const double* truth;        // B x P (device)
+    double* quant;              // B x nq x P
+    double* cdf;                // B x P
+};
+
+struct SmSeg {
+    size_t b;
+    int j;
+    const uint64_t* ix;
+    const double* dd;
+    double h;
+    bool rect;
+    const double* beta;         // method 1: beta_kj at beta[k P]
+    const double* ob;           // method 1: the target's scores
+};
+
+__device__ __forceinline__ SmSeg sm_seg(const SmArgs& a, size_t b, int j) {
+    SmSeg s;
+    s.b = b;
+    s.j = j;
+    s.ix = a.idx ? a.idx + b * a.K : nullptr;
+    s.dd = nullptr;
+    s.h = 0.0;
+    s.rect = true;
+    s.beta = nullptr;
+    s.ob = nullptr;
+    if (a.method == 1) {
+        s.dd = a.dist + b * a.K;
+        s.h = s.dd[a.K - 1];
+        s.rect = a.kernel == 1 || aj_fallback(s.dd, a.K);
+        s.beta = a.coef + b * (size_t)(a.A + 1) * a.P + a.P + j;
+        s.ob = a.O + b * (size_t)a.KCO;
+    }
+    return s;
+}
+
+__device__ __forceinline__ double sm_value(const SmArgs& a, const SmSeg& s, size_t e) {
+    if (a.method == 0) return a.Y[(size_t)s.ix[e] + a.ldy * (size_t)s.j];
+    if (a.method == 1) {
+        const size_t i = (size_t)s.ix[e];
+        const int nc = a.nc;
+        return aj_adjusted(aj_val(a.src, i, nc + s.j, nc), [&](int k) { return aj_val(a.src, i, k, nc) - s.ob[k]; }, s.beta,
+                           (size_t)a.P, nc);
+    }
+    return a.V[e + a.ldv * (size_t)s.j];
+}
+
+__device__ __forceinline__ double sm_weight(const SmArgs& a, const SmSeg& s, size_t e) {
+    if (a.method == 1) return aj_weight(s.dd[e], s.h, s.rect);
+    if (a.method == 2 && a.w) return a.w[e];
+    return 1.0;
+}
+
+__device__ __forceinline__ unsigned long long sm_key(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | (1ull << 63));
+}
+__device__ __forceinline__ double sm_unkey(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
+}
+__device__ __forceinline__ bool sm_less(unsigned long long ka, unsigned ia, unsigned long long kb, unsigned ib) {
+    return ka < kb || (ka == kb && ia < ib);
+}
+
+// entries e0 .. e0 + len - 1 of the segment as (key, e) pairs in key[0..n2) / id[0..n2) (n2 a power of two >= len, padding behind),
+// sorted ascending by a bitonic sort; the count of positive weights and a non-finite flag added to *cnt / *bad
+__device__ void sm_build_sort(const SmArgs& a, const SmSeg& s, size_t e0, int len, int n2, unsigned long long* key, unsigned* id,
+                              unsigned* cnt, int* bad) {
+    const int t = threadIdx.x;
+    unsigned c = 0;
+    int nf = 0;
+    for (int r = t; r < n2; r += SM_BS) {
+        unsigned long long k = SM_PAD_KEY;
+        unsigned i = SM_PAD_ID;
+        if (r < len) {
+            const size_t e = e0 + (size_t)r;
+            const double v = sm_value(a, s, e);
+            if (!isfinite(v)) nf = 1;
+            i = (unsigned)e;
+            if (sm_weight(a, s, e) > 0.0) {
+                k = sm_key(v);
+                c++;
+            }
+        }
+        key[r] = k;
+        id[r] = i;
+    }
+    if (c) atomicAdd(cnt, c);
+    if (nf) atomicOr(bad, 1);
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1)
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            for (int p = t; p < n2 / 2; p += SM_BS) {
+                const int i = (p / jj) * 2 * jj + (p % jj), l = i + jj;
+                const bool asc = (i & k) == 0;
+                const unsigned long long ki = key[i], kl = key[l];
+                const unsigned ii = id[i], il = id[l];
+                if (sm_less(kl, il, ki, ii) == asc) {
+                    key[i] = kl; key[l] = ki;
+                    id[i] = il; id[l] = ii;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// the evaluation of one segment from its n sorted entries with positive weight (key[r], id[r]); H (n entries) receives the knots'
+// numerators and may overlay id from byte 0 of id (the LDS path; only one tile there).  red: 3 x SM_BS doubles of LDS.
+__device__ void sm_eval(const SmArgs& a, const SmSeg& s, const SmProbs& pr, const unsigned long long* key, const unsigned* id,
+                        double* H, size_t n, bool bad, double* red) {
+    const int t = threadIdx.x;
+    double* scan = red;
+    double* rl = red + SM_BS;
+    double* re = red + 2 * SM_BS;
+    const double tau = a.cdf ? a.truth[s.b * a.P + s.j] : 0.0;
+    double carry = 0.0, L = 0.0, E = 0.0;
+    for (size_t base = 0; base < n; base += SM_TILE) {
+        const size_t r0 = base + (size_t)t * SM_PER;
+        double om[SM_PER], inc[SM_PER];
+        double acc = 0.0, lt = 0.0, et = 0.0;
+#pragma unroll
+        for (int q = 0; q < SM_PER; q++) {
+            const size_t r = r0 + q;
+            om[q] = 0.0;
+            if (r < n) {
+                om[q] = sm_weight(a, s, (size_t)id[r]);
+                const double u = sm_unkey(key[r]);
+                if (u < tau) lt += om[q];
+                else if (u == tau) et += om[q];
+            }
+            acc += om[q];
+            inc[q] = acc;
+        }
+        scan[t] = acc;
+        rl[t] = lt;
+        re[t] = et;
+        __syncthreads();                                       // (also: every id of the tile is read before H is written)
+        for (int off = 1; off < SM_BS; off <<= 1) {
+            const double v = (t >= off) ? scan[t - off] : 0.0;
+            __syncthreads();
+            scan[t] += v;
+            __syncthreads();
+        }
+        for (int st = SM_BS / 2; st > 0; st >>= 1) {
+            if (t < st) {
+                rl[t] += rl[t + st];
+                re[t] += re[t + st];
+            }
+            __syncthreads();
+        }
+        const double off = carry + ((t > 0) ? scan[t - 1] : 0.0);
+#pragma unroll
+        for (int q = 0; q < SM_PER; q++) {
+            const size_t r = r0 + q;
+            if (r < n) H[r] = fma(-0.5, om[q], off + inc[q]);
+        }
+        carry += scan[SM_BS - 1];
+        L += rl[0];
+        E += re[0];
+        __syncthreads();                                       // scan / rl / re read before the next tile writes them
+    }
+    __syncthreads();                                           // H complete
+    const double W = carry;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int qi = t; qi < pr.nq; qi += SM_BS) {
+        const double q = pr.q[qi];
+        double res;
+        if (bad || n == 0) {
+            res = nan;
+        } else if (q <= H[0] / W) {
+            res = sm_unkey(key[0]);
+        } else if (q >= H[n - 1] / W) {
+            res = sm_unkey(key[n - 1]);
+        } else {                                               // p_lo <= q < p_hi
+            size_t lo = 0, hi = n - 1;
+            while (hi - lo > 1) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (H[mid] / W <= q) lo = mid; else hi = mid;
+            }
+            const double plo = H[lo] / W, phi = H[hi] / W;
+            const double tt = (q - plo) / (phi - plo);
+            const double ulo = sm_unkey(key[lo]), uhi = sm_unkey(key[hi]);
+            res = fma(tt, uhi - ulo, ulo);
+        }
+        if (a.quant) a.quant[(s.b * (size_t)pr.nq + qi) * a.P + s.j] = res;
+    }
+    if (a.cdf && t == 0) a.cdf[s.b * a.P + s.j] = (bad || n == 0 || isnan(tau)) ? nan : fma(0.5, E, L) / W;
+}
+
+// LDS path: grid (P, targets b0 + blockIdx.y); dynamic LDS 16 n2 bytes: keys (8 n2), then e (4 n2) overlaid by H (8 n2)
+__global__ __launch_bounds__(SM_BS) void k_sm_lds(SmArgs a, SmProbs pr, int n2, size_t b0) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long smk[];
+    __shared__ double red[3 * SM_BS];
+    __shared__ unsigned s_cnt;
+    __shared__ int s_bad;
+    unsigned long long* key = smk;
+    unsigned* id = (unsigned*)(smk + n2);
+    double* H = (double*)(smk + n2);
+    if (threadIdx.x == 0) { s_cnt = 0; s_bad = 0; }
+    __syncthreads();
+    const SmSeg s = sm_seg(a, b0 + blockIdx.y, (int)blockIdx.x);
+    sm_build_sort(a, s, 0, (int)a.K, n2, key, id, &s_cnt, &s_bad);
+    sm_eval(a, s, pr, key, id, H, (size_t)s_cnt, s_bad != 0, red);
+}
+
+// global path, 1: grid (chunks x P, batch targets); chunk c of segment (bl, j) sorted in LDS and written to key / id at
+// seg K + c SM_LDS_MAX, seg = bl P + j; positive weights counted into cnt[seg], non-finite values flagged in bad[seg]
+__global__ __launch_bounds__(SM_BS) void k_sm_chunk(SmArgs a, size_t b0, unsigned long long* __restrict__ gkey, unsigned* __restrict__ gid,
+                                                    unsigned* __restrict__ cnt, int* __restrict__ bad) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long key[];   // SM_LDS_MAX keys, then SM_LDS_MAX e
+    unsigned* id = (unsigned*)(key + SM_LDS_MAX);
+    const int j = (int)(blockIdx.x % (unsigned)a.P);
+    const size_t c = blockIdx.x / (unsigned)a.P, bl = blockIdx.y;
+    const size_t e0 = c * SM_LDS_MAX;
+    const int len = (a.K - e0 < (size_t)SM_LDS_MAX) ? (int)(a.K - e0) : SM_LDS_MAX;
+    int n2 = 1;
+    while (n2 < len) n2 <<= 1;
+    const size_t seg = bl * a.P + j;
+    const SmSeg s = sm_seg(a, b0 + bl, j);
+    sm_build_sort(a, s, e0, len, n2, key, id, cnt + seg, bad + seg);
+    unsigned long long* ok = gkey + seg * a.K + e0;
+    unsigned* oi = gid + seg * a.K + e0;
+    for (int r = threadIdx.x; r < len; r += SM_BS) {
+        ok[r] = key[r];
+        oi[r] = id[r];
+    }
+}
+
+// global path, 2: runs of w entries of every segment merged pairwise (in -> out), one thread per entry
+__global__ __launch_bounds__(256) void k_sm_merge(const unsigned long long* __restrict__ ik, const unsigned* __restrict__ ii, size_t K,
+                                                  size_t total, size_t w, unsigned long long* __restrict__ okey,
+                                                  unsigned* __restrict__ oid) {
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (size_t)gridDim.x * 256) {
+        const size_t seg = g / K, i = g % K, run = i / w, start = run * w, ps = (run ^ 1) * w;
+        const unsigned long long k = ik[g];
+        const unsigned d = ii[g];
+        size_t pos = i;
+        if (ps < K) {
+            const size_t pe = (ps + w < K) ? ps + w : K;
+            const unsigned long long* pk = ik + seg * K;
+            const unsigned* pi = ii + seg * K;
+            size_t lo = ps, hi = pe;                            // entries of the partner run below (k, d)
+            while (lo < hi) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (sm_less(pk[mid], pi[mid], k, d)) lo = mid + 1; else hi = mid;
+            }
+            pos = (start < ps ? start : ps) + (i - start) + (lo - ps);
+        }
+        okey[seg * K + pos] = k;
+        oid[seg * K + pos] = d;
+    }
+}
+
+// global path, 3: grid (P, batch targets); H: the other key buffer
+__global__ __launch_bounds__(SM_BS) void k_sm_eval_global(SmArgs a, SmProbs pr, size_t b0, const unsigned long long* __restrict__ gkey,
+                                                          const unsigned* __restrict__ gid, double* __restrict__ gH,
+                                                          const unsigned* __restrict__ cnt, const int* __restrict__ bad) {
+    __shared__ double red[3 * SM_BS];
+    const int j = (int)blockIdx.x;
+    const size_t bl = blockIdx.y, seg = bl * a.P + j;
+    const SmSeg s = sm_seg(a, b0 + bl, j);
+    sm_eval(a, s, pr, gkey + seg * a.K, gid + seg * a.K, gH + seg * a.K, (size_t)cnt[seg], bad[seg] != 0, red);
+}
+
+// generic weights: flags[0] |= 1 for a negative or non-finite weight, flags[1] |= 1 for a positive one
+__global__ __launch_bounds__(256) void k_sm_wcheck(const double* __restrict__ w, size_t K, int* __restrict__ flags) {
+    int neg = 0, pos = 0;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < K; e += (size_t)gridDim.x * 256) {
+        const double v = w[e];
+        if (!(v >= 0.0) || !isfinite(v)) neg = 1;
+        else if (v > 0.0) pos = 1;
+    }
+    if (neg) atomicOr(flags, 1);
+    if (pos) atomicOr(flags + 1, 1);
+}
+
+// the LDS path up to SM_LDS_MAX (a work-group's sort and knots in 16 K bytes of LDS); diagnostic switch ABC_SUMMARY_PATH=lds / global
+// (ABC_DIAG=1) forces a path
+bool sm_use_lds(size_t K) {
+    if (const char* e = abc_diag_env("ABC_SUMMARY_PATH")) {
+        if (!strcmp(e, "lds")) return K <= (size_t)SM_LDS_MAX;
+        if (!strcmp(e, "global")) return false;
+    }
+    return K <= (size_t)SM_LDS_MAX;
+}
+
+size_t sm_batch(size_t B, size_t K, size_t P) {
+    size_t bb = SM_WS_BYTES / (P * K * 24);
+    if (bb < 1) bb = 1;
+    if (bb > SM_MAX_GRID_Y) bb = SM_MAX_GRID_Y;
+    return bb < B ? bb : B;
+}
+
+}  // namespace
+
+size_t abc_summary_need(size_t B, size_t K, size_t P) {
+    size_t b = 16 * 256;
+    if (!sm_use_lds(K)) {
+        const size_t bb = sm_batch(B, K, P), ns = bb * P;
+        b += 2 * ns * K * 8 + 2 * ns * K * 4 + 2 * ns * 4 + 8 * 256;
+    }
+    return b;
+}
+
+int launch_summary(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const abc_summary* sum) {
+    if ((!sum->quant && !sum->cdf) || B == 0 || K == 0 || P == 0) return ABC_OK;
+    SmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.method = sv.method;
+    a.idx = sv.idx;
+    a.Y = sv.Y;
+    a.ldy = sv.ldy;
+    a.A = sv.A;
+    a.P = (int)P;
+    a.kernel = sv.kernel;
+    if (sv.method == 1) {
+        a.src = sv.adj->src;
+        a.O = sv.adj->O;
+        a.KCO = sv.adj->KCO;
+        a.nc = sv.adj->nc;
+        a.coef = sv.adj->coef;
+        a.dist = sv.adj->dist;
+    }
+    a.V = sv.V;
+    a.ldv = sv.ldv;
+    a.w = sv.w;
+    a.K = K;
+    a.truth = sum->truth;
+    a.quant = sum->quant;
+    a.cdf = sum->cdf;
+    SmProbs pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.nq = (int)sum->nq;
+    for (size_t q = 0; q < sum->nq; q++) pr.q[q] = sum->probs[q];
+
+    if (sm_use_lds(K)) {
+        int n2 = 1;
+        while ((size_t)n2 < K) n2 <<= 1;
+        const size_t lds = (size_t)n2 * 16;
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_sm_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        for (size_t b0 = 0; b0 < B; b0 += SM_MAX_GRID_Y) {
+            const size_t nb = (B - b0 < SM_MAX_GRID_Y) ? B - b0 : SM_MAX_GRID_Y;
+            hipLaunchKernelGGL(k_sm_lds, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, n2, b0);
+            ABC_HIP(ctx, hipGetLastError());
+        }
+        return ABC_OK;
+    }
+
+    const size_t bb = sm_batch(B, K, P), ns = bb * P;
+    unsigned long long* k0 = (unsigned long long*)abc_ws_alloc(ctx, ns * K * 8);
+    unsigned long long* k1 = (unsigned long long*)abc_ws_alloc(ctx, ns * K * 8);
+    unsigned* i0 = (unsigned*)abc_ws_alloc(ctx, ns * K * 4);
+    unsigned* i1 = (unsigned*)abc_ws_alloc(ctx, ns * K * 4);
+    unsigned* cnt = (unsigned*)abc_ws_alloc(ctx, ns * 4);
+    int* bad = (int*)abc_ws_alloc(ctx, ns * 4);
+    if (!k0 || !k1 || !i0 || !i1 || !cnt || !bad) ABC_FAIL(ctx, ABC_ERR_NOMEM, "summary: workspace exhausted");
+    const size_t nch = (K + SM_LDS_MAX - 1) / SM_LDS_MAX;
+    const size_t lds_c = (size_t)SM_LDS_MAX * 12;
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_sm_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+    for (size_t b0 = 0; b0 < B; b0 += bb) {
+        const size_t nb = (B - b0 < bb) ? B - b0 : bb, nseg = nb * P, total = nseg * K;
+        ABC_HIP(ctx, hipMemsetAsync(cnt, 0, nseg * 4, ctx->stream));
+        ABC_HIP(ctx, hipMemsetAsync(bad, 0, nseg * 4, ctx->stream));
+        hipLaunchKernelGGL(k_sm_chunk, dim3((unsigned)(nch * P), (unsigned)nb), dim3(SM_BS), lds_c, ctx->stream, a, b0, k0, i0, cnt, bad);
+        ABC_HIP(ctx, hipGetLastError());
+        unsigned long long *ka = k0, *kb = k1;
+        unsigned *ia = i0, *ib = i1;
+        size_t blocks = (total + 255) / 256;
+        if (blocks > 16384) blocks = 16384;
+        for (size_t w = SM_LDS_MAX; w < K; w *= 2) {
+            hipLaunchKernelGGL(k_sm_merge, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const unsigned long long*)ka,
+                               (const unsigned*)ia, K, total, w, kb, ib);
+            ABC_HIP(ctx, hipGetLastError());
+            unsigned long long* tk = ka; ka = kb; kb = tk;
+            unsigned* ti = ia; ia = ib; ib = ti;
+        }
+        hipLaunchKernelGGL(k_sm_eval_global, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), 0, ctx->stream, a, pr, b0,
+                           (const unsigned long long*)ka, (const unsigned*)ia, (double*)kb, (const unsigned*)cnt, (const int*)bad);
+        ABC_HIP(ctx, hipGetLastError());
+    }
+    return ABC_OK;
+}
+
+int abc_summary_check_weights(abc_ctx* ctx, const double* w, size_t K, const char* fn) {
+    int* flags = (int*)abc_ws_alloc(ctx, 2 * sizeof(int));
+    if (!flags) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_HIP(ctx, hipMemsetAsync(flags, 0, 2 * sizeof(int), ctx->stream));
+    size_t blocks = (K + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_sm_wcheck, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, w, K, flags);
+    ABC_HIP(ctx, hipGetLastError());
+    int h[2] = {0, 0};
+    ABC_HIP(ctx, hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h[0]) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: a weight is negative or non-finite", fn);
+    if (!h[1]) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every weight is zero", fn);
+    return ABC_OK;
+}
+
+static_assert(SM_TILE == SM_LDS_MAX, "the LDS path evaluates its segment in one tile");

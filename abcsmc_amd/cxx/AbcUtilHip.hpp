@@ -384,6 +384,52 @@ inline std::vector<TargetAdjustment> particle_ranking_PLS_targets_adjust(const M
     }
     return res;
 }
+// The same ranking followed by weighted posterior quantiles of every target's K rows and, with truth (B x P), the posterior CDF at
+// the truth (abc_particle_ranking_pls_targets_summary; method 0 rejection, 1 loclinear with kernel 0 Epanechnikov / 1 rectangular).
+// Per target: quant (nq x P, row q = level probs[q]) and cdf (P; empty without truth).
+struct TargetSummary {
+    Mat2D quant;
+    std::vector<double> cdf;
+};
+inline std::vector<TargetSummary> particle_ranking_PLS_targets_summary(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                       const float_type train_frac, size_t K,
+                                                                       const std::vector<double>& probs, const Mat2D* truth = nullptr,
+                                                                       int method = 0, int kernel = 0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols(), nq = probs.size();
+    if (truth && (truth->rows() != B || truth->cols() != P)) throw HipError(ABC_ERR_INVALID, "truth must be B x P");
+    std::vector<double> tr, q(B * nq * P), cdf(truth ? B * P : 0);
+    if (truth) {
+        tr.resize(B * P);
+        for (size_t b = 0; b < B; b++)
+            for (size_t j = 0; j < P; j++) tr[b * P + j] = (*truth)(b, j);
+    }
+    abc_summary sum = {probs.data(), nq, truth ? tr.data() : nullptr, q.data(), truth ? cdf.data() : nullptr};
+    check(abc_particle_ranking_pls_targets_summary(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac,
+                                                   max_components_ref(), component_rule(), nullptr, K, method, kernel, nullptr, nullptr,
+                                                   nullptr, &sum, nullptr));
+    std::vector<TargetSummary> res(B);
+    for (size_t b = 0; b < B; b++) {
+        res[b].quant = Mat2D(nq, P);
+        for (size_t k = 0; k < nq; k++)
+            for (size_t j = 0; j < P; j++) res[b].quant(k, j) = q[(b * nq + k) * P + j];
+        if (truth) res[b].cdf.assign(cdf.begin() + b * P, cdf.begin() + (b + 1) * P);
+    }
+    return res;
+}
+// Weighted quantiles of every column of values (K x P; weights: K entries, or empty for equal weights, which gives NumPy's
+// "hazen" / R's type 5): nq x P, row q = level probs[q] (abc_weighted_summary).
+inline Mat2D weighted_quantiles(const Mat2D& values, const std::vector<double>& weights, const std::vector<double>& probs) {
+    const size_t K = values.rows(), P = values.cols(), nq = probs.size();
+    if (!weights.empty() && weights.size() != K) throw HipError(ABC_ERR_INVALID, "weights needs one entry per row");
+    std::vector<double> q(nq * P);
+    abc_summary sum = {probs.data(), nq, nullptr, q.data(), nullptr};
+    check(abc_weighted_summary(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &sum));
+    Mat2D out(nq, P);
+    for (size_t k = 0; k < nq; k++)
+        for (size_t j = 0; j < P; j++) out(k, j) = q[k * P + j];
+    return out;
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

@@ -152,3 +152,75 @@ def rank_targets_adjust(X, model, A, targets, K, Y, exclude=None, kernel=_lib.KE
                                                 _ptr(exclude), K, int(kernel), r["idx"].data_ptr(), _ptr(r["dist"]),
                                                 C.byref(out)))
     return r
+
+
+def _summary(probs, truth, quant, cdf):
+    pr = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    s = _lib.Summary(pr.ctypes.data, pr.size, truth.data_ptr() if truth is not None else None,
+                     quant.data_ptr() if quant is not None else None, cdf.data_ptr() if cdf is not None else None)
+    return s, pr
+
+
+def rank_targets_summary(X, model, A, targets, K, Y, probs=(0.025, 0.5, 0.975), truth=None, method=_lib.POSTERIOR_REJECTION,
+                         kernel=_lib.KERNEL_EPANECHNIKOV, exclude=None, dist=False, adjust=(), ctx=None):
+    """rank_targets followed by weighted posterior quantiles and the posterior CDF at `truth` of every (target, parameter)
+    (abc_rank_targets_summary_dev; method 0 rejection, 1 loclinear).  truth: (B, P) row-major device tensor or None.  adjust:
+    names of abc_adjust_out members to return as well (method 1: "theta", "weight", "coef", "rank", "status").
+    Returns dict(idx (B, K) int64, dist (B, K) or None, quant (B, nq, P), cdf (B, P) or None, and the adjust members)."""
+    assert X.dim() == 2 and (X.stride(1) == 1 or X.shape[1] == 1)
+    assert targets.dim() == 2 and (targets.stride(1) == 1 or targets.shape[1] == 1)
+    assert Y is not None and Y.dim() == 2 and Y.shape[1] == X.shape[1] and (Y.stride(1) == 1 or Y.shape[0] <= 1)
+    M, N = X.shape
+    B = targets.shape[1]
+    P = Y.shape[0]
+    assert targets.shape[0] == M
+    dev = X.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    f64 = torch.float64
+    nq = len(np.atleast_1d(probs))
+    if truth is not None:
+        truth = truth.to(device=dev, dtype=f64).contiguous()
+        assert truth.shape == (B, P)
+    r = dict(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
+             dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None,
+             quant=torch.empty((B, nq, P), dtype=f64, device=dev),
+             cdf=torch.empty((B, P), dtype=f64, device=dev) if truth is not None else None)
+    shapes = dict(theta=((B, K, P), f64), weight=((B, K), f64), coef=((B, A + 1, P), f64), rank=((B,), torch.int32),
+                  status=((B,), torch.int32))
+    for k in adjust:
+        r[k] = torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev)
+    adj = _lib.AdjustOut(*(r[k].data_ptr() if k in adjust else None for k in ("theta", "weight", "coef", "rank", "status")))
+    s, _pr = _summary(probs, truth, r["quant"], r["cdf"])
+    if exclude is not None:
+        exclude = exclude.to(device=dev, dtype=torch.int64).contiguous()
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ldy = Y.stride(0) if P > 1 else N
+    ctx.check(lib().abc_rank_targets_summary_dev(ctx.handle, X.data_ptr(), X.stride(0) if M > 1 else N, Y.data_ptr(), ldy, N, M, P,
+                                                 model.data_ptr(), A, targets.data_ptr(), targets.stride(0) if M > 1 else B, B,
+                                                 _ptr(exclude), K, int(method), int(kernel), r["idx"].data_ptr(), _ptr(r["dist"]),
+                                                 C.byref(adj), C.byref(s)))
+    return r
+
+
+def weighted_summary(V, w=None, probs=(0.025, 0.5, 0.975), truth=None, ctx=None):
+    """Weighted quantiles and CDF of P columns of K values (abc_weighted_summary_dev).  V: (P, K) holder of a K x P
+    column-major matrix (row j = column j's values, unit stride); w: K weights or None (equal); truth: P values or None.
+    Returns dict(quant (nq, P), cdf (P,) or None) as device tensors."""
+    assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
+    P, K = V.shape
+    dev = V.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    f64 = torch.float64
+    nq = len(np.atleast_1d(probs))
+    if w is not None:
+        w = w.to(device=dev, dtype=f64).contiguous()
+        assert w.numel() == K
+    if truth is not None:
+        truth = truth.to(device=dev, dtype=f64).contiguous()
+        assert truth.numel() == P
+    r = dict(quant=torch.empty((nq, P), dtype=f64, device=dev),
+             cdf=torch.empty(P, dtype=f64, device=dev) if truth is not None else None)
+    s, _pr = _summary(probs, truth, r["quant"], r["cdf"])
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx.check(lib().abc_weighted_summary_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(s)))
+    return r

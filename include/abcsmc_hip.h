@@ -421,6 +421,59 @@ int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const double* X, const
                                             const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
                                             const abc_adjust_out* out, int32_t* ncomp);
 
+/* ---- weighted posterior quantiles and CDF of the batched ranking ------------------------------------------------------------
+ * A segment is one (target b, parameter j): values v_e and weights w_e, e = 0..K-1 in the ranking's row order, exclusion applied.
+ *   method 0, rejection (ABC_POSTERIOR_REJECTION):  v_e = Y[i_e, j], w_e = 1 (the kernel argument is checked, no effect)
+ *   method 1, loclinear (ABC_POSTERIOR_LOCLINEAR):  v_e = theta*_e[j], w_e = the adjustment's weight: the same bits that
+ *             abc_adjust_out.theta / .weight hold for the same call (Epanechnikov, rectangular and the rectangular fallback)
+ *   generic (abc_weighted_summary*):                 v_e = V[e + ldv j], w_e = w[e] (1 when w is NULL)
+ * If any value of a segment is non-finite, all of that segment's outputs are NaN (other segments are unaffected).
+ * The entries with w_e > 0, sorted ascending by the IEEE totalOrder of the value (-0.0 before +0.0), ties by e, are
+ * u_0 .. u_{n-1} with weights om_r.
+ *   W_r = om_0 + ... + om_r (reference: left to right in fp64; the device sums in another fixed order), W = W_{n-1}
+ *   knots       p_r = fma(-0.5, om_r, W_r) / W
+ *   quantile    q <= p_0: u_0;  q >= p_{n-1}: u_{n-1};  otherwise r = the largest index with p_r <= q,
+ *               t = (q - p_r) / (p_{r+1} - p_r), Q(q) = fma(t, u_{r+1} - u_r, u_r).  With equal weights this is R's type 5
+ *               ("hazen" in NumPy): the median of an even count is the midpoint of the middle two values.
+ *   CDF at tau  F = fma(0.5, E, L) / W, L = sum of om_r over u_r < tau, E = sum over u_r == tau (IEEE equality: -0 == +0), both
+ *               in sorted order; NaN tau gives NaN, +-inf gives 0 or 1.  Across well-calibrated cross-validation targets F is
+ *               roughly uniform (the coverage diagnostic of Prangle et al. 2014).
+ * This definition is the project's own, chosen to equal type 5 for equal weights.  R's abc package has its own convention for
+ * weighted quantiles; it has not been checked against R.
+ * With equal weights (method 0; method 1 with kernel 1 or the fallback; generic with w NULL) every W_r is an exact integer, so
+ * the device's quantiles and CDF are the reference's bits.  With unequal weights the device's sums differ from the reference's
+ * only by the rounding of another fixed summation order (|dW_r| <= 4 K 2^-53 W).  A target's outputs are the same bits on a
+ * repeat run, alone (B = 1) and in any batch, and through the device and host entry points.
+ * Outputs: quant B x nq x P row-major ([b][q][j]), cdf and truth B x P row-major (as post_mean); generic entry: quant nq x P,
+ * cdf and truth P.  Limits as the adjustment's: A <= 64, P <= 1024 (ABC_ERR_UNSUPPORTED beyond); any K <= N. */
+typedef struct {
+    const double* probs;  size_t nq;  /* 1..64 finite levels in [0, 1], any order, repeats allowed; host memory in every entry */
+    const double* truth;              /* optional; memory as the entry point's other arrays                                    */
+    double* quant;                    /* optional                                                                             */
+    double* cdf;                      /* optional; requires truth                                                             */
+} abc_summary;
+enum { ABC_POSTERIOR_REJECTION = 0, ABC_POSTERIOR_LOCLINEAR = 1 };
+/* Device pointers (as abc_rank_targets_adjust_dev; Y required).  idx, dist and adj are optional; when given they receive the
+ * bits of abc_rank_targets_dev / abc_rank_targets_adjust_dev for the same arguments (adj is ignored by method 0).  Besides the
+ * ranking's and the adjustment's own checks, ABC_ERR_INVALID for method or kernel not 0 / 1, NULL sum, nq = 0 or > 64, a NaN
+ * or out-of-range level, and cdf without truth.  Output members left NULL are not written. */
+int abc_rank_targets_summary_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                 size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                 const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                 const abc_adjust_out* adj, const abc_summary* sum);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_adjust); every array of adj and sum in host memory. */
+int abc_particle_ranking_pls_targets_summary(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                             const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                             const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                             double* dist, const abc_adjust_out* adj, const abc_summary* sum, int32_t* ncomp);
+/* The same summaries of P given columns of K values (V[e + ldv j], device memory; w: K weights or NULL; truth, quant and cdf in
+ * device memory).  ABC_ERR_INVALID also for K = 0, P = 0, ldv < K, NULL V, and weights that are negative, non-finite or all
+ * zero (checked on the device; the call synchronises). */
+int abc_weighted_summary_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
+                             const abc_summary* sum);
+/* HOST-pointer form: V is K x P column-major (ldv = K); w, truth, quant and cdf in host memory. */
+int abc_weighted_summary(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_summary* sum);
+
 /* ======================================================================================== */
 /* Multi-GPU: rows (particles) sharded over several GPUs of one node             */
 /* ======================================================================================== */
