@@ -536,7 +536,9 @@ __global__ __launch_bounds__(64 * NW) void k_pls_fit(const double* __restrict__ 
         double ww = 0.0;
         for (int m = lane; m < M; m += NT) ww = fma(wv[m], wv[m], ww);
         ww = sqrt(pls_sum<NW>(ww, red));
-        for (int m = lane; m < M; m += NT) { const double x = wv[m] / ww; wv[m] = x; rv[m] = x; }
+        // w == 0 (XY exactly zero: constant responses or metrics) makes a zero component: w, r, p, q stay 0 (tt == 0 below), so
+        // its H row is 0, its PRESS repeats the previous count's and XY is left as it was -- every later component is zero too
+        for (int m = lane; m < M; m += NT) { const double x = (ww > 0.0) ? wv[m] / ww : 0.0; wv[m] = x; rv[m] = x; }
         PLS_SYNC();
         if constexpr (NW == 1) {
             for (int j = 0; j < comp; j++) {
@@ -607,7 +609,7 @@ __global__ __launch_bounds__(64 * NW) void k_pls_fit(const double* __restrict__ 
             tt = pls_sum<NW>(tt, red);
         }
         for (int m = lane; m < M; m += NT) {
-            const double pm = xr[m] / tt;
+            const double pm = (tt != 0.0) ? xr[m] / tt : 0.0;
             pv[m] = pm;
             Pm[m + (size_t)M * comp] = pm;
             Pl[m + (size_t)M * comp] = pm;
@@ -631,7 +633,7 @@ __global__ __launch_bounds__(64 * NW) void k_pls_fit(const double* __restrict__ 
             for (int j = lane; j < P; j += NT) {
                 double s = 0.0;
                 for (int part = 0; part < 8; part++) s += xp[part * P + j];
-                s /= tt;
+                s = (tt != 0.0) ? s / tt : 0.0;
                 qv[j] = s;
                 Qm[j + (size_t)P * comp] = s;
             }
@@ -639,7 +641,7 @@ __global__ __launch_bounds__(64 * NW) void k_pls_fit(const double* __restrict__ 
         for (int j = lane; j < P; j += NT) {
             double s = 0.0;
             _Pragma("unroll 8") for (int m = 0; m < M; m++) s = fma(XY[m + M * j], rv[m], s);
-            s /= tt;
+            s = (tt != 0.0) ? s / tt : 0.0;
             qv[j] = s;
             Qm[j + (size_t)P * comp] = s;
         }
@@ -842,7 +844,7 @@ __global__ __launch_bounds__(64 * NW) void k_pls_fit16(const double* zwork, cons
             }
             tt = wave_sum(t);
             STAMP16(8);
-            itt = 1.0 / tt;
+            itt = (tt != 0.0) ? 1.0 / tt : 0.0;          // (tt == 0: a zero component, see k_pls_fit)
             STAMP16(9);
 #pragma unroll
             for (int b = 0; b < NB; b++) {
@@ -1101,7 +1103,8 @@ __global__ __launch_bounds__(64 * NW) void k_pls_fit16(const double* zwork, cons
         {
             double ss = 0.0;
             for (int m = l; m < M; m += 64) ss = fma(wv[m], wv[m], ss);
-            iww = 1.0 / sqrt(wave_sum(ss));
+            const double nw = sqrt(wave_sum(ss));
+            iww = (nw > 0.0) ? 1.0 / nw : 0.0;                // (w == 0: a zero component, see k_pls_fit)
         }
         for (int m = tid; m < M; m += NT) wn[m] = wv[m] * iww;
         for (int j = wave; j < comp; j += NW) {

@@ -179,7 +179,8 @@ int orc_pls_fit(const double* X, const double* Y, size_t n, size_t M, size_t P, 
         double ww = 0.0;
         for (size_t m = 0; m < M; m++) ww = std::fma(w[m], w[m], ww);
         ww = std::sqrt(ww);
-        for (size_t m = 0; m < M; m++) w[m] /= ww;
+        /* declared deviation: w == 0 (an exactly-zero XY) is a zero component -- w, r, p, q = 0 (tt == 0), no 0/0 */
+        for (size_t m = 0; m < M; m++) w[m] = (ww > 0.0) ? w[m] / ww : 0.0;
         for (size_t m = 0; m < M; m++) r[m] = w[m];
         for (size_t j = 0; j < i; j++) {
             double pw = 0.0;
@@ -194,7 +195,7 @@ int orc_pls_fit(const double* X, const double* Y, size_t n, size_t M, size_t P, 
                 xxr[a] = s;
             }
             for (size_t m = 0; m < M; m++) tt = std::fma(r[m], xxr[m], tt);
-            for (size_t m = 0; m < M; m++) p[m] = xxr[m] / tt;
+            for (size_t m = 0; m < M; m++) p[m] = (tt != 0.0) ? xxr[m] / tt : 0.0;
         } else {
             for (size_t k = 0; k < n; k++) t[k] = 0.0;
             for (size_t m = 0; m < M; m++) {
@@ -205,13 +206,13 @@ int orc_pls_fit(const double* X, const double* Y, size_t n, size_t M, size_t P, 
             for (size_t m = 0; m < M; m++) {
                 double s = 0.0;
                 for (size_t k = 0; k < n; k++) s = std::fma(X[k + n * m], t[k], s);
-                p[m] = s / tt;
+                p[m] = (tt != 0.0) ? s / tt : 0.0;
             }
         }
         for (size_t j = 0; j < P; j++) {
             double s = 0.0;
             for (size_t m = 0; m < M; m++) s = std::fma(XY[m + M * j], r[m], s);
-            Q[j + P * i] = s / tt;
+            Q[j + P * i] = (tt != 0.0) ? s / tt : 0.0;
         }
         for (size_t j = 0; j < P; j++)
             for (size_t m = 0; m < M; m++) XY[m + M * j] -= tt * (p[m] * Q[j + P * i]);

@@ -96,13 +96,14 @@ class NumpyBackend:
             else:
                 ev, V = np.linalg.eigh(XY.T @ XY)
                 w = XY @ V[:, -1]
-            w /= np.linalg.norm(w)
+            nw = np.linalg.norm(w)
+            w = w / nw if nw > 0 else np.zeros_like(w)         # w == 0: a zero component, as the kernels
             r = w.copy()
             for j in range(i):
                 r -= (Pm[:, j] @ w) * R[:, j]
             xr = XX @ r
             tt = r @ xr
-            p, q = xr / tt, (XY.T @ r) / tt
+            p, q = (xr / tt, (XY.T @ r) / tt) if tt != 0 else (np.zeros_like(xr), np.zeros(XY.shape[1]))
             XY -= tt * np.outer(p, q)
             R[:, i], Q[:, i], Pm[:, i] = r, q, p
         XYte, XXte, YYte = Zte[:M, M:], Zte[:M, :M], np.diag(Zte[M:, M:])
