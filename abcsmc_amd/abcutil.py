@@ -64,13 +64,9 @@ def particle_ranking_PLS(X_orig, Y_orig, target_values, training_fraction, K=Non
     return idx
 
 
-def particle_ranking_PLS_targets(X_orig, Y_orig, targets, training_fraction, K, exclude=None, max_comp=0,
-                                 rule=_lib.RULE_DEFAULT, details=False, ctx=None):
-    """particle_ranking_PLS for B observed targets at once (abc_particle_ranking_pls_targets): ONE fit shared by all of
-    them.  targets: (B, M); exclude: B row numbers (or None; -1 / 2**64 - 1 = none) never ranked for their target (the row
-    still takes part in the fit).  Returns idx (B, K): row b = the first K of particle_ranking_PLS(X, Y, targets[b]).
-    details=True: dict(idx, dist (B, K), post_mean (B, P): mean parameter row of each target's K rows, ncomp)."""
-    ctx = _ctx(ctx)
+def _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude):
+    """What the particle_ranking_PLS_targets family shares: column-major X, Y and targets (B, M), the sizes, K as an int and
+    exclude as uint64 (B,) or None."""
     X, Y = _f(X_orig), _f(Y_orig)
     T = _f(np.atleast_2d(np.asarray(targets, dtype=np.float64)))
     N, M = X.shape
@@ -86,6 +82,23 @@ def particle_ranking_PLS_targets(X_orig, Y_orig, targets, training_fraction, K, 
         ex = np.asarray(exclude, dtype=np.int64).astype(np.uint64)
         if ex.shape != (B,):
             raise ValueError("exclude needs one entry per target")
+    return X, Y, T, N, M, P, B, K, ex
+
+
+def _choice(what, value, table):
+    if value not in table:
+        raise ValueError("%s must be one of %s" % (what, sorted(table)))
+    return table[value]
+
+
+def particle_ranking_PLS_targets(X_orig, Y_orig, targets, training_fraction, K, exclude=None, max_comp=0,
+                                 rule=_lib.RULE_DEFAULT, details=False, ctx=None):
+    """particle_ranking_PLS for B observed targets at once (abc_particle_ranking_pls_targets): ONE fit shared by all of
+    them.  targets: (B, M); exclude: B row numbers (or None; -1 / 2**64 - 1 = none) never ranked for their target (the row
+    still takes part in the fit).  Returns idx (B, K): row b = the first K of particle_ranking_PLS(X, Y, targets[b]).
+    details=True: dict(idx, dist (B, K), post_mean (B, P): mean parameter row of each target's K rows, ncomp)."""
+    ctx = _ctx(ctx)
+    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
     idx = np.empty((B, K), dtype=np.uint64)
     dist = np.empty((B, K))
     pm = np.empty((B, P))
@@ -109,23 +122,8 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
     with theta=False, weight (B, K), coef (B, A + 1, P): [b, 0] = alpha, [b, 1 + k] = beta_k, post_mean = coef[:, 0]: the
     adjusted posterior means, rank (B,), status (B,): bit 0 a component skipped, bit 1 rectangular fallback, ncomp)."""
     ctx = _ctx(ctx)
-    if kernel not in _KERNELS:
-        raise ValueError("kernel must be one of %s" % sorted(_KERNELS))
-    X, Y = _f(X_orig), _f(Y_orig)
-    T = _f(np.atleast_2d(np.asarray(targets, dtype=np.float64)))
-    N, M = X.shape
-    P = Y.shape[1]
-    B = T.shape[0]
-    if Y.shape[0] != N or T.shape[1] != M:
-        raise ValueError("shape mismatch")
-    if not (0 < training_fraction <= 1):
-        raise ValueError("training_fraction must be in (0,1]")
-    K = int(K)
-    ex = None
-    if exclude is not None:
-        ex = np.asarray(exclude, dtype=np.int64).astype(np.uint64)
-        if ex.shape != (B,):
-            raise ValueError("exclude needs one entry per target")
+    kernel = _choice("kernel", kernel, _KERNELS)
+    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
     A = max_comp if max_comp > 0 else min(M, P)
     idx = np.empty((B, K), dtype=np.uint64)
     dist = np.empty((B, K))
@@ -137,7 +135,7 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
     out = _lib.AdjustOut(_p(th), _p(w), _p(coef), _p(rank), _p(status))
     ncomp = C.c_int32(0)
     ctx.check(lib().abc_particle_ranking_pls_targets_adjust(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
-                                                            int(max_comp), int(rule), _p(ex), K, _KERNELS[kernel], _p(idx),
+                                                            int(max_comp), int(rule), _p(ex), K, kernel, _p(idx),
                                                             _p(dist), C.byref(out), C.addressof(ncomp)))
     return dict(idx=idx, dist=dist, theta=th, weight=w, coef=coef, post_mean=coef[:, 0], rank=rank, status=status,
                 ncomp=ncomp.value)
@@ -160,25 +158,8 @@ def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fract
     (as particle_ranking_PLS_targets_adjust).  Returns dict(quant (B, nq, P): [b, q, j], cdf (B, P) or None, probs, idx (B, K),
     dist (B, K), ncomp)."""
     ctx = _ctx(ctx)
-    if method not in _METHODS:
-        raise ValueError("method must be one of %s" % sorted(_METHODS))
-    if kernel not in _KERNELS:
-        raise ValueError("kernel must be one of %s" % sorted(_KERNELS))
-    X, Y = _f(X_orig), _f(Y_orig)
-    T = _f(np.atleast_2d(np.asarray(targets, dtype=np.float64)))
-    N, M = X.shape
-    P = Y.shape[1]
-    B = T.shape[0]
-    if Y.shape[0] != N or T.shape[1] != M:
-        raise ValueError("shape mismatch")
-    if not (0 < training_fraction <= 1):
-        raise ValueError("training_fraction must be in (0,1]")
-    K = int(K)
-    ex = None
-    if exclude is not None:
-        ex = np.asarray(exclude, dtype=np.int64).astype(np.uint64)
-        if ex.shape != (B,):
-            raise ValueError("exclude needs one entry per target")
+    method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
+    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
     tr = None
     if truth is not None:
         tr = np.ascontiguousarray(np.asarray(truth, dtype=np.float64).reshape(B, P))
@@ -190,7 +171,7 @@ def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fract
     s, pr = _summary_arg(probs, tr, quant, cdf)
     ncomp = C.c_int32(0)
     ctx.check(lib().abc_particle_ranking_pls_targets_summary(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
-                                                             int(max_comp), int(rule), _p(ex), K, _METHODS[method], _KERNELS[kernel],
+                                                             int(max_comp), int(rule), _p(ex), K, method, kernel,
                                                              _p(idx), _p(dist), None, C.byref(s), C.addressof(ncomp)))
     return dict(quant=quant, cdf=cdf, probs=pr, idx=idx, dist=dist, ncomp=ncomp.value)
 

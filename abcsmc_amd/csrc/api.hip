@@ -1048,14 +1048,19 @@ extern "C" int abc_generation_dev(abc_ctx* ctx, const abc_generation_cfg* cfg, c
 namespace {
 struct Stage {   // host<->device staging inside the arena
     abc_ctx* ctx;
+    bool full = false;   // some allocation found the arena exhausted (and returned NULL)
     template <typename T>
     T* up(const T* h, size_t n) {
-        T* d = (T*)abc_ws_alloc(ctx, n * sizeof(T));
+        T* d = dev<T>(n);
         if (d && h && n) (void)hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
         return d;
     }
     template <typename T>
-    T* dev(size_t n) { return (T*)abc_ws_alloc(ctx, n * sizeof(T)); }
+    T* dev(size_t n) {
+        T* d = (T*)abc_ws_alloc(ctx, n * sizeof(T));
+        if (!d) full = true;
+        return d;
+    }
     template <typename T>
     void down(T* h, const T* d, size_t n) {
         if (h && d && n) (void)hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
@@ -1267,195 +1272,30 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
     return sample_host(ctx, rng, n, w, theta, K, P, priors, dv, 0, out, parent, seeds);
 }
 
-// ---- batched ranking of many observed targets against one fitted set (targets.hip) ------------------------------------------
-// Argument checks shared by the device and the host entry.  ex: the exclusions in host memory (NULL: none).
-static int targets_check(abc_ctx* ctx, const char* fn, size_t N, size_t M, size_t B, size_t K, const uint64_t* ex, bool* any_excl) {
-    if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
-    if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
-    if (M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no metrics (M == 0)", fn);
-    if (K > N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N = %zu", fn, K, N);
-    if (N >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: N = %zu rows (at most 2^32 - 1)", fn, N);
-    *any_excl = false;
-    if (ex)
-        for (size_t b = 0; b < B; b++) {
-            if (ex[b] == UINT64_MAX) continue;
-            if (ex[b] >= N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: exclude[%zu] = %llu is not a row (N = %zu)", fn, b,
-                                     (unsigned long long)ex[b], N);
-            *any_excl = true;
-        }
-    if (*any_excl && K > N - 1) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N - 1 = %zu with an excluded row", fn, K, N - 1);
-    return ABC_OK;
-}
+// ---- batched ranking of many observed targets against one fitted set (targets.hip), optionally followed by the local-linear
+// adjustment (adjust.hip) and the weighted posterior quantiles and CDF (summary.hip): one pipeline behind six entry points ----
+namespace {
+enum { TG_PLAIN, TG_ADJUST, TG_SUMMARY };      // what follows the ranking: nothing, the adjustment, the summaries
+struct TgRequest {                             // (members in the order of the entries' arguments)
+    int kind;
+    const double* X;  size_t ldx;
+    const double* Y;  size_t ldy;
+    size_t N, M, P;
+    const double* model;  size_t A;
+    const double* targets;  size_t ldt, B;
+    const uint64_t* exclude;
+    size_t K;
+    uint64_t* idx;                             // optional for TG_SUMMARY
+    double* dist;                              // optional
+    double* post_mean = nullptr;               // TG_PLAIN only, optional
+    int method = 0, kernel = 0;                // method: TG_SUMMARY only (of which values the summaries are)
+    const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; TG_SUMMARY: optional, method 1 only
+    const abc_summary* sum = nullptr;          // TG_SUMMARY only
+    bool any_excl = false;                     // exclude names a row for some target: set by tg_check
+    bool regress() const { return kind == TG_ADJUST || (kind == TG_SUMMARY && method == ABC_POSTERIOR_LOCLINEAR); }
+};
+}  // namespace
 
-extern "C" int abc_rank_targets_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
-                                    size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
-                                    const uint64_t* exclude, size_t K, uint64_t* idx, double* dist, double* post_mean) {
-    CHECK_CTX(ctx);
-    const char* fn = "abc_rank_targets_dev";
-    if (!X || !model || !targets || !idx) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, model, targets and idx are required)", fn);
-    if (post_mean && P && !Y) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: post_mean needs Y", fn);
-    if (A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
-    if (ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, ldx, N);
-    if (ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, ldt, B);
-    if (post_mean && P && ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, ldy, N);
-    std::vector<uint64_t> ex;
-    if (exclude && B) {
-        ex.resize(B);
-        ABC_HIP(ctx, hipMemcpyAsync(ex.data(), exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    bool any_excl = false;
-    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude ? ex.data() : nullptr, &any_excl));
-    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, 1, 1, 1, K + 1, 0, 0) + abc_targets_need(N, A, B, K, any_excl)));
-    return launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, idx, dist, post_mean);
-}
-
-extern "C" int abc_particle_ranking_pls_targets(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
-                                                const double* targets, size_t B, double train_frac, int max_comp, int rule,
-                                                const uint64_t* exclude, size_t K, uint64_t* idx, double* dist, double* post_mean,
-                                                int32_t* ncomp) {
-    CHECK_CTX(ctx);
-    const char* fn = "abc_particle_ranking_pls_targets";
-    if (!X || !Y || !targets || !idx) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, Y, targets and idx are required)", fn);
-    bool any_excl = false;
-    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude, &any_excl));
-    const size_t A = default_A(M, P, max_comp);
-    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, M, P, A, K + 1, 0, 0) + (N * (M + P) + M + 4) * 8 +
-                                    (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0) +
-                                    (B * M + B + 2 * B * K + B * P) * 8 + 8 * 256 + abc_targets_need(N, A, B, K, any_excl)));
-    Stage s{ctx};
-    // the fit: the single-target ranking's own path (generation_core) on an all-zero observation, whose scores are not used
-    abc_generation_io io;
-    memset(&io, 0, sizeof(io));
-    io.X = s.up(X, N * M);
-    io.Y = s.up(Y, N * P);
-    double* zobs = s.dev<double>(M);
-    io.obs = zobs;
-    io.idx = s.dev<uint64_t>(1);
-    io.dist = s.dev<double>(1);
-    if (!io.X || !io.Y || !zobs || !io.idx || !io.dist) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    ABC_HIP(ctx, hipMemsetAsync(zobs, 0, M * sizeof(double), ctx->stream));
-    abc_generation_cfg cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.N = N; cfg.M = M; cfg.P = P; cfg.K = 1; cfg.train_frac = train_frac;
-    cfg.max_comp = max_comp; cfg.rule = rule;
-    const double* model = nullptr;
-    ABC_TRY(generation_core(ctx, &cfg, &io, nullptr, ncomp, 0, &model));
-    const double* t_d = s.up(targets, B * M);
-    const uint64_t* ex_d = exclude ? s.up(exclude, B) : nullptr;
-    uint64_t* idx_d = s.dev<uint64_t>(B * K);
-    double* dist_d = dist ? s.dev<double>(B * K) : nullptr;
-    double* pm_d = (post_mean && P) ? s.dev<double>(B * P) : nullptr;
-    if (!t_d || (exclude && !ex_d) || !idx_d || (dist && !dist_d) || (post_mean && P && !pm_d))
-        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    ABC_TRY(launch_rank_targets(ctx, io.X, N, io.Y, N, N, M, P, model, A, t_d, B, B, ex_d, any_excl, K, idx_d, dist_d, pm_d));
-    s.down(idx, idx_d, B * K);
-    s.down(dist, dist_d, B * K);
-    s.down(post_mean, pm_d, B * P);
-    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
-}
-
-// ---- local-linear adjustment of the batched ranking (adjust.hip) -----------------------------------------------------------
-static int adjust_check(abc_ctx* ctx, const char* fn, const double* Y, size_t ldy, size_t N, size_t A, size_t P, int kernel,
-                        const abc_adjust_out* out) {
-    if (!Y) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (Y is required)", fn);
-    if (!out) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (out is required)", fn);
-    if (kernel != ABC_KERNEL_EPANECHNIKOV && kernel != ABC_KERNEL_RECTANGULAR)
-        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: kernel %d (0 = Epanechnikov, 1 = rectangular)", fn, kernel);
-    if (P > 0 && ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, ldy, N);
-    if (A > 64) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: A = %zu components (at most 64)", fn, A);
-    if (P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, P);
-    return ABC_OK;
-}
-
-extern "C" int abc_rank_targets_adjust_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
-                                           size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
-                                           const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
-                                           const abc_adjust_out* out) {
-    CHECK_CTX(ctx);
-    const char* fn = "abc_rank_targets_adjust_dev";
-    if (!X || !model || !targets || !idx) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, model, targets and idx are required)", fn);
-    if (A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
-    if (ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, ldx, N);
-    if (ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, ldt, B);
-    ABC_TRY(adjust_check(ctx, fn, Y, ldy, N, A, P, kernel, out));
-    std::vector<uint64_t> ex;
-    if (exclude && B) {
-        ex.resize(B);
-        ABC_HIP(ctx, hipMemcpyAsync(ex.data(), exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    bool any_excl = false;
-    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude ? ex.data() : nullptr, &any_excl));
-    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, 1, 1, 1, K + 1, 0, 0) + abc_targets_need(N, A, B, K, any_excl) +
-                                    abc_adjust_need(N, A, P, B, K)));
-    return launch_rank_targets_adjust(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, kernel, idx, dist,
-                                      out);
-}
-
-extern "C" int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
-                                                       const double* targets, size_t B, double train_frac, int max_comp, int rule,
-                                                       const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
-                                                       const abc_adjust_out* out, int32_t* ncomp) {
-    CHECK_CTX(ctx);
-    const char* fn = "abc_particle_ranking_pls_targets_adjust";
-    if (!X || !targets || !idx) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, Y, targets and idx are required)", fn);
-    const size_t A = default_A(M, P, max_comp);
-    ABC_TRY(adjust_check(ctx, fn, Y, N, N, A, P, kernel, out));
-    bool any_excl = false;
-    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude, &any_excl));
-    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, M, P, A, K + 1, 0, 0) + (N * (M + P) + M + 4) * 8 +
-                                    (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0) +
-                                    (B * M + B + 2 * B * K + B * (A + 1) * P + B * K * P + B * K + B) * 8 + 16 * 256 +
-                                    abc_targets_need(N, A, B, K, any_excl) + abc_adjust_need(N, A, P, B, K)));
-    Stage s{ctx};
-    // the fit: as abc_particle_ranking_pls_targets
-    abc_generation_io io;
-    memset(&io, 0, sizeof(io));
-    io.X = s.up(X, N * M);
-    io.Y = s.up(Y, N * P);
-    double* zobs = s.dev<double>(M);
-    io.obs = zobs;
-    io.idx = s.dev<uint64_t>(1);
-    io.dist = s.dev<double>(1);
-    if (!io.X || !io.Y || !zobs || !io.idx || !io.dist) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    ABC_HIP(ctx, hipMemsetAsync(zobs, 0, M * sizeof(double), ctx->stream));
-    abc_generation_cfg cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.N = N; cfg.M = M; cfg.P = P; cfg.K = 1; cfg.train_frac = train_frac;
-    cfg.max_comp = max_comp; cfg.rule = rule;
-    const double* model = nullptr;
-    ABC_TRY(generation_core(ctx, &cfg, &io, nullptr, ncomp, 0, &model));
-    const double* t_d = s.up(targets, B * M);
-    const uint64_t* ex_d = exclude ? s.up(exclude, B) : nullptr;
-    uint64_t* idx_d = s.dev<uint64_t>(B * K);
-    double* dist_d = dist ? s.dev<double>(B * K) : nullptr;
-    abc_adjust_out od;
-    od.theta = out->theta ? s.dev<double>(B * K * P + 1) : nullptr;
-    od.weight = out->weight ? s.dev<double>(B * K) : nullptr;
-    od.coef = out->coef ? s.dev<double>(B * (A + 1) * P + 1) : nullptr;
-    od.rank = out->rank ? s.dev<int32_t>(B) : nullptr;
-    od.status = out->status ? s.dev<int32_t>(B) : nullptr;
-    if (!t_d || (exclude && !ex_d) || !idx_d || (dist && !dist_d) || (out->theta && !od.theta) || (out->weight && !od.weight) ||
-        (out->coef && !od.coef) || (out->rank && !od.rank) || (out->status && !od.status))
-        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    ABC_TRY(launch_rank_targets_adjust(ctx, io.X, N, io.Y, N, N, M, P, model, A, t_d, B, B, ex_d, any_excl, K, kernel, idx_d, dist_d,
-                                       &od));
-    s.down(idx, idx_d, B * K);
-    s.down(dist, dist_d, B * K);
-    s.down(out->theta, od.theta, B * K * P);
-    s.down(out->weight, od.weight, B * K);
-    s.down(out->coef, od.coef, B * (A + 1) * P);
-    s.down(out->rank, od.rank, B);
-    s.down(out->status, od.status, B);
-    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
-}
-
-// ---- weighted posterior quantiles and CDF (summary.hip) -------------------------------------------------------------------
 static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
     if (!sum) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (sum is required)", fn);
     if (sum->nq == 0 || sum->nq > 64) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: nq = %zu levels (1 to 64)", fn, sum->nq);
@@ -1467,46 +1307,224 @@ static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
     return ABC_OK;
 }
 
-static int summary_method_check(abc_ctx* ctx, const char* fn, int method) {
-    if (method != ABC_POSTERIOR_REJECTION && method != ABC_POSTERIOR_LOCLINEAR)
-        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: method %d (0 = rejection, 1 = loclinear)", fn, method);
+// Argument checks of the family; sets r.any_excl.  host: the arrays are in host memory and the model is fitted by the call
+// (which needs Y); otherwise exclude is brought to the host here, after every check that does not need it.
+static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
+    const bool plain = r.kind == TG_PLAIN, summary = r.kind == TG_SUMMARY;
+    const size_t N = r.N, B = r.B, K = r.K;
+    if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
+    if (!r.targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (targets is required)", fn);
+    if (!r.idx && !summary) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (idx is required)", fn);
+    if (!r.Y && (host || !plain)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (Y is required)", fn);
+    if (!r.Y && r.post_mean && r.P) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: post_mean needs Y", fn);
+    if (!host) {
+        if (!r.model) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (model is required)", fn);
+        if (r.A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
+        if (r.ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, r.ldx, N);
+        if (r.ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, r.ldt, B);
+    }
+    if (summary && r.method != ABC_POSTERIOR_REJECTION && r.method != ABC_POSTERIOR_LOCLINEAR)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: method %d (0 = rejection, 1 = loclinear)", fn, r.method);
+    if (r.kind == TG_ADJUST && !r.adj) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (out is required)", fn);
+    if (!plain && r.kernel != ABC_KERNEL_EPANECHNIKOV && r.kernel != ABC_KERNEL_RECTANGULAR)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: kernel %d (0 = Epanechnikov, 1 = rectangular)", fn, r.kernel);
+    if ((!plain || r.post_mean) && r.P && r.ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, r.ldy, N);
+    if (!plain) {     // the adjustment's limits, for both summary methods too
+        if (r.A > 64) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: A = %zu components (at most 64)", fn, r.A);
+        if (r.P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, r.P);
+    }
+    if (summary) ABC_TRY(summary_check(ctx, fn, r.sum));
+    if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
+    if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
+    if (r.M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no metrics (M == 0)", fn);
+    if (K > N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N = %zu", fn, K, N);
+    if (N >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: N = %zu rows (at most 2^32 - 1)", fn, N);
+    std::vector<uint64_t> copy;
+    const uint64_t* ex = r.exclude;
+    if (ex && !host) {
+        copy.resize(B);
+        ABC_HIP(ctx, hipMemcpyAsync(copy.data(), r.exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ex = copy.data();
+    }
+    r.any_excl = false;
+    if (ex)
+        for (size_t b = 0; b < B; b++) {
+            if (ex[b] == UINT64_MAX) continue;
+            if (ex[b] >= N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: exclude[%zu] = %llu is not a row (N = %zu)", fn, b,
+                                     (unsigned long long)ex[b], N);
+            r.any_excl = true;
+        }
+    if (r.any_excl && K > N - 1) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N - 1 = %zu with an excluded row", fn, K, N - 1);
     return ABC_OK;
 }
 
-// workspace of rank_summary beyond the ranking's own
-static size_t rank_summary_need(size_t N, size_t A, size_t P, size_t B, size_t K, int method) {
-    return 2 * B * K * 8 + 16 * 256 + (method == ABC_POSTERIOR_LOCLINEAR ? abc_adjust_need(N, A, P, B, K) : 0) +
-           abc_summary_need(B, K, P);
+// Arena bytes of a checked request: what tg_run takes and, for the host entries (host: the fit under `rule`, every array staged),
+// what tg_host takes around it.  The device entries get the model from the caller, so their ranking needs no fit workspace.
+static size_t tg_need(const TgRequest& r, bool host, int rule) {
+    const size_t N = r.N, M = r.M, P = r.P, A = r.A, B = r.B, K = r.K;
+    size_t b = abc_targets_need(N, A, B, K, r.any_excl);
+    if (r.regress()) b += abc_adjust_need(N, A, P, B, K);
+    if (r.kind == TG_SUMMARY) b += 2 * B * K * 8 + 16 * 256 + abc_summary_need(B, K, P);     // (tg_run's own idx and dist)
+    if (!host) return b + abc_ws_need(N, 1, 1, 1, K + 1, 0, 0);
+    b += abc_ws_need(N, M, P, A, K + 1, 0, 0) + (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0);
+    b += (N * (M + P) + M + 4) * 8;                                               // X, Y, the zero observation and its one idx, dist
+    b += (B * M + B + 2 * B * K) * 8 + 8 * 256;                                   // targets, exclude, idx, dist
+    if (r.kind == TG_PLAIN) b += B * P * 8;                                       // post_mean
+    else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
+    if (r.kind == TG_SUMMARY) b += B * P * (r.sum->nq + 2) * 8 + 16 * 256;        // truth, quant, cdf
+    return b;
 }
 
-// the ranking (method 0) or the adjustment (method 1), then the summaries; device pointers, the workspace reserved
-static int rank_summary(abc_ctx* ctx, const char* fn, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
-                        size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                        bool any_excl, size_t K, int method, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* adj,
-                        const abc_summary* sum) {
-    uint64_t* ix = idx ? idx : (uint64_t*)abc_ws_alloc(ctx, B * K * 8);
-    double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
-    if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    SmValues sv;
-    memset(&sv, 0, sizeof(sv));
-    sv.method = method;
-    sv.idx = ix;
-    sv.Y = Y;
-    sv.ldy = ldy;
-    sv.A = (int)A;
-    sv.kernel = kernel;
-    abc_adj_keep keep;
-    if (method == ABC_POSTERIOR_REJECTION) {
-        ABC_TRY(launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, ix, d, nullptr));
-    } else {
-        abc_adjust_out od;
-        memset(&od, 0, sizeof(od));
-        if (adj) od = *adj;
-        ABC_TRY(launch_rank_targets_adjust(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, kernel, ix, d,
-                                           &od, &keep));
-        sv.adj = &keep;
+// The ranking or (regress) the ranking with the adjustment, then the summaries if asked for; device pointers, the workspace reserved.
+static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
+    const size_t B = r.B, K = r.K;
+    const bool summary = r.kind == TG_SUMMARY;
+    uint64_t* ix = r.idx;
+    double* d = r.dist;
+    if (summary) {     // the summaries read both
+        if (!ix) ix = (uint64_t*)abc_ws_alloc(ctx, B * K * 8);
+        if (!d) d = (double*)abc_ws_alloc(ctx, B * K * 8);
+        if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     }
-    return launch_summary(ctx, sv, B, K, P, sum);
+    abc_adj_keep keep;
+    if (!r.regress()) {     // (post_mean: of the plain ranking only)
+        ABC_TRY(launch_rank_targets(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
+                                    r.any_excl, K, ix, d, r.post_mean));
+    } else {                // (without keep nothing is regressed when every member of adj is NULL)
+        abc_adjust_out od = {};
+        if (r.adj) od = *r.adj;
+        ABC_TRY(launch_rank_targets_adjust(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
+                                           r.any_excl, K, r.kernel, ix, d, &od, summary ? &keep : nullptr));
+    }
+    if (!summary) return ABC_OK;
+    SmValues sv = {};
+    sv.method = r.method;
+    sv.idx = ix;
+    sv.Y = r.Y;
+    sv.ldy = r.ldy;
+    sv.adj = r.regress() ? &keep : nullptr;
+    sv.A = (int)r.A;
+    sv.kernel = r.kernel;
+    return launch_summary(ctx, sv, B, K, r.P, r.sum);
+}
+
+static int tg_dev(abc_ctx* ctx, const char* fn, TgRequest r) {
+    ABC_TRY(tg_check(ctx, fn, r, false));
+    ABC_TRY(abc_ws_reserve(ctx, tg_need(r, false, 0)));
+    return tg_run(ctx, fn, r);
+}
+
+// an abc_summary's arrays for G groups of P segments, host (h) <-> arena: probs stay where they are, NULL members stay NULL
+static abc_summary summary_stage(Stage& s, const abc_summary* h, size_t G, size_t P) {
+    abc_summary d = *h;
+    d.truth = h->truth ? s.up(h->truth, G * P) : nullptr;
+    d.quant = h->quant ? s.dev<double>(G * h->nq * P) : nullptr;
+    d.cdf = h->cdf ? s.dev<double>(G * P) : nullptr;
+    return d;
+}
+static void summary_down(Stage& s, const abc_summary* h, const abc_summary& d, size_t G, size_t P) {
+    s.down(h->quant, d.quant, G * h->nq * P);
+    s.down(h->cdf, d.cdf, G * P);
+}
+
+// The host entries: h holds host pointers.  Upload, one fit, the request on the arena's copies, downloads, synchronise.
+static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac, int max_comp, int rule, int32_t* ncomp) {
+    const size_t N = h.N, M = h.M, P = h.P, B = h.B, K = h.K;
+    const size_t A = h.A = default_A(M, P, max_comp);
+    ABC_TRY(tg_check(ctx, fn, h, true));
+    ABC_TRY(abc_ws_reserve(ctx, tg_need(h, true, rule)));
+    Stage s{ctx};
+    // the fit: the single-target ranking's own path (generation_core) on an all-zero observation, whose scores are not used
+    abc_generation_io io;
+    memset(&io, 0, sizeof(io));
+    io.X = s.up(h.X, N * M);
+    io.Y = s.up(h.Y, N * P);
+    double* zobs = s.dev<double>(M);
+    io.obs = zobs;
+    io.idx = s.dev<uint64_t>(1);
+    io.dist = s.dev<double>(1);
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_HIP(ctx, hipMemsetAsync(zobs, 0, M * sizeof(double), ctx->stream));
+    abc_generation_cfg cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.N = N; cfg.M = M; cfg.P = P; cfg.K = 1; cfg.train_frac = train_frac;
+    cfg.max_comp = max_comp; cfg.rule = rule;
+    ABC_TRY(generation_core(ctx, &cfg, &io, nullptr, ncomp, 0, &h.model));
+    // the request on device copies: every output the caller gave, in the arena
+    TgRequest r = h;
+    r.X = io.X; r.Y = io.Y;
+    r.targets = s.up(h.targets, B * M);
+    r.exclude = h.exclude ? s.up(h.exclude, B) : nullptr;
+    r.idx = h.idx ? s.dev<uint64_t>(B * K) : nullptr;
+    r.dist = h.dist ? s.dev<double>(B * K) : nullptr;
+    r.post_mean = (h.post_mean && P) ? s.dev<double>(B * P) : nullptr;
+    const abc_adjust_out* ah = h.regress() ? h.adj : nullptr;
+    abc_adjust_out od = {};
+    if (ah) {     // (theta and coef one element longer, as the adjustment's own buffers)
+        od.theta = ah->theta ? s.dev<double>(B * K * P + 1) : nullptr;
+        od.weight = ah->weight ? s.dev<double>(B * K) : nullptr;
+        od.coef = ah->coef ? s.dev<double>(B * (A + 1) * P + 1) : nullptr;
+        od.rank = ah->rank ? s.dev<int32_t>(B) : nullptr;
+        od.status = ah->status ? s.dev<int32_t>(B) : nullptr;
+    }
+    r.adj = ah ? &od : nullptr;
+    abc_summary sd;
+    if (h.sum) {
+        sd = summary_stage(s, h.sum, B, P);
+        r.sum = &sd;
+    }
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    ABC_TRY(tg_run(ctx, fn, r));
+    s.down(h.idx, r.idx, B * K);
+    s.down(h.dist, r.dist, B * K);
+    s.down(h.post_mean, r.post_mean, B * P);
+    if (ah) {
+        s.down(ah->theta, od.theta, B * K * P);
+        s.down(ah->weight, od.weight, B * K);
+        s.down(ah->coef, od.coef, B * (A + 1) * P);
+        s.down(ah->rank, od.rank, B);
+        s.down(ah->status, od.status, B);
+    }
+    if (h.sum) summary_down(s, h.sum, sd, B, P);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+extern "C" int abc_rank_targets_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                    size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                    const uint64_t* exclude, size_t K, uint64_t* idx, double* dist, double* post_mean) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_PLAIN, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, post_mean};
+    return tg_dev(ctx, "abc_rank_targets_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                const uint64_t* exclude, size_t K, uint64_t* idx, double* dist, double* post_mean,
+                                                int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_PLAIN, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, post_mean};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets", h, train_frac, max_comp, rule, ncomp);
+}
+
+extern "C" int abc_rank_targets_adjust_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                           size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                           const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
+                                           const abc_adjust_out* out) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_ADJUST, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, 0, kernel, out};
+    return tg_dev(ctx, "abc_rank_targets_adjust_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                       const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                       const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
+                                                       const abc_adjust_out* out, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_ADJUST, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, 0, kernel, out};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_adjust", h, train_frac, max_comp, rule, ncomp);
 }
 
 extern "C" int abc_rank_targets_summary_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
@@ -1514,27 +1532,9 @@ extern "C" int abc_rank_targets_summary_dev(abc_ctx* ctx, const double* X, size_
                                             const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
                                             const abc_adjust_out* adj, const abc_summary* sum) {
     CHECK_CTX(ctx);
-    const char* fn = "abc_rank_targets_summary_dev";
-    if (!X || !model || !targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, Y, model and targets are required)", fn);
-    if (A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
-    if (ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, ldx, N);
-    if (ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, ldt, B);
-    ABC_TRY(summary_method_check(ctx, fn, method));
-    const abc_adjust_out none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ABC_TRY(adjust_check(ctx, fn, Y, ldy, N, A, P, kernel, &none));
-    ABC_TRY(summary_check(ctx, fn, sum));
-    std::vector<uint64_t> ex;
-    if (exclude && B) {
-        ex.resize(B);
-        ABC_HIP(ctx, hipMemcpyAsync(ex.data(), exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    bool any_excl = false;
-    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude ? ex.data() : nullptr, &any_excl));
-    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, 1, 1, 1, K + 1, 0, 0) + abc_targets_need(N, A, B, K, any_excl) +
-                                    rank_summary_need(N, A, P, B, K, method)));
-    return rank_summary(ctx, fn, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, method, kernel, idx, dist,
-                        method == ABC_POSTERIOR_LOCLINEAR ? adj : nullptr, sum);
+    const TgRequest r{TG_SUMMARY, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, sum};
+    return tg_dev(ctx, "abc_rank_targets_summary_dev", r);
 }
 
 extern "C" int abc_particle_ranking_pls_targets_summary(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
@@ -1543,77 +1543,9 @@ extern "C" int abc_particle_ranking_pls_targets_summary(abc_ctx* ctx, const doub
                                                         double* dist, const abc_adjust_out* adj, const abc_summary* sum,
                                                         int32_t* ncomp) {
     CHECK_CTX(ctx);
-    const char* fn = "abc_particle_ranking_pls_targets_summary";
-    if (!X || !targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, Y and targets are required)", fn);
-    ABC_TRY(summary_method_check(ctx, fn, method));
-    const size_t A = default_A(M, P, max_comp);
-    const abc_adjust_out none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ABC_TRY(adjust_check(ctx, fn, Y, N, N, A, P, kernel, &none));
-    ABC_TRY(summary_check(ctx, fn, sum));
-    bool any_excl = false;
-    ABC_TRY(targets_check(ctx, fn, N, M, B, K, exclude, &any_excl));
-    const bool ll = method == ABC_POSTERIOR_LOCLINEAR;
-    const abc_adjust_out* ah = ll ? adj : nullptr;
-    const size_t nq = sum->nq;
-    ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(N, M, P, A, K + 1, 0, 0) + (N * (M + P) + M + 4) * 8 +
-                                    (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0) +
-                                    (B * M + B + 2 * B * K + B * (A + 1) * P + B * K * P + B * K + B + B * P * (nq + 2)) * 8 +
-                                    32 * 256 + abc_targets_need(N, A, B, K, any_excl) + rank_summary_need(N, A, P, B, K, method)));
-    Stage s{ctx};
-    // the fit: as abc_particle_ranking_pls_targets
-    abc_generation_io io;
-    memset(&io, 0, sizeof(io));
-    io.X = s.up(X, N * M);
-    io.Y = s.up(Y, N * P);
-    double* zobs = s.dev<double>(M);
-    io.obs = zobs;
-    io.idx = s.dev<uint64_t>(1);
-    io.dist = s.dev<double>(1);
-    if (!io.X || !io.Y || !zobs || !io.idx || !io.dist) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    ABC_HIP(ctx, hipMemsetAsync(zobs, 0, M * sizeof(double), ctx->stream));
-    abc_generation_cfg cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.N = N; cfg.M = M; cfg.P = P; cfg.K = 1; cfg.train_frac = train_frac;
-    cfg.max_comp = max_comp; cfg.rule = rule;
-    const double* model = nullptr;
-    ABC_TRY(generation_core(ctx, &cfg, &io, nullptr, ncomp, 0, &model));
-    const double* t_d = s.up(targets, B * M);
-    const uint64_t* ex_d = exclude ? s.up(exclude, B) : nullptr;
-    uint64_t* idx_d = idx ? s.dev<uint64_t>(B * K) : nullptr;
-    double* dist_d = dist ? s.dev<double>(B * K) : nullptr;
-    abc_adjust_out od;
-    memset(&od, 0, sizeof(od));
-    if (ah) {
-        od.theta = ah->theta ? s.dev<double>(B * K * P + 1) : nullptr;
-        od.weight = ah->weight ? s.dev<double>(B * K) : nullptr;
-        od.coef = ah->coef ? s.dev<double>(B * (A + 1) * P + 1) : nullptr;
-        od.rank = ah->rank ? s.dev<int32_t>(B) : nullptr;
-        od.status = ah->status ? s.dev<int32_t>(B) : nullptr;
-    }
-    abc_summary sd = *sum;
-    sd.truth = sum->truth ? s.up(sum->truth, B * P) : nullptr;
-    sd.quant = sum->quant ? s.dev<double>(B * nq * P) : nullptr;
-    sd.cdf = sum->cdf ? s.dev<double>(B * P) : nullptr;
-    if (!t_d || (exclude && !ex_d) || (idx && !idx_d) || (dist && !dist_d) || (ah && ah->theta && !od.theta) ||
-        (ah && ah->weight && !od.weight) || (ah && ah->coef && !od.coef) || (ah && ah->rank && !od.rank) ||
-        (ah && ah->status && !od.status) || (sum->truth && !sd.truth) || (sum->quant && !sd.quant) || (sum->cdf && !sd.cdf))
-        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    ABC_TRY(rank_summary(ctx, fn, io.X, N, io.Y, N, N, M, P, model, A, t_d, B, B, ex_d, any_excl, K, method, kernel, idx_d, dist_d,
-                         ah ? &od : nullptr, &sd));
-    s.down(idx, idx_d, B * K);
-    s.down(dist, dist_d, B * K);
-    if (ah) {
-        s.down(ah->theta, od.theta, B * K * P);
-        s.down(ah->weight, od.weight, B * K);
-        s.down(ah->coef, od.coef, B * (A + 1) * P);
-        s.down(ah->rank, od.rank, B);
-        s.down(ah->status, od.status, B);
-    }
-    s.down(sum->quant, sd.quant, B * nq * P);
-    s.down(sum->cdf, sd.cdf, B * P);
-    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
+    const TgRequest h{TG_SUMMARY, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, sum};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_summary", h, train_frac, max_comp, rule, ncomp);
 }
 
 static int weighted_summary_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P,
@@ -1652,12 +1584,8 @@ extern "C" int abc_weighted_summary(abc_ctx* ctx, const double* V, size_t K, siz
     Stage s{ctx};
     const double* V_d = s.up(V, K * P);
     const double* w_d = w ? s.up(w, K) : nullptr;
-    abc_summary sd = *sum;
-    sd.truth = sum->truth ? s.up(sum->truth, P) : nullptr;
-    sd.quant = sum->quant ? s.dev<double>(nq * P) : nullptr;
-    sd.cdf = sum->cdf ? s.dev<double>(P) : nullptr;
-    if (!V_d || (w && !w_d) || (sum->truth && !sd.truth) || (sum->quant && !sd.quant) || (sum->cdf && !sd.cdf))
-        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    const abc_summary sd = summary_stage(s, sum, 1, P);
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
     SmValues sv;
     memset(&sv, 0, sizeof(sv));
@@ -1666,8 +1594,7 @@ extern "C" int abc_weighted_summary(abc_ctx* ctx, const double* V, size_t K, siz
     sv.ldv = K;
     sv.w = w_d;
     ABC_TRY(launch_summary(ctx, sv, 1, K, P, &sd));
-    s.down(sum->quant, sd.quant, nq * P);
-    s.down(sum->cdf, sd.cdf, P);
+    summary_down(s, sum, sd, 1, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;

@@ -94,30 +94,47 @@ class Generation:
         return self
 
 
+def _targets_holders(X, targets, Y, exclude, ctx, strict=False):
+    """What the rank_targets family shares: the holders' layout asserts, the sizes, the leading dimensions (ldx, ldy, ldt; a
+    single-column holder counts as dense), exclude as int64 on the device and the context on the current stream.  strict
+    (rank_targets): X and targets have unit stride even with a single column, and Y may be None (P = 0)."""
+    assert X.dim() == 2 and (X.stride(1) == 1 or (not strict and X.shape[1] == 1))
+    assert targets.dim() == 2 and (targets.stride(1) == 1 or (not strict and targets.shape[1] == 1))
+    assert strict or Y is not None
+    M, N = X.shape
+    B = targets.shape[1]
+    P = Y.shape[0] if Y is not None else 0
+    if Y is not None:
+        assert Y.dim() == 2 and Y.shape[1] == N and (Y.stride(1) == 1 or P <= 1)
+    assert targets.shape[0] == M
+    dev = X.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    if exclude is not None:
+        exclude = exclude.to(device=dev, dtype=torch.int64).contiguous()
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ld = (X.stride(0) if M > 1 else N, Y.stride(0) if P > 1 else N, targets.stride(0) if M > 1 else B)
+    return N, M, P, B, dev, ctx, exclude, ld
+
+
+def _adjust_out(names, B, K, P, A, dev):
+    """Device tensors for the named abc_adjust_out members, and the struct that points at them (the other members NULL)."""
+    f64, i32 = torch.float64, torch.int32
+    shapes = dict(theta=((B, K, P), f64), weight=((B, K), f64), coef=((B, A + 1, P), f64), rank=((B,), i32), status=((B,), i32))
+    t = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in names}
+    return t, _lib.AdjustOut(*(t[k].data_ptr() if k in t else None for k in shapes))
+
+
 def rank_targets(X, model, A, targets, K, Y=None, exclude=None, post_mean=False, dist=True, ctx=None):
     """Batched ranking on the device (abc_rank_targets_dev).  X: (M, N) column-major holder (a column-slice view with a row
     stride >= N is fine: ldx = X.stride(0)); model: a finished model record (abc_pls_model_dev [+ abc_pls_wilcoxon_dev]) for
     (M, P, A); targets: (M, B) holder (ldt = targets.stride(0)); Y: (P, N) holder, needed for post_mean; exclude: int64 (B,)
     (-1: none).  Returns (idx (B, K) int64, dist (B, K) or None, post_mean (B, P) or None) as device tensors."""
-    assert X.dim() == 2 and X.stride(1) == 1 and targets.dim() == 2 and targets.stride(1) == 1
-    M, N = X.shape
-    B = targets.shape[1]
-    assert targets.shape[0] == M
-    dev = X.device
-    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
-    P = Y.shape[0] if Y is not None else 0
-    if Y is not None:
-        assert Y.dim() == 2 and Y.shape[1] == N and (Y.stride(1) == 1 or P <= 1)
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx, strict=True)
     idx = torch.empty((B, K), dtype=torch.int64, device=dev)
     d = torch.empty((B, K), dtype=torch.float64, device=dev) if dist else None
     pm = torch.empty((B, P), dtype=torch.float64, device=dev) if post_mean else None
-    if exclude is not None:
-        exclude = exclude.to(device=dev, dtype=torch.int64).contiguous()
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ldy = Y.stride(0) if (Y is not None and P > 1) else N
-    ctx.check(lib().abc_rank_targets_dev(ctx.handle, X.data_ptr(), X.stride(0) if M > 1 else N, _ptr(Y), ldy, N, M, P,
-                                         model.data_ptr(), A, targets.data_ptr(), targets.stride(0) if M > 1 else B, B,
-                                         _ptr(exclude), K, idx.data_ptr(), _ptr(d), _ptr(pm)))
+    ctx.check(lib().abc_rank_targets_dev(ctx.handle, X.data_ptr(), ldx, _ptr(Y), ldy, N, M, P, model.data_ptr(), A,
+                                         targets.data_ptr(), ldt, B, _ptr(exclude), K, idx.data_ptr(), _ptr(d), _ptr(pm)))
     return idx, d, pm
 
 
@@ -126,31 +143,14 @@ def rank_targets_adjust(X, model, A, targets, K, Y, exclude=None, kernel=_lib.KE
     """rank_targets followed by the local-linear adjustment (abc_rank_targets_adjust_dev); Y: (P, N) holder (required).
     Returns dict(idx (B, K) int64, dist (B, K) or None, theta (B, K, P) or None, weight (B, K) or None, coef (B, A + 1, P),
     rank (B,) int32, status (B,) int32) as device tensors."""
-    assert X.dim() == 2 and (X.stride(1) == 1 or X.shape[1] == 1)
-    assert targets.dim() == 2 and (targets.stride(1) == 1 or targets.shape[1] == 1)
-    assert Y is not None and Y.dim() == 2 and Y.shape[1] == X.shape[1] and (Y.stride(1) == 1 or Y.shape[0] <= 1)
-    M, N = X.shape
-    B = targets.shape[1]
-    P = Y.shape[0]
-    assert targets.shape[0] == M
-    dev = X.device
-    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
-    f64 = torch.float64
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
     r = dict(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
-             dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None,
-             theta=torch.empty((B, K, P), dtype=f64, device=dev) if theta else None,
-             weight=torch.empty((B, K), dtype=f64, device=dev) if weight else None,
-             coef=torch.empty((B, A + 1, P), dtype=f64, device=dev),
-             rank=torch.empty(B, dtype=torch.int32, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev))
-    out = _lib.AdjustOut(*(r[k].data_ptr() if r[k] is not None else None for k in ("theta", "weight", "coef", "rank", "status")))
-    if exclude is not None:
-        exclude = exclude.to(device=dev, dtype=torch.int64).contiguous()
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ldy = Y.stride(0) if P > 1 else N
-    ctx.check(lib().abc_rank_targets_adjust_dev(ctx.handle, X.data_ptr(), X.stride(0) if M > 1 else N, Y.data_ptr(), ldy, N, M, P,
-                                                model.data_ptr(), A, targets.data_ptr(), targets.stride(0) if M > 1 else B, B,
-                                                _ptr(exclude), K, int(kernel), r["idx"].data_ptr(), _ptr(r["dist"]),
-                                                C.byref(out)))
+             dist=torch.empty((B, K), dtype=torch.float64, device=dev) if dist else None, theta=None, weight=None)
+    members, out = _adjust_out(("theta",) * bool(theta) + ("weight",) * bool(weight) + ("coef", "rank", "status"), B, K, P, A, dev)
+    r.update(members)
+    ctx.check(lib().abc_rank_targets_adjust_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
+                                                targets.data_ptr(), ldt, B, _ptr(exclude), K, int(kernel), r["idx"].data_ptr(),
+                                                _ptr(r["dist"]), C.byref(out)))
     return r
 
 
@@ -167,15 +167,7 @@ def rank_targets_summary(X, model, A, targets, K, Y, probs=(0.025, 0.5, 0.975), 
     (abc_rank_targets_summary_dev; method 0 rejection, 1 loclinear).  truth: (B, P) row-major device tensor or None.  adjust:
     names of abc_adjust_out members to return as well (method 1: "theta", "weight", "coef", "rank", "status").
     Returns dict(idx (B, K) int64, dist (B, K) or None, quant (B, nq, P), cdf (B, P) or None, and the adjust members)."""
-    assert X.dim() == 2 and (X.stride(1) == 1 or X.shape[1] == 1)
-    assert targets.dim() == 2 and (targets.stride(1) == 1 or targets.shape[1] == 1)
-    assert Y is not None and Y.dim() == 2 and Y.shape[1] == X.shape[1] and (Y.stride(1) == 1 or Y.shape[0] <= 1)
-    M, N = X.shape
-    B = targets.shape[1]
-    P = Y.shape[0]
-    assert targets.shape[0] == M
-    dev = X.device
-    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
     f64 = torch.float64
     nq = len(np.atleast_1d(probs))
     if truth is not None:
@@ -185,20 +177,12 @@ def rank_targets_summary(X, model, A, targets, K, Y, probs=(0.025, 0.5, 0.975), 
              dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None,
              quant=torch.empty((B, nq, P), dtype=f64, device=dev),
              cdf=torch.empty((B, P), dtype=f64, device=dev) if truth is not None else None)
-    shapes = dict(theta=((B, K, P), f64), weight=((B, K), f64), coef=((B, A + 1, P), f64), rank=((B,), torch.int32),
-                  status=((B,), torch.int32))
-    for k in adjust:
-        r[k] = torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev)
-    adj = _lib.AdjustOut(*(r[k].data_ptr() if k in adjust else None for k in ("theta", "weight", "coef", "rank", "status")))
+    members, adj = _adjust_out(adjust, B, K, P, A, dev)
+    r.update(members)
     s, _pr = _summary(probs, truth, r["quant"], r["cdf"])
-    if exclude is not None:
-        exclude = exclude.to(device=dev, dtype=torch.int64).contiguous()
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ldy = Y.stride(0) if P > 1 else N
-    ctx.check(lib().abc_rank_targets_summary_dev(ctx.handle, X.data_ptr(), X.stride(0) if M > 1 else N, Y.data_ptr(), ldy, N, M, P,
-                                                 model.data_ptr(), A, targets.data_ptr(), targets.stride(0) if M > 1 else B, B,
-                                                 _ptr(exclude), K, int(method), int(kernel), r["idx"].data_ptr(), _ptr(r["dist"]),
-                                                 C.byref(adj), C.byref(s)))
+    ctx.check(lib().abc_rank_targets_summary_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
+                                                 targets.data_ptr(), ldt, B, _ptr(exclude), K, int(method), int(kernel),
+                                                 r["idx"].data_ptr(), _ptr(r["dist"]), C.byref(adj), C.byref(s)))
     return r
 
 

@@ -276,6 +276,46 @@ def test_bad_arguments(gpu_ctx):
     refused(dev(o=None), INVALID)
     refused(dev(ldx=N - 1), INVALID)
     refused(dev(A=65), UNSUPPORTED)
+    refused(dev(kernel=-1), INVALID)
+    # what the plain batched ranking refuses (test_gpu_targets.py), on both entries
+    U = lambda v: np.array(v, dtype=np.int64).astype(np.uint64)
+    Tn, Ti = np.array(T), np.array(T)
+    Tn[2, 1], Ti[0, 0] = np.nan, np.inf
+    Tn, Ti = np.asfortranarray(Tn), np.asfortranarray(Ti)
+
+    def host2(K=10, ex=None, Xm=X, Tm=T, idx_=idx):
+        return L.abc_particle_ranking_pls_targets_adjust(gpu_ctx.handle, p(Xm), p(Y), N, M, P, p(Tm), 4, 0.5, 3, 0, p(ex), K, 0,
+                                                         p(idx_), None, C.byref(out), None)
+
+    refused(host2(K=N, ex=U([3, -1, -1, -1])), INVALID)
+    refused(host2(ex=U([N, -1, -1, -1])), INVALID)
+    refused(host2(Xm=None), INVALID)
+    refused(host2(Tm=None), INVALID)
+    refused(host2(idx_=None), INVALID)
+    refused(host2(Tm=Tn), INVALID)
+    refused(host2(Tm=Ti), INVALID)
+    dp = lambda t: t.data_ptr() if t is not None else None
+    exd = lambda v: torch.tensor(v, dtype=torch.int64, device=DEV)
+    Ywd = device.colmajor(Yw, DEV)
+
+    def dev2(B=4, K=10, ex=None, Xm=Xd, Ym=Yd, Pm=P, tg=Td, idx_=ib, md=model, A=3, ldt=4):
+        return L.abc_rank_targets_adjust_dev(gpu_ctx.handle, dp(Xm), N, dp(Ym), N, N, M, Pm, dp(md), A, dp(tg), ldt, B, dp(ex), K, 0,
+                                             dp(idx_), None, C.byref(dout))
+
+    refused(dev2(B=0), INVALID)
+    refused(dev2(K=0), INVALID)
+    refused(dev2(K=N + 1), INVALID)
+    refused(dev2(K=N, ex=exd([3, -1, -1, -1])), INVALID)
+    refused(dev2(ex=exd([N, -1, -1, -1])), INVALID)
+    refused(dev2(Xm=None), INVALID)
+    refused(dev2(tg=None), INVALID)
+    refused(dev2(idx_=None), INVALID)
+    refused(dev2(md=None), INVALID)
+    refused(dev2(ldt=3), INVALID)
+    refused(dev2(A=0), INVALID)
+    refused(dev2(Ym=Ywd, Pm=1025), UNSUPPORTED)
+    refused(dev2(tg=device.colmajor(Tn, DEV)), INVALID)
+    refused(dev2(tg=device.colmajor(Ti, DEV)), INVALID)
     # the context stays usable
     from abcsmc_amd import abcutil
     a = abcutil.particle_ranking_PLS_targets_adjust(X, Y, T, 0.5, 10, max_comp=3, rule=0, ctx=gpu_ctx)

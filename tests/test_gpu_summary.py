@@ -280,6 +280,54 @@ def test_argument_errors(ctx):
     rc = L.abc_rank_targets_summary_dev(ctx.handle, F["Xd"].data_ptr(), 800, F["Yd"].data_ptr(), 800, 800, 5, 3,
                                         F["model"].data_ptr(), 3, Td.data_ptr(), 4, 4, None, 50, 0, 0, None, None, None, None)
     assert rc != 0                                           # sum NULL
+    # every refusal of the ranking, the adjustment and the summaries, on the device and the host entry
+    INVALID, UNSUPPORTED = -1, -4
+    N, M, P = 800, 5, 3
+    Xf, Yf, Tf = np.asfortranarray(X), np.asfortranarray(Y), np.asfortranarray(T)
+    Yw = np.asfortranarray(np.random.default_rng(0).standard_normal((N, 1025)))
+    Tn, Ti = np.array(T), np.array(T)
+    Tn[2, 1], Ti[0, 0] = np.nan, np.inf
+    hq, hcdf = np.empty(4 * 65 * 3), np.empty(4 * 3)
+    hp = lambda v: v.ctypes.data_as(C.c_void_p) if v is not None else None
+    dp = lambda t: t.data_ptr() if t is not None else None
+    q65 = torch.empty(4 * 65 * 3, dtype=torch.float64, device=DEV)
+    levels, l_high, l_low, l_nan = np.full(65, 0.5), np.array([0.5, 1.5]), np.array([-0.1]), np.array([0.5, np.nan])
+
+    def summary(quant, probs=levels, nq=1, cdf=None):
+        return _lib.Summary(probs.ctypes.data if probs is not None else None, nq, None, quant, cdf)
+
+    def host(B=4, K=50, ex=None, Xm=Xf, Ym=Yf, Pm=P, Tm=Tf, mc=3, method=0, kernel=0, sm=summary(hp(hq))):
+        return L.abc_particle_ranking_pls_targets_summary(ctx.handle, hp(Xm), hp(Ym), N, M, Pm, hp(Tm), B, 0.5, mc, 0, hp(ex), K,
+                                                          method, kernel, None, None, None, C.byref(sm) if sm is not None else None,
+                                                          None)
+
+    def dev(B=4, K=50, ex=None, Xm=F["Xd"], Ym=F["Yd"], Pm=P, tg=Td, md=F["model"], A=3, ldx=N, ldy=N, ldt=4, method=0, kernel=0,
+            sm=summary(q65.data_ptr())):
+        return L.abc_rank_targets_summary_dev(ctx.handle, dp(Xm), ldx, dp(Ym), ldy, N, M, Pm, dp(md), A, dp(tg), ldt, B, dp(ex), K,
+                                              method, kernel, None, None, None, C.byref(sm) if sm is not None else None)
+
+    def refused(rc, code):
+        assert rc == code, rc
+        assert L.abc_last_error(ctx.handle)
+
+    U = lambda v: np.array(v, dtype=np.int64).astype(np.uint64)
+    exd = lambda v: torch.tensor(v, dtype=torch.int64, device=DEV)
+    for call, buf, cdfbuf, ex, arr in ((host, hp(hq), hp(hcdf), U, np.asfortranarray),
+                                       (dev, q65.data_ptr(), cdf.data_ptr(), exd, lambda t: device.colmajor(t, DEV))):
+        for bad in (dict(B=0), dict(K=0), dict(K=N + 1), dict(K=N, ex=ex([3, -1, -1, -1])), dict(ex=ex([N, -1, -1, -1])),
+                    dict(Xm=None), dict(Ym=None), dict(method=2), dict(method=-1), dict(kernel=2), dict(kernel=-1), dict(sm=None),
+                    dict(sm=summary(buf, nq=0)), dict(sm=summary(buf, nq=65)), dict(sm=summary(buf, probs=None)),
+                    dict(sm=summary(buf, probs=l_high, nq=2)), dict(sm=summary(buf, probs=l_low)),
+                    dict(sm=summary(buf, probs=l_nan, nq=2)), dict(sm=summary(buf, cdf=cdfbuf))):
+            refused(call(**bad), INVALID)
+        refused(call(**{"Tm" if call is host else "tg": None}), INVALID)
+        refused(call(**{"Tm" if call is host else "tg": arr(Tn)}), INVALID)
+        refused(call(**{"Tm" if call is host else "tg": arr(Ti)}), INVALID)
+        refused(call(**{"mc" if call is host else "A": 65}), UNSUPPORTED)
+    refused(host(Ym=Yw, Pm=1025), UNSUPPORTED)
+    refused(dev(Ym=device.colmajor(Yw, DEV), Pm=1025), UNSUPPORTED)
+    for bad in (dict(ldx=N - 1), dict(ldy=N - 1), dict(ldt=3), dict(md=None), dict(A=0)):
+        refused(dev(**bad), INVALID)
     V = np.random.default_rng(0).normal(size=(100, 2))
     for bad_w in (-np.ones(100), np.zeros(100), np.where(np.arange(100) == 7, np.nan, 1.0), np.where(np.arange(100) == 7, np.inf, 1.0)):
         with pytest.raises(RuntimeError):

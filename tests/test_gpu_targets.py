@@ -277,8 +277,8 @@ def test_bad_arguments(gpu_ctx):
     idx = np.empty(4 * N, dtype=np.uint64)
     p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
 
-    def call(B=4, K=10, ex=None, Tm=T, Xm=X, idx_=idx):
-        return L.abc_particle_ranking_pls_targets(gpu_ctx.handle, p(Xm), p(Y), N, M, P, p(Tm), B, 0.5, 3, 0, p(ex), K, p(idx_),
+    def call(B=4, K=10, ex=None, Tm=T, Xm=X, idx_=idx, Ym=Y):
+        return L.abc_particle_ranking_pls_targets(gpu_ctx.handle, p(Xm), p(Ym), N, M, P, p(Tm), B, 0.5, 3, 0, p(ex), K, p(idx_),
                                                   None, None, None)
 
     def invalid(rc):
@@ -312,6 +312,25 @@ def test_bad_arguments(gpu_ctx):
     invalid(dev(pm=ib.data_ptr()))                       # post_mean without Y
     invalid(dev(md=None))
     invalid(dev(tg=None))
+    # each entry also refuses what the other one was shown to refuse above
+    invalid(call(Tm=None))
+    invalid(call(Ym=None))
+    Yd = device.colmajor(Y, "cuda:0")
+    invalid(dev(Ym=Yd.data_ptr(), ldy=N - 1, pm=ib.data_ptr()))
+    dp = lambda t: t.data_ptr() if t is not None else None
+    exd = lambda v: torch.tensor(v, dtype=torch.int64, device="cuda:0")
+    dev2 = lambda B=4, K=10, ex=None, Xm=Xd, idx_=ib, tg=Td, A=3: L.abc_rank_targets_dev(
+        gpu_ctx.handle, dp(Xm), N, None, N, N, M, P, model.data_ptr(), A, tg.data_ptr(), 4, B, dp(ex), K, dp(idx_), None, None)
+    invalid(dev2(B=0))
+    invalid(dev2(K=0))
+    invalid(dev2(K=N + 1))
+    invalid(dev2(K=N, ex=exd([3, -1, -1, -1])))
+    invalid(dev2(ex=exd([N, -1, -1, -1])))
+    invalid(dev2(Xm=None))
+    invalid(dev2(idx_=None))
+    invalid(dev2(A=0))
+    invalid(dev2(tg=device.colmajor(Tn, "cuda:0")))
+    invalid(dev2(tg=device.colmajor(Ti, "cuda:0")))
     # the context stays usable
     g = _batched(gpu_ctx, X, Y, T, 0.5, 3, 0, 10)
     s = _single(gpu_ctx, X, Y, T[0], 0.5, 3, 0, 10)
