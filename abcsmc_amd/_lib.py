@@ -83,6 +83,13 @@ class Summary(C.Structure):
     _fields_ = [("probs", C.c_void_p), ("nq", C.c_size_t), ("truth", C.c_void_p), ("quant", C.c_void_p), ("cdf", C.c_void_p)]
 
 
+class Density(C.Structure):
+    """abc_density: G, cut, bw_scale, then bw (optional input) and the optional outputs dens / grid / bw_out / mode / mode_dens
+    (memory as the entry point's other arrays)"""
+    _fields_ = [("G", C.c_size_t), ("cut", C.c_double), ("bw_scale", C.c_double), ("bw", C.c_void_p), ("dens", C.c_void_p),
+                ("grid", C.c_void_p), ("bw_out", C.c_void_p), ("mode", C.c_void_p), ("mode_dens", C.c_void_p)]
+
+
 ALL_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 BROADCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -141,6 +148,12 @@ SIGNATURES = {
                                                       _vp, _vp, _vp, _vp]),
     "abc_weighted_summary_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_weighted_summary": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "abc_rank_targets_density_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _i, _vp,
+                                          _vp, _vp, _vp]),
+    "abc_particle_ranking_pls_targets_density": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _i, _vp,
+                                                      _vp, _vp, _vp, _vp]),
+    "abc_weighted_density_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    "abc_weighted_density": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "abc_particle_ranking_simple": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_calculate_doubled_variance": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "abc_weight_predictive_prior_uniform": (_i, [_vp, _sz, _vp]),

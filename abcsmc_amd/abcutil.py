@@ -197,6 +197,68 @@ def weighted_summary(values, weights=None, probs=(0.025, 0.5, 0.975), truth=None
     return dict(quant=quant, cdf=cdf)
 
 
+def _density_arg(G, cut, bw_scale, bw, ns, lead):
+    """Host arrays for ns segments (shaped lead + ...) and the abc_density pointing at them"""
+    G = int(G)
+    b = None
+    if bw is not None:
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(bw, dtype=np.float64), lead).reshape(ns))
+    o = dict(dens=np.empty(lead + (G,)), grid=np.empty(lead + (2,)), bw=np.empty(lead), mode=np.empty(lead),
+             mode_dens=np.empty(lead))
+    d = _lib.Density(G, float(cut), float(bw_scale), _p(b), _p(o["dens"]), _p(o["grid"]), _p(o["bw"]), _p(o["mode"]),
+                     _p(o["mode_dens"]))
+    return d, o, b
+
+
+def _grid_points(grid, G):
+    """x (..., G) from grid (..., 2) = lo_x, step: x_g = lo_x + g * step in float64, within one rounding of the device's
+    fma(g, step, lo_x) (which is what mode holds)"""
+    return grid[..., 0:1] + np.arange(G, dtype=np.float64) * grid[..., 1:2]
+
+
+def particle_ranking_PLS_targets_density(X_orig, Y_orig, targets, training_fraction, K, G=512, cut=3.0, bw=None, bw_scale=1.0,
+                                         method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
+                                         rule=_lib.RULE_DEFAULT, dens=True, ctx=None):
+    """particle_ranking_PLS_targets followed by the weighted Gaussian kernel density of every (target, parameter) on a grid of G
+    points and the mode taken from it (abc_particle_ranking_pls_targets_density; the definition is in the header: R's density()
+    with bw.nrd0, cut and adjust = bw_scale).  method and kernel as particle_ranking_PLS_targets_summary; bw: given bandwidths
+    (B, P) (or a scalar) in place of the rule.  Returns dict(dens (B, P, G) (None with dens=False), x (B, P, G): the grid points,
+    grid (B, P, 2): lo_x and step, bw (B, P): the bandwidths used, mode (B, P), mode_dens (B, P), idx (B, K), dist (B, K),
+    ncomp)."""
+    ctx = _ctx(ctx)
+    method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
+    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
+    d, o, _b = _density_arg(G, cut, bw_scale, bw, B * P, (B, P))
+    if not dens:
+        d.dens, o["dens"] = None, None
+    idx = np.empty((B, K), dtype=np.uint64)
+    dist = np.empty((B, K))
+    ncomp = C.c_int32(0)
+    ctx.check(lib().abc_particle_ranking_pls_targets_density(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
+                                                             int(max_comp), int(rule), _p(ex), K, method, kernel,
+                                                             _p(idx), _p(dist), None, C.byref(d), C.addressof(ncomp)))
+    o.update(x=_grid_points(o["grid"], int(G)), idx=idx, dist=dist, ncomp=ncomp.value)
+    return o
+
+
+def weighted_density(values, weights=None, G=512, cut=3.0, bw=None, bw_scale=1.0, ctx=None):
+    """The weighted Gaussian kernel density and mode of every column of values (K, P) on the device (abc_weighted_density; the
+    definition is in the header); equal weights when weights is None.  Returns dict(dens (P, G), x (P, G), grid (P, 2), bw (P,),
+    mode (P,), mode_dens (P,))."""
+    ctx = _ctx(ctx)
+    V = _f(values)
+    if V.ndim == 1:
+        V = _f(V.reshape(-1, 1))
+    K, P = V.shape
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    if w is not None and w.size != K:
+        raise ValueError("weights needs one entry per row")
+    d, o, _b = _density_arg(G, cut, bw_scale, bw, P, (P,))
+    ctx.check(lib().abc_weighted_density(ctx.handle, _p(V), K, P, _p(w), C.byref(d)))
+    o["x"] = _grid_points(o["grid"], int(G))
+    return o
+
+
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
                        ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
@@ -207,7 +269,8 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
     the true values do not vary).  method="loclinear": the estimate is instead the local-linear adjusted posterior mean alpha of
     particle_ranking_PLS_targets_adjust (kernel as there), the comparison cv4abc makes between "rejection" and "loclinear".
     statistic="median": the estimate (post_median instead of post_mean) and pred_error come from the posterior median (weighted
-    for loclinear), cv4abc's default.  coverage=True adds truth_cdf (n_targets, P): each left-out row's true parameter's place in
+    for loclinear), cv4abc's default.  statistic="mode": they come from the mode of the weighted kernel density
+    (particle_ranking_PLS_targets_density with its defaults; post_mode).  coverage=True adds truth_cdf (n_targets, P): each left-out row's true parameter's place in
     its own posterior (roughly uniform when calibrated), and ci95 (P,): the fraction of targets whose truth lies in
     [Q(0.025), Q(0.975)]."""
     X, Y = _f(X_orig), _f(Y_orig)
@@ -217,8 +280,8 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
         raise ValueError("n_targets must be in [1, N]")
     if method not in ("rejection", "loclinear"):
         raise ValueError("method must be 'rejection' or 'loclinear'")
-    if statistic not in ("mean", "median"):
-        raise ValueError("statistic must be 'mean' or 'median'")
+    if statistic not in ("mean", "median", "mode"):
+        raise ValueError("statistic must be 'mean', 'median' or 'mode'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
     theta = np.ascontiguousarray(Y[rows])
     sm = None
@@ -228,19 +291,22 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
                                                   max_comp=max_comp, rule=rule, ctx=ctx)
     if statistic == "median":
         r = sm
+    elif statistic == "mode":
+        r = particle_ranking_PLS_targets_density(X, Y, X[rows], training_fraction, K, method=method, kernel=kernel, exclude=rows,
+                                                 max_comp=max_comp, rule=rule, dens=False, ctx=ctx)
     elif method == "rejection":
         r = particle_ranking_PLS_targets(X, Y, X[rows], training_fraction, K, exclude=rows, max_comp=max_comp, rule=rule,
                                          details=True, ctx=ctx)
     else:
         r = particle_ranking_PLS_targets_adjust(X, Y, X[rows], training_fraction, K, exclude=rows, kernel=kernel,
                                                 max_comp=max_comp, rule=rule, theta=False, ctx=ctx)
-    pm = sm["quant"][:, 0, :] if statistic == "median" else r["post_mean"]
+    pm = sm["quant"][:, 0, :] if statistic == "median" else r["mode" if statistic == "mode" else "post_mean"]
     var = theta.var(axis=0, ddof=1) if n_targets > 1 else np.zeros(theta.shape[1])
     sse = ((pm - theta) ** 2).sum(axis=0)
     with np.errstate(divide="ignore", invalid="ignore"):
         err = np.where(var > 0, sse / (n_targets * np.where(var > 0, var, 1.0)), np.nan)
     out = dict(rows=rows, theta=theta, pred_error=err, idx=r["idx"], ncomp=r["ncomp"])
-    out["post_median" if statistic == "median" else "post_mean"] = pm
+    out["post_" + statistic] = pm
     if coverage:
         out["truth_cdf"] = sm["cdf"]
         out["ci95"] = ((sm["quant"][:, 1, :] <= theta) & (theta <= sm["quant"][:, 2, :])).mean(axis=0)

@@ -291,6 +291,11 @@ size_t abc_summary_need(size_t B, size_t K, size_t P);
 int launch_summary(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_summary* sum);
 // generic weights (device): ABC_ERR_INVALID when one is negative or non-finite or all are zero (synchronises)
 int abc_summary_check_weights(abc_ctx*, const double* w, size_t K, const char* fn);
+// weighted posterior densities and modes (density.hip) of the same segments: the quantiles it needs come from launch_summary.
+// abc_density_need: workspace of launch_density (launch_summary's included); dn: every array in device memory; a given
+// bandwidth that is not finite and positive is ABC_ERR_INVALID (checked on the device: synchronises)
+size_t abc_density_need(size_t B, size_t K, size_t P, size_t G);
+int launch_density(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_density* dn, const char* fn);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

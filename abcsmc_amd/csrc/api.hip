@@ -1273,9 +1273,10 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
 }
 
 // ---- batched ranking of many observed targets against one fitted set (targets.hip), optionally followed by the local-linear
-// adjustment (adjust.hip) and the weighted posterior quantiles and CDF (summary.hip): one pipeline behind six entry points ----
+// adjustment (adjust.hip) and the weighted posterior quantiles and CDF (summary.hip) or densities and modes (density.hip): one
+// pipeline behind eight entry points ----
 namespace {
-enum { TG_PLAIN, TG_ADJUST, TG_SUMMARY };      // what follows the ranking: nothing, the adjustment, the summaries
+enum { TG_PLAIN, TG_ADJUST, TG_SUMMARY, TG_DENSITY };      // what follows the ranking: nothing, the adjustment, the summaries, the densities
 struct TgRequest {                             // (members in the order of the entries' arguments)
     int kind;
     const double* X;  size_t ldx;
@@ -1285,14 +1286,16 @@ struct TgRequest {                             // (members in the order of the e
     const double* targets;  size_t ldt, B;
     const uint64_t* exclude;
     size_t K;
-    uint64_t* idx;                             // optional for TG_SUMMARY
+    uint64_t* idx;                             // optional for TG_SUMMARY and TG_DENSITY
     double* dist;                              // optional
     double* post_mean = nullptr;               // TG_PLAIN only, optional
-    int method = 0, kernel = 0;                // method: TG_SUMMARY only (of which values the summaries are)
-    const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; TG_SUMMARY: optional, method 1 only
+    int method = 0, kernel = 0;                // method: TG_SUMMARY and TG_DENSITY only (of which values the summaries are)
+    const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; TG_SUMMARY / TG_DENSITY: optional, method 1 only
     const abc_summary* sum = nullptr;          // TG_SUMMARY only
+    const abc_density* den = nullptr;          // TG_DENSITY only
     bool any_excl = false;                     // exclude names a row for some target: set by tg_check
-    bool regress() const { return kind == TG_ADJUST || (kind == TG_SUMMARY && method == ABC_POSTERIOR_LOCLINEAR); }
+    bool segments() const { return kind == TG_SUMMARY || kind == TG_DENSITY; }      // the rows' values are read after the ranking
+    bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
 };
 }  // namespace
 
@@ -1307,10 +1310,21 @@ static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
     return ABC_OK;
 }
 
+static int density_check(abc_ctx* ctx, const char* fn, const abc_density* den) {
+    if (!den) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (den is required)", fn);
+    if (den->G < 2 || den->G > 4096) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: G = %zu grid points (2 to 4096)", fn, den->G);
+    if (!(den->cut >= 0.0) || !std::isfinite(den->cut)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: cut = %g (finite, >= 0)", fn, den->cut);
+    if (!(den->bw_scale > 0.0) || !std::isfinite(den->bw_scale))
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: bw_scale = %g (finite, > 0)", fn, den->bw_scale);
+    if (!den->dens && !den->grid && !den->bw_out && !den->mode && !den->mode_dens)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of den is NULL", fn);
+    return ABC_OK;
+}
+
 // Argument checks of the family; sets r.any_excl.  host: the arrays are in host memory and the model is fitted by the call
 // (which needs Y); otherwise exclude is brought to the host here, after every check that does not need it.
 static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
-    const bool plain = r.kind == TG_PLAIN, summary = r.kind == TG_SUMMARY;
+    const bool plain = r.kind == TG_PLAIN, summary = r.segments();
     const size_t N = r.N, B = r.B, K = r.K;
     if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
     if (!r.targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (targets is required)", fn);
@@ -1333,7 +1347,8 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
         if (r.A > 64) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: A = %zu components (at most 64)", fn, r.A);
         if (r.P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, r.P);
     }
-    if (summary) ABC_TRY(summary_check(ctx, fn, r.sum));
+    if (r.kind == TG_SUMMARY) ABC_TRY(summary_check(ctx, fn, r.sum));
+    if (r.kind == TG_DENSITY) ABC_TRY(density_check(ctx, fn, r.den));
     if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
     if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
     if (r.M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no metrics (M == 0)", fn);
@@ -1365,7 +1380,9 @@ static size_t tg_need(const TgRequest& r, bool host, int rule) {
     const size_t N = r.N, M = r.M, P = r.P, A = r.A, B = r.B, K = r.K;
     size_t b = abc_targets_need(N, A, B, K, r.any_excl);
     if (r.regress()) b += abc_adjust_need(N, A, P, B, K);
-    if (r.kind == TG_SUMMARY) b += 2 * B * K * 8 + 16 * 256 + abc_summary_need(B, K, P);     // (tg_run's own idx and dist)
+    if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
+    if (r.kind == TG_SUMMARY) b += abc_summary_need(B, K, P);
+    if (r.kind == TG_DENSITY) b += abc_density_need(B, K, P, r.den->G);
     if (!host) return b + abc_ws_need(N, 1, 1, 1, K + 1, 0, 0);
     b += abc_ws_need(N, M, P, A, K + 1, 0, 0) + (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0);
     b += (N * (M + P) + M + 4) * 8;                                               // X, Y, the zero observation and its one idx, dist
@@ -1373,16 +1390,17 @@ static size_t tg_need(const TgRequest& r, bool host, int rule) {
     if (r.kind == TG_PLAIN) b += B * P * 8;                                       // post_mean
     else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
     if (r.kind == TG_SUMMARY) b += B * P * (r.sum->nq + 2) * 8 + 16 * 256;        // truth, quant, cdf
+    if (r.kind == TG_DENSITY) b += B * P * (r.den->G + 6) * 8 + 32 * 256;         // bw, dens, grid, bw_out, mode, mode_dens
     return b;
 }
 
-// The ranking or (regress) the ranking with the adjustment, then the summaries if asked for; device pointers, the workspace reserved.
+// The ranking or (regress) the ranking with the adjustment, then the summaries or densities if asked for; device pointers, the workspace reserved.
 static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
     const size_t B = r.B, K = r.K;
-    const bool summary = r.kind == TG_SUMMARY;
+    const bool summary = r.segments();
     uint64_t* ix = r.idx;
     double* d = r.dist;
-    if (summary) {     // the summaries read both
+    if (summary) {     // the summaries and densities read both
         if (!ix) ix = (uint64_t*)abc_ws_alloc(ctx, B * K * 8);
         if (!d) d = (double*)abc_ws_alloc(ctx, B * K * 8);
         if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
@@ -1406,6 +1424,7 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
     sv.adj = r.regress() ? &keep : nullptr;
     sv.A = (int)r.A;
     sv.kernel = r.kernel;
+    if (r.kind == TG_DENSITY) return launch_density(ctx, sv, B, K, r.P, r.den, fn);
     return launch_summary(ctx, sv, B, K, r.P, r.sum);
 }
 
@@ -1426,6 +1445,25 @@ static abc_summary summary_stage(Stage& s, const abc_summary* h, size_t G, size_
 static void summary_down(Stage& s, const abc_summary* h, const abc_summary& d, size_t G, size_t P) {
     s.down(h->quant, d.quant, G * h->nq * P);
     s.down(h->cdf, d.cdf, G * P);
+}
+
+// an abc_density's arrays for ns segments, host (h) <-> arena: NULL members stay NULL
+static abc_density density_stage(Stage& s, const abc_density* h, size_t ns) {
+    abc_density d = *h;
+    d.bw = h->bw ? s.up(h->bw, ns) : nullptr;
+    d.dens = h->dens ? s.dev<double>(ns * h->G) : nullptr;
+    d.grid = h->grid ? s.dev<double>(ns * 2) : nullptr;
+    d.bw_out = h->bw_out ? s.dev<double>(ns) : nullptr;
+    d.mode = h->mode ? s.dev<double>(ns) : nullptr;
+    d.mode_dens = h->mode_dens ? s.dev<double>(ns) : nullptr;
+    return d;
+}
+static void density_down(Stage& s, const abc_density* h, const abc_density& d, size_t ns) {
+    s.down(h->dens, d.dens, ns * h->G);
+    s.down(h->grid, d.grid, ns * 2);
+    s.down(h->bw_out, d.bw_out, ns);
+    s.down(h->mode, d.mode, ns);
+    s.down(h->mode_dens, d.mode_dens, ns);
 }
 
 // The host entries: h holds host pointers.  Upload, one fit, the request on the arena's copies, downloads, synchronise.
@@ -1474,6 +1512,11 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         sd = summary_stage(s, h.sum, B, P);
         r.sum = &sd;
     }
+    abc_density dd;
+    if (h.den) {
+        dd = density_stage(s, h.den, B * P);
+        r.den = &dd;
+    }
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_TRY(tg_run(ctx, fn, r));
     s.down(h.idx, r.idx, B * K);
@@ -1487,6 +1530,7 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         s.down(ah->status, od.status, B);
     }
     if (h.sum) summary_down(s, h.sum, sd, B, P);
+    if (h.den) density_down(s, h.den, dd, B * P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
@@ -1548,14 +1592,19 @@ extern "C" int abc_particle_ranking_pls_targets_summary(abc_ctx* ctx, const doub
     return tg_host(ctx, "abc_particle_ranking_pls_targets_summary", h, train_frac, max_comp, rule, ncomp);
 }
 
-static int weighted_summary_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P,
-                                  const abc_summary* sum) {
+static int weighted_values_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P) {
     if (!V) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (V is required)", fn);
     if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
     if (P == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: P == 0", fn);
     if (ldv < K) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldv %zu < K %zu", fn, ldv, K);
     if (P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, P);
     if (K >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: K = %zu values (at most 2^32 - 1)", fn, K);
+    return ABC_OK;
+}
+
+static int weighted_summary_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P,
+                                  const abc_summary* sum) {
+    ABC_TRY(weighted_values_check(ctx, fn, V, ldv, K, P));
     return summary_check(ctx, fn, sum);
 }
 
@@ -1595,6 +1644,69 @@ extern "C" int abc_weighted_summary(abc_ctx* ctx, const double* V, size_t K, siz
     sv.w = w_d;
     ABC_TRY(launch_summary(ctx, sv, 1, K, P, &sd));
     summary_down(s, sum, sd, 1, P);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+extern "C" int abc_rank_targets_density_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                            size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                            const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                            const abc_adjust_out* adj, const abc_density* den) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_DENSITY, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, nullptr, den};
+    return tg_dev(ctx, "abc_rank_targets_density_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_density(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                        const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                        const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                                        double* dist, const abc_adjust_out* adj, const abc_density* den,
+                                                        int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_DENSITY, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, nullptr, den};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_density", h, train_frac, max_comp, rule, ncomp);
+}
+
+extern "C" int abc_weighted_density_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
+                                        const abc_density* den) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_weighted_density_dev";
+    ABC_TRY(weighted_values_check(ctx, fn, V, ldv, K, P));
+    ABC_TRY(density_check(ctx, fn, den));
+    ABC_TRY(abc_ws_reserve(ctx, abc_density_need(1, K, P, den->G) + 16 * 256));
+    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
+    SmValues sv;
+    memset(&sv, 0, sizeof(sv));
+    sv.method = 2;
+    sv.V = V;
+    sv.ldv = ldv;
+    sv.w = w;
+    return launch_density(ctx, sv, 1, K, P, den, fn);
+}
+
+extern "C" int abc_weighted_density(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_density* den) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_weighted_density";
+    ABC_TRY(weighted_values_check(ctx, fn, V, K, K, P));
+    ABC_TRY(density_check(ctx, fn, den));
+    ABC_TRY(abc_ws_reserve(ctx, abc_density_need(1, K, P, den->G) + (K * P + K + P * (den->G + 6)) * 8 + 48 * 256));
+    Stage s{ctx};
+    const double* V_d = s.up(V, K * P);
+    const double* w_d = w ? s.up(w, K) : nullptr;
+    const abc_density dd = density_stage(s, den, P);
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
+    SmValues sv;
+    memset(&sv, 0, sizeof(sv));
+    sv.method = 2;
+    sv.V = V_d;
+    sv.ldv = K;
+    sv.w = w_d;
+    ABC_TRY(launch_density(ctx, sv, 1, K, P, &dd, fn));
+    density_down(s, den, dd, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;

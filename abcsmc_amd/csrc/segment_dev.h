@@ -1,0 +1,104 @@
+// How a segment's values and weights are made, shared by summary.hip and density.hip.  A segment is one (target b, parameter j):
+// K values made in registers from the ranking's rows (Y, or the adjusted value theta* of adjust_dev.h, which k_adj_apply computes
+// with the same function), or read from a given matrix.  Both files call these functions, so the quantiles and the densities of
+// a segment see the same bits.
+#pragma once
+#include <string.h>
+
+#include "abc_internal.h"
+#include "adjust_dev.h"
+
+// what a kernel needs to make the values and weights of segment (b0 + blockIdx.y, j); the last three members are the
+// summaries' own inputs and outputs (summary.hip), NULL elsewhere
+struct SmArgs {
+    int method;                 // 0 rejection, 1 loclinear, 2 generic
+    const uint64_t* idx;        // B x K
+    const double* Y;
+    size_t ldy;
+    AjSrc src;                  // method 1: as launch_rank_targets_adjust read the rows
+    const double* O;
+    int KCO, nc, A, P, kernel;
+    const double* coef;
+    const double* dist;
+    const double* V;            // method 2
+    size_t ldv;
+    const double* w;
+    size_t K;
+    const double* truth;        // B x P (device)
+    double* quant;              // B x nq x P
+    double* cdf;                // B x P
+};
+
+struct SmSeg {
+    size_t b;
+    int j;
+    const uint64_t* ix;
+    const double* dd;
+    double h;
+    bool rect;
+    const double* beta;         // method 1: beta_kj at beta[k P]
+    const double* ob;           // method 1: the target's scores
+};
+
+// the value-making members of SmArgs from a caller's SmValues (host)
+static inline SmArgs sm_args(const SmValues& sv, size_t K, size_t P) {
+    SmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.method = sv.method;
+    a.idx = sv.idx;
+    a.Y = sv.Y;
+    a.ldy = sv.ldy;
+    a.A = sv.A;
+    a.P = (int)P;
+    a.kernel = sv.kernel;
+    if (sv.method == 1) {
+        a.src = sv.adj->src;
+        a.O = sv.adj->O;
+        a.KCO = sv.adj->KCO;
+        a.nc = sv.adj->nc;
+        a.coef = sv.adj->coef;
+        a.dist = sv.adj->dist;
+    }
+    a.V = sv.V;
+    a.ldv = sv.ldv;
+    a.w = sv.w;
+    a.K = K;
+    return a;
+}
+
+__device__ __forceinline__ SmSeg sm_seg(const SmArgs& a, size_t b, int j) {
+    SmSeg s;
+    s.b = b;
+    s.j = j;
+    s.ix = a.idx ? a.idx + b * a.K : nullptr;
+    s.dd = nullptr;
+    s.h = 0.0;
+    s.rect = true;
+    s.beta = nullptr;
+    s.ob = nullptr;
+    if (a.method == 1) {
+        s.dd = a.dist + b * a.K;
+        s.h = s.dd[a.K - 1];
+        s.rect = a.kernel == 1 || aj_fallback(s.dd, a.K);
+        s.beta = a.coef + b * (size_t)(a.A + 1) * a.P + a.P + j;
+        s.ob = a.O + b * (size_t)a.KCO;
+    }
+    return s;
+}
+
+__device__ __forceinline__ double sm_value(const SmArgs& a, const SmSeg& s, size_t e) {
+    if (a.method == 0) return a.Y[(size_t)s.ix[e] + a.ldy * (size_t)s.j];
+    if (a.method == 1) {
+        const size_t i = (size_t)s.ix[e];
+        const int nc = a.nc;
+        return aj_adjusted(aj_val(a.src, i, nc + s.j, nc), [&](int k) { return aj_val(a.src, i, k, nc) - s.ob[k]; }, s.beta,
+                           (size_t)a.P, nc);
+    }
+    return a.V[e + a.ldv * (size_t)s.j];
+}
+
+__device__ __forceinline__ double sm_weight(const SmArgs& a, const SmSeg& s, size_t e) {
+    if (a.method == 1) return aj_weight(s.dd[e], s.h, s.rect);
+    if (a.method == 2 && a.w) return a.w[e];
+    return 1.0;
+}

@@ -1,6 +1,5 @@
 // Weighted posterior quantiles and CDF of segments (abc_rank_targets_summary_dev, abc_weighted_summary_dev; the definition is in
-// the header).  A segment is one (target b, parameter j): K values made in registers from the ranking's rows (Y, or the adjusted
-// value theta* of adjust_dev.h, which k_adj_apply computes with the same function), or read from a given matrix.
+// the header).  A segment is one (target b, parameter j); its K values and weights are made by segment_dev.h.
 //
 // The key of a value is its order-preserving 64-bit image (IEEE totalOrder); an entry of weight 0 gets the key ~0 and sorts
 // behind every finite value.  A segment's entries are sorted by (key, e), then one pass in tiles of SM_TILE sorted entries makes
@@ -17,7 +16,7 @@
 #include <math.h>
 
 #include "abc_internal.h"
-#include "adjust_dev.h"
+#include "segment_dev.h"
 
 namespace {
 
@@ -35,74 +34,6 @@ struct SmProbs {
     double q[SM_MAXQ];
     int nq;
 };
-
-// what a kernel needs to make the values and weights of segment (b0 + blockIdx.y, j) and to write its outputs
-struct SmArgs {
-    int method;                 // 0 rejection, 1 loclinear, 2 generic
-    const uint64_t* idx;        // B x K
-    const double* Y;
-    size_t ldy;
-    AjSrc src;                  // method 1: as launch_rank_targets_adjust read the rows
-    const double* O;
-    int KCO, nc, A, P, kernel;
-    const double* coef;
-    const double* dist;
-    const double* V;            // method 2
-    size_t ldv;
-    const double* w;
-    size_t K;
-    const double* truth;        // B x P (device)
-    double* quant;              // B x nq x P
-    double* cdf;                // B x P
-};
-
-struct SmSeg {
-    size_t b;
-    int j;
-    const uint64_t* ix;
-    const double* dd;
-    double h;
-    bool rect;
-    const double* beta;         // method 1: beta_kj at beta[k P]
-    const double* ob;           // method 1: the target's scores
-};
-
-__device__ __forceinline__ SmSeg sm_seg(const SmArgs& a, size_t b, int j) {
-    SmSeg s;
-    s.b = b;
-    s.j = j;
-    s.ix = a.idx ? a.idx + b * a.K : nullptr;
-    s.dd = nullptr;
-    s.h = 0.0;
-    s.rect = true;
-    s.beta = nullptr;
-    s.ob = nullptr;
-    if (a.method == 1) {
-        s.dd = a.dist + b * a.K;
-        s.h = s.dd[a.K - 1];
-        s.rect = a.kernel == 1 || aj_fallback(s.dd, a.K);
-        s.beta = a.coef + b * (size_t)(a.A + 1) * a.P + a.P + j;
-        s.ob = a.O + b * (size_t)a.KCO;
-    }
-    return s;
-}
-
-__device__ __forceinline__ double sm_value(const SmArgs& a, const SmSeg& s, size_t e) {
-    if (a.method == 0) return a.Y[(size_t)s.ix[e] + a.ldy * (size_t)s.j];
-    if (a.method == 1) {
-        const size_t i = (size_t)s.ix[e];
-        const int nc = a.nc;
-        return aj_adjusted(aj_val(a.src, i, nc + s.j, nc), [&](int k) { return aj_val(a.src, i, k, nc) - s.ob[k]; }, s.beta,
-                           (size_t)a.P, nc);
-    }
-    return a.V[e + a.ldv * (size_t)s.j];
-}
-
-__device__ __forceinline__ double sm_weight(const SmArgs& a, const SmSeg& s, size_t e) {
-    if (a.method == 1) return aj_weight(s.dd[e], s.h, s.rect);
-    if (a.method == 2 && a.w) return a.w[e];
-    return 1.0;
-}
 
 __device__ __forceinline__ unsigned long long sm_key(double v) {
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
@@ -357,27 +288,7 @@ size_t abc_summary_need(size_t B, size_t K, size_t P) {
 
 int launch_summary(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const abc_summary* sum) {
     if ((!sum->quant && !sum->cdf) || B == 0 || K == 0 || P == 0) return ABC_OK;
-    SmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.method = sv.method;
-    a.idx = sv.idx;
-    a.Y = sv.Y;
-    a.ldy = sv.ldy;
-    a.A = sv.A;
-    a.P = (int)P;
-    a.kernel = sv.kernel;
-    if (sv.method == 1) {
-        a.src = sv.adj->src;
-        a.O = sv.adj->O;
-        a.KCO = sv.adj->KCO;
-        a.nc = sv.adj->nc;
-        a.coef = sv.adj->coef;
-        a.dist = sv.adj->dist;
-    }
-    a.V = sv.V;
-    a.ldv = sv.ldv;
-    a.w = sv.w;
-    a.K = K;
+    SmArgs a = sm_args(sv, K, P);
     a.truth = sum->truth;
     a.quant = sum->quant;
     a.cdf = sum->cdf;

@@ -430,6 +430,59 @@ inline Mat2D weighted_quantiles(const Mat2D& values, const std::vector<double>& 
         for (size_t j = 0; j < P; j++) out(k, j) = q[k * P + j];
     return out;
 }
+// The same ranking followed by the weighted Gaussian kernel density of every (target, parameter) on G grid points and the mode
+// taken from it (abc_particle_ranking_pls_targets_density: R's density() with bw.nrd0; bw_scale is R's adjust).  Per target:
+// dens (P x G), lo_x / step / bw / mode / mode_dens (P each); the grid points are x_g = fma(g, step, lo_x).
+struct TargetDensity {
+    Mat2D dens;
+    std::vector<double> lo_x, step, bw, mode, mode_dens;
+};
+namespace detail {
+inline TargetDensity target_density(const double* dens, const double* grid, const double* bw, const double* mode,
+                                    const double* mode_dens, size_t P, size_t G) {
+    TargetDensity r;
+    r.dens = Mat2D(P, G);
+    r.lo_x.resize(P);
+    r.step.resize(P);
+    for (size_t j = 0; j < P; j++) {
+        for (size_t g = 0; g < G; g++) r.dens(j, g) = dens[j * G + g];
+        r.lo_x[j] = grid[2 * j];
+        r.step[j] = grid[2 * j + 1];
+    }
+    r.bw.assign(bw, bw + P);
+    r.mode.assign(mode, mode + P);
+    r.mode_dens.assign(mode_dens, mode_dens + P);
+    return r;
+}
+}  // namespace detail
+inline std::vector<TargetDensity> particle_ranking_PLS_targets_density(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                       const float_type train_frac, size_t K, size_t G = 512,
+                                                                       double cut = 3.0, double bw_scale = 1.0, int method = 0,
+                                                                       int kernel = 0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols(), ns = B * P;
+    std::vector<double> dens(ns * G), grid(ns * 2), bw(ns), mode(ns), md(ns);
+    abc_density den = {G, cut, bw_scale, nullptr, dens.data(), grid.data(), bw.data(), mode.data(), md.data()};
+    check(abc_particle_ranking_pls_targets_density(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac,
+                                                   max_components_ref(), component_rule(), nullptr, K, method, kernel, nullptr, nullptr,
+                                                   nullptr, &den, nullptr));
+    std::vector<TargetDensity> res(B);
+    for (size_t b = 0; b < B; b++)
+        res[b] = detail::target_density(dens.data() + b * P * G, grid.data() + b * P * 2, bw.data() + b * P, mode.data() + b * P,
+                                        md.data() + b * P, P, G);
+    return res;
+}
+// The weighted kernel density and mode of every column of values (K x P; weights: K entries, or empty for equal weights)
+// (abc_weighted_density).
+inline TargetDensity weighted_density(const Mat2D& values, const std::vector<double>& weights, size_t G = 512, double cut = 3.0,
+                                      double bw_scale = 1.0) {
+    const size_t K = values.rows(), P = values.cols();
+    if (!weights.empty() && weights.size() != K) throw HipError(ABC_ERR_INVALID, "weights needs one entry per row");
+    std::vector<double> dens(P * G), grid(P * 2), bw(P), mode(P), md(P);
+    abc_density den = {G, cut, bw_scale, nullptr, dens.data(), grid.data(), bw.data(), mode.data(), md.data()};
+    check(abc_weighted_density(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &den));
+    return detail::target_density(dens.data(), grid.data(), bw.data(), mode.data(), md.data(), P, G);
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

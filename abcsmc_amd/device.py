@@ -208,3 +208,54 @@ def weighted_summary(V, w=None, probs=(0.025, 0.5, 0.975), truth=None, ctx=None)
     ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     ctx.check(lib().abc_weighted_summary_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(s)))
     return r
+
+
+def _density(G, cut, bw_scale, bw, lead, dev, dens, mode):
+    """Device tensors for ns = prod(lead) segments and the abc_density pointing at them (bw: given bandwidths or None)"""
+    f64 = torch.float64
+    G = int(G)
+    if bw is not None:
+        bw = torch.as_tensor(bw, dtype=f64).to(dev).expand(lead).contiguous()
+    r = dict(dens=torch.empty(lead + (G,), dtype=f64, device=dev) if dens else None,
+             grid=torch.empty(lead + (2,), dtype=f64, device=dev), bw=torch.empty(lead, dtype=f64, device=dev),
+             mode=torch.empty(lead, dtype=f64, device=dev) if mode else None,
+             mode_dens=torch.empty(lead, dtype=f64, device=dev) if mode else None)
+    d = _lib.Density(G, float(cut), float(bw_scale), _ptr(bw), _ptr(r["dens"]), _ptr(r["grid"]), _ptr(r["bw"]), _ptr(r["mode"]),
+                     _ptr(r["mode_dens"]))
+    return d, r, bw
+
+
+def rank_targets_density(X, model, A, targets, K, Y, G=512, cut=3.0, bw=None, bw_scale=1.0, method=_lib.POSTERIOR_REJECTION,
+                         kernel=_lib.KERNEL_EPANECHNIKOV, exclude=None, dist=False, adjust=(), dens=True, mode=True, ctx=None):
+    """rank_targets followed by the weighted kernel density on G grid points and the mode of every (target, parameter)
+    (abc_rank_targets_density_dev; method 0 rejection, 1 loclinear).  bw: given bandwidths (B, P) or None (the bw.nrd0 rule times
+    bw_scale).  adjust: names of abc_adjust_out members to return as well (method 1).  Returns dict(idx (B, K) int64, dist (B, K)
+    or None, dens (B, P, G) or None, grid (B, P, 2): lo_x and step (x_g = fma(g, step, lo_x)), bw (B, P): the bandwidths used,
+    mode and mode_dens (B, P) or None, and the adjust members)."""
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
+    d, r, _bw = _density(G, cut, bw_scale, bw, (B, P), dev, dens, mode)
+    r.update(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
+             dist=torch.empty((B, K), dtype=torch.float64, device=dev) if dist else None)
+    members, adj = _adjust_out(adjust, B, K, P, A, dev)
+    r.update(members)
+    ctx.check(lib().abc_rank_targets_density_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
+                                                 targets.data_ptr(), ldt, B, _ptr(exclude), K, int(method), int(kernel),
+                                                 r["idx"].data_ptr(), _ptr(r["dist"]), C.byref(adj), C.byref(d)))
+    return r
+
+
+def weighted_density(V, w=None, G=512, cut=3.0, bw=None, bw_scale=1.0, dens=True, mode=True, ctx=None):
+    """The weighted kernel density and mode of P columns of K values (abc_weighted_density_dev).  V: (P, K) holder as
+    weighted_summary's; w: K weights or None (equal); bw: P given bandwidths or None.  Returns dict(dens (P, G) or None,
+    grid (P, 2), bw (P,), mode and mode_dens (P,) or None) as device tensors."""
+    assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
+    P, K = V.shape
+    dev = V.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    if w is not None:
+        w = w.to(device=dev, dtype=torch.float64).contiguous()
+        assert w.numel() == K
+    d, r, _bw = _density(G, cut, bw_scale, bw, (P,), dev, dens, mode)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx.check(lib().abc_weighted_density_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(d)))
+    return r

@@ -474,6 +474,64 @@ int abc_weighted_summary_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K
 /* HOST-pointer form: V is K x P column-major (ldv = K); w, truth, quant and cdf in host memory. */
 int abc_weighted_summary(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_summary* sum);
 
+/* ---- weighted posterior densities and modes of the batched ranking -----------------------------------------------------------
+ * The marginal posterior density of every segment on a grid, a Gaussian kernel estimate as R's density() with bw.nrd0, and the
+ * mode taken from it (summary.abc's "Weighted Mode").  A segment is that of the summaries above: values v_e and weights w_e,
+ * e = 0..K-1 in the ranking's row order, exclusion applied; method 0 (rejection): Y rows, w = 1; method 1 (loclinear): theta*_e
+ * with the adjustment's weights, the same bits as abc_adjust_out.theta / .weight; generic (abc_weighted_density*): V[e + ldv j],
+ * w[e] (1 when w is NULL).  Only entries with w_e > 0 count.  If any value of a segment is non-finite, every output of that segment
+ * is NaN (other segments are unaffected).
+ *   moments     over the entries with w_e > 0: W = sum w, S2 = sum w^2, mean m = sum w v / W, n_eff = W^2 / S2,
+ *               s^2 = sum w (v - m)^2 / (W - S2 / W): the n - 1 variance when the weights are equal; s = 0 when that denominator
+ *               is <= 0 (a single entry).  The centred sum is taken about m in a second pass (the device: about u_min plus the
+ *               mean of v - u_min), never as sum w v^2 - (sum w v)^2 / W.
+ *   bandwidth   R's bw.nrd0: IQR = Q(0.75) - Q(0.25) by the weighted quantile definition above; lo = min(s, IQR / 1.34); if lo is
+ *               0, lo = s; if that is 0, lo = |v of the first entry with w > 0 in ranking order|; if that is 0, lo = 1;
+ *               h = bw_scale * 0.9 * lo * n_eff^(-1/5).  A given bandwidth (bw, one per segment) replaces the rule; bw_scale is
+ *               not applied to it.  Two deviations from R: the IQR is type 5 here (R: type 7), and n_eff stands for length(x)
+ *               (with equal weights n_eff = n).
+ *   grid        u_min, u_max: the smallest and largest value with w > 0 (Q(0), Q(1)); lo_x = u_min - cut * h;
+ *               step = ((u_max + cut * h) - lo_x) / (G - 1); x_g = fma((double)g, step, lo_x), g = 0..G-1.
+ *   density     f(x_g) = sum_e w_e exp(-((x_g - v_e) / h)^2 / 2) / (W h sqrt(2 pi))
+ *   mode        g* = the smallest g at which the device's own f is largest; mode = x_{g*}, mode_dens = f(x_{g*}).
+ * Accuracy: |f_dev - f_ref| <= 1e-6 f_ref(x_g) + 1e-290 max_g f_ref, f_ref the long-double evaluation of the density at the
+ * device's own h and grid (1e-6: the project's parity tolerance for weights).  The kernel's argument is formed in fp64; only the
+ * factor 2^r, |r| <= 1/2, of each exponential is taken in f32.  bw_out agrees with a long-double evaluation of the rule to the
+ * rounding of fixed-order sums of K terms and of the quantiles.
+ * The order of every sum depends on (K, G) only and no floating-point atomics are involved: a target's outputs are the same bits
+ * on a repeat run, alone (B = 1) and in any batch, through the device and host entry points, and whether or not dens is asked for.
+ * This has not been checked against R.
+ * Segment order: B x P row-major (as quant / cdf), P segments for the generic entry.  Limits as the summaries'. */
+typedef struct {
+    size_t G;            /* 2..4096 grid points per segment                                                                  */
+    double cut;          /* finite, >= 0 (R: 3)                                                                              */
+    double bw_scale;     /* finite, > 0 (R's adjust; 1)                                                                      */
+    const double* bw;    /* optional: given bandwidths, one per segment, finite and > 0                                      */
+    double* dens;        /* optional: [segment][g]                                                                           */
+    double* grid;        /* optional: [segment][2] = lo_x, step                                                              */
+    double* bw_out;      /* optional: h used                                                                                 */
+    double* mode;        /* optional                                                                                         */
+    double* mode_dens;   /* optional                                                                                         */
+} abc_density;           /* memory of every array as the entry point's other arrays                                          */
+/* Device pointers; the arguments of abc_rank_targets_summary_dev with den in place of sum.  idx, dist and adj are optional and
+ * receive the bits of the plain calls.  Besides the ranking's, the adjustment's and the method / kernel checks, ABC_ERR_INVALID
+ * for NULL den, G outside 2..4096, cut negative or non-finite, bw_scale <= 0 or non-finite, every output member NULL, and a given
+ * bandwidth that is <= 0 or non-finite (checked on the device; the call then synchronises). */
+int abc_rank_targets_density_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                 size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                 const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                 const abc_adjust_out* adj, const abc_density* den);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_summary); every array of adj and den in host memory. */
+int abc_particle_ranking_pls_targets_density(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                             const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                             const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                             double* dist, const abc_adjust_out* adj, const abc_density* den, int32_t* ncomp);
+/* The same densities of P given columns of K values (as abc_weighted_summary_dev, with its checks of V, ldv, K, P and w). */
+int abc_weighted_density_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
+                             const abc_density* den);
+/* HOST-pointer form: V is K x P column-major (ldv = K); w and den's arrays in host memory. */
+int abc_weighted_density(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_density* den);
+
 /* ======================================================================================== */
 /* Multi-GPU: rows (particles) sharded over several GPUs of one node             */
 /* ======================================================================================== */
