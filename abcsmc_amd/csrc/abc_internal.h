@@ -176,6 +176,16 @@ struct StageTimer {
         if (rc_ != ABC_OK) return rc_; \
     } while (0)
 
+// Scoped stream switch: the launchers queue on the context's stream, so work for another stream (side, cascade) is queued with
+// that stream installed; the previous one is back when the scope ends, whichever way it is left
+struct StreamScope {
+    abc_ctx* ctx; hipStream_t prev;
+    StreamScope(abc_ctx* c, hipStream_t s) : ctx(c), prev(c->stream) { c->stream = s; }
+    ~StreamScope() { ctx->stream = prev; }
+    StreamScope(const StreamScope&) = delete;
+    StreamScope& operator=(const StreamScope&) = delete;
+};
+
 // ---- workspace ------------------------------------------------------------------------
 int abc_ws_reserve(abc_ctx* ctx, size_t bytes);           // may reallocate; resets the arena
 void* abc_ws_alloc(abc_ctx* ctx, size_t bytes);           // 256-B aligned bump; NULL if exhausted
@@ -465,6 +475,34 @@ int launch_perturb(abc_ctx*, const abc_rng* rng, const double* theta, size_t K, 
                    const abc_prior* priors, const uint64_t* parent, uint64_t i0, size_t n,
                    int multivariate, const double* L_or_dv, double* out, uint64_t* seeds,
                    uint64_t seed_stream_offset, const abc_perturb_prep* prep = nullptr);
+
+// ---- the tail of a generation, shared by the fused and the sharded driver (resample.hip): from "the K winners' rows are in theta"
+// to "the proposals are written".  The drivers keep their own conditions and call positions.
+// The posterior's moments and what follows from them (doubled variance, proposal factor, the perturbation's row-major copy and
+// padded factor, the status words into the pinned block) on the SIDE stream: allocates the factor (L_io or arena) and the
+// perturbation's inputs, orders the side stream behind ev_theta (recorded here unless theta_ev_bound: the kernel that wrote theta
+// carries it), queues launch_theta_stats + launch_post_tail there and records ev_moments.  who: prefix of the messages.
+struct abc_side_moments { abc_theta_fused out; double* stats; double* L; };
+int abc_moments_on_side(abc_ctx* ctx, const double* theta, size_t K, size_t P, bool multivariate, double* L_io, double* dv,
+                        int* spd_dev, const double* model_hdr, bool theta_ev_bound, const char* who, abc_side_moments* m);
+// AbcUtil.cpp:583 in front of launch_resample over Nn draws: *w_on_host says whether the normalised weights were mirrored into the
+// pinned scratch (weights_on_host there)
+int abc_normalize_for_resample(abc_ctx* ctx, double* w, size_t K, size_t Nn, const double* sumsq, bool* w_on_host);
+// launch_resample's while_host_builds of both drivers: GPU work that does not need the alias table.  moments: the posterior's
+// moments were deferred to here (theta_stats, dv, L, prep and the status words are then outputs); L == NULL: independent noise, or
+// the factor is there already; i0 / seed_off: this caller's slice of the proposals and the length of the seed stream's first half
+struct abc_prep_arg {
+    abc_ctx* ctx; const abc_rng* rng; const double* theta; const double* theta_stats; size_t K, P, Nn;
+    uint64_t i0, seed_off; uint64_t* seeds; abc_perturb_prep* prep; double* L; int* spd_dev; double* dv; bool moments;
+    const double* model_hdr; double* hdr_pin; int* spd_pin;
+};
+int abc_prep_hook(void* prep_arg);
+// the device build of the resampling table did not verify: the draws and the proposals of rows i0 .. i0 + Nn - 1 once more with the
+// table from the host, from the rng of the generation's entry, then a synchronisation (the weights are final; only what depends
+// on the table is repeated).  giveups_to_snapshot: the proposals' give-up counter goes back to the gather's snapshot first.
+int abc_alias_repair(abc_ctx* ctx, const abc_rng* rng_entry, const double* w, size_t K, uint64_t i0, size_t Nn, uint64_t seed_off,
+                     uint64_t* parent, const double* theta, size_t P, const abc_prior* priors, int multivariate, const double* L_or_dv,
+                     double* next, abc_perturb_prep* prep, bool giveups_to_snapshot);
 
 // reference-stream proposals (host loop, refstream_host.cpp): rng = state after the n resampling draws, advanced past all it consumes
 int launch_perturb_reference(abc_ctx*, abc_rng* rng_after_draws, const double* theta, size_t K, size_t P, const abc_prior* priors,

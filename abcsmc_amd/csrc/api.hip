@@ -642,11 +642,10 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         // ONE pass over X for both: the ranking's projection (main stream) also writes the validation rows' scores, all A
         // components, and the cascade's sweeps wait for it -- as two launches the validation half of X was read twice and the
         // second pass (51 us at configs[2]) ran beside the selection's kernels
-        hipStream_t main_stream = ctx->stream;
         // (round 6: the pass leaves the scores of EVERY row, not only the validation half -- N x A doubles of this call's arena: should
         // the reduction lower the largest count, the distances are taken again from them, N x count x 8 bytes instead of X once more)
         struct ScoresArg { abc_ctx* ctx; hipStream_t main; const double* X; size_t N, M, P, A, ntrain; const double* model; double* dist; double* S_all; }
-            sarg = {ctx, main_stream, io->X, N, M, P, A, (size_t)ntrain, model, dist, nullptr};
+            sarg = {ctx, ctx->stream, io->X, N, M, P, A, (size_t)ntrain, model, dist, nullptr};
         if (!(N & 1)) sarg.S_all = (double*)abc_ws_alloc(ctx, N * A * 8);
         abc_wx_scores_hook hook = {
             [](void* a, double** S, size_t* sld) -> int {
@@ -658,11 +657,13 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
                     S_half = (double*)abc_ws_alloc(c, (q->N - q->ntrain) * q->A * 8);
                     if (!S_half) { snprintf(c->err, sizeof(c->err), "generation: workspace exhausted"); return ABC_ERR_NOMEM; }
                 }
-                c->stream = q->main;
-                int rc = q->S_all ? launch_project_distance_scores(c, q->X, q->N, q->N, q->M, q->P, q->A, q->model, q->dist, q->S_all, q->N, 0, c->ev_wx_scores)
+                int rc;
+                {
+                    StreamScope on_main(c, q->main);
+                    rc = q->S_all ? launch_project_distance_scores(c, q->X, q->N, q->N, q->M, q->P, q->A, q->model, q->dist, q->S_all, q->N, 0, c->ev_wx_scores)
                                   : launch_project_distance_scores(c, q->X, q->N, q->N, q->M, q->P, q->A, q->model, q->dist, S_half, q->N - q->ntrain, q->ntrain,
                                                                    c->ev_wx_scores);
-                c->stream = wx;
+                }
                 if (rc == 0 && hipStreamWaitEvent(wx, c->ev_wx_scores, 0) != hipSuccess) rc = ABC_ERR_HIP;
                 if (rc == 0) {
                     q->dist = nullptr;          // (taken)
@@ -673,13 +674,13 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
                 return rc;
             },
             &sarg};
-        ctx->stream = ctx->wx_stream;
-        // (level 0's sweep is held back until the selection and the gather are queued: the sweep cannot start before the projection
-        // has ended anyway, and queued in front of them its three launches kept the selection from the main stream for ~65 us)
-        const int rcb = launch_wilcoxon_begin(ctx, io->X, io->Y, N, N, N, M, P, A, (size_t)ntrain, model, wx_dec, /*stop_at_max=*/1, &wx_run, &hook,
-                                              /*hold_level0=*/1);
-        ctx->stream = main_stream;
-        ABC_TRY(rcb);
+        {
+            StreamScope on_wx(ctx, ctx->wx_stream);
+            // (level 0's sweep is held back until the selection and the gather are queued: the sweep cannot start before the projection
+            // has ended anyway, and queued in front of them its three launches kept the selection from the main stream for ~65 us)
+            ABC_TRY(launch_wilcoxon_begin(ctx, io->X, io->Y, N, N, N, M, P, A, (size_t)ntrain, model, wx_dec, /*stop_at_max=*/1, &wx_run, &hook,
+                                          /*hold_level0=*/1));
+        }
         projected = sarg.dist == nullptr;
         scores_all = projected ? sarg.S_all : nullptr;
     } else if (wx_rule)
@@ -732,11 +733,8 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     ABC_TRY(launch_gather_rows(ctx, io->Y, N, N, P, io->idx, K, 0, theta, K, bins_deferred ? ctx->sel_fail_dev : nullptr, pfail_early,
                                theta_ev_bound ? ctx->ev_theta : nullptr));
     if (wx_run) {                                        // level 0 of the cascade, behind the ranking's launches in host order
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->wx_stream;
-        const int rc0 = launch_wilcoxon_level0(ctx, wx_run);
-        ctx->stream = main_stream;
-        ABC_TRY(rc0);
+        StreamScope on_wx(ctx, ctx->wx_stream);
+        ABC_TRY(launch_wilcoxon_level0(ctx, wx_run));
     }
     // Where the host looks at the cascade: HERE, in front of the weight stage (round 6; round 5's first form).  The verdict of the
     // cascade's first half -- the tests of a few responses that hold the largest count -- is there by the time the gather ends; a count
@@ -746,13 +744,13 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     if (wx_spec) {
         // the reduction itself, on its own stream, while the ranking queued above runs (the host's looks at the cascade's level
         // counts happen here, beside GPU work that does not depend on them)
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->wx_stream;
-        int changed = 2;
-        int rc = launch_wilcoxon_finish(ctx, wx_run, &changed);
-        wx_run = nullptr;
-        if (rc == ABC_OK && hipEventRecord(ctx->ev_wx_done, ctx->wx_stream) != hipSuccess) rc = ABC_ERR_HIP;
-        ctx->stream = main_stream;
+        int changed = 2, rc;
+        {
+            StreamScope on_wx(ctx, ctx->wx_stream);
+            rc = launch_wilcoxon_finish(ctx, wx_run, &changed);
+            wx_run = nullptr;
+            if (rc == ABC_OK && hipEventRecord(ctx->ev_wx_done, ctx->wx_stream) != hipSuccess) rc = ABC_ERR_HIP;
+        }
         if (rc == ABC_INTERNAL_RETRY) {          // a bin of its exact step outgrew LDS (massive ties): once more in stream order, on the sorted path
             ABC_HIP(ctx, hipStreamSynchronize(ctx->wx_stream));
             ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -766,10 +764,8 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         } else if (changed == 0) {
             // the per-response counts into the model record on the cascade's own stream: nothing this generation still queues reads
             // them (the largest count, which everything used, is the fit's); the host waits for that stream at the generation's end
-            ctx->stream = ctx->wx_stream;
-            const int rcc = launch_wilcoxon_commit(ctx, model, M, P, A, wx_dec, 0);
-            ctx->stream = main_stream;
-            ABC_TRY(rcc);
+            StreamScope on_wx(ctx, ctx->wx_stream);
+            ABC_TRY(launch_wilcoxon_commit(ctx, model, M, P, A, wx_dec, 0));
             wx_tail_pending = true;
         }
         if (changed) {                           // the largest count moved: the ranking once more, with it
@@ -829,16 +825,7 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         const double* sumsq = nullptr;       // the normalisation's sum of squares comes out of the weight stage's last kernel
         ABC_TRY(launch_weights_raw(ctx, io->priors, theta, K, P, 0, K, io->theta_prev, Kp, io->w_prev, io->dv_prev,
                                    io->w, &wprev, &sumsq));
-        // (with proposals to draw the host builds the alias table of these weights next: the normalisation kernel stores them
-        // into the pinned scratch as it writes them -- launch_resample then has nothing to copy)
-        double* mirror = nullptr;
-        const bool alias_on_device = ctx->alias_mode == ABC_ALIAS_DEVICE && K >= ABC_ALIAS_DEV_MIN_K && K <= ABC_ALIAS_DEV_MAX_K;
-        if (Nn && !alias_on_device) {          // (the device build reads the weights where they are)
-            ABC_TRY(abc_pin_reserve(ctx, abc_alias_pin_bytes(K)));
-            mirror = (double*)ctx->pin;
-        }
-        ABC_TRY(launch_normalize_l2(ctx, io->w, K, mirror, sumsq));           // AbcUtil.cpp:583
-        w_on_host = mirror != nullptr;
+        ABC_TRY(abc_normalize_for_resample(ctx, io->w, K, Nn, sumsq, &w_on_host));
     }
     // (queued BEHIND the weight stage's launches since round 5: with the ranking speculating beside the Wilcoxon cascade the host
     // arrives here late, and the side stream's four launches in front of them delayed the pair sums by their enqueue time)
@@ -846,34 +833,14 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
     // and padded factor) need the gathered rows only: with the resampling table built on the device nothing waits for the host
     // any more, so they run on the SIDE stream from here on, beside the weight stage, and are long done when the proposals need
     // them (round 2 hid them behind the host's alias build).
-    double* L_early = nullptr;
-    abc_theta_fused side_out = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    abc_side_moments side = {};
     bool moments_on_side = false, seeds_waited = false;
     // (set 0 has nothing to overlap them with: two cross-stream hand-overs for nothing, measured +35 us)
     if (moments_side_planned) {
-        if (cfg->multivariate) {
-            L_early = io->L ? io->L : (double*)abc_ws_alloc(ctx, P * P * 8);
-            if (!L_early) ABC_FAIL(ctx, ABC_ERR_NOMEM, "generation: workspace exhausted");
-        }
-        const int PPr = abc_perturb_pp(P);
-        side_out.dv = dv; side_out.L = L_early; side_out.spd = spd_dev;
-        side_out.model_hdr = simple ? nullptr : model; side_out.hdr_pin = hdr_pin; side_out.spd_pin = L_early ? spd_pin : nullptr;
-        status_early = true;
-        side_out.rows = (double*)abc_ws_alloc(ctx, K * (size_t)PPr * sizeof(double));
-        if (L_early) side_out.Lpad = (double*)abc_ws_alloc(ctx, (size_t)PPr * PPr * sizeof(double));
-        if (!side_out.rows || (L_early && !side_out.Lpad)) ABC_FAIL(ctx, ABC_ERR_NOMEM, "generation: workspace exhausted");
-        if (!theta_ev_bound) ABC_HIP(ctx, hipEventRecord(ctx->ev_theta, ctx->stream));
-        ABC_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_theta, 0));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->side;                        // the launchers below queue on the context's stream
-        double* st = nullptr;
-        int rc = launch_theta_stats(ctx, theta, K, P, &st);
-        if (rc == ABC_OK) rc = launch_post_tail(ctx, theta, K, P, st, &side_out);
-        ctx->stream = main_stream;
-        ABC_TRY(rc);
-        ABC_HIP(ctx, hipEventRecord(ctx->ev_moments, ctx->side));
-        theta_stats = st;
-        moments_on_side = true;
+        ABC_TRY(abc_moments_on_side(ctx, theta, K, P, cfg->multivariate != 0, io->L, dv, spd_dev, simple ? nullptr : model, theta_ev_bound,
+                                    "generation", &side));
+        theta_stats = side.stats;
+        moments_on_side = status_early = true;
     }
     int spd = 0;
     bool have_spd = false;
@@ -886,62 +853,22 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         if (!parent) ABC_FAIL(ctx, ABC_ERR_NOMEM, "generation: workspace exhausted");
         double* L = nullptr;
         if (cfg->multivariate) {
-            L = L_early ? L_early : (io->L ? io->L : (double*)abc_ws_alloc(ctx, P * P * 8));
+            L = side.L ? side.L : (io->L ? io->L : (double*)abc_ws_alloc(ctx, P * P * 8));
             have_spd = true;
         }
-        // The alias-table host round trip sits inside launch_resample.  What does not depend on the weights runs on the GPU
-        // meanwhile: the MVN factor (covariance + Cholesky), the row-major posterior copy and the seed stream of the
-        // perturbation.
-        abc_perturb_prep prep = {moments_on_side ? side_out.rows : nullptr, (early && io->seeds) ? 1 : 0, moments_on_side ? side_out.Lpad : nullptr};
+        // (side.out: nulls unless the moments went to the side stream)
+        abc_perturb_prep prep = {side.out.rows, (early && io->seeds) ? 1 : 0, side.out.Lpad};
         if (moments_on_side) { ABC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_moments, 0)); seeds_waited = true; }   // (recorded behind the seeds)
-        struct PrepArg {
-            abc_ctx* ctx; const abc_rng* rng; const double* theta; const double* theta_stats; size_t K, P, Nn;
-            uint64_t* seeds; abc_perturb_prep* prep; double* L; int* spd_dev; double* dv; bool moments;
-            const double* model_hdr; double* hdr_pin; int* spd_pin;
-        };
+        // (abc_prep_hook: what does not depend on the weights, beside the alias table's host round trip inside launch_resample)
         const bool hook_moments = defer_moments && !moments_on_side;
-        PrepArg pa = {ctx, rng, theta, theta_stats, K, P, Nn, io->seeds, &prep, moments_on_side ? nullptr : L, spd_dev, dv,
-                      hook_moments, nullptr, nullptr, nullptr};
+        abc_prep_arg pa = {ctx, rng, theta, theta_stats, K, P, Nn, 0, Nn, io->seeds, &prep, moments_on_side ? nullptr : L, spd_dev, dv,
+                           hook_moments, nullptr, nullptr, nullptr};
         if (hook_moments) {
             pa.model_hdr = simple ? nullptr : model; pa.hdr_pin = hdr_pin; pa.spd_pin = L ? spd_pin : nullptr;
             status_early = true;
         }
-        auto hook = [](void* a) -> int {
-            PrepArg* q = (PrepArg*)a;
-            int fused_done = 0;
-            if (q->moments) {
-                StageTimer tm(q->ctx, ST_GATHER_DV);
-                double* st = nullptr;
-                ABC_TRY(launch_theta_stats(q->ctx, q->theta, q->K, q->P, &st));
-                q->theta_stats = st;
-                // doubled variance, proposal factor and the perturbation's inputs (row-major copy, padded factor) in ONE launch
-                abc_theta_fused f = {q->dv, q->L, q->spd_dev, nullptr, nullptr, q->model_hdr, q->hdr_pin, q->spd_pin};
-                if (q->ctx->noise_mode != ABC_NOISE_REFERENCE_STREAM) {
-                    const int PP = abc_perturb_pp(q->P);
-                    f.rows = (double*)abc_ws_alloc(q->ctx, q->K * (size_t)PP * sizeof(double));
-                    if (q->L) f.Lpad = (double*)abc_ws_alloc(q->ctx, (size_t)PP * PP * sizeof(double));
-                    if (!f.rows || (q->L && !f.Lpad)) { snprintf(q->ctx->err, sizeof(q->ctx->err), "generation: workspace exhausted"); return ABC_ERR_NOMEM; }
-                }
-                ABC_TRY(launch_post_tail(q->ctx, q->theta, q->K, q->P, st, &f));
-                q->prep->rows = f.rows;
-                q->prep->Lpad = f.Lpad;
-                fused_done = 1;
-            }
-            if (q->L && !fused_done) {
-                if (q->theta_stats) {
-                    StageTimer tm(q->ctx, ST_MVN);
-                    ABC_TRY(launch_mvn_from_stats(q->ctx, q->theta_stats, q->P, q->L, q->spd_dev));
-                } else {
-                    ABC_TRY(launch_mvn_setup(q->ctx, q->theta, q->K, q->P, q->L, nullptr, q->spd_dev));
-                }
-            }
-            if (q->ctx->noise_mode == ABC_NOISE_REFERENCE_STREAM) return ABC_OK;     // nothing of the device stream is needed
-            // ... and the row-major posterior copy, the padded factor and the seeds of the proposals
-            return launch_perturb_prepare(q->ctx, q->rng, q->theta, q->K, q->P, 0, q->Nn, q->seeds, q->Nn, q->prep,
-                                          q->L ? 1 : 0, q->L ? q->L : q->dv);
-        };
         {
-            const int rc = launch_resample(ctx, rng, io->w, K, 0, Nn, parent, hook, &pa, uniform_w, raw_early, w_on_host,
+            const int rc = launch_resample(ctx, rng, io->w, K, 0, Nn, parent, abc_prep_hook, &pa, uniform_w, raw_early, w_on_host,
                                            bins_deferred ? pfail_early : nullptr, parent_early != nullptr,
                                            ctx->noise_mode == ABC_NOISE_REFERENCE_STREAM ? nullptr : &alias_deferred);
             if (rc == ABC_INTERNAL_RETRY) return repeat_with_radix();
@@ -995,19 +922,8 @@ static int generation_core(abc_ctx* ctx, const abc_generation_cfg* cfg, const ab
         // the device build of the resampling table did not verify: the draws and the proposals once more, with the table from the
         // host (the weights are final; only what depends on the table is repeated)
         if (alias_deferred && *(volatile int*)&ctx->status_pin->alias_fail && parent_used) {
-            ctx->alias_dev_fallbacks++;
-            const int mode = ctx->alias_mode;
-            ctx->alias_mode = ABC_ALIAS_HOST;
-            int rc = launch_resample(ctx, &rng_entry, io->w, K, 0, Nn, parent_used);
-            ctx->alias_mode = mode;
-            ABC_TRY(rc);
-            prep_used.seeds_done = 1;
-            // (the first pass's give-ups belong to proposals that are being replaced: counter back to the generation's snapshot)
-            if (ctx->giveups_dev)
-                ABC_HIP(ctx, hipMemcpyAsync(ctx->giveups_dev, ctx->giveups_dev + 1, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
-            ABC_TRY(launch_perturb(ctx, &rng_entry, theta, K, P, io->priors, parent_used, 0, Nn, cfg->multivariate,
-                                   cfg->multivariate ? L_used : dv, io->next, nullptr, Nn, &prep_used));
-            ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            ABC_TRY(abc_alias_repair(ctx, &rng_entry, io->w, K, 0, Nn, Nn, parent_used, theta, P, io->priors, cfg->multivariate,
+                                     cfg->multivariate ? L_used : dv, io->next, &prep_used, /*giveups_to_snapshot=*/true));
         }
     }
     if (ctx->timing && ctx->nev > 128) ABC_TRY(abc_timing_flush(ctx));

@@ -920,6 +920,102 @@ int launch_perturb(abc_ctx* ctx, const abc_rng* rng, const double* theta, size_t
     return ABC_OK;
 }
 
+// ---- the tail of a generation (abc_internal.h) -------------------------------------------------------------------------------------
+int abc_moments_on_side(abc_ctx* ctx, const double* theta, size_t K, size_t P, bool multivariate, double* L_io, double* dv,
+                        int* spd_dev, const double* model_hdr, bool theta_ev_bound, const char* who, abc_side_moments* m) {
+    m->L = m->stats = nullptr;
+    if (multivariate) {
+        m->L = L_io ? L_io : (double*)abc_ws_alloc(ctx, P * P * 8);
+        if (!m->L) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", who);
+    }
+    const int PPr = abc_perturb_pp(P);
+    // the generation's status words go straight into the pinned block from k_post_tail -- no copies behind the proposals
+    abc_status_block* pin = ctx->status_pin;
+    m->out = {dv, m->L, spd_dev, nullptr, nullptr, model_hdr, pin->model_hdr, m->L ? &pin->spd : nullptr};
+    pin->model_hdr[0] = 0.0; pin->spd = 0;
+    m->out.rows = (double*)abc_ws_alloc(ctx, K * (size_t)PPr * sizeof(double));
+    if (m->L) m->out.Lpad = (double*)abc_ws_alloc(ctx, (size_t)PPr * PPr * sizeof(double));
+    if (!m->out.rows || (m->L && !m->out.Lpad)) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", who);
+    if (!theta_ev_bound) ABC_HIP(ctx, hipEventRecord(ctx->ev_theta, ctx->stream));
+    ABC_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_theta, 0));
+    {
+        StreamScope on_side(ctx, ctx->side);
+        ABC_TRY(launch_theta_stats(ctx, theta, K, P, &m->stats));
+        ABC_TRY(launch_post_tail(ctx, theta, K, P, m->stats, &m->out));
+    }
+    ABC_HIP(ctx, hipEventRecord(ctx->ev_moments, ctx->side));
+    return ABC_OK;
+}
+
+int abc_normalize_for_resample(abc_ctx* ctx, double* w, size_t K, size_t Nn, const double* sumsq, bool* w_on_host) {
+    // (with proposals to draw the host builds the alias table of these weights next: the normalisation kernel stores them
+    // into the pinned scratch as it writes them -- launch_resample then has nothing to copy)
+    double* mirror = nullptr;
+    const bool alias_on_device = ctx->alias_mode == ABC_ALIAS_DEVICE && K >= ABC_ALIAS_DEV_MIN_K && K <= ABC_ALIAS_DEV_MAX_K;
+    if (Nn && !alias_on_device) {          // (the device build reads the weights where they are)
+        ABC_TRY(abc_pin_reserve(ctx, abc_alias_pin_bytes(K)));
+        mirror = (double*)ctx->pin;
+    }
+    ABC_TRY(launch_normalize_l2(ctx, w, K, mirror, sumsq));           // AbcUtil.cpp:583
+    *w_on_host = mirror != nullptr;
+    return ABC_OK;
+}
+
+// The alias-table host round trip sits inside launch_resample.  What does not depend on the weights runs on the GPU meanwhile: the
+// MVN factor (covariance + Cholesky), the row-major posterior copy and the seed stream of the perturbation.
+int abc_prep_hook(void* a) {
+    abc_prep_arg* q = (abc_prep_arg*)a;
+    int fused_done = 0;
+    if (q->moments) {
+        StageTimer tm(q->ctx, ST_GATHER_DV);
+        double* st = nullptr;
+        ABC_TRY(launch_theta_stats(q->ctx, q->theta, q->K, q->P, &st));
+        q->theta_stats = st;
+        // doubled variance, proposal factor and the perturbation's inputs (row-major copy, padded factor) in ONE launch
+        abc_theta_fused f = {q->dv, q->L, q->spd_dev, nullptr, nullptr, q->model_hdr, q->hdr_pin, q->spd_pin};
+        if (q->ctx->noise_mode != ABC_NOISE_REFERENCE_STREAM) {
+            const int PP = abc_perturb_pp(q->P);
+            f.rows = (double*)abc_ws_alloc(q->ctx, q->K * (size_t)PP * sizeof(double));
+            if (q->L) f.Lpad = (double*)abc_ws_alloc(q->ctx, (size_t)PP * PP * sizeof(double));
+            if (!f.rows || (q->L && !f.Lpad)) ABC_FAIL(q->ctx, ABC_ERR_NOMEM, "generation: workspace exhausted");
+        }
+        ABC_TRY(launch_post_tail(q->ctx, q->theta, q->K, q->P, st, &f));
+        q->prep->rows = f.rows;
+        q->prep->Lpad = f.Lpad;
+        fused_done = 1;
+    }
+    if (q->L && !fused_done) {
+        if (q->theta_stats) {
+            StageTimer tm(q->ctx, ST_MVN);
+            ABC_TRY(launch_mvn_from_stats(q->ctx, q->theta_stats, q->P, q->L, q->spd_dev));
+        } else {
+            ABC_TRY(launch_mvn_setup(q->ctx, q->theta, q->K, q->P, q->L, nullptr, q->spd_dev));
+        }
+    }
+    if (q->ctx->noise_mode == ABC_NOISE_REFERENCE_STREAM) return ABC_OK;     // nothing of the device stream is needed
+    // ... and the row-major posterior copy, the padded factor and the seeds of the proposals
+    return launch_perturb_prepare(q->ctx, q->rng, q->theta, q->K, q->P, q->i0, q->Nn, q->seeds, q->seed_off, q->prep,
+                                  q->L ? 1 : 0, q->L ? q->L : q->dv);
+}
+
+int abc_alias_repair(abc_ctx* ctx, const abc_rng* rng_entry, const double* w, size_t K, uint64_t i0, size_t Nn, uint64_t seed_off,
+                     uint64_t* parent, const double* theta, size_t P, const abc_prior* priors, int multivariate, const double* L_or_dv,
+                     double* next, abc_perturb_prep* prep, bool giveups_to_snapshot) {
+    ctx->alias_dev_fallbacks++;
+    const int mode = ctx->alias_mode;
+    ctx->alias_mode = ABC_ALIAS_HOST;
+    const int rc = launch_resample(ctx, rng_entry, w, K, i0, Nn, parent);
+    ctx->alias_mode = mode;
+    ABC_TRY(rc);
+    prep->seeds_done = 1;
+    // (the first pass's give-ups belong to proposals that are being replaced: counter back to the generation's snapshot)
+    if (giveups_to_snapshot && ctx->giveups_dev)
+        ABC_HIP(ctx, hipMemcpyAsync(ctx->giveups_dev, ctx->giveups_dev + 1, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+    ABC_TRY(launch_perturb(ctx, rng_entry, theta, K, P, priors, parent, i0, Nn, multivariate, L_or_dv, next, nullptr, seed_off, prep));
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ABC_OK;
+}
+
 // ---- reference-stream proposals (abc_ctx_set_noise_mode): everything the host loop needs comes down, the proposals go back up
 int launch_perturb_reference(abc_ctx* ctx, abc_rng* rng_after_draws, const double* theta, size_t K, size_t P,
                              const abc_prior* priors, const uint64_t* parent, size_t n, int multivariate, const double* L_or_dv,

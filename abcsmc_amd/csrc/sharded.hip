@@ -774,34 +774,13 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
     // As in the single-GPU driver: with proposals to draw behind a weight stage, the posterior's moments and everything that
     // follows from them (doubled variance, proposal factor, the perturbation's row-major copy and padded factor) run on the SIDE
     // stream beside the pair sums -- nothing waits for the host any more (the resampling table is built on the device).
-    double* L_early = nullptr;
-    abc_theta_fused side_out = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    abc_side_moments side = {};
     bool moments_on_side = false, status_early = false;
     if (moments_planned) {
-        if (cfg->multivariate) {
-            L_early = io->L ? io->L : (double*)abc_ws_alloc(ctx, P * P * 8);
-            if (!L_early) ABC_FAIL(ctx, ABC_ERR_NOMEM, "sharded generation: workspace exhausted");
-        }
-        const int PPr = abc_perturb_pp(P);
-        side_out.dv = dv; side_out.L = L_early; side_out.spd = spd_dev;
-        // (as the fused driver: the generation's status words go straight into the pinned block from k_post_tail -- no copies behind
-        // the proposals)
-        side_out.model_hdr = model; side_out.hdr_pin = ctx->status_pin->model_hdr; side_out.spd_pin = L_early ? &ctx->status_pin->spd : nullptr;
-        ctx->status_pin->model_hdr[0] = 0.0; ctx->status_pin->spd = 0;
-        status_early = true;
-        side_out.rows = (double*)abc_ws_alloc(ctx, K * (size_t)PPr * sizeof(double));
-        if (L_early) side_out.Lpad = (double*)abc_ws_alloc(ctx, (size_t)PPr * PPr * sizeof(double));
-        if (!side_out.rows || (L_early && !side_out.Lpad)) ABC_FAIL(ctx, ABC_ERR_NOMEM, "sharded generation: workspace exhausted");
-        if (!theta_ev_bound) ABC_HIP(ctx, hipEventRecord(ctx->ev_theta, ctx->stream));      // (the radix protocol's k_place_rows)
-        ABC_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_theta, 0));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->side;
-        int rc = launch_theta_stats(ctx, theta, K, P, &theta_stats);
-        if (rc == ABC_OK) rc = launch_post_tail(ctx, theta, K, P, theta_stats, &side_out);
-        ctx->stream = main_stream;
-        ABC_TRY(rc);
-        ABC_HIP(ctx, hipEventRecord(ctx->ev_moments, ctx->side));
-        moments_on_side = true;
+        // (theta_ev_bound is false behind the radix protocol's k_place_rows only)
+        ABC_TRY(abc_moments_on_side(ctx, theta, K, P, cfg->multivariate != 0, io->L, dv, spd_dev, model, theta_ev_bound, "sharded generation", &side));
+        theta_stats = side.stats;
+        moments_on_side = status_early = true;
     } else if (P <= 64 && K >= 2) {
         StageTimer tm(ctx, ST_GATHER_DV);
         ABC_TRY(launch_theta_stats(ctx, theta, K, P, &theta_stats));
@@ -823,15 +802,7 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
             hipLaunchKernelGGL(k_unpad_slices, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ctx->stream, w_slices, K, W, kmax, io->w);
             ABC_HIP(ctx, hipGetLastError());
         }
-        // (as in the single-GPU driver: the normalised weights go to the pinned scratch as they are written)
-        double* mirror = nullptr;
-        const bool alias_on_device = ctx->alias_mode == ABC_ALIAS_DEVICE && K >= ABC_ALIAS_DEV_MIN_K && K <= ABC_ALIAS_DEV_MAX_K;
-        if (Nn && !alias_on_device) {          // (the device build reads the weights where they are)
-            ABC_TRY(abc_pin_reserve(ctx, abc_alias_pin_bytes(K)));
-            mirror = (double*)ctx->pin;
-        }
-        ABC_TRY(launch_normalize_l2(ctx, io->w, K, mirror, sumsq));                     // AbcUtil.cpp:583
-        w_on_host = mirror != nullptr;
+        ABC_TRY(abc_normalize_for_resample(ctx, io->w, K, Nn, sumsq, &w_on_host));
     }
 
     // ---- proposals for this rank's slice of the next set --------------------------------------------------------------------
@@ -846,31 +817,16 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
         if (!parent) ABC_FAIL(ctx, ABC_ERR_NOMEM, "sharded generation: workspace exhausted");
         double* L = nullptr;
         if (cfg->multivariate) {
-            L = L_early ? L_early : (io->L ? io->L : (double*)abc_ws_alloc(ctx, P * P * 8));
+            L = side.L ? side.L : (io->L ? io->L : (double*)abc_ws_alloc(ctx, P * P * 8));
             have_spd = true;
         }
-        abc_perturb_prep prep = {moments_on_side ? side_out.rows : nullptr, io->seeds ? 1 : 0, moments_on_side ? side_out.Lpad : nullptr};
+        abc_perturb_prep prep = {side.out.rows, io->seeds ? 1 : 0, side.out.Lpad};
         if (moments_on_side) ABC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_moments, 0));
-        struct PrepArg {
-            abc_ctx* ctx; const abc_rng* rng; const double* theta; const double* theta_stats; size_t K, P, Nn;
-            uint64_t i0, seed_off; uint64_t* seeds; abc_perturb_prep* prep; double* L; int* spd_dev; const double* dv;
-        };
-        PrepArg pa = {ctx, rng, theta, theta_stats, K, P, Nn, cfg->next0, cfg->Nnext_total, io->seeds, &prep, moments_on_side ? nullptr : L, spd_dev, dv};
-        auto hook = [](void* a) -> int {          // GPU work that does not need the alias table runs while the host builds it
-            PrepArg* q = (PrepArg*)a;
-            if (q->L) {
-                if (q->theta_stats) {
-                    StageTimer tm(q->ctx, ST_MVN);
-                    ABC_TRY(launch_mvn_from_stats(q->ctx, q->theta_stats, q->P, q->L, q->spd_dev));
-                } else {
-                    ABC_TRY(launch_mvn_setup(q->ctx, q->theta, q->K, q->P, q->L, nullptr, q->spd_dev));
-                }
-            }
-            return launch_perturb_prepare(q->ctx, q->rng, q->theta, q->K, q->P, q->i0, q->Nn, q->seeds, q->seed_off, q->prep,
-                                          q->L ? 1 : 0, q->L ? q->L : q->dv);
-        };
+        // (abc_prep_hook: GPU work that does not need the alias table runs while the host builds it; no moments are deferred to it here)
+        abc_prep_arg pa = {ctx, rng, theta, theta_stats, K, P, Nn, cfg->next0, cfg->Nnext_total, io->seeds, &prep, moments_on_side ? nullptr : L,
+                           spd_dev, dv, false, nullptr, nullptr, nullptr};
         {
-            const int rc = launch_resample(ctx, rng, io->w, K, cfg->next0, Nn, parent, hook, &pa, uniform_w, raw_early, w_on_host,
+            const int rc = launch_resample(ctx, rng, io->w, K, cfg->next0, Nn, parent, abc_prep_hook, &pa, uniform_w, raw_early, w_on_host,
                                            (ds_fail_dev && !uniform_w) ? pfail_early : nullptr, false, &alias_deferred);
             if (rc == ABC_INTERNAL_RETRY) return repeat_with_radix();
             ABC_TRY(rc);
@@ -899,16 +855,9 @@ static int sharded_core(abc_ctx* ctx, const abc_sharded_cfg* cfg, const abc_gene
         // the device build of the resampling table did not verify (every rank builds the same table from the same weights, so
         // every rank lands here alike): this rank's draws and proposals once more, with the table from the host
         if (alias_deferred && *(volatile int*)&ctx->status_pin->alias_fail && parent_used) {
-            ctx->alias_dev_fallbacks++;
-            const int mode = ctx->alias_mode;
-            ctx->alias_mode = ABC_ALIAS_HOST;
-            const int rc = launch_resample(ctx, &rng_entry, io->w, K, cfg->next0, Nn, parent_used);
-            ctx->alias_mode = mode;
-            ABC_TRY(rc);
-            prep_used.seeds_done = 1;
-            ABC_TRY(launch_perturb(ctx, &rng_entry, theta, K, P, io->priors, parent_used, cfg->next0, Nn, cfg->multivariate,
-                                   cfg->multivariate ? L_used : dv, io->next, nullptr, cfg->Nnext_total, &prep_used));
-            ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            // (the give-up counter keeps the first pass's count here, unlike in the fused driver: inherited, not examined)
+            ABC_TRY(abc_alias_repair(ctx, &rng_entry, io->w, K, cfg->next0, Nn, cfg->Nnext_total, parent_used, theta, P, io->priors,
+                                     cfg->multivariate, cfg->multivariate ? L_used : dv, io->next, &prep_used, /*giveups_to_snapshot=*/false));
         }
     }
     // this rank's proposals the perturbation gave up on during THIS call (abc_generation_giveups; ADVICE round 4: the sharded driver

@@ -299,6 +299,79 @@ def test_sharded_world1_equals_fused(gpu_ctx):
     assert (r1.s1, r1.s2, r1.s3) == (r2.s1, r2.s2, r2.s3)
 
 
+def _tail_pair(gpu_ctx, ctx, N, K, Kp, Nn, multivariate, seed=5):
+    """one generation by the fused driver (gpu_ctx) and one by the sharded driver on ctx (no communicator: world 1), same inputs and seed"""
+    import torch
+    from abcsmc_amd import _lib, abcutil, device, sharded, synthetic
+    M, P, A = 32, 16, 8
+    wl = synthetic.Workload(M, P)
+    X, Y = wl.rows(0, N)
+    dev = "cuda:0"
+    args = [device.colmajor(a, dev) for a in (X, Y, wl.observed())]
+    pri = device.priors_to_device(_lib.make_priors(wl.prior_spec()), dev)
+    prev = [device.colmajor(a, dev) for a in wl.previous_set(Kp)] if Kp else []
+    g1 = device.Generation(N, M, P, K, Kp, Nn, 0.5, A, rule=_lib.RULE_MIN_PRESS, multivariate=multivariate, device=dev, ctx=gpu_ctx)
+    r1 = abcutil.rng(seed)
+    g1.run(*args, pri, r1, *prev)
+    g2 = sharded.CabiShardedGeneration(ctx, dev, N, M, P, K, Kp, Nn, 0.5, A, rule=_lib.RULE_MIN_PRESS, multivariate=multivariate)
+    r2 = abcutil.rng(seed)
+    g2.run(*args, pri, r2, *prev)
+    torch.cuda.synchronize()
+    return g1, r1, g2, r2
+
+
+def _assert_same_generation(g1, r1, g2, r2, Nn, with_L):
+    import torch
+    for name in ("idx", "w", "dv", "theta") + (("L",) if with_L else ()):
+        assert torch.equal(getattr(g1, name), getattr(g2, name)), name
+    for name in ("parent", "seeds"):
+        assert torch.equal(getattr(g1, name)[:Nn], getattr(g2, name)[:Nn]), name
+    assert torch.equal(g1.next[:, :Nn], g2.next[:, :Nn])
+    assert (r1.s1, r1.s2, r1.s3) == (r2.s1, r2.s2, r2.s3) and g2.ncomp == g1.ncomp.value
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Kp,Nn,multivariate", [(500, 5000, True), (500, 5000, False), (0, 5000, True), (0, 5000, False), (500, 0, True)],
+                         ids=["weighted-mvn", "weighted-independent", "first-set-mvn", "first-set-independent", "no-proposals"])
+def test_sharded_world1_tail_equals_fused(gpu_ctx, Kp, Nn, multivariate):
+    """the part of a generation behind the gathered rows is one piece of code under both drivers (moments on the side stream,
+    normalisation, launch_resample's preparation hook, proposals): every output, the rng state and the component count of the
+    sharded driver at world 1 equal the fused driver's bit for bit -- weighted sets (moments on the side stream), first sets (uniform
+    weights: the hook computes the factor), independent noise (no factor anywhere), and a set without proposals, where the sharded
+    driver alone computes the factor the caller gave room for (the fused driver leaves L untouched then: that factor is compared with
+    the one of a fused generation WITH proposals over the same rows, to the bound the factor has against the oracle elsewhere)"""
+    import numpy as np
+    from abcsmc_amd import _lib, device
+    N, K = 6000, 700
+    ctx = _lib.Context(0)
+    g1, r1, g2, r2 = _tail_pair(gpu_ctx, ctx, N, K, Kp, Nn, multivariate)
+    _assert_same_generation(g1, r1, g2, r2, Nn, with_L=multivariate and Nn > 0)
+    if multivariate and not Nn:
+        g3 = _tail_pair(gpu_ctx, ctx, N, K, Kp, 5000, True)[0]
+        assert np.allclose(np.tril(device.to_numpy(g2.L)), np.tril(device.to_numpy(g3.L)), rtol=1e-7, atol=1e-12)
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_sharded_world1_repeats_its_proposals_when_the_device_alias_build_fails(gpu_ctx, monkeypatch):
+    """the repair behind a device alias build that did not verify is shared by the two drivers: under ABC_ALIAS_FORCE_FAIL the
+    sharded driver at world 1 counts one fallback per build and leaves the outputs of the fused driver under the same switch, bit
+    for bit (the smallest K the device build takes; give-up counts are not compared: only the fused driver puts the counter back
+    to its snapshot before it repeats the proposals)"""
+    from abcsmc_amd import _lib
+    monkeypatch.setenv("ABC_ALIAS_FORCE_FAIL", "1")
+    ctx = _lib.Context(0)
+    gpu_ctx.alias_stats(reset=True)
+    g1, r1, g2, r2 = _tail_pair(gpu_ctx, ctx, 220000, 22000, 500, 30000, True)
+    builds, fallbacks = ctx.alias_stats()
+    builds1, fallbacks1 = gpu_ctx.alias_stats(reset=True)
+    monkeypatch.delenv("ABC_ALIAS_FORCE_FAIL")
+    assert builds >= 1 and fallbacks == builds
+    assert builds1 >= 1 and fallbacks1 == builds1
+    _assert_same_generation(g1, r1, g2, r2, 30000, with_L=True)
+    ctx.close()
+
+
 @pytest.mark.gpu
 def test_a_raising_collective_callback_fails_the_generation():
     """abc_comm_init_callbacks with Python collectives: an exception inside one (transport timeout, shape error) must not be
