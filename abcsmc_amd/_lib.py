@@ -90,6 +90,25 @@ class Density(C.Structure):
                 ("grid", C.c_void_p), ("bw_out", C.c_void_p), ("mode", C.c_void_p), ("mode_dens", C.c_void_p)]
 
 
+class Joint(C.Structure):
+    """abc_joint: G, cut, bw_scale, bw (optional input), pairs (optional, HOST int32 npairs x 2) and npairs, then the optional
+    outputs mean / cov / corr / dens / grid / bw_out / mode / mode_dens (memory as the entry point's other arrays)"""
+    _fields_ = [("G", C.c_size_t), ("cut", C.c_double), ("bw_scale", C.c_double), ("bw", C.c_void_p), ("pairs", C.c_void_p),
+                ("npairs", C.c_size_t), ("mean", C.c_void_p), ("cov", C.c_void_p), ("corr", C.c_void_p), ("dens", C.c_void_p),
+                ("grid", C.c_void_p), ("bw_out", C.c_void_p), ("mode", C.c_void_p), ("mode_dens", C.c_void_p)]
+
+
+def _joint_pairs(pairs, P):
+    """The pair list of an abc_joint as C-contiguous int32 (npairs, 2) host arrays: (all, given).  given is what the descriptor
+    points at: the caller's rows (i, j), or None when pairs is None; all is then every i < j in the library's default order
+    (0, 1), (0, 2), ..., and given otherwise."""
+    import numpy as np
+    if pairs is None:
+        return np.array([(i, j) for i in range(P) for j in range(i + 1, P)], dtype=np.int32).reshape(-1, 2), None
+    given = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    return given, given
+
+
 ALL_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 BROADCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -154,6 +173,12 @@ SIGNATURES = {
                                                       _vp, _vp, _vp, _vp]),
     "abc_weighted_density_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_weighted_density": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "abc_rank_targets_joint_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _i, _vp,
+                                        _vp, _vp, _vp]),
+    "abc_particle_ranking_pls_targets_joint": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _i, _vp,
+                                                    _vp, _vp, _vp, _vp]),
+    "abc_weighted_joint_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    "abc_weighted_joint": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "abc_particle_ranking_simple": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_calculate_doubled_variance": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "abc_weight_predictive_prior_uniform": (_i, [_vp, _sz, _vp]),

@@ -259,6 +259,82 @@ def weighted_density(values, weights=None, G=512, cut=3.0, bw=None, bw_scale=1.0
     return o
 
 
+def _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens):
+    """Host arrays for the joint outputs of prod(lead) targets with P parameters and the abc_joint pointing at them"""
+    G = int(G)
+    b = None
+    if bw is not None:
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(bw, dtype=np.float64), lead + (P,)))
+    pr, given = _lib._joint_pairs(pairs, P)
+    n = pr.shape[0]
+    e = lambda *shape: np.empty(lead + shape)
+    o = dict(mean=e(P), cov=e(P, P), corr=e(P, P), dens=e(n, G, G) if dens else None, grid=e(P, 2), bw=e(P), mode=e(n, 2),
+             mode_dens=e(n), pairs=pr)
+    d = _lib.Joint(G, float(cut), float(bw_scale), _p(b), _p(given), n if given is not None else 0, _p(o["mean"]), _p(o["cov"]),
+                   _p(o["corr"]), _p(o["dens"]), _p(o["grid"]), _p(o["bw"]), _p(o["mode"]), _p(o["mode_dens"]))
+    return d, o, (b, given)
+
+
+def particle_ranking_PLS_targets_joint(X_orig, Y_orig, targets, training_fraction, K, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None,
+                                       method="rejection", kernel="epanechnikov", exclude=None, max_comp=0, rule=_lib.RULE_DEFAULT,
+                                       dens=True, ctx=None):
+    """particle_ranking_PLS_targets followed by the joint posterior of every target, what a pairs plot draws
+    (abc_particle_ranking_pls_targets_joint; the definition is in the header): the weighted means, the covariance matrix
+    (numpy.cov with aweights) and the Pearson correlations of the P parameters, and for every pair of parameters in pairs (rows
+    (i, j), i != j; None: all i < j) the product-Gaussian kernel density (as MASS::kde2d, with the marginal densities' bandwidths) on a
+    G x G grid and its mode.  method, kernel, bw, cut and bw_scale as particle_ranking_PLS_targets_density.  dens holds
+    B * npairs * G * G doubles (3.9 GB for 1000 targets, 120 pairs, G = 64): choose pairs, G or dens=False accordingly.  Returns
+    dict(mean (B, P), cov (B, P, P), corr (B, P, P), dens (B, npairs, G, G) (None with dens=False; [g, g']: g along parameter i),
+    x (B, P, G): every parameter's grid points, grid (B, P, 2), bw (B, P), mode (B, npairs, 2), mode_dens (B, npairs), pairs
+    (npairs, 2), idx (B, K), dist (B, K), ncomp)."""
+    ctx = _ctx(ctx)
+    method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
+    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
+    d, o, _keep = _joint_arg(G, cut, bw_scale, bw, pairs, (B,), P, dens)
+    idx = np.empty((B, K), dtype=np.uint64)
+    dist = np.empty((B, K))
+    ncomp = C.c_int32(0)
+    ctx.check(lib().abc_particle_ranking_pls_targets_joint(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
+                                                           int(max_comp), int(rule), _p(ex), K, method, kernel, _p(idx), _p(dist),
+                                                           None, C.byref(d), C.addressof(ncomp)))
+    o.update(x=_grid_points(o["grid"], int(G)), idx=idx, dist=dist, ncomp=ncomp.value)
+    return o
+
+
+def weighted_joint(values, weights=None, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None, dens=True, ctx=None):
+    """The joint posterior of the columns of values (K, P) on the device (abc_weighted_joint; the definition is in the header);
+    equal weights when weights is None.  Returns dict(mean (P,), cov (P, P), corr (P, P), dens (npairs, G, G) or None, x (P, G),
+    grid (P, 2), bw (P,), mode (npairs, 2), mode_dens (npairs,), pairs (npairs, 2))."""
+    ctx = _ctx(ctx)
+    V = _f(values)
+    if V.ndim == 1:
+        V = _f(V.reshape(-1, 1))
+    K, P = V.shape
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    if w is not None and w.size != K:
+        raise ValueError("weights needs one entry per row")
+    d, o, _keep = _joint_arg(G, cut, bw_scale, bw, pairs, (), P, dens)
+    ctx.check(lib().abc_weighted_joint(ctx.handle, _p(V), K, P, _p(w), C.byref(d)))
+    o["x"] = _grid_points(o["grid"], int(G))
+    return o
+
+
+def hpd_levels(dens, step_x, step_y, probs=(0.5, 0.9, 0.95)):
+    """Contour heights of highest-density regions of one gridded pair density (host only, pure NumPy).  dens: (G, G') values of f on
+    a grid with cell area step_x * step_y.  The cells are sorted by descending f and their masses f * step_x * step_y accumulated;
+    the level for probability alpha is the f of the first cell at which the cumulative mass reaches alpha times the grid's total
+    mass.  Drawing the contour f = level encloses about alpha of the mass.  Returns an array shaped as probs."""
+    f = np.sort(np.asarray(dens, dtype=np.float64).reshape(-1))[::-1]
+    if f.size == 0 or not np.all(np.isfinite(f)):
+        raise ValueError("dens must be a non-empty array of finite values")
+    pr = np.asarray(probs, dtype=np.float64)
+    if np.any(~(pr >= 0)) or np.any(pr > 1):
+        raise ValueError("probs must lie in [0, 1]")
+    mass = np.cumsum(f * (float(step_x) * float(step_y)))
+    at = np.minimum(np.searchsorted(mass, pr.reshape(-1) * mass[-1], side="left"), f.size - 1)
+    return f[at].reshape(pr.shape)
+
+
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
                        ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn

@@ -306,6 +306,18 @@ int abc_summary_check_weights(abc_ctx*, const double* w, size_t K, const char* f
 // bandwidth that is not finite and positive is ABC_ERR_INVALID (checked on the device: synchronises)
 size_t abc_density_need(size_t B, size_t K, size_t P, size_t G);
 int launch_density(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_density* dn, const char* fn);
+// the first half of launch_density, shared with the pair densities: the bandwidth check, the quantiles and k_dn_moments.  *segs:
+// B x P records (density_dev.h) in the workspace; grid and bw_out of dn are written when given, its other outputs are not touched.
+struct DnSeg;
+size_t abc_density_segs_need(size_t B, size_t K, size_t P);
+int launch_density_segs(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_density* dn, const DnSeg** segs,
+                        const char* fn);
+// joint posterior of the same segments (joint.hip): means, covariances, correlations, pair densities and joint modes.  npairs: the
+// pairs of the request (jt->npairs, or P (P - 1) / 2 when jt->pairs is NULL); jt: pairs in host memory, every other array in device
+// memory; a given bandwidth is checked as launch_density's
+size_t abc_joint_pairs(const abc_joint* jt, size_t P);
+size_t abc_joint_need(size_t B, size_t K, size_t P, size_t G, size_t npairs);
+int launch_joint(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_joint* jt, const char* fn);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

@@ -1189,10 +1189,11 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
 }
 
 // ---- batched ranking of many observed targets against one fitted set (targets.hip), optionally followed by the local-linear
-// adjustment (adjust.hip) and the weighted posterior quantiles and CDF (summary.hip) or densities and modes (density.hip): one
-// pipeline behind eight entry points ----
+// adjustment (adjust.hip) and the weighted posterior quantiles and CDF (summary.hip), densities and modes (density.hip) or joint
+// moments and pair densities (joint.hip): one pipeline behind ten entry points ----
 namespace {
-enum { TG_PLAIN, TG_ADJUST, TG_SUMMARY, TG_DENSITY };      // what follows the ranking: nothing, the adjustment, the summaries, the densities
+// what follows the ranking: nothing, the adjustment, the summaries, the densities, the joint moments and pair densities
+enum { TG_PLAIN, TG_ADJUST, TG_SUMMARY, TG_DENSITY, TG_JOINT };
 struct TgRequest {                             // (members in the order of the entries' arguments)
     int kind;
     const double* X;  size_t ldx;
@@ -1202,15 +1203,16 @@ struct TgRequest {                             // (members in the order of the e
     const double* targets;  size_t ldt, B;
     const uint64_t* exclude;
     size_t K;
-    uint64_t* idx;                             // optional for TG_SUMMARY and TG_DENSITY
+    uint64_t* idx;                             // optional for TG_SUMMARY, TG_DENSITY and TG_JOINT
     double* dist;                              // optional
     double* post_mean = nullptr;               // TG_PLAIN only, optional
-    int method = 0, kernel = 0;                // method: TG_SUMMARY and TG_DENSITY only (of which values the summaries are)
-    const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; TG_SUMMARY / TG_DENSITY: optional, method 1 only
+    int method = 0, kernel = 0;                // method: the segment kinds only (of which values the summaries are)
+    const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; the segment kinds: optional, method 1 only
     const abc_summary* sum = nullptr;          // TG_SUMMARY only
     const abc_density* den = nullptr;          // TG_DENSITY only
+    const abc_joint* jnt = nullptr;            // TG_JOINT only
     bool any_excl = false;                     // exclude names a row for some target: set by tg_check
-    bool segments() const { return kind == TG_SUMMARY || kind == TG_DENSITY; }      // the rows' values are read after the ranking
+    bool segments() const { return kind == TG_SUMMARY || kind == TG_DENSITY || kind == TG_JOINT; }      // the rows' values are read after the ranking
     bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
 };
 }  // namespace
@@ -1234,6 +1236,27 @@ static int density_check(abc_ctx* ctx, const char* fn, const abc_density* den) {
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: bw_scale = %g (finite, > 0)", fn, den->bw_scale);
     if (!den->dens && !den->grid && !den->bw_out && !den->mode && !den->mode_dens)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of den is NULL", fn);
+    return ABC_OK;
+}
+
+static int joint_check(abc_ctx* ctx, const char* fn, const abc_joint* jt, size_t P) {
+    if (!jt) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (jt is required)", fn);
+    if (jt->G < 2 || jt->G > 256) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: G = %zu grid points per axis (2 to 256)", fn, jt->G);
+    if (!(jt->cut >= 0.0) || !std::isfinite(jt->cut)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: cut = %g (finite, >= 0)", fn, jt->cut);
+    if (!(jt->bw_scale > 0.0) || !std::isfinite(jt->bw_scale))
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: bw_scale = %g (finite, > 0)", fn, jt->bw_scale);
+    if (jt->pairs) {
+        if (jt->npairs == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: pairs given with npairs == 0", fn);
+        if (jt->npairs > ((size_t)1 << 22)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: npairs = %zu (at most 2^22)", fn, jt->npairs);
+        for (size_t p = 0; p < jt->npairs; p++) {
+            const int32_t i = jt->pairs[2 * p], j = jt->pairs[2 * p + 1];
+            if (i < 0 || j < 0 || (size_t)i >= P || (size_t)j >= P || i == j)
+                ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: pairs[%zu] = (%d, %d) is not a pair of two of the %zu parameters", fn, p, (int)i,
+                         (int)j, P);
+        }
+    }
+    if (!jt->mean && !jt->cov && !jt->corr && !jt->dens && !jt->grid && !jt->bw_out && !jt->mode && !jt->mode_dens)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of jt is NULL", fn);
     return ABC_OK;
 }
 
@@ -1265,6 +1288,7 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
     }
     if (r.kind == TG_SUMMARY) ABC_TRY(summary_check(ctx, fn, r.sum));
     if (r.kind == TG_DENSITY) ABC_TRY(density_check(ctx, fn, r.den));
+    if (r.kind == TG_JOINT) ABC_TRY(joint_check(ctx, fn, r.jnt, r.P));
     if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
     if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
     if (r.M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no metrics (M == 0)", fn);
@@ -1292,6 +1316,7 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
 
 // Arena bytes of a checked request: what tg_run takes and, for the host entries (host: the fit under `rule`, every array staged),
 // what tg_host takes around it.  The device entries get the model from the caller, so their ranking needs no fit workspace.
+static size_t joint_stage_bytes(const abc_joint* h, size_t B, size_t P);
 static size_t tg_need(const TgRequest& r, bool host, int rule) {
     const size_t N = r.N, M = r.M, P = r.P, A = r.A, B = r.B, K = r.K;
     size_t b = abc_targets_need(N, A, B, K, r.any_excl);
@@ -1299,6 +1324,7 @@ static size_t tg_need(const TgRequest& r, bool host, int rule) {
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
     if (r.kind == TG_SUMMARY) b += abc_summary_need(B, K, P);
     if (r.kind == TG_DENSITY) b += abc_density_need(B, K, P, r.den->G);
+    if (r.kind == TG_JOINT) b += abc_joint_need(B, K, P, r.jnt->G, abc_joint_pairs(r.jnt, P));
     if (!host) return b + abc_ws_need(N, 1, 1, 1, K + 1, 0, 0);
     b += abc_ws_need(N, M, P, A, K + 1, 0, 0) + (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0);
     b += (N * (M + P) + M + 4) * 8;                                               // X, Y, the zero observation and its one idx, dist
@@ -1307,6 +1333,7 @@ static size_t tg_need(const TgRequest& r, bool host, int rule) {
     else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
     if (r.kind == TG_SUMMARY) b += B * P * (r.sum->nq + 2) * 8 + 16 * 256;        // truth, quant, cdf
     if (r.kind == TG_DENSITY) b += B * P * (r.den->G + 6) * 8 + 32 * 256;         // bw, dens, grid, bw_out, mode, mode_dens
+    if (r.kind == TG_JOINT) b += joint_stage_bytes(r.jnt, B, P);
     return b;
 }
 
@@ -1341,6 +1368,7 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
     sv.A = (int)r.A;
     sv.kernel = r.kernel;
     if (r.kind == TG_DENSITY) return launch_density(ctx, sv, B, K, r.P, r.den, fn);
+    if (r.kind == TG_JOINT) return launch_joint(ctx, sv, B, K, r.P, r.jnt, fn);
     return launch_summary(ctx, sv, B, K, r.P, r.sum);
 }
 
@@ -1380,6 +1408,37 @@ static void density_down(Stage& s, const abc_density* h, const abc_density& d, s
     s.down(h->bw_out, d.bw_out, ns);
     s.down(h->mode, d.mode, ns);
     s.down(h->mode_dens, d.mode_dens, ns);
+}
+
+// an abc_joint's arrays for B targets of P parameters, host (h) <-> arena: pairs stay where they are, NULL members stay NULL
+static size_t joint_stage_bytes(const abc_joint* h, size_t B, size_t P) {
+    const size_t np = abc_joint_pairs(h, P);
+    return B * (P * (2 * P + 5) + np * ((h->dens ? h->G * h->G : 0) + 3)) * 8 + 40 * 256;
+}
+static abc_joint joint_stage(Stage& s, const abc_joint* h, size_t B, size_t P) {
+    const size_t np = abc_joint_pairs(h, P);
+    abc_joint d = *h;
+    d.bw = h->bw ? s.up(h->bw, B * P) : nullptr;
+    d.mean = h->mean ? s.dev<double>(B * P) : nullptr;
+    d.cov = h->cov ? s.dev<double>(B * P * P) : nullptr;
+    d.corr = h->corr ? s.dev<double>(B * P * P) : nullptr;
+    d.dens = (h->dens && np) ? s.dev<double>(B * np * h->G * h->G) : nullptr;
+    d.grid = h->grid ? s.dev<double>(B * P * 2) : nullptr;
+    d.bw_out = h->bw_out ? s.dev<double>(B * P) : nullptr;
+    d.mode = (h->mode && np) ? s.dev<double>(B * np * 2) : nullptr;
+    d.mode_dens = (h->mode_dens && np) ? s.dev<double>(B * np) : nullptr;
+    return d;
+}
+static void joint_down(Stage& s, const abc_joint* h, const abc_joint& d, size_t B, size_t P) {
+    const size_t np = abc_joint_pairs(h, P);
+    s.down(h->mean, d.mean, B * P);
+    s.down(h->cov, d.cov, B * P * P);
+    s.down(h->corr, d.corr, B * P * P);
+    s.down(h->dens, d.dens, B * np * h->G * h->G);
+    s.down(h->grid, d.grid, B * P * 2);
+    s.down(h->bw_out, d.bw_out, B * P);
+    s.down(h->mode, d.mode, B * np * 2);
+    s.down(h->mode_dens, d.mode_dens, B * np);
 }
 
 // The host entries: h holds host pointers.  Upload, one fit, the request on the arena's copies, downloads, synchronise.
@@ -1433,6 +1492,11 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         dd = density_stage(s, h.den, B * P);
         r.den = &dd;
     }
+    abc_joint jd;
+    if (h.jnt) {
+        jd = joint_stage(s, h.jnt, B, P);
+        r.jnt = &jd;
+    }
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_TRY(tg_run(ctx, fn, r));
     s.down(h.idx, r.idx, B * K);
@@ -1447,6 +1511,7 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
     }
     if (h.sum) summary_down(s, h.sum, sd, B, P);
     if (h.den) density_down(s, h.den, dd, B * P);
+    if (h.jnt) joint_down(s, h.jnt, jd, B, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
@@ -1623,6 +1688,69 @@ extern "C" int abc_weighted_density(abc_ctx* ctx, const double* V, size_t K, siz
     sv.w = w_d;
     ABC_TRY(launch_density(ctx, sv, 1, K, P, &dd, fn));
     density_down(s, den, dd, P);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+extern "C" int abc_rank_targets_joint_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                          size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                          const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                          const abc_adjust_out* adj, const abc_joint* jt) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_JOINT, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, nullptr, nullptr, jt};
+    return tg_dev(ctx, "abc_rank_targets_joint_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_joint(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                      const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                      const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                                      double* dist, const abc_adjust_out* adj, const abc_joint* jt, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_JOINT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, nullptr, nullptr, jt};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_joint", h, train_frac, max_comp, rule, ncomp);
+}
+
+extern "C" int abc_weighted_joint_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
+                                      const abc_joint* jt) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_weighted_joint_dev";
+    ABC_TRY(weighted_values_check(ctx, fn, V, ldv, K, P));
+    ABC_TRY(joint_check(ctx, fn, jt, P));
+    ABC_TRY(abc_ws_reserve(ctx, abc_joint_need(1, K, P, jt->G, abc_joint_pairs(jt, P)) + 16 * 256));
+    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
+    SmValues sv;
+    memset(&sv, 0, sizeof(sv));
+    sv.method = 2;
+    sv.V = V;
+    sv.ldv = ldv;
+    sv.w = w;
+    return launch_joint(ctx, sv, 1, K, P, jt, fn);
+}
+
+extern "C" int abc_weighted_joint(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_joint* jt) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_weighted_joint";
+    ABC_TRY(weighted_values_check(ctx, fn, V, K, K, P));
+    ABC_TRY(joint_check(ctx, fn, jt, P));
+    ABC_TRY(abc_ws_reserve(ctx, abc_joint_need(1, K, P, jt->G, abc_joint_pairs(jt, P)) + (K * P + K) * 8 + joint_stage_bytes(jt, 1, P) +
+                                    16 * 256));
+    Stage s{ctx};
+    const double* V_d = s.up(V, K * P);
+    const double* w_d = w ? s.up(w, K) : nullptr;
+    const abc_joint jd = joint_stage(s, jt, 1, P);
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
+    SmValues sv;
+    memset(&sv, 0, sizeof(sv));
+    sv.method = 2;
+    sv.V = V_d;
+    sv.ldv = K;
+    sv.w = w_d;
+    ABC_TRY(launch_joint(ctx, sv, 1, K, P, &jd, fn));
+    joint_down(s, jt, jd, 1, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;

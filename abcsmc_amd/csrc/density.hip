@@ -13,7 +13,9 @@
 //               The work-group's largest f (smallest g on ties) is found by a fixed tree; with one chunk it is the mode, otherwise
 //               k_dn_mode takes the chunks' candidates in chunk order.  dens is written only when asked for, and the mode never
 //               reads it back.
-// Kernel evaluation (dn_kern): the argument t = -((x - v) c)^2, c = sqrt(log2(e) / 2) / h, is formed in fp64; 2^t is split as
+// launch_density_segs is the first half (the bandwidth check, the quantiles, k_dn_moments) on its own: the pair densities of
+// joint.hip start from the same records, and density_dev.h holds what the two files share on the device (DnSeg, dn_kern).
+// Kernel evaluation (dn_kern, density_dev.h): the argument t = -((x - v) c)^2, c = sqrt(log2(e) / 2) / h, is formed in fp64; 2^t is split as
 // 2^n 2^(t - n) with n = rint(t), and only the factor 2^(t - n), |t - n| <= 1/2, is taken in f32 (v_exp_f32), then scaled by
 // v_ldexp_f64.  Relative error of a term about 1e-7 (the f32 exponential's rounding), inside the header's 1e-6 contract;
 // -DDN_EXP_FP64 builds the plain fp64 exp2 instead (DESIGN.md has both timings).
@@ -21,6 +23,7 @@
 #include <math.h>
 
 #include "abc_internal.h"
+#include "density_dev.h"
 #include "segment_dev.h"
 
 namespace {
@@ -31,30 +34,12 @@ constexpr int DN_GC = DN_BS * DN_R;                         // grid points per w
 constexpr int DN_TILE = 1024;                               // entries staged in LDS at a time
 constexpr unsigned DN_MAX_GRID_Y = 65535;
 
-struct DnSeg {                                              // per segment, made by k_dn_moments (all NaN: a bad segment)
-    double h, lo_x, step, den, c;
-};
-
 struct DnArgs {
     int G;
     double cut, bw_scale;
     const double* bw;
     double *dens, *grid, *bw_out, *mode, *mode_dens;
 };
-
-__device__ __forceinline__ double dn_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// 2^-(z^2); below 2^-2000 it is 0 either way
-__device__ __forceinline__ double dn_kern(double z) {
-    const double t = fmax(-(z * z), -2000.0);
-#ifdef DN_EXP_FP64
-    return exp2(t);
-#else
-    const double n = rint(t);
-    const float p = __builtin_amdgcn_exp2f((float)(t - n));
-    return ldexp((double)p, (int)n);
-#endif
-}
 
 // grid (P, targets b0 + blockIdx.y); q4: B x 4 x P quantiles at 0, 0.25, 0.75, 1
 __global__ __launch_bounds__(DN_BS) void k_dn_moments(SmArgs a, DnArgs d, size_t b0, const double* __restrict__ q4,
@@ -238,17 +223,35 @@ __global__ __launch_bounds__(256) void k_dn_bwcheck(const double* __restrict__ b
 
 const double DN_PROBS[4] = {0.0, 0.25, 0.75, 1.0};
 
+DnArgs dn_args(const abc_density* dn) {
+    DnArgs d;
+    d.G = (int)dn->G;
+    d.cut = dn->cut;
+    d.bw_scale = dn->bw_scale;
+    d.bw = dn->bw;
+    d.dens = dn->dens;
+    d.grid = dn->grid;
+    d.bw_out = dn->bw_out;
+    d.mode = dn->mode;
+    d.mode_dens = dn->mode_dens;
+    return d;
+}
+
 }  // namespace
+
+size_t abc_density_segs_need(size_t B, size_t K, size_t P) {
+    const size_t ns = B * P;
+    return abc_summary_need(B, K, P) + ns * 4 * 8 + ns * sizeof(DnSeg) + 8 * 256;
+}
 
 size_t abc_density_need(size_t B, size_t K, size_t P, size_t G) {
     const size_t ns = B * P, nchunk = (G + DN_GC - 1) / DN_GC;
-    return abc_summary_need(B, K, P) + ns * 4 * 8 + ns * sizeof(DnSeg) + ns * nchunk * 12 + 16 * 256;
+    return abc_density_segs_need(B, K, P) + ns * nchunk * 12 + 8 * 256;
 }
 
-int launch_density(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const abc_density* dn, const char* fn) {
-    if (B == 0 || K == 0 || P == 0) return ABC_OK;
+int launch_density_segs(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const abc_density* dn, const DnSeg** segs,
+                        const char* fn) {
     const size_t ns = B * P;
-    const int G = (int)dn->G, nchunk = (G + DN_GC - 1) / DN_GC;
     if (dn->bw) {     // (synchronises, as the generic weights' check)
         int* flag = (int*)abc_ws_alloc(ctx, sizeof(int));
         if (!flag) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
@@ -264,43 +267,49 @@ int launch_density(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t 
     }
     double* q4 = (double*)abc_ws_alloc(ctx, ns * 4 * 8);
     DnSeg* sp = (DnSeg*)abc_ws_alloc(ctx, ns * sizeof(DnSeg));
-    double* pf = nullptr;
-    int* pg = nullptr;
-    if (nchunk > 1) {
-        pf = (double*)abc_ws_alloc(ctx, ns * nchunk * 8);
-        pg = (int*)abc_ws_alloc(ctx, ns * nchunk * 4);
-    }
-    if (!q4 || !sp || (nchunk > 1 && (!pf || !pg))) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    if (!q4 || !sp) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     abc_summary s4;
     memset(&s4, 0, sizeof(s4));
     s4.probs = DN_PROBS;
     s4.nq = 4;
     s4.quant = q4;
     ABC_TRY(launch_summary(ctx, sv, B, K, P, &s4));
-
     const SmArgs a = sm_args(sv, K, P);
-    DnArgs d;
-    d.G = G;
-    d.cut = dn->cut;
-    d.bw_scale = dn->bw_scale;
-    d.bw = dn->bw;
-    d.dens = dn->dens;
-    d.grid = dn->grid;
-    d.bw_out = dn->bw_out;
-    d.mode = dn->mode;
-    d.mode_dens = dn->mode_dens;
-    const bool mode = d.mode || d.mode_dens;
+    const DnArgs d = dn_args(dn);
     for (size_t b0 = 0; b0 < B; b0 += DN_MAX_GRID_Y) {
         const size_t nb = (B - b0 < DN_MAX_GRID_Y) ? B - b0 : DN_MAX_GRID_Y;
         hipLaunchKernelGGL(k_dn_moments, dim3((unsigned)P, (unsigned)nb), dim3(DN_BS), 0, ctx->stream, a, d, b0, (const double*)q4, sp);
         ABC_HIP(ctx, hipGetLastError());
-        if (!d.dens && !mode) continue;
-        hipLaunchKernelGGL(k_dn_dens, dim3((unsigned)(P * nchunk), (unsigned)nb), dim3(DN_BS), 0, ctx->stream, a, d, b0,
-                           (const DnSeg*)sp, nchunk, pf, pg);
+    }
+    *segs = sp;
+    return ABC_OK;
+}
+
+int launch_density(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const abc_density* dn, const char* fn) {
+    if (B == 0 || K == 0 || P == 0) return ABC_OK;
+    const size_t ns = B * P;
+    const int G = (int)dn->G, nchunk = (G + DN_GC - 1) / DN_GC;
+    const DnSeg* sp = nullptr;
+    ABC_TRY(launch_density_segs(ctx, sv, B, K, P, dn, &sp, fn));
+    const SmArgs a = sm_args(sv, K, P);
+    const DnArgs d = dn_args(dn);
+    const bool mode = d.mode || d.mode_dens;
+    if (!d.dens && !mode) return ABC_OK;
+    double* pf = nullptr;
+    int* pg = nullptr;
+    if (nchunk > 1) {
+        pf = (double*)abc_ws_alloc(ctx, ns * nchunk * 8);
+        pg = (int*)abc_ws_alloc(ctx, ns * nchunk * 4);
+        if (!pf || !pg) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    }
+    for (size_t b0 = 0; b0 < B; b0 += DN_MAX_GRID_Y) {
+        const size_t nb = (B - b0 < DN_MAX_GRID_Y) ? B - b0 : DN_MAX_GRID_Y;
+        hipLaunchKernelGGL(k_dn_dens, dim3((unsigned)(P * nchunk), (unsigned)nb), dim3(DN_BS), 0, ctx->stream, a, d, b0, sp, nchunk,
+                           pf, pg);
         ABC_HIP(ctx, hipGetLastError());
     }
     if (mode && nchunk > 1) {
-        hipLaunchKernelGGL(k_dn_mode, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, d, ns, (const DnSeg*)sp, nchunk,
+        hipLaunchKernelGGL(k_dn_mode, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, d, ns, sp, nchunk,
                            (const double*)pf, (const int*)pg);
         ABC_HIP(ctx, hipGetLastError());
     }

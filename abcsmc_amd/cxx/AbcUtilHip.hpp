@@ -483,6 +483,105 @@ inline TargetDensity weighted_density(const Mat2D& values, const std::vector<dou
     check(abc_weighted_density(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &den));
     return detail::target_density(dens.data(), grid.data(), bw.data(), mode.data(), md.data(), P, G);
 }
+// The same ranking followed by the joint posterior of every target (abc_particle_ranking_pls_targets_joint): weighted means,
+// covariance and correlation matrices of the P parameters, and for every pair of parameters (pairs: (i, j) with i != j; empty: all
+// i < j) the product-Gaussian kernel density on a G x G grid, dens[p](g, g') with g along parameter i, and its mode.  Per
+// target: mean / lo_x / step / bw (P each), cov and corr (P x P), dens (one G x G matrix per pair), mode_x / mode_y / mode_dens
+// (one per pair).  The densities take B * npairs * G * G doubles on the host and in the context's workspace; with dens = false
+// they are neither computed into memory nor returned (TargetJoint::dens stays empty) and the moments and modes are the same bits.
+struct TargetJoint {
+    std::vector<double> mean, lo_x, step, bw;
+    Mat2D cov, corr;
+    std::vector<std::pair<int, int>> pairs;
+    std::vector<Mat2D> dens;
+    std::vector<double> mode_x, mode_y, mode_dens;
+};
+namespace detail {
+struct JointBuffers {
+    size_t P, G, np;
+    std::vector<int32_t> pairs;
+    std::vector<double> mean, cov, corr, dens, grid, bw, mode, md;
+    bool with_dens;
+    JointBuffers(size_t B, size_t P_, size_t G_, const std::vector<std::pair<int, int>>& given, bool dens_)
+        : P(P_), G(G_), with_dens(dens_) {
+        for (const auto& p : given) {
+            pairs.push_back(p.first);
+            pairs.push_back(p.second);
+        }
+        np = given.empty() ? P * (P - 1) / 2 : given.size();
+        mean.resize(B * P); cov.resize(B * P * P); corr.resize(B * P * P);
+        if (with_dens) dens.resize(B * np * G * G);
+        grid.resize(B * P * 2); bw.resize(B * P); mode.resize(B * np * 2); md.resize(B * np);
+    }
+    abc_joint arg(double cut, double bw_scale) {
+        return {G, cut, bw_scale, nullptr, pairs.empty() ? nullptr : pairs.data(), pairs.size() / 2, mean.data(), cov.data(),
+                corr.data(), with_dens ? dens.data() : nullptr, grid.data(), bw.data(), mode.data(), md.data()};
+    }
+    TargetJoint target(size_t b) const {
+        TargetJoint r;
+        r.mean.assign(mean.begin() + b * P, mean.begin() + (b + 1) * P);
+        r.bw.assign(bw.begin() + b * P, bw.begin() + (b + 1) * P);
+        r.lo_x.resize(P);
+        r.step.resize(P);
+        r.cov = Mat2D(P, P);
+        r.corr = Mat2D(P, P);
+        for (size_t i = 0; i < P; i++) {
+            r.lo_x[i] = grid[(b * P + i) * 2];
+            r.step[i] = grid[(b * P + i) * 2 + 1];
+            for (size_t j = 0; j < P; j++) {
+                r.cov(i, j) = cov[(b * P + i) * P + j];
+                r.corr(i, j) = corr[(b * P + i) * P + j];
+            }
+        }
+        if (pairs.empty()) {
+            for (size_t i = 0; i < P; i++)
+                for (size_t j = i + 1; j < P; j++) r.pairs.emplace_back((int)i, (int)j);
+        } else {
+            for (size_t p = 0; p < np; p++) r.pairs.emplace_back(pairs[2 * p], pairs[2 * p + 1]);
+        }
+        for (size_t p = 0; p < np; p++) {
+            if (with_dens) {
+                const double* f = dens.data() + (b * np + p) * G * G;
+                Mat2D d(G, G);
+                for (size_t g = 0; g < G; g++)
+                    for (size_t g2 = 0; g2 < G; g2++) d(g, g2) = f[g * G + g2];
+                r.dens.push_back(d);
+            }
+            r.mode_x.push_back(mode[(b * np + p) * 2]);
+            r.mode_y.push_back(mode[(b * np + p) * 2 + 1]);
+            r.mode_dens.push_back(md[b * np + p]);
+        }
+        return r;
+    }
+};
+}  // namespace detail
+inline std::vector<TargetJoint> particle_ranking_PLS_targets_joint(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                   const float_type train_frac, size_t K, size_t G = 64,
+                                                                   const std::vector<std::pair<int, int>>& pairs = {},
+                                                                   double cut = 3.0, double bw_scale = 1.0, int method = 0,
+                                                                   int kernel = 0, bool dens = true) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols();
+    detail::JointBuffers buf(B, P, G, pairs, dens);
+    abc_joint jt = buf.arg(cut, bw_scale);
+    check(abc_particle_ranking_pls_targets_joint(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac,
+                                                 max_components_ref(), component_rule(), nullptr, K, method, kernel, nullptr, nullptr,
+                                                 nullptr, &jt, nullptr));
+    std::vector<TargetJoint> res;
+    for (size_t b = 0; b < B; b++) res.push_back(buf.target(b));
+    return res;
+}
+// The joint posterior of the columns of values (K x P; weights: K entries, or empty for equal weights) (abc_weighted_joint).
+inline TargetJoint weighted_joint(const Mat2D& values, const std::vector<double>& weights, size_t G = 64,
+                                  const std::vector<std::pair<int, int>>& pairs = {}, double cut = 3.0, double bw_scale = 1.0,
+                                  bool dens = true) {
+    const size_t K = values.rows(), P = values.cols();
+    if (!weights.empty() && weights.size() != K) throw HipError(ABC_ERR_INVALID, "weights needs one entry per row");
+    detail::JointBuffers buf(1, P, G, pairs, dens);
+    abc_joint jt = buf.arg(cut, bw_scale);
+    check(abc_weighted_joint(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &jt));
+    return buf.target(0);
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

@@ -259,3 +259,60 @@ def weighted_density(V, w=None, G=512, cut=3.0, bw=None, bw_scale=1.0, dens=True
     ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     ctx.check(lib().abc_weighted_density_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(d)))
     return r
+
+
+def _joint(G, cut, bw_scale, bw, pairs, lead, P, dev, dens, mode):
+    """Device tensors for the joint outputs of prod(lead) targets with P parameters and the abc_joint pointing at them; pairs: None
+    or (npairs, 2).  Returns (struct, tensors, what must stay alive during the call)"""
+    f64 = torch.float64
+    G = int(G)
+    if bw is not None:
+        bw = torch.as_tensor(bw, dtype=f64).to(dev).expand(lead + (P,)).contiguous()
+    pr, given = _lib._joint_pairs(pairs, P)
+    n = pr.shape[0]
+    e = lambda *shape: torch.empty(lead + shape, dtype=f64, device=dev)
+    r = dict(mean=e(P), cov=e(P, P), corr=e(P, P), dens=e(n, G, G) if dens else None, grid=e(P, 2), bw=e(P),
+             mode=e(n, 2) if mode else None, mode_dens=e(n) if mode else None, pairs=pr)
+    d = _lib.Joint(G, float(cut), float(bw_scale), _ptr(bw), given.ctypes.data if given is not None else None,
+                   n if given is not None else 0, _ptr(r["mean"]), _ptr(r["cov"]), _ptr(r["corr"]), _ptr(r["dens"]), _ptr(r["grid"]),
+                   _ptr(r["bw"]), _ptr(r["mode"]), _ptr(r["mode_dens"]))
+    return d, r, (bw, given)
+
+
+def rank_targets_joint(X, model, A, targets, K, Y, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None, method=_lib.POSTERIOR_REJECTION,
+                       kernel=_lib.KERNEL_EPANECHNIKOV, exclude=None, dist=False, adjust=(), dens=True, mode=True, ctx=None):
+    """rank_targets followed by the joint posterior of every target (abc_rank_targets_joint_dev; method 0 rejection, 1 loclinear):
+    weighted means, covariance and correlation matrices of the P parameters, and for every pair in pairs ((npairs, 2) rows (i, j),
+    i != j; None: all i < j) the product-Gaussian kernel density on a G x G grid with its mode.  bw: given bandwidths (B, P) or None
+    (the marginal densities' rule times bw_scale).  dens holds B * npairs * G * G doubles: size the request accordingly.  Returns
+    dict(idx (B, K) int64, dist (B, K) or None, mean (B, P), cov and corr (B, P, P), dens (B, npairs, G, G) or None ([g, g']: g on
+    parameter i's grid), grid (B, P, 2): lo_x and step, bw (B, P), mode (B, npairs, 2) and mode_dens (B, npairs) or None, pairs: the
+    (npairs, 2) int32 host array, and the adjust members)."""
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
+    d, r, _keep = _joint(G, cut, bw_scale, bw, pairs, (B,), P, dev, dens, mode)
+    r.update(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
+             dist=torch.empty((B, K), dtype=torch.float64, device=dev) if dist else None)
+    members, adj = _adjust_out(adjust, B, K, P, A, dev)
+    r.update(members)
+    ctx.check(lib().abc_rank_targets_joint_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
+                                               targets.data_ptr(), ldt, B, _ptr(exclude), K, int(method), int(kernel),
+                                               r["idx"].data_ptr(), _ptr(r["dist"]), C.byref(adj), C.byref(d)))
+    return r
+
+
+def weighted_joint(V, w=None, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None, dens=True, mode=True, ctx=None):
+    """The joint posterior of P columns of K values (abc_weighted_joint_dev).  V: (P, K) holder as weighted_summary's; w: K weights
+    or None (equal); bw: P given bandwidths or None; pairs as rank_targets_joint.  Returns dict(mean (P,), cov and corr (P, P),
+    dens (npairs, G, G) or None, grid (P, 2), bw (P,), mode (npairs, 2) and mode_dens (npairs,) or None, pairs) as device tensors
+    (pairs: int32 host array)."""
+    assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
+    P, K = V.shape
+    dev = V.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    if w is not None:
+        w = w.to(device=dev, dtype=torch.float64).contiguous()
+        assert w.numel() == K
+    d, r, _keep = _joint(G, cut, bw_scale, bw, pairs, (), P, dev, dens, mode)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx.check(lib().abc_weighted_joint_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(d)))
+    return r

@@ -532,6 +532,68 @@ int abc_weighted_density_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K
 /* HOST-pointer form: V is K x P column-major (ldv = K); w and den's arrays in host memory. */
 int abc_weighted_density(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_density* den);
 
+/* ---- joint posterior of the batched ranking: covariances, correlations and pair densities -------------------------------------
+ * What a pairs plot of a posterior draws, for every target at once: the weighted means, covariance and Pearson correlation matrix
+ * of the P parameters, and for chosen pairs of parameters the two-dimensional Gaussian kernel density on a G x G grid with its
+ * mode.  For target b the entries are e = 0..K-1 in the ranking's row order; the values v_e[j] and weights w_e are those of the
+ * summaries and densities above (method 0 rejection, method 1 loclinear, generic: V[e + ldv j] and w[e], 1 when w is NULL).  Only
+ * entries with w_e > 0 count.  A parameter j that holds any non-finite value is bad: every output that involves j is NaN (mean_j,
+ * row and column j of cov and corr, grid and bw_out of j, dens / mode / mode_dens of every pair with j); the others are unaffected.
+ *   moments     W = sum w, S2 = sum w^2, mean_j = sum w v_j / W,
+ *               cov_ij = sum w (v_i - mean_i)(v_j - mean_j) / (W - S2 / W), the centred sum taken about the means in a second pass,
+ *               never from raw second moments; cov is 0 everywhere when that denominator is <= 0 (a single entry).  This is
+ *               numpy.cov(aweights = w).  One triangle is computed and mirrored: cov and corr are symmetric bit for bit.
+ *   correlation corr_ij = cov_ij / (sqrt(cov_ii) sqrt(cov_jj)), clamped to [-1, 1]; corr_ii is exactly 1 when cov_ii > 0; corr_ij
+ *               is NaN when either variance is 0.
+ *   bandwidth h_j and grid (lo_x_j, step_j) of parameter j: the bits abc_*_density returns for the same segment with the same G,
+ *               cut, bw_scale and bw (bw.nrd0 on the weighted moments and quantiles, as defined above); x_g = fma(g, step, lo_x).
+ *   pair density, for a pair (i, j), i != j, i on the first grid axis (x), j on the second (y):
+ *               f(x_g, y_g') = sum_e w_e exp(-((x_g - v_ei) / h_i)^2 / 2) exp(-((y_g' - v_ej) / h_j)^2 / 2) / (W 2 pi h_i h_j),
+ *               the product-Gaussian estimate of MASS::kde2d.  The bandwidths are those of the marginal densities above, not
+ *               kde2d's bandwidth.nrd.
+ *   joint mode  the smallest flat index g G + g' at which the device's own f is largest: mode = (x_g, y_g'), mode_dens = f there.
+ * Accuracy: |f_dev - f_ref| <= 1e-6 f_ref + 1e-290 max f_ref over the pair's grid, f_ref the long-double evaluation at the device's
+ * own h and grids: each factor's argument is formed in fp64 and only 2^r, |r| <= 1/2, is taken in f32, as the marginal density's
+ * terms.  mean within K 2^-52 max|v| and cov within 1e-9 sqrt(cov_ii cov_jj) of the long-double values.
+ * The order of every sum depends on (K, P) only and no floating-point atomics are involved: a target's outputs are the same bits on
+ * a repeat run, alone (B = 1) and in any batch, through the device and host entry points, whether or not dens is asked for, and for
+ * a pair alone or among other pairs.  The pair (j, i) is computed on its own and equals the transpose of (i, j) within the accuracy
+ * above, not bit for bit.  None of this has been checked against R.
+ * Layout: mean [b][P]; cov, corr [b][P][P]; grid [b][P][2] = lo_x, step; bw_out [b][P]; dens [b][pair][g][g']; mode [b][pair][2];
+ * mode_dens [b][pair]; the generic entries have one b.  The caller sizes dens: B npairs G^2 doubles, which is 3.9 GB for 1000
+ * targets x 120 pairs x 64^2; the host entries stage it in the context's workspace as well.  Limits as the summaries': A <= 64,
+ * P <= 1024, and a given pair list holds at most 2^22 pairs (ABC_ERR_UNSUPPORTED beyond). */
+typedef struct {
+    size_t G;                 /* 2..256 grid points per axis                                                                 */
+    double cut, bw_scale;     /* as abc_density                                                                              */
+    const double* bw;         /* optional: given bandwidths, one per (target, parameter), as abc_density                     */
+    const int32_t* pairs;     /* optional, HOST memory in every entry: npairs x 2 = (i, j), 0 <= i, j < P, i != j;           */
+    size_t npairs;            /*   NULL: all i < j in the order (0,1), (0,2), ..., (P-2,P-1), and npairs is ignored          */
+    double *mean, *cov, *corr;        /* [b][P], [b][P][P], [b][P][P]                                                        */
+    double* dens;                     /* [b][pair][g][g']                                                                    */
+    double *grid, *bw_out;            /* [b][P][2], [b][P]: those of abc_density at this G                                   */
+    double *mode, *mode_dens;         /* [b][pair][2], [b][pair]                                                             */
+} abc_joint;                  /* every output optional, at least one required; memory as the entry point's other arrays     */
+/* Device pointers; the arguments of abc_rank_targets_density_dev with jt in place of den.  idx, dist and adj are optional and
+ * receive the bits of the plain calls.  Besides the ranking's, the adjustment's and the method / kernel checks, ABC_ERR_INVALID
+ * for NULL jt, G outside 2..256, cut negative or non-finite, bw_scale <= 0 or non-finite, a pair index out of range or with
+ * i == j, pairs given with npairs == 0, every output member NULL, and a given bandwidth that is <= 0 or non-finite (checked on the
+ * device; the call then synchronises).  P = 1 with pairs NULL is valid: there are no pairs, and dens, mode and mode_dens are not
+ * written. */
+int abc_rank_targets_joint_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                               size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                               const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                               const abc_adjust_out* adj, const abc_joint* jt);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_density); every array of adj and jt in host memory. */
+int abc_particle_ranking_pls_targets_joint(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                           const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                           const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                           double* dist, const abc_adjust_out* adj, const abc_joint* jt, int32_t* ncomp);
+/* The same of P given columns of K values (as abc_weighted_density_dev, with its checks of V, ldv, K, P and w). */
+int abc_weighted_joint_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w, const abc_joint* jt);
+/* HOST-pointer form: V is K x P column-major (ldv = K); w and jt's arrays in host memory. */
+int abc_weighted_joint(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_joint* jt);
+
 /* ======================================================================================== */
 /* Multi-GPU: rows (particles) sharded over several GPUs of one node             */
 /* ======================================================================================== */
