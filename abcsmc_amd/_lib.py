@@ -161,24 +161,6 @@ SIGNATURES = {
                                          _vp]),
     "abc_particle_ranking_pls_targets_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _vp, _vp,
                                                      _vp, _vp]),
-    "abc_rank_targets_summary_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _i, _vp,
-                                          _vp, _vp, _vp]),
-    "abc_particle_ranking_pls_targets_summary": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _i, _vp,
-                                                      _vp, _vp, _vp, _vp]),
-    "abc_weighted_summary_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
-    "abc_weighted_summary": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
-    "abc_rank_targets_density_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _i, _vp,
-                                          _vp, _vp, _vp]),
-    "abc_particle_ranking_pls_targets_density": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _i, _vp,
-                                                      _vp, _vp, _vp, _vp]),
-    "abc_weighted_density_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
-    "abc_weighted_density": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
-    "abc_rank_targets_joint_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _i, _vp,
-                                        _vp, _vp, _vp]),
-    "abc_particle_ranking_pls_targets_joint": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _i, _vp,
-                                                    _vp, _vp, _vp, _vp]),
-    "abc_weighted_joint_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
-    "abc_weighted_joint": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "abc_particle_ranking_simple": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_calculate_doubled_variance": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "abc_weight_predictive_prior_uniform": (_i, [_vp, _sz, _vp]),
@@ -221,6 +203,18 @@ SIGNATURES = {
     "abc_generation_sharded_dev": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "abc_generation_multi": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
 }
+
+# The posterior products (abc_summary, abc_density, abc_joint) share their four argument lists, each ending in the product's
+# descriptor: a new product adds its name here.
+_PRODUCT_ARGS = {
+    "abc_rank_targets_%s_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp],
+    "abc_particle_ranking_pls_targets_%s": [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp,
+                                            _vp],
+    "abc_weighted_%s_dev": [_vp, _vp, _sz, _sz, _sz, _vp, _vp],
+    "abc_weighted_%s": [_vp, _vp, _sz, _sz, _vp, _vp],
+}
+PRODUCTS = ("summary", "density", "joint")
+SIGNATURES.update((entry % product, (_i, args)) for product in PRODUCTS for entry, args in _PRODUCT_ARGS.items())
 
 _LIB = None
 

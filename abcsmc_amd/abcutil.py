@@ -144,9 +144,45 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
 _METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_LOCLINEAR}
 
 
-def _summary_arg(probs, truth, quant, cdf):
+def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx):
+    """The call of particle_ranking_PLS_targets_{summary,density,joint}.  make(lead, P) -> (the product's struct, its outputs as a
+    dict, what must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and ncomp added."""
+    ctx = _ctx(ctx)
+    method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
+    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
+    d, o, _keep = make((B,), P)
+    idx = np.empty((B, K), dtype=np.uint64)
+    dist = np.empty((B, K))
+    ncomp = C.c_int32(0)
+    entry = getattr(lib(), "abc_particle_ranking_pls_targets_" + product)
+    ctx.check(entry(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K,
+                    method, kernel, _p(idx), _p(dist), None, C.byref(d), C.addressof(ncomp)))
+    o.update(idx=idx, dist=dist, ncomp=ncomp.value)
+    return o
+
+
+def _weighted_product(product, make, values, weights, ctx):
+    """The call of weighted_{summary,density,joint}: values as (K, P) column-major, weights as K contiguous values or None, and
+    make as _targets_product's with lead = ().  Returns the outputs."""
+    ctx = _ctx(ctx)
+    V = _f(values)
+    if V.ndim == 1:
+        V = _f(V.reshape(-1, 1))
+    K, P = V.shape
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    if w is not None and w.size != K:
+        raise ValueError("weights needs one entry per row")
+    d, o, _keep = make((), P)
+    ctx.check(getattr(lib(), "abc_weighted_" + product)(ctx.handle, _p(V), K, P, _p(w), C.byref(d)))
+    return o
+
+
+def _summary_arg(probs, truth, lead, P):
+    """Host arrays for the summaries of prod(lead) targets with P parameters and the abc_summary pointing at them"""
     pr = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
-    return _lib.Summary(pr.ctypes.data, pr.size, _p(truth), _p(quant), _p(cdf)), pr
+    tr = None if truth is None else np.ascontiguousarray(np.asarray(truth, dtype=np.float64).reshape(lead + (P,)))
+    o = dict(quant=np.empty(lead + (np.atleast_1d(probs).size, P)), cdf=np.empty(lead + (P,)) if tr is not None else None)
+    return _lib.Summary(pr.ctypes.data, pr.size, _p(tr), _p(o["quant"]), _p(o["cdf"])), o, (pr, tr)
 
 
 def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fraction, K, probs=(0.025, 0.5, 0.975), truth=None,
@@ -157,53 +193,29 @@ def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fract
     method "rejection": the rows' parameters, equal weights; "loclinear": the local-linear adjusted rows with the kernel's weights
     (as particle_ranking_PLS_targets_adjust).  Returns dict(quant (B, nq, P): [b, q, j], cdf (B, P) or None, probs, idx (B, K),
     dist (B, K), ncomp)."""
-    ctx = _ctx(ctx)
-    method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
-    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
-    tr = None
-    if truth is not None:
-        tr = np.ascontiguousarray(np.asarray(truth, dtype=np.float64).reshape(B, P))
-    nq = np.atleast_1d(probs).size
-    idx = np.empty((B, K), dtype=np.uint64)
-    dist = np.empty((B, K))
-    quant = np.empty((B, nq, P))
-    cdf = np.empty((B, P)) if tr is not None else None
-    s, pr = _summary_arg(probs, tr, quant, cdf)
-    ncomp = C.c_int32(0)
-    ctx.check(lib().abc_particle_ranking_pls_targets_summary(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
-                                                             int(max_comp), int(rule), _p(ex), K, method, kernel,
-                                                             _p(idx), _p(dist), None, C.byref(s), C.addressof(ncomp)))
-    return dict(quant=quant, cdf=cdf, probs=pr, idx=idx, dist=dist, ncomp=ncomp.value)
+    def make(lead, P):
+        s, o, keep = _summary_arg(probs, truth, lead, P)
+        o["probs"] = keep[0]
+        return s, o, keep
+    return _targets_product("summary", make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule,
+                            ctx)
 
 
 def weighted_summary(values, weights=None, probs=(0.025, 0.5, 0.975), truth=None, ctx=None):
     """Weighted quantiles (and the CDF at truth) of every column of values (K, P) on the device (abc_weighted_summary; the
     definition is in the header): equal weights when weights is None; with equal weights the quantiles are NumPy's "hazen".
     Returns dict(quant (nq, P), cdf (P,) or None)."""
-    ctx = _ctx(ctx)
-    V = _f(values)
-    if V.ndim == 1:
-        V = _f(V.reshape(-1, 1))
-    K, P = V.shape
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-    if w is not None and w.size != K:
-        raise ValueError("weights needs one entry per row")
-    tr = None if truth is None else np.ascontiguousarray(np.asarray(truth, dtype=np.float64).reshape(P))
-    nq = np.atleast_1d(probs).size
-    quant = np.empty((nq, P))
-    cdf = np.empty(P) if tr is not None else None
-    s, pr = _summary_arg(probs, tr, quant, cdf)
-    ctx.check(lib().abc_weighted_summary(ctx.handle, _p(V), K, P, _p(w), C.byref(s)))
-    return dict(quant=quant, cdf=cdf)
+    return _weighted_product("summary", lambda lead, P: _summary_arg(probs, truth, lead, P), values, weights, ctx)
 
 
-def _density_arg(G, cut, bw_scale, bw, ns, lead):
-    """Host arrays for ns segments (shaped lead + ...) and the abc_density pointing at them"""
+def _density_arg(G, cut, bw_scale, bw, lead, P, dens=True):
+    """Host arrays for the densities of prod(lead) targets with P parameters and the abc_density pointing at them"""
     G = int(G)
+    lead = lead + (P,)
     b = None
     if bw is not None:
-        b = np.ascontiguousarray(np.broadcast_to(np.asarray(bw, dtype=np.float64), lead).reshape(ns))
-    o = dict(dens=np.empty(lead + (G,)), grid=np.empty(lead + (2,)), bw=np.empty(lead), mode=np.empty(lead),
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(bw, dtype=np.float64), lead))
+    o = dict(dens=np.empty(lead + (G,)) if dens else None, grid=np.empty(lead + (2,)), bw=np.empty(lead), mode=np.empty(lead),
              mode_dens=np.empty(lead))
     d = _lib.Density(G, float(cut), float(bw_scale), _p(b), _p(o["dens"]), _p(o["grid"]), _p(o["bw"]), _p(o["mode"]),
                      _p(o["mode_dens"]))
@@ -225,19 +237,9 @@ def particle_ranking_PLS_targets_density(X_orig, Y_orig, targets, training_fract
     (B, P) (or a scalar) in place of the rule.  Returns dict(dens (B, P, G) (None with dens=False), x (B, P, G): the grid points,
     grid (B, P, 2): lo_x and step, bw (B, P): the bandwidths used, mode (B, P), mode_dens (B, P), idx (B, K), dist (B, K),
     ncomp)."""
-    ctx = _ctx(ctx)
-    method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
-    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
-    d, o, _b = _density_arg(G, cut, bw_scale, bw, B * P, (B, P))
-    if not dens:
-        d.dens, o["dens"] = None, None
-    idx = np.empty((B, K), dtype=np.uint64)
-    dist = np.empty((B, K))
-    ncomp = C.c_int32(0)
-    ctx.check(lib().abc_particle_ranking_pls_targets_density(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
-                                                             int(max_comp), int(rule), _p(ex), K, method, kernel,
-                                                             _p(idx), _p(dist), None, C.byref(d), C.addressof(ncomp)))
-    o.update(x=_grid_points(o["grid"], int(G)), idx=idx, dist=dist, ncomp=ncomp.value)
+    o = _targets_product("density", lambda lead, P: _density_arg(G, cut, bw_scale, bw, lead, P, dens), X_orig, Y_orig, targets,
+                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx)
+    o["x"] = _grid_points(o["grid"], int(G))
     return o
 
 
@@ -245,16 +247,7 @@ def weighted_density(values, weights=None, G=512, cut=3.0, bw=None, bw_scale=1.0
     """The weighted Gaussian kernel density and mode of every column of values (K, P) on the device (abc_weighted_density; the
     definition is in the header); equal weights when weights is None.  Returns dict(dens (P, G), x (P, G), grid (P, 2), bw (P,),
     mode (P,), mode_dens (P,))."""
-    ctx = _ctx(ctx)
-    V = _f(values)
-    if V.ndim == 1:
-        V = _f(V.reshape(-1, 1))
-    K, P = V.shape
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-    if w is not None and w.size != K:
-        raise ValueError("weights needs one entry per row")
-    d, o, _b = _density_arg(G, cut, bw_scale, bw, P, (P,))
-    ctx.check(lib().abc_weighted_density(ctx.handle, _p(V), K, P, _p(w), C.byref(d)))
+    o = _weighted_product("density", lambda lead, P: _density_arg(G, cut, bw_scale, bw, lead, P), values, weights, ctx)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
 
@@ -287,17 +280,9 @@ def particle_ranking_PLS_targets_joint(X_orig, Y_orig, targets, training_fractio
     dict(mean (B, P), cov (B, P, P), corr (B, P, P), dens (B, npairs, G, G) (None with dens=False; [g, g']: g along parameter i),
     x (B, P, G): every parameter's grid points, grid (B, P, 2), bw (B, P), mode (B, npairs, 2), mode_dens (B, npairs), pairs
     (npairs, 2), idx (B, K), dist (B, K), ncomp)."""
-    ctx = _ctx(ctx)
-    method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
-    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
-    d, o, _keep = _joint_arg(G, cut, bw_scale, bw, pairs, (B,), P, dens)
-    idx = np.empty((B, K), dtype=np.uint64)
-    dist = np.empty((B, K))
-    ncomp = C.c_int32(0)
-    ctx.check(lib().abc_particle_ranking_pls_targets_joint(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
-                                                           int(max_comp), int(rule), _p(ex), K, method, kernel, _p(idx), _p(dist),
-                                                           None, C.byref(d), C.addressof(ncomp)))
-    o.update(x=_grid_points(o["grid"], int(G)), idx=idx, dist=dist, ncomp=ncomp.value)
+    o = _targets_product("joint", lambda lead, P: _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens), X_orig, Y_orig, targets,
+                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx)
+    o["x"] = _grid_points(o["grid"], int(G))
     return o
 
 
@@ -305,16 +290,7 @@ def weighted_joint(values, weights=None, G=64, cut=3.0, bw=None, bw_scale=1.0, p
     """The joint posterior of the columns of values (K, P) on the device (abc_weighted_joint; the definition is in the header);
     equal weights when weights is None.  Returns dict(mean (P,), cov (P, P), corr (P, P), dens (npairs, G, G) or None, x (P, G),
     grid (P, 2), bw (P,), mode (npairs, 2), mode_dens (npairs,), pairs (npairs, 2))."""
-    ctx = _ctx(ctx)
-    V = _f(values)
-    if V.ndim == 1:
-        V = _f(V.reshape(-1, 1))
-    K, P = V.shape
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-    if w is not None and w.size != K:
-        raise ValueError("weights needs one entry per row")
-    d, o, _keep = _joint_arg(G, cut, bw_scale, bw, pairs, (), P, dens)
-    ctx.check(lib().abc_weighted_joint(ctx.handle, _p(V), K, P, _p(w), C.byref(d)))
+    o = _weighted_product("joint", lambda lead, P: _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens), values, weights, ctx)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
 

@@ -1189,34 +1189,10 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
 }
 
 // ---- batched ranking of many observed targets against one fitted set (targets.hip), optionally followed by the local-linear
-// adjustment (adjust.hip) and the weighted posterior quantiles and CDF (summary.hip), densities and modes (density.hip) or joint
-// moments and pair densities (joint.hip): one pipeline behind ten entry points ----
-namespace {
-// what follows the ranking: nothing, the adjustment, the summaries, the densities, the joint moments and pair densities
-enum { TG_PLAIN, TG_ADJUST, TG_SUMMARY, TG_DENSITY, TG_JOINT };
-struct TgRequest {                             // (members in the order of the entries' arguments)
-    int kind;
-    const double* X;  size_t ldx;
-    const double* Y;  size_t ldy;
-    size_t N, M, P;
-    const double* model;  size_t A;
-    const double* targets;  size_t ldt, B;
-    const uint64_t* exclude;
-    size_t K;
-    uint64_t* idx;                             // optional for TG_SUMMARY, TG_DENSITY and TG_JOINT
-    double* dist;                              // optional
-    double* post_mean = nullptr;               // TG_PLAIN only, optional
-    int method = 0, kernel = 0;                // method: the segment kinds only (of which values the summaries are)
-    const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; the segment kinds: optional, method 1 only
-    const abc_summary* sum = nullptr;          // TG_SUMMARY only
-    const abc_density* den = nullptr;          // TG_DENSITY only
-    const abc_joint* jnt = nullptr;            // TG_JOINT only
-    bool any_excl = false;                     // exclude names a row for some target: set by tg_check
-    bool segments() const { return kind == TG_SUMMARY || kind == TG_DENSITY || kind == TG_JOINT; }      // the rows' values are read after the ranking
-    bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
-};
-}  // namespace
-
+// adjustment (adjust.hip) or by a posterior product of every target's retained rows: the weighted quantiles and CDF (summary.hip),
+// the densities and modes (density.hip) or the joint moments and pair densities (joint.hip).  One pipeline (tg_*) behind the ten
+// entry points of the family and one pair of paths (weighted_dev, weighted_host) behind the six abc_weighted_* entries, which
+// compute the same products from given values; what differs between the products is in Product ----
 static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
     if (!sum) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (sum is required)", fn);
     if (sum->nq == 0 || sum->nq > 64) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: nq = %zu levels (1 to 64)", fn, sum->nq);
@@ -1258,124 +1234,6 @@ static int joint_check(abc_ctx* ctx, const char* fn, const abc_joint* jt, size_t
     if (!jt->mean && !jt->cov && !jt->corr && !jt->dens && !jt->grid && !jt->bw_out && !jt->mode && !jt->mode_dens)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of jt is NULL", fn);
     return ABC_OK;
-}
-
-// Argument checks of the family; sets r.any_excl.  host: the arrays are in host memory and the model is fitted by the call
-// (which needs Y); otherwise exclude is brought to the host here, after every check that does not need it.
-static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
-    const bool plain = r.kind == TG_PLAIN, summary = r.segments();
-    const size_t N = r.N, B = r.B, K = r.K;
-    if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
-    if (!r.targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (targets is required)", fn);
-    if (!r.idx && !summary) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (idx is required)", fn);
-    if (!r.Y && (host || !plain)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (Y is required)", fn);
-    if (!r.Y && r.post_mean && r.P) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: post_mean needs Y", fn);
-    if (!host) {
-        if (!r.model) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (model is required)", fn);
-        if (r.A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
-        if (r.ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, r.ldx, N);
-        if (r.ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, r.ldt, B);
-    }
-    if (summary && r.method != ABC_POSTERIOR_REJECTION && r.method != ABC_POSTERIOR_LOCLINEAR)
-        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: method %d (0 = rejection, 1 = loclinear)", fn, r.method);
-    if (r.kind == TG_ADJUST && !r.adj) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (out is required)", fn);
-    if (!plain && r.kernel != ABC_KERNEL_EPANECHNIKOV && r.kernel != ABC_KERNEL_RECTANGULAR)
-        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: kernel %d (0 = Epanechnikov, 1 = rectangular)", fn, r.kernel);
-    if ((!plain || r.post_mean) && r.P && r.ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, r.ldy, N);
-    if (!plain) {     // the adjustment's limits, for both summary methods too
-        if (r.A > 64) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: A = %zu components (at most 64)", fn, r.A);
-        if (r.P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, r.P);
-    }
-    if (r.kind == TG_SUMMARY) ABC_TRY(summary_check(ctx, fn, r.sum));
-    if (r.kind == TG_DENSITY) ABC_TRY(density_check(ctx, fn, r.den));
-    if (r.kind == TG_JOINT) ABC_TRY(joint_check(ctx, fn, r.jnt, r.P));
-    if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
-    if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
-    if (r.M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no metrics (M == 0)", fn);
-    if (K > N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N = %zu", fn, K, N);
-    if (N >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: N = %zu rows (at most 2^32 - 1)", fn, N);
-    std::vector<uint64_t> copy;
-    const uint64_t* ex = r.exclude;
-    if (ex && !host) {
-        copy.resize(B);
-        ABC_HIP(ctx, hipMemcpyAsync(copy.data(), r.exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ex = copy.data();
-    }
-    r.any_excl = false;
-    if (ex)
-        for (size_t b = 0; b < B; b++) {
-            if (ex[b] == UINT64_MAX) continue;
-            if (ex[b] >= N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: exclude[%zu] = %llu is not a row (N = %zu)", fn, b,
-                                     (unsigned long long)ex[b], N);
-            r.any_excl = true;
-        }
-    if (r.any_excl && K > N - 1) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N - 1 = %zu with an excluded row", fn, K, N - 1);
-    return ABC_OK;
-}
-
-// Arena bytes of a checked request: what tg_run takes and, for the host entries (host: the fit under `rule`, every array staged),
-// what tg_host takes around it.  The device entries get the model from the caller, so their ranking needs no fit workspace.
-static size_t joint_stage_bytes(const abc_joint* h, size_t B, size_t P);
-static size_t tg_need(const TgRequest& r, bool host, int rule) {
-    const size_t N = r.N, M = r.M, P = r.P, A = r.A, B = r.B, K = r.K;
-    size_t b = abc_targets_need(N, A, B, K, r.any_excl);
-    if (r.regress()) b += abc_adjust_need(N, A, P, B, K);
-    if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
-    if (r.kind == TG_SUMMARY) b += abc_summary_need(B, K, P);
-    if (r.kind == TG_DENSITY) b += abc_density_need(B, K, P, r.den->G);
-    if (r.kind == TG_JOINT) b += abc_joint_need(B, K, P, r.jnt->G, abc_joint_pairs(r.jnt, P));
-    if (!host) return b + abc_ws_need(N, 1, 1, 1, K + 1, 0, 0);
-    b += abc_ws_need(N, M, P, A, K + 1, 0, 0) + (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0);
-    b += (N * (M + P) + M + 4) * 8;                                               // X, Y, the zero observation and its one idx, dist
-    b += (B * M + B + 2 * B * K) * 8 + 8 * 256;                                   // targets, exclude, idx, dist
-    if (r.kind == TG_PLAIN) b += B * P * 8;                                       // post_mean
-    else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
-    if (r.kind == TG_SUMMARY) b += B * P * (r.sum->nq + 2) * 8 + 16 * 256;        // truth, quant, cdf
-    if (r.kind == TG_DENSITY) b += B * P * (r.den->G + 6) * 8 + 32 * 256;         // bw, dens, grid, bw_out, mode, mode_dens
-    if (r.kind == TG_JOINT) b += joint_stage_bytes(r.jnt, B, P);
-    return b;
-}
-
-// The ranking or (regress) the ranking with the adjustment, then the summaries or densities if asked for; device pointers, the workspace reserved.
-static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
-    const size_t B = r.B, K = r.K;
-    const bool summary = r.segments();
-    uint64_t* ix = r.idx;
-    double* d = r.dist;
-    if (summary) {     // the summaries and densities read both
-        if (!ix) ix = (uint64_t*)abc_ws_alloc(ctx, B * K * 8);
-        if (!d) d = (double*)abc_ws_alloc(ctx, B * K * 8);
-        if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    }
-    abc_adj_keep keep;
-    if (!r.regress()) {     // (post_mean: of the plain ranking only)
-        ABC_TRY(launch_rank_targets(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                    r.any_excl, K, ix, d, r.post_mean));
-    } else {                // (without keep nothing is regressed when every member of adj is NULL)
-        abc_adjust_out od = {};
-        if (r.adj) od = *r.adj;
-        ABC_TRY(launch_rank_targets_adjust(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                           r.any_excl, K, r.kernel, ix, d, &od, summary ? &keep : nullptr));
-    }
-    if (!summary) return ABC_OK;
-    SmValues sv = {};
-    sv.method = r.method;
-    sv.idx = ix;
-    sv.Y = r.Y;
-    sv.ldy = r.ldy;
-    sv.adj = r.regress() ? &keep : nullptr;
-    sv.A = (int)r.A;
-    sv.kernel = r.kernel;
-    if (r.kind == TG_DENSITY) return launch_density(ctx, sv, B, K, r.P, r.den, fn);
-    if (r.kind == TG_JOINT) return launch_joint(ctx, sv, B, K, r.P, r.jnt, fn);
-    return launch_summary(ctx, sv, B, K, r.P, r.sum);
-}
-
-static int tg_dev(abc_ctx* ctx, const char* fn, TgRequest r) {
-    ABC_TRY(tg_check(ctx, fn, r, false));
-    ABC_TRY(abc_ws_reserve(ctx, tg_need(r, false, 0)));
-    return tg_run(ctx, fn, r);
 }
 
 // an abc_summary's arrays for G groups of P segments, host (h) <-> arena: probs stay where they are, NULL members stay NULL
@@ -1441,6 +1299,211 @@ static void joint_down(Stage& s, const abc_joint* h, const abc_joint& d, size_t 
     s.down(h->mode_dens, d.mode_dens, B * np);
 }
 
+namespace {
+// A posterior product: what is computed from the segments' values and weights, described by the caller's abc_summary, abc_density
+// or abc_joint.  Every member below has one row per kind, and nothing else in this file tells the kinds apart: a new product adds
+// its constructor and its six rows here.
+struct Product {
+    enum Kind { NONE, SUMMARY, DENSITY, JOINT } kind = NONE;
+    union {
+        const abc_summary* sum = nullptr;
+        const abc_density* den;
+        const abc_joint* jnt;
+    };
+    union { abc_summary sum; abc_density den; abc_joint jnt; } staged;      // stage()'s copy of the descriptor
+    Product() {}
+    explicit Product(const abc_summary* s) : kind(SUMMARY), sum(s) {}
+    explicit Product(const abc_density* d) : kind(DENSITY), den(d) {}
+    explicit Product(const abc_joint* j) : kind(JOINT), jnt(j) {}
+
+    // the descriptor's own argument checks (a NULL descriptor among them)
+    int check(abc_ctx* ctx, const char* fn, size_t P) const {
+        switch (kind) {
+        case SUMMARY: return summary_check(ctx, fn, sum);
+        case DENSITY: return density_check(ctx, fn, den);
+        case JOINT: return joint_check(ctx, fn, jnt, P);
+        default: return ABC_OK;
+        }
+    }
+    // workspace of launch() for B groups of P segments of K values; checked descriptors only, as everything below
+    size_t need(size_t B, size_t K, size_t P) const {
+        switch (kind) {
+        case SUMMARY: return abc_summary_need(B, K, P);
+        case DENSITY: return abc_density_need(B, K, P, den->G);
+        case JOINT: return abc_joint_need(B, K, P, jnt->G, abc_joint_pairs(jnt, P));
+        default: return 0;
+        }
+    }
+    // arena bytes of stage(): what the host entries reserve beyond need()
+    size_t stage_bytes(size_t B, size_t P) const {
+        switch (kind) {
+        case SUMMARY: return B * P * (sum->nq + 2) * 8 + 16 * 256;         // truth, quant, cdf
+        case DENSITY: return B * P * (den->G + 6) * 8 + 32 * 256;          // bw, dens, grid, bw_out, mode, mode_dens
+        case JOINT: return joint_stage_bytes(jnt, B, P);
+        default: return 0;
+        }
+    }
+    // A host descriptor's arrays in the arena (inputs uploaded, NULL members stay NULL): the product on those copies.  It points
+    // into this object, which has to outlive it.
+    Product stage(Stage& s, size_t B, size_t P) {
+        switch (kind) {
+        case SUMMARY: staged.sum = summary_stage(s, sum, B, P); return Product(&staged.sum);
+        case DENSITY: staged.den = density_stage(s, den, B * P); return Product(&staged.den);
+        case JOINT: staged.jnt = joint_stage(s, jnt, B, P); return Product(&staged.jnt);
+        default: return Product();
+        }
+    }
+    // stage()'s outputs back into the host descriptor's arrays
+    void down(Stage& s, size_t B, size_t P) const {
+        switch (kind) {
+        case SUMMARY: summary_down(s, sum, staged.sum, B, P); break;
+        case DENSITY: density_down(s, den, staged.den, B * P); break;
+        case JOINT: joint_down(s, jnt, staged.jnt, B, P); break;
+        default: break;
+        }
+    }
+    // device descriptor, the workspace reserved
+    int launch(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const char* fn) const {
+        switch (kind) {
+        case SUMMARY: return launch_summary(ctx, sv, B, K, P, sum);
+        case DENSITY: return launch_density(ctx, sv, B, K, P, den, fn);
+        case JOINT: return launch_joint(ctx, sv, B, K, P, jnt, fn);
+        default: return ABC_OK;
+        }
+    }
+};
+
+// what follows the ranking: nothing, the adjustment, a posterior product
+enum { TG_PLAIN, TG_ADJUST, TG_PRODUCT };
+struct TgRequest {                             // (members in the order of the entries' arguments)
+    int kind;
+    const double* X;  size_t ldx;
+    const double* Y;  size_t ldy;
+    size_t N, M, P;
+    const double* model;  size_t A;
+    const double* targets;  size_t ldt, B;
+    const uint64_t* exclude;
+    size_t K;
+    uint64_t* idx;                             // optional for TG_PRODUCT
+    double* dist;                              // optional
+    double* post_mean = nullptr;               // TG_PLAIN only, optional
+    int method = 0, kernel = 0;                // method: TG_PRODUCT only (of which values the segments are)
+    const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; TG_PRODUCT: optional, method 1 only
+    Product prod;                              // TG_PRODUCT only
+    bool any_excl = false;                     // exclude names a row for some target: set by tg_check
+    bool segments() const { return kind == TG_PRODUCT; }      // the rows' values are read after the ranking
+    bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
+};
+}  // namespace
+
+// Argument checks of the family; sets r.any_excl.  host: the arrays are in host memory and the model is fitted by the call
+// (which needs Y); otherwise exclude is brought to the host here, after every check that does not need it.
+static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
+    const bool plain = r.kind == TG_PLAIN, summary = r.segments();
+    const size_t N = r.N, B = r.B, K = r.K;
+    if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
+    if (!r.targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (targets is required)", fn);
+    if (!r.idx && !summary) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (idx is required)", fn);
+    if (!r.Y && (host || !plain)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (Y is required)", fn);
+    if (!r.Y && r.post_mean && r.P) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: post_mean needs Y", fn);
+    if (!host) {
+        if (!r.model) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (model is required)", fn);
+        if (r.A == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A == 0", fn);
+        if (r.ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, r.ldx, N);
+        if (r.ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, r.ldt, B);
+    }
+    if (summary && r.method != ABC_POSTERIOR_REJECTION && r.method != ABC_POSTERIOR_LOCLINEAR)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: method %d (0 = rejection, 1 = loclinear)", fn, r.method);
+    if (r.kind == TG_ADJUST && !r.adj) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (out is required)", fn);
+    if (!plain && r.kernel != ABC_KERNEL_EPANECHNIKOV && r.kernel != ABC_KERNEL_RECTANGULAR)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: kernel %d (0 = Epanechnikov, 1 = rectangular)", fn, r.kernel);
+    if ((!plain || r.post_mean) && r.P && r.ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, r.ldy, N);
+    if (!plain) {     // the adjustment's limits, for both of a product's methods too
+        if (r.A > 64) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: A = %zu components (at most 64)", fn, r.A);
+        if (r.P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, r.P);
+    }
+    ABC_TRY(r.prod.check(ctx, fn, r.P));
+    if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
+    if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
+    if (r.M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no metrics (M == 0)", fn);
+    if (K > N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N = %zu", fn, K, N);
+    if (N >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: N = %zu rows (at most 2^32 - 1)", fn, N);
+    std::vector<uint64_t> copy;
+    const uint64_t* ex = r.exclude;
+    if (ex && !host) {
+        copy.resize(B);
+        ABC_HIP(ctx, hipMemcpyAsync(copy.data(), r.exclude, B * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ex = copy.data();
+    }
+    r.any_excl = false;
+    if (ex)
+        for (size_t b = 0; b < B; b++) {
+            if (ex[b] == UINT64_MAX) continue;
+            if (ex[b] >= N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: exclude[%zu] = %llu is not a row (N = %zu)", fn, b,
+                                     (unsigned long long)ex[b], N);
+            r.any_excl = true;
+        }
+    if (r.any_excl && K > N - 1) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K = %zu > N - 1 = %zu with an excluded row", fn, K, N - 1);
+    return ABC_OK;
+}
+
+// Arena bytes of a checked request: what tg_run takes and, for the host entries (host: the fit under `rule`, every array staged),
+// what tg_host takes around it.  The device entries get the model from the caller, so their ranking needs no fit workspace.
+static size_t tg_need(const TgRequest& r, bool host, int rule) {
+    const size_t N = r.N, M = r.M, P = r.P, A = r.A, B = r.B, K = r.K;
+    size_t b = abc_targets_need(N, A, B, K, r.any_excl);
+    if (r.regress()) b += abc_adjust_need(N, A, P, B, K);
+    if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
+    b += r.prod.need(B, K, P);
+    if (!host) return b + abc_ws_need(N, 1, 1, 1, K + 1, 0, 0);
+    b += abc_ws_need(N, M, P, A, K + 1, 0, 0) + (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0);
+    b += (N * (M + P) + M + 4) * 8;                                               // X, Y, the zero observation and its one idx, dist
+    b += (B * M + B + 2 * B * K) * 8 + 8 * 256;                                   // targets, exclude, idx, dist
+    if (r.kind == TG_PLAIN) b += B * P * 8;                                       // post_mean
+    else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
+    return b + r.prod.stage_bytes(B, P);
+}
+
+// The ranking or (regress) the ranking with the adjustment, then the product if one is asked for; device pointers, the workspace reserved.
+static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
+    const size_t B = r.B, K = r.K;
+    const bool summary = r.segments();
+    uint64_t* ix = r.idx;
+    double* d = r.dist;
+    if (summary) {     // every product reads both
+        if (!ix) ix = (uint64_t*)abc_ws_alloc(ctx, B * K * 8);
+        if (!d) d = (double*)abc_ws_alloc(ctx, B * K * 8);
+        if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    }
+    abc_adj_keep keep;
+    if (!r.regress()) {     // (post_mean: of the plain ranking only)
+        ABC_TRY(launch_rank_targets(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
+                                    r.any_excl, K, ix, d, r.post_mean));
+    } else {                // (without keep nothing is regressed when every member of adj is NULL)
+        abc_adjust_out od = {};
+        if (r.adj) od = *r.adj;
+        ABC_TRY(launch_rank_targets_adjust(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
+                                           r.any_excl, K, r.kernel, ix, d, &od, summary ? &keep : nullptr));
+    }
+    if (!summary) return ABC_OK;
+    SmValues sv = {};
+    sv.method = r.method;
+    sv.idx = ix;
+    sv.Y = r.Y;
+    sv.ldy = r.ldy;
+    sv.adj = r.regress() ? &keep : nullptr;
+    sv.A = (int)r.A;
+    sv.kernel = r.kernel;
+    return r.prod.launch(ctx, sv, B, K, r.P, fn);
+}
+
+static int tg_dev(abc_ctx* ctx, const char* fn, TgRequest r) {
+    ABC_TRY(tg_check(ctx, fn, r, false));
+    ABC_TRY(abc_ws_reserve(ctx, tg_need(r, false, 0)));
+    return tg_run(ctx, fn, r);
+}
+
 // The host entries: h holds host pointers.  Upload, one fit, the request on the arena's copies, downloads, synchronise.
 static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac, int max_comp, int rule, int32_t* ncomp) {
     const size_t N = h.N, M = h.M, P = h.P, B = h.B, K = h.K;
@@ -1482,21 +1545,7 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         od.status = ah->status ? s.dev<int32_t>(B) : nullptr;
     }
     r.adj = ah ? &od : nullptr;
-    abc_summary sd;
-    if (h.sum) {
-        sd = summary_stage(s, h.sum, B, P);
-        r.sum = &sd;
-    }
-    abc_density dd;
-    if (h.den) {
-        dd = density_stage(s, h.den, B * P);
-        r.den = &dd;
-    }
-    abc_joint jd;
-    if (h.jnt) {
-        jd = joint_stage(s, h.jnt, B, P);
-        r.jnt = &jd;
-    }
+    r.prod = h.prod.stage(s, B, P);
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_TRY(tg_run(ctx, fn, r));
     s.down(h.idx, r.idx, B * K);
@@ -1509,9 +1558,7 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         s.down(ah->rank, od.rank, B);
         s.down(ah->status, od.status, B);
     }
-    if (h.sum) summary_down(s, h.sum, sd, B, P);
-    if (h.den) density_down(s, h.den, dd, B * P);
-    if (h.jnt) joint_down(s, h.jnt, jd, B, P);
+    h.prod.down(s, B, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
@@ -1557,22 +1604,62 @@ extern "C" int abc_rank_targets_summary_dev(abc_ctx* ctx, const double* X, size_
                                             const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
                                             const abc_adjust_out* adj, const abc_summary* sum) {
     CHECK_CTX(ctx);
-    const TgRequest r{TG_SUMMARY, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
-                      adj, sum};
+    const TgRequest r{TG_PRODUCT, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(sum)};
     return tg_dev(ctx, "abc_rank_targets_summary_dev", r);
 }
 
 extern "C" int abc_particle_ranking_pls_targets_summary(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
                                                         const double* targets, size_t B, double train_frac, int max_comp, int rule,
                                                         const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
-                                                        double* dist, const abc_adjust_out* adj, const abc_summary* sum,
-                                                        int32_t* ncomp) {
+                                                        double* dist, const abc_adjust_out* adj, const abc_summary* sum, int32_t* ncomp) {
     CHECK_CTX(ctx);
-    const TgRequest h{TG_SUMMARY, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
-                      adj, sum};
+    const TgRequest h{TG_PRODUCT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(sum)};
     return tg_host(ctx, "abc_particle_ranking_pls_targets_summary", h, train_frac, max_comp, rule, ncomp);
 }
 
+extern "C" int abc_rank_targets_density_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                            size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                            const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                            const abc_adjust_out* adj, const abc_density* den) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_PRODUCT, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(den)};
+    return tg_dev(ctx, "abc_rank_targets_density_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_density(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                        const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                        const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                                        double* dist, const abc_adjust_out* adj, const abc_density* den, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_PRODUCT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(den)};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_density", h, train_frac, max_comp, rule, ncomp);
+}
+
+extern "C" int abc_rank_targets_joint_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                          size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                          const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                          const abc_adjust_out* adj, const abc_joint* jt) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_PRODUCT, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(jt)};
+    return tg_dev(ctx, "abc_rank_targets_joint_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_joint(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                      const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                      const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                                      double* dist, const abc_adjust_out* adj, const abc_joint* jt, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_PRODUCT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(jt)};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_joint", h, train_frac, max_comp, rule, ncomp);
+}
+
+// ---- the same products of P given columns of K values (V[e + ldv j], weights w or NULL): one segment group ----
 static int weighted_values_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P) {
     if (!V) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (V is required)", fn);
     if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
@@ -1583,177 +1670,74 @@ static int weighted_values_check(abc_ctx* ctx, const char* fn, const double* V, 
     return ABC_OK;
 }
 
-static int weighted_summary_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P,
-                                  const abc_summary* sum) {
+static SmValues weighted_values(const double* V, size_t ldv, const double* w) {
+    SmValues sv = {};
+    sv.method = 2;
+    sv.V = V;
+    sv.ldv = ldv;
+    sv.w = w;
+    return sv;
+}
+
+// device pointers (p's arrays too)
+static int weighted_dev(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P, const double* w,
+                        const Product& p) {
     ABC_TRY(weighted_values_check(ctx, fn, V, ldv, K, P));
-    return summary_check(ctx, fn, sum);
+    ABC_TRY(p.check(ctx, fn, P));
+    ABC_TRY(abc_ws_reserve(ctx, p.need(1, K, P) + 16 * 256));
+    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
+    return p.launch(ctx, weighted_values(V, ldv, w), 1, K, P, fn);
+}
+
+// host pointers: upload, the product on the arena's copies, downloads, synchronise
+static int weighted_host(abc_ctx* ctx, const char* fn, const double* V, size_t K, size_t P, const double* w, Product p) {
+    ABC_TRY(weighted_values_check(ctx, fn, V, K, K, P));
+    ABC_TRY(p.check(ctx, fn, P));
+    ABC_TRY(abc_ws_reserve(ctx, p.need(1, K, P) + (K * P + K) * 8 + p.stage_bytes(1, P) + 16 * 256));
+    Stage s{ctx};
+    const double* V_d = s.up(V, K * P);
+    const double* w_d = w ? s.up(w, K) : nullptr;
+    const Product d = p.stage(s, 1, P);
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
+    ABC_TRY(d.launch(ctx, weighted_values(V_d, K, w_d), 1, K, P, fn));
+    p.down(s, 1, P);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
 }
 
 extern "C" int abc_weighted_summary_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
                                         const abc_summary* sum) {
     CHECK_CTX(ctx);
-    const char* fn = "abc_weighted_summary_dev";
-    ABC_TRY(weighted_summary_check(ctx, fn, V, ldv, K, P, sum));
-    ABC_TRY(abc_ws_reserve(ctx, abc_summary_need(1, K, P) + 16 * 256));
-    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
-    SmValues sv;
-    memset(&sv, 0, sizeof(sv));
-    sv.method = 2;
-    sv.V = V;
-    sv.ldv = ldv;
-    sv.w = w;
-    return launch_summary(ctx, sv, 1, K, P, sum);
+    return weighted_dev(ctx, "abc_weighted_summary_dev", V, ldv, K, P, w, Product(sum));
 }
 
 extern "C" int abc_weighted_summary(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_summary* sum) {
     CHECK_CTX(ctx);
-    const char* fn = "abc_weighted_summary";
-    ABC_TRY(weighted_summary_check(ctx, fn, V, K, K, P, sum));
-    const size_t nq = sum->nq;
-    ABC_TRY(abc_ws_reserve(ctx, abc_summary_need(1, K, P) + (K * P + K + P * (nq + 2)) * 8 + 32 * 256));
-    Stage s{ctx};
-    const double* V_d = s.up(V, K * P);
-    const double* w_d = w ? s.up(w, K) : nullptr;
-    const abc_summary sd = summary_stage(s, sum, 1, P);
-    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
-    SmValues sv;
-    memset(&sv, 0, sizeof(sv));
-    sv.method = 2;
-    sv.V = V_d;
-    sv.ldv = K;
-    sv.w = w_d;
-    ABC_TRY(launch_summary(ctx, sv, 1, K, P, &sd));
-    summary_down(s, sum, sd, 1, P);
-    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
-}
-
-extern "C" int abc_rank_targets_density_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
-                                            size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
-                                            const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
-                                            const abc_adjust_out* adj, const abc_density* den) {
-    CHECK_CTX(ctx);
-    const TgRequest r{TG_DENSITY, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
-                      adj, nullptr, den};
-    return tg_dev(ctx, "abc_rank_targets_density_dev", r);
-}
-
-extern "C" int abc_particle_ranking_pls_targets_density(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
-                                                        const double* targets, size_t B, double train_frac, int max_comp, int rule,
-                                                        const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
-                                                        double* dist, const abc_adjust_out* adj, const abc_density* den,
-                                                        int32_t* ncomp) {
-    CHECK_CTX(ctx);
-    const TgRequest h{TG_DENSITY, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
-                      adj, nullptr, den};
-    return tg_host(ctx, "abc_particle_ranking_pls_targets_density", h, train_frac, max_comp, rule, ncomp);
+    return weighted_host(ctx, "abc_weighted_summary", V, K, P, w, Product(sum));
 }
 
 extern "C" int abc_weighted_density_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
                                         const abc_density* den) {
     CHECK_CTX(ctx);
-    const char* fn = "abc_weighted_density_dev";
-    ABC_TRY(weighted_values_check(ctx, fn, V, ldv, K, P));
-    ABC_TRY(density_check(ctx, fn, den));
-    ABC_TRY(abc_ws_reserve(ctx, abc_density_need(1, K, P, den->G) + 16 * 256));
-    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
-    SmValues sv;
-    memset(&sv, 0, sizeof(sv));
-    sv.method = 2;
-    sv.V = V;
-    sv.ldv = ldv;
-    sv.w = w;
-    return launch_density(ctx, sv, 1, K, P, den, fn);
+    return weighted_dev(ctx, "abc_weighted_density_dev", V, ldv, K, P, w, Product(den));
 }
 
 extern "C" int abc_weighted_density(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_density* den) {
     CHECK_CTX(ctx);
-    const char* fn = "abc_weighted_density";
-    ABC_TRY(weighted_values_check(ctx, fn, V, K, K, P));
-    ABC_TRY(density_check(ctx, fn, den));
-    ABC_TRY(abc_ws_reserve(ctx, abc_density_need(1, K, P, den->G) + (K * P + K + P * (den->G + 6)) * 8 + 48 * 256));
-    Stage s{ctx};
-    const double* V_d = s.up(V, K * P);
-    const double* w_d = w ? s.up(w, K) : nullptr;
-    const abc_density dd = density_stage(s, den, P);
-    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
-    SmValues sv;
-    memset(&sv, 0, sizeof(sv));
-    sv.method = 2;
-    sv.V = V_d;
-    sv.ldv = K;
-    sv.w = w_d;
-    ABC_TRY(launch_density(ctx, sv, 1, K, P, &dd, fn));
-    density_down(s, den, dd, P);
-    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
-}
-
-extern "C" int abc_rank_targets_joint_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
-                                          size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
-                                          const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
-                                          const abc_adjust_out* adj, const abc_joint* jt) {
-    CHECK_CTX(ctx);
-    const TgRequest r{TG_JOINT, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
-                      adj, nullptr, nullptr, jt};
-    return tg_dev(ctx, "abc_rank_targets_joint_dev", r);
-}
-
-extern "C" int abc_particle_ranking_pls_targets_joint(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
-                                                      const double* targets, size_t B, double train_frac, int max_comp, int rule,
-                                                      const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
-                                                      double* dist, const abc_adjust_out* adj, const abc_joint* jt, int32_t* ncomp) {
-    CHECK_CTX(ctx);
-    const TgRequest h{TG_JOINT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
-                      adj, nullptr, nullptr, jt};
-    return tg_host(ctx, "abc_particle_ranking_pls_targets_joint", h, train_frac, max_comp, rule, ncomp);
+    return weighted_host(ctx, "abc_weighted_density", V, K, P, w, Product(den));
 }
 
 extern "C" int abc_weighted_joint_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
                                       const abc_joint* jt) {
     CHECK_CTX(ctx);
-    const char* fn = "abc_weighted_joint_dev";
-    ABC_TRY(weighted_values_check(ctx, fn, V, ldv, K, P));
-    ABC_TRY(joint_check(ctx, fn, jt, P));
-    ABC_TRY(abc_ws_reserve(ctx, abc_joint_need(1, K, P, jt->G, abc_joint_pairs(jt, P)) + 16 * 256));
-    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
-    SmValues sv;
-    memset(&sv, 0, sizeof(sv));
-    sv.method = 2;
-    sv.V = V;
-    sv.ldv = ldv;
-    sv.w = w;
-    return launch_joint(ctx, sv, 1, K, P, jt, fn);
+    return weighted_dev(ctx, "abc_weighted_joint_dev", V, ldv, K, P, w, Product(jt));
 }
 
 extern "C" int abc_weighted_joint(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_joint* jt) {
     CHECK_CTX(ctx);
-    const char* fn = "abc_weighted_joint";
-    ABC_TRY(weighted_values_check(ctx, fn, V, K, K, P));
-    ABC_TRY(joint_check(ctx, fn, jt, P));
-    ABC_TRY(abc_ws_reserve(ctx, abc_joint_need(1, K, P, jt->G, abc_joint_pairs(jt, P)) + (K * P + K) * 8 + joint_stage_bytes(jt, 1, P) +
-                                    16 * 256));
-    Stage s{ctx};
-    const double* V_d = s.up(V, K * P);
-    const double* w_d = w ? s.up(w, K) : nullptr;
-    const abc_joint jd = joint_stage(s, jt, 1, P);
-    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
-    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
-    SmValues sv;
-    memset(&sv, 0, sizeof(sv));
-    sv.method = 2;
-    sv.V = V_d;
-    sv.ldv = K;
-    sv.w = w_d;
-    ABC_TRY(launch_joint(ctx, sv, 1, K, P, &jd, fn));
-    joint_down(s, jt, jd, 1, P);
-    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
+    return weighted_host(ctx, "abc_weighted_joint", V, K, P, w, Product(jt));
 }
 
 extern "C" int abc_targets_fallbacks(abc_ctx* ctx, uint64_t* count, int reset) {

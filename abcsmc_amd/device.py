@@ -154,11 +154,49 @@ def rank_targets_adjust(X, model, A, targets, K, Y, exclude=None, kernel=_lib.KE
     return r
 
 
-def _summary(probs, truth, quant, cdf):
+def _rank_targets_product(product, make, X, model, A, targets, K, Y, method, kernel, exclude, dist, adjust, ctx):
+    """The call of rank_targets_{summary,density,joint}.  make(lead, P, dev) -> (the product's struct, its outputs as a dict, what
+    must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and the adjust members added."""
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
+    d, r, _keep = make((B,), P, dev)
+    r.update(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
+             dist=torch.empty((B, K), dtype=torch.float64, device=dev) if dist else None)
+    members, adj = _adjust_out(adjust, B, K, P, A, dev)
+    r.update(members)
+    entry = getattr(lib(), "abc_rank_targets_%s_dev" % product)
+    ctx.check(entry(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A, targets.data_ptr(), ldt, B,
+                    _ptr(exclude), K, int(method), int(kernel), r["idx"].data_ptr(), _ptr(r["dist"]), C.byref(adj), C.byref(d)))
+    return r
+
+
+def _weighted_product(product, make, V, w, ctx):
+    """The call of weighted_{summary,density,joint}: the holder's layout assert, the context, the weights on the device, and make
+    as _rank_targets_product's with lead = (); the context takes the current stream after make's work, just before the call."""
+    assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
+    P, K = V.shape
+    dev = V.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    if w is not None:
+        w = w.to(device=dev, dtype=torch.float64).contiguous()
+        assert w.numel() == K
+    d, r, _keep = make((), P, dev)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    entry = getattr(lib(), "abc_weighted_%s_dev" % product)
+    ctx.check(entry(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(d)))
+    return r
+
+
+def _summary(probs, truth, lead, P, dev):
+    """Device tensors for the summaries of prod(lead) targets with P parameters and the abc_summary pointing at them (truth:
+    lead + (P,) values, P values in any shape when lead is empty, or None)"""
+    f64 = torch.float64
     pr = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
-    s = _lib.Summary(pr.ctypes.data, pr.size, truth.data_ptr() if truth is not None else None,
-                     quant.data_ptr() if quant is not None else None, cdf.data_ptr() if cdf is not None else None)
-    return s, pr
+    if truth is not None:
+        truth = truth.to(device=dev, dtype=f64).contiguous()
+        assert truth.shape == lead + (P,) if lead else truth.numel() == P
+    r = dict(quant=torch.empty(lead + (len(np.atleast_1d(probs)), P), dtype=f64, device=dev),
+             cdf=torch.empty(lead + (P,), dtype=f64, device=dev) if truth is not None else None)
+    return _lib.Summary(pr.ctypes.data, pr.size, _ptr(truth), _ptr(r["quant"]), _ptr(r["cdf"])), r, (pr, truth)
 
 
 def rank_targets_summary(X, model, A, targets, K, Y, probs=(0.025, 0.5, 0.975), truth=None, method=_lib.POSTERIOR_REJECTION,
@@ -167,53 +205,23 @@ def rank_targets_summary(X, model, A, targets, K, Y, probs=(0.025, 0.5, 0.975), 
     (abc_rank_targets_summary_dev; method 0 rejection, 1 loclinear).  truth: (B, P) row-major device tensor or None.  adjust:
     names of abc_adjust_out members to return as well (method 1: "theta", "weight", "coef", "rank", "status").
     Returns dict(idx (B, K) int64, dist (B, K) or None, quant (B, nq, P), cdf (B, P) or None, and the adjust members)."""
-    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
-    f64 = torch.float64
-    nq = len(np.atleast_1d(probs))
-    if truth is not None:
-        truth = truth.to(device=dev, dtype=f64).contiguous()
-        assert truth.shape == (B, P)
-    r = dict(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
-             dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None,
-             quant=torch.empty((B, nq, P), dtype=f64, device=dev),
-             cdf=torch.empty((B, P), dtype=f64, device=dev) if truth is not None else None)
-    members, adj = _adjust_out(adjust, B, K, P, A, dev)
-    r.update(members)
-    s, _pr = _summary(probs, truth, r["quant"], r["cdf"])
-    ctx.check(lib().abc_rank_targets_summary_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
-                                                 targets.data_ptr(), ldt, B, _ptr(exclude), K, int(method), int(kernel),
-                                                 r["idx"].data_ptr(), _ptr(r["dist"]), C.byref(adj), C.byref(s)))
-    return r
+    return _rank_targets_product("summary", lambda lead, P, dev: _summary(probs, truth, lead, P, dev), X, model, A, targets, K, Y,
+                                 method, kernel, exclude, dist, adjust, ctx)
 
 
 def weighted_summary(V, w=None, probs=(0.025, 0.5, 0.975), truth=None, ctx=None):
     """Weighted quantiles and CDF of P columns of K values (abc_weighted_summary_dev).  V: (P, K) holder of a K x P
     column-major matrix (row j = column j's values, unit stride); w: K weights or None (equal); truth: P values or None.
     Returns dict(quant (nq, P), cdf (P,) or None) as device tensors."""
-    assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
-    P, K = V.shape
-    dev = V.device
-    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
-    f64 = torch.float64
-    nq = len(np.atleast_1d(probs))
-    if w is not None:
-        w = w.to(device=dev, dtype=f64).contiguous()
-        assert w.numel() == K
-    if truth is not None:
-        truth = truth.to(device=dev, dtype=f64).contiguous()
-        assert truth.numel() == P
-    r = dict(quant=torch.empty((nq, P), dtype=f64, device=dev),
-             cdf=torch.empty(P, dtype=f64, device=dev) if truth is not None else None)
-    s, _pr = _summary(probs, truth, r["quant"], r["cdf"])
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ctx.check(lib().abc_weighted_summary_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(s)))
-    return r
+    return _weighted_product("summary", lambda lead, P, dev: _summary(probs, truth, lead, P, dev), V, w, ctx)
 
 
-def _density(G, cut, bw_scale, bw, lead, dev, dens, mode):
-    """Device tensors for ns = prod(lead) segments and the abc_density pointing at them (bw: given bandwidths or None)"""
+def _density(G, cut, bw_scale, bw, lead, P, dev, dens, mode):
+    """Device tensors for the densities of prod(lead) targets with P parameters and the abc_density pointing at them (bw: given
+    bandwidths or None)"""
     f64 = torch.float64
     G = int(G)
+    lead = lead + (P,)
     if bw is not None:
         bw = torch.as_tensor(bw, dtype=f64).to(dev).expand(lead).contiguous()
     r = dict(dens=torch.empty(lead + (G,), dtype=f64, device=dev) if dens else None,
@@ -232,33 +240,15 @@ def rank_targets_density(X, model, A, targets, K, Y, G=512, cut=3.0, bw=None, bw
     bw_scale).  adjust: names of abc_adjust_out members to return as well (method 1).  Returns dict(idx (B, K) int64, dist (B, K)
     or None, dens (B, P, G) or None, grid (B, P, 2): lo_x and step (x_g = fma(g, step, lo_x)), bw (B, P): the bandwidths used,
     mode and mode_dens (B, P) or None, and the adjust members)."""
-    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
-    d, r, _bw = _density(G, cut, bw_scale, bw, (B, P), dev, dens, mode)
-    r.update(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
-             dist=torch.empty((B, K), dtype=torch.float64, device=dev) if dist else None)
-    members, adj = _adjust_out(adjust, B, K, P, A, dev)
-    r.update(members)
-    ctx.check(lib().abc_rank_targets_density_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
-                                                 targets.data_ptr(), ldt, B, _ptr(exclude), K, int(method), int(kernel),
-                                                 r["idx"].data_ptr(), _ptr(r["dist"]), C.byref(adj), C.byref(d)))
-    return r
+    return _rank_targets_product("density", lambda lead, P, dev: _density(G, cut, bw_scale, bw, lead, P, dev, dens, mode), X, model, A,
+                                 targets, K, Y, method, kernel, exclude, dist, adjust, ctx)
 
 
 def weighted_density(V, w=None, G=512, cut=3.0, bw=None, bw_scale=1.0, dens=True, mode=True, ctx=None):
     """The weighted kernel density and mode of P columns of K values (abc_weighted_density_dev).  V: (P, K) holder as
     weighted_summary's; w: K weights or None (equal); bw: P given bandwidths or None.  Returns dict(dens (P, G) or None,
     grid (P, 2), bw (P,), mode and mode_dens (P,) or None) as device tensors."""
-    assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
-    P, K = V.shape
-    dev = V.device
-    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
-    if w is not None:
-        w = w.to(device=dev, dtype=torch.float64).contiguous()
-        assert w.numel() == K
-    d, r, _bw = _density(G, cut, bw_scale, bw, (P,), dev, dens, mode)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ctx.check(lib().abc_weighted_density_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(d)))
-    return r
+    return _weighted_product("density", lambda lead, P, dev: _density(G, cut, bw_scale, bw, lead, P, dev, dens, mode), V, w, ctx)
 
 
 def _joint(G, cut, bw_scale, bw, pairs, lead, P, dev, dens, mode):
@@ -288,16 +278,8 @@ def rank_targets_joint(X, model, A, targets, K, Y, G=64, cut=3.0, bw=None, bw_sc
     dict(idx (B, K) int64, dist (B, K) or None, mean (B, P), cov and corr (B, P, P), dens (B, npairs, G, G) or None ([g, g']: g on
     parameter i's grid), grid (B, P, 2): lo_x and step, bw (B, P), mode (B, npairs, 2) and mode_dens (B, npairs) or None, pairs: the
     (npairs, 2) int32 host array, and the adjust members)."""
-    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
-    d, r, _keep = _joint(G, cut, bw_scale, bw, pairs, (B,), P, dev, dens, mode)
-    r.update(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
-             dist=torch.empty((B, K), dtype=torch.float64, device=dev) if dist else None)
-    members, adj = _adjust_out(adjust, B, K, P, A, dev)
-    r.update(members)
-    ctx.check(lib().abc_rank_targets_joint_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
-                                               targets.data_ptr(), ldt, B, _ptr(exclude), K, int(method), int(kernel),
-                                               r["idx"].data_ptr(), _ptr(r["dist"]), C.byref(adj), C.byref(d)))
-    return r
+    return _rank_targets_product("joint", lambda lead, P, dev: _joint(G, cut, bw_scale, bw, pairs, lead, P, dev, dens, mode), X, model,
+                                 A, targets, K, Y, method, kernel, exclude, dist, adjust, ctx)
 
 
 def weighted_joint(V, w=None, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None, dens=True, mode=True, ctx=None):
@@ -305,14 +287,4 @@ def weighted_joint(V, w=None, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None, 
     or None (equal); bw: P given bandwidths or None; pairs as rank_targets_joint.  Returns dict(mean (P,), cov and corr (P, P),
     dens (npairs, G, G) or None, grid (P, 2), bw (P,), mode (npairs, 2) and mode_dens (npairs,) or None, pairs) as device tensors
     (pairs: int32 host array)."""
-    assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
-    P, K = V.shape
-    dev = V.device
-    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
-    if w is not None:
-        w = w.to(device=dev, dtype=torch.float64).contiguous()
-        assert w.numel() == K
-    d, r, _keep = _joint(G, cut, bw_scale, bw, pairs, (), P, dev, dens, mode)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    ctx.check(lib().abc_weighted_joint_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else K, K, P, _ptr(w), C.byref(d)))
-    return r
+    return _weighted_product("joint", lambda lead, P, dev: _joint(G, cut, bw_scale, bw, pairs, lead, P, dev, dens, mode), V, w, ctx)
