@@ -98,6 +98,24 @@ class Joint(C.Structure):
                 ("grid", C.c_void_p), ("bw_out", C.c_void_p), ("mode", C.c_void_p), ("mode_dens", C.c_void_p)]
 
 
+class Draws(C.Structure):
+    """abc_draws: S, smooth, bw_scale, bw (optional input), seed, stream (optional, HOST uint64, one id per target), then the
+    optional outputs draws / src / bw_out / ess (memory as the entry point's other arrays)"""
+    _fields_ = [("S", C.c_size_t), ("smooth", C.c_int), ("bw_scale", C.c_double), ("bw", C.c_void_p), ("seed", C.c_uint64),
+                ("stream", C.c_void_p), ("draws", C.c_void_p), ("src", C.c_void_p), ("bw_out", C.c_void_p), ("ess", C.c_void_p)]
+
+
+def _draws_stream(stream, n):
+    """The stream ids of an abc_draws as a C-contiguous uint64 host array of n entries, or None (target b takes id b)"""
+    import numpy as np
+    if stream is None:
+        return None
+    ids = np.ascontiguousarray(np.asarray(stream, dtype=np.uint64).reshape(-1))
+    if ids.size != n:
+        raise ValueError("stream needs one id per target")
+    return ids
+
+
 def _joint_pairs(pairs, P):
     """The pair list of an abc_joint as C-contiguous int32 (npairs, 2) host arrays: (all, given).  given is what the descriptor
     points at: the caller's rows (i, j), or None when pairs is None; all is then every i < j in the library's default order
@@ -204,7 +222,7 @@ SIGNATURES = {
     "abc_generation_multi": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
 }
 
-# The posterior products (abc_summary, abc_density, abc_joint) share their four argument lists, each ending in the product's
+# The posterior products (abc_summary, abc_density, abc_joint, abc_draws) share their four argument lists, each ending in the product's
 # descriptor: a new product adds its name here.
 _PRODUCT_ARGS = {
     "abc_rank_targets_%s_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp],
@@ -213,7 +231,7 @@ _PRODUCT_ARGS = {
     "abc_weighted_%s_dev": [_vp, _vp, _sz, _sz, _sz, _vp, _vp],
     "abc_weighted_%s": [_vp, _vp, _sz, _sz, _vp, _vp],
 }
-PRODUCTS = ("summary", "density", "joint")
+PRODUCTS = ("summary", "density", "joint", "draws")
 SIGNATURES.update((entry % product, (_i, args)) for product in PRODUCTS for entry, args in _PRODUCT_ARGS.items())
 
 _LIB = None

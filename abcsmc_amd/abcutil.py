@@ -145,7 +145,7 @@ _METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_L
 
 
 def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx):
-    """The call of particle_ranking_PLS_targets_{summary,density,joint}.  make(lead, P) -> (the product's struct, its outputs as a
+    """The call of particle_ranking_PLS_targets_{summary,density,joint,draws}.  make(lead, P) -> (the product's struct, its outputs as a
     dict, what must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and ncomp added."""
     ctx = _ctx(ctx)
     method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
@@ -162,7 +162,7 @@ def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, 
 
 
 def _weighted_product(product, make, values, weights, ctx):
-    """The call of weighted_{summary,density,joint}: values as (K, P) column-major, weights as K contiguous values or None, and
+    """The call of weighted_{summary,density,joint,draws}: values as (K, P) column-major, weights as K contiguous values or None, and
     make as _targets_product's with lead = ().  Returns the outputs."""
     ctx = _ctx(ctx)
     V = _f(values)
@@ -293,6 +293,43 @@ def weighted_joint(values, weights=None, G=64, cut=3.0, bw=None, bw_scale=1.0, p
     o = _weighted_product("joint", lambda lead, P: _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens), values, weights, ctx)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
+
+
+def _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P):
+    """Host arrays for the draws of prod(lead) targets with P parameters and the abc_draws pointing at them"""
+    S = int(S)
+    b = None
+    if smooth and bw is not None:
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(bw, dtype=np.float64), lead + (P,)))
+    ids = _lib._draws_stream(stream, int(np.prod(lead, dtype=np.int64)))
+    o = dict(draws=np.empty(lead + (S, P)), src=np.empty(lead + (S,), dtype=np.uint64), ess=np.empty(lead), bw=np.empty(lead + (P,)))
+    d = _lib.Draws(S, int(bool(smooth)), float(bw_scale), _p(b), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(ids), _p(o["draws"]), _p(o["src"]),
+                   _p(o["bw"]), _p(o["ess"]))
+    return d, o, (b, ids)
+
+
+def particle_ranking_PLS_targets_draws(X_orig, Y_orig, targets, training_fraction, K, S, smooth=False, seed=0, method="rejection",
+                                       kernel="epanechnikov", bw=None, bw_scale=1.0, stream=None, exclude=None, max_comp=0,
+                                       rule=_lib.RULE_DEFAULT, ctx=None):
+    """particle_ranking_PLS_targets followed by S posterior draws of every target, made on the device
+    (abc_particle_ranking_pls_targets_draws; the definition is in the header): rows of the target's K retained rows resampled with
+    their weights (method and kernel as particle_ranking_PLS_targets_summary), as they are (smooth=False, the weighted bootstrap)
+    or with h_j z_j added to parameter j (smooth=True, the smoothed bootstrap: a sample of the kernel density estimate of
+    particle_ranking_PLS_targets_density with the same bw and bw_scale).  seed keys the Philox stream of the draws (the context's
+    generator is not used); stream: one id per target (None: target b takes b), so that a target split off into another call keeps
+    its draws.  Nothing is clipped to prior bounds.  Returns dict(draws (B, S, P), src (B, S): the position in 0..K-1 of the row
+    each draw came from (idx[b, src[b, s]] is its row of the set), ess (B,): the effective sample size W^2 / sum w^2, bw (B, P):
+    the bandwidths used (NaN with smooth=False), idx (B, K), dist (B, K), ncomp)."""
+    return _targets_product("draws", lambda lead, P: _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P), X_orig, Y_orig,
+                            targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx)
+
+
+def weighted_draws(values, weights=None, S=1000, smooth=False, seed=0, bw=None, bw_scale=1.0, stream=None, ctx=None):
+    """S draws of the rows of values (K, P) with the given weights on the device (abc_weighted_draws; the definition is in the
+    header); equal weights when weights is None; smooth, seed, bw and bw_scale as particle_ranking_PLS_targets_draws; stream: the
+    one stream id (None: 0).  Returns dict(draws (S, P), src (S,), ess, bw (P,))."""
+    return _weighted_product("draws", lambda lead, P: _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P), values, weights,
+                             ctx)
 
 
 def hpd_levels(dens, step_x, step_y, probs=(0.5, 0.9, 0.95)):

@@ -318,6 +318,11 @@ int launch_density_segs(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t
 size_t abc_joint_pairs(const abc_joint* jt, size_t P);
 size_t abc_joint_need(size_t B, size_t K, size_t P, size_t G, size_t npairs);
 int launch_joint(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_joint* jt, const char* fn);
+// posterior draws of the same segments (draws.hip): the weighted bootstrap, smoothed by the marginal densities' bandwidths on
+// request (launch_density_segs's records).  dr: stream in host memory, every other array in device memory; a given bandwidth is
+// checked as launch_density's
+size_t abc_draws_need(size_t B, size_t K, size_t P, int smooth);
+int launch_draws(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_draws* dr, const char* fn);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

@@ -1190,8 +1190,9 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
 
 // ---- batched ranking of many observed targets against one fitted set (targets.hip), optionally followed by the local-linear
 // adjustment (adjust.hip) or by a posterior product of every target's retained rows: the weighted quantiles and CDF (summary.hip),
-// the densities and modes (density.hip) or the joint moments and pair densities (joint.hip).  One pipeline (tg_*) behind the ten
-// entry points of the family and one pair of paths (weighted_dev, weighted_host) behind the six abc_weighted_* entries, which
+// the densities and modes (density.hip), the joint moments and pair densities (joint.hip) or the posterior draws (draws.hip).  One
+// pipeline (tg_*) behind the twelve entry points of the family and one pair of paths (weighted_dev, weighted_host) behind the eight
+// abc_weighted_* entries, which
 // compute the same products from given values; what differs between the products is in Product ----
 static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
     if (!sum) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (sum is required)", fn);
@@ -1233,6 +1234,17 @@ static int joint_check(abc_ctx* ctx, const char* fn, const abc_joint* jt, size_t
     }
     if (!jt->mean && !jt->cov && !jt->corr && !jt->dens && !jt->grid && !jt->bw_out && !jt->mode && !jt->mode_dens)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of jt is NULL", fn);
+    return ABC_OK;
+}
+
+static int draws_check(abc_ctx* ctx, const char* fn, const abc_draws* dr) {
+    if (!dr) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (dr is required)", fn);
+    if (dr->S == 0 || dr->S > ((size_t)1 << 24)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: S = %zu draws per target (1 to 2^24)", fn, dr->S);
+    if (dr->smooth != 0 && dr->smooth != 1)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: smooth %d (0 = weighted, 1 = smoothed bootstrap)", fn, dr->smooth);
+    if (dr->smooth && (!(dr->bw_scale > 0.0) || !std::isfinite(dr->bw_scale)))
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: bw_scale = %g (finite, > 0)", fn, dr->bw_scale);
+    if (!dr->draws && !dr->src && !dr->bw_out && !dr->ess) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of dr is NULL", fn);
     return ABC_OK;
 }
 
@@ -1299,22 +1311,42 @@ static void joint_down(Stage& s, const abc_joint* h, const abc_joint& d, size_t 
     s.down(h->mode_dens, d.mode_dens, B * np);
 }
 
+// an abc_draws's arrays for B targets of P parameters, host (h) <-> arena: stream stays where it is, NULL members stay NULL
+static abc_draws draws_stage(Stage& s, const abc_draws* h, size_t B, size_t P) {
+    abc_draws d = *h;
+    d.bw = (h->smooth && h->bw) ? s.up(h->bw, B * P) : nullptr;
+    d.draws = h->draws ? s.dev<double>(B * h->S * P) : nullptr;
+    d.src = h->src ? s.dev<uint64_t>(B * h->S) : nullptr;
+    d.bw_out = h->bw_out ? s.dev<double>(B * P) : nullptr;
+    d.ess = h->ess ? s.dev<double>(B) : nullptr;
+    return d;
+}
+static void draws_down(Stage& s, const abc_draws* h, const abc_draws& d, size_t B, size_t P) {
+    s.down(h->draws, d.draws, B * h->S * P);
+    s.down(h->src, d.src, B * h->S);
+    s.down(h->bw_out, d.bw_out, B * P);
+    s.down(h->ess, d.ess, B);
+}
+
 namespace {
-// A posterior product: what is computed from the segments' values and weights, described by the caller's abc_summary, abc_density
-// or abc_joint.  Every member below has one row per kind, and nothing else in this file tells the kinds apart: a new product adds
+// A posterior product: what is computed from the segments' values and weights, described by the caller's abc_summary, abc_density,
+// abc_joint or abc_draws.  Every member below has one row per kind, and nothing else in this file tells the kinds apart: a new
+// product adds
 // its constructor and its six rows here.
 struct Product {
-    enum Kind { NONE, SUMMARY, DENSITY, JOINT } kind = NONE;
+    enum Kind { NONE, SUMMARY, DENSITY, JOINT, DRAWS } kind = NONE;
     union {
         const abc_summary* sum = nullptr;
         const abc_density* den;
         const abc_joint* jnt;
+        const abc_draws* drw;
     };
-    union { abc_summary sum; abc_density den; abc_joint jnt; } staged;      // stage()'s copy of the descriptor
+    union { abc_summary sum; abc_density den; abc_joint jnt; abc_draws drw; } staged;      // stage()'s copy of the descriptor
     Product() {}
     explicit Product(const abc_summary* s) : kind(SUMMARY), sum(s) {}
     explicit Product(const abc_density* d) : kind(DENSITY), den(d) {}
     explicit Product(const abc_joint* j) : kind(JOINT), jnt(j) {}
+    explicit Product(const abc_draws* d) : kind(DRAWS), drw(d) {}
 
     // the descriptor's own argument checks (a NULL descriptor among them)
     int check(abc_ctx* ctx, const char* fn, size_t P) const {
@@ -1322,6 +1354,7 @@ struct Product {
         case SUMMARY: return summary_check(ctx, fn, sum);
         case DENSITY: return density_check(ctx, fn, den);
         case JOINT: return joint_check(ctx, fn, jnt, P);
+        case DRAWS: return draws_check(ctx, fn, drw);
         default: return ABC_OK;
         }
     }
@@ -1331,6 +1364,7 @@ struct Product {
         case SUMMARY: return abc_summary_need(B, K, P);
         case DENSITY: return abc_density_need(B, K, P, den->G);
         case JOINT: return abc_joint_need(B, K, P, jnt->G, abc_joint_pairs(jnt, P));
+        case DRAWS: return abc_draws_need(B, K, P, drw->smooth);
         default: return 0;
         }
     }
@@ -1340,6 +1374,7 @@ struct Product {
         case SUMMARY: return B * P * (sum->nq + 2) * 8 + 16 * 256;         // truth, quant, cdf
         case DENSITY: return B * P * (den->G + 6) * 8 + 32 * 256;          // bw, dens, grid, bw_out, mode, mode_dens
         case JOINT: return joint_stage_bytes(jnt, B, P);
+        case DRAWS: return B * (drw->S * (P + 1) + 2 * P + 1) * 8 + 20 * 256;  // draws, src, bw, bw_out, ess
         default: return 0;
         }
     }
@@ -1350,6 +1385,7 @@ struct Product {
         case SUMMARY: staged.sum = summary_stage(s, sum, B, P); return Product(&staged.sum);
         case DENSITY: staged.den = density_stage(s, den, B * P); return Product(&staged.den);
         case JOINT: staged.jnt = joint_stage(s, jnt, B, P); return Product(&staged.jnt);
+        case DRAWS: staged.drw = draws_stage(s, drw, B, P); return Product(&staged.drw);
         default: return Product();
         }
     }
@@ -1359,6 +1395,7 @@ struct Product {
         case SUMMARY: summary_down(s, sum, staged.sum, B, P); break;
         case DENSITY: density_down(s, den, staged.den, B * P); break;
         case JOINT: joint_down(s, jnt, staged.jnt, B, P); break;
+        case DRAWS: draws_down(s, drw, staged.drw, B, P); break;
         default: break;
         }
     }
@@ -1368,6 +1405,7 @@ struct Product {
         case SUMMARY: return launch_summary(ctx, sv, B, K, P, sum);
         case DENSITY: return launch_density(ctx, sv, B, K, P, den, fn);
         case JOINT: return launch_joint(ctx, sv, B, K, P, jnt, fn);
+        case DRAWS: return launch_draws(ctx, sv, B, K, P, drw, fn);
         default: return ABC_OK;
         }
     }
@@ -1659,6 +1697,26 @@ extern "C" int abc_particle_ranking_pls_targets_joint(abc_ctx* ctx, const double
     return tg_host(ctx, "abc_particle_ranking_pls_targets_joint", h, train_frac, max_comp, rule, ncomp);
 }
 
+extern "C" int abc_rank_targets_draws_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                          size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                          const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                          const abc_adjust_out* adj, const abc_draws* dr) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_PRODUCT, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(dr)};
+    return tg_dev(ctx, "abc_rank_targets_draws_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_draws(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                      const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                      const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                                      double* dist, const abc_adjust_out* adj, const abc_draws* dr, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_PRODUCT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(dr)};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_draws", h, train_frac, max_comp, rule, ncomp);
+}
+
 // ---- the same products of P given columns of K values (V[e + ldv j], weights w or NULL): one segment group ----
 static int weighted_values_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P) {
     if (!V) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (V is required)", fn);
@@ -1738,6 +1796,17 @@ extern "C" int abc_weighted_joint_dev(abc_ctx* ctx, const double* V, size_t ldv,
 extern "C" int abc_weighted_joint(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_joint* jt) {
     CHECK_CTX(ctx);
     return weighted_host(ctx, "abc_weighted_joint", V, K, P, w, Product(jt));
+}
+
+extern "C" int abc_weighted_draws_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
+                                      const abc_draws* dr) {
+    CHECK_CTX(ctx);
+    return weighted_dev(ctx, "abc_weighted_draws_dev", V, ldv, K, P, w, Product(dr));
+}
+
+extern "C" int abc_weighted_draws(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_draws* dr) {
+    CHECK_CTX(ctx);
+    return weighted_host(ctx, "abc_weighted_draws", V, K, P, w, Product(dr));
 }
 
 extern "C" int abc_targets_fallbacks(abc_ctx* ctx, uint64_t* count, int reset) {

@@ -582,6 +582,58 @@ inline TargetJoint weighted_joint(const Mat2D& values, const std::vector<double>
     check(abc_weighted_joint(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &jt));
     return buf.target(0);
 }
+// The same ranking followed by S posterior draws of every target, made on the device (abc_particle_ranking_pls_targets_draws): rows
+// of the target's K retained rows resampled with their weights, as they are (smooth = false, the weighted bootstrap) or with h_j z_j
+// added to parameter j (smooth = true, the smoothed bootstrap with the marginal densities' bandwidths).  seed keys the Philox stream
+// of the draws (no RNG object is advanced); target b takes stream id b.  Nothing is clipped to prior bounds.  Per target: draws
+// (S x P), src (S: the position in 0..K-1 of the row a draw came from), bw (P; NaN without smoothing) and ess = W^2 / sum w^2.
+struct TargetDraws {
+    Mat2D draws;
+    std::vector<size_t> src;
+    std::vector<double> bw;
+    double ess;
+};
+namespace detail {
+inline TargetDraws target_draws(const double* draws, const uint64_t* src, const double* bw, double ess, size_t S, size_t P) {
+    TargetDraws r;
+    r.draws = Mat2D(S, P);
+    for (size_t s = 0; s < S; s++)
+        for (size_t j = 0; j < P; j++) r.draws(s, j) = draws[s * P + j];
+    r.src.assign(src, src + S);
+    r.bw.assign(bw, bw + P);
+    r.ess = ess;
+    return r;
+}
+}  // namespace detail
+inline std::vector<TargetDraws> particle_ranking_PLS_targets_draws(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                   const float_type train_frac, size_t K, size_t S,
+                                                                   bool smooth = false, uint64_t seed = 0, int method = 0,
+                                                                   int kernel = 0, double bw_scale = 1.0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols();
+    std::vector<double> draws(B * S * P), bw(B * P), ess(B);
+    std::vector<uint64_t> src(B * S);
+    abc_draws dr = {S, smooth ? 1 : 0, bw_scale, nullptr, seed, nullptr, draws.data(), src.data(), bw.data(), ess.data()};
+    check(abc_particle_ranking_pls_targets_draws(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac,
+                                                 max_components_ref(), component_rule(), nullptr, K, method, kernel, nullptr, nullptr,
+                                                 nullptr, &dr, nullptr));
+    std::vector<TargetDraws> res(B);
+    for (size_t b = 0; b < B; b++)
+        res[b] = detail::target_draws(draws.data() + b * S * P, src.data() + b * S, bw.data() + b * P, ess[b], S, P);
+    return res;
+}
+// S draws of the rows of values (K x P; weights: K entries, or empty for equal weights) (abc_weighted_draws); stream id 0.
+inline TargetDraws weighted_draws(const Mat2D& values, const std::vector<double>& weights, size_t S, bool smooth = false,
+                                  uint64_t seed = 0, double bw_scale = 1.0) {
+    const size_t K = values.rows(), P = values.cols();
+    if (!weights.empty() && weights.size() != K) throw HipError(ABC_ERR_INVALID, "weights needs one entry per row");
+    std::vector<double> draws(S * P), bw(P);
+    std::vector<uint64_t> src(S);
+    double ess = 0.0;
+    abc_draws dr = {S, smooth ? 1 : 0, bw_scale, nullptr, seed, nullptr, draws.data(), src.data(), bw.data(), &ess};
+    check(abc_weighted_draws(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &dr));
+    return detail::target_draws(draws.data(), src.data(), bw.data(), ess, S, P);
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

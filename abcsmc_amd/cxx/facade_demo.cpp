@@ -67,6 +67,14 @@ int main() {
         (void)rng_get(&r2);
         const Row tm = gsl_ran_trunc_mv_normal(&r2, qp, mu, Lq);
         std::printf("trunc_mv_normal: %.17g %.17g %.17g state %lu\n", tm[0], tm[1], tm[2], rng_get(&r2));
+        // posterior draws of the set's first two rows as targets (smoothed bootstrap), and of the weighted posterior above
+        Mat2D tg(2, M);
+        for (size_t m = 0; m < M; m++) { tg(0, m) = X(0, m); tg(1, m) = X(1, m); }
+        const std::vector<TargetDraws> td = particle_ranking_PLS_targets_draws(X, Y, tg, 0.5, K, 100, true, 7, ABC_POSTERIOR_LOCLINEAR);
+        const TargetDraws wd = weighted_draws(post, w, 100, false, 7);
+        std::printf("draws: %zu targets, ess %.1f, bw[0] %.3g, first %.3f; weighted src[0] %zu ess %.1f\n", td.size(), td[0].ess,
+                    td[0].bw[0], td[0].draws(0, 0), wd.src[0], wd.ess);
+        if (!(wd.draws(0, 0) == post(wd.src[0], 0)) || !(td[1].ess > 1.0)) return 4;
     } catch (const HipError& e) {
         std::printf("HipError %d: %s\n", e.code, e.what());
         return 1;

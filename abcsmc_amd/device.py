@@ -155,7 +155,7 @@ def rank_targets_adjust(X, model, A, targets, K, Y, exclude=None, kernel=_lib.KE
 
 
 def _rank_targets_product(product, make, X, model, A, targets, K, Y, method, kernel, exclude, dist, adjust, ctx):
-    """The call of rank_targets_{summary,density,joint}.  make(lead, P, dev) -> (the product's struct, its outputs as a dict, what
+    """The call of rank_targets_{summary,density,joint,draws}.  make(lead, P, dev) -> (the product's struct, its outputs as a dict, what
     must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and the adjust members added."""
     N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
     d, r, _keep = make((B,), P, dev)
@@ -170,7 +170,7 @@ def _rank_targets_product(product, make, X, model, A, targets, K, Y, method, ker
 
 
 def _weighted_product(product, make, V, w, ctx):
-    """The call of weighted_{summary,density,joint}: the holder's layout assert, the context, the weights on the device, and make
+    """The call of weighted_{summary,density,joint,draws}: the holder's layout assert, the context, the weights on the device, and make
     as _rank_targets_product's with lead = (); the context takes the current stream after make's work, just before the call."""
     assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
     P, K = V.shape
@@ -288,3 +288,42 @@ def weighted_joint(V, w=None, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None, 
     dens (npairs, G, G) or None, grid (P, 2), bw (P,), mode (npairs, 2) and mode_dens (npairs,) or None, pairs) as device tensors
     (pairs: int32 host array)."""
     return _weighted_product("joint", lambda lead, P, dev: _joint(G, cut, bw_scale, bw, pairs, lead, P, dev, dens, mode), V, w, ctx)
+
+
+def _draws(S, smooth, seed, bw, bw_scale, stream, lead, P, dev, draws, src):
+    """Device tensors for the draws of prod(lead) targets with P parameters and the abc_draws pointing at them (bw: given
+    bandwidths or None; stream: one id per target, host, or None)"""
+    f64 = torch.float64
+    S = int(S)
+    if smooth and bw is not None:
+        bw = torch.as_tensor(bw, dtype=f64).to(dev).expand(lead + (P,)).contiguous()
+    else:
+        bw = None
+    ids = _lib._draws_stream(stream, int(np.prod(lead, dtype=np.int64)))
+    r = dict(draws=torch.empty(lead + (S, P), dtype=f64, device=dev) if draws else None,
+             src=torch.empty(lead + (S,), dtype=torch.int64, device=dev) if src else None,
+             bw=torch.empty(lead + (P,), dtype=f64, device=dev), ess=torch.empty(lead, dtype=f64, device=dev))
+    d = _lib.Draws(S, int(bool(smooth)), float(bw_scale), _ptr(bw), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                   ids.ctypes.data if ids is not None else None, _ptr(r["draws"]), _ptr(r["src"]), _ptr(r["bw"]), _ptr(r["ess"]))
+    return d, r, (bw, ids)
+
+
+def rank_targets_draws(X, model, A, targets, K, Y, S, smooth=False, seed=0, bw=None, bw_scale=1.0, stream=None,
+                       method=_lib.POSTERIOR_REJECTION, kernel=_lib.KERNEL_EPANECHNIKOV, exclude=None, dist=False, adjust=(), draws=True,
+                       src=True, ctx=None):
+    """rank_targets followed by S posterior draws of every target (abc_rank_targets_draws_dev; method 0 rejection, 1 loclinear): the
+    weighted bootstrap of the target's K retained rows, smoothed by the marginal densities' bandwidths with smooth=True (bw: given
+    bandwidths (B, P) or None: the bw.nrd0 rule times bw_scale).  seed keys the draws' Philox stream; stream: one id per target
+    (host values; None: target b takes b).  The adjusted rows are made in registers: nothing of size B K P is written unless
+    "theta" is named in adjust.  Returns dict(idx (B, K) int64, dist (B, K) or None, draws (B, S, P) or None, src (B, S) int64
+    or None, ess (B,), bw (B, P): NaN without smoothing, and the adjust members)."""
+    return _rank_targets_product("draws", lambda lead, P, dev: _draws(S, smooth, seed, bw, bw_scale, stream, lead, P, dev, draws, src),
+                                 X, model, A, targets, K, Y, method, kernel, exclude, dist, adjust, ctx)
+
+
+def weighted_draws(V, w=None, S=1000, smooth=False, seed=0, bw=None, bw_scale=1.0, stream=None, draws=True, src=True, ctx=None):
+    """S draws of the K rows of P columns with weights w (abc_weighted_draws_dev).  V: (P, K) holder as weighted_summary's; w: K
+    weights or None (equal); the other arguments as rank_targets_draws (stream: the one id, None: 0).  Returns dict(draws (S, P) or
+    None, src (S,) int64 or None, ess (0-d), bw (P,)) as device tensors."""
+    return _weighted_product("draws", lambda lead, P, dev: _draws(S, smooth, seed, bw, bw_scale, stream, lead, P, dev, draws, src),
+                             V, w, ctx)

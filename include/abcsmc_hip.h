@@ -594,6 +594,71 @@ int abc_weighted_joint_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, 
 /* HOST-pointer form: V is K x P column-major (ldv = K); w and jt's arrays in host memory. */
 int abc_weighted_joint(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_joint* jt);
 
+/* ---- posterior draws of the batched ranking: weighted and smoothed bootstrap -------------------------------------------------
+ * A posterior handed back as a sample: S rows per target, resampled from the target's K entries with the entries' weights (the
+ * weighted bootstrap) and, on request, jittered by the marginal densities' bandwidths (the smoothed bootstrap: a sample of the
+ * estimate that abc_*_density draws).  For a posterior predictive check, or to start a follow-up set per target.  For target b the
+ * entries are e = 0..K-1 in the ranking's row order; the values v_e[j] and weights w_e are those of the products above (method 0
+ * rejection: Y rows, w = 1; method 1 loclinear: theta*_e with the adjustment's weights; generic: V[e + ldv j] and w[e], 1 when w
+ * is NULL).
+ *   cumulative  c_e = w_0 + ... + w_e, an inclusive prefix sum in a fixed order that depends on K only (entries with w_e <= 0 add
+ *               0); W = c_{K-1} is that same sum.  The order is a tree, not left to right: |c_e - exact| <= 4 K 2^-53 W, the
+ *               bound of the summaries' sums.  c is non-decreasing, and c_e == c_{e-1} exactly when w_e == 0.  With equal weights
+ *               c_e = e + 1 exactly.
+ *   selection   of draw s of target b, t = stream[b] (b when stream is NULL): the Philox4x32-10 block of counter
+ *               (lo32(t), hi32(t), s, 0) under the key (k0, k1) = (lo32(seed), hi32(seed)) gives the words x0..x3;
+ *               m = (x0 << 21) | (x1 >> 11) (53 bits), u = m 2^-53, tau = u W (one rounding); src = the smallest e with
+ *               c_e > tau.  An entry with w_e = 0 is never chosen.  With equal weights src = floor(u K), exact on both sides.
+ *   values      smooth == 0: draws[b][s][j] = v_src[j], the bits of abc_adjust_out.theta / Y / V at that row.
+ *               smooth == 1: draws[b][s][j] = fma(h_j, z_j, v_src[j]).  h_j is bit for bit the bandwidth that abc_*_density returns
+ *               in bw_out for segment (b, j) with the same bw_scale and bw (bw.nrd0 on the weighted moments and quantiles; a given
+ *               bandwidth replaces the rule).  z_j is deviate j mod 4 of the four normal deviates made of the Philox block of counter
+ *               (lo32(t), hi32(t), s, 1 + j / 4): two Box-Muller pairs (x0, x1) and (x2, x3) evaluated in f32 (the radius from all
+ *               32 bits of the first word of a pair, the angle from the top 24 bits of the second), the deviates of the device
+ *               noise stream of abc_perturb_dev; they carry f32 rounding, about 1e-7 relative.
+ *   bad         a parameter j with a non-finite value among a target's entries has h_j = NaN, as in the densities: its smoothed
+ *               draws are NaN.  Plain draws copy the values as they are.  The other parameters are unaffected.
+ *   ess         W^2 / S2, S2 = sum of w^2, over the entries with w > 0 (K with equal weights).
+ * A draw depends on (seed, stream id, s) and its target's segment only.  So a target with the same stream id gets the same bits
+ * alone (B = 1) and in any batch, on a repeat run, through the device and host entry points, and whichever output members are asked
+ * for; a call with S' < S gives the first S' draws of the call with S; and two targets with different stream ids get independent
+ * selections and noise.  A caller that splits a batch over several calls passes each target's own number in stream.  The context's
+ * abc_rng is not used and not advanced.  No floating-point atomics are involved.
+ * Not done here: the draws are not clipped to prior bounds, the smoothed bootstrap is not shrunk towards the mean (its variance is
+ * the sample's plus h^2), and the kernel is a product of marginal ones (no correlated smoothing).
+ * Layout: draws [b][s][j], src [b][s], bw_out [b][j], ess [b]; the generic entries have one b.  The caller sizes draws: B S P doubles;
+ * the host entries stage it in the context's workspace as well.  Limits as the summaries': A <= 64, P <= 1024. */
+typedef struct {
+    size_t S;               /* draws per target, 1..2^24                                                                    */
+    int smooth;             /* 0: weighted bootstrap (rows as they are); 1: smoothed bootstrap, + h_j z_j                   */
+    double bw_scale;        /* smooth only: as abc_density (finite, > 0)                                                    */
+    const double* bw;       /* smooth only, optional: given bandwidths, one per segment, as abc_density                     */
+    uint64_t seed;          /* Philox key: k0 = lo32(seed), k1 = hi32(seed)                                                 */
+    const uint64_t* stream; /* optional, B entries (1 for the generic entry): the stream id of target b;                    */
+                            /* NULL: b.  HOST memory in every entry, as abc_joint.pairs                                     */
+    double* draws;          /* optional: [b][s][j], B x S x P                                                               */
+    uint64_t* src;          /* optional: [b][s], the position e in 0..K-1 (ranking order) the draw came from                */
+    double* bw_out;         /* optional: [b][j], h used (smooth only; NaN when smooth == 0)                                 */
+    double* ess;            /* optional: [b], W^2 / S2 over the entries with w > 0                                          */
+} abc_draws;                /* at least one output required; memory of bw and the outputs as the entry point's other arrays */
+/* Device pointers; the arguments of abc_rank_targets_density_dev with dr in place of den.  idx, dist and adj are optional and
+ * receive the bits of the plain calls.  Besides the ranking's, the adjustment's and the method / kernel checks, ABC_ERR_INVALID
+ * for NULL dr, S outside 1..2^24, smooth not 0 / 1, every output member NULL, and when smoothing bw_scale <= 0 or non-finite and
+ * a given bandwidth that is <= 0 or non-finite (checked on the device; the call then synchronises). */
+int abc_rank_targets_draws_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                               size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                               const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                               const abc_adjust_out* adj, const abc_draws* dr);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_density); every array of adj and dr in host memory. */
+int abc_particle_ranking_pls_targets_draws(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                           const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                           const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                           double* dist, const abc_adjust_out* adj, const abc_draws* dr, int32_t* ncomp);
+/* The same of P given columns of K values (as abc_weighted_density_dev, with its checks of V, ldv, K, P and w). */
+int abc_weighted_draws_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w, const abc_draws* dr);
+/* HOST-pointer form: V is K x P column-major (ldv = K); w and dr's arrays in host memory. */
+int abc_weighted_draws(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_draws* dr);
+
 /* ======================================================================================== */
 /* Multi-GPU: rows (particles) sharded over several GPUs of one node             */
 /* ======================================================================================== */
