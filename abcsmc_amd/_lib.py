@@ -72,6 +72,12 @@ class ShardedCfg(C.Structure):
                 ("max_comp", C.c_int32), ("rule", C.c_int32), ("multivariate", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Path(C.Structure):
+    """abc_path: Ks (host memory, T strictly ascending tolerances); every output pointer optional (None: not written)"""
+    _fields_ = [("Ks", C.c_void_p), ("T", C.c_size_t), ("post_mean", C.c_void_p), ("coef", C.c_void_p), ("rank", C.c_void_p),
+                ("status", C.c_void_p), ("h", C.c_void_p)]
+
+
 class AdjustOut(C.Structure):
     """abc_adjust_out: every pointer optional (None: not written)"""
     _fields_ = [("theta", C.c_void_p), ("weight", C.c_void_p), ("coef", C.c_void_p), ("rank", C.c_void_p),
@@ -179,6 +185,9 @@ SIGNATURES = {
                                          _vp]),
     "abc_particle_ranking_pls_targets_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _vp, _vp,
                                                      _vp, _vp]),
+    "abc_rank_targets_path_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _i, _vp, _vp, _vp]),
+    "abc_particle_ranking_pls_targets_path": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _i, _vp, _vp, _vp,
+                                                   _vp]),
     "abc_particle_ranking_simple": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_calculate_doubled_variance": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "abc_weight_predictive_prior_uniform": (_i, [_vp, _sz, _vp]),

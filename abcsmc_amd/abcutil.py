@@ -141,6 +141,36 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
                 ncomp=ncomp.value)
 
 
+def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction, Ks, kernel="epanechnikov", exclude=None,
+                                      max_comp=0, rule=_lib.RULE_DEFAULT, ctx=None):
+    """Tolerance path (abc_particle_ranking_pls_targets_path): particle_ranking_PLS_targets ONCE at K_max = Ks[-1], then the
+    rejection estimate and the local-linear fit of particle_ranking_PLS_targets_adjust at every tolerance of the strictly ascending
+    list Ks (at most 16): what cv4abc computes for tols = c(...), without ranking once per tolerance.  Tolerance t uses the first
+    Ks[t] retained rows only, with the bandwidth h = dist[:, Ks[t] - 1].  Returns dict(post_mean (B, T, P): the mean parameter row,
+    coef (B, T, A + 1, P), alpha (B, T, P) = coef[:, :, 0]: the adjusted posterior means (a view), rank (B, T), status (B, T), h (B, T),
+    Ks, idx (B, K_max), dist (B, K_max), ncomp)."""
+    ctx = _ctx(ctx)
+    kernel = _choice("kernel", kernel, _KERNELS)
+    ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))
+    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, ks[-1] if ks.size else 0, exclude)
+    nt = ks.size
+    A = max_comp if max_comp > 0 else min(M, P)
+    idx = np.empty((B, K), dtype=np.uint64)
+    dist = np.empty((B, K))
+    pm = np.empty((B, nt, P))
+    coef = np.empty((B, nt, A + 1, P))
+    rank = np.empty((B, nt), dtype=np.int32)
+    status = np.empty((B, nt), dtype=np.int32)
+    h = np.empty((B, nt))
+    path = _lib.Path(_p(ks), nt, _p(pm), _p(coef), _p(rank), _p(status), _p(h))
+    ncomp = C.c_int32(0)
+    ctx.check(lib().abc_particle_ranking_pls_targets_path(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
+                                                          int(max_comp), int(rule), _p(ex), kernel, _p(idx), _p(dist),
+                                                          C.byref(path), C.addressof(ncomp)))
+    return dict(post_mean=pm, coef=coef, alpha=coef[:, :, 0], rank=rank, status=status, h=h, Ks=ks.astype(np.int64), idx=idx,
+                dist=dist, ncomp=ncomp.value)
+
+
 _METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_LOCLINEAR}
 
 
@@ -400,6 +430,33 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
         out["truth_cdf"] = sm["cdf"]
         out["ci95"] = ((sm["quant"][:, 1, :] <= theta) & (theta <= sm["quant"][:, 2, :])).mean(axis=0)
     return out
+
+
+def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
+                            ctx=None, method="rejection", kernel="epanechnikov"):
+    """cross_validate_pls at every tolerance of the strictly ascending list Ks from ONE call of
+    particle_ranking_PLS_targets_path: cv4abc with tols = c(...).  The left-out rows are drawn from `seed` exactly as
+    cross_validate_pls draws them.  method: "rejection" (the mean of the Ks[t] nearest rows) or "loclinear" (alpha of the fit at
+    tolerance t).  Returns dict(rows, theta, Ks, post_mean (n_targets, T, P), pred_error (T, P) by cross_validate_pls's formula,
+    best (P,): the index of the tolerance with the smallest error of each parameter (0 where every error is NaN), idx, ncomp)."""
+    X, Y = _f(X_orig), _f(Y_orig)
+    N = X.shape[0]
+    n_targets = int(n_targets)
+    if not (1 <= n_targets <= N):
+        raise ValueError("n_targets must be in [1, N]")
+    if method not in ("rejection", "loclinear"):
+        raise ValueError("method must be 'rejection' or 'loclinear'")
+    rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
+    theta = np.ascontiguousarray(Y[rows])
+    r = particle_ranking_PLS_targets_path(X, Y, X[rows], training_fraction, Ks, kernel=kernel, exclude=rows, max_comp=max_comp,
+                                          rule=rule, ctx=ctx)
+    pm = np.ascontiguousarray(r["post_mean"] if method == "rejection" else r["alpha"])
+    var = theta.var(axis=0, ddof=1) if n_targets > 1 else np.zeros(theta.shape[1])
+    sse = ((pm - theta[:, None, :]) ** 2).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        err = np.where(var > 0, sse / (n_targets * np.where(var > 0, var, 1.0)), np.nan)
+    best = np.argmin(np.where(np.isnan(err), np.inf, err), axis=0)
+    return dict(rows=rows, theta=theta, Ks=r["Ks"], post_mean=pm, pred_error=err, best=best, idx=r["idx"], ncomp=r["ncomp"])
 
 
 def particle_ranking_simple(X_orig, Y_orig, target_values, K=None, details=False, ctx=None):

@@ -282,6 +282,12 @@ int launch_rank_targets_adjust(abc_ctx*, const double* X, size_t ldx, const doub
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
                                struct abc_adj_keep* keep = nullptr);
+// tolerance path (adjust.hip): the ranking at K = path->Ks[T - 1], then the rejection mean and the regression at every tolerance;
+// path: Ks in host memory, the outputs device pointers; dist may be NULL
+size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T);
+int launch_rank_targets_path(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
+                             const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
+                             bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path);
 // weighted posterior quantiles and CDF (summary.hip).  abc_summary_need: workspace of launch_summary for B segment groups of P
 // segments of K values.  SmValues: how the values and weights of segment (b, j) are made (method 0 / 1: the ranking's rows,
 // method 2: V and w); sum: probs in host memory, truth / quant / cdf in device memory.

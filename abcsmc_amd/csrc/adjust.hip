@@ -10,6 +10,11 @@
 //   k_adj_solve     one work-group per target: the chunks' blocks summed in chunk order, centred, the sweep in LDS (64 right-hand
 //                   sides at a time), coef / rank / status
 //   k_adj_apply     (only for theta / weight) the adjusted rows and the weights
+// The tolerance path (abc_rank_targets_path_dev) ranks once at K_max and runs the regression at every tolerance K_t of a list:
+//   k_adj_moments_path  k_adj_moments with one weight column and one set of accumulators per tolerance: the chunk's rows are staged
+//                       once and the tolerances' chains run interleaved over the same LDS reads; tolerance t's chain stops at row K_t
+//   k_adj_solve         grid (targets, tolerances): the blocks of the chunks below K_t
+//   k_path_mean         the rejection mean of the first K_t rows and the bandwidth
 // Chunk sizes depend on K only, tile sizes on (nc, P) only, and the gather paths copy the same bits: a target's outputs are the
 // same alone and in any batch.
 #include <math.h>
@@ -90,13 +95,184 @@ __device__ __forceinline__ void aj_chain(const double* __restrict__ tv, const do
     }
 }
 
-// grid (chunks, targets b0 + blockIdx.y); part[((blockIdx.y nch + chunk) U + r) D + c] = sum over the chunk's rows e (ascending) of
+// nr rows of a tile, shifted by the target's first row: tv[r Ds + 0] = 1, [1 + c] = value c of row ix[r] minus shift[1 + c], 0 in the
+// padding columns
+__device__ __forceinline__ void aj_stage_rows(const AjSrc& src, const uint64_t* __restrict__ ix, const double* __restrict__ shift,
+                                              double* __restrict__ tv, int nr, int nc, int P, int t) {
+    const int D = 1 + nc + P, Wv = nc + P, Ds = aj_stride(nc, P);
+    for (int q = t; q < nr * Wv; q += 256) {
+        const int r = q / Wv, c = q % Wv;
+        tv[r * Ds + 1 + c] = aj_val(src, (size_t)ix[r], c, nc) - shift[1 + c];
+    }
+    for (int r = t; r < nr; r += 256) {
+        tv[r * Ds] = 1.0;
+        for (int c = D; c < Ds; c++) tv[r * Ds + c] = 0.0;
+    }
+}
+
+// the tolerances of a path, ascending (kernel argument)
+constexpr int AJ_MAXT = 16;
+struct AjKs {
+    size_t K[AJ_MAXT];
+};
+
+// aj_chain for the tolerance lanes L0 .. TL - 1 at once, all of them over the same nr rows: every lane has its own weight column
+// (tw + l TRp) and its own four sums, and runs the chain of aj_chain (the same operations in the same order); the lanes share the
+// loads of u and v and their fmas are independent of one another
+template <int TL, int L0>
+__device__ __forceinline__ void aj_chain_lanes(const double* __restrict__ tv, const double* __restrict__ tw, int TRp, int Ds, int nr,
+                                               int c, int g, double (&acc)[TL][4]) {
+    constexpr int RU = 4;                                       // rows loaded ahead of their fmas, as aj_chain
+    int r = 0;
+    for (; r + RU <= nr; r += RU) {
+        double v[RU], u[RU][4], w[TL][RU];
+#pragma unroll
+        for (int q = 0; q < RU; q++) {
+            const double* row = tv + (r + q) * Ds;
+            v[q] = row[c];
+#pragma unroll
+            for (int k = 0; k < 4; k++) u[q][k] = row[g + k];
+#pragma unroll
+            for (int l = L0; l < TL; l++) w[l][q] = tw[l * TRp + r + q];
+        }
+#pragma unroll
+        for (int q = 0; q < RU; q++)
+#pragma unroll
+            for (int l = L0; l < TL; l++)
+#pragma unroll
+                for (int k = 0; k < 4; k++) acc[l][k] = fma(w[l][q] * u[q][k], v[q], acc[l][k]);
+    }
+    for (; r < nr; r++) {
+        const double* row = tv + r * Ds;
+        const double v = row[c];
+#pragma unroll
+        for (int l = L0; l < TL; l++) {
+            const double w = tw[l * TRp + r];
+#pragma unroll
+            for (int k = 0; k < 4; k++) acc[l][k] = fma(w * row[g + k], v, acc[l][k]);
+        }
+    }
+}
+// l0: the first lane whose chain covers all nr rows of the tile (the tolerances ascend, so every later lane does too)
+template <int TL, int L0 = 0>
+__device__ __forceinline__ void aj_chain_from(int l0, const double* __restrict__ tv, const double* __restrict__ tw, int TRp, int Ds,
+                                              int nr, int c, int g, double (&acc)[TL][4]) {
+    if constexpr (L0 < TL) {
+        if (l0 == L0) aj_chain_lanes<TL, L0>(tv, tw, TRp, Ds, nr, c, g, acc);
+        else aj_chain_from<TL, L0 + 1>(l0, tv, tw, TRp, Ds, nr, c, g, acc);
+    }
+}
+
+// k_adj_moments for the tolerances t0 .. t0 + TL - 1 of a path (t0 may be negative: the lanes below tolerance 0 are idle) over the
+// ranking at K_max = ld; blocks of at most 256 entry groups only.  Grid (chunks of K_max, targets b0 + blockIdx.y).  The chunk's rows are staged once, up to the largest
+// tolerance of the pass; lane l's chain runs over the rows e0 <= e < min(e1, K_l) with h = d_{K_l - 1} and its own fallback, and is
+// absent (nothing written) when e0 >= K_l.  part[(((blockIdx.y T + t) nchs + chunk) U + r) D + c].
+template <int TL>
+__global__ __launch_bounds__(256) void k_adj_moments_path(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
+                                                          size_t ld, AjKs ks, int T, int t0, int nc, int P, int kernel, size_t CH,
+                                                          int TR, size_t b0, size_t nchs, double* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int t = threadIdx.x;
+    const int U = 1 + nc, D = 1 + nc + P, Wv = nc + P, Ds = aj_stride(nc, P);
+    const int Dp = (D + 1) & ~1, TRp = (TR + 1) & ~1;
+    double* shift = sm;                  // [1 + c]: the first row's value c
+    double* tw = sm + Dp;                // TL x TRp weights
+    double* tv = tw + TL * TRp;          // TR x Ds
+    const size_t b = b0 + blockIdx.y, chunk = blockIdx.x;
+    const uint64_t* ix = idx + b * ld;
+    const double* dd = dist + b * ld;
+    const size_t e0 = chunk * CH;
+    size_t Kl[TL], Kp = 0;
+    double h[TL];
+    bool rect[TL];
+#pragma unroll
+    for (int l = 0; l < TL; l++) {
+        Kl[l] = (t0 + l >= 0 && t0 + l < T) ? ks.K[t0 + l] : 0;
+        if (Kl[l] <= e0) Kl[l] = 0;                             // no part in this chunk (such lanes come first: ascending)
+        if (Kl[l] > Kp) Kp = Kl[l];
+        h[l] = Kl[l] ? dd[Kl[l] - 1] : 0.0;
+        rect[l] = kernel == 1 || (Kl[l] && aj_fallback(dd, Kl[l]));
+    }
+    if (Kp == 0) return;                                        // (uniform)
+    const size_t e1 = (e0 + CH < Kp) ? e0 + CH : Kp;
+    const size_t i0 = (size_t)ix[0];
+    for (int c = t; c < Wv; c += 256) shift[1 + c] = aj_val(src, i0, c, nc);
+    const int J = D * ((U + 3) / 4);                            // <= 256
+    const int c = t % D, g = 4 * (t / D);
+    double acc[TL][4];
+#pragma unroll
+    for (int l = 0; l < TL; l++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) acc[l][k] = 0.0;
+    for (size_t r0 = e0; r0 < e1; r0 += (size_t)TR) {
+        const int nr = (e1 - r0 < (size_t)TR) ? (int)(e1 - r0) : TR;
+        int nrl[TL], l0 = 0;
+#pragma unroll
+        for (int l = 0; l < TL; l++) {
+            nrl[l] = (Kl[l] <= r0) ? 0 : ((Kl[l] - r0 < (size_t)nr) ? (int)(Kl[l] - r0) : nr);
+            if (nrl[l] < nr) l0 = l + 1;
+        }
+        __syncthreads();                                        // the shift is written, the previous tile consumed
+        aj_stage_rows(src, ix + r0, shift, tv, nr, nc, P, t);
+#pragma unroll
+        for (int l = 0; l < TL; l++)
+            for (int r = t; r < nrl[l]; r += 256) tw[l * TRp + r] = aj_weight(dd[r0 + r], h[l], rect[l]);
+        __syncthreads();
+        if (t >= J) continue;
+#pragma unroll
+        for (int l = 0; l < TL; l++)                            // a tolerance that ends inside the tile: its own shorter chain
+            if (nrl[l] > 0 && nrl[l] < nr) aj_chain(tv, tw + l * TRp, Ds, nrl[l], c, g, acc[l]);
+        aj_chain_from<TL>(l0, tv, tw, TRp, Ds, nr, c, g, acc);
+    }
+    if (t >= J) return;
+#pragma unroll
+    for (int l = 0; l < TL; l++) {
+        if (!Kl[l]) continue;
+        double* pp = part + (((size_t)blockIdx.y * T + t0 + l) * nchs + chunk) * (size_t)U * D;
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (g + u < U) pp[(size_t)(g + u) * D + c] = acc[l][u];
+    }
+}
+
+// grid (targets, tolerances): post_mean[(b T + t) P + j] = the fp64 mean of Y[i_e, j] over e < K_t (NS = 256 / min(P, 256) threads
+// per parameter, each the sum of every NS-th row in ascending order, then those sums in thread order: (K_t, P) only);
+// hout[b T + t] = d_{K_t - 1}.  src is read for the parameters only (columns nc ..).
+__global__ __launch_bounds__(256) void k_path_mean(AjSrc src, int nc, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
+                                                   size_t ld, AjKs ks, int T, int P, double* __restrict__ post_mean,
+                                                   double* __restrict__ hout) {
+    __shared__ double red[256];
+    const int t = threadIdx.x, tt = blockIdx.y;
+    const size_t b = blockIdx.x, K = ks.K[tt];
+    const uint64_t* ix = idx + b * ld;
+    if (hout && t == 0) hout[b * T + tt] = dist[b * ld + K - 1];
+    if (!post_mean || P == 0) return;
+    const int PW = P < 256 ? P : 256, NS = 256 / PW;
+    const int j = t % PW, s = t / PW;
+    for (int j0 = 0; j0 < P; j0 += PW) {
+        const bool mine = s < NS && j0 + j < P;
+        double a = 0.0;
+        if (mine)
+            for (size_t e = (size_t)s; e < K; e += (size_t)NS) a += aj_val(src, (size_t)ix[e], nc + j0 + j, nc);
+        red[t] = a;
+        __syncthreads();
+        if (mine && s == 0) {
+            for (int q = 1; q < NS; q++) a += red[q * PW + j];
+            post_mean[(b * T + tt) * (size_t)P + j0 + j] = a / (double)K;
+        }
+        __syncthreads();
+    }
+}
+
+// grid (chunks, targets b0 + blockIdx.y); part[((blockIdx.y pstride + chunk) U + r) D + c] = sum over the chunk's rows e (ascending) of
 // (w_e u_r) v_c, u = [1, x'], v = [1, x', theta'], x' / theta' = the row's values minus those of the target's first row.  Rows are
 // staged TR at a time.  A thread owns one group of four entries when the block has at most 256 groups and keeps their sums in
 // registers; otherwise an entry's running sum passes between tiles through part.  The chain is the same either way and for every TR.
+// ld: a target's rows start at idx + b ld (K itself, or K_max when the rows are a prefix of a longer ranking); pstride: blocks
+// between two targets in part (the grid's chunk count, or more when other tolerances' blocks lie between).
 __global__ __launch_bounds__(256) void k_adj_moments(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
-                                                     size_t K, int nc, int P, int kernel, size_t CH, int TR, size_t b0,
-                                                     double* __restrict__ part) {
+                                                     size_t ld, size_t K, int nc, int P, int kernel, size_t CH, int TR, size_t b0,
+                                                     size_t pstride, double* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x;
     const int U = 1 + nc, D = 1 + nc + P, Wv = nc + P, Ds = aj_stride(nc, P);
@@ -104,30 +280,23 @@ __global__ __launch_bounds__(256) void k_adj_moments(AjSrc src, const uint64_t* 
     double* shift = sm;                  // [1 + c]: the first row's value c
     double* tw = sm + Dp;                // TR weights
     double* tv = tw + TRp;               // TR x Ds
-    const size_t b = b0 + blockIdx.y, nch = gridDim.x, chunk = blockIdx.x;
-    const uint64_t* ix = idx + b * K;
-    const double* dd = dist + b * K;
+    const size_t b = b0 + blockIdx.y, chunk = blockIdx.x;
+    const uint64_t* ix = idx + b * ld;
+    const double* dd = dist + b * ld;
     const size_t e0 = chunk * CH, e1 = (e0 + CH < K) ? e0 + CH : K;
     const double h = dd[K - 1];
     const bool rect = kernel == 1 || aj_fallback(dd, K);
     const size_t i0 = (size_t)ix[0];
     for (int c = t; c < Wv; c += 256) shift[1 + c] = aj_val(src, i0, c, nc);
-    double* pp = part + ((size_t)blockIdx.y * nch + chunk) * (size_t)U * D;
+    double* pp = part + ((size_t)blockIdx.y * pstride + chunk) * (size_t)U * D;
     const int nrg = (U + 3) / 4, J = D * nrg;
     const bool regs = J <= 256;
     double racc[4] = {0.0, 0.0, 0.0, 0.0};
     for (size_t r0 = e0; r0 < e1; r0 += (size_t)TR) {
         const int nr = (e1 - r0 < (size_t)TR) ? (int)(e1 - r0) : TR;
         __syncthreads();                                        // the shift is written, the previous tile consumed
-        for (int q = t; q < nr * Wv; q += 256) {
-            const int r = q / Wv, c = q % Wv;
-            tv[r * Ds + 1 + c] = aj_val(src, (size_t)ix[r0 + r], c, nc) - shift[1 + c];
-        }
-        for (int r = t; r < nr; r += 256) {
-            tv[r * Ds] = 1.0;
-            for (int c = D; c < Ds; c++) tv[r * Ds + c] = 0.0;
-            tw[r] = aj_weight(dd[r0 + r], h, rect);
-        }
+        aj_stage_rows(src, ix + r0, shift, tv, nr, nc, P, t);
+        for (int r = t; r < nr; r += 256) tw[r] = aj_weight(dd[r0 + r], h, rect);
         __syncthreads();
         if (regs) {
             if (t < J) aj_chain(tv, tw, Ds, nr, t % D, 4 * (t / D), racc);
@@ -152,11 +321,14 @@ __global__ __launch_bounds__(256) void k_adj_moments(AjSrc src, const uint64_t* 
     }
 }
 
-// one work-group per target b0 + blockIdx.x: the moments (chunks summed in order), centred; the sweep; coef, rank and status
+// one work-group per (target b0 + blockIdx.x, tolerance t = blockIdx.y of T; the adjustment itself: T = 1, ks.K[0] = ld = K): the
+// moments of the rows below K_t (the blocks of the chunks e0 < K_t, summed in chunk order; part holds nchs block slots per target and
+// tolerance), centred; the sweep; coef, rank and status at slot b T + t
 __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
-                                                   size_t K, int nc, int P, int A, int kernel, const double* __restrict__ O, int KCO,
-                                                   const double* __restrict__ part, int nch, size_t b0, double* __restrict__ coef,
-                                                   int32_t* __restrict__ rank, int32_t* __restrict__ status) {
+                                                   size_t ld, AjKs ks, int T, size_t CH, int nc, int P, int A, int kernel,
+                                                   const double* __restrict__ O, int KCO, const double* __restrict__ part, int nchs,
+                                                   size_t b0, double* __restrict__ coef, int32_t* __restrict__ rank,
+                                                   int32_t* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x;
     const int U = 1 + nc, D = 1 + nc + P, NB = nc + AJ_RHS, ncp = (nc + 1) & ~1;
@@ -171,10 +343,11 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
     double* ts = rowk + NB;                 // AJ_RHS: sum w theta'
     double* tm = ts + AJ_RHS;               // mean of theta (not shifted)
     double* sW = tm + AJ_RHS;               // [0] sum of the weights, [1] pivot of this step
-    const size_t bl = blockIdx.x, b = b0 + bl;
+    const size_t bl = blockIdx.x, b = b0 + bl, K = ks.K[blockIdx.y], slot = b * T + blockIdx.y;
+    const int nch = (int)((K + CH - 1) / CH);
     const size_t blk = (size_t)U * D;
-    const double* pb = part + bl * (size_t)nch * blk;
-    const size_t i0 = (size_t)idx[b * K];
+    const double* pb = part + (bl * T + blockIdx.y) * (size_t)nchs * blk;
+    const size_t i0 = (size_t)idx[b * ld];
     for (int q = t; q < U; q += 256) {
         double s = 0.0;
         for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + q];
@@ -193,7 +366,7 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
         for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + (size_t)(1 + lo) * D + 1 + hi];
         C0[q] = fma(-xm[lo], xs[hi], s);
     }
-    double* cb = coef + b * (size_t)(A + 1) * P;
+    double* cb = coef + slot * (size_t)(A + 1) * P;
     for (int j0 = 0; j0 == 0 || j0 < P; j0 += AJ_RHS) {
         const int nb = (P - j0 < AJ_RHS) ? P - j0 : AJ_RHS, NW = nc + nb;
         __syncthreads();                                        // C0 written, the previous batch's coefficients read
@@ -246,8 +419,8 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
     if (t == 0) {
         int r = 0;
         for (int k = 0; k < nc; k++) r += kept[k] != 0.0;
-        if (rank) rank[b] = r;
-        if (status) status[b] = (r < nc ? 1 : 0) | ((kernel == 0 && aj_fallback(dist + b * K, K)) ? 2 : 0);
+        if (rank) rank[slot] = r;
+        if (status) status[slot] = (r < nc ? 1 : 0) | ((kernel == 0 && aj_fallback(dist + b * ld, K)) ? 2 : 0);
     }
 }
 
@@ -391,12 +564,15 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
     const size_t lds_m = (size_t)(((D + 1) & ~1) + ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, Pi)) * 8;
     const size_t lds_s = aj_solve_lds(nc);
     ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+    AjKs ks = {};
+    ks.K[0] = K;
     for (size_t b0 = 0; b0 < B; b0 += bb) {
         const size_t nb = (B - b0 < bb) ? B - b0 : bb;
         hipLaunchKernelGGL(k_adj_moments, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds_m, ctx->stream, src, (const uint64_t*)idx,
-                           (const double*)d, K, nc, Pi, kernel, pl.CH, pl.TR, b0, part);
+                           (const double*)d, K, K, nc, Pi, kernel, pl.CH, pl.TR, b0, pl.nch, part);
         hipLaunchKernelGGL(k_adj_solve, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx, (const double*)d, K,
-                           nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0, coef, out->rank, out->status);
+                           ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0, coef, out->rank,
+                           out->status);
         ABC_HIP(ctx, hipGetLastError());
     }
 
@@ -422,6 +598,130 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
             hipLaunchKernelGGL(k_adj_apply, dim3((unsigned)tiles, (unsigned)nb), dim3(256), lds_a, ctx->stream, src, (const uint64_t*)idx,
                                (const double*)d, K, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)coef, TR, beta_lds, b0,
                                out->theta, out->weight);
+            ABC_HIP(ctx, hipGetLastError());
+        }
+    }
+    return ABC_OK;
+}
+
+namespace {
+
+size_t aj_path_batch(size_t K, size_t A, size_t P, size_t B, size_t T) {
+    size_t bb = AJ_PART_BYTES / (T * aj_part_bytes(K, A, P));
+    if (bb < 1) bb = 1;
+    if (bb > AJ_MAX_GRID_Y) bb = AJ_MAX_GRID_Y;
+    return bb < B ? bb : B;
+}
+
+template <int TL>
+int aj_launch_moments_path(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, const double* d, size_t ld, const AjKs& ks, int T,
+                           int t0, int nc, int P, int kernel, const AjPlan& pl, size_t b0, size_t nb, double* part) {
+    const int D = 1 + nc + P;
+    const size_t lds = (size_t)(((D + 1) & ~1) + TL * ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, P)) * 8;       // <= 64.5 KiB
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_moments_path<TL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_adj_moments_path<TL>, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds, ctx->stream, src, idx, d, ld, ks, T,
+                       t0, nc, P, kernel, pl.CH, pl.TR, b0, pl.nch, part);
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+}  // namespace
+
+size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T) {
+    size_t b = 0;
+    b += B * K * 8;                                                  // distances (the caller's may be NULL)
+    b += B * T * (A + 1) * P * 8 + 8;                                // coefficients (the caller's may be NULL)
+    if (aj_use_table(N, A, P, B, K)) b += N * (A + P) * 8;           // the row-major table
+    b += aj_path_batch(K, A, P, B, T) * T * aj_part_bytes(K, A, P);  // moment blocks of one batch, every tolerance
+    return b + 16 * 256;
+}
+
+int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
+                             const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
+                             bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path) {
+    const int T = (int)path->T, Pi = (int)P;
+    AjKs ks = {};
+    for (int t = 0; t < T; t++) ks.K[t] = path->Ks[t];
+    const size_t K = ks.K[T - 1];                                    // K_max: the ranking's K and the rows' stride
+    double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
+    if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
+    abc_tg_scores sc;
+    ABC_TRY(launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, idx, d, nullptr, &sc));
+    const bool fit = path->coef || path->rank || path->status;
+    if (!fit && !path->post_mean && !path->h) return ABC_OK;
+
+    AjSrc src;                                                       // without the fit: the parameters only
+    src.T = nullptr;
+    src.W = P;
+    src.S = nullptr;
+    src.sld = 0;
+    src.Y = Y;
+    src.ldy = ldy;
+    int nc = 0;
+    if (fit) {
+        double hdr = 0.0;
+        ABC_HIP(ctx, hipMemcpyAsync(&hdr, model, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        nc = hdr < 0.0 ? 0 : (hdr > (double)A ? (int)A : (int)hdr);  // the ranking's tg_ncomp
+        double* coef = path->coef ? path->coef : (double*)abc_ws_alloc(ctx, B * T * (A + 1) * P * 8 + 8);
+        if (!coef) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
+        src.W = (size_t)nc + P;
+        src.S = sc.S;
+        src.sld = sc.sld;
+        if (aj_use_table(N, A, P, B, K) && src.W > 0) {              // the adjustment's rule with K = K_max
+            double* Tb = (double*)abc_ws_alloc(ctx, N * src.W * 8);
+            if (!Tb) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
+            size_t blocks = (N + 63) / 64;
+            if (blocks > 8192) blocks = 8192;
+            hipLaunchKernelGGL(k_adj_table, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sc.S, sc.sld, Y, ldy, N, nc, Pi, Tb);
+            ABC_HIP(ctx, hipGetLastError());
+            src.T = Tb;
+        }
+        const AjPlan pl = aj_plan(K, nc, Pi);
+        const size_t bb = aj_path_batch(K, A, P, B, (size_t)T);
+        const size_t blk = (size_t)(1 + nc) * (1 + nc + P);
+        double* part = (double*)abc_ws_alloc(ctx, bb * T * pl.nch * blk * 8);
+        if (!part) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
+        const int D = 1 + nc + Pi;
+        const bool wide = D * ((1 + nc + 3) / 4) > 256;              // more than 256 entry groups: k_adj_moments, once per tolerance
+        const size_t lds_m = (size_t)(((D + 1) & ~1) + ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, Pi)) * 8;
+        const size_t lds_s = aj_solve_lds(nc);
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+        for (size_t b0 = 0; b0 < B; b0 += bb) {
+            const size_t nb = (B - b0 < bb) ? B - b0 : bb;
+            if (wide) {
+                for (int t = 0; t < T; t++) {
+                    const size_t ncht = (ks.K[t] + pl.CH - 1) / pl.CH;
+                    hipLaunchKernelGGL(k_adj_moments, dim3((unsigned)ncht, (unsigned)nb), dim3(256), lds_m, ctx->stream, src,
+                                       (const uint64_t*)idx, (const double*)d, K, ks.K[t], nc, Pi, kernel, pl.CH, pl.TR, b0,
+                                       (size_t)T * pl.nch, part + (size_t)t * pl.nch * blk);
+                }
+                ABC_HIP(ctx, hipGetLastError());
+            } else {
+                // passes of at most 4 tolerance lanes, from the largest down (8 lanes take 256 VGPRs on gfx950: one work-group per CU)
+                for (int hi = T; hi > 0;) {
+                    const int n = hi < 4 ? hi : 4, TL = n > 2 ? 4 : n, t0 = hi - TL;
+                    switch (TL) {
+                    case 1: ABC_TRY(aj_launch_moments_path<1>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part)); break;
+                    case 2: ABC_TRY(aj_launch_moments_path<2>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part)); break;
+                    default: ABC_TRY(aj_launch_moments_path<4>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part)); break;
+                    }
+                    hi -= n;
+                }
+            }
+            hipLaunchKernelGGL(k_adj_solve, dim3((unsigned)nb, (unsigned)T), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+                               (const double*)d, K, ks, T, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch,
+                               b0, coef, path->rank, path->status);
+            ABC_HIP(ctx, hipGetLastError());
+        }
+    }
+    if (path->post_mean || path->h) {
+        const size_t step = (size_t)1 << 30;
+        for (size_t b0 = 0; b0 < B; b0 += step) {
+            const size_t nb = (B - b0 < step) ? B - b0 : step;
+            hipLaunchKernelGGL(k_path_mean, dim3((unsigned)nb, (unsigned)T), dim3(256), 0, ctx->stream, src, nc,
+                               (const uint64_t*)idx + b0 * K, (const double*)d + b0 * K, K, ks, T, Pi,
+                               path->post_mean ? path->post_mean + b0 * T * P : nullptr, path->h ? path->h + b0 * T : nullptr);
             ABC_HIP(ctx, hipGetLastError());
         }
     }

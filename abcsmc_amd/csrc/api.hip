@@ -1411,8 +1411,8 @@ struct Product {
     }
 };
 
-// what follows the ranking: nothing, the adjustment, a posterior product
-enum { TG_PLAIN, TG_ADJUST, TG_PRODUCT };
+// what follows the ranking: nothing, the adjustment, a posterior product, the tolerance path
+enum { TG_PLAIN, TG_ADJUST, TG_PRODUCT, TG_PATH };
 struct TgRequest {                             // (members in the order of the entries' arguments)
     int kind;
     const double* X;  size_t ldx;
@@ -1421,7 +1421,7 @@ struct TgRequest {                             // (members in the order of the e
     const double* model;  size_t A;
     const double* targets;  size_t ldt, B;
     const uint64_t* exclude;
-    size_t K;
+    size_t K;                                  // TG_PATH: set by tg_check to the largest tolerance
     uint64_t* idx;                             // optional for TG_PRODUCT
     double* dist;                              // optional
     double* post_mean = nullptr;               // TG_PLAIN only, optional
@@ -1429,15 +1429,33 @@ struct TgRequest {                             // (members in the order of the e
     const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; TG_PRODUCT: optional, method 1 only
     Product prod;                              // TG_PRODUCT only
     bool any_excl = false;                     // exclude names a row for some target: set by tg_check
+    const abc_path* path = nullptr;            // TG_PATH only: required; Ks in host memory
     bool segments() const { return kind == TG_PRODUCT; }      // the rows' values are read after the ranking
     bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
 };
 }  // namespace
 
-// Argument checks of the family; sets r.any_excl.  host: the arrays are in host memory and the model is fitted by the call
+// the tolerance list of a path request
+static int path_check(abc_ctx* ctx, const char* fn, const abc_path* path) {
+    if (!path) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (path is required)", fn);
+    if (!path->Ks) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (path->Ks is required)", fn);
+    if (path->T == 0 || path->T > 16) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: T = %zu tolerances (1 to 16)", fn, path->T);
+    if (path->Ks[0] == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: Ks[0] == 0", fn);
+    for (size_t t = 1; t < path->T; t++)
+        if (path->Ks[t] <= path->Ks[t - 1])
+            ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: Ks[%zu] = %zu after Ks[%zu] = %zu (strictly ascending)", fn, t, path->Ks[t], t - 1,
+                     path->Ks[t - 1]);
+    return ABC_OK;
+}
+
+// Argument checks of the family; sets r.any_excl (and r.K of a path).  host: the arrays are in host memory and the model is fitted by the call
 // (which needs Y); otherwise exclude is brought to the host here, after every check that does not need it.
 static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
     const bool plain = r.kind == TG_PLAIN, summary = r.segments();
+    if (r.kind == TG_PATH) {
+        ABC_TRY(path_check(ctx, fn, r.path));
+        r.K = r.path->Ks[r.path->T - 1];
+    }
     const size_t N = r.N, B = r.B, K = r.K;
     if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
     if (!r.targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (targets is required)", fn);
@@ -1492,6 +1510,7 @@ static size_t tg_need(const TgRequest& r, bool host, int rule) {
     const size_t N = r.N, M = r.M, P = r.P, A = r.A, B = r.B, K = r.K;
     size_t b = abc_targets_need(N, A, B, K, r.any_excl);
     if (r.regress()) b += abc_adjust_need(N, A, P, B, K);
+    if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T);
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
     b += r.prod.need(B, K, P);
     if (!host) return b + abc_ws_need(N, 1, 1, 1, K + 1, 0, 0);
@@ -1499,6 +1518,7 @@ static size_t tg_need(const TgRequest& r, bool host, int rule) {
     b += (N * (M + P) + M + 4) * 8;                                               // X, Y, the zero observation and its one idx, dist
     b += (B * M + B + 2 * B * K) * 8 + 8 * 256;                                   // targets, exclude, idx, dist
     if (r.kind == TG_PLAIN) b += B * P * 8;                                       // post_mean
+    else if (r.kind == TG_PATH) b += B * r.path->T * ((A + 2) * P + 2) * 8 + 8 * 256;      // abc_path: post_mean, coef, rank + status, h
     else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
     return b + r.prod.stage_bytes(B, P);
 }
@@ -1514,6 +1534,9 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
         if (!d) d = (double*)abc_ws_alloc(ctx, B * K * 8);
         if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     }
+    if (r.kind == TG_PATH)
+        return launch_rank_targets_path(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
+                                        r.any_excl, r.kernel, ix, d, r.path);
     abc_adj_keep keep;
     if (!r.regress()) {     // (post_mean: of the plain ranking only)
         ABC_TRY(launch_rank_targets(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
@@ -1544,9 +1567,10 @@ static int tg_dev(abc_ctx* ctx, const char* fn, TgRequest r) {
 
 // The host entries: h holds host pointers.  Upload, one fit, the request on the arena's copies, downloads, synchronise.
 static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac, int max_comp, int rule, int32_t* ncomp) {
-    const size_t N = h.N, M = h.M, P = h.P, B = h.B, K = h.K;
+    const size_t N = h.N, M = h.M, P = h.P, B = h.B;
     const size_t A = h.A = default_A(M, P, max_comp);
     ABC_TRY(tg_check(ctx, fn, h, true));
+    const size_t K = h.K;                                   // (a path's: set by the check)
     ABC_TRY(abc_ws_reserve(ctx, tg_need(h, true, rule)));
     Stage s{ctx};
     // the fit: the single-target ranking's own path (generation_core) on an all-zero observation, whose scores are not used
@@ -1583,6 +1607,17 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         od.status = ah->status ? s.dev<int32_t>(B) : nullptr;
     }
     r.adj = ah ? &od : nullptr;
+    abc_path pd = {};
+    if (h.kind == TG_PATH) {     // (coef one element longer, as the adjustment's own buffer)
+        const size_t T = h.path->T;
+        pd = *h.path;
+        pd.post_mean = (h.path->post_mean && P) ? s.dev<double>(B * T * P) : nullptr;
+        pd.coef = h.path->coef ? s.dev<double>(B * T * (A + 1) * P + 1) : nullptr;
+        pd.rank = h.path->rank ? s.dev<int32_t>(B * T) : nullptr;
+        pd.status = h.path->status ? s.dev<int32_t>(B * T) : nullptr;
+        pd.h = h.path->h ? s.dev<double>(B * T) : nullptr;
+        r.path = &pd;
+    }
     r.prod = h.prod.stage(s, B, P);
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_TRY(tg_run(ctx, fn, r));
@@ -1595,6 +1630,14 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         s.down(ah->coef, od.coef, B * (A + 1) * P);
         s.down(ah->rank, od.rank, B);
         s.down(ah->status, od.status, B);
+    }
+    if (h.kind == TG_PATH) {
+        const size_t T = h.path->T;
+        s.down(h.path->post_mean, pd.post_mean, B * T * P);
+        s.down(h.path->coef, pd.coef, B * T * (A + 1) * P);
+        s.down(h.path->rank, pd.rank, B * T);
+        s.down(h.path->status, pd.status, B * T);
+        s.down(h.path->h, pd.h, B * T);
     }
     h.prod.down(s, B, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1635,6 +1678,25 @@ extern "C" int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const doubl
     CHECK_CTX(ctx);
     const TgRequest h{TG_ADJUST, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, 0, kernel, out};
     return tg_host(ctx, "abc_particle_ranking_pls_targets_adjust", h, train_frac, max_comp, rule, ncomp);
+}
+
+extern "C" int abc_rank_targets_path_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                         size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                         const uint64_t* exclude, int kernel, uint64_t* idx, double* dist, const abc_path* path) {
+    CHECK_CTX(ctx);
+    TgRequest r{TG_PATH, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, 0, idx, dist, nullptr, 0, kernel};
+    r.path = path;
+    return tg_dev(ctx, "abc_rank_targets_path_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_path(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                     const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                     const uint64_t* exclude, int kernel, uint64_t* idx, double* dist,
+                                                     const abc_path* path, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    TgRequest h{TG_PATH, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, 0, idx, dist, nullptr, 0, kernel};
+    h.path = path;
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_path", h, train_frac, max_comp, rule, ncomp);
 }
 
 extern "C" int abc_rank_targets_summary_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,

@@ -384,6 +384,45 @@ inline std::vector<TargetAdjustment> particle_ranking_PLS_targets_adjust(const M
     }
     return res;
 }
+// Tolerance path (abc_particle_ranking_pls_targets_path): ONE ranking at K_max = Ks.back(), then the rejection mean and the
+// local-linear fit at every tolerance of the strictly ascending list Ks (at most 16), each from the first Ks[t] rows only.  Per
+// target: the K_max rows, post_mean (T x P), alpha (T x P: the adjusted posterior means), the bandwidths h, rank and status (T).
+struct TargetPath {
+    std::vector<size_t> idx;
+    Mat2D post_mean, alpha;
+    std::vector<double> h;
+    std::vector<int> rank, status;
+};
+inline std::vector<TargetPath> particle_ranking_PLS_targets_path(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                const float_type train_frac, const std::vector<size_t>& Ks,
+                                                                int kernel = 0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols(), T = Ks.size(), K = T ? Ks.back() : 0;
+    const int mc = max_components_ref();
+    const size_t A = mc > 0 ? (size_t)mc : (M < P ? M : P);
+    std::vector<uint64_t> idx(B * K);
+    std::vector<double> pm(B * T * P), cf(B * T * (A + 1) * P), h(B * T);
+    std::vector<int32_t> rank(B * T), status(B * T);
+    abc_path path = {Ks.data(), T, pm.data(), cf.data(), rank.data(), status.data(), h.data()};
+    check(abc_particle_ranking_pls_targets_path(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac, mc,
+                                                component_rule(), nullptr, kernel, idx.data(), nullptr, &path, nullptr));
+    std::vector<TargetPath> res(B);
+    for (size_t b = 0; b < B; b++) {
+        TargetPath& r = res[b];
+        r.idx.assign(idx.begin() + b * K, idx.begin() + (b + 1) * K);
+        r.post_mean = Mat2D(T, P);
+        r.alpha = Mat2D(T, P);
+        for (size_t t = 0; t < T; t++)
+            for (size_t j = 0; j < P; j++) {
+                r.post_mean(t, j) = pm[(b * T + t) * P + j];
+                r.alpha(t, j) = cf[(b * T + t) * (A + 1) * P + j];
+            }
+        r.h.assign(h.begin() + b * T, h.begin() + (b + 1) * T);
+        r.rank.assign(rank.begin() + b * T, rank.begin() + (b + 1) * T);
+        r.status.assign(status.begin() + b * T, status.begin() + (b + 1) * T);
+    }
+    return res;
+}
 // The same ranking followed by weighted posterior quantiles of every target's K rows and, with truth (B x P), the posterior CDF at
 // the truth (abc_particle_ranking_pls_targets_summary; method 0 rejection, 1 loclinear with kernel 0 Epanechnikov / 1 rectangular).
 // Per target: quant (nq x P, row q = level probs[q]) and cdf (P; empty without truth).

@@ -75,6 +75,11 @@ int main() {
         std::printf("draws: %zu targets, ess %.1f, bw[0] %.3g, first %.3f; weighted src[0] %zu ess %.1f\n", td.size(), td[0].ess,
                     td[0].bw[0], td[0].draws(0, 0), wd.src[0], wd.ess);
         if (!(wd.draws(0, 0) == post(wd.src[0], 0)) || !(td[1].ess > 1.0)) return 4;
+        // the tolerance path: one ranking, the rejection mean and the local-linear fit at three tolerances
+        const std::vector<TargetPath> tp = particle_ranking_PLS_targets_path(X, Y, tg, 0.5, {K / 4, K / 2, K});
+        std::printf("path: %zu rows, h %.3g %.3g %.3g, alpha[0] %.3f %.3f %.3f\n", tp[0].idx.size(), tp[0].h[0], tp[0].h[1], tp[0].h[2],
+                    tp[0].alpha(0, 0), tp[0].alpha(1, 0), tp[0].alpha(2, 0));
+        if (tp[0].idx.size() != K || !(tp[0].h[0] <= tp[0].h[1] && tp[0].h[1] <= tp[0].h[2])) return 5;
     } catch (const HipError& e) {
         std::printf("HipError %d: %s\n", e.code, e.what());
         return 1;

@@ -154,6 +154,36 @@ def rank_targets_adjust(X, model, A, targets, K, Y, exclude=None, kernel=_lib.KE
     return r
 
 
+def _path_ks(Ks):
+    """The tolerance list as a uint64 array (it stays in host memory) and its largest entry."""
+    ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))
+    return ks, (int(ks[-1]) if ks.size else 0)
+
+
+def rank_targets_path(X, model, A, targets, Ks, Y, exclude=None, kernel=_lib.KERNEL_EPANECHNIKOV, post_mean=True, coef=True,
+                      dist=True, ctx=None):
+    """Tolerance path on the device (abc_rank_targets_path_dev): one ranking at K_max = Ks[-1], then the rejection mean and the
+    local-linear fit of rank_targets_adjust at every tolerance of the strictly ascending list Ks (at most 16).  Returns
+    dict(idx (B, K_max) int64, dist (B, K_max) or None, post_mean (B, T, P) or None, coef (B, T, A + 1, P) or None, rank (B, T)
+    int32, status (B, T) int32, h (B, T): the bandwidths) as device tensors."""
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
+    ks, K = _path_ks(Ks)
+    T = ks.size
+    f64, i32 = torch.float64, torch.int32
+    r = dict(idx=torch.empty((B, K), dtype=torch.int64, device=dev),
+             dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None,
+             post_mean=torch.empty((B, T, P), dtype=f64, device=dev) if post_mean else None,
+             coef=torch.empty((B, T, A + 1, P), dtype=f64, device=dev) if coef else None,
+             rank=torch.empty((B, T), dtype=i32, device=dev), status=torch.empty((B, T), dtype=i32, device=dev),
+             h=torch.empty((B, T), dtype=f64, device=dev))
+    path = _lib.Path(ks.ctypes.data, T, _ptr(r["post_mean"]), _ptr(r["coef"]), r["rank"].data_ptr(), r["status"].data_ptr(),
+                     r["h"].data_ptr())
+    ctx.check(lib().abc_rank_targets_path_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
+                                              targets.data_ptr(), ldt, B, _ptr(exclude), int(kernel), r["idx"].data_ptr(),
+                                              _ptr(r["dist"]), C.byref(path)))
+    return r
+
+
 def _rank_targets_product(product, make, X, model, A, targets, K, Y, method, kernel, exclude, dist, adjust, ctx):
     """The call of rank_targets_{summary,density,joint,draws}.  make(lead, P, dev) -> (the product's struct, its outputs as a dict, what
     must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and the adjust members added."""

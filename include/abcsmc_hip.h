@@ -421,6 +421,39 @@ int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const double* X, const
                                             const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
                                             const abc_adjust_out* out, int32_t* ncomp);
 
+/* ---- tolerance path: one batched ranking, the rejection estimate and the local-linear fit at several tolerances ------------
+ * What cv4abc does with tols = c(.005, .01, .05): ONE ranking at K_max = Ks[T-1] (idx and dist, K_max x B, are the bits of
+ * abc_rank_targets_dev with K = K_max; dist may be NULL), and from it an estimate at every tolerance K_t of an ascending list.
+ * The full (dist, row) order is nested, so rows e = 0..K_t-1 of that ranking are the ranking at K_t bit for bit.
+ * Definition at tolerance t: the adjustment's definition above applied to rows e = 0..K_t-1 with h = d_{K_t-1}: the same weight
+ * formula, the rectangular fallback evaluated on those K_t rows, the same shift by the first retained row, sweep and pivot rule.
+ * post_mean is thetabar of the rectangular kernel over those rows (an fp64 mean).  Rows e >= K_t take NO part in tolerance t: they
+ * are left out of its sums, not multiplied by a zero weight, so a non-finite parameter in a farther row never reaches a nearer
+ * tolerance.
+ * Every reduction's order depends on (K_max, K_t, nc, P) only: the outputs of (b, t) are the same bits alone, inside any batch,
+ * through either entry point and whatever other tolerances the list holds (given its K_max).  A path of one tolerance, Ks = {K},
+ * gives in coef, rank and status the bits of abc_rank_targets_adjust_dev with that K.
+ * Limits and errors: those of the ranking (with K = K_max) and of the adjustment (A <= 64, P <= 1024), and ABC_ERR_INVALID for a
+ * NULL path, NULL Ks, T = 0, T > 16, Ks[0] = 0 and a list that is not strictly ascending. */
+typedef struct {
+    const size_t* Ks; size_t T;  /* HOST memory in every entry: 1..16 strictly ascending tolerances, Ks[0] >= 1;
+                                    K_max = Ks[T-1] obeys the ranking's limits (<= N, <= N-1 with an exclusion) */
+    double*  post_mean;          /* B x T x P      rejection: fp64 mean of Y over the first K_t retained rows   */
+    double*  coef;               /* B x T x (A+1) x P  loclinear at tolerance t, laid out as abc_adjust_out.coef */
+    int32_t* rank;               /* B x T */
+    int32_t* status;             /* B x T   bits as abc_adjust_out.status */
+    double*  h;                  /* B x T   the bandwidth d_{K_t-1} (the bits of dist[b K_max + K_t - 1]) */
+} abc_path;                      /* every output optional (NULL: not written); device or host memory per the entry point */
+/* Device pointers (as abc_rank_targets_adjust_dev; Y required). */
+int abc_rank_targets_path_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                              size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                              const uint64_t* exclude, int kernel, uint64_t* idx, double* dist, const abc_path* path);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_adjust), path's outputs in host memory. */
+int abc_particle_ranking_pls_targets_path(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                          const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                          const uint64_t* exclude, int kernel, uint64_t* idx, double* dist,
+                                          const abc_path* path, int32_t* ncomp);
+
 /* ---- weighted posterior quantiles and CDF of the batched ranking ------------------------------------------------------------
  * A segment is one (target b, parameter j): values v_e and weights w_e, e = 0..K-1 in the ranking's row order, exclusion applied.
  *   method 0, rejection (ABC_POSTERIOR_REJECTION):  v_e = Y[i_e, j], w_e = 1 (the kernel argument is checked, no effect)
