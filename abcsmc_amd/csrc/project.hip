@@ -437,12 +437,13 @@ int launch_project_distance(abc_ctx* ctx, const double* X, size_t n, size_t ldx,
         return ABC_OK;
     }
     // the LDS kernel pads the loadings itself; the others read the padded copy k_pad_model leaves in the workspace
-    const bool lds_kernel = (KC == 8 || KC == 16 || KC == 32) && (M * KC + KC) * sizeof(double) <= 64 * 1024 && npairs;
+    const bool lds_kernel = (KC == 8 || KC == 16) && (M * KC + KC) * sizeof(double) <= 64 * 1024 && npairs;
     if (!lds_kernel || ntail) {
         hipLaunchKernelGGL(k_pad_model, dim3(1), dim3(256), 0, ctx->stream, model, (int)M, (int)P, (int)A, KC, Rpad, opad);
         ABC_HIP(ctx, hipGetLastError());
     }
-    // (16 / 32 components with the loadings in LDS; beyond 64 KB of them the scalar-operand kernel)
+    // (8 / 16 components with the loadings in LDS; beyond 64 KB of them, and at 32 components beyond the matrix-pipe kernel's LDS,
+    // the scalar-operand kernel)
 #define LAUNCH_PD_LDS(KCV)                                                                                             \
     do {                                                                                                               \
         const int lb = (int)((M * KCV + KCV) * sizeof(double));                                                        \
@@ -473,7 +474,7 @@ int launch_project_distance(abc_ctx* ctx, const double* X, size_t n, size_t ldx,
         case 4: LAUNCH_PD(4); break;
         case 8: if (lds_kernel) LAUNCH_PD_LDS(8); else LAUNCH_PD(8); break;
         case 16: if (lds_kernel) LAUNCH_PD_LDS(16); else LAUNCH_PD(16); break;
-        default: if (lds_kernel) LAUNCH_PD_LDS(32); else LAUNCH_PD(32); break;
+        default: LAUNCH_PD(32); break;      // (32 components with row pairs and the loadings within LDS: the matrix-pipe kernel above)
     }
 #undef LAUNCH_PD
 #undef LAUNCH_PD_LDS
