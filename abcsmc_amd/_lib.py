@@ -188,6 +188,10 @@ SIGNATURES = {
     "abc_rank_targets_path_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _i, _vp, _vp, _vp]),
     "abc_particle_ranking_pls_targets_path": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _i, _vp, _vp, _vp,
                                                    _vp]),
+    "abc_rank_targets_path_summary_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _i, _i, _vp, _vp,
+                                               _vp, _vp]),
+    "abc_particle_ranking_pls_targets_path_summary": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _i, _i, _vp, _vp,
+                                                           _vp, _vp, _vp]),
     "abc_particle_ranking_simple": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "abc_calculate_doubled_variance": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "abc_weight_predictive_prior_uniform": (_i, [_vp, _sz, _vp]),

@@ -174,6 +174,44 @@ def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction
 _METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_LOCLINEAR}
 
 
+def particle_ranking_PLS_targets_path_summary(X_orig, Y_orig, targets, training_fraction, Ks, probs=(0.025, 0.5, 0.975), truth=None,
+                                              method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
+                                              rule=_lib.RULE_DEFAULT, ctx=None):
+    """particle_ranking_PLS_targets_path with the summaries of particle_ranking_PLS_targets_summary at every tolerance
+    (abc_particle_ranking_pls_targets_path_summary; the definition is in the header): the ranking, the fit and, under "rejection",
+    the sort of every (target, parameter) are made once for all of Ks.  Tolerance t's quantiles and CDF are those of the summary
+    call with K = Ks[t] (bit for bit under "rejection").  Returns the path's dict plus quant (B, T, nq, P): [b, t, q, j], cdf
+    (B, T, P) or None, and probs."""
+    ctx = _ctx(ctx)
+    method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
+    ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))
+    X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, ks[-1] if ks.size else 0, exclude)
+    nt = ks.size
+    A = max_comp if max_comp > 0 else min(M, P)
+    idx = np.empty((B, K), dtype=np.uint64)
+    dist = np.empty((B, K))
+    pm = np.empty((B, nt, P))
+    coef = np.empty((B, nt, A + 1, P))
+    rank = np.empty((B, nt), dtype=np.int32)
+    status = np.empty((B, nt), dtype=np.int32)
+    h = np.empty((B, nt))
+    path = _lib.Path(_p(ks), nt, _p(pm), _p(coef), _p(rank), _p(status), _p(h))
+    sm, o, keep = _summary_arg(probs, None, (B, nt), P)     # quant (B, T, nq, P); truth is per target, the CDF per tolerance
+    tr = None
+    if truth is not None:
+        tr = np.ascontiguousarray(np.asarray(truth, dtype=np.float64).reshape(B, P))
+        o["cdf"] = np.empty((B, nt, P))
+        sm.truth, sm.cdf = tr.ctypes.data, o["cdf"].ctypes.data
+    ncomp = C.c_int32(0)
+    ctx.check(lib().abc_particle_ranking_pls_targets_path_summary(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B,
+                                                                  float(training_fraction), int(max_comp), int(rule), _p(ex), method,
+                                                                  kernel, _p(idx), _p(dist), C.byref(path), C.byref(sm),
+                                                                  C.addressof(ncomp)))
+    o.update(post_mean=pm, coef=coef, alpha=coef[:, :, 0], rank=rank, status=status, h=h, Ks=ks.astype(np.int64), idx=idx, dist=dist,
+             ncomp=ncomp.value, probs=keep[0])
+    return o
+
+
 def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx):
     """The call of particle_ranking_PLS_targets_{summary,density,joint,draws}.  make(lead, P) -> (the product's struct, its outputs as a
     dict, what must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and ncomp added."""
@@ -433,12 +471,17 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
 
 
 def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
-                            ctx=None, method="rejection", kernel="epanechnikov"):
+                            ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False):
     """cross_validate_pls at every tolerance of the strictly ascending list Ks from ONE call of
     particle_ranking_PLS_targets_path: cv4abc with tols = c(...).  The left-out rows are drawn from `seed` exactly as
     cross_validate_pls draws them.  method: "rejection" (the mean of the Ks[t] nearest rows) or "loclinear" (alpha of the fit at
     tolerance t).  Returns dict(rows, theta, Ks, post_mean (n_targets, T, P), pred_error (T, P) by cross_validate_pls's formula,
-    best (P,): the index of the tolerance with the smallest error of each parameter (0 where every error is NaN), idx, ncomp)."""
+    best (P,): the index of the tolerance with the smallest error of each parameter (0 where every error is NaN), idx, ncomp).
+    statistic="median" (cv4abc's default) or coverage=True take ONE call of particle_ranking_PLS_targets_path_summary instead:
+    with "median" the estimate is post_median (n_targets, T, P) in place of post_mean, and pred_error and best come from it; with
+    coverage=True the result gains truth_cdf (n_targets, T, P) and ci95 (T, P) as cross_validate_pls's at every tolerance,
+    coverage_ks (T, P): the Kolmogorov distance of the finite truth_cdf values from the uniform (coverage_ks below), and
+    best_calibrated (P,): the index of the tolerance with the smallest coverage_ks (0 where all are NaN)."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -446,17 +489,52 @@ def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fracti
         raise ValueError("n_targets must be in [1, N]")
     if method not in ("rejection", "loclinear"):
         raise ValueError("method must be 'rejection' or 'loclinear'")
+    if statistic not in ("mean", "median"):
+        raise ValueError("statistic must be 'mean' or 'median'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
     theta = np.ascontiguousarray(Y[rows])
-    r = particle_ranking_PLS_targets_path(X, Y, X[rows], training_fraction, Ks, kernel=kernel, exclude=rows, max_comp=max_comp,
-                                          rule=rule, ctx=ctx)
-    pm = np.ascontiguousarray(r["post_mean"] if method == "rejection" else r["alpha"])
+    if statistic == "median" or coverage:
+        r = particle_ranking_PLS_targets_path_summary(X, Y, X[rows], training_fraction, Ks, probs=(0.5, 0.025, 0.975),
+                                                      truth=theta if coverage else None, method=method, kernel=kernel, exclude=rows,
+                                                      max_comp=max_comp, rule=rule, ctx=ctx)
+    else:
+        r = particle_ranking_PLS_targets_path(X, Y, X[rows], training_fraction, Ks, kernel=kernel, exclude=rows, max_comp=max_comp,
+                                              rule=rule, ctx=ctx)
+    if statistic == "median":
+        pm = np.ascontiguousarray(r["quant"][:, :, 0, :])
+    else:
+        pm = np.ascontiguousarray(r["post_mean"] if method == "rejection" else r["alpha"])
     var = theta.var(axis=0, ddof=1) if n_targets > 1 else np.zeros(theta.shape[1])
     sse = ((pm - theta[:, None, :]) ** 2).sum(axis=0)
     with np.errstate(divide="ignore", invalid="ignore"):
         err = np.where(var > 0, sse / (n_targets * np.where(var > 0, var, 1.0)), np.nan)
     best = np.argmin(np.where(np.isnan(err), np.inf, err), axis=0)
-    return dict(rows=rows, theta=theta, Ks=r["Ks"], post_mean=pm, pred_error=err, best=best, idx=r["idx"], ncomp=r["ncomp"])
+    out = dict(rows=rows, theta=theta, Ks=r["Ks"], pred_error=err, best=best, idx=r["idx"], ncomp=r["ncomp"])
+    out["post_" + statistic] = pm
+    if coverage:
+        th = theta[:, None, :]
+        out["truth_cdf"] = r["cdf"]
+        out["ci95"] = ((r["quant"][:, :, 1, :] <= th) & (th <= r["quant"][:, :, 2, :])).mean(axis=0)
+        out["coverage_ks"] = ks = coverage_ks(r["cdf"])
+        out["best_calibrated"] = np.argmin(np.where(np.isnan(ks), np.inf, ks), axis=0)
+    return out
+
+
+def coverage_ks(truth_cdf):
+    """The Kolmogorov distance sup_x |F_n(x) - x| between the empirical distribution of the finite values of truth_cdf along its
+    first axis (n targets; values in [0, 1]) and the uniform distribution, per remaining index: the size of the coverage
+    diagnostic's departure from calibration (no p-value).  With the m finite values sorted, u_(1) <= ... <= u_(m), it is
+    max_i max(i / m - u_(i), u_(i) - (i - 1) / m).  NaN where no value is finite."""
+    u = np.asarray(truth_cdf, dtype=np.float64)
+    flat = u.reshape(u.shape[0], -1)
+    out = np.full(flat.shape[1], np.nan)
+    for c in range(flat.shape[1]):
+        v = np.sort(flat[np.isfinite(flat[:, c]), c])
+        m = v.size
+        if m:
+            i = np.arange(1, m + 1, dtype=np.float64)
+            out[c] = max(np.max(i / m - v), np.max(v - (i - 1) / m))
+    return out.reshape(u.shape[1:])
 
 
 def particle_ranking_simple(X_orig, Y_orig, target_values, K=None, details=False, ctx=None):

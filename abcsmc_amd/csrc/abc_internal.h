@@ -283,11 +283,13 @@ int launch_rank_targets_adjust(abc_ctx*, const double* X, size_t ldx, const doub
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
                                struct abc_adj_keep* keep = nullptr);
 // tolerance path (adjust.hip): the ranking at K = path->Ks[T - 1], then the rejection mean and the regression at every tolerance;
-// path: Ks in host memory, the outputs device pointers; dist may be NULL
+// path: Ks in host memory, the outputs device pointers; dist may be NULL.  keep (optional): the fit is made whatever outputs path
+// names, and keep receives what a reader of the adjusted rows needs, with coef B x T x (A + 1) x P and dist B x K_max
 size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T);
 int launch_rank_targets_path(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                             bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path);
+                             bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path,
+                             struct abc_adj_keep* keep = nullptr);
 // weighted posterior quantiles and CDF (summary.hip).  abc_summary_need: workspace of launch_summary for B segment groups of P
 // segments of K values.  SmValues: how the values and weights of segment (b, j) are made (method 0 / 1: the ranking's rows,
 // method 2: V and w); sum: probs in host memory, truth / quant / cdf in device memory.
@@ -305,6 +307,10 @@ struct SmValues {
 };
 size_t abc_summary_need(size_t B, size_t K, size_t P);
 int launch_summary(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_summary* sum);
+// the summaries at every tolerance of a path (Ks: T ascending tolerances, host): sv describes the ranking at K_max = Ks[T - 1] (idx
+// and, method 1, adj->dist with that row stride; adj->coef B x T x (A + 1) x P); quant B x T x nq x P, cdf B x T x P, truth B x P
+size_t abc_path_summary_need(size_t B, const size_t* Ks, size_t T, size_t P, int method);
+int launch_path_summary(abc_ctx*, const SmValues& sv, size_t B, const size_t* Ks, size_t T, size_t P, const abc_summary* sum);
 // generic weights (device): ABC_ERR_INVALID when one is negative or non-finite or all are zero (synchronises)
 int abc_summary_check_weights(abc_ctx*, const double* w, size_t K, const char* fn);
 // weighted posterior densities and modes (density.hip) of the same segments: the quantiles it needs come from launch_summary.

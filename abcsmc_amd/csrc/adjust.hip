@@ -638,7 +638,7 @@ size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T)
 
 int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                             bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path) {
+                             bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path, abc_adj_keep* keep) {
     const int T = (int)path->T, Pi = (int)P;
     AjKs ks = {};
     for (int t = 0; t < T; t++) ks.K[t] = path->Ks[t];
@@ -647,7 +647,7 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
     if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
     abc_tg_scores sc;
     ABC_TRY(launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, idx, d, nullptr, &sc));
-    const bool fit = path->coef || path->rank || path->status;
+    const bool fit = path->coef || path->rank || path->status || keep;
     if (!fit && !path->post_mean && !path->h) return ABC_OK;
 
     AjSrc src;                                                       // without the fit: the parameters only
@@ -713,6 +713,14 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
                                (const double*)d, K, ks, T, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch,
                                b0, coef, path->rank, path->status);
             ABC_HIP(ctx, hipGetLastError());
+        }
+        if (keep) {
+            keep->src = src;
+            keep->O = sc.O;
+            keep->KCO = sc.KCO;
+            keep->nc = nc;
+            keep->coef = coef;
+            keep->dist = d;
         }
     }
     if (path->post_mean || path->h) {

@@ -1191,7 +1191,7 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
 // ---- batched ranking of many observed targets against one fitted set (targets.hip), optionally followed by the local-linear
 // adjustment (adjust.hip) or by a posterior product of every target's retained rows: the weighted quantiles and CDF (summary.hip),
 // the densities and modes (density.hip), the joint moments and pair densities (joint.hip) or the posterior draws (draws.hip).  One
-// pipeline (tg_*) behind the twelve entry points of the family and one pair of paths (weighted_dev, weighted_host) behind the eight
+// pipeline (tg_*) behind the fourteen entry points of the family and one pair of paths (weighted_dev, weighted_host) behind the eight
 // abc_weighted_* entries, which
 // compute the same products from given values; what differs between the products is in Product ----
 static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
@@ -1422,16 +1422,17 @@ struct TgRequest {                             // (members in the order of the e
     const double* targets;  size_t ldt, B;
     const uint64_t* exclude;
     size_t K;                                  // TG_PATH: set by tg_check to the largest tolerance
-    uint64_t* idx;                             // optional for TG_PRODUCT
+    uint64_t* idx;                             // optional for TG_PRODUCT and a path with summaries
     double* dist;                              // optional
     double* post_mean = nullptr;               // TG_PLAIN only, optional
     int method = 0, kernel = 0;                // method: TG_PRODUCT only (of which values the segments are)
     const abc_adjust_out* adj = nullptr;       // TG_ADJUST: required, any member may be NULL; TG_PRODUCT: optional, method 1 only
-    Product prod;                              // TG_PRODUCT only
+    Product prod;                              // TG_PRODUCT; TG_PATH: none or the summaries (method: of those)
     bool any_excl = false;                     // exclude names a row for some target: set by tg_check
     const abc_path* path = nullptr;            // TG_PATH only: required; Ks in host memory
     bool segments() const { return kind == TG_PRODUCT; }      // the rows' values are read after the ranking
     bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
+    bool path_summary() const { return kind == TG_PATH && prod.kind == Product::SUMMARY; }      // prod: the summaries at every tolerance
 };
 }  // namespace
 
@@ -1459,7 +1460,7 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
     const size_t N = r.N, B = r.B, K = r.K;
     if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
     if (!r.targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (targets is required)", fn);
-    if (!r.idx && !summary) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (idx is required)", fn);
+    if (!r.idx && !summary && !r.path_summary()) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (idx is required)", fn);
     if (!r.Y && (host || !plain)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (Y is required)", fn);
     if (!r.Y && r.post_mean && r.P) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: post_mean needs Y", fn);
     if (!host) {
@@ -1468,7 +1469,7 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
         if (r.ldx < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < N %zu", fn, r.ldx, N);
         if (r.ldt < B) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldt %zu < B %zu", fn, r.ldt, B);
     }
-    if (summary && r.method != ABC_POSTERIOR_REJECTION && r.method != ABC_POSTERIOR_LOCLINEAR)
+    if ((summary || r.path_summary()) && r.method != ABC_POSTERIOR_REJECTION && r.method != ABC_POSTERIOR_LOCLINEAR)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: method %d (0 = rejection, 1 = loclinear)", fn, r.method);
     if (r.kind == TG_ADJUST && !r.adj) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (out is required)", fn);
     if (!plain && r.kernel != ABC_KERNEL_EPANECHNIKOV && r.kernel != ABC_KERNEL_RECTANGULAR)
@@ -1479,6 +1480,8 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
         if (r.P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, r.P);
     }
     ABC_TRY(r.prod.check(ctx, fn, r.P));
+    if (r.path_summary() && !r.prod.sum->quant && !r.prod.sum->cdf)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: quant and cdf of sum are both NULL", fn);
     if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
     if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
     if (r.M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no metrics (M == 0)", fn);
@@ -1512,7 +1515,8 @@ static size_t tg_need(const TgRequest& r, bool host, int rule) {
     if (r.regress()) b += abc_adjust_need(N, A, P, B, K);
     if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T);
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
-    b += r.prod.need(B, K, P);
+    if (r.path_summary()) b += abc_path_summary_need(B, r.path->Ks, r.path->T, P, r.method) + (r.idx ? 0 : B * K * 8 + 256);
+    else b += r.prod.need(B, K, P);
     if (!host) return b + abc_ws_need(N, 1, 1, 1, K + 1, 0, 0);
     b += abc_ws_need(N, M, P, A, K + 1, 0, 0) + (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0);
     b += (N * (M + P) + M + 4) * 8;                                               // X, Y, the zero observation and its one idx, dist
@@ -1520,6 +1524,7 @@ static size_t tg_need(const TgRequest& r, bool host, int rule) {
     if (r.kind == TG_PLAIN) b += B * P * 8;                                       // post_mean
     else if (r.kind == TG_PATH) b += B * r.path->T * ((A + 2) * P + 2) * 8 + 8 * 256;      // abc_path: post_mean, coef, rank + status, h
     else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
+    if (r.path_summary()) return b + B * P * (r.path->T * (r.prod.sum->nq + 1) + 1) * 8 + 16 * 256;     // truth, quant, cdf
     return b + r.prod.stage_bytes(B, P);
 }
 
@@ -1534,9 +1539,26 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
         if (!d) d = (double*)abc_ws_alloc(ctx, B * K * 8);
         if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     }
-    if (r.kind == TG_PATH)
-        return launch_rank_targets_path(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                        r.any_excl, r.kernel, ix, d, r.path);
+    if (r.kind == TG_PATH) {
+        const bool ps = r.path_summary(), lin = ps && r.method == ABC_POSTERIOR_LOCLINEAR;
+        if (ps && !ix) {
+            ix = (uint64_t*)abc_ws_alloc(ctx, B * K * 8);
+            if (!ix) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+        }
+        abc_adj_keep pk;
+        ABC_TRY(launch_rank_targets_path(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
+                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr));
+        if (!ps) return ABC_OK;
+        SmValues pv = {};
+        pv.method = r.method;
+        pv.idx = ix;
+        pv.Y = r.Y;
+        pv.ldy = r.ldy;
+        pv.adj = lin ? &pk : nullptr;
+        pv.A = (int)r.A;
+        pv.kernel = r.kernel;
+        return launch_path_summary(ctx, pv, B, r.path->Ks, r.path->T, r.P, r.prod.sum);
+    }
     abc_adj_keep keep;
     if (!r.regress()) {     // (post_mean: of the plain ranking only)
         ABC_TRY(launch_rank_targets(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
@@ -1618,7 +1640,18 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         pd.h = h.path->h ? s.dev<double>(B * T) : nullptr;
         r.path = &pd;
     }
-    r.prod = h.prod.stage(s, B, P);
+    abc_summary psd = {};
+    if (h.path_summary()) {     // (truth per target, the outputs per target and tolerance)
+        const abc_summary* sh = h.prod.sum;
+        const size_t T = h.path->T;
+        psd = *sh;
+        psd.truth = sh->truth ? s.up(sh->truth, B * P) : nullptr;
+        psd.quant = sh->quant ? s.dev<double>(B * T * sh->nq * P) : nullptr;
+        psd.cdf = sh->cdf ? s.dev<double>(B * T * P) : nullptr;
+        r.prod = Product(&psd);
+    } else {
+        r.prod = h.prod.stage(s, B, P);
+    }
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_TRY(tg_run(ctx, fn, r));
     s.down(h.idx, r.idx, B * K);
@@ -1639,7 +1672,12 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         s.down(h.path->status, pd.status, B * T);
         s.down(h.path->h, pd.h, B * T);
     }
-    h.prod.down(s, B, P);
+    if (h.path_summary()) {
+        s.down(h.prod.sum->quant, psd.quant, B * h.path->T * h.prod.sum->nq * P);
+        s.down(h.prod.sum->cdf, psd.cdf, B * h.path->T * P);
+    } else {
+        h.prod.down(s, B, P);
+    }
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
@@ -1697,6 +1735,29 @@ extern "C" int abc_particle_ranking_pls_targets_path(abc_ctx* ctx, const double*
     TgRequest h{TG_PATH, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, 0, idx, dist, nullptr, 0, kernel};
     h.path = path;
     return tg_host(ctx, "abc_particle_ranking_pls_targets_path", h, train_frac, max_comp, rule, ncomp);
+}
+
+extern "C" int abc_rank_targets_path_summary_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N,
+                                                 size_t M, size_t P, const double* model, size_t A, const double* targets, size_t ldt,
+                                                 size_t B, const uint64_t* exclude, int method, int kernel, uint64_t* idx, double* dist,
+                                                 const abc_path* path, const abc_summary* sum) {
+    CHECK_CTX(ctx);
+    TgRequest r{TG_PATH, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, 0, idx, dist, nullptr, method, kernel, nullptr,
+                Product(sum)};
+    r.path = path;
+    return tg_dev(ctx, "abc_rank_targets_path_summary_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_path_summary(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M,
+                                                             size_t P, const double* targets, size_t B, double train_frac,
+                                                             int max_comp, int rule, const uint64_t* exclude, int method, int kernel,
+                                                             uint64_t* idx, double* dist, const abc_path* path,
+                                                             const abc_summary* sum, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    TgRequest h{TG_PATH, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, 0, idx, dist, nullptr, method, kernel, nullptr,
+                Product(sum)};
+    h.path = path;
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_path_summary", h, train_frac, max_comp, rule, ncomp);
 }
 
 extern "C" int abc_rank_targets_summary_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,

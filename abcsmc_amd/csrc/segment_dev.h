@@ -12,7 +12,7 @@
 // summaries' own inputs and outputs (summary.hip), NULL elsewhere
 struct SmArgs {
     int method;                 // 0 rejection, 1 loclinear, 2 generic
-    const uint64_t* idx;        // B x K
+    const uint64_t* idx;        // B rows of ld entries, the first K of a row are the segment's
     const double* Y;
     size_t ldy;
     AjSrc src;                  // method 1: as launch_rank_targets_adjust read the rows
@@ -23,14 +23,17 @@ struct SmArgs {
     const double* V;            // method 2
     size_t ldv;
     const double* w;
-    size_t K;
+    size_t K;                   // entries of a segment (a tolerance path: K_t)
+    size_t ld;                  // row stride of idx and dist (K; a tolerance path: K_max)
+    int T, t;                   // tolerance t of T (1, 0 outside a path): coefficients and outputs at slot b T + t
     const double* truth;        // B x P (device)
-    double* quant;              // B x nq x P
-    double* cdf;                // B x P
+    double* quant;              // B x T x nq x P
+    double* cdf;                // B x T x P
 };
 
 struct SmSeg {
     size_t b;
+    size_t slot;                // b T + t: where the segment's coefficients and outputs are
     int j;
     const uint64_t* ix;
     const double* dd;
@@ -63,24 +66,28 @@ static inline SmArgs sm_args(const SmValues& sv, size_t K, size_t P) {
     a.ldv = sv.ldv;
     a.w = sv.w;
     a.K = K;
+    a.ld = K;
+    a.T = 1;
+    a.t = 0;
     return a;
 }
 
 __device__ __forceinline__ SmSeg sm_seg(const SmArgs& a, size_t b, int j) {
     SmSeg s;
     s.b = b;
+    s.slot = b * (size_t)a.T + (size_t)a.t;
     s.j = j;
-    s.ix = a.idx ? a.idx + b * a.K : nullptr;
+    s.ix = a.idx ? a.idx + b * a.ld : nullptr;
     s.dd = nullptr;
     s.h = 0.0;
     s.rect = true;
     s.beta = nullptr;
     s.ob = nullptr;
     if (a.method == 1) {
-        s.dd = a.dist + b * a.K;
+        s.dd = a.dist + b * a.ld;
         s.h = s.dd[a.K - 1];
         s.rect = a.kernel == 1 || aj_fallback(s.dd, a.K);
-        s.beta = a.coef + b * (size_t)(a.A + 1) * a.P + a.P + j;
+        s.beta = a.coef + s.slot * (size_t)(a.A + 1) * a.P + a.P + j;
         s.ob = a.O + b * (size_t)a.KCO;
     }
     return s;

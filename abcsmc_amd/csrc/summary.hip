@@ -13,6 +13,14 @@
 // The sums run in an order fixed by the tile (SM_TILE entries, SM_PER consecutive ones per thread, a fixed scan and tree over the
 // threads, tiles in order) and nothing else, so both paths give the same bits for any weights, a target's bits do not depend on the
 // batch, and no floating-point atomics are involved.
+//
+// Tolerance paths (abc_rank_targets_path_summary_dev).  Under rejection the values do not depend on the tolerance and the tie-break
+// is the entry number, so the (key, e) list sorted at K_max, filtered by e < K_t, is the sorted segment at K_t: ONE sort per
+// (target, parameter), then k_smp_lds / k_smp_eval_global walk the tolerances from the largest down, evaluate the n = K_t dense
+// entries and compact them (stable, by an integer count scan) to those with e < K_{t-1}.  With unit weights sm_eval's knot numerator
+// of rank r is exactly r + 0.5 and W = n, so no H array is kept; the expressions are sm_eval's.  Under loclinear the values change
+// with the tolerance (its own beta): segment (b, t, j) goes through the kernels above with K = K_t, the row stride K_max and the
+// coefficient and output slot b T + t (SmArgs ld, T, t).
 #include <math.h>
 
 #include "abc_internal.h"
@@ -166,9 +174,9 @@ __device__ void sm_eval(const SmArgs& a, const SmSeg& s, const SmProbs& pr, cons
             const double ulo = sm_unkey(key[lo]), uhi = sm_unkey(key[hi]);
             res = fma(tt, uhi - ulo, ulo);
         }
-        if (a.quant) a.quant[(s.b * (size_t)pr.nq + qi) * a.P + s.j] = res;
+        if (a.quant) a.quant[(s.slot * (size_t)pr.nq + qi) * a.P + s.j] = res;
     }
-    if (a.cdf && t == 0) a.cdf[s.b * a.P + s.j] = (bad || n == 0 || isnan(tau)) ? nan : fma(0.5, E, L) / W;
+    if (a.cdf && t == 0) a.cdf[s.slot * a.P + s.j] = (bad || n == 0 || isnan(tau)) ? nan : fma(0.5, E, L) / W;
 }
 
 // LDS path: grid (P, targets b0 + blockIdx.y); dynamic LDS 16 n2 bytes: keys (8 n2), then e (4 n2) overlaid by H (8 n2)
@@ -246,6 +254,187 @@ __global__ __launch_bounds__(SM_BS) void k_sm_eval_global(SmArgs a, SmProbs pr, 
     sm_eval(a, s, pr, gkey + seg * a.K, gid + seg * a.K, gH + seg * a.K, (size_t)cnt[seg], bad[seg] != 0, red);
 }
 
+// ---- tolerance path, rejection: one sort at K_max, every tolerance from it ----
+constexpr int SM_MAXT = 16;
+struct SmKs {
+    size_t K[SM_MAXT];
+    int T;
+};
+
+// the outputs of one tolerance from its n sorted entries key[0..n), all of weight 1: sm_eval's expressions with H[r] = r + 0.5 and
+// W = n (both exact); L, E: the entries below and equal to tau, nf: the non-finite ones
+__device__ void smp_out(const SmArgs& a, const SmSeg& s, const SmProbs& pr, const unsigned long long* key, size_t n, bool bad, double L,
+                        double E, double tau) {
+    const int t = threadIdx.x;
+    const double W = (double)n;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int qi = t; qi < pr.nq; qi += SM_BS) {
+        const double q = pr.q[qi];
+        double res;
+        if (bad || n == 0) {
+            res = nan;
+        } else if (q <= 0.5 / W) {
+            res = sm_unkey(key[0]);
+        } else if (q >= ((double)(n - 1) + 0.5) / W) {
+            res = sm_unkey(key[n - 1]);
+        } else {                                               // p_lo <= q < p_hi
+            size_t lo = 0, hi = n - 1;
+            while (hi - lo > 1) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (((double)mid + 0.5) / W <= q) lo = mid; else hi = mid;
+            }
+            const double plo = ((double)lo + 0.5) / W, phi = ((double)hi + 0.5) / W;
+            const double tt = (q - plo) / (phi - plo);
+            const double ulo = sm_unkey(key[lo]), uhi = sm_unkey(key[hi]);
+            res = fma(tt, uhi - ulo, ulo);
+        }
+        if (a.quant) a.quant[(s.slot * (size_t)pr.nq + qi) * a.P + s.j] = res;
+    }
+    if (a.cdf && t == 0) a.cdf[s.slot * a.P + s.j] = (bad || n == 0 || isnan(tau)) ? nan : fma(0.5, E, L) / W;
+}
+
+// exclusive offset of this thread's count c among the work-group's (wave scan, then the waves' sums through ws); *total: all of them.
+// Two barriers: ws may be written again after the return.
+__device__ __forceinline__ unsigned smp_scan(unsigned c, unsigned* ws, unsigned* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned inc = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) ws[wave] = inc;
+    __syncthreads();
+    unsigned off = inc - c, tot = 0;
+    for (int w = 0; w < SM_BS / 64; w++) {
+        const unsigned v = ws[w];
+        if (w < wave) off += v;
+        tot += v;
+    }
+    __syncthreads();
+    *total = tot;
+    return off;
+}
+
+// LDS path of the tolerance path: grid (P, targets b0 + blockIdx.y); a.K = K_max; dynamic LDS 12 n2 bytes: keys (8 n2), then e (4 n2)
+__global__ __launch_bounds__(SM_BS) void k_smp_lds(SmArgs a, SmProbs pr, SmKs ks, int n2, size_t b0) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long smk[];
+    __shared__ unsigned s_cnt, s_ws[SM_BS / 64], s_L, s_E, s_nf;
+    __shared__ int s_bad;
+    unsigned long long* key = smk;
+    unsigned* id = (unsigned*)(smk + n2);
+    const int t = threadIdx.x;
+    if (t == 0) { s_cnt = 0; s_bad = 0; }
+    __syncthreads();
+    SmSeg s = sm_seg(a, b0 + blockIdx.y, (int)blockIdx.x);
+    sm_build_sort(a, s, 0, (int)a.K, n2, key, id, &s_cnt, &s_bad);
+    const double tau = a.cdf ? a.truth[s.b * a.P + s.j] : 0.0;
+    for (int ti = ks.T - 1; ti >= 0; ti--) {
+        const unsigned n = (unsigned)ks.K[ti], keep = ti > 0 ? (unsigned)ks.K[ti - 1] : 0u;
+        if (t == 0) { s_L = 0; s_E = 0; s_nf = 0; }
+        __syncthreads();
+        unsigned long long kr[SM_PER];
+        unsigned ir[SM_PER];
+        unsigned c = 0, lt = 0, eq = 0, nf = 0;
+#pragma unroll
+        for (int q = 0; q < SM_PER; q++) {
+            const unsigned r = (unsigned)t * SM_PER + q;
+            kr[q] = SM_PAD_KEY;
+            ir[q] = SM_PAD_ID;
+            if (r < n) {
+                kr[q] = key[r];
+                ir[q] = id[r];
+                const double u = sm_unkey(kr[q]);
+                if (!isfinite(u)) nf++;
+                if (u < tau) lt++;
+                else if (u == tau) eq++;
+                if (ir[q] < keep) c++;
+            }
+        }
+        if (lt) atomicAdd(&s_L, lt);
+        if (eq) atomicAdd(&s_E, eq);
+        if (nf) atomicAdd(&s_nf, nf);
+        unsigned total;
+        unsigned pos = smp_scan(c, s_ws, &total);              // (its barriers: the counts above are complete)
+        s.slot = s.b * (size_t)ks.T + (size_t)ti;
+        smp_out(a, s, pr, key, (size_t)n, s_nf != 0, (double)s_L, (double)s_E, tau);
+        __syncthreads();                                       // every key of this tolerance read before the next one's are written
+        if (ti > 0) {
+#pragma unroll
+            for (int q = 0; q < SM_PER; q++)
+                if (ir[q] < keep) {                            // (padding: SM_PAD_ID, never below keep)
+                    key[pos] = kr[q];
+                    id[pos] = ir[q];
+                    pos++;
+                }
+        }
+        __syncthreads();
+    }
+}
+
+// global path of the tolerance path: grid (P, batch targets); (k0, i0): the segments' sorted entries at a.K = K_max, (k1, i1): the
+// other pair of buffers; the tolerances' dense lists alternate between the two
+__global__ __launch_bounds__(SM_BS) void k_smp_eval_global(SmArgs a, SmProbs pr, SmKs ks, size_t b0, unsigned long long* k0, unsigned* i0,
+                                                           unsigned long long* k1, unsigned* i1) {
+    __shared__ unsigned s_ws[SM_BS / 64];
+    __shared__ unsigned long long s_L, s_E, s_nf;
+    const int t = threadIdx.x, j = (int)blockIdx.x;
+    const size_t bl = blockIdx.y, seg = bl * a.P + j;
+    SmSeg s = sm_seg(a, b0 + bl, j);
+    unsigned long long *ks_ = k0 + seg * a.K, *kd = k1 + seg * a.K;
+    unsigned *is = i0 + seg * a.K, *idd = i1 + seg * a.K;
+    const double tau = a.cdf ? a.truth[s.b * a.P + s.j] : 0.0;
+    for (int ti = ks.T - 1; ti >= 0; ti--) {
+        const size_t n = ks.K[ti], keep = ti > 0 ? ks.K[ti - 1] : 0;
+        if (t == 0) { s_L = 0; s_E = 0; s_nf = 0; }
+        __syncthreads();
+        unsigned long long lt = 0, eq = 0, nf = 0;
+        size_t carry = 0;
+        for (size_t base = 0; base < n; base += SM_TILE) {
+            const size_t r0 = base + (size_t)t * SM_PER;
+            unsigned long long kr[SM_PER];
+            unsigned ir[SM_PER];
+            unsigned c = 0;
+#pragma unroll
+            for (int q = 0; q < SM_PER; q++) {
+                const size_t r = r0 + q;
+                kr[q] = SM_PAD_KEY;
+                ir[q] = SM_PAD_ID;
+                if (r < n) {
+                    kr[q] = ks_[r];
+                    ir[q] = is[r];
+                    const double u = sm_unkey(kr[q]);
+                    if (!isfinite(u)) nf++;
+                    if (u < tau) lt++;
+                    else if (u == tau) eq++;
+                    if ((size_t)ir[q] < keep) c++;
+                }
+            }
+            if (ti > 0) {                                      // (uniform) the kept entries of the tile, in order, behind the earlier tiles'
+                unsigned total;
+                size_t pos = carry + smp_scan(c, s_ws, &total);
+#pragma unroll
+                for (int q = 0; q < SM_PER; q++)
+                    if ((size_t)ir[q] < keep) {
+                        kd[pos] = kr[q];
+                        idd[pos] = ir[q];
+                        pos++;
+                    }
+                carry += total;
+            }
+        }
+        if (lt) atomicAdd(&s_L, lt);
+        if (eq) atomicAdd(&s_E, eq);
+        if (nf) atomicAdd(&s_nf, nf);
+        __syncthreads();
+        s.slot = s.b * (size_t)ks.T + (size_t)ti;
+        smp_out(a, s, pr, ks_, n, s_nf != 0, (double)s_L, (double)s_E, tau);
+        __syncthreads();                                       // (also: the next tolerance's list is written)
+        unsigned long long* tk = ks_; ks_ = kd; kd = tk;
+        unsigned* tq = is; is = idd; idd = tq;
+    }
+}
+
 // generic weights: flags[0] |= 1 for a negative or non-finite weight, flags[1] |= 1 for a positive one
 __global__ __launch_bounds__(256) void k_sm_wcheck(const double* __restrict__ w, size_t K, int* __restrict__ flags) {
     int neg = 0, pos = 0;
@@ -286,25 +475,30 @@ size_t abc_summary_need(size_t B, size_t K, size_t P) {
     return b;
 }
 
-int launch_summary(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const abc_summary* sum) {
-    if ((!sum->quant && !sum->cdf) || B == 0 || K == 0 || P == 0) return ABC_OK;
-    SmArgs a = sm_args(sv, K, P);
-    a.truth = sum->truth;
-    a.quant = sum->quant;
-    a.cdf = sum->cdf;
+namespace {
+
+SmProbs sm_probs(const abc_summary* sum) {
     SmProbs pr;
     memset(&pr, 0, sizeof(pr));
     pr.nq = (int)sum->nq;
     for (size_t q = 0; q < sum->nq; q++) pr.q[q] = sum->probs[q];
+    return pr;
+}
 
+// the B x a.P segments of a.K entries: sort and evaluation; ks: the tolerances of a rejection path (every one evaluated from the one
+// sort at a.K = K_max), NULL otherwise
+int sm_launch(abc_ctx* ctx, const SmArgs& a, const SmProbs& pr, size_t B, const SmKs* ks) {
+    const size_t K = a.K, P = (size_t)a.P;
     if (sm_use_lds(K)) {
         int n2 = 1;
         while ((size_t)n2 < K) n2 <<= 1;
-        const size_t lds = (size_t)n2 * 16;
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_sm_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const size_t lds = (size_t)n2 * (ks ? 12 : 16);
+        ABC_HIP(ctx, hipFuncSetAttribute(ks ? (const void*)k_smp_lds : (const void*)k_sm_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)lds));
         for (size_t b0 = 0; b0 < B; b0 += SM_MAX_GRID_Y) {
             const size_t nb = (B - b0 < SM_MAX_GRID_Y) ? B - b0 : SM_MAX_GRID_Y;
-            hipLaunchKernelGGL(k_sm_lds, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, n2, b0);
+            if (ks) hipLaunchKernelGGL(k_smp_lds, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, *ks, n2, b0);
+            else hipLaunchKernelGGL(k_sm_lds, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, n2, b0);
             ABC_HIP(ctx, hipGetLastError());
         }
         return ABC_OK;
@@ -338,9 +532,59 @@ int launch_summary(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t 
             unsigned long long* tk = ka; ka = kb; kb = tk;
             unsigned* ti = ia; ia = ib; ib = ti;
         }
-        hipLaunchKernelGGL(k_sm_eval_global, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), 0, ctx->stream, a, pr, b0,
-                           (const unsigned long long*)ka, (const unsigned*)ia, (double*)kb, (const unsigned*)cnt, (const int*)bad);
+        if (ks)
+            hipLaunchKernelGGL(k_smp_eval_global, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), 0, ctx->stream, a, pr, *ks, b0, ka, ia, kb,
+                               ib);
+        else
+            hipLaunchKernelGGL(k_sm_eval_global, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), 0, ctx->stream, a, pr, b0,
+                               (const unsigned long long*)ka, (const unsigned*)ia, (double*)kb, (const unsigned*)cnt, (const int*)bad);
         ABC_HIP(ctx, hipGetLastError());
+    }
+    return ABC_OK;
+}
+
+}  // namespace
+
+int launch_summary(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const abc_summary* sum) {
+    if ((!sum->quant && !sum->cdf) || B == 0 || K == 0 || P == 0) return ABC_OK;
+    SmArgs a = sm_args(sv, K, P);
+    a.truth = sum->truth;
+    a.quant = sum->quant;
+    a.cdf = sum->cdf;
+    return sm_launch(ctx, a, sm_probs(sum), B, nullptr);
+}
+
+size_t abc_path_summary_need(size_t B, const size_t* Ks, size_t T, size_t P, int method) {
+    if (method == 0) return abc_summary_need(B, Ks[T - 1], P);       // the one sort at K_max
+    size_t b = 0;
+    for (size_t t = 0; t < T; t++) {                                 // one tolerance's launch set at a time
+        const size_t bt = abc_summary_need(B, Ks[t], P);
+        if (bt > b) b = bt;
+    }
+    return b;
+}
+
+int launch_path_summary(abc_ctx* ctx, const SmValues& sv, size_t B, const size_t* Ks, size_t T, size_t P, const abc_summary* sum) {
+    if ((!sum->quant && !sum->cdf) || B == 0 || P == 0) return ABC_OK;
+    SmArgs a = sm_args(sv, Ks[T - 1], P);                            // ld = K_max
+    a.truth = sum->truth;
+    a.quant = sum->quant;
+    a.cdf = sum->cdf;
+    a.T = (int)T;
+    const SmProbs pr = sm_probs(sum);
+    if (sv.method == 0) {
+        SmKs ks = {};
+        ks.T = (int)T;
+        for (size_t t = 0; t < T; t++) ks.K[t] = Ks[t];
+        a.t = (int)T - 1;
+        return sm_launch(ctx, a, pr, B, &ks);
+    }
+    for (size_t t = 0; t < T; t++) {
+        a.K = Ks[t];
+        a.t = (int)t;
+        const size_t mark = ctx->ws_off;                             // (stream order: a tolerance's buffers are free for the next)
+        ABC_TRY(sm_launch(ctx, a, pr, B, nullptr));
+        ctx->ws_off = mark;
     }
     return ABC_OK;
 }

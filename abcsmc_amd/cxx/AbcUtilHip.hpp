@@ -456,6 +456,58 @@ inline std::vector<TargetSummary> particle_ranking_PLS_targets_summary(const Mat
     }
     return res;
 }
+// The tolerance path with the summaries at every tolerance (abc_particle_ranking_pls_targets_path_summary): one ranking at
+// K_max = Ks.back(), the path's outputs, and the quantiles and CDF of particle_ranking_PLS_targets_summary at every Ks[t] (bit for
+// bit under method 0, from one sort per target and parameter).  Per target: the TargetPath fields, quant (T x nq x P: row t * nq + q
+// = level probs[q] at tolerance t) and cdf (T x P; 0 x 0 without truth).
+struct TargetPathSummary : TargetPath {
+    Mat2D quant, cdf;
+};
+inline std::vector<TargetPathSummary> particle_ranking_PLS_targets_path_summary(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                                const float_type train_frac,
+                                                                                const std::vector<size_t>& Ks,
+                                                                                const std::vector<double>& probs,
+                                                                                const Mat2D* truth = nullptr, int method = 0,
+                                                                                int kernel = 0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols(), T = Ks.size(), K = T ? Ks.back() : 0, nq = probs.size();
+    if (truth && (truth->rows() != B || truth->cols() != P)) throw HipError(ABC_ERR_INVALID, "truth must be B x P");
+    const int mc = max_components_ref();
+    const size_t A = mc > 0 ? (size_t)mc : (M < P ? M : P);
+    std::vector<uint64_t> idx(B * K);
+    std::vector<double> pm(B * T * P), cf(B * T * (A + 1) * P), h(B * T), tr, q(B * T * nq * P), cdf(truth ? B * T * P : 0);
+    std::vector<int32_t> rank(B * T), status(B * T);
+    if (truth) {
+        tr.resize(B * P);
+        for (size_t b = 0; b < B; b++)
+            for (size_t j = 0; j < P; j++) tr[b * P + j] = (*truth)(b, j);
+    }
+    abc_path path = {Ks.data(), T, pm.data(), cf.data(), rank.data(), status.data(), h.data()};
+    abc_summary sum = {probs.data(), nq, truth ? tr.data() : nullptr, q.data(), truth ? cdf.data() : nullptr};
+    check(abc_particle_ranking_pls_targets_path_summary(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac, mc,
+                                                        component_rule(), nullptr, method, kernel, idx.data(), nullptr, &path, &sum,
+                                                        nullptr));
+    std::vector<TargetPathSummary> res(B);
+    for (size_t b = 0; b < B; b++) {
+        TargetPathSummary& r = res[b];
+        r.idx.assign(idx.begin() + b * K, idx.begin() + (b + 1) * K);
+        r.post_mean = Mat2D(T, P);
+        r.alpha = Mat2D(T, P);
+        r.quant = Mat2D(T * nq, P);
+        if (truth) r.cdf = Mat2D(T, P);
+        for (size_t t = 0; t < T; t++)
+            for (size_t j = 0; j < P; j++) {
+                r.post_mean(t, j) = pm[(b * T + t) * P + j];
+                r.alpha(t, j) = cf[(b * T + t) * (A + 1) * P + j];
+                if (truth) r.cdf(t, j) = cdf[(b * T + t) * P + j];
+                for (size_t k = 0; k < nq; k++) r.quant(t * nq + k, j) = q[((b * T + t) * nq + k) * P + j];
+            }
+        r.h.assign(h.begin() + b * T, h.begin() + (b + 1) * T);
+        r.rank.assign(rank.begin() + b * T, rank.begin() + (b + 1) * T);
+        r.status.assign(status.begin() + b * T, status.begin() + (b + 1) * T);
+    }
+    return res;
+}
 // Weighted quantiles of every column of values (K x P; weights: K entries, or empty for equal weights, which gives NumPy's
 // "hazen" / R's type 5): nq x P, row q = level probs[q] (abc_weighted_summary).
 inline Mat2D weighted_quantiles(const Mat2D& values, const std::vector<double>& weights, const std::vector<double>& probs) {

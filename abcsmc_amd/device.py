@@ -184,6 +184,39 @@ def rank_targets_path(X, model, A, targets, Ks, Y, exclude=None, kernel=_lib.KER
     return r
 
 
+def rank_targets_path_summary(X, model, A, targets, Ks, Y, probs=(0.025, 0.5, 0.975), truth=None, method=_lib.POSTERIOR_REJECTION,
+                              kernel=_lib.KERNEL_EPANECHNIKOV, exclude=None, quant=True, post_mean=True, coef=True, fit=True,
+                              idx=True, dist=True, ctx=None):
+    """rank_targets_path with the summaries of rank_targets_summary at every tolerance (abc_rank_targets_path_summary_dev): one
+    ranking at K_max = Ks[-1] and, under rejection, one sort per (target, parameter) for all tolerances.  truth: (B, P) row-major
+    device tensor or None.  quant=False leaves the quantiles out (truth is then needed); fit=False leaves rank, status and h out,
+    idx=False the ranking.  Works on device tensors and copies nothing.  Returns rank_targets_path's dict (None for what was left
+    out) plus quant (B, T, nq, P) or None and cdf (B, T, P) or None."""
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
+    ks, K = _path_ks(Ks)
+    T = ks.size
+    f64, i32 = torch.float64, torch.int32
+    pr = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    if truth is not None:
+        truth = truth.to(device=dev, dtype=f64).contiguous()
+        assert truth.shape == (B, P)
+    r = dict(idx=torch.empty((B, K), dtype=torch.int64, device=dev) if idx else None,
+             dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None,
+             post_mean=torch.empty((B, T, P), dtype=f64, device=dev) if post_mean else None,
+             coef=torch.empty((B, T, A + 1, P), dtype=f64, device=dev) if coef else None,
+             rank=torch.empty((B, T), dtype=i32, device=dev) if fit else None,
+             status=torch.empty((B, T), dtype=i32, device=dev) if fit else None,
+             h=torch.empty((B, T), dtype=f64, device=dev) if fit else None,
+             quant=torch.empty((B, T, pr.size, P), dtype=f64, device=dev) if quant else None,
+             cdf=torch.empty((B, T, P), dtype=f64, device=dev) if truth is not None else None)
+    path = _lib.Path(ks.ctypes.data, T, _ptr(r["post_mean"]), _ptr(r["coef"]), _ptr(r["rank"]), _ptr(r["status"]), _ptr(r["h"]))
+    sm = _lib.Summary(pr.ctypes.data, pr.size, _ptr(truth), _ptr(r["quant"]), _ptr(r["cdf"]))
+    ctx.check(lib().abc_rank_targets_path_summary_dev(ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
+                                                      targets.data_ptr(), ldt, B, _ptr(exclude), int(method), int(kernel),
+                                                      _ptr(r["idx"]), _ptr(r["dist"]), C.byref(path), C.byref(sm)))
+    return r
+
+
 def _rank_targets_product(product, make, X, model, A, targets, K, Y, method, kernel, exclude, dist, adjust, ctx):
     """The call of rank_targets_{summary,density,joint,draws}.  make(lead, P, dev) -> (the product's struct, its outputs as a dict, what
     must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and the adjust members added."""

@@ -499,6 +499,35 @@ int abc_particle_ranking_pls_targets_summary(abc_ctx* ctx, const double* X, cons
                                              const double* targets, size_t B, double train_frac, int max_comp, int rule,
                                              const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
                                              double* dist, const abc_adjust_out* adj, const abc_summary* sum, int32_t* ncomp);
+/* ---- tolerance path with summaries: weighted quantiles and the CDF at the truth at EVERY tolerance of one ranking -------------
+ * What a user needs to choose the tolerance by cross-validation with cv4abc's default statistic (the median) and by the coverage
+ * diagnostic (Prangle et al. 2014): the path call above and, from the same ranking at K_max, the summaries above at every K_t.
+ * path is required and carries Ks and T; its five outputs stay optional and receive the bits of abc_rank_targets_path_dev for the
+ * same arguments, as do idx and dist (both optional here).  sum is the abc_summary above with truth B x P,
+ * quant B x T x nq x P ([b][t][q][j]) and cdf B x T x P; at least one of quant and cdf is required.
+ * Definition: segment (b, t, j) is the summaries' segment built on rows e = 0..K_t-1 of the ranking at K_max.
+ *   method 0: v_e = Y[i_e, j], w_e = 1.  The outputs are bit for bit those of abc_rank_targets_summary_dev with K = K_t.  (The
+ *             values do not depend on t and ties break by e, so the (value, e) list sorted once at K_max and filtered by e < K_t is
+ *             the sorted segment at K_t: one sort per (b, j) answers every tolerance.)
+ *   method 1: v_e = theta*_e[j] with the coefficients of (b, t), the bits that path->coef[b][t] holds or would hold, and
+ *             w_e = the adjustment's weight with h_t = d_{K_t-1}, the rectangular fallback evaluated on the first K_t distances as
+ *             the path does.  With Ks = {K} quant and cdf are the bits of abc_rank_targets_summary_dev with that K, method 1.
+ * Rows e >= K_t take no part in (b, t): a non-finite value in a farther row does not make a nearer tolerance NaN; one among the
+ * first K_t entries makes that (b, t, j) NaN and nothing else.
+ * Every reduction's order depends on (K_max, K_t, nc, P) only: (b, t) gives the same bits alone, in any batch, through either
+ * entry, whatever the other tolerances of the list (given K_max) and whichever outputs are asked for.
+ * Errors: the path's and the summaries' own, and ABC_ERR_INVALID for a NULL sum and for quant and cdf both NULL.  Limits:
+ * A <= 64, P <= 1024, T <= 16, nq <= 64.  The caller sizes the outputs; nothing of size B K P is written. */
+int abc_rank_targets_path_summary_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                      size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                      const uint64_t* exclude, int method, int kernel, uint64_t* idx, double* dist,
+                                      const abc_path* path, const abc_summary* sum);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_path); every array of path and sum in host memory. */
+int abc_particle_ranking_pls_targets_path_summary(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                  const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                  const uint64_t* exclude, int method, int kernel, uint64_t* idx, double* dist,
+                                                  const abc_path* path, const abc_summary* sum, int32_t* ncomp);
+
 /* The same summaries of P given columns of K values (V[e + ldv j], device memory; w: K weights or NULL; truth, quant and cdf in
  * device memory).  ABC_ERR_INVALID also for K = 0, P = 0, ldv < K, NULL V, and weights that are negative, non-finite or all
  * zero (checked on the device; the call synchronises). */
