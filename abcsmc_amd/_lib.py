@@ -24,6 +24,8 @@ ALIAS_DEVICE, ALIAS_HOST = 0, 1
 KERNEL_EPANECHNIKOV, KERNEL_RECTANGULAR = 0, 1
 ADJ_STATUS_SKIPPED, ADJ_STATUS_RECTANGULAR = 1, 2
 POSTERIOR_REJECTION, POSTERIOR_LOCLINEAR = 0, 1
+TRANSF_NONE, TRANSF_LOG, TRANSF_LOGIT = 0, 1, 2
+TRANSF_KINDS = {"none": TRANSF_NONE, "log": TRANSF_LOG, "logit": TRANSF_LOGIT}
 
 
 class LibraryMissing(ImportError):
@@ -76,6 +78,31 @@ class Path(C.Structure):
     """abc_path: Ks (host memory, T strictly ascending tolerances); every output pointer optional (None: not written)"""
     _fields_ = [("Ks", C.c_void_p), ("T", C.c_size_t), ("post_mean", C.c_void_p), ("coef", C.c_void_p), ("rank", C.c_void_p),
                 ("status", C.c_void_p), ("h", C.c_void_p)]
+
+
+class ParamTransf(C.Structure):
+    """abc_param_transf_t: P kinds (host int32) and the logit bounds lo / hi (host doubles, None when no kind is logit)"""
+    _fields_ = [("P", C.c_size_t), ("kind", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p)]
+
+
+def transf_arrays(kinds, lo=None, hi=None):
+    """A parameter-transform setting as host arrays (kind int32 (P,), lo (P,), hi (P,)): kinds holds TRANSF_* values or the names
+    "none" / "log" / "logit"; lo / hi are read for the logit entries (scalars broadcast) and are 0 elsewhere."""
+    import numpy as np
+    ks = [TRANSF_KINDS[k.lower()] if isinstance(k, str) and k.lower() in TRANSF_KINDS else k for k in kinds]
+    if any(isinstance(k, str) for k in ks):
+        raise ValueError("transf entries must be 'none', 'log' or 'logit'")
+    kind = np.ascontiguousarray(np.asarray(ks, dtype=np.int64).reshape(-1).astype(np.int32))
+    logit = kind == TRANSF_LOGIT
+    if logit.any() and (lo is None or hi is None):
+        raise ValueError("logit entries need bounds")
+    out = []
+    for b in (lo, hi):
+        v = np.zeros(kind.size)
+        if b is not None and logit.any():
+            v[logit] = np.broadcast_to(np.asarray(b, dtype=np.float64), kind.shape)[logit]
+        out.append(v)
+    return kind, out[0], out[1]
 
 
 class AdjustOut(C.Structure):
@@ -181,6 +208,10 @@ SIGNATURES = {
     "abc_particle_ranking_pls_targets": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "abc_rank_targets_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
     "abc_targets_fallbacks": (_i, [_vp, _vp, _i]),
+    "abc_ctx_set_param_transf": (_i, [_vp, _vp]),
+    "abc_param_transf_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _sz]),
+    "abc_param_transf": (_i, [_vp, _vp, _sz, _sz, _i, _vp]),
+    "abc_param_transf_outside": (_i, [_vp, _vp, _i]),
     "abc_rank_targets_adjust_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _vp, _vp,
                                          _vp]),
     "abc_particle_ranking_pls_targets_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _vp, _vp,
@@ -382,6 +413,42 @@ class Context:
         """targets the batched ranking recomputed by the exact single-target path (abc_targets_fallbacks)"""
         n = C.c_uint64(0)
         self.check(lib().abc_targets_fallbacks(self._h, C.byref(n), int(reset)))
+        return n.value
+
+    def set_param_transf(self, kinds=None, lo=None, hi=None):
+        """The parameter transforms of the local-linear adjustment (abc_ctx_set_param_transf; the definition is in the header):
+        kinds: one of "none" / "log" / "logit" (or TRANSF_*) per parameter, lo / hi: the logit entries' bounds.  None (or every
+        kind "none") turns them off.  The setting is copied; it applies to every call of this context that regresses."""
+        if kinds is None:
+            self.check(lib().abc_ctx_set_param_transf(self._h, None))
+            self._transf = None
+            return
+        kind, lo_a, hi_a = transf_arrays(kinds, lo, hi)
+        tf = ParamTransf(kind.size, kind.ctypes.data, lo_a.ctypes.data, hi_a.ctypes.data)
+        self.check(lib().abc_ctx_set_param_transf(self._h, C.byref(tf)))
+        self._transf = (kind, lo_a, hi_a) if (kind != TRANSF_NONE).any() else None
+
+    def param_transf(self, kinds=None, lo=None, hi=None):
+        """Context manager: set_param_transf(kinds, lo, hi) inside the block, what was set before (through this object) after it."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            before = getattr(self, "_transf", None)
+            self.set_param_transf(kinds, lo, hi)
+            try:
+                yield self
+            finally:
+                if before is None:
+                    self.set_param_transf(None)
+                else:
+                    self.set_param_transf(*before)
+        return scope()
+
+    def param_transf_outside(self, reset=False):
+        """entries the forward transforms found outside their domain (abc_param_transf_outside)"""
+        n = C.c_uint64(0)
+        self.check(lib().abc_param_transf_outside(self._h, C.byref(n), int(reset)))
         return n.value
 
     def set_alias_mode(self, mode):

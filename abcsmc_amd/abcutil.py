@@ -91,6 +91,90 @@ def _choice(what, value, table):
     return table[value]
 
 
+def _transf_kinds(transf, bounds, P):
+    """(kind int32 (P,), lo (P,), hi (P,)) of a transf / bounds pair: transf a sequence of "none" / "log" / "logit" of length P,
+    bounds (P, 2) read for the "logit" rows (None when there is none)"""
+    b = None if bounds is None else np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
+    kind, lo, hi = _lib.transf_arrays(transf, None if b is None else b[:, 0], None if b is None else b[:, 1])
+    if kind.size != P or (b is not None and b.shape[0] != P):
+        raise ValueError("transf needs one entry per parameter, bounds one row per parameter")
+    if np.any((kind < 0) | (kind > 2)):
+        raise ValueError("transf entries must be 'none', 'log' or 'logit'")
+    return kind, lo, hi
+
+
+def transform_params(Y, transf, bounds=None):
+    """The forward parameter transforms of the local-linear adjustment in NumPy (the definition is in the header, "log and logit
+    parameter transforms"): Y (..., P); "none": the value itself, bit for bit; "log": log(y) for finite y > 0, otherwise NaN (0
+    too); "logit": log((y - lo) / (hi - y)) for lo < y < hi, otherwise NaN.  Works in Y's floating type (float64 by default)."""
+    Y = np.asarray(Y)
+    if Y.dtype.kind != "f":
+        Y = Y.astype(np.float64)
+    kind, lo, hi = _transf_kinds(transf, bounds, Y.shape[-1])
+    T = Y.copy()
+    ft = Y.dtype.type
+    with np.errstate(all="ignore"):
+        for j in range(kind.size):
+            y = Y[..., j]
+            if kind[j] == _lib.TRANSF_LOG:
+                ok = (y > 0) & np.isfinite(y)
+                T[..., j] = np.where(ok, np.log(np.where(ok, y, 1)), np.nan)
+            elif kind[j] == _lib.TRANSF_LOGIT:
+                l, h = ft(lo[j]), ft(hi[j])
+                ok = (y > l) & (y < h)
+                ys = np.where(ok, y, (l + h) / 2)
+                T[..., j] = np.where(ok, np.log((ys - l) / (h - ys)), np.nan)
+    return T
+
+
+def untransform_params(T, transf, bounds=None):
+    """The back direction of transform_params: NaN stays NaN; "log": exp(t); "logit": s = 1 / (1 + exp(-t)), y = (hi - lo) s + lo
+    (one rounding, as fma) clamped to [lo, hi], so t = -inf gives lo and t = +inf gives hi; "none": the value itself."""
+    T = np.asarray(T)
+    if T.dtype.kind != "f":
+        T = T.astype(np.float64)
+    kind, lo, hi = _transf_kinds(transf, bounds, T.shape[-1])
+    Y = T.copy()
+    LD = np.longdouble
+    ft = T.dtype.type
+    with np.errstate(all="ignore"):
+        for j in range(kind.size):
+            t = T[..., j]
+            if kind[j] == _lib.TRANSF_LOG:
+                Y[..., j] = np.where(np.isnan(t), t, np.exp(t))
+            elif kind[j] == _lib.TRANSF_LOGIT:
+                l, h = ft(lo[j]), ft(hi[j])
+                s = 1 / (1 + np.exp(-t))
+                # fma(hi - lo, s, lo): the product of two float64 is exact in the 64-bit significand of x86's long double only up
+                # to a second rounding, so the sum is made there and rounded once more; where long double is float64 this is the
+                # plain expression
+                y = ((h - l).astype(LD) * s.astype(LD) + LD(l)).astype(T.dtype) if T.dtype == np.float64 else (h - l) * s + l
+                y = np.where(np.isposinf(t), h, np.where(np.isneginf(t), l, np.minimum(np.maximum(y, l), h)))
+                Y[..., j] = np.where(np.isnan(t), t, y)
+    return Y
+
+
+def _with_transf(ctx, transf, bounds, P, call):
+    """call() under the context's parameter transforms transf / bounds (None: whatever the context holds), restored afterwards"""
+    if transf is None:
+        if bounds is not None:
+            raise ValueError("bounds without transf")
+        return call()
+    kind, lo, hi = _transf_kinds(transf, bounds, P)
+    with ctx.param_transf(kind, lo, hi):
+        return call()
+
+
+def _tf_kw(transf, bounds):
+    """transf / bounds as keywords for a wrapped call, only when they are given"""
+    kw = {}
+    if transf is not None:
+        kw["transf"] = transf
+    if bounds is not None:
+        kw["bounds"] = bounds
+    return kw
+
+
 def particle_ranking_PLS_targets(X_orig, Y_orig, targets, training_fraction, K, exclude=None, max_comp=0,
                                  rule=_lib.RULE_DEFAULT, details=False, ctx=None):
     """particle_ranking_PLS for B observed targets at once (abc_particle_ranking_pls_targets): ONE fit shared by all of
@@ -115,12 +199,17 @@ _KERNELS = {"epanechnikov": _lib.KERNEL_EPANECHNIKOV, "rectangular": _lib.KERNEL
 
 
 def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fraction, K, exclude=None, kernel="epanechnikov",
-                                        max_comp=0, rule=_lib.RULE_DEFAULT, theta=True, ctx=None):
+                                        max_comp=0, rule=_lib.RULE_DEFAULT, theta=True, ctx=None, transf=None, bounds=None):
     """particle_ranking_PLS_targets followed by the local-linear regression adjustment of every target's K rows on their PLS
     scores (abc_particle_ranking_pls_targets_adjust; Beaumont, Zhang & Balding 2002; the definition is in the header).  kernel:
     "epanechnikov" (default) or "rectangular".  Returns dict(idx (B, K), dist (B, K), theta (B, K, P): the adjusted rows, or None
     with theta=False, weight (B, K), coef (B, A + 1, P): [b, 0] = alpha, [b, 1 + k] = beta_k, post_mean = coef[:, 0]: the
-    adjusted posterior means, rank (B,), status (B,): bit 0 a component skipped, bit 1 rectangular fallback, ncomp)."""
+    adjusted posterior means, rank (B,), status (B,): bit 0 a component skipped, bit 1 rectangular fallback, ncomp).
+    transf / bounds: parameter transforms ("none" / "log" / "logit" per parameter, bounds (P, 2) for the "logit" rows; as
+    transf and logit.bounds of R's abc), set in the context around this call: the regression runs on transform_params(Y), coef
+    is on that scale, and theta holds the adjusted rows carried back, which stay inside the support.  post_mean is then
+    untransform_params(coef[:, 0]): the fitted value at the observation carried back.  It is NOT the mean of the adjusted rows
+    (the back-transform is not linear); particle_ranking_PLS_targets_joint's mean gives that."""
     ctx = _ctx(ctx)
     kernel = _choice("kernel", kernel, _KERNELS)
     X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
@@ -134,21 +223,23 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
     status = np.empty(B, dtype=np.int32)
     out = _lib.AdjustOut(_p(th), _p(w), _p(coef), _p(rank), _p(status))
     ncomp = C.c_int32(0)
-    ctx.check(lib().abc_particle_ranking_pls_targets_adjust(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
-                                                            int(max_comp), int(rule), _p(ex), K, kernel, _p(idx),
-                                                            _p(dist), C.byref(out), C.addressof(ncomp)))
-    return dict(idx=idx, dist=dist, theta=th, weight=w, coef=coef, post_mean=coef[:, 0], rank=rank, status=status,
-                ncomp=ncomp.value)
+    _with_transf(ctx, transf, bounds, P, lambda: ctx.check(lib().abc_particle_ranking_pls_targets_adjust(
+        ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K, kernel, _p(idx),
+        _p(dist), C.byref(out), C.addressof(ncomp))))
+    pm = coef[:, 0] if transf is None else untransform_params(coef[:, 0], transf, bounds)
+    return dict(idx=idx, dist=dist, theta=th, weight=w, coef=coef, post_mean=pm, rank=rank, status=status, ncomp=ncomp.value)
 
 
 def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction, Ks, kernel="epanechnikov", exclude=None,
-                                      max_comp=0, rule=_lib.RULE_DEFAULT, ctx=None):
+                                      max_comp=0, rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None):
     """Tolerance path (abc_particle_ranking_pls_targets_path): particle_ranking_PLS_targets ONCE at K_max = Ks[-1], then the
     rejection estimate and the local-linear fit of particle_ranking_PLS_targets_adjust at every tolerance of the strictly ascending
     list Ks (at most 16): what cv4abc computes for tols = c(...), without ranking once per tolerance.  Tolerance t uses the first
     Ks[t] retained rows only, with the bandwidth h = dist[:, Ks[t] - 1].  Returns dict(post_mean (B, T, P): the mean parameter row,
     coef (B, T, A + 1, P), alpha (B, T, P) = coef[:, :, 0]: the adjusted posterior means (a view), rank (B, T), status (B, T), h (B, T),
-    Ks, idx (B, K_max), dist (B, K_max), ncomp)."""
+    Ks, idx (B, K_max), dist (B, K_max), ncomp).  transf / bounds as particle_ranking_PLS_targets_adjust: coef and alpha are then on
+    the transformed scale, post_mean (the rejection mean of the raw rows) and h do not change, and the dict gains alpha_back =
+    untransform_params(alpha): the fitted value at the observation carried back, not the mean of the adjusted rows."""
     ctx = _ctx(ctx)
     kernel = _choice("kernel", kernel, _KERNELS)
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))
@@ -164,11 +255,14 @@ def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction
     h = np.empty((B, nt))
     path = _lib.Path(_p(ks), nt, _p(pm), _p(coef), _p(rank), _p(status), _p(h))
     ncomp = C.c_int32(0)
-    ctx.check(lib().abc_particle_ranking_pls_targets_path(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
-                                                          int(max_comp), int(rule), _p(ex), kernel, _p(idx), _p(dist),
-                                                          C.byref(path), C.addressof(ncomp)))
-    return dict(post_mean=pm, coef=coef, alpha=coef[:, :, 0], rank=rank, status=status, h=h, Ks=ks.astype(np.int64), idx=idx,
-                dist=dist, ncomp=ncomp.value)
+    _with_transf(ctx, transf, bounds, P, lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path(
+        ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), kernel, _p(idx),
+        _p(dist), C.byref(path), C.addressof(ncomp))))
+    r = dict(post_mean=pm, coef=coef, alpha=coef[:, :, 0], rank=rank, status=status, h=h, Ks=ks.astype(np.int64), idx=idx,
+             dist=dist, ncomp=ncomp.value)
+    if transf is not None:
+        r["alpha_back"] = untransform_params(coef[:, :, 0], transf, bounds)
+    return r
 
 
 _METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_LOCLINEAR}
@@ -176,12 +270,13 @@ _METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_L
 
 def particle_ranking_PLS_targets_path_summary(X_orig, Y_orig, targets, training_fraction, Ks, probs=(0.025, 0.5, 0.975), truth=None,
                                               method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                              rule=_lib.RULE_DEFAULT, ctx=None):
+                                              rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None):
     """particle_ranking_PLS_targets_path with the summaries of particle_ranking_PLS_targets_summary at every tolerance
     (abc_particle_ranking_pls_targets_path_summary; the definition is in the header): the ranking, the fit and, under "rejection",
     the sort of every (target, parameter) are made once for all of Ks.  Tolerance t's quantiles and CDF are those of the summary
     call with K = Ks[t] (bit for bit under "rejection").  Returns the path's dict plus quant (B, T, nq, P): [b, t, q, j], cdf
-    (B, T, P) or None, and probs."""
+    (B, T, P) or None, and probs.  transf / bounds as particle_ranking_PLS_targets_path; under "loclinear" the quantiles and the
+    CDF are those of the adjusted rows carried back."""
     ctx = _ctx(ctx)
     method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))
@@ -203,18 +298,23 @@ def particle_ranking_PLS_targets_path_summary(X_orig, Y_orig, targets, training_
         o["cdf"] = np.empty((B, nt, P))
         sm.truth, sm.cdf = tr.ctypes.data, o["cdf"].ctypes.data
     ncomp = C.c_int32(0)
-    ctx.check(lib().abc_particle_ranking_pls_targets_path_summary(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B,
-                                                                  float(training_fraction), int(max_comp), int(rule), _p(ex), method,
-                                                                  kernel, _p(idx), _p(dist), C.byref(path), C.byref(sm),
-                                                                  C.addressof(ncomp)))
+    _with_transf(ctx, transf, bounds, P, lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path_summary(
+        ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), method, kernel,
+        _p(idx), _p(dist), C.byref(path), C.byref(sm), C.addressof(ncomp))))
+    if transf is not None:
+        o["alpha_back"] = untransform_params(coef[:, :, 0], transf, bounds)
     o.update(post_mean=pm, coef=coef, alpha=coef[:, :, 0], rank=rank, status=status, h=h, Ks=ks.astype(np.int64), idx=idx, dist=dist,
              ncomp=ncomp.value, probs=keep[0])
     return o
 
 
-def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx):
+def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx,
+                     transf=None, bounds=None):
     """The call of particle_ranking_PLS_targets_{summary,density,joint,draws}.  make(lead, P) -> (the product's struct, its outputs as a
-    dict, what must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and ncomp added."""
+    dict, what must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and ncomp added.  transf /
+    bounds: the parameter transforms of particle_ranking_PLS_targets_adjust around the call ("loclinear" only; "rejection" does
+    not regress and ignores them).  The product itself works on the parameter's own scale, after the back-transform: a density
+    grid or a smoothed draw may still pass a bound, as in R."""
     ctx = _ctx(ctx)
     method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
     X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
@@ -223,8 +323,9 @@ def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, 
     dist = np.empty((B, K))
     ncomp = C.c_int32(0)
     entry = getattr(lib(), "abc_particle_ranking_pls_targets_" + product)
-    ctx.check(entry(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K,
-                    method, kernel, _p(idx), _p(dist), None, C.byref(d), C.addressof(ncomp)))
+    _with_transf(ctx, transf, bounds, P, lambda: ctx.check(entry(
+        ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K, method, kernel,
+        _p(idx), _p(dist), None, C.byref(d), C.addressof(ncomp))))
     o.update(idx=idx, dist=dist, ncomp=ncomp.value)
     return o
 
@@ -255,18 +356,21 @@ def _summary_arg(probs, truth, lead, P):
 
 def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fraction, K, probs=(0.025, 0.5, 0.975), truth=None,
                                          method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                         rule=_lib.RULE_DEFAULT, ctx=None):
+                                         rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None):
     """particle_ranking_PLS_targets followed by weighted posterior quantiles of every target's K retained rows and, with truth
     (B, P), the posterior CDF at the truth (abc_particle_ranking_pls_targets_summary; the definition is in the header).
     method "rejection": the rows' parameters, equal weights; "loclinear": the local-linear adjusted rows with the kernel's weights
     (as particle_ranking_PLS_targets_adjust).  Returns dict(quant (B, nq, P): [b, q, j], cdf (B, P) or None, probs, idx (B, K),
-    dist (B, K), ncomp)."""
+    dist (B, K), ncomp).  transf / bounds ("loclinear" only, here and in the density, joint and draws calls below): the parameter
+    transforms of particle_ranking_PLS_targets_adjust; the values are then the adjusted rows carried back, and everything
+    computed from them (quantiles, densities, covariances, bandwidths, the smoothing of smoothed draws) is on the parameter's own
+    scale, so a density grid or a smoothed draw may still pass a bound, as in R."""
     def make(lead, P):
         s, o, keep = _summary_arg(probs, truth, lead, P)
         o["probs"] = keep[0]
         return s, o, keep
     return _targets_product("summary", make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule,
-                            ctx)
+                            ctx, transf, bounds)
 
 
 def weighted_summary(values, weights=None, probs=(0.025, 0.5, 0.975), truth=None, ctx=None):
@@ -298,7 +402,7 @@ def _grid_points(grid, G):
 
 def particle_ranking_PLS_targets_density(X_orig, Y_orig, targets, training_fraction, K, G=512, cut=3.0, bw=None, bw_scale=1.0,
                                          method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                         rule=_lib.RULE_DEFAULT, dens=True, ctx=None):
+                                         rule=_lib.RULE_DEFAULT, dens=True, ctx=None, transf=None, bounds=None):
     """particle_ranking_PLS_targets followed by the weighted Gaussian kernel density of every (target, parameter) on a grid of G
     points and the mode taken from it (abc_particle_ranking_pls_targets_density; the definition is in the header: R's density()
     with bw.nrd0, cut and adjust = bw_scale).  method and kernel as particle_ranking_PLS_targets_summary; bw: given bandwidths
@@ -306,7 +410,7 @@ def particle_ranking_PLS_targets_density(X_orig, Y_orig, targets, training_fract
     grid (B, P, 2): lo_x and step, bw (B, P): the bandwidths used, mode (B, P), mode_dens (B, P), idx (B, K), dist (B, K),
     ncomp)."""
     o = _targets_product("density", lambda lead, P: _density_arg(G, cut, bw_scale, bw, lead, P, dens), X_orig, Y_orig, targets,
-                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx)
+                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
 
@@ -338,7 +442,7 @@ def _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens):
 
 def particle_ranking_PLS_targets_joint(X_orig, Y_orig, targets, training_fraction, K, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None,
                                        method="rejection", kernel="epanechnikov", exclude=None, max_comp=0, rule=_lib.RULE_DEFAULT,
-                                       dens=True, ctx=None):
+                                       dens=True, ctx=None, transf=None, bounds=None):
     """particle_ranking_PLS_targets followed by the joint posterior of every target, what a pairs plot draws
     (abc_particle_ranking_pls_targets_joint; the definition is in the header): the weighted means, the covariance matrix
     (numpy.cov with aweights) and the Pearson correlations of the P parameters, and for every pair of parameters in pairs (rows
@@ -349,7 +453,7 @@ def particle_ranking_PLS_targets_joint(X_orig, Y_orig, targets, training_fractio
     x (B, P, G): every parameter's grid points, grid (B, P, 2), bw (B, P), mode (B, npairs, 2), mode_dens (B, npairs), pairs
     (npairs, 2), idx (B, K), dist (B, K), ncomp)."""
     o = _targets_product("joint", lambda lead, P: _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens), X_orig, Y_orig, targets,
-                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx)
+                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
 
@@ -378,7 +482,7 @@ def _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P):
 
 def particle_ranking_PLS_targets_draws(X_orig, Y_orig, targets, training_fraction, K, S, smooth=False, seed=0, method="rejection",
                                        kernel="epanechnikov", bw=None, bw_scale=1.0, stream=None, exclude=None, max_comp=0,
-                                       rule=_lib.RULE_DEFAULT, ctx=None):
+                                       rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None):
     """particle_ranking_PLS_targets followed by S posterior draws of every target, made on the device
     (abc_particle_ranking_pls_targets_draws; the definition is in the header): rows of the target's K retained rows resampled with
     their weights (method and kernel as particle_ranking_PLS_targets_summary), as they are (smooth=False, the weighted bootstrap)
@@ -389,7 +493,7 @@ def particle_ranking_PLS_targets_draws(X_orig, Y_orig, targets, training_fractio
     each draw came from (idx[b, src[b, s]] is its row of the set), ess (B,): the effective sample size W^2 / sum w^2, bw (B, P):
     the bandwidths used (NaN with smooth=False), idx (B, K), dist (B, K), ncomp)."""
     return _targets_product("draws", lambda lead, P: _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P), X_orig, Y_orig,
-                            targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx)
+                            targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds)
 
 
 def weighted_draws(values, weights=None, S=1000, smooth=False, seed=0, bw=None, bw_scale=1.0, stream=None, ctx=None):
@@ -417,7 +521,8 @@ def hpd_levels(dens, step_x, step_y, probs=(0.5, 0.9, 0.95)):
 
 
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
-                       ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False):
+                       ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False, transf=None,
+                       bounds=None):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
     without replacement (numpy Generator seeded with `seed`) serve as pseudo-observed data, each ranked against the set with
     itself excluded (the fit is shared: the row stays in it), and the posterior mean of its K nearest rows estimates its
@@ -429,7 +534,9 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
     for loclinear), cv4abc's default.  statistic="mode": they come from the mode of the weighted kernel density
     (particle_ranking_PLS_targets_density with its defaults; post_mode).  coverage=True adds truth_cdf (n_targets, P): each left-out row's true parameter's place in
     its own posterior (roughly uniform when calibrated), and ci95 (P,): the fraction of targets whose truth lies in
-    [Q(0.025), Q(0.975)]."""
+    [Q(0.025), Q(0.975)].  transf / bounds: the parameter transforms of particle_ranking_PLS_targets_adjust, handed to the
+    "loclinear" calls (and only when given); the estimate under statistic="mean" is then its post_mean, the fitted value at the
+    observation carried back."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -441,22 +548,23 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
         raise ValueError("statistic must be 'mean', 'median' or 'mode'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
     theta = np.ascontiguousarray(Y[rows])
+    tkw = _tf_kw(transf, bounds)
     sm = None
     if statistic == "median" or coverage:
         sm = particle_ranking_PLS_targets_summary(X, Y, X[rows], training_fraction, K, probs=(0.5, 0.025, 0.975),
                                                   truth=theta if coverage else None, method=method, kernel=kernel, exclude=rows,
-                                                  max_comp=max_comp, rule=rule, ctx=ctx)
+                                                  max_comp=max_comp, rule=rule, ctx=ctx, **tkw)
     if statistic == "median":
         r = sm
     elif statistic == "mode":
         r = particle_ranking_PLS_targets_density(X, Y, X[rows], training_fraction, K, method=method, kernel=kernel, exclude=rows,
-                                                 max_comp=max_comp, rule=rule, dens=False, ctx=ctx)
+                                                 max_comp=max_comp, rule=rule, dens=False, ctx=ctx, **tkw)
     elif method == "rejection":
         r = particle_ranking_PLS_targets(X, Y, X[rows], training_fraction, K, exclude=rows, max_comp=max_comp, rule=rule,
                                          details=True, ctx=ctx)
     else:
         r = particle_ranking_PLS_targets_adjust(X, Y, X[rows], training_fraction, K, exclude=rows, kernel=kernel,
-                                                max_comp=max_comp, rule=rule, theta=False, ctx=ctx)
+                                                max_comp=max_comp, rule=rule, theta=False, ctx=ctx, **tkw)
     pm = sm["quant"][:, 0, :] if statistic == "median" else r["mode" if statistic == "mode" else "post_mean"]
     var = theta.var(axis=0, ddof=1) if n_targets > 1 else np.zeros(theta.shape[1])
     sse = ((pm - theta) ** 2).sum(axis=0)
@@ -471,7 +579,8 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
 
 
 def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
-                            ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False):
+                            ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False, transf=None,
+                            bounds=None):
     """cross_validate_pls at every tolerance of the strictly ascending list Ks from ONE call of
     particle_ranking_PLS_targets_path: cv4abc with tols = c(...).  The left-out rows are drawn from `seed` exactly as
     cross_validate_pls draws them.  method: "rejection" (the mean of the Ks[t] nearest rows) or "loclinear" (alpha of the fit at
@@ -481,7 +590,8 @@ def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fracti
     with "median" the estimate is post_median (n_targets, T, P) in place of post_mean, and pred_error and best come from it; with
     coverage=True the result gains truth_cdf (n_targets, T, P) and ci95 (T, P) as cross_validate_pls's at every tolerance,
     coverage_ks (T, P): the Kolmogorov distance of the finite truth_cdf values from the uniform (coverage_ks below), and
-    best_calibrated (P,): the index of the tolerance with the smallest coverage_ks (0 where all are NaN)."""
+    best_calibrated (P,): the index of the tolerance with the smallest coverage_ks (0 where all are NaN).  transf / bounds as
+    cross_validate_pls (handed on only when given); the "loclinear" mean estimate is then alpha_back of the path."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -493,17 +603,18 @@ def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fracti
         raise ValueError("statistic must be 'mean' or 'median'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
     theta = np.ascontiguousarray(Y[rows])
+    tkw = _tf_kw(transf, bounds)
     if statistic == "median" or coverage:
         r = particle_ranking_PLS_targets_path_summary(X, Y, X[rows], training_fraction, Ks, probs=(0.5, 0.025, 0.975),
                                                       truth=theta if coverage else None, method=method, kernel=kernel, exclude=rows,
-                                                      max_comp=max_comp, rule=rule, ctx=ctx)
+                                                      max_comp=max_comp, rule=rule, ctx=ctx, **tkw)
     else:
         r = particle_ranking_PLS_targets_path(X, Y, X[rows], training_fraction, Ks, kernel=kernel, exclude=rows, max_comp=max_comp,
-                                              rule=rule, ctx=ctx)
+                                              rule=rule, ctx=ctx, **tkw)
     if statistic == "median":
         pm = np.ascontiguousarray(r["quant"][:, :, 0, :])
     else:
-        pm = np.ascontiguousarray(r["post_mean"] if method == "rejection" else r["alpha"])
+        pm = np.ascontiguousarray(r["post_mean"] if method == "rejection" else r.get("alpha_back", r["alpha"]))
     var = theta.var(axis=0, ddof=1) if n_targets > 1 else np.zeros(theta.shape[1])
     sse = ((pm - theta[:, None, :]) ** 2).sum(axis=0)
     with np.errstate(divide="ignore", invalid="ignore"):

@@ -111,6 +111,11 @@ struct abc_ctx {
     bool sel_bins_ran;       // the last launch_select_smallest took the bin path and has not been checked yet
     bool sel_force_radix;    // set by a caller that repeats its work after a failed bin selection
     unsigned long long targets_fallbacks;   // targets of abc_rank_targets_dev that took the exact single-target path
+    // parameter transforms of the local-linear adjustment (abc_ctx_set_param_transf): one device allocation [lo | hi | kind] of tf_P
+    // entries each, NULL / 0 while nothing is set; the forward passes' out-of-domain counter (device, abc_param_transf_outside)
+    char* tf_buf;
+    size_t tf_P;
+    unsigned long long* tf_outside_dev;
     unsigned long long wx_moved_counts, generation_repeats;      // abc_generation_repeats
     bool wx_gather_rows;     // diagnostic (ABC_DIAG=1 ABC_WX_GATHER=1, set at context creation): the sharded generation's Wilcoxon rule by
                              // gathering the validation rows on every rank (rounds 1-4) instead of the sharded cascade
@@ -281,7 +286,8 @@ size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K);
 int launch_rank_targets_adjust(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
-                               struct abc_adj_keep* keep = nullptr);
+                               struct abc_adj_keep* keep = nullptr, const struct AbcTf* tf = nullptr);
+// tf (optional, transf_dev.h): Y is already forward(Y) (launch_param_transf); theta and keep's readers carry the adjusted rows back
 // tolerance path (adjust.hip): the ranking at K = path->Ks[T - 1], then the rejection mean and the regression at every tolerance;
 // path: Ks in host memory, the outputs device pointers; dist may be NULL.  keep (optional): the fit is made whatever outputs path
 // names, and keep receives what a reader of the adjusted rows needs, with coef B x T x (A + 1) x P and dist B x K_max
@@ -289,7 +295,12 @@ size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T)
 int launch_rank_targets_path(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                              bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path,
-                             struct abc_adj_keep* keep = nullptr);
+                             struct abc_adj_keep* keep = nullptr, const double* Yt = nullptr, const struct AbcTf* tf = nullptr);
+// Yt / tf (optional, both or neither): forward(Y) as N x P with ld = N, which the fit reads; post_mean stays the mean of the raw Y.
+// launch_param_transf: the context's parameter transforms over a column-major n x P matrix (adjust.hip: k_tf_apply); tf NULL: a copy; in place is
+// allowed; outside (optional, device): a forward pass adds the entries of transformed columns it found outside their domain
+int launch_param_transf(abc_ctx*, const struct AbcTf* tf, const double* V, size_t ldv, size_t n, size_t P, int inverse, double* out,
+                        size_t ldo, unsigned long long* outside);
 // weighted posterior quantiles and CDF (summary.hip).  abc_summary_need: workspace of launch_summary for B segment groups of P
 // segments of K values.  SmValues: how the values and weights of segment (b, j) are made (method 0 / 1: the ranking's rows,
 // method 2: V and w); sum: probs in host memory, truth / quant / cdf in device memory.

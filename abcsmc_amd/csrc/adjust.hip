@@ -10,6 +10,9 @@
 //   k_adj_solve     one work-group per target: the chunks' blocks summed in chunk order, centred, the sweep in LDS (64 right-hand
 //                   sides at a time), coef / rank / status
 //   k_adj_apply     (only for theta / weight) the adjusted rows and the weights
+// Under parameter transforms (abc_ctx_set_param_transf) the caller hands forward(Y) as Y, made once per call by k_tf_apply (N P
+// logarithms, not B K P at every gather), so everything above runs on the transformed scale unchanged; k_adj_apply carries the
+// adjusted rows back (tf_back_j, as sm_value of segment_dev.h does for the products).
 // The tolerance path (abc_rank_targets_path_dev) ranks once at K_max and runs the regression at every tolerance K_t of a list:
 //   k_adj_moments_path  k_adj_moments with one weight column and one set of accumulators per tolerance: the chunk's rows are staged
 //                       once and the tolerances' chains run interleaved over the same LDS reads; tolerance t's chain stops at row K_t
@@ -428,7 +431,7 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
 // order), weight[b K + e] = w_e
 __global__ __launch_bounds__(256) void k_adj_apply(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist, size_t K,
                                                    int nc, int P, int A, int kernel, const double* __restrict__ O, int KCO,
-                                                   const double* __restrict__ coef, int TR, int beta_lds, size_t b0,
+                                                   const double* __restrict__ coef, int TR, int beta_lds, size_t b0, AbcTf tf,
                                                    double* __restrict__ theta, double* __restrict__ weight) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, Wv = nc + P;
@@ -458,8 +461,37 @@ __global__ __launch_bounds__(256) void k_adj_apply(AjSrc src, const uint64_t* __
     for (int q = t; q < nr * P; q += 256) {
         const int r = q / P, j = q % P;
         const double* x = tv + r * Wv;
-        theta[(b * K + e0 + r) * (size_t)P + j] = aj_adjusted(x[nc + j], [&](int k) { return x[k]; }, bt + j, (size_t)P, nc);
+        const double v = aj_adjusted(x[nc + j], [&](int k) { return x[k]; }, bt + j, (size_t)P, nc);
+        theta[(b * K + e0 + r) * (size_t)P + j] = tf.kind ? tf_back_j(tf, j, v) : v;
     }
+}
+
+// out[i + ldo j] = forward (inverse: back) transform of V[i + ldv j] under parameter j's kind (tf.kind == NULL or kind 0: copied bit
+// for bit).  Grid (row blocks, parameters), lanes along rows; in place is allowed (an element is read and written by one thread).
+// A forward pass counts the entries of LOG / LOGIT columns outside their domain: one atomic add per work-group that found any.
+__global__ __launch_bounds__(256) void k_tf_apply(AbcTf tf, const double* V, size_t ldv, size_t n, int inverse, double* out, size_t ldo,
+                                                  unsigned long long* outside) {
+    __shared__ unsigned red[256];
+    const int t = threadIdx.x, j = (int)blockIdx.y;
+    const int kind = tf.kind ? tf.kind[j] : 0;
+    const double lo = kind == 2 ? tf.lo[j] : 0.0, hi = kind == 2 ? tf.hi[j] : 0.0;
+    const double* v = V + ldv * (size_t)j;
+    double* o = out + ldo * (size_t)j;
+    unsigned cnt = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + t; i < n; i += (size_t)gridDim.x * 256) {
+        const double y = v[i];
+        const double r = inverse ? tf_back(kind, lo, hi, y) : tf_forward(kind, lo, hi, y);
+        if (!inverse && kind != 0 && isnan(r)) cnt++;
+        o[i] = r;
+    }
+    if (inverse || kind == 0 || !outside) return;                   // (uniform)
+    red[t] = cnt;
+    __syncthreads();
+    for (int sft = 128; sft > 0; sft >>= 1) {
+        if (t < sft) red[t] += red[t + sft];
+        __syncthreads();
+    }
+    if (t == 0 && red[0]) atomicAdd(outside, (unsigned long long)red[0]);
 }
 
 struct AjPlan {
@@ -523,7 +555,8 @@ size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K) {
 int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
-                               abc_adj_keep* keep) {
+                               abc_adj_keep* keep, const AbcTf* tf) {
+    const AbcTf tfd = tf ? *tf : AbcTf{nullptr, nullptr, nullptr};
     double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
     if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
     abc_tg_scores sc;
@@ -583,6 +616,7 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
         keep->nc = nc;
         keep->coef = coef;
         keep->dist = d;
+        keep->tf = tfd;
     }
     if (out->theta || out->weight) {
         const int Wv = nc + Pi;
@@ -597,7 +631,7 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
             const size_t nb = (B - b0 < AJ_MAX_GRID_Y) ? B - b0 : AJ_MAX_GRID_Y;
             hipLaunchKernelGGL(k_adj_apply, dim3((unsigned)tiles, (unsigned)nb), dim3(256), lds_a, ctx->stream, src, (const uint64_t*)idx,
                                (const double*)d, K, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)coef, TR, beta_lds, b0,
-                               out->theta, out->weight);
+                               tfd, out->theta, out->weight);
             ABC_HIP(ctx, hipGetLastError());
         }
     }
@@ -638,7 +672,8 @@ size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T)
 
 int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                             bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path, abc_adj_keep* keep) {
+                             bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path, abc_adj_keep* keep,
+                             const double* Yt, const AbcTf* tf) {
     const int T = (int)path->T, Pi = (int)P;
     AjKs ks = {};
     for (int t = 0; t < T; t++) ks.K[t] = path->Ks[t];
@@ -657,6 +692,7 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
     src.sld = 0;
     src.Y = Y;
     src.ldy = ldy;
+    const AjSrc raw = src;                                           // post_mean is of the raw Y under transforms too
     int nc = 0;
     if (fit) {
         double hdr = 0.0;
@@ -668,12 +704,16 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
         src.W = (size_t)nc + P;
         src.S = sc.S;
         src.sld = sc.sld;
+        if (Yt) {                                                    // the fit on the transformed scale (N x P, ld = N)
+            src.Y = Yt;
+            src.ldy = N;
+        }
         if (aj_use_table(N, A, P, B, K) && src.W > 0) {              // the adjustment's rule with K = K_max
             double* Tb = (double*)abc_ws_alloc(ctx, N * src.W * 8);
             if (!Tb) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
             size_t blocks = (N + 63) / 64;
             if (blocks > 8192) blocks = 8192;
-            hipLaunchKernelGGL(k_adj_table, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sc.S, sc.sld, Y, ldy, N, nc, Pi, Tb);
+            hipLaunchKernelGGL(k_adj_table, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sc.S, sc.sld, src.Y, src.ldy, N, nc, Pi, Tb);
             ABC_HIP(ctx, hipGetLastError());
             src.T = Tb;
         }
@@ -721,17 +761,35 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
             keep->nc = nc;
             keep->coef = coef;
             keep->dist = d;
+            keep->tf = (Yt && tf) ? *tf : AbcTf{nullptr, nullptr, nullptr};
         }
     }
     if (path->post_mean || path->h) {
         const size_t step = (size_t)1 << 30;
         for (size_t b0 = 0; b0 < B; b0 += step) {
             const size_t nb = (B - b0 < step) ? B - b0 : step;
-            hipLaunchKernelGGL(k_path_mean, dim3((unsigned)nb, (unsigned)T), dim3(256), 0, ctx->stream, src, nc,
+            hipLaunchKernelGGL(k_path_mean, dim3((unsigned)nb, (unsigned)T), dim3(256), 0, ctx->stream, Yt ? raw : src, nc,
                                (const uint64_t*)idx + b0 * K, (const double*)d + b0 * K, K, ks, T, Pi,
                                path->post_mean ? path->post_mean + b0 * T * P : nullptr, path->h ? path->h + b0 * T : nullptr);
             ABC_HIP(ctx, hipGetLastError());
         }
+    }
+    return ABC_OK;
+}
+
+int launch_param_transf(abc_ctx* ctx, const AbcTf* tf, const double* V, size_t ldv, size_t n, size_t P, int inverse, double* out,
+                        size_t ldo, unsigned long long* outside) {
+    if (n == 0 || P == 0) return ABC_OK;
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const AbcTf tfd = tf ? *tf : AbcTf{nullptr, nullptr, nullptr};
+    for (size_t j0 = 0; j0 < P; j0 += AJ_MAX_GRID_Y) {
+        const size_t np = (P - j0 < AJ_MAX_GRID_Y) ? P - j0 : AJ_MAX_GRID_Y;
+        AbcTf tj = tfd;
+        if (tj.kind) { tj.kind += j0; tj.lo += j0; tj.hi += j0; }
+        hipLaunchKernelGGL(k_tf_apply, dim3((unsigned)blocks, (unsigned)np), dim3(256), 0, ctx->stream, tj, V + ldv * j0, ldv, n, inverse,
+                           out + ldo * j0, ldo, outside);
+        ABC_HIP(ctx, hipGetLastError());
     }
     return ABC_OK;
 }

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "transf_dev.h"
+
 // where the retained rows are read from: the table (T != NULL, row i at T + i W) or the scores and Y directly (same bits)
 struct AjSrc {
     const double* T;
@@ -52,4 +54,6 @@ struct abc_adj_keep {
     int nc;
     const double* coef;     // B x (A + 1) x P
     const double* dist;     // B x K
+    AbcTf tf;               // the parameter transforms the fit was made under (kind == NULL: none): src.Y is forward(Y), and a reader
+                            // of the adjusted rows carries theta* back with tf_back_j
 };

@@ -105,6 +105,8 @@ extern "C" void abc_ctx_destroy(abc_ctx* ctx) {
     if (ctx->kde_which) (void)hipFree(ctx->kde_which);
     if (ctx->giveups_dev) (void)hipFree(ctx->giveups_dev);
     if (ctx->alias_fail_dev) (void)hipFree(ctx->alias_fail_dev);
+    if (ctx->tf_buf) (void)hipFree(ctx->tf_buf);
+    if (ctx->tf_outside_dev) (void)hipFree(ctx->tf_outside_dev);
     abc_comm_release(ctx);
     if (ctx->xbuf) (void)hipFree(ctx->xbuf);
     if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);
@@ -314,6 +316,90 @@ extern "C" void abc_rng_jump(abc_rng* r, uint64_t n) { taus2_jump(r, n); }
         if (hipSetDevice((ctx)->device) != hipSuccess) ABC_FAIL(ctx, ABC_ERR_HIP, "hipSetDevice failed"); \
         if ((ctx)->timing && (ctx)->nev > 128) ABC_TRY(abc_timing_flush(ctx)); \
     } while (0)
+
+// ---- parameter transforms of the local-linear adjustment ---------------------------------------------------------------------
+// the context's setting as the kernels take it (kind == NULL: nothing set)
+static AbcTf ctx_tf(const abc_ctx* ctx) {
+    AbcTf t{nullptr, nullptr, nullptr};
+    if (ctx->tf_buf) {
+        const double* lo = (const double*)ctx->tf_buf;
+        t.lo = lo;
+        t.hi = lo + ctx->tf_P;
+        t.kind = (const int32_t*)(lo + 2 * ctx->tf_P);
+    }
+    return t;
+}
+
+extern "C" int abc_ctx_set_param_transf(abc_ctx* ctx, const abc_param_transf_t* tf) {
+    if (!ctx) return ABC_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) ABC_FAIL(ctx, ABC_ERR_HIP, "hipSetDevice failed");
+    bool any = false;
+    if (tf && tf->P) {
+        const size_t P = tf->P;
+        if (P > 1024) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_param_transf: P = %zu parameters (at most 1024)", P);
+        if (!tf->kind) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_param_transf: null argument (kind is required)");
+        for (size_t j = 0; j < P; j++) {
+            const int32_t k = tf->kind[j];
+            if (k != ABC_TRANSF_NONE && k != ABC_TRANSF_LOG && k != ABC_TRANSF_LOGIT)
+                ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_param_transf: kind[%zu] = %d (0 = none, 1 = log, 2 = logit)", j, (int)k);
+            if (k == ABC_TRANSF_LOGIT) {
+                if (!tf->lo || !tf->hi)
+                    ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_param_transf: null bounds (lo and hi are required for logit, parameter %zu)", j);
+                const double lo = tf->lo[j], hi = tf->hi[j];
+                if (!isfinite(lo) || !isfinite(hi) || !(lo < hi))
+                    ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_param_transf: bounds [%g, %g] of parameter %zu (finite, lo < hi)", lo, hi, j);
+            }
+            any = any || k != ABC_TRANSF_NONE;
+        }
+    }
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // (queued kernels may still read the previous setting)
+    if (ctx->tf_buf) { ABC_HIP(ctx, hipFree(ctx->tf_buf)); ctx->tf_buf = nullptr; ctx->tf_P = 0; }
+    if (!any) return ABC_OK;
+    const size_t P = tf->P;
+    std::vector<double> h(2 * P + (P + 1) / 2, 0.0);                 // [lo | hi | kind]
+    for (size_t j = 0; j < P; j++)
+        if (tf->kind[j] == ABC_TRANSF_LOGIT) { h[j] = tf->lo[j]; h[P + j] = tf->hi[j]; }
+    memcpy(h.data() + 2 * P, tf->kind, P * sizeof(int32_t));
+    if (!ctx->tf_outside_dev) {
+        ABC_HIP(ctx, hipMalloc((void**)&ctx->tf_outside_dev, sizeof(unsigned long long)));
+        ABC_HIP(ctx, hipMemset(ctx->tf_outside_dev, 0, sizeof(unsigned long long)));
+    }
+    ABC_HIP(ctx, hipMalloc((void**)&ctx->tf_buf, h.size() * sizeof(double)));
+    ABC_HIP(ctx, hipMemcpy(ctx->tf_buf, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    ctx->tf_P = P;
+    return ABC_OK;
+}
+
+static int param_transf_check(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t n, size_t P, const double* out,
+                              size_t ldo) {
+    if (!V || !out) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (V and out are required)", fn);
+    if (ldv < n) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldv %zu < n %zu", fn, ldv, n);
+    if (ldo < n) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldo %zu < n %zu", fn, ldo, n);
+    if (ctx->tf_buf && P != ctx->tf_P)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: P = %zu, but the parameter transforms were set for %zu parameters", fn, P, ctx->tf_P);
+    return ABC_OK;
+}
+
+extern "C" int abc_param_transf_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t n, size_t P, int inverse, double* out,
+                                    size_t ldo) {
+    CHECK_CTX(ctx);
+    ABC_TRY(param_transf_check(ctx, "abc_param_transf_dev", V, ldv, n, P, out, ldo));
+    const AbcTf tf = ctx_tf(ctx);
+    return launch_param_transf(ctx, &tf, V, ldv, n, P, inverse, out, ldo, ctx->tf_outside_dev);
+}
+
+extern "C" int abc_param_transf_outside(abc_ctx* ctx, uint64_t* count, int reset) {
+    if (!ctx || !count) return ABC_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) ABC_FAIL(ctx, ABC_ERR_HIP, "hipSetDevice failed");
+    unsigned long long dev = 0;
+    if (ctx->tf_outside_dev) {
+        ABC_HIP(ctx, hipMemcpyAsync(&dev, ctx->tf_outside_dev, sizeof(dev), hipMemcpyDeviceToHost, ctx->stream));
+        if (reset) ABC_HIP(ctx, hipMemsetAsync(ctx->tf_outside_dev, 0, sizeof(dev), ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    *count = (uint64_t)dev;
+    return ABC_OK;
+}
 
 static size_t default_A(size_t M, size_t P, int max_comp) {
     return (max_comp > 0) ? (size_t)max_comp : (M < P ? M : P);
@@ -1433,6 +1519,11 @@ struct TgRequest {                             // (members in the order of the e
     bool segments() const { return kind == TG_PRODUCT; }      // the rows' values are read after the ranking
     bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
     bool path_summary() const { return kind == TG_PATH && prod.kind == Product::SUMMARY; }      // prod: the summaries at every tolerance
+    // the call fits the regression, so the context's parameter transforms (if any) apply to it
+    bool fits() const {
+        if (kind == TG_PATH) return path && (path->coef || path->rank || path->status || (path_summary() && method == ABC_POSTERIOR_LOCLINEAR));
+        return regress();
+    }
 };
 }  // namespace
 
@@ -1458,6 +1549,8 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
         r.K = r.path->Ks[r.path->T - 1];
     }
     const size_t N = r.N, B = r.B, K = r.K;
+    if (ctx->tf_buf && r.fits() && r.P != ctx->tf_P)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: P = %zu, but the parameter transforms were set for %zu parameters", fn, r.P, ctx->tf_P);
     if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
     if (!r.targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (targets is required)", fn);
     if (!r.idx && !summary && !r.path_summary()) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (idx is required)", fn);
@@ -1509,9 +1602,10 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
 
 // Arena bytes of a checked request: what tg_run takes and, for the host entries (host: the fit under `rule`, every array staged),
 // what tg_host takes around it.  The device entries get the model from the caller, so their ranking needs no fit workspace.
-static size_t tg_need(const TgRequest& r, bool host, int rule) {
+static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rule) {
     const size_t N = r.N, M = r.M, P = r.P, A = r.A, B = r.B, K = r.K;
     size_t b = abc_targets_need(N, A, B, K, r.any_excl);
+    if (ctx->tf_buf && r.fits()) b += N * P * 8 + 256;                                      // forward(Y)
     if (r.regress()) b += abc_adjust_need(N, A, P, B, K);
     if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T);
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
@@ -1539,6 +1633,15 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
         if (!d) d = (double*)abc_ws_alloc(ctx, B * K * 8);
         if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     }
+    // parameter transforms: forward(Y) once per call (N x P, ld = N), which the regression reads as its Y; everything that reads raw
+    // values (method 0, the path's post_mean) keeps r.Y
+    const AbcTf tf = ctx_tf(ctx);
+    double* Yt = nullptr;
+    if (tf.kind && r.fits() && r.P) {
+        Yt = (double*)abc_ws_alloc(ctx, r.N * r.P * 8);
+        if (!Yt) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+        ABC_TRY(launch_param_transf(ctx, &tf, r.Y, r.ldy, r.N, r.P, 0, Yt, r.N, ctx->tf_outside_dev));
+    }
     if (r.kind == TG_PATH) {
         const bool ps = r.path_summary(), lin = ps && r.method == ABC_POSTERIOR_LOCLINEAR;
         if (ps && !ix) {
@@ -1547,7 +1650,7 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
         }
         abc_adj_keep pk;
         ABC_TRY(launch_rank_targets_path(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr));
+                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr, Yt, Yt ? &tf : nullptr));
         if (!ps) return ABC_OK;
         SmValues pv = {};
         pv.method = r.method;
@@ -1566,8 +1669,9 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
     } else {                // (without keep nothing is regressed when every member of adj is NULL)
         abc_adjust_out od = {};
         if (r.adj) od = *r.adj;
-        ABC_TRY(launch_rank_targets_adjust(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                           r.any_excl, K, r.kernel, ix, d, &od, summary ? &keep : nullptr));
+        ABC_TRY(launch_rank_targets_adjust(ctx, r.X, r.ldx, Yt ? Yt : r.Y, Yt ? r.N : r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt,
+                                           B, r.exclude, r.any_excl, K, r.kernel, ix, d, &od, summary ? &keep : nullptr,
+                                           Yt ? &tf : nullptr));
     }
     if (!summary) return ABC_OK;
     SmValues sv = {};
@@ -1583,7 +1687,7 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
 
 static int tg_dev(abc_ctx* ctx, const char* fn, TgRequest r) {
     ABC_TRY(tg_check(ctx, fn, r, false));
-    ABC_TRY(abc_ws_reserve(ctx, tg_need(r, false, 0)));
+    ABC_TRY(abc_ws_reserve(ctx, tg_need(ctx, r, false, 0)));
     return tg_run(ctx, fn, r);
 }
 
@@ -1593,7 +1697,7 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
     const size_t A = h.A = default_A(M, P, max_comp);
     ABC_TRY(tg_check(ctx, fn, h, true));
     const size_t K = h.K;                                   // (a path's: set by the check)
-    ABC_TRY(abc_ws_reserve(ctx, tg_need(h, true, rule)));
+    ABC_TRY(abc_ws_reserve(ctx, tg_need(ctx, h, true, rule)));
     Stage s{ctx};
     // the fit: the single-target ranking's own path (generation_core) on an all-zero observation, whose scores are not used
     abc_generation_io io;
@@ -1930,6 +2034,22 @@ extern "C" int abc_weighted_draws_dev(abc_ctx* ctx, const double* V, size_t ldv,
 extern "C" int abc_weighted_draws(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_draws* dr) {
     CHECK_CTX(ctx);
     return weighted_host(ctx, "abc_weighted_draws", V, K, P, w, Product(dr));
+}
+
+extern "C" int abc_param_transf(abc_ctx* ctx, const double* V, size_t n, size_t P, int inverse, double* out) {
+    CHECK_CTX(ctx);
+    ABC_TRY(param_transf_check(ctx, "abc_param_transf", V, n, n, P, out, n));
+    if (n == 0 || P == 0) return ABC_OK;
+    ABC_TRY(abc_ws_reserve(ctx, n * P * 8 + 4 * 256));
+    Stage s{ctx};
+    const double* V_d = s.up(V, n * P);
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "abc_param_transf: workspace exhausted");
+    const AbcTf tf = ctx_tf(ctx);
+    ABC_TRY(launch_param_transf(ctx, &tf, V_d, n, n, P, inverse, (double*)V_d, n, ctx->tf_outside_dev));
+    s.down(out, V_d, n * P);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
 }
 
 extern "C" int abc_targets_fallbacks(abc_ctx* ctx, uint64_t* count, int reset) {

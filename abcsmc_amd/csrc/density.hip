@@ -127,6 +127,7 @@ __global__ __launch_bounds__(DN_BS) void k_dn_moments(SmArgs a, DnArgs d, size_t
 }
 
 // grid (P x nchunk, targets b0 + blockIdx.y); pf / pg: the chunks' candidates [segment][chunk] (nchunk > 1)
+template <bool TF>
 __global__ __launch_bounds__(DN_BS) void k_dn_dens(SmArgs a, DnArgs d, size_t b0, const DnSeg* __restrict__ sp, int nchunk,
                                                    double* __restrict__ pf, int* __restrict__ pg) {
     __shared__ __attribute__((aligned(16))) double2 tile[DN_TILE];
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(DN_BS) void k_dn_dens(SmArgs a, DnArgs d, size_t b0
             for (int i = t; i < len; i += DN_BS) {
                 const size_t e = base + (size_t)i;
                 const double w = sm_weight(a, s, e);
-                tile[i] = make_double2(sm_value(a, s, e), w > 0.0 ? w : 0.0);
+                tile[i] = make_double2(sm_value<TF>(a, s, e), w > 0.0 ? w : 0.0);
             }
             __syncthreads();
 #pragma unroll 4
@@ -304,8 +305,9 @@ int launch_density(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t 
     }
     for (size_t b0 = 0; b0 < B; b0 += DN_MAX_GRID_Y) {
         const size_t nb = (B - b0 < DN_MAX_GRID_Y) ? B - b0 : DN_MAX_GRID_Y;
-        hipLaunchKernelGGL(k_dn_dens, dim3((unsigned)(P * nchunk), (unsigned)nb), dim3(DN_BS), 0, ctx->stream, a, d, b0, sp, nchunk,
-                           pf, pg);
+        // (the back-transform costs k_dn_dens a wave per SIMD: calls without transforms keep the instance without it)
+        hipLaunchKernelGGL(a.tf.kind ? k_dn_dens<true> : k_dn_dens<false>, dim3((unsigned)(P * nchunk), (unsigned)nb), dim3(DN_BS), 0,
+                           ctx->stream, a, d, b0, sp, nchunk, pf, pg);
         ABC_HIP(ctx, hipGetLastError());
     }
     if (mode && nchunk > 1) {

@@ -83,6 +83,7 @@ __global__ __launch_bounds__(JT_BS) void k_jt_mean(SmArgs a, JtArgs d, size_t b0
 }
 
 // grid (tiles ti <= tj of 16 parameters, targets b0 + blockIdx.y); thread (il, jl) = (t >> 4, t & 15)
+template <bool TF>
 __global__ __launch_bounds__(JT_BS) void k_jt_cov(SmArgs a, JtArgs d, size_t b0, const double* __restrict__ mu,
                                                   const double* __restrict__ ws) {
     __shared__ double dv[2 * JT_CT][JT_CE + 1];
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(JT_BS) void k_jt_cov(SmArgs a, JtArgs d, size_t b0,
             if (p < P && el < len) {
                 const double m = mu[b * P + p];
                 const SmSeg s = sm_seg(a, b, p);
-                if (!isnan(m) && sm_weight(a, s, base + (size_t)el) > 0.0) v = sm_value(a, s, base + (size_t)el) - m;
+                if (!isnan(m) && sm_weight(a, s, base + (size_t)el) > 0.0) v = sm_value<TF>(a, s, base + (size_t)el) - m;
             }
             dv[c][el] = v;
         }
@@ -379,8 +380,9 @@ int launch_joint(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P,
         hipLaunchKernelGGL(k_jt_mean, dim3((unsigned)P, (unsigned)nb), dim3(JT_BS), 0, ctx->stream, a, d, b0, sp, mu, ws);
         ABC_HIP(ctx, hipGetLastError());
         if (d.cov || d.corr) {
-            hipLaunchKernelGGL(k_jt_cov, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)nb), dim3(JT_BS), 0, ctx->stream, a, d, b0,
-                               (const double*)mu, (const double*)ws);
+            // (the back-transform costs k_jt_cov a wave per SIMD: calls without transforms keep the instance without it)
+            hipLaunchKernelGGL(a.tf.kind ? k_jt_cov<true> : k_jt_cov<false>, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)nb),
+                               dim3(JT_BS), 0, ctx->stream, a, d, b0, (const double*)mu, (const double*)ws);
             ABC_HIP(ctx, hipGetLastError());
         }
         if (!pair) continue;

@@ -20,6 +20,7 @@ struct SmArgs {
     int KCO, nc, A, P, kernel;
     const double* coef;
     const double* dist;
+    AbcTf tf;                   // method 1: the fit's parameter transforms (kind == NULL: none)
     const double* V;            // method 2
     size_t ldv;
     const double* w;
@@ -61,6 +62,7 @@ static inline SmArgs sm_args(const SmValues& sv, size_t K, size_t P) {
         a.nc = sv.adj->nc;
         a.coef = sv.adj->coef;
         a.dist = sv.adj->dist;
+        a.tf = sv.adj->tf;
     }
     a.V = sv.V;
     a.ldv = sv.ldv;
@@ -93,13 +95,18 @@ __device__ __forceinline__ SmSeg sm_seg(const SmArgs& a, size_t b, int j) {
     return s;
 }
 
+// TF = false: an instance without the back-transform for a kernel whose registers it would cost (its launcher takes it when
+// a.tf.kind == NULL, so calls without transforms run the code they ran before there were any)
+template <bool TF = true>
 __device__ __forceinline__ double sm_value(const SmArgs& a, const SmSeg& s, size_t e) {
     if (a.method == 0) return a.Y[(size_t)s.ix[e] + a.ldy * (size_t)s.j];
     if (a.method == 1) {
         const size_t i = (size_t)s.ix[e];
         const int nc = a.nc;
-        return aj_adjusted(aj_val(a.src, i, nc + s.j, nc), [&](int k) { return aj_val(a.src, i, k, nc) - s.ob[k]; }, s.beta,
-                           (size_t)a.P, nc);
+        const double v = aj_adjusted(aj_val(a.src, i, nc + s.j, nc), [&](int k) { return aj_val(a.src, i, k, nc) - s.ob[k]; }, s.beta,
+                                     (size_t)a.P, nc);
+        if constexpr (TF) return a.tf.kind ? tf_back_j(a.tf, s.j, v) : v;     // (the fit's scale back to the parameter's own)
+        return v;
     }
     return a.V[e + a.ldv * (size_t)s.j];
 }

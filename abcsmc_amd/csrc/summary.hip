@@ -56,6 +56,7 @@ __device__ __forceinline__ bool sm_less(unsigned long long ka, unsigned ia, unsi
 
 // entries e0 .. e0 + len - 1 of the segment as (key, e) pairs in key[0..n2) / id[0..n2) (n2 a power of two >= len, padding behind),
 // sorted ascending by a bitonic sort; the count of positive weights and a non-finite flag added to *cnt / *bad
+template <bool TF = true>
 __device__ void sm_build_sort(const SmArgs& a, const SmSeg& s, size_t e0, int len, int n2, unsigned long long* key, unsigned* id,
                               unsigned* cnt, int* bad) {
     const int t = threadIdx.x;
@@ -66,7 +67,7 @@ __device__ void sm_build_sort(const SmArgs& a, const SmSeg& s, size_t e0, int le
         unsigned i = SM_PAD_ID;
         if (r < len) {
             const size_t e = e0 + (size_t)r;
-            const double v = sm_value(a, s, e);
+            const double v = sm_value<TF>(a, s, e);
             if (!isfinite(v)) nf = 1;
             i = (unsigned)e;
             if (sm_weight(a, s, e) > 0.0) {
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(SM_BS) void k_smp_lds(SmArgs a, SmProbs pr, SmKs ks
     if (t == 0) { s_cnt = 0; s_bad = 0; }
     __syncthreads();
     SmSeg s = sm_seg(a, b0 + blockIdx.y, (int)blockIdx.x);
-    sm_build_sort(a, s, 0, (int)a.K, n2, key, id, &s_cnt, &s_bad);
+    sm_build_sort<false>(a, s, 0, (int)a.K, n2, key, id, &s_cnt, &s_bad);     // (rejection only: launch_path_summary)
     const double tau = a.cdf ? a.truth[s.b * a.P + s.j] : 0.0;
     for (int ti = ks.T - 1; ti >= 0; ti--) {
         const unsigned n = (unsigned)ks.K[ti], keep = ti > 0 ? (unsigned)ks.K[ti - 1] : 0u;

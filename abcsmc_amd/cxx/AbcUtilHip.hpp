@@ -384,6 +384,24 @@ inline std::vector<TargetAdjustment> particle_ranking_PLS_targets_adjust(const M
     }
     return res;
 }
+// Parameter transforms of the local-linear adjustment (abc_ctx_set_param_transf; the definition is in the header): kinds holds
+// ABC_TRANSF_NONE / ABC_TRANSF_LOG / ABC_TRANSF_LOGIT per parameter, lo / hi the bounds of the LOGIT entries (may be empty when
+// there is none).  The setting stays in the process's context until it is cleared: every call above and below that regresses then
+// fits on the transformed scale and returns adjusted rows carried back into the support.
+inline void set_param_transf(const std::vector<int>& kinds, const std::vector<double>& lo = {}, const std::vector<double>& hi = {}) {
+    if ((!lo.empty() && lo.size() != kinds.size()) || (!hi.empty() && hi.size() != kinds.size()))
+        throw HipError(ABC_ERR_INVALID, "set_param_transf: lo and hi need one entry per parameter");
+    const std::vector<int32_t> k(kinds.begin(), kinds.end());
+    const abc_param_transf_t tf = {k.size(), k.data(), lo.empty() ? nullptr : lo.data(), hi.empty() ? nullptr : hi.data()};
+    check(abc_ctx_set_param_transf(context(), &tf));
+}
+inline void clear_param_transf() { check(abc_ctx_set_param_transf(context(), nullptr)); }
+// the context's transforms over the columns of V (rows x P), forward or (inverse) back; with nothing set a copy
+inline Mat2D param_transf(const Mat2D& V, bool inverse = false) {
+    Mat2D out(V.rows(), V.cols());
+    check(abc_param_transf(context(), V.data(), V.rows(), V.cols(), inverse ? 1 : 0, out.data()));
+    return out;
+}
 // Tolerance path (abc_particle_ranking_pls_targets_path): ONE ranking at K_max = Ks.back(), then the rejection mean and the
 // local-linear fit at every tolerance of the strictly ascending list Ks (at most 16), each from the first Ks[t] rows only.  Per
 // target: the K_max rows, post_mean (T x P), alpha (T x P: the adjusted posterior means), the bandwidths h, rank and status (T).

@@ -154,6 +154,21 @@ def rank_targets_adjust(X, model, A, targets, K, Y, exclude=None, kernel=_lib.KE
     return r
 
 
+def param_transf(V, inverse=False, ctx=None):
+    """The context's parameter transforms (Context.set_param_transf) over V, a (P, n) column-major holder (a view with a row
+    stride >= n is fine): forward, or back with inverse=True (abc_param_transf_dev).  With nothing set it copies.  Returns a
+    new contiguous (P, n) tensor."""
+    assert V.dim() == 2 and (V.stride(1) == 1 or V.shape[1] == 1)
+    P, n = V.shape
+    dev = V.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    out = torch.empty((P, n), dtype=torch.float64, device=dev)
+    ctx.check(lib().abc_param_transf_dev(ctx.handle, V.data_ptr(), V.stride(0) if P > 1 else n, n, P, int(bool(inverse)),
+                                         out.data_ptr(), n))
+    return out
+
+
 def _path_ks(Ks):
     """The tolerance list as a uint64 array (it stays in host memory) and its largest entry."""
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))

@@ -421,6 +421,41 @@ int abc_particle_ranking_pls_targets_adjust(abc_ctx* ctx, const double* X, const
                                             const uint64_t* exclude, size_t K, int kernel, uint64_t* idx, double* dist,
                                             const abc_adjust_out* out, int32_t* ncomp);
 
+/* ---- log and logit parameter transforms of the local-linear adjustment (R abc: transf = c("log", "logit"), logit.bounds) ------
+ * The adjustment above regresses the parameters on their raw scale, so theta* = theta - beta' x can leave a parameter's support (a
+ * rate below 0, a probability past 1).  With transforms set, the regression runs on a transformed scale and the adjusted rows are
+ * carried back, so they stay inside the support.  Each parameter j has a kind; LOGIT also has finite bounds lo_j < hi_j.
+ *   forward  NONE   t = y, copied bit for bit (signed zeros and NaNs pass through)
+ *            LOG    t = log(y) for finite y > 0, otherwise NaN (y == 0 gives NaN, not -inf)
+ *            LOGIT  t = log((y - lo) / (hi - y)) for lo < y < hi, otherwise NaN
+ *   back     a NaN t gives NaN (tested first);  NONE y = t;  LOG y = exp(t);
+ *            LOGIT  s = 1.0 / (1.0 + exp(-t)), y = fma(hi - lo, s, lo), then clamped to [lo, hi]; t = -inf gives lo, t = +inf gives hi
+ * Every kernel takes these operations from one device header (csrc/transf_dev.h), so a value has the same bits wherever it is made.
+ * With a setting active, the local-linear fit of a target is the definition above with theta_e = forward(Y[i_e, :]):
+ *   coef (alpha, beta), rank and status are on the transformed scale; the weights are unchanged;
+ *   the adjusted row is back(theta*_e): the bits abc_adjust_out.theta holds and the values v_e every product sees under method 1
+ *   (summary, density, joint, draws, path summary).  Quantiles, densities, covariances, bandwidths and the smoothing of smoothed
+ *   draws work on the parameter's own scale, after the back-transform: a density grid or a smoothed draw may still pass a bound, as
+ *   in R.  An out-of-domain Y entry in a retained row makes that (target, parameter) NaN and nothing else, as a NaN parameter does.
+ * Unchanged bit for bit whether or not a setting is active: idx, dist, the PLS fit of the host entries (fitted on the raw Y),
+ * everything under method 0 (rejection), the path's post_mean and h, the generic abc_weighted_* entries, the generation path.
+ * The setting lives in the context (as abc_ctx_set_weight_kernel's): it is copied at set time; NULL, P = 0 or every kind NONE turn
+ * it off (the default).  ABC_ERR_INVALID at set time for P > 1024, a kind outside 0..2, NULL kind, and a LOGIT entry whose bounds
+ * are NULL, non-finite or not lo < hi.  A call that regresses (abc_rank_targets_adjust_dev, the path calls that fit, every product
+ * under method 1, and their host forms) under a setting with another P is refused with ABC_ERR_INVALID before anything is queued;
+ * calls that do not regress ignore the setting.  The forward pass costs N x P x 8 bytes of workspace and one streaming kernel. */
+enum { ABC_TRANSF_NONE = 0, ABC_TRANSF_LOG = 1, ABC_TRANSF_LOGIT = 2 };
+typedef struct { size_t P; const int32_t* kind; const double* lo; const double* hi; } abc_param_transf_t;  /* host memory; lo / hi read
+                                                                    for LOGIT entries only, may be NULL when there is none */
+int abc_ctx_set_param_transf(abc_ctx* ctx, const abc_param_transf_t* tf);
+/* The context's transforms over a column-major n x P matrix (V[i + ldv j] -> out[i + ldo j]); inverse != 0: the back direction; in
+ * place is allowed; with nothing set it copies.  ABC_ERR_INVALID for NULL V / out, ldv < n, ldo < n, and P other than the setting's. */
+int abc_param_transf_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t n, size_t P, int inverse, double* out, size_t ldo);
+int abc_param_transf(abc_ctx* ctx, const double* V, size_t n, size_t P, int inverse, double* out);   /* host pointers, ld = n */
+/* Entries of LOG / LOGIT columns that forward passes (those of the calls that regress and of abc_param_transf*) found outside
+ * their domain, non-finite ones included, since the context was created or the last reset.  Never changes a result. */
+int abc_param_transf_outside(abc_ctx* ctx, uint64_t* count, int reset);
+
 /* ---- tolerance path: one batched ranking, the rejection estimate and the local-linear fit at several tolerances ------------
  * What cv4abc does with tols = c(.005, .01, .05): ONE ranking at K_max = Ks[T-1] (idx and dist, K_max x B, are the bits of
  * abc_rank_targets_dev with K = K_max; dist may be NULL), and from it an estimate at every tolerance K_t of an ascending list.
