@@ -165,6 +165,19 @@ ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_siz
 BROADCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 
+WX_REC_LEVELS = 6
+WX_PATH_NONE, WX_PATH_CASCADE, WX_PATH_CASCADE_THEN_SORTED, WX_PATH_SORTED = -1, 0, 1, 2
+
+
+class WxTestRecord(C.Structure):
+    """abc_wx_test_record (include/abcsmc_hip.h)"""
+    _fields_ = [("response", C.c_int32), ("candidate", C.c_int32), ("optimum", C.c_int32), ("n_levels", C.c_int32),
+                ("verdict", C.c_int32), ("passed", C.c_int32), ("w_taken", C.c_int32), ("pad_", C.c_int32),
+                ("nz", C.c_uint64), ("W", C.c_double),
+                ("level_bins", C.c_int64 * WX_REC_LEVELS), ("level_lo2", C.c_int64 * WX_REC_LEVELS),
+                ("level_hi2", C.c_int64 * WX_REC_LEVELS)]
+
+
 class CommCallbacks(C.Structure):
     _fields_ = [("all_reduce_sum", ALL_REDUCE_FN), ("all_gather", ALL_GATHER_FN), ("broadcast", BROADCAST_FN),
                 ("user", C.c_void_p)]
@@ -188,6 +201,8 @@ SIGNATURES = {
     "abc_ctx_set_kde_mode": (_i, [_vp, _i]),
     "abc_ctx_set_gram_mode": (_i, [_vp, _i]),
     "abc_kde_last_kernel": (_i, [_vp, _vp]),
+    "abc_ctx_set_wx_record": (_i, [_vp, _i]),
+    "abc_wx_last_record": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "abc_ctx_set_noise_mode": (_i, [_vp, _i]),
     "abc_ctx_set_weight_kernel": (_i, [_vp, _i]),
     "abc_perturb_giveups": (_i, [_vp, _vp, _i]),
@@ -393,6 +408,29 @@ class Context:
         w = C.c_int(0)
         self.check(lib().abc_kde_last_kernel(self._h, C.byref(w)))
         return w.value
+
+    def set_wx_record(self, on):
+        """switch the per-test record of the Wilcoxon reductions on this context on or off (abc_ctx_set_wx_record)"""
+        self.check(lib().abc_ctx_set_wx_record(self._h, int(bool(on))))
+
+    def wx_last_record(self):
+        """(path, tests) of the last Wilcoxon reduction run with the record on (abc_wx_last_record): path one of WX_PATH_*, tests a
+        list of dicts in plan order -- response, candidate, optimum, nz, levels [(bins, lo2, hi2), ...] (Python integers),
+        n_levels, verdict, passed, W, w_taken"""
+        n, path = C.c_size_t(0), C.c_int(0)
+        self.check(lib().abc_wx_last_record(self._h, None, 0, C.byref(n), C.byref(path)))      # (the number of tests first)
+        cap = n.value
+        buf = (WxTestRecord * max(cap, 1))()
+        if cap:
+            self.check(lib().abc_wx_last_record(self._h, buf, cap, C.byref(n), C.byref(path)))
+        out = []
+        for r in buf[:n.value]:
+            k = min(int(r.n_levels), WX_REC_LEVELS)
+            out.append(dict(response=int(r.response), candidate=int(r.candidate), optimum=int(r.optimum), nz=int(r.nz),
+                            levels=[(int(r.level_bins[i]), int(r.level_lo2[i]), int(r.level_hi2[i])) for i in range(k)],
+                            n_levels=int(r.n_levels), verdict=int(r.verdict), passed=int(r.passed), W=float(r.W),
+                            w_taken=int(r.w_taken)))
+        return path.value, out
 
     def set_weight_kernel(self, kernel):
         """WEIGHT_GAUSSIAN (the reference's, default) or WEIGHT_EPANECHNIKOV (extension): abc_ctx_set_weight_kernel"""

@@ -119,6 +119,12 @@ struct abc_ctx {
     unsigned long long wx_moved_counts, generation_repeats;      // abc_generation_repeats
     bool wx_gather_rows;     // diagnostic (ABC_DIAG=1 ABC_WX_GATHER=1, set at context creation): the sharded generation's Wilcoxon rule by
                              // gathering the validation rows on every rank (rounds 1-4) instead of the sharded cascade
+    // the per-test record of the last Wilcoxon reduction (abc_ctx_set_wx_record / abc_wx_last_record): a device allocation of the
+    // context, [256 bytes: tests, path | abc_wx_test_record x wx_rec_cap], NULL until a reduction runs with the switch on
+    int wx_record;
+    char* wx_rec_dev;
+    size_t wx_rec_cap;
+    bool wx_rec_valid;       // a reduction has written it since the switch went on
     bool in_mvn;   // the covariance pass reuses k_gram: keep it out of the k_gram stage timer
     int nev;
     struct { hipEvent_t a, b; int stage; } ev[256];

@@ -107,6 +107,7 @@ extern "C" void abc_ctx_destroy(abc_ctx* ctx) {
     if (ctx->alias_fail_dev) (void)hipFree(ctx->alias_fail_dev);
     if (ctx->tf_buf) (void)hipFree(ctx->tf_buf);
     if (ctx->tf_outside_dev) (void)hipFree(ctx->tf_outside_dev);
+    if (ctx->wx_rec_dev) (void)hipFree(ctx->wx_rec_dev);
     abc_comm_release(ctx);
     if (ctx->xbuf) (void)hipFree(ctx->xbuf);
     if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);
@@ -215,6 +216,32 @@ extern "C" int abc_kde_last_kernel(abc_ctx* ctx, int* which) {
     if (!ctx->kde_which) return ABC_OK;
     ABC_HIP(ctx, hipMemcpyAsync(which, ctx->kde_which, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ABC_OK;
+}
+
+extern "C" int abc_ctx_set_wx_record(abc_ctx* ctx, int on) {
+    if (!ctx) return ABC_ERR_INVALID;
+    ctx->wx_record = on ? 1 : 0;
+    ctx->wx_rec_valid = false;
+    return ABC_OK;
+}
+
+extern "C" int abc_wx_last_record(abc_ctx* ctx, abc_wx_test_record* out, size_t cap, size_t* ntests, int* path) {
+    if (!ctx || !ntests || !path || (cap && !out)) return ABC_ERR_INVALID;
+    *ntests = 0;
+    *path = ABC_WX_PATH_NONE;
+    if (!ctx->wx_rec_dev || !ctx->wx_rec_valid) return ABC_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) ABC_FAIL(ctx, ABC_ERR_HIP, "hipSetDevice failed");
+    if (ctx->wx_stream) ABC_HIP(ctx, hipStreamSynchronize(ctx->wx_stream));
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int hdr[2] = {0, ABC_WX_PATH_NONE};
+    ABC_HIP(ctx, hipMemcpy(hdr, ctx->wx_rec_dev, sizeof(hdr), hipMemcpyDeviceToHost));
+    size_t n = hdr[0] > 0 ? (size_t)hdr[0] : 0;
+    if (n > ctx->wx_rec_cap) n = ctx->wx_rec_cap;
+    *ntests = n;
+    *path = hdr[1];
+    const size_t take = n < cap ? n : cap;
+    if (take) ABC_HIP(ctx, hipMemcpy(out, ctx->wx_rec_dev + 256, take * sizeof(abc_wx_test_record), hipMemcpyDeviceToHost));
     return ABC_OK;
 }
 

@@ -640,7 +640,8 @@ __global__ __launch_bounds__(1024) void k_wx_bounds(int NBX, int act_n, const in
                                                     double* __restrict__ model, int M, int A, double* __restrict__ dec,
                                                     const double* __restrict__ per_keep, int stop_at_max,
                                                     const unsigned char* __restrict__ in_first /* the first half: the picked responses only */,
-                                                    const int* __restrict__ nrest_p /* ... and the number of tests outside it */) {
+                                                    const int* __restrict__ nrest_p /* ... and the number of tests outside it */,
+                                                    abc_wx_test_record* __restrict__ rec /* abc_wx_last_record; NULL: switched off */) {
     extern __shared__ unsigned int wxb_cp[];              // [NBX] packed (all keys, positive keys) of the test's bins
     __shared__ long long red[3][16];
     __shared__ unsigned long long wtot[16];
@@ -698,6 +699,12 @@ __global__ __launch_bounds__(1024) void k_wx_bounds(int NBX, int act_n, const in
             lo2 = hi2 = m = 0;
             for (int w = 0; w < 16; w++) { lo2 += red[0][w]; hi2 += red[1][w]; m += red[2][w]; }
             nz[seg] = (unsigned long long)m;
+            if (rec) {                                         // (a test is in one slot of a level, the levels follow each other on the stream)
+                abc_wx_test_record* r = rec + seg;
+                const int n = r->n_levels;
+                if (n < ABC_WX_REC_LEVELS) { r->level_bins[n] = NBX; r->level_lo2[n] = lo2; r->level_hi2[n] = hi2; }
+                r->n_levels = n + 1;
+            }
             int v = 1;                                         // no non-zero difference: p = 1, the test passes (k_wx_decide)
             if (m > 0) {
                 const double md = (double)m, sigma = sqrt(md * (md + 1.0) * (2.0 * md + 1.0) / 6.0);
@@ -1271,13 +1278,54 @@ __global__ void k_wx_commit(double* __restrict__ model, int M, int P, int A, con
     if (threadIdx.x == 0 && with_hdr) model[ML.off_hdr] = dec[P];
 }
 
+// the per-test record of a reduction (abc_wx_last_record), behind everything else of the call: what the plan, the levels (their
+// intervals are in the record already: k_wx_bounds) and the decision left.  v3 NULL: the sorted path (no bounds, every sum taken);
+// act / nact_p: the tests of the exact step.  hdr: the record's two header words (tests, path).
+__global__ __launch_bounds__(1024) void k_wx_record(abc_wx_test_record* __restrict__ rec, int* __restrict__ hdr, const WxPlan* __restrict__ plan,
+                                                    const unsigned long long* __restrict__ nz, const double* __restrict__ W,
+                                                    const int* __restrict__ v3, const unsigned char* __restrict__ pass,
+                                                    const int* __restrict__ act, const int* __restrict__ nact_p, int all_taken, int path) {
+    const int nseg = plan->nseg;
+    for (int s = threadIdx.x; s < nseg; s += blockDim.x) {
+        abc_wx_test_record* r = rec + s;
+        const int j = plan->seg_j[s];
+        r->response = j; r->candidate = plan->seg_a[s]; r->optimum = plan->astar[j];
+        r->verdict = v3 ? v3[s] : 2;
+        r->passed = pass ? (int)pass[s] : ((v3 && v3[s] == 1) ? 1 : 0);
+        r->w_taken = all_taken;
+        r->pad_ = 0;
+        r->nz = nz[s];
+        r->W = W[s];
+    }
+    __syncthreads();
+    if (act) { const int na = *nact_p; for (int i = threadIdx.x; i < na; i += blockDim.x) rec[act[i]].w_taken = 1; }
+    if (threadIdx.x == 0) { hdr[0] = nseg; hdr[1] = path; }
+}
 
 }  // namespace
+
+// the context's record buffer for a reduction of up to nseg_max tests, cleared (abc_ctx_set_wx_record off: NULL)
+static int wx_rec_prepare(abc_ctx* ctx, size_t nseg_max, abc_wx_test_record** out) {
+    *out = nullptr;
+    ctx->wx_rec_valid = false;
+    if (!ctx->wx_record || nseg_max == 0 || nseg_max > MAXSEG) return ABC_OK;
+    const size_t bytes = 256 + nseg_max * sizeof(abc_wx_test_record);
+    if (nseg_max > ctx->wx_rec_cap) {
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->wx_rec_dev) { (void)hipFree(ctx->wx_rec_dev); ctx->wx_rec_dev = nullptr; ctx->wx_rec_cap = 0; }
+        ABC_HIP(ctx, hipMalloc((void**)&ctx->wx_rec_dev, bytes));
+        ctx->wx_rec_cap = nseg_max;
+    }
+    ABC_HIP(ctx, hipMemsetAsync(ctx->wx_rec_dev, 0, bytes, ctx->stream));      // (valid once k_wx_record is queued: a call that returns early leaves none)
+    *out = (abc_wx_test_record*)(ctx->wx_rec_dev + 256);
+    return ABC_OK;
+}
+static int* wx_rec_hdr(abc_wx_test_record* rec) { return (int*)((char*)rec - 256); }
 
 // The SORTED path (rounds 1-3): every (key, segment) pair of all tests in one stable LSD radix sort.  Any shape; the fallback of
 // the binned path.  Allocates from the arena: the caller has reserved abc_wx_sorted_need().
 static int launch_wilcoxon_sorted(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M,
-                    size_t P, size_t A, size_t row_test, double* model) {
+                    size_t P, size_t A, size_t row_test, double* model, abc_wx_test_record* rec, int path) {
     if (row_test >= n) return ABC_OK;                    // empty validation set: nothing to reduce
     if (P * (A - 1) > MAXSEG)
         ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "wilcoxon: P (A - 1) = %zu tests, more than %zu", P * (A - 1), MAXSEG);
@@ -1295,6 +1343,8 @@ static int launch_wilcoxon_sorted(abc_ctx* ctx, const double* X, const double* Y
     unsigned long long* val0 = (unsigned long long*)abc_ws_alloc(ctx, nseg_max * nt * 8);
     unsigned long long* key1 = (unsigned long long*)abc_ws_alloc(ctx, nseg_max * nt * 8);
     unsigned long long* val1 = (unsigned long long*)abc_ws_alloc(ctx, nseg_max * nt * 8);
+    unsigned char* passb = rec ? (unsigned char*)abc_ws_alloc(ctx, nseg_max) : nullptr;       // (the record: the verdicts the decision used)
+    if (rec && !passb) ABC_FAIL(ctx, ABC_ERR_NOMEM, "wilcoxon: workspace exhausted (%zu segments)", nseg_max);
     if (!plan || !seg_j || !seg_a || !astar || !nz || !W || !S || !key0 || !val0 || !key1 || !val1)
         ABC_FAIL(ctx, ABC_ERR_NOMEM, "wilcoxon: workspace exhausted (%zu segments x %zu rows)", nseg_max, nt);
     hipLaunchKernelGGL(k_wx_plan, dim3(1), dim3(256), 0, ctx->stream, (const double*)model, (int)M, (int)P, (int)A, plan, seg_j, seg_a, astar,
@@ -1332,7 +1382,12 @@ static int launch_wilcoxon_sorted(abc_ctx* ctx, const double* X, const double* Y
     ABC_TRY(abc_sort_u64_bytes(ctx, key0, val0, key1, val1, tot, 0, 8));
     ABC_TRY(abc_sort_u64_bytes(ctx, val0, key0, val1, key1, tot, 4, 6));
     hipLaunchKernelGGL(k_wx_ranksum, dim3(rb, nseg_host), dim3(256), 0, ctx->stream, key0, val0, nt, plan, nz, W);
-    hipLaunchKernelGGL(k_wx_decide, dim3(1), dim3(64), 0, ctx->stream, model, (int)M, (int)P, (int)A, plan, nz, W, (unsigned char*)nullptr, (const int*)nullptr);
+    hipLaunchKernelGGL(k_wx_decide, dim3(1), dim3(64), 0, ctx->stream, model, (int)M, (int)P, (int)A, plan, nz, W, passb, (const int*)nullptr);
+    if (rec) {
+        hipLaunchKernelGGL(k_wx_record, dim3(1), dim3(1024), 0, ctx->stream, rec, wx_rec_hdr(rec), (const WxPlan*)plan, (const unsigned long long*)nz,
+                           (const double*)W, (const int*)nullptr, (const unsigned char*)passb, (const int*)nullptr, (const int*)nullptr, 1, path);
+        ctx->wx_rec_valid = true;
+    }
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
 }
@@ -1340,7 +1395,8 @@ static int launch_wilcoxon_sorted(abc_ctx* ctx, const double* X, const double* Y
 static size_t wx_sorted_need(size_t nt, size_t P, size_t A) {
     const size_t seg = P * (A > 0 ? A - 1 : 0);
     // (scores, four key / value buffers, the per-chunk digit histograms of the two radix sorts, the plan)
-    return nt * A * 8 + 4 * seg * nt * 8 + 2 * 256 * ((seg * nt) / 1024 + 2) * 4 + seg * 32 + P * 8 + (2u << 20);
+    // (... and, with the per-test record on, one byte per test for the verdicts the decision used)
+    return nt * A * 8 + 4 * seg * nt * 8 + 2 * 256 * ((seg * nt) / 1024 + 2) * 4 + seg * 32 + P * 8 + seg + 256 + (2u << 20);
 }
 
 
@@ -1565,6 +1621,7 @@ struct abc_wx_run {
     // the largest count first (k_wx_plan): the tests of first_r picked responses (actA, at most first_bound of them), then -- only
     // if none of those responses keeps its optimum -- the rest (act_rest)
     int first_r, first_bound; int* act_rest; unsigned char* in_first; bool looked0; int left0; bool decided0;
+    abc_wx_test_record* rec;           // the per-test record (abc_wx_last_record), NULL while it is switched off
 
     // one level over the tests act[0 .. nact_host) (nact on the device at nact_p): sweeps in batches, the counts (all-reduced over
     // the ranks), bounds; the last bounds work-group leaves the tests still needed in act_out / nact_out and their number in the
@@ -1578,7 +1635,12 @@ struct abc_wx_run {
         if (blds > (48u << 10)) ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_wx_bounds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds));
         for (int lo = 0; lo < nact_host;) {
             const WxLevel g = wx_level(nt, nvt, sharded, A, nact_host - lo, NBX, per_test, bc_bytes);
-            if ((size_t)g.RR * g.nslots * NBX * 4 > bc_bytes && sharded)
+            // A launch whose counters do not fit the buffer is refused, for row shards and without them: the sweep would write past the
+            // buffer's end (it did, silently, without row shards).  wx_level_one cuts a level into whole groups of tests, so what can fail
+            // to fit is ONE group, runs x <= 144 KB of counters: under a cap below that (ABC_WX_BC_CAP_KB), and -- without any cap --
+            // once the runs outgrow their target of 256 because a run is at its limit of 65535 / (1024 R) tiles: from ~1.6e7 validation
+            // rows on this rank the runs grow with the rows, and a full group (<= 144 KB a run) passes the 97 MB at ~690 runs, ~4e7 rows.
+            if ((size_t)g.RR * g.nslots * NBX * 4 > bc_bytes)
                 ABC_FAIL(ctx, ABC_ERR_NOMEM, "wilcoxon: %d runs x %d tests x %d bins do not fit the counter buffer", g.RR, g.nslots, NBX);
             const size_t lds = (size_t)g.G * per_test + (mode == 0 ? (size_t)NBX * 4 : 256) + 64, ne = (size_t)g.nslots * NBX;
             unsigned long long* totals = (unsigned long long*)abc_ws_alloc(ctx, ne * 8);
@@ -1593,7 +1655,7 @@ struct abc_wx_run {
                                nz, v3, cl, cl_ld, cl_by_test, slotmap, tickets + lvl, (unsigned int)nact_host, (const int*)astar, (int)P, (const int*)segbase,
                                act_out, nact_out, nv_ranks, nv_stride, Wr, (int*)pin, wx_no_bounds() ? 1 : 0, model, (int)M, (int)A, dec,
                                (const double*)per_keep, stop_at_max, first_half ? (const unsigned char*)in_first : (const unsigned char*)nullptr,
-                               first_half ? (const int*)(nactv + 4) : (const int*)nullptr);
+                               first_half ? (const int*)(nactv + 4) : (const int*)nullptr, rec);
             ABC_HIP(ctx, hipGetLastError());
             lo += g.nslots;
         }
@@ -1802,6 +1864,12 @@ struct abc_wx_run {
         if (exact)          // (else: the last bounds kernel has written the component counts itself)
             hipLaunchKernelGGL(k_wx_decide, dim3(1), dim3(1024), 0, st, model, (int)M, (int)P, (int)A, plan, nz, W, passb, (const int*)v3, dec,
                                (const double*)per_keep, (int*)pin);
+        if (rec) {
+            hipLaunchKernelGGL(k_wx_record, dim3(1), dim3(1024), 0, st, rec, wx_rec_hdr(rec), (const WxPlan*)plan, (const unsigned long long*)nz, (const double*)W,
+                               (const int*)v3, exact ? (const unsigned char*)passb : (const unsigned char*)nullptr,
+                               exact ? (const int*)act_cur : (const int*)nullptr, exact ? cur_n_p : (const int*)nullptr, 0, (int)ABC_WX_PATH_CASCADE);
+            ctx->wx_rec_valid = true;
+        }
         ABC_HIP(ctx, hipGetLastError());
         *fail_host = 0;
         if (exact) {
@@ -1835,6 +1903,8 @@ int launch_wilcoxon(abc_ctx* ctx, const double* X, const double* Y, size_t n, si
     if (P * (A - 1) > MAXSEG)
         ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "wilcoxon: P (A - 1) = %zu tests, more than %zu", P * (A - 1), MAXSEG);
     StageTimer tm(ctx, ST_PLS_MODEL);
+    abc_wx_test_record* rec = nullptr;
+    ABC_TRY(wx_rec_prepare(ctx, P * (A - 1), &rec));
     if (abc_wx_cascade_applies(nvt, P, A)) {
         // k_wx_decide needs the PRESS optima as the model fit left them: the cascade rewrites them, so keep a copy for a repeat
         const ModelLayout ML = model_layout(M, P, A);
@@ -1846,7 +1916,7 @@ int launch_wilcoxon(abc_ctx* ctx, const double* X, const double* Y, size_t n, si
         memset((void*)&run, 0, sizeof(run));
         run.ctx = ctx; run.X = X; run.Y = Y; run.nt = nt; run.ldx = ldx; run.ldy = ldy; run.M = M; run.P = P; run.A = A; run.row_test = row_test;
         run.model = model; run.has_sh = sh != nullptr; if (sh) run.shv = *sh;
-        run.per_keep = per_keep; run.dec = dec; run.stop_at_max = stop_at_max;
+        run.per_keep = per_keep; run.dec = dec; run.stop_at_max = stop_at_max; run.rec = rec;
         ABC_TRY(run.begin());                                   // (its plan kernel makes the copy of the PRESS optima)
         ABC_TRY(run.finish(&failed, &changed));
         static const bool force_fail = abc_diag_env("ABC_WX_FORCE_FAIL") != nullptr;   // tests: exercise the repeat
@@ -1863,14 +1933,14 @@ int launch_wilcoxon(abc_ctx* ctx, const double* X, const double* Y, size_t n, si
         ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (hipMalloc((void**)&tmp, need) != hipSuccess) ABC_FAIL(ctx, ABC_ERR_NOMEM, "wilcoxon: %zu bytes for the sorted path", need);
         ctx->ws = tmp; ctx->ws_bytes = need; ctx->ws_off = 0;
-        const int rc = launch_wilcoxon_sorted(ctx, X, Y, n, ldx, ldy, M, P, A, row_test, model);
+        const int rc = launch_wilcoxon_sorted(ctx, X, Y, n, ldx, ldy, M, P, A, row_test, model, rec, ABC_WX_PATH_CASCADE_THEN_SORTED);
         (void)hipStreamSynchronize(ctx->stream);
         ctx->ws = ws; ctx->ws_bytes = ws_bytes; ctx->ws_off = ws_off;
         (void)hipFree(tmp);
         return rc;
     }
     if (sh) return ABC_INTERNAL_RETRY;           // small sets: the caller gathers the rows
-    return launch_wilcoxon_sorted(ctx, X, Y, n, ldx, ldy, M, P, A, row_test, model);
+    return launch_wilcoxon_sorted(ctx, X, Y, n, ldx, ldy, M, P, A, row_test, model, rec, ABC_WX_PATH_SORTED);
 }
 
 // the decision of a speculative run (launch_wilcoxon with dec) into the model record, on the context's stream
@@ -1891,9 +1961,12 @@ int launch_wilcoxon_begin(abc_ctx* ctx, const double* X, const double* Y, size_t
     *out = nullptr;
     const size_t nt = n > row_test ? n - row_test : 0;
     if (!abc_wx_cascade_applies(sh ? sh->nv_total : nt, P, A) || !dec) ABC_FAIL(ctx, ABC_ERR_INVALID, "wilcoxon: not a set for the two-halves cascade");
+    abc_wx_test_record* rec = nullptr;
+    ABC_TRY(wx_rec_prepare(ctx, P * (A - 1), &rec));
     abc_wx_run* run = new (std::nothrow) abc_wx_run;
     if (!run) ABC_FAIL(ctx, ABC_ERR_NOMEM, "wilcoxon: host memory");
     memset((void*)run, 0, sizeof(*run));
+    run->rec = rec;
     run->ctx = ctx; run->X = X; run->Y = Y; run->nt = nt; run->ldx = ldx; run->ldy = ldy; run->M = M; run->P = P; run->A = A; run->row_test = row_test;
     run->model = model; run->has_sh = sh != nullptr; if (sh) run->shv = *sh;
     run->dec = dec; run->stop_at_max = stop_at_max; run->scores_hook = scores; run->hold_level0 = hold_level0 != 0;

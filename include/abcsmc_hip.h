@@ -117,6 +117,30 @@ int  abc_ctx_set_gram_mode(abc_ctx* ctx, int mode);
 /* Which of the two kernels produced the pair sums of the most recent weight call on this context (synchronises). */
 enum { ABC_KDE_RAN_NONE = 0, ABC_KDE_RAN_FP64 = 1, ABC_KDE_RAN_SPLIT = 2 };
 int  abc_kde_last_kernel(abc_ctx* ctx, int* which);
+/* What the last Wilcoxon reduction on this context (abc_pls_wilcoxon_dev, the Wilcoxon rule of a ranking or a generation) computed
+ * for each of its (response, candidate) tests, in plan order: responses ascending, candidates a' = 1 .. a* - 1 of each.  Off by
+ * default; abc_ctx_set_wx_record(ctx, 1) switches it on for the calls that follow (a device buffer of the context then takes one
+ * record per test; with it off the reduction's kernels get null pointers and nothing else about a launch changes).
+ *   nz                    non-zero paired differences; valid once a level or the sorted path has seen the test (n_levels > 0, or a
+ *                         path other than ABC_WX_PATH_CASCADE)
+ *   level_bins/lo2/hi2    for each level of the cascade of bounds the test went through, in order: its bins and the interval
+ *                         [lo2, hi2] of TWICE the signed rank sum that the level's counts leave (n_levels may exceed
+ *                         ABC_WX_REC_LEVELS: the levels beyond are not kept)
+ *   verdict               0 rejected / 1 passed by the bounds, 2 undecided by them, 3 left open as not needed (largest count first)
+ *   passed                the pass / fail the decision used (an undecided test whose sum was never taken: not meaningful)
+ *   W, w_taken            the signed rank sum, and whether the exact step or the sorted path actually took it
+ * path: how the call ended.  abc_wx_last_record synchronises; ntests = 0 and path = ABC_WX_PATH_NONE while nothing is recorded. */
+enum { ABC_WX_REC_LEVELS = 6 };
+enum { ABC_WX_PATH_NONE = -1, ABC_WX_PATH_CASCADE = 0, ABC_WX_PATH_CASCADE_THEN_SORTED = 1, ABC_WX_PATH_SORTED = 2 };
+typedef struct abc_wx_test_record {
+    int32_t response, candidate, optimum, n_levels;
+    int32_t verdict, passed, w_taken, pad_;
+    uint64_t nz;
+    double W;
+    int64_t level_bins[ABC_WX_REC_LEVELS], level_lo2[ABC_WX_REC_LEVELS], level_hi2[ABC_WX_REC_LEVELS];
+} abc_wx_test_record;
+int  abc_ctx_set_wx_record(abc_ctx* ctx, int on);
+int  abc_wx_last_record(abc_ctx* ctx, abc_wx_test_record* out, size_t cap, size_t* ntests, int* path);
 /* Kernel of the importance weights (weight_predictive_prior, set > 0).  ABC_WEIGHT_GAUSSIAN (default) is the reference's product
  * of Gaussian factors (AbcUtil.cpp:572-576).  ABC_WEIGHT_EPANECHNIKOV is an EXTENSION with no reference counterpart (the
  * reference only mentions the name in a comment, AbcUtil.cpp:476; BASELINE.json's north_star asks for it): the radial

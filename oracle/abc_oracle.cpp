@@ -289,6 +289,76 @@ double orc_wilcoxon_p(const double* e1, const double* e2, size_t n) {
     return 2.0 * (1.0 - orc_normalcdf(std::fabs(z)));
 }
 
+/* The statistic behind orc_wilcoxon_p, as integers: m = the non-zero differences d_i = |e1_i| - |e2_i|, W2 = twice the signed sum
+ * of their "average" ranks (a rank is a multiple of 1/2, so 2 W is an integer and its sum has no rounding).  Returns p as
+ * orc_wilcoxon_p does. */
+double orc_wilcoxon_stat(const double* e1, const double* e2, size_t n, int64_t* m_out, int64_t* W2_out, double* d_out) {
+    std::vector<double> ad; std::vector<int> sg;
+    ad.reserve(n); sg.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        const double d = std::fabs(e1[i]) - std::fabs(e2[i]);
+        if (d_out) d_out[i] = d;
+        if (d == 0.0) continue;
+        ad.push_back(std::fabs(d)); sg.push_back(d > 0.0 ? 1 : -1);
+    }
+    const size_t m = ad.size();
+    *m_out = static_cast<int64_t>(m);
+    *W2_out = 0;
+    if (m == 0) return 1.0;
+    std::vector<uint64_t> ord(m);
+    orc_ordered(ad.data(), m, ord.data());
+    int64_t W2 = 0;
+    for (size_t c = 0, reps; c < m; c += reps) {
+        reps = 1;
+        while (c + reps < m && ad[ord[c]] == ad[ord[c + reps]]) ++reps;
+        const int64_t rk2 = static_cast<int64_t>(2 * c + reps - 1) + 2;          /* twice ranker.h:74-75 */
+        for (size_t k = 0; k < reps; k++) W2 += sg[ord[c + k]] * rk2;
+    }
+    *W2_out = W2;
+    const double dm = static_cast<double>(m);
+    const double sigma = std::sqrt(dm * (dm + 1.0) * (2.0 * dm + 1.0) / 6.0);
+    const double z = (static_cast<double>(W2) / 2.0) / sigma;
+    return 2.0 * (1.0 - orc_normalcdf(std::fabs(z)));
+}
+
+/* Every test of the Wilcoxon reduction on a given model, in plan order (responses ascending; for response j with PRESS optimum
+ * a*_j > 1 the candidates a' = 1 .. a*_j - 1): seg_j / seg_a / astar (1-based counts), m, 2 W and p of each; d (optional, cap x nt,
+ * test-major): the paired differences |e_a*| - |e_a'| themselves.  Same inputs and residual chains as
+ * orc_pls_optimal_components.  Returns the number of tests (at most cap are written). */
+size_t orc_pls_wilcoxon_tests(const double* Xt, const double* Yt, size_t nt, size_t M, size_t P, size_t A, const double* R,
+                              const double* Q, size_t cap, int32_t* seg_j, int32_t* seg_a, int32_t* astar, int64_t* m,
+                              int64_t* W2, double* p, double* d) {
+    std::vector<double> press(A * P);
+    orc_pls_press(Xt, Yt, nt, M, P, A, R, Q, press.data());
+    std::vector<double> S(nt * A);
+    orc_pls_scores(Xt, nt, M, R, A, S.data());
+    size_t ntests = 0;
+    std::vector<double> pred(nt), e1(nt), e2(nt);
+    for (size_t j = 0; j < P; j++) {
+        size_t mi = 0;
+        for (size_t a = 1; a < A; a++) if (press[a + A * j] < press[mi + A * j]) mi = a;
+        if (mi == 0) continue;
+        std::fill(pred.begin(), pred.end(), 0.0);
+        for (size_t a = 0; a <= mi; a++) {
+            const double qja = Q[j + P * a];
+            for (size_t i = 0; i < nt; i++) pred[i] = std::fma(S[i + nt * a], qja, pred[i]);
+        }
+        for (size_t i = 0; i < nt; i++) e1[i] = Yt[i + nt * j] - pred[i];
+        std::fill(pred.begin(), pred.end(), 0.0);
+        for (size_t a = 0; a < mi; a++) {
+            const double qja = Q[j + P * a];
+            for (size_t i = 0; i < nt; i++) { pred[i] = std::fma(S[i + nt * a], qja, pred[i]); e2[i] = Yt[i + nt * j] - pred[i]; }
+            if (ntests < cap) {
+                seg_j[ntests] = static_cast<int32_t>(j); seg_a[ntests] = static_cast<int32_t>(a) + 1;
+                astar[ntests] = static_cast<int32_t>(mi) + 1;
+                p[ntests] = orc_wilcoxon_stat(e1.data(), e2.data(), nt, &m[ntests], &W2[ntests], d ? d + ntests * nt : nullptr);
+            }
+            ntests++;
+        }
+    }
+    return ntests;
+}
+
 /* [PLS] optimal_num_components (AbcUtil.cpp:447-449): argmin PRESS per response (first
  * minimum), optionally reduced to the smallest a' whose |errors| are not Wilcoxon-different
  * (alpha = 0.1).  Returns max over responses (the caller's .maxCoeff()). */

@@ -84,6 +84,10 @@ int orc_pls_optimal_components(const double* Xt, const double* Yt, size_t nt, si
                                size_t A, const double* R, const double* Q, int rule,
                                int32_t* per_response);
 double orc_wilcoxon_p(const double* e1, const double* e2, size_t n);
+double orc_wilcoxon_stat(const double* e1, const double* e2, size_t n, int64_t* m_out, int64_t* W2_out, double* d_out);
+size_t orc_pls_wilcoxon_tests(const double* Xt, const double* Yt, size_t nt, size_t M, size_t P, size_t A, const double* R,
+                              const double* Q, size_t cap, int32_t* seg_j, int32_t* seg_a, int32_t* astar, int64_t* m,
+                              int64_t* W2, double* p, double* d);
 double orc_normalcdf(double z);
 
 /* staged projection+distance with the fixed operation order shared with the HIP kernel */

@@ -63,6 +63,8 @@ def lib():
         L.orc_normalcdf.restype = C.c_double
         L.orc_normalcdf.argtypes = [C.c_double]
         L.orc_wilcoxon_p.restype = C.c_double
+        L.orc_wilcoxon_stat.restype = C.c_double
+        L.orc_pls_wilcoxon_tests.restype = C.c_size_t
         L.orc_prior_likelihood.restype = C.c_double
         L.orc_prior_likelihood.argtypes = [C.c_void_p, C.c_double]
         L.orc_prior_recast.restype = C.c_double
@@ -169,6 +171,35 @@ def pls_optimal_components(Xt, Yt, R, Q, rule=RULE_MIN_PRESS):
 def wilcoxon_p(e1, e2):
     e1, e2 = _f(e1), _f(e2)
     return lib().orc_wilcoxon_p(_p(e1), _p(e2), _sz(e1.size))
+
+
+def wilcoxon_stat(e1, e2, want_d=False):
+    """(m, 2 W, p[, d]) of the signed-rank test of |e1| against |e2|: the integers behind wilcoxon_p"""
+    e1, e2 = _f(e1), _f(e2)
+    m, W2 = C.c_int64(0), C.c_int64(0)
+    d = np.empty(e1.size) if want_d else None
+    p = lib().orc_wilcoxon_stat(_p(e1), _p(e2), _sz(e1.size), C.byref(m), C.byref(W2), _p(d))
+    return (m.value, W2.value, p, d) if want_d else (m.value, W2.value, p)
+
+
+def pls_wilcoxon_tests(Xt, Yt, R, Q, want_d=False):
+    """Every (response, candidate) test of the Wilcoxon reduction on the given model, in plan order: dict(seg_j, seg_a (1-based),
+    astar, m, W2 (int64: twice the signed rank sum), p[, d (tests x nt): the paired differences])."""
+    Xt, Yt, R, Q = _f(Xt), _f(Yt), _f(R), _f(Q)
+    nt, M = Xt.shape; P = Yt.shape[1]; A = R.shape[1]
+    cap = P * max(A - 1, 0)
+    seg_j, seg_a, astar = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+    m, W2, p = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64), np.ones(cap)
+    args = [_p(Xt), _p(Yt), _sz(nt), _sz(M), _sz(P), _sz(A), _p(R), _p(Q), _sz(cap), _p(seg_j), _p(seg_a), _p(astar), _p(m), _p(W2), _p(p)]
+    d = None
+    if want_d:                       # (the number of tests first: the differences are tests x nt doubles)
+        n = lib().orc_pls_wilcoxon_tests(*(args[:8] + [_sz(0)] + args[9:] + [None]))
+        d = np.zeros((n, nt))
+    n = lib().orc_pls_wilcoxon_tests(*(args + [_p(d)]))
+    out = dict(seg_j=seg_j[:n], seg_a=seg_a[:n], astar=astar[:n], m=m[:n], W2=W2[:n], p=p[:n])
+    if want_d:
+        out["d"] = d
+    return out
 
 
 def project_distance(X, mean, sd, R, a, obs_scores):

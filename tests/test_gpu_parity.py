@@ -1702,43 +1702,31 @@ def test_gram_mode_is_a_public_setting(gpu_ctx):
     assert _lib.lib().abc_ctx_set_gram_mode(gpu_ctx.handle, 7) == _lib.lib().abc_ctx_set_gram_mode(None, 0) != 0
 
 
-def _wilcoxon_per_response(gpu_ctx, oracle, X, Y, obs, A, f=0.5):
+def _wilcoxon_per_response(gpu_ctx, oracle, X, Y, obs, A, f=0.5, near_ok=False):
     """The Wilcoxon reduction alone, through the staged entry points: statistics -> model under argmin PRESS -> abc_pls_wilcoxon_dev;
     the per-response component counts it leaves in the model record against the oracle's reduction RUN ON THE DEVICE'S OWN MODEL
-    (its loadings, means and deviations: the residuals are then the same bits on both sides, and so is every rank sum)."""
-    import torch
-    from abcsmc_amd import _lib, device, sharded
-    lib = _lib.lib()
+    (its loadings, means and deviations: the residuals are then the same bits on both sides, and so is every rank sum).
+    The call runs twice: as it always did, and with the per-test record on (abc_wx_last_record) -- the model record it leaves is
+    the same bytes, and every test's count of non-zero differences, rank sum, bounds and verdict are held against the oracle's
+    statistic (tests/_wx_record.py).  No bounds verdict may go unchecked because its reference p lies within 1e-9 of 0.1 -- the
+    fixed seeds of the tests have none; near_ok (the fuzzer's random sets) only reports them."""
+    import _wx_record
     N, M = X.shape
     P = Y.shape[1]
-    dev = "cuda:0"
-    be = sharded.HipBackend(dev, gpu_ctx)
-    dX, dY, dobs = device.colmajor(X, dev), device.colmajor(Y, dev), device.colmajor(obs, dev)
-    ntrain = int(round(N * f))
-    stats = be.zeros(be.stats_len(M, P))
-    L = be.model_len(M, P, A)
-    model = be.zeros(L + 8)
-    be.stats_shift(dX, dY, stats)
-    be.stats_accumulate(dX, dY, 0, ntrain, stats)
-    be.pls_model(stats, dobs, M, P, A, _lib.RULE_MIN_PRESS, model)
-    torch.cuda.synchronize()
-    m0 = model.cpu().numpy().copy()
-    gpu_ctx.check(lib.abc_pls_wilcoxon_dev(gpu_ctx.handle, dX.data_ptr(), dY.data_ptr(), N, N, N, M, P, A, ntrain, model.data_ptr()))
-    torch.cuda.synchronize()
-    m1 = model.cpu().numpy()
-    off_mean, off_sd = 4, 4 + M + P
-    off_R = off_sd + (M + P) + M + A
-    off_Q = off_R + M * A
-    off_per = L - P
-    per_press, per_wx = m0[off_per:L].astype(int), m1[off_per:L].astype(int)
-    mean, sd = m0[off_mean:off_mean + M + P], m0[off_sd:off_sd + M + P]
-    R = np.asfortranarray(m0[off_R:off_R + M * A].reshape(A, M).T)
-    Q = np.asfortranarray(m0[off_Q:off_Q + P * A].reshape(A, P).T)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        Zx = np.where(sd[:M] == 0, 0.0, (X[ntrain:] - mean[:M]) / sd[:M])
-        Zy = np.where(sd[M:] == 0, 0.0, (Y[ntrain:] - mean[M:]) / sd[M:])
+    on = _wx_record.run_reduction(gpu_ctx, X, Y, obs, A, f, record=True, both="off first")
+    m0, m1, ntrain = on["m0"], on["m1_off"], on["ntrain"]
+    assert on["m1"].tobytes() == m1.tobytes()
+    L = len(m0) - 8
+    Zx, Zy, R, Q, per_press = _wx_record.oracle_inputs(X, Y, m0, A, ntrain)
+    per_wx = m1[L - P:L].astype(int)
     _, o_press = oracle.pls_optimal_components(Zx, Zy, R, Q, oracle.RULE_MIN_PRESS)
     _, o_wx = oracle.pls_optimal_components(Zx, Zy, R, Q, oracle.RULE_WILCOXON)
+    if np.array_equal(per_press, o_press):                # (else the caller's first assertion fails: different tests on the two sides)
+        ref = _wx_record.reference(oracle, X, Y, m0, A, ntrain)
+        out = _wx_record.check_record(on["path"], on["rec"], ref, m1, P, label="N=%d P=%d A=%d" % (N, P, A))
+        print("wilcoxon record: %d tests, path %d, %d sums taken, %d verdicts by the bounds (%d next to the threshold left out), levels %s"
+              % (len(on["rec"]), on["path"], out["taken"], out["settled"], out["left_out"], sorted(out["levels"].items())))
+        assert near_ok or (not ref["near"] and out["left_out"] == 0), ref["near"]
     return per_press, per_wx, o_press.astype(int), o_wx.astype(int), int(m1[0])
 
 
@@ -1748,12 +1736,14 @@ def _wilcoxon_per_response(gpu_ctx, oracle, X, Y, obs, A, f=0.5):
     (6000, 12, 5, 5, "zeros"),             # responses the model predicts equally well at several counts: zero differences dropped
     (40_000, 16, 6, 8, "plain"),           # 2e4 validation rows: 16 bins
     (40_000, 16, 6, 8, "pairs"),
-    (300_000, 32, 16, 8, "plain"),         # 1.5e5 rows, 128 bins, up to 112 tests
-    (300_000, 24, 8, 16, "plain"),         # two rows per thread (9..16 components)
+    (300_000, 32, 16, 8, "plain"),         # 1.5e5 rows, up to 112 tests: one group of tests, 37 tiles -- one row per thread (_wx_dispatch.py)
+    (300_000, 24, 8, 16, "plain"),         # 9..16 components: 74 tiles of two rows per thread are fewer than 192 -- one row per thread
     (200_000, 40, 6, 24, "plain"),         # one row per thread (17..32 components)
     (300_000, 16, 4, 6, "copies50"),       # 50 distinct validation rows: tie groups of 3000, a few values per bin
-    (300_000, 16, 4, 6, "copies8"),        # 8 distinct rows: groups of 18750 outgrow a bin -> the build repeats on the sorted path
-    (10_000_000, 8, 2, 4, "plain"),        # 5e6 validation rows (configs[3]'s count): 4096 bins, 8192 fine bins of the bounds sweep
+    (300_000, 16, 4, 6, "copies8"),        # 8 distinct rows: groups of 18750 would outgrow a bin of the exact step -- but a tie group has one
+                                           # sign, so level 0's bounds are points and settle every test (the record: path 0, one level); the
+                                           # repeat on the sorted path is reached in test_gpu_wilcoxon.py (two distinct rows, every test forced)
+    (10_000_000, 8, 2, 4, "plain"),        # 5e6 validation rows (configs[3]'s count): level 0 at four rows per thread (k_wx_sweep<8, 4, 0>)
 ])
 def test_wilcoxon_reduction_per_response_binned_path(gpu_ctx, oracle, N, M, P, A, kind):
     """Round 4's binned rank sums (wilcoxon.hip): per response the reduced component count equals the oracle's, on plain data, on
