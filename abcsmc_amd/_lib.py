@@ -227,6 +227,9 @@ SIGNATURES = {
     "abc_param_transf_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _sz]),
     "abc_param_transf": (_i, [_vp, _vp, _sz, _sz, _i, _vp]),
     "abc_param_transf_outside": (_i, [_vp, _vp, _i]),
+    "abc_ctx_set_adjust_hcorr": (_i, [_vp, _i]),
+    "abc_adjust_last_hcorr": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "abc_adjust_hcorr_skipped": (_i, [_vp, _vp, _i]),
     "abc_rank_targets_adjust_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _vp, _vp,
                                          _vp]),
     "abc_particle_ranking_pls_targets_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _vp, _vp,
@@ -330,6 +333,7 @@ class Context:
         if rc:
             raise AbcError(rc, "abc_ctx_create(device=%d) failed: no usable GPU (HIP path is mandatory)" % device)
         self.device = device
+        self._hcorr = False          # the variance correction as set through this object (adjust_hcorr restores it)
 
     @classmethod
     def from_handle(cls, handle, device):
@@ -337,6 +341,7 @@ class Context:
         self = cls.__new__(cls)
         self._h = C.c_void_p(handle)
         self.device = int(device)
+        self._hcorr = False
         self._borrowed = True
         return self
 
@@ -487,6 +492,44 @@ class Context:
         """entries the forward transforms found outside their domain (abc_param_transf_outside)"""
         n = C.c_uint64(0)
         self.check(lib().abc_param_transf_outside(self._h, C.byref(n), int(reset)))
+        return n.value
+
+    def set_adjust_hcorr(self, on):
+        """The heteroscedastic variance correction of the local-linear adjustment (abc_ctx_set_adjust_hcorr; the definition is
+        in the header): on or off (the default).  It applies to every call of this context that regresses."""
+        self.check(lib().abc_ctx_set_adjust_hcorr(self._h, int(on)))
+        self._hcorr = bool(on)
+
+    def adjust_hcorr(self, on=True):
+        """Context manager: set_adjust_hcorr(on) inside the block, what was set before (through this object) after it."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            before = self._hcorr
+            self.set_adjust_hcorr(on)
+            try:
+                yield self
+            finally:
+                self.set_adjust_hcorr(before)
+        return scope()
+
+    def last_hcorr(self):
+        """hcoef of the last regressing call made under the variance correction (abc_adjust_last_hcorr): an array of shape
+        (slots, A + 1, P), row 0 the log residual variance at the observation (NaN: the parameter was skipped), row 1 + k the
+        slope g_k; (0, 0, 0) while there is nothing"""
+        import numpy as np
+        n, a1, P = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self.check(lib().abc_adjust_last_hcorr(self._h, None, 0, C.byref(n), C.byref(a1), C.byref(P)))
+        out = np.empty((n.value, a1.value, P.value))
+        if out.size:
+            self.check(lib().abc_adjust_last_hcorr(self._h, out.ctypes.data, out.size, C.byref(n), C.byref(a1), C.byref(P)))
+        return out
+
+    def adjust_hcorr_skipped(self, reset=False):
+        """(slot, parameter) pairs the variance correction skipped (abc_adjust_hcorr_skipped)"""
+        n = C.c_uint64(0)
+        self.check(lib().abc_adjust_hcorr_skipped(self._h, C.byref(n), int(reset)))
         return n.value
 
     def set_alias_mode(self, mode):

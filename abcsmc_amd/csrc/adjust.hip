@@ -18,6 +18,16 @@
 //                       once and the tolerances' chains run interleaved over the same LDS reads; tolerance t's chain stops at row K_t
 //   k_adj_solve         grid (targets, tolerances): the blocks of the chunks below K_t
 //   k_path_mean         the rejection mean of the first K_t rows and the bandwidth
+// Under the heteroscedastic variance correction (abc_ctx_set_adjust_hcorr) a second fit follows every first one:
+//   k_adj_moments2  grid (row chunks, targets): the chunk's rows staged raw, the parameter columns turned into z = 2 log|v - alpha|
+//                   (v with aj_adjusted's bits) minus the first row's z, the scores shifted as in the first pass; the same ascending
+//                   fma chains for the (1 + nc) x P block [1 x'] w z' only.  The tolerance path runs, per tolerance, the whole
+//                   chain of the adjustment with K = K_t (k_adj_moments, k_adj_solve, k_adj_moments2, k_adj_solve<true> in that
+//                   call's chunks), so that a slot of hcoef has that call's bits
+//   k_adj_solve<true>  the first fit's C from the first pass's blocks (the same sums, so the same pivots), the new right-hand sides;
+//                   hcoef, the skip rule and its counter
+// and k_adj_apply<true> rescales the residual of every made value (aj_hcorr, as sm_value<.., true> of segment_dev.h).  All three are
+// instances of their own: calls without the setting launch the code they launched before it existed.
 // Chunk sizes depend on K only, tile sizes on (nc, P) only, and the gather paths copy the same bits: a target's outputs are the
 // same alone and in any batch.
 #include <math.h>
@@ -324,15 +334,119 @@ __global__ __launch_bounds__(256) void k_adj_moments(AjSrc src, const uint64_t* 
     }
 }
 
+// the second stage's moments (the variance correction).  Grid and chunks as k_adj_moments; coefficient slot b T + tt.
+// part2[((blockIdx.y pstride + chunk) U + r) P + j] = sum over the chunk's rows e (ascending) of (w_e u_r) z'_j, u = [1, x'] as in the
+// first pass, z'_j = z_e[j] - z_0[j], z = 2 log|v_e[j] - alpha_j| with v_e[j] = aj_adjusted of the raw row (the bits k_adj_apply gives).
+// A row with a zero or non-finite residual makes entry (0, j) non-finite for good (w u_0 = w >= 0: NaN from 0 x inf, or an
+// infinity that no finite term removes), which is how k_adj_solve sees the skip rule.  cf_lds: the slot's (1 + nc) x P
+// coefficients staged in LDS.
+__global__ __launch_bounds__(256) void k_adj_moments2(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
+                                                      size_t ld, size_t K, int nc, int P, int A, int kernel, size_t CH, int TR, size_t b0,
+                                                      size_t pstride, const double* __restrict__ O, int KCO,
+                                                      const double* __restrict__ coef, int T, int tt, int cf_lds,
+                                                      double* __restrict__ part2) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int t = threadIdx.x;
+    const int U = 1 + nc, D = 1 + nc + P, Wv = nc + P, Ds = aj_stride(nc, P);
+    const int Dp = (D + 1) & ~1, TRp = (TR + 1) & ~1;
+    double* shift = sm;                  // [1 + k]: the first row's score k; [1 + nc + j]: the first row's z_j
+    double* tw = sm + Dp;                // TR weights
+    double* tv = tw + TRp;               // TR x Ds
+    double* cf = tv + (size_t)TR * Ds;   // (1 + nc) x P coefficients (cf_lds)
+    const size_t b = b0 + blockIdx.y, chunk = blockIdx.x;
+    const uint64_t* ix = idx + b * ld;
+    const double* dd = dist + b * ld;
+    const size_t e0 = chunk * CH, e1 = (e0 + CH < K) ? e0 + CH : K;
+    const double h = dd[K - 1];
+    const bool rect = kernel == 1 || aj_fallback(dd, K);
+    const size_t i0 = (size_t)ix[0];
+    const double* cg = coef + (b * (size_t)T + (size_t)tt) * (size_t)(A + 1) * P;     // alpha_j at [j], beta_kj at [(1 + k) P + j]
+    const double* ob = O + b * (size_t)KCO;
+    if (cf_lds)
+        for (int q = t; q < U * P; q += 256) cf[q] = cg[q];
+    const double* cc = cf_lds ? cf : cg;
+    for (int c = t; c < nc; c += 256) shift[1 + c] = aj_val(src, i0, c, nc);
+    __syncthreads();
+    for (int j = t; j < P; j += 256) {
+        const double v0 = aj_adjusted(aj_val(src, i0, nc + j, nc), [&](int k) { return aj_val(src, i0, k, nc) - ob[k]; }, cc + P + j,
+                                      (size_t)P, nc);
+        shift[1 + nc + j] = aj_logres(v0, cc[j]);
+    }
+    double* pp = part2 + ((size_t)blockIdx.y * pstride + chunk) * (size_t)U * P;
+    const int nrg = (U + 3) / 4, J = P * nrg;
+    const bool regs = J <= 256;
+    double racc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (size_t r0 = e0; r0 < e1; r0 += (size_t)TR) {
+        const int nr = (e1 - r0 < (size_t)TR) ? (int)(e1 - r0) : TR;
+        __syncthreads();                                        // the shift is written, the previous tile consumed
+        for (int q = t; q < nr * Wv; q += 256) {                // the rows, raw
+            const int r = q / Wv, c = q % Wv;
+            tv[r * Ds + 1 + c] = aj_val(src, (size_t)ix[r0 + r], c, nc);
+        }
+        for (int r = t; r < nr; r += 256) {
+            tv[r * Ds] = 1.0;
+            for (int c = D; c < Ds; c++) tv[r * Ds + c] = 0.0;
+            tw[r] = aj_weight(dd[r0 + r], h, rect);
+        }
+        __syncthreads();
+        for (int q = t; q < nr * P; q += 256) {                 // theta_e[j] -> z'_e[j] (its own slot; the scores are only read)
+            const int r = q / P, j = q % P;
+            double* row = tv + r * Ds;
+            const double v = aj_adjusted(row[1 + nc + j], [&](int k) { return row[1 + k] - ob[k]; }, cc + P + j, (size_t)P, nc);
+            row[1 + nc + j] = aj_logres(v, cc[j]) - shift[1 + nc + j];
+        }
+        __syncthreads();
+        for (int q = t; q < nr * nc; q += 256) {                // x' as the first pass staged it
+            const int r = q / nc, k = q % nc;
+            tv[r * Ds + 1 + k] = tv[r * Ds + 1 + k] - shift[1 + k];
+        }
+        __syncthreads();
+        if (regs) {
+            if (t < J) aj_chain(tv, tw, Ds, nr, 1 + nc + t % P, 4 * (t / P), racc);
+            continue;
+        }
+        for (int j = t; j < J; j += 256) {
+            const int jj = j % P, g = 4 * (j / P);
+            double acc[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) acc[u] = (r0 == e0 || g + u >= U) ? 0.0 : pp[(size_t)(g + u) * P + jj];
+            aj_chain(tv, tw, Ds, nr, 1 + nc + jj, g, acc);
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (g + u < U) pp[(size_t)(g + u) * P + jj] = acc[u];
+        }
+    }
+    if (regs && t < J) {
+        const int jj = t % P, g = 4 * (t / P);
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (g + u < U) pp[(size_t)(g + u) * P + jj] = racc[u];
+    }
+}
+
+// the second fit's inputs and outputs of k_adj_solve<true>
+struct AjHcSolve {
+    const double* part2;            // k_adj_moments2's blocks, nchs slots per target and tolerance
+    const double* coef;             // the first fit (read)
+    double* hcoef;                  // the second fit (written), laid out as coef, at slot b hstride + hoff
+    unsigned long long* skipped;    // (slot, parameter) pairs the skip rule took
+    size_t hstride, hoff;           // 1, 0; a tolerance path (one tolerance per launch): T, t
+};
+
 // one work-group per (target b0 + blockIdx.x, tolerance t = blockIdx.y of T; the adjustment itself: T = 1, ks.K[0] = ld = K): the
 // moments of the rows below K_t (the blocks of the chunks e0 < K_t, summed in chunk order; part holds nchs block slots per target and
-// tolerance), centred; the sweep; coef, rank and status at slot b T + t
+// tolerance), centred; the sweep; coef, rank and status at slot b T + t.
+// HC (the variance correction's second fit): C, the means and so every pivot decision from the same blocks by the same operations;
+// the right-hand sides from hs.part2, shifted by the first row's z; hs.hcoef instead of coef (a = zbar - g' xbar in row 0); a
+// parameter is skipped (NaN in row 0, zeros below) when K <= nc + 2 or its moment sum w z' is not finite; rank and status stay.
+template <bool HC>
 __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
                                                    size_t ld, AjKs ks, int T, size_t CH, int nc, int P, int A, int kernel,
                                                    const double* __restrict__ O, int KCO, const double* __restrict__ part, int nchs,
                                                    size_t b0, double* __restrict__ coef, int32_t* __restrict__ rank,
-                                                   int32_t* __restrict__ status) {
+                                                   int32_t* __restrict__ status, AjHcSolve hs) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ unsigned s_skip;
     const int t = threadIdx.x;
     const int U = 1 + nc, D = 1 + nc + P, NB = nc + AJ_RHS, ncp = (nc + 1) & ~1;
     double* C0 = sm;                        // nc x nc: the centred moments
@@ -351,6 +465,10 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
     const size_t blk = (size_t)U * D;
     const double* pb = part + (bl * T + blockIdx.y) * (size_t)nchs * blk;
     const size_t i0 = (size_t)idx[b * ld];
+    const size_t blk2 = (size_t)U * P;
+    const double* pb2 = HC ? hs.part2 + (bl * T + blockIdx.y) * (size_t)nchs * blk2 : nullptr;
+    const double* c1 = HC ? hs.coef + slot * (size_t)(A + 1) * P : nullptr;
+    if (HC && t == 0) s_skip = 0;
     for (int q = t; q < U; q += 256) {
         double s = 0.0;
         for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + q];
@@ -369,12 +487,22 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
         for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + (size_t)(1 + lo) * D + 1 + hi];
         C0[q] = fma(-xm[lo], xs[hi], s);
     }
-    double* cb = coef + slot * (size_t)(A + 1) * P;
+    double* cb = HC ? hs.hcoef + (b * hs.hstride + hs.hoff) * (size_t)(A + 1) * P : coef + slot * (size_t)(A + 1) * P;
     for (int j0 = 0; j0 == 0 || j0 < P; j0 += AJ_RHS) {
         const int nb = (P - j0 < AJ_RHS) ? P - j0 : AJ_RHS, NW = nc + nb;
         __syncthreads();                                        // C0 written, the previous batch's coefficients read
         for (int jj = t; jj < nb; jj += 256) {
             double s = 0.0;
+            if constexpr (HC) {
+                const int j = j0 + jj;
+                for (int ch = 0; ch < nch; ch++) s += pb2[ch * blk2 + j];
+                const double* ob = O + b * (size_t)KCO;
+                const double v0 = aj_adjusted(aj_val(src, i0, nc + j, nc), [&](int k) { return aj_val(src, i0, k, nc) - ob[k]; },
+                                              c1 + P + j, (size_t)P, nc);
+                ts[jj] = s;
+                tm[jj] = aj_logres(v0, c1[j]) + s / W;
+                continue;
+            }
             for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + 1 + nc + j0 + jj];
             ts[jj] = s;
             tm[jj] = aj_val(src, i0, nc + j0 + jj, nc) + s / W;
@@ -384,7 +512,11 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
         for (int q = t; q < nc * nb; q += 256) {
             const int k = q / nb, jj = q % nb;
             double s = 0.0;
-            for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + (size_t)(1 + k) * D + 1 + nc + j0 + jj];
+            if constexpr (HC) {
+                for (int ch = 0; ch < nch; ch++) s += pb2[ch * blk2 + (size_t)(1 + k) * P + j0 + jj];
+            } else {
+                for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + (size_t)(1 + k) * D + 1 + nc + j0 + jj];
+            }
             Wk[k * NB + nc + jj] = fma(-xm[k], ts[jj], s);
         }
         __syncthreads();
@@ -409,6 +541,14 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
         __syncthreads();
         for (int jj = t; jj < nb; jj += 256) {
             const int j = j0 + jj;
+            if constexpr (HC) {
+                if (K <= (size_t)nc + 2 || !isfinite(ts[jj])) {     // the skip rule
+                    cb[j] = __longlong_as_double(0x7ff8000000000000ll);
+                    for (int k = 0; k < A; k++) cb[(size_t)(1 + k) * P + j] = 0.0;
+                    atomicAdd(&s_skip, 1u);
+                    continue;
+                }
+            }
             double a = tm[jj];
             for (int k = 0; k < nc; k++) {
                 const double be = (kept[k] != 0.0) ? Wk[k * NB + nc + jj] : 0.0;
@@ -419,6 +559,11 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
             cb[j] = a;
         }
     }
+    if constexpr (HC) {
+        __syncthreads();
+        if (t == 0 && s_skip && hs.skipped) atomicAdd(hs.skipped, (unsigned long long)s_skip);
+        return;
+    }
     if (t == 0) {
         int r = 0;
         for (int k = 0; k < nc; k++) r += kept[k] != 0.0;
@@ -428,11 +573,14 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
 }
 
 // grid (tiles of TR rows, targets b0 + blockIdx.y): theta[(b K + e) P + j] = theta_e[j] - sum_k beta_kj x_e[k] (one fma chain in k
-// order), weight[b K + e] = w_e
+// order), weight[b K + e] = w_e.  HC: the variance correction on top (aj_hcorr with the second fit hcoef, unless row 0 of the
+// parameter holds the skip flag), before the back-transform
+template <bool HC>
 __global__ __launch_bounds__(256) void k_adj_apply(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist, size_t K,
                                                    int nc, int P, int A, int kernel, const double* __restrict__ O, int KCO,
                                                    const double* __restrict__ coef, int TR, int beta_lds, size_t b0, AbcTf tf,
-                                                   double* __restrict__ theta, double* __restrict__ weight) {
+                                                   double* __restrict__ theta, double* __restrict__ weight,
+                                                   const double* __restrict__ hcoef) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, Wv = nc + P;
     const size_t b = b0 + blockIdx.y, e0 = (size_t)blockIdx.x * TR;
@@ -461,7 +609,11 @@ __global__ __launch_bounds__(256) void k_adj_apply(AjSrc src, const uint64_t* __
     for (int q = t; q < nr * P; q += 256) {
         const int r = q / P, j = q % P;
         const double* x = tv + r * Wv;
-        const double v = aj_adjusted(x[nc + j], [&](int k) { return x[k]; }, bt + j, (size_t)P, nc);
+        double v = aj_adjusted(x[nc + j], [&](int k) { return x[k]; }, bt + j, (size_t)P, nc);
+        if constexpr (HC) {
+            const double* hc = hcoef + b * (size_t)(A + 1) * P + j;
+            if (!isnan(hc[0])) v = aj_hcorr(v, beta[j - P], [&](int k) { return x[k]; }, hc + P, (size_t)P, nc);
+        }
         theta[(b * K + e0 + r) * (size_t)P + j] = tf.kind ? tf_back_j(tf, j, v) : v;
     }
 }
@@ -518,6 +670,30 @@ size_t aj_part_bytes(size_t K, size_t A, size_t P) {     // one target's moment 
     return p.nch * (1 + A) * (1 + A + P) * 8;
 }
 
+size_t aj_part2_bytes(size_t K, size_t A, size_t P) {    // ... and its second-stage blocks (the variance correction)
+    const AjPlan p = aj_plan(K, 0, 0);
+    return p.nch * (1 + A) * P * 8;
+}
+
+// k_adj_moments2's tile: the slot's coefficients in LDS up to AJ_APPLY_DBL doubles, the rows in what is left of AJ_TILE_DBL (the
+// chains do not depend on the tile's rows)
+struct AjPlan2 {
+    int TR, cf_lds;
+    size_t lds;
+};
+
+AjPlan2 aj_plan2(const AjPlan& pl, int nc, int P) {
+    AjPlan2 q;
+    const int D = 1 + nc + P, Ds = aj_stride(nc, P), ncf = (1 + nc) * P;
+    q.cf_lds = ncf <= AJ_APPLY_DBL ? 1 : 0;
+    int tr = (AJ_TILE_DBL - (D + 1) - 2 - (q.cf_lds ? ncf : 0)) / (Ds + 1);
+    if (tr > 128) tr = 128;
+    if ((size_t)tr > pl.CH) tr = (int)pl.CH;
+    q.TR = tr < 1 ? 1 : tr;
+    q.lds = (size_t)(((D + 1) & ~1) + ((q.TR + 1) & ~1) + q.TR * Ds + (q.cf_lds ? ncf : 0)) * 8;      // <= 60 KiB
+    return q;
+}
+
 size_t aj_batch(size_t K, size_t A, size_t P, size_t B) {
     size_t bb = AJ_PART_BYTES / aj_part_bytes(K, A, P);
     if (bb < 1) bb = 1;
@@ -543,19 +719,20 @@ size_t aj_solve_lds(int nc) {
 
 }  // namespace
 
-size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K) {
+size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K, bool hcorr) {
     size_t b = 0;
     b += B * K * 8;                                          // distances (the caller's may be NULL)
     b += B * (A + 1) * P * 8 + 2 * B * 4;                    // coefficients, rank, status
     if (aj_use_table(N, A, P, B, K)) b += N * (A + P) * 8;   // the row-major table
     b += aj_batch(K, A, P, B) * aj_part_bytes(K, A, P);      // moment blocks of one batch
+    if (hcorr) b += aj_batch(K, A, P, B) * aj_part2_bytes(K, A, P) + 256;
     return b + 16 * 256;
 }
 
 int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
-                               abc_adj_keep* keep, const AbcTf* tf) {
+                               abc_adj_keep* keep, const AbcTf* tf, const AbcHc* hc) {
     const AbcTf tfd = tf ? *tf : AbcTf{nullptr, nullptr, nullptr};
     double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
     if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
@@ -596,16 +773,34 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
     const int D = 1 + nc + Pi;
     const size_t lds_m = (size_t)(((D + 1) & ~1) + ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, Pi)) * 8;
     const size_t lds_s = aj_solve_lds(nc);
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+    double* hcoef = (hc && Pi > 0) ? hc->hcoef : nullptr;              // the variance correction: a second fit after every first
+    const AjPlan2 p2 = aj_plan2(pl, nc, Pi);
+    double* part2 = nullptr;
+    if (hcoef) {
+        part2 = (double*)abc_ws_alloc(ctx, bb * pl.nch * (size_t)(1 + nc) * P * 8);
+        if (!part2) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+    }
+    const AjHcSolve hs0 = {nullptr, nullptr, nullptr, nullptr, 1, 0};
+    const AjHcSolve hs1 = {part2, coef, hcoef, hcoef ? hc->skipped : nullptr, 1, 0};
     AjKs ks = {};
     ks.K[0] = K;
     for (size_t b0 = 0; b0 < B; b0 += bb) {
         const size_t nb = (B - b0 < bb) ? B - b0 : bb;
         hipLaunchKernelGGL(k_adj_moments, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds_m, ctx->stream, src, (const uint64_t*)idx,
                            (const double*)d, K, K, nc, Pi, kernel, pl.CH, pl.TR, b0, pl.nch, part);
-        hipLaunchKernelGGL(k_adj_solve, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx, (const double*)d, K,
-                           ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0, coef, out->rank,
-                           out->status);
+        hipLaunchKernelGGL(k_adj_solve<false>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+                           (const double*)d, K, ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0,
+                           coef, out->rank, out->status, hs0);
+        ABC_HIP(ctx, hipGetLastError());
+        if (!hcoef) continue;
+        hipLaunchKernelGGL(k_adj_moments2, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src, (const uint64_t*)idx,
+                           (const double*)d, K, K, nc, Pi, (int)A, kernel, pl.CH, p2.TR, b0, pl.nch, sc.O, sc.KCO, (const double*)coef, 1,
+                           0, p2.cf_lds, part2);
+        hipLaunchKernelGGL(k_adj_solve<true>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+                           (const double*)d, K, ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0,
+                           (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, hs1);
         ABC_HIP(ctx, hipGetLastError());
     }
 
@@ -617,6 +812,7 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
         keep->coef = coef;
         keep->dist = d;
         keep->tf = tfd;
+        keep->hcoef = hcoef;
     }
     if (out->theta || out->weight) {
         const int Wv = nc + Pi;
@@ -625,13 +821,14 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
         if (TR < 1) TR = 1;
         const int beta_lds = (nc * Pi <= AJ_APPLY_DBL) ? 1 : 0;
         const size_t lds_a = (size_t)((((size_t)TR * Wv + 1) & ~(size_t)1) + (beta_lds ? (size_t)nc * Pi : 0)) * 8;     // <= 64 KiB
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
+        const auto apply = hcoef ? k_adj_apply<true> : k_adj_apply<false>;
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
         const size_t tiles = (K + TR - 1) / TR;
         for (size_t b0 = 0; b0 < B; b0 += AJ_MAX_GRID_Y) {
             const size_t nb = (B - b0 < AJ_MAX_GRID_Y) ? B - b0 : AJ_MAX_GRID_Y;
-            hipLaunchKernelGGL(k_adj_apply, dim3((unsigned)tiles, (unsigned)nb), dim3(256), lds_a, ctx->stream, src, (const uint64_t*)idx,
+            hipLaunchKernelGGL(apply, dim3((unsigned)tiles, (unsigned)nb), dim3(256), lds_a, ctx->stream, src, (const uint64_t*)idx,
                                (const double*)d, K, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)coef, TR, beta_lds, b0,
-                               tfd, out->theta, out->weight);
+                               tfd, out->theta, out->weight, (const double*)hcoef);
             ABC_HIP(ctx, hipGetLastError());
         }
     }
@@ -661,19 +858,20 @@ int aj_launch_moments_path(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, 
 
 }  // namespace
 
-size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T) {
+size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T, bool hcorr) {
     size_t b = 0;
     b += B * K * 8;                                                  // distances (the caller's may be NULL)
     b += B * T * (A + 1) * P * 8 + 8;                                // coefficients (the caller's may be NULL)
     if (aj_use_table(N, A, P, B, K)) b += N * (A + P) * 8;           // the row-major table
     b += aj_path_batch(K, A, P, B, T) * T * aj_part_bytes(K, A, P);  // moment blocks of one batch, every tolerance
+    if (hcorr) b += aj_path_batch(K, A, P, B, T) * aj_part2_bytes(K, A, P) + B * (A + 1) * P * 8 + 3 * 256;   // + the refit's coef
     return b + 16 * 256;
 }
 
 int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                              bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path, abc_adj_keep* keep,
-                             const double* Yt, const AbcTf* tf) {
+                             const double* Yt, const AbcTf* tf, const AbcHc* hc) {
     const int T = (int)path->T, Pi = (int)P;
     AjKs ks = {};
     for (int t = 0; t < T; t++) ks.K[t] = path->Ks[t];
@@ -694,6 +892,7 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
     src.ldy = ldy;
     const AjSrc raw = src;                                           // post_mean is of the raw Y under transforms too
     int nc = 0;
+    double* hcoef = nullptr;
     if (fit) {
         double hdr = 0.0;
         ABC_HIP(ctx, hipMemcpyAsync(&hdr, model, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -726,7 +925,21 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
         const bool wide = D * ((1 + nc + 3) / 4) > 256;              // more than 256 entry groups: k_adj_moments, once per tolerance
         const size_t lds_m = (size_t)(((D + 1) & ~1) + ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, Pi)) * 8;
         const size_t lds_s = aj_solve_lds(nc);
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+        // the variance correction: at every tolerance the fit of abc_rank_targets_adjust_dev with K = K_t over again, in that call's
+        // own chunks (coef1: its first fit, which differs from the path's coef in the last bits where the chunks of K_max and of
+        // K_t differ), then its second fit, so that slot (b, t) of hcoef has that call's bits; one tolerance at a time, the first
+        // pass's blocks in `part` once the path's own solve has read it
+        hcoef = (hc && Pi > 0) ? hc->hcoef : nullptr;
+        const size_t blk2 = (size_t)(1 + nc) * P;
+        double *part2 = nullptr, *coef1 = nullptr;
+        if (hcoef) {
+            part2 = (double*)abc_ws_alloc(ctx, bb * pl.nch * blk2 * 8);
+            coef1 = (double*)abc_ws_alloc(ctx, B * (A + 1) * P * 8 + 8);
+            if (!part2 || !coef1) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
+            ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+        }
+        const AjHcSolve hs0 = {nullptr, nullptr, nullptr, nullptr, 1, 0};
         for (size_t b0 = 0; b0 < B; b0 += bb) {
             const size_t nb = (B - b0 < bb) ? B - b0 : bb;
             if (wide) {
@@ -749,10 +962,32 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
                     hi -= n;
                 }
             }
-            hipLaunchKernelGGL(k_adj_solve, dim3((unsigned)nb, (unsigned)T), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
-                               (const double*)d, K, ks, T, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch,
-                               b0, coef, path->rank, path->status);
+            hipLaunchKernelGGL(k_adj_solve<false>, dim3((unsigned)nb, (unsigned)T), dim3(256), lds_s, ctx->stream, src,
+                               (const uint64_t*)idx, (const double*)d, K, ks, T, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO,
+                               (const double*)part, (int)pl.nch, b0, coef, path->rank, path->status, hs0);
             ABC_HIP(ctx, hipGetLastError());
+            if (!hcoef) continue;
+            for (int t = 0; t < T; t++) {
+                const size_t Kt = ks.K[t];
+                const AjPlan pt = aj_plan(Kt, nc, Pi);               // (pt.nch <= pl.nch: the chunk count does not fall with K)
+                const AjPlan2 p2 = aj_plan2(pt, nc, Pi);
+                const size_t lds_t = (size_t)(((D + 1) & ~1) + ((pt.TR + 1) & ~1) + pt.TR * aj_stride(nc, Pi)) * 8;
+                AjKs k1 = {};
+                k1.K[0] = Kt;
+                const AjHcSolve hs1 = {part2, coef1, hcoef, hc->skipped, (size_t)T, (size_t)t};
+                hipLaunchKernelGGL(k_adj_moments, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), lds_t, ctx->stream, src,
+                                   (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, kernel, pt.CH, pt.TR, b0, pt.nch, part);
+                hipLaunchKernelGGL(k_adj_solve<false>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+                                   (const double*)d, K, k1, 1, pt.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part,
+                                   (int)pt.nch, b0, coef1, (int32_t*)nullptr, (int32_t*)nullptr, hs0);
+                hipLaunchKernelGGL(k_adj_moments2, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src,
+                                   (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, (int)A, kernel, pt.CH, p2.TR, b0, pt.nch,
+                                   sc.O, sc.KCO, (const double*)coef1, 1, 0, p2.cf_lds, part2);
+                hipLaunchKernelGGL(k_adj_solve<true>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+                                   (const double*)d, K, k1, 1, pt.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part,
+                                   (int)pt.nch, b0, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, hs1);
+                ABC_HIP(ctx, hipGetLastError());
+            }
         }
         if (keep) {
             keep->src = src;
@@ -762,6 +997,7 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
             keep->coef = coef;
             keep->dist = d;
             keep->tf = (Yt && tf) ? *tf : AbcTf{nullptr, nullptr, nullptr};
+            keep->hcoef = hcoef;
         }
     }
     if (path->post_mean || path->h) {

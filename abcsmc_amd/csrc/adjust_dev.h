@@ -46,6 +46,25 @@ __device__ __forceinline__ double aj_adjusted(double th, XF x, const double* bet
     return a;
 }
 
+// ---- heteroscedastic variance correction (abc_ctx_set_adjust_hcorr; the definition is in the header) ----
+// the corrected value of a row: v the plain adjusted value (aj_adjusted's bits), alpha the stored intercept, g[k ldb] = g_kj the
+// second fit's slopes; r = v - alpha, q = sum_k g_kj x_e[k] (one fma chain from 0.0 in k order), theta** = fma(r, exp(-q / 2), alpha)
+template <class XF>
+__device__ __forceinline__ double aj_hcorr(double v, double alpha, XF x, const double* g, size_t ldb, int nc) {
+    double q = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < nc; k++) q = fma(g[(size_t)k * ldb], x(k), q);
+    return fma(v - alpha, exp(-0.5 * q), alpha);
+}
+// the second fit's response of a row: z = 2 log|v - alpha| (-inf for a zero residual, NaN or +inf for a non-finite one)
+__device__ __forceinline__ double aj_logres(double v, double alpha) { return 2.0 * log(fabs(v - alpha)); }
+
+// where a regressing call under the correction writes the second fit (the context's record) and counts the skipped parameters
+struct AbcHc {
+    double* hcoef;                  // slots x (A + 1) x P, laid out as coef; NULL: the correction is off
+    unsigned long long* skipped;    // device counter
+};
+
 // what launch_rank_targets_adjust leaves in the arena for a caller that reads the adjusted rows itself (summary.hip)
 struct abc_adj_keep {
     AjSrc src;
@@ -56,4 +75,6 @@ struct abc_adj_keep {
     const double* dist;     // B x K
     AbcTf tf;               // the parameter transforms the fit was made under (kind == NULL: none): src.Y is forward(Y), and a reader
                             // of the adjusted rows carries theta* back with tf_back_j
+    const double* hcoef;    // the variance correction's second fit, laid out as coef (NULL: off); a NaN in row 0 of a parameter:
+                            // skipped, the row is the plain adjusted value
 };

@@ -107,6 +107,8 @@ extern "C" void abc_ctx_destroy(abc_ctx* ctx) {
     if (ctx->alias_fail_dev) (void)hipFree(ctx->alias_fail_dev);
     if (ctx->tf_buf) (void)hipFree(ctx->tf_buf);
     if (ctx->tf_outside_dev) (void)hipFree(ctx->tf_outside_dev);
+    if (ctx->hc_buf) (void)hipFree(ctx->hc_buf);
+    if (ctx->hc_skipped_dev) (void)hipFree(ctx->hc_skipped_dev);
     if (ctx->wx_rec_dev) (void)hipFree(ctx->wx_rec_dev);
     abc_comm_release(ctx);
     if (ctx->xbuf) (void)hipFree(ctx->xbuf);
@@ -394,6 +396,67 @@ extern "C" int abc_ctx_set_param_transf(abc_ctx* ctx, const abc_param_transf_t* 
     ABC_HIP(ctx, hipMalloc((void**)&ctx->tf_buf, h.size() * sizeof(double)));
     ABC_HIP(ctx, hipMemcpy(ctx->tf_buf, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
     ctx->tf_P = P;
+    return ABC_OK;
+}
+
+// ---- heteroscedastic variance correction of the local-linear adjustment ------------------------------------------------------
+
+extern "C" int abc_ctx_set_adjust_hcorr(abc_ctx* ctx, int on) {
+    CHECK_CTX(ctx);
+    if (on != 0 && on != 1) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_adjust_hcorr: on = %d (0 or 1)", on);
+    if (on && !ctx->hc_skipped_dev) {
+        ABC_HIP(ctx, hipMalloc((void**)&ctx->hc_skipped_dev, sizeof(unsigned long long)));
+        ABC_HIP(ctx, hipMemset(ctx->hc_skipped_dev, 0, sizeof(unsigned long long)));
+    }
+    ctx->hcorr = on;
+    return ABC_OK;
+}
+
+// the context's record for a regressing call of `slots` fits under the setting (grown here, never while the setting is off); the
+// counts are zeroed here and set by tg_run once every launch of the call has been queued, so a call that fails leaves no record
+static int hcorr_record(abc_ctx* ctx, const char* fn, size_t slots, size_t A, size_t P, AbcHc* hc) {
+    const size_t n = slots * (A + 1) * P;
+    if (n > ctx->hc_cap) {
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->hc_buf) { ABC_HIP(ctx, hipFree(ctx->hc_buf)); ctx->hc_buf = nullptr; ctx->hc_cap = 0; }
+        ctx->hc_slots = ctx->hc_a1 = ctx->hc_P = 0;
+        if (hipMalloc((void**)&ctx->hc_buf, n * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->hc_buf = nullptr;
+            ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: no memory for the variance correction's record (%zu doubles)", fn, n);
+        }
+        ctx->hc_cap = n;
+    }
+    ctx->hc_slots = ctx->hc_a1 = ctx->hc_P = 0;         // nothing recorded until the call has queued its fits (tg_run)
+    hc->hcoef = ctx->hc_buf;
+    hc->skipped = ctx->hc_skipped_dev;
+    return ABC_OK;
+}
+
+extern "C" int abc_adjust_last_hcorr(abc_ctx* ctx, double* hcoef, size_t cap, size_t* slots, size_t* a1, size_t* P) {
+    CHECK_CTX(ctx);
+    if (!slots || !a1 || !P) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_adjust_last_hcorr: null argument (slots, a1 and P are required)");
+    *slots = ctx->hc_slots;
+    *a1 = ctx->hc_a1;
+    *P = ctx->hc_P;
+    size_t n = ctx->hc_slots * ctx->hc_a1 * ctx->hc_P;
+    if (n > cap) n = cap;
+    if (n && !hcoef) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_adjust_last_hcorr: null argument (hcoef with cap = %zu)", cap);
+    if (n) ABC_HIP(ctx, hipMemcpyAsync(hcoef, ctx->hc_buf, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ABC_OK;
+}
+
+extern "C" int abc_adjust_hcorr_skipped(abc_ctx* ctx, uint64_t* count, int reset) {
+    CHECK_CTX(ctx);
+    if (!count) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_adjust_hcorr_skipped: null argument (count is required)");
+    unsigned long long dev = 0;
+    if (ctx->hc_skipped_dev) {
+        ABC_HIP(ctx, hipMemcpyAsync(&dev, ctx->hc_skipped_dev, sizeof(dev), hipMemcpyDeviceToHost, ctx->stream));
+        if (reset) ABC_HIP(ctx, hipMemsetAsync(ctx->hc_skipped_dev, 0, sizeof(dev), ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    *count = (uint64_t)dev;
     return ABC_OK;
 }
 
@@ -1633,8 +1696,9 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     const size_t N = r.N, M = r.M, P = r.P, A = r.A, B = r.B, K = r.K;
     size_t b = abc_targets_need(N, A, B, K, r.any_excl);
     if (ctx->tf_buf && r.fits()) b += N * P * 8 + 256;                                      // forward(Y)
-    if (r.regress()) b += abc_adjust_need(N, A, P, B, K);
-    if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T);
+    const bool hc = ctx->hcorr && r.fits();
+    if (r.regress()) b += abc_adjust_need(N, A, P, B, K, hc);
+    if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T, hc);
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
     if (r.path_summary()) b += abc_path_summary_need(B, r.path->Ks, r.path->T, P, r.method) + (r.idx ? 0 : B * K * 8 + 256);
     else b += r.prod.need(B, K, P);
@@ -1650,7 +1714,7 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
 }
 
 // The ranking or (regress) the ranking with the adjustment, then the product if one is asked for; device pointers, the workspace reserved.
-static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
+static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const AbcHc* hc) {
     const size_t B = r.B, K = r.K;
     const bool summary = r.segments();
     uint64_t* ix = r.idx;
@@ -1677,7 +1741,7 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
         }
         abc_adj_keep pk;
         ABC_TRY(launch_rank_targets_path(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr, Yt, Yt ? &tf : nullptr));
+                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr, Yt, Yt ? &tf : nullptr, hc));
         if (!ps) return ABC_OK;
         SmValues pv = {};
         pv.method = r.method;
@@ -1698,7 +1762,7 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
         if (r.adj) od = *r.adj;
         ABC_TRY(launch_rank_targets_adjust(ctx, r.X, r.ldx, Yt ? Yt : r.Y, Yt ? r.N : r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt,
                                            B, r.exclude, r.any_excl, K, r.kernel, ix, d, &od, summary ? &keep : nullptr,
-                                           Yt ? &tf : nullptr));
+                                           Yt ? &tf : nullptr, hc));
     }
     if (!summary) return ABC_OK;
     SmValues sv = {};
@@ -1710,6 +1774,22 @@ static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
     sv.A = (int)r.A;
     sv.kernel = r.kernel;
     return r.prod.launch(ctx, sv, B, K, r.P, fn);
+}
+
+// tg_run_queued under the variance correction: the call's second fits go to the context's record, which names them only after
+// everything has been queued without an error
+static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
+    AbcHc hcd = {nullptr, nullptr};
+    const bool hcon = ctx->hcorr && r.fits() && r.P;
+    const size_t slots = r.kind == TG_PATH ? r.B * r.path->T : r.B;
+    if (hcon) ABC_TRY(hcorr_record(ctx, fn, slots, r.A, r.P, &hcd));
+    ABC_TRY(tg_run_queued(ctx, fn, r, hcon ? &hcd : nullptr));
+    if (hcon) {
+        ctx->hc_slots = slots;
+        ctx->hc_a1 = r.A + 1;
+        ctx->hc_P = r.P;
+    }
+    return ABC_OK;
 }
 
 static int tg_dev(abc_ctx* ctx, const char* fn, TgRequest r) {

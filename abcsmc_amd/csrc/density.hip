@@ -41,14 +41,16 @@ struct DnArgs {
     double *dens, *grid, *bw_out, *mode, *mode_dens;
 };
 
-// grid (P, targets b0 + blockIdx.y); q4: B x 4 x P quantiles at 0, 0.25, 0.75, 1
+// grid (P, targets b0 + blockIdx.y); q4: B x 4 x P quantiles at 0, 0.25, 0.75, 1.  HC: the values under the variance correction
+// (taken by the launcher only when a.hcoef is set, here and in k_dn_dens)
+template <bool HC>
 __global__ __launch_bounds__(DN_BS) void k_dn_moments(SmArgs a, DnArgs d, size_t b0, const double* __restrict__ q4,
                                                       DnSeg* __restrict__ sp) {
     __shared__ double r0[DN_BS], r1[DN_BS], r2[DN_BS];
     __shared__ unsigned rf[DN_BS];
     const int t = threadIdx.x, j = (int)blockIdx.x;
     const size_t b = b0 + blockIdx.y, sg = b * a.P + j, K = a.K;
-    const SmSeg s = sm_seg(a, b, j);
+    const SmSeg s = sm_seg<HC>(a, b, j);
     const double* q = q4 + b * 4 * (size_t)a.P + j;
     const double umin = q[0], q25 = q[a.P], q75 = q[2 * (size_t)a.P], umax = q[3 * (size_t)a.P];
     const bool bad = isnan(umin);
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(DN_BS) void k_dn_moments(SmArgs a, DnArgs d, size_t
         for (size_t e = t; e < K; e += DN_BS) {
             const double w = sm_weight(a, s, e);
             if (w > 0.0) {
-                const double v = sm_value(a, s, e);
+                const double v = sm_value<true, HC>(a, s, e);
                 W += w;
                 S2 = fma(w, w, S2);
                 A1 = fma(w, v - umin, A1);
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(DN_BS) void k_dn_moments(SmArgs a, DnArgs d, size_t
         for (size_t e = t; e < K; e += DN_BS) {
             const double w = sm_weight(a, s, e);
             if (w > 0.0) {
-                const double dv = (sm_value(a, s, e) - umin) - moff;
+                const double dv = (sm_value<true, HC>(a, s, e) - umin) - moff;
                 C2 = fma(w, dv * dv, C2);
             }
         }
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(DN_BS) void k_dn_moments(SmArgs a, DnArgs d, size_t
             const double neff = W * W / S2;
             double lo = fmin(sd, (q75 - q25) / 1.34);
             if (lo == 0.0) lo = sd;
-            if (lo == 0.0) lo = fabs(sm_value(a, s, (size_t)first));
+            if (lo == 0.0) lo = fabs(sm_value<true, HC>(a, s, (size_t)first));
             if (lo == 0.0) lo = 1.0;
             h = d.bw_scale * 0.9 * lo * pow(neff, -0.2);
         }
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(DN_BS) void k_dn_moments(SmArgs a, DnArgs d, size_t
 }
 
 // grid (P x nchunk, targets b0 + blockIdx.y); pf / pg: the chunks' candidates [segment][chunk] (nchunk > 1)
-template <bool TF>
+template <bool TF, bool HC>
 __global__ __launch_bounds__(DN_BS) void k_dn_dens(SmArgs a, DnArgs d, size_t b0, const DnSeg* __restrict__ sp, int nchunk,
                                                    double* __restrict__ pf, int* __restrict__ pg) {
     __shared__ __attribute__((aligned(16))) double2 tile[DN_TILE];
@@ -135,7 +137,7 @@ __global__ __launch_bounds__(DN_BS) void k_dn_dens(SmArgs a, DnArgs d, size_t b0
     __shared__ int rg[DN_BS];
     const int t = threadIdx.x, j = (int)(blockIdx.x % (unsigned)a.P), c = (int)(blockIdx.x / (unsigned)a.P), G = d.G;
     const size_t b = b0 + blockIdx.y, sg = b * a.P + j, K = a.K;
-    const SmSeg s = sm_seg(a, b, j);
+    const SmSeg s = sm_seg<HC>(a, b, j);
     const DnSeg p = sp[sg];
     const bool bad = isnan(p.h);
     double x[DN_R], acc[DN_R];
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(DN_BS) void k_dn_dens(SmArgs a, DnArgs d, size_t b0
             for (int i = t; i < len; i += DN_BS) {
                 const size_t e = base + (size_t)i;
                 const double w = sm_weight(a, s, e);
-                tile[i] = make_double2(sm_value<TF>(a, s, e), w > 0.0 ? w : 0.0);
+                tile[i] = make_double2(sm_value<TF, HC>(a, s, e), w > 0.0 ? w : 0.0);
             }
             __syncthreads();
 #pragma unroll 4
@@ -279,7 +281,8 @@ int launch_density_segs(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, si
     const DnArgs d = dn_args(dn);
     for (size_t b0 = 0; b0 < B; b0 += DN_MAX_GRID_Y) {
         const size_t nb = (B - b0 < DN_MAX_GRID_Y) ? B - b0 : DN_MAX_GRID_Y;
-        hipLaunchKernelGGL(k_dn_moments, dim3((unsigned)P, (unsigned)nb), dim3(DN_BS), 0, ctx->stream, a, d, b0, (const double*)q4, sp);
+        hipLaunchKernelGGL(a.hcoef ? k_dn_moments<true> : k_dn_moments<false>, dim3((unsigned)P, (unsigned)nb), dim3(DN_BS), 0,
+                           ctx->stream, a, d, b0, (const double*)q4, sp);
         ABC_HIP(ctx, hipGetLastError());
     }
     *segs = sp;
@@ -306,8 +309,9 @@ int launch_density(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t 
     for (size_t b0 = 0; b0 < B; b0 += DN_MAX_GRID_Y) {
         const size_t nb = (B - b0 < DN_MAX_GRID_Y) ? B - b0 : DN_MAX_GRID_Y;
         // (the back-transform costs k_dn_dens a wave per SIMD: calls without transforms keep the instance without it)
-        hipLaunchKernelGGL(a.tf.kind ? k_dn_dens<true> : k_dn_dens<false>, dim3((unsigned)(P * nchunk), (unsigned)nb), dim3(DN_BS), 0,
-                           ctx->stream, a, d, b0, sp, nchunk, pf, pg);
+        // (so does the variance correction's exponential: one instance with both, taken only under that setting)
+        const auto dens = a.hcoef ? k_dn_dens<true, true> : a.tf.kind ? k_dn_dens<true, false> : k_dn_dens<false, false>;
+        hipLaunchKernelGGL(dens, dim3((unsigned)(P * nchunk), (unsigned)nb), dim3(DN_BS), 0, ctx->stream, a, d, b0, sp, nchunk, pf, pg);
         ABC_HIP(ctx, hipGetLastError());
     }
     if (mode && nchunk > 1) {

@@ -116,7 +116,8 @@ __global__ __launch_bounds__(DR_BS) void k_dr_cdf(SmArgs a, size_t b0, double* _
 }
 
 // grid (blocks of DR_DB draws, targets b0 + blockIdx.y); sp: the segments' records (SMOOTH)
-template <bool SMOOTH>
+// HC: the values under the variance correction (the launcher takes it only when a.hcoef is set)
+template <bool SMOOTH, bool HC>
 __global__ __launch_bounds__(DR_BS) void k_dr_draw(SmArgs a, DrArgs d, size_t b0, const DnSeg* __restrict__ sp) {
     __shared__ double tile[DR_TILE];
     __shared__ unsigned ssrc[DR_DB];
@@ -174,7 +175,8 @@ __global__ __launch_bounds__(DR_BS) void k_dr_draw(SmArgs a, DrArgs d, size_t b0
                     SmSeg sj = seg0;                           // sm_seg(a, b, j): the members that depend on j
                     sj.j = j;
                     if (a.method == 1) sj.beta = seg0.beta + j;
-                    double v = sm_value(a, sj, e);
+                    if constexpr (HC) sm_seg_hc(a, sj);
+                    double v = sm_value<true, HC>(a, sj, e);
                     if (SMOOTH) v = fma(sp[b * P + j].h, z[k], v);
                     tile[sl * P + j] = v;
                 }
@@ -230,7 +232,8 @@ int launch_draws(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P,
     d.src = dr->src;
     d.ess = dr->ess;
     const unsigned nblk = (unsigned)((d.S + DR_DB - 1) / DR_DB);
-    const auto draw = dr->smooth ? k_dr_draw<true> : k_dr_draw<false>;
+    const auto draw = a.hcoef ? (dr->smooth ? k_dr_draw<true, true> : k_dr_draw<false, true>)
+                              : (dr->smooth ? k_dr_draw<true, false> : k_dr_draw<false, false>);
     for (size_t b0 = 0; b0 < B; b0 += DR_MAX_GRID_Y) {
         const size_t nb = (B - b0 < DR_MAX_GRID_Y) ? B - b0 : DR_MAX_GRID_Y;
         if (c || d.ess) {

@@ -45,13 +45,15 @@ struct JtArgs {
     double *mean, *cov, *corr, *dens, *mode, *mode_dens;
 };
 
-// grid (P, targets b0 + blockIdx.y); mu: B x P means, ws: B x 2 = W, S2
+// grid (P, targets b0 + blockIdx.y); mu: B x P means, ws: B x 2 = W, S2.  HC (here, in k_jt_cov and in k_jt_pair): the values under
+// the variance correction, an instance the launcher takes only when a.hcoef is set
+template <bool HC>
 __global__ __launch_bounds__(JT_BS) void k_jt_mean(SmArgs a, JtArgs d, size_t b0, const DnSeg* __restrict__ sp, double* __restrict__ mu,
                                                    double* __restrict__ ws) {
     __shared__ double r0[JT_BS], r1[JT_BS], r2[JT_BS];
     const int t = threadIdx.x, j = (int)blockIdx.x;
     const size_t b = b0 + blockIdx.y, sg = b * a.P + j, K = a.K;
-    const SmSeg s = sm_seg(a, b, j);
+    const SmSeg s = sm_seg<HC>(a, b, j);
     const bool bad = isnan(sp[sg].h);
     double W = 0.0, S2 = 0.0, A1 = 0.0;
     for (size_t e = t; e < K; e += JT_BS) {
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(JT_BS) void k_jt_mean(SmArgs a, JtArgs d, size_t b0
         if (w > 0.0) {
             W += w;
             S2 = fma(w, w, S2);
-            if (!bad) A1 = fma(w, sm_value(a, s, e), A1);
+            if (!bad) A1 = fma(w, sm_value<true, HC>(a, s, e), A1);
         }
     }
     r0[t] = W; r1[t] = S2; r2[t] = A1;
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(JT_BS) void k_jt_mean(SmArgs a, JtArgs d, size_t b0
 }
 
 // grid (tiles ti <= tj of 16 parameters, targets b0 + blockIdx.y); thread (il, jl) = (t >> 4, t & 15)
-template <bool TF>
+template <bool TF, bool HC>
 __global__ __launch_bounds__(JT_BS) void k_jt_cov(SmArgs a, JtArgs d, size_t b0, const double* __restrict__ mu,
                                                   const double* __restrict__ ws) {
     __shared__ double dv[2 * JT_CT][JT_CE + 1];
@@ -111,8 +113,8 @@ __global__ __launch_bounds__(JT_BS) void k_jt_cov(SmArgs a, JtArgs d, size_t b0,
             double v = 0.0;
             if (p < P && el < len) {
                 const double m = mu[b * P + p];
-                const SmSeg s = sm_seg(a, b, p);
-                if (!isnan(m) && sm_weight(a, s, base + (size_t)el) > 0.0) v = sm_value<TF>(a, s, base + (size_t)el) - m;
+                const SmSeg s = sm_seg<HC>(a, b, p);
+                if (!isnan(m) && sm_weight(a, s, base + (size_t)el) > 0.0) v = sm_value<TF, HC>(a, s, base + (size_t)el) - m;
             }
             dv[c][el] = v;
         }
@@ -178,7 +180,7 @@ __device__ __forceinline__ void jt_mma(jd4 (&acc)[4][4], const double (&av)[4], 
 
 // grid (npairs x nchunk, targets b0 + blockIdx.y), NW waves; wave wv takes block chunk NW + wv of the nbx x nbx blocks of 64 x 64;
 // pf / pg: the candidates [b][pair][block]
-template <int NW>
+template <int NW, bool HC>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_jt_pair(SmArgs a, JtArgs d, size_t b0, const DnSeg* __restrict__ sp,
                                                      const double* __restrict__ ws, const int* __restrict__ pairs, int nbx, int nchunk,
                                                      double* __restrict__ pf, int* __restrict__ pg) {
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int bi = live ? blk / nbx : 0, bj = live ? blk % nbx : 0;
     const size_t b = b0 + blockIdx.y, K = a.K;
     const int pi = pairs[2 * pr], pj = pairs[2 * pr + 1];
-    const SmSeg si = sm_seg(a, b, pi), sj = sm_seg(a, b, pj);
+    const SmSeg si = sm_seg<HC>(a, b, pi), sj = sm_seg<HC>(a, b, pj);
     const DnSeg qi = sp[b * a.P + pi], qj = sp[b * a.P + pj];
     const bool bad = isnan(qi.h) || isnan(qj.h);
     const int nrb = (G - 64 * bi + 15) / 16 < 4 ? (G - 64 * bi + 15) / 16 : 4;
@@ -223,8 +225,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                     const size_t e = base + (size_t)i;
                     w = sm_weight(a, si, e);
                     w = w > 0.0 ? w : 0.0;
-                    vi = sm_value(a, si, e);
-                    vj = sm_value(a, sj, e);
+                    vi = sm_value<true, HC>(a, si, e);
+                    vj = sm_value<true, HC>(a, sj, e);
                 }
                 tvi[i] = vi; tvj[i] = vj; tw[i] = w;
             }
@@ -377,22 +379,26 @@ int launch_joint(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P,
     const int nchunk = G <= 64 ? 1 : (nblk + 3) / 4;
     for (size_t b0 = 0; b0 < B; b0 += JT_MAX_GRID_Y) {
         const size_t nb = (B - b0 < JT_MAX_GRID_Y) ? B - b0 : JT_MAX_GRID_Y;
-        hipLaunchKernelGGL(k_jt_mean, dim3((unsigned)P, (unsigned)nb), dim3(JT_BS), 0, ctx->stream, a, d, b0, sp, mu, ws);
+        hipLaunchKernelGGL(a.hcoef ? k_jt_mean<true> : k_jt_mean<false>, dim3((unsigned)P, (unsigned)nb), dim3(JT_BS), 0, ctx->stream, a, d, b0, sp, mu, ws);
         ABC_HIP(ctx, hipGetLastError());
         if (d.cov || d.corr) {
             // (the back-transform costs k_jt_cov a wave per SIMD: calls without transforms keep the instance without it)
-            hipLaunchKernelGGL(a.tf.kind ? k_jt_cov<true> : k_jt_cov<false>, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)nb),
-                               dim3(JT_BS), 0, ctx->stream, a, d, b0, (const double*)mu, (const double*)ws);
+            // (the variance correction's exponential likewise: one instance with both, under that setting only)
+            const auto cov = a.hcoef ? k_jt_cov<true, true> : a.tf.kind ? k_jt_cov<true, false> : k_jt_cov<false, false>;
+            hipLaunchKernelGGL(cov, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)nb), dim3(JT_BS), 0, ctx->stream, a, d, b0,
+                               (const double*)mu, (const double*)ws);
             ABC_HIP(ctx, hipGetLastError());
         }
         if (!pair) continue;
         const dim3 grid((unsigned)(np * nchunk), (unsigned)nb);
+        const auto pair1 = a.hcoef ? k_jt_pair<1, true> : k_jt_pair<1, false>;
+        const auto pair4 = a.hcoef ? k_jt_pair<4, true> : k_jt_pair<4, false>;
         if (G <= 64)
-            hipLaunchKernelGGL(k_jt_pair<1>, grid, dim3(64), 0, ctx->stream, a, d, b0, sp, (const double*)ws, (const int*)pairs, nbx,
-                               nchunk, pf, pg);
+            hipLaunchKernelGGL(pair1, grid, dim3(64), 0, ctx->stream, a, d, b0, sp, (const double*)ws, (const int*)pairs, nbx, nchunk,
+                               pf, pg);
         else
-            hipLaunchKernelGGL(k_jt_pair<4>, grid, dim3(256), 0, ctx->stream, a, d, b0, sp, (const double*)ws, (const int*)pairs, nbx,
-                               nchunk, pf, pg);
+            hipLaunchKernelGGL(pair4, grid, dim3(256), 0, ctx->stream, a, d, b0, sp, (const double*)ws, (const int*)pairs, nbx, nchunk,
+                               pf, pg);
         ABC_HIP(ctx, hipGetLastError());
     }
     if (pair && mode) {

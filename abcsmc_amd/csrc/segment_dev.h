@@ -21,6 +21,7 @@ struct SmArgs {
     const double* coef;
     const double* dist;
     AbcTf tf;                   // method 1: the fit's parameter transforms (kind == NULL: none)
+    const double* hcoef;        // method 1: the variance correction's second fit, laid out as coef (NULL: off)
     const double* V;            // method 2
     size_t ldv;
     const double* w;
@@ -42,6 +43,8 @@ struct SmSeg {
     bool rect;
     const double* beta;         // method 1: beta_kj at beta[k P]
     const double* ob;           // method 1: the target's scores
+    const double* g;            // method 1 under the variance correction: g_kj at g[k P]; NULL: off, or this parameter is skipped
+    double alpha;               // ... and the first fit's intercept
 };
 
 // the value-making members of SmArgs from a caller's SmValues (host)
@@ -63,6 +66,7 @@ static inline SmArgs sm_args(const SmValues& sv, size_t K, size_t P) {
         a.coef = sv.adj->coef;
         a.dist = sv.adj->dist;
         a.tf = sv.adj->tf;
+        a.hcoef = sv.adj->hcoef;
     }
     a.V = sv.V;
     a.ldv = sv.ldv;
@@ -74,6 +78,19 @@ static inline SmArgs sm_args(const SmValues& sv, size_t K, size_t P) {
     return a;
 }
 
+// the variance correction's members of a method-1 segment whose slot, j and beta are set: g stays NULL for a skipped parameter
+__device__ __forceinline__ void sm_seg_hc(const SmArgs& a, SmSeg& s) {
+    const double* hc = a.hcoef + s.slot * (size_t)(a.A + 1) * a.P + s.j;
+    s.g = nullptr;
+    s.alpha = 0.0;
+    if (!isnan(hc[0])) {
+        s.g = hc + a.P;
+        s.alpha = s.beta[-(ptrdiff_t)a.P];
+    }
+}
+
+// HC: with the variance correction's members (the instances that make corrected values)
+template <bool HC = false>
 __device__ __forceinline__ SmSeg sm_seg(const SmArgs& a, size_t b, int j) {
     SmSeg s;
     s.b = b;
@@ -85,26 +102,32 @@ __device__ __forceinline__ SmSeg sm_seg(const SmArgs& a, size_t b, int j) {
     s.rect = true;
     s.beta = nullptr;
     s.ob = nullptr;
+    s.g = nullptr;
+    s.alpha = 0.0;
     if (a.method == 1) {
         s.dd = a.dist + b * a.ld;
         s.h = s.dd[a.K - 1];
         s.rect = a.kernel == 1 || aj_fallback(s.dd, a.K);
         s.beta = a.coef + s.slot * (size_t)(a.A + 1) * a.P + a.P + j;
         s.ob = a.O + b * (size_t)a.KCO;
+        if constexpr (HC) sm_seg_hc(a, s);
     }
     return s;
 }
 
 // TF = false: an instance without the back-transform for a kernel whose registers it would cost (its launcher takes it when
-// a.tf.kind == NULL, so calls without transforms run the code they ran before there were any)
-template <bool TF = true>
+// a.tf.kind == NULL, so calls without transforms run the code they ran before there were any).  HC = true: the instance with the
+// variance correction (aj_hcorr, as k_adj_apply), which a launcher takes only when a.hcoef is set, for the same reason.
+template <bool TF = true, bool HC = false>
 __device__ __forceinline__ double sm_value(const SmArgs& a, const SmSeg& s, size_t e) {
     if (a.method == 0) return a.Y[(size_t)s.ix[e] + a.ldy * (size_t)s.j];
     if (a.method == 1) {
         const size_t i = (size_t)s.ix[e];
         const int nc = a.nc;
-        const double v = aj_adjusted(aj_val(a.src, i, nc + s.j, nc), [&](int k) { return aj_val(a.src, i, k, nc) - s.ob[k]; }, s.beta,
-                                     (size_t)a.P, nc);
+        const auto x = [&](int k) { return aj_val(a.src, i, k, nc) - s.ob[k]; };
+        double v = aj_adjusted(aj_val(a.src, i, nc + s.j, nc), x, s.beta, (size_t)a.P, nc);
+        if constexpr (HC)
+            if (s.g) v = aj_hcorr(v, s.alpha, x, s.g, (size_t)a.P, nc);
         if constexpr (TF) return a.tf.kind ? tf_back_j(a.tf, s.j, v) : v;     // (the fit's scale back to the parameter's own)
         return v;
     }

@@ -56,7 +56,7 @@ __device__ __forceinline__ bool sm_less(unsigned long long ka, unsigned ia, unsi
 
 // entries e0 .. e0 + len - 1 of the segment as (key, e) pairs in key[0..n2) / id[0..n2) (n2 a power of two >= len, padding behind),
 // sorted ascending by a bitonic sort; the count of positive weights and a non-finite flag added to *cnt / *bad
-template <bool TF = true>
+template <bool TF = true, bool HC = false>
 __device__ void sm_build_sort(const SmArgs& a, const SmSeg& s, size_t e0, int len, int n2, unsigned long long* key, unsigned* id,
                               unsigned* cnt, int* bad) {
     const int t = threadIdx.x;
@@ -67,7 +67,7 @@ __device__ void sm_build_sort(const SmArgs& a, const SmSeg& s, size_t e0, int le
         unsigned i = SM_PAD_ID;
         if (r < len) {
             const size_t e = e0 + (size_t)r;
-            const double v = sm_value<TF>(a, s, e);
+            const double v = sm_value<TF, HC>(a, s, e);
             if (!isfinite(v)) nf = 1;
             i = (unsigned)e;
             if (sm_weight(a, s, e) > 0.0) {
@@ -180,7 +180,9 @@ __device__ void sm_eval(const SmArgs& a, const SmSeg& s, const SmProbs& pr, cons
     if (a.cdf && t == 0) a.cdf[s.slot * a.P + s.j] = (bad || n == 0 || isnan(tau)) ? nan : fma(0.5, E, L) / W;
 }
 
-// LDS path: grid (P, targets b0 + blockIdx.y); dynamic LDS 16 n2 bytes: keys (8 n2), then e (4 n2) overlaid by H (8 n2)
+// LDS path: grid (P, targets b0 + blockIdx.y); dynamic LDS 16 n2 bytes: keys (8 n2), then e (4 n2) overlaid by H (8 n2).  HC (here
+// and in k_sm_chunk): the values under the variance correction, an instance the launcher takes only when a.hcoef is set
+template <bool HC>
 __global__ __launch_bounds__(SM_BS) void k_sm_lds(SmArgs a, SmProbs pr, int n2, size_t b0) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long smk[];
     __shared__ double red[3 * SM_BS];
@@ -191,13 +193,14 @@ __global__ __launch_bounds__(SM_BS) void k_sm_lds(SmArgs a, SmProbs pr, int n2, 
     double* H = (double*)(smk + n2);
     if (threadIdx.x == 0) { s_cnt = 0; s_bad = 0; }
     __syncthreads();
-    const SmSeg s = sm_seg(a, b0 + blockIdx.y, (int)blockIdx.x);
-    sm_build_sort(a, s, 0, (int)a.K, n2, key, id, &s_cnt, &s_bad);
+    const SmSeg s = sm_seg<HC>(a, b0 + blockIdx.y, (int)blockIdx.x);
+    sm_build_sort<true, HC>(a, s, 0, (int)a.K, n2, key, id, &s_cnt, &s_bad);
     sm_eval(a, s, pr, key, id, H, (size_t)s_cnt, s_bad != 0, red);
 }
 
 // global path, 1: grid (chunks x P, batch targets); chunk c of segment (bl, j) sorted in LDS and written to key / id at
 // seg K + c SM_LDS_MAX, seg = bl P + j; positive weights counted into cnt[seg], non-finite values flagged in bad[seg]
+template <bool HC>
 __global__ __launch_bounds__(SM_BS) void k_sm_chunk(SmArgs a, size_t b0, unsigned long long* __restrict__ gkey, unsigned* __restrict__ gid,
                                                     unsigned* __restrict__ cnt, int* __restrict__ bad) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long key[];   // SM_LDS_MAX keys, then SM_LDS_MAX e
@@ -209,8 +212,8 @@ __global__ __launch_bounds__(SM_BS) void k_sm_chunk(SmArgs a, size_t b0, unsigne
     int n2 = 1;
     while (n2 < len) n2 <<= 1;
     const size_t seg = bl * a.P + j;
-    const SmSeg s = sm_seg(a, b0 + bl, j);
-    sm_build_sort(a, s, e0, len, n2, key, id, cnt + seg, bad + seg);
+    const SmSeg s = sm_seg<HC>(a, b0 + bl, j);
+    sm_build_sort<true, HC>(a, s, e0, len, n2, key, id, cnt + seg, bad + seg);
     unsigned long long* ok = gkey + seg * a.K + e0;
     unsigned* oi = gid + seg * a.K + e0;
     for (int r = threadIdx.x; r < len; r += SM_BS) {
@@ -494,12 +497,13 @@ int sm_launch(abc_ctx* ctx, const SmArgs& a, const SmProbs& pr, size_t B, const 
         int n2 = 1;
         while ((size_t)n2 < K) n2 <<= 1;
         const size_t lds = (size_t)n2 * (ks ? 12 : 16);
-        ABC_HIP(ctx, hipFuncSetAttribute(ks ? (const void*)k_smp_lds : (const void*)k_sm_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
+        const auto lds_k = a.hcoef ? k_sm_lds<true> : k_sm_lds<false>;
+        ABC_HIP(ctx, hipFuncSetAttribute(ks ? (const void*)k_smp_lds : (const void*)lds_k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)lds));
         for (size_t b0 = 0; b0 < B; b0 += SM_MAX_GRID_Y) {
             const size_t nb = (B - b0 < SM_MAX_GRID_Y) ? B - b0 : SM_MAX_GRID_Y;
             if (ks) hipLaunchKernelGGL(k_smp_lds, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, *ks, n2, b0);
-            else hipLaunchKernelGGL(k_sm_lds, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, n2, b0);
+            else hipLaunchKernelGGL(lds_k, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, n2, b0);
             ABC_HIP(ctx, hipGetLastError());
         }
         return ABC_OK;
@@ -515,12 +519,13 @@ int sm_launch(abc_ctx* ctx, const SmArgs& a, const SmProbs& pr, size_t B, const 
     if (!k0 || !k1 || !i0 || !i1 || !cnt || !bad) ABC_FAIL(ctx, ABC_ERR_NOMEM, "summary: workspace exhausted");
     const size_t nch = (K + SM_LDS_MAX - 1) / SM_LDS_MAX;
     const size_t lds_c = (size_t)SM_LDS_MAX * 12;
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_sm_chunk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+    const auto chunk_k = a.hcoef ? k_sm_chunk<true> : k_sm_chunk<false>;
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)chunk_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
     for (size_t b0 = 0; b0 < B; b0 += bb) {
         const size_t nb = (B - b0 < bb) ? B - b0 : bb, nseg = nb * P, total = nseg * K;
         ABC_HIP(ctx, hipMemsetAsync(cnt, 0, nseg * 4, ctx->stream));
         ABC_HIP(ctx, hipMemsetAsync(bad, 0, nseg * 4, ctx->stream));
-        hipLaunchKernelGGL(k_sm_chunk, dim3((unsigned)(nch * P), (unsigned)nb), dim3(SM_BS), lds_c, ctx->stream, a, b0, k0, i0, cnt, bad);
+        hipLaunchKernelGGL(chunk_k, dim3((unsigned)(nch * P), (unsigned)nb), dim3(SM_BS), lds_c, ctx->stream, a, b0, k0, i0, cnt, bad);
         ABC_HIP(ctx, hipGetLastError());
         unsigned long long *ka = k0, *kb = k1;
         unsigned *ia = i0, *ib = i1;

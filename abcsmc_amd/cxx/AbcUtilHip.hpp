@@ -402,6 +402,23 @@ inline Mat2D param_transf(const Mat2D& V, bool inverse = false) {
     check(abc_param_transf(context(), V.data(), V.rows(), V.cols(), inverse ? 1 : 0, out.data()));
     return out;
 }
+
+// Heteroscedastic variance correction of the local-linear adjustment (abc_ctx_set_adjust_hcorr; the definition is in the header):
+// on, every call that regresses rescales the residuals of its adjusted rows by a fitted model of the residual variance.
+inline void set_adjust_hcorr(bool on) { check(abc_ctx_set_adjust_hcorr(context(), on ? 1 : 0)); }
+
+// hcoef of the last regressing call made under the correction (abc_adjust_last_hcorr), slot after slot: (slots * (A + 1)) x P,
+// row s (A + 1) the log residual variance at the observation of slot s (NaN: skipped), the A rows after it its slopes
+inline Mat2D last_hcorr() {
+    size_t slots = 0, a1 = 0, P = 0;
+    check(abc_adjust_last_hcorr(context(), nullptr, 0, &slots, &a1, &P));
+    std::vector<double> buf(slots * a1 * P);
+    if (!buf.empty()) check(abc_adjust_last_hcorr(context(), buf.data(), buf.size(), &slots, &a1, &P));
+    Mat2D out(slots * a1, P);
+    for (size_t r = 0; r < slots * a1; r++)
+        for (size_t j = 0; j < P; j++) out(r, j) = buf[r * P + j];
+    return out;
+}
 // Tolerance path (abc_particle_ranking_pls_targets_path): ONE ranking at K_max = Ks.back(), then the rejection mean and the
 // local-linear fit at every tolerance of the strictly ascending list Ks (at most 16), each from the first Ks[t] rows only.  Per
 // target: the K_max rows, post_mean (T x P), alpha (T x P: the adjusted posterior means), the bandwidths h, rank and status (T).

@@ -169,6 +169,15 @@ def param_transf(V, inverse=False, ctx=None):
     return out
 
 
+def adjust_hcorr(on=True, ctx=None, device=0):
+    """Context manager: the heteroscedastic variance correction of the local-linear adjustment (Context.adjust_hcorr,
+    abc_ctx_set_adjust_hcorr) on ctx, or on the default context of `device`, inside the block.  Every rank_targets_* call that
+    regresses then makes its adjusted rows with the correction (rank_targets_adjust's theta, the products under method 1, the path
+    summaries); their arguments and results are otherwise unchanged, and ctx.last_hcorr() returns the call's second fit."""
+    ctx = ctx if ctx is not None else _lib.default_context(device)
+    return ctx.adjust_hcorr(on)
+
+
 def _path_ks(Ks):
     """The tolerance list as a uint64 array (it stays in host memory) and its largest entry."""
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))

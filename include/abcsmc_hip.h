@@ -480,6 +480,47 @@ int abc_param_transf(abc_ctx* ctx, const double* V, size_t n, size_t P, int inve
  * their domain, non-finite ones included, since the context was created or the last reset.  Never changes a result. */
 int abc_param_transf_outside(abc_ctx* ctx, uint64_t* count, int reset);
 
+/* ---- heteroscedastic variance correction of the local-linear adjustment (R abc: hcorr = TRUE) ----------------------------------
+ * The adjustment above shifts the retained rows along the regression; their spread stays the pooled spread of the whole tolerance
+ * window.  With this setting on, a second weighted regression models the log residual variance over the same covariates, and the
+ * residual of every adjusted row is rescaled to the variance the model gives at the observation.  Per slot (a target b, or (b, t) on
+ * a tolerance path with K = K_t rows) and per parameter j; x_e, w_e, alpha, beta, C, the kept pivots and the shift by the first
+ * retained row are the first fit's, on the transformed scale when parameter transforms are set:
+ *   1. v_e[j] = theta_e[j] - sum_k beta_kj x_e[k], the plain adjusted value (the bits the adjustment gives without the setting);
+ *      r_e[j] = v_e[j] - alpha_j, one fp64 subtraction with the stored alpha_j.
+ *   2. z_e[j] = 2 log|r_e[j]|  (R's log(residuals^2), without the underflow of the square).
+ *   3. The first fit's weighted regression with z in place of theta: the same weights and covariates, the one-pass moment scheme
+ *      shifted by the first retained row's x and z; C and its pivot decisions are the first fit's (same bits);
+ *      c2 = sum w (x - xbar)(z - zbar)', g = C^-1 c2 by the same sweep, g_k = 0 for a skipped pivot;
+ *      a_j = zbar_j - g_j' xbar: the log residual variance at the observation.  rank and status do not change.
+ *   4. q = sum_k g_kj x_e[k] (an fma chain from 0.0 in k order), f = exp(-0.5 q) = sigma(observation) / sigma(x_e),
+ *      theta**_e[j] = fma(r_e[j], f, alpha_j); under transforms the back-transform follows, unchanged.
+ *   5. Parameter j of a slot is SKIPPED when K <= nc + 2 (the first fit interpolates, the residuals are rounding noise) or when any
+ *      retained row, zero-weight rows included, has r_e[j] == 0 or non-finite (a constant parameter column, duplicated rows with
+ *      h == 0, a NaN parameter; R's lsfit errors out on these).  Then the row is v_e[j], bit for bit the plain adjustment's,
+ *      hcoef[slot][0][j] = NaN and hcoef[slot][1 + k][j] = 0.
+ *   6. hcoef is laid out as coef: slots x (A + 1) x P, row 0 = a, row 1 + k = g_k (0 for k >= nc).
+ * The correction applies wherever adjusted rows are made: abc_adjust_out.theta, and the values every product sees under method 1
+ * (summary, density, joint, draws, path summary), in the device and the host entries alike, from one device function.
+ * Unchanged under the setting: idx, dist, weight, coef (so alpha, the local-linear point estimate), rank, status, the path's
+ * post_mean and h, everything under method 0, the generic abc_weighted_* entries, the generation path.  With the setting off (the
+ * default) every output of every call keeps its bits.  The device exp and log are not bit-exact against a host library; batch
+ * invariance is: a slot's outputs are the same bits alone, in any batch and through either entry point, and every reduction's
+ * order depends on (K, nc, P) only.  On a tolerance path that holds of hcoef too: slot (b, t) is made as
+ * abc_rank_targets_adjust_dev with K = K_t makes it (that call's order of sums, its first fit computed over again), so it has
+ * that call's bits whatever K_max and the other tolerances are.  The path's own coef keeps its definition above (its sums'
+ * order depends on K_max as well) and may differ from that first fit in its last bits; the values of the path summary take
+ * alpha and beta from the path's coef and g from hcoef.
+ * The setting lives in the context (as abc_ctx_set_param_transf's); calls that do not regress ignore it.  ABC_ERR_INVALID for on
+ * outside 0 / 1.  Workspace: one more (1 + nc) x P moment block per row chunk. */
+int abc_ctx_set_adjust_hcorr(abc_ctx* ctx, int on);
+/* hcoef of the last regressing call made under the setting, copied to host memory: at most cap doubles (hcoef may be NULL when
+ * cap = 0); *slots, *a1 = A + 1 and *P are always written, 0 / 0 / 0 while there is nothing.  Synchronises.  The record lives in a
+ * device buffer of the context, allocated or grown only while the setting is on and freed with the context. */
+int abc_adjust_last_hcorr(abc_ctx* ctx, double* hcoef, size_t cap, size_t* slots, size_t* a1, size_t* P);
+/* (slot, parameter) pairs skipped by rule 5 since the context was created or the last reset. */
+int abc_adjust_hcorr_skipped(abc_ctx* ctx, uint64_t* count, int reset);
+
 /* ---- tolerance path: one batched ranking, the rejection estimate and the local-linear fit at several tolerances ------------
  * What cv4abc does with tols = c(.005, .01, .05): ONE ranking at K_max = Ks[T-1] (idx and dist, K_max x B, are the bits of
  * abc_rank_targets_dev with K = K_max; dist may be NULL), and from it an estimate at every tolerance K_t of an ascending list.
