@@ -230,6 +230,9 @@ SIGNATURES = {
     "abc_ctx_set_adjust_hcorr": (_i, [_vp, _i]),
     "abc_adjust_last_hcorr": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "abc_adjust_hcorr_skipped": (_i, [_vp, _vp, _i]),
+    "abc_ctx_set_adjust_ridge": (_i, [_vp, _vp, _sz]),
+    "abc_adjust_last_ridge": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "abc_adjust_ridge_unscored": (_i, [_vp, _vp, _i]),
     "abc_rank_targets_adjust_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _vp, _vp,
                                          _vp]),
     "abc_particle_ranking_pls_targets_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _vp, _vp,
@@ -334,6 +337,7 @@ class Context:
             raise AbcError(rc, "abc_ctx_create(device=%d) failed: no usable GPU (HIP path is mandatory)" % device)
         self.device = device
         self._hcorr = False          # the variance correction as set through this object (adjust_hcorr restores it)
+        self._ridge = ()             # the ridge penalties as set through this object (adjust_ridge restores them)
 
     @classmethod
     def from_handle(cls, handle, device):
@@ -342,6 +346,7 @@ class Context:
         self._h = C.c_void_p(handle)
         self.device = int(device)
         self._hcorr = False
+        self._ridge = ()
         self._borrowed = True
         return self
 
@@ -530,6 +535,49 @@ class Context:
         """(slot, parameter) pairs the variance correction skipped (abc_adjust_hcorr_skipped)"""
         n = C.c_uint64(0)
         self.check(lib().abc_adjust_hcorr_skipped(self._h, C.byref(n), int(reset)))
+        return n.value
+
+    def set_adjust_ridge(self, lambdas):
+        """The ridge adjustment with the penalty chosen by leave-one-out PRESS (abc_ctx_set_adjust_ridge; the definition is in the
+        header): a strictly ascending sequence of 1 to 8 finite penalties >= 0, or None / () for off (the default).  It applies
+        to every call of this context that regresses."""
+        import numpy as np
+        lam = np.ascontiguousarray(np.asarray(() if lambdas is None else lambdas, dtype=np.float64).reshape(-1))
+        self.check(lib().abc_ctx_set_adjust_ridge(self._h, lam.ctypes.data if lam.size else None, lam.size))
+        self._ridge = tuple(lam.tolist())
+
+    def adjust_ridge(self, lambdas):
+        """Context manager: set_adjust_ridge(lambdas) inside the block, what was set before (through this object) after it."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            before = self._ridge
+            self.set_adjust_ridge(lambdas)
+            try:
+                yield self
+            finally:
+                self.set_adjust_ridge(before)
+        return scope()
+
+    def last_ridge(self):
+        """(pick (slots, P) int32, press (slots, L, P)) of the last regressing call made under the ridge adjustment
+        (abc_adjust_last_ridge): the chosen penalty's index and the leave-one-out PRESS of every penalty (+inf: the fit
+        interpolates); shapes (0, 0) and (0, 0, 0) while there is nothing"""
+        import numpy as np
+        n, L, P = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self.check(lib().abc_adjust_last_ridge(self._h, None, 0, None, 0, C.byref(n), C.byref(L), C.byref(P)))
+        pick = np.empty((n.value, P.value), dtype=np.int32)
+        press = np.empty((n.value, L.value, P.value))
+        if pick.size:
+            self.check(lib().abc_adjust_last_ridge(self._h, pick.ctypes.data, pick.size, press.ctypes.data, press.size, C.byref(n),
+                                                   C.byref(L), C.byref(P)))
+        return pick, press
+
+    def adjust_ridge_unscored(self, reset=False):
+        """(slot, parameter) pairs for which no penalty could be scored (abc_adjust_ridge_unscored)"""
+        n = C.c_uint64(0)
+        self.check(lib().abc_adjust_ridge_unscored(self._h, C.byref(n), int(reset)))
         return n.value
 
     def set_alias_mode(self, mode):

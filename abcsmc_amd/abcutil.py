@@ -154,9 +154,28 @@ def untransform_params(T, transf, bounds=None):
     return Y
 
 
-def _with_transf(ctx, transf, bounds, P, call, hcorr=False):
-    """call() under the context's parameter transforms transf / bounds (None: whatever the context holds) and, with hcorr, under
-    the heteroscedastic variance correction (False: whatever the context holds); both restored afterwards"""
+def _ridge_list(ridge):
+    """ridge= as the list of penalties: one number or a sequence"""
+    return [float(v) for v in np.atleast_1d(np.asarray(ridge, dtype=np.float64)).reshape(-1)]
+
+
+def _ridge_out(ctx, o, ridge, lead):
+    """adds the ridge adjustment's record of the call just made to its result o: ridge_lambda (L,), ridge_pick lead + (P,),
+    ridge_press lead + (L, P)"""
+    pick, press = ctx.last_ridge()
+    o["ridge_lambda"] = np.asarray(_ridge_list(ridge))
+    o["ridge_pick"] = pick.reshape(lead + pick.shape[1:])
+    o["ridge_press"] = press.reshape(lead + press.shape[1:])
+    return o
+
+
+def _with_transf(ctx, transf, bounds, P, call, hcorr=False, ridge=None):
+    """call() under the context's parameter transforms transf / bounds (None: whatever the context holds), with hcorr under the
+    heteroscedastic variance correction (False: whatever the context holds) and with ridge under the ridge adjustment with those
+    penalties (None: whatever the context holds); all restored afterwards"""
+    if ridge is not None:
+        with ctx.adjust_ridge(_ridge_list(ridge)):
+            return _with_transf(ctx, transf, bounds, P, call, hcorr)
     if hcorr:
         with ctx.adjust_hcorr(True):
             return _with_transf(ctx, transf, bounds, P, call)
@@ -169,11 +188,13 @@ def _with_transf(ctx, transf, bounds, P, call, hcorr=False):
         return call()
 
 
-def _tf_kw(transf, bounds, hcorr=False):
-    """transf / bounds / hcorr as keywords for a wrapped call, only when they are given"""
+def _tf_kw(transf, bounds, hcorr=False, ridge=None):
+    """transf / bounds / hcorr / ridge as keywords for a wrapped call, only when they are given"""
     kw = {}
     if hcorr:
         kw["hcorr"] = True
+    if ridge is not None:
+        kw["ridge"] = ridge
     if transf is not None:
         kw["transf"] = transf
     if bounds is not None:
@@ -205,7 +226,7 @@ _KERNELS = {"epanechnikov": _lib.KERNEL_EPANECHNIKOV, "rectangular": _lib.KERNEL
 
 
 def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fraction, K, exclude=None, kernel="epanechnikov",
-                                        max_comp=0, rule=_lib.RULE_DEFAULT, theta=True, ctx=None, transf=None, bounds=None, hcorr=False):
+                                        max_comp=0, rule=_lib.RULE_DEFAULT, theta=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
     """particle_ranking_PLS_targets followed by the local-linear regression adjustment of every target's K rows on their PLS
     scores (abc_particle_ranking_pls_targets_adjust; Beaumont, Zhang & Balding 2002; the definition is in the header).  kernel:
     "epanechnikov" (default) or "rectangular".  Returns dict(idx (B, K), dist (B, K), theta (B, K, P): the adjusted rows, or None
@@ -220,7 +241,11 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
     the header), set in the context around this call: theta holds the rows with their residuals rescaled by the fitted model of
     the residual variance, and the dict gains hcoef (B, A + 1, P): [b, 0] the log residual variance at the observation (NaN: the
     parameter was skipped, its rows are the plain adjustment's), [b, 1 + k] its slope g_k.  coef, and so alpha and post_mean,
-    do not change."""
+    do not change.
+    ridge: None, one penalty or an ascending sequence of at most 8 (abc_ctx_set_adjust_ridge, the definition is in the header;
+    method = "ridge" of R's abc), set in the context around this call: coef, and so alpha, post_mean and theta, is per parameter
+    the ridge fit of the penalty with the smallest exact leave-one-out PRESS, and the dict gains ridge_lambda (L,), ridge_pick
+    (B, P): the chosen penalty's index, and ridge_press (B, L, P) (+inf: the fit interpolates).  rank and status do not change."""
     ctx = _ctx(ctx)
     kernel = _choice("kernel", kernel, _KERNELS)
     X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
@@ -234,18 +259,20 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
     status = np.empty(B, dtype=np.int32)
     out = _lib.AdjustOut(_p(th), _p(w), _p(coef), _p(rank), _p(status))
     ncomp = C.c_int32(0)
-    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_adjust(
+    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_adjust(
         ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K, kernel, _p(idx),
         _p(dist), C.byref(out), C.addressof(ncomp))))
     pm = coef[:, 0] if transf is None else untransform_params(coef[:, 0], transf, bounds)
     r = dict(idx=idx, dist=dist, theta=th, weight=w, coef=coef, post_mean=pm, rank=rank, status=status, ncomp=ncomp.value)
     if hcorr:
         r["hcoef"] = ctx.last_hcorr()
+    if ridge is not None:
+        _ridge_out(ctx, r, ridge, (B,))
     return r
 
 
 def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction, Ks, kernel="epanechnikov", exclude=None,
-                                      max_comp=0, rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False):
+                                      max_comp=0, rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
     """Tolerance path (abc_particle_ranking_pls_targets_path): particle_ranking_PLS_targets ONCE at K_max = Ks[-1], then the
     rejection estimate and the local-linear fit of particle_ranking_PLS_targets_adjust at every tolerance of the strictly ascending
     list Ks (at most 16): what cv4abc computes for tols = c(...), without ranking once per tolerance.  Tolerance t uses the first
@@ -255,7 +282,9 @@ def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction
     the transformed scale, post_mean (the rejection mean of the raw rows) and h do not change, and the dict gains alpha_back =
     untransform_params(alpha): the fitted value at the observation carried back, not the mean of the adjusted rows.  hcorr=True
     (as particle_ranking_PLS_targets_adjust): nothing above changes, and the dict gains hcoef (B, T, A + 1, P), the second fit at
-    every tolerance."""
+    every tolerance.  ridge (as particle_ranking_PLS_targets_adjust): coef and alpha at slot (b, t) are the ridge fit of that call
+    with K = Ks[t], and the dict gains ridge_lambda, ridge_pick (B, T, P) and ridge_press (B, T, L, P); post_mean, h, rank and
+    status do not change."""
     ctx = _ctx(ctx)
     kernel = _choice("kernel", kernel, _KERNELS)
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))
@@ -271,7 +300,7 @@ def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction
     h = np.empty((B, nt))
     path = _lib.Path(_p(ks), nt, _p(pm), _p(coef), _p(rank), _p(status), _p(h))
     ncomp = C.c_int32(0)
-    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path(
+    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path(
         ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), kernel, _p(idx),
         _p(dist), C.byref(path), C.addressof(ncomp))))
     r = dict(post_mean=pm, coef=coef, alpha=coef[:, :, 0], rank=rank, status=status, h=h, Ks=ks.astype(np.int64), idx=idx,
@@ -280,6 +309,8 @@ def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction
         r["alpha_back"] = untransform_params(coef[:, :, 0], transf, bounds)
     if hcorr:
         r["hcoef"] = ctx.last_hcorr().reshape(B, nt, A + 1, P)
+    if ridge is not None:
+        _ridge_out(ctx, r, ridge, (B, nt))
     return r
 
 
@@ -288,14 +319,16 @@ _METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_L
 
 def particle_ranking_PLS_targets_path_summary(X_orig, Y_orig, targets, training_fraction, Ks, probs=(0.025, 0.5, 0.975), truth=None,
                                               method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                              rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False):
+                                              rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
     """particle_ranking_PLS_targets_path with the summaries of particle_ranking_PLS_targets_summary at every tolerance
     (abc_particle_ranking_pls_targets_path_summary; the definition is in the header): the ranking, the fit and, under "rejection",
     the sort of every (target, parameter) are made once for all of Ks.  Tolerance t's quantiles and CDF are those of the summary
     call with K = Ks[t] (bit for bit under "rejection").  Returns the path's dict plus quant (B, T, nq, P): [b, t, q, j], cdf
     (B, T, P) or None, and probs.  transf / bounds as particle_ranking_PLS_targets_path; under "loclinear" the quantiles and the
     CDF are those of the adjusted rows carried back.  hcorr=True: under "loclinear" the quantiles and the CDF are those of the
-    variance-corrected rows, and the dict gains hcoef (B, T, A + 1, P); ignored under "rejection"."""
+    variance-corrected rows, and the dict gains hcoef (B, T, A + 1, P); ignored under "rejection".  ridge: under "loclinear" the
+    path's coef is the ridge fit and the dict gains ridge_lambda, ridge_pick (B, T, P) and ridge_press (B, T, L, P); ignored under
+    "rejection"."""
     ctx = _ctx(ctx)
     method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))
@@ -317,27 +350,31 @@ def particle_ranking_PLS_targets_path_summary(X_orig, Y_orig, targets, training_
         o["cdf"] = np.empty((B, nt, P))
         sm.truth, sm.cdf = tr.ctypes.data, o["cdf"].ctypes.data
     ncomp = C.c_int32(0)
-    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path_summary(
+    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path_summary(
         ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), method, kernel,
         _p(idx), _p(dist), C.byref(path), C.byref(sm), C.addressof(ncomp))))
     if transf is not None:
         o["alpha_back"] = untransform_params(coef[:, :, 0], transf, bounds)
     if hcorr and method == _lib.POSTERIOR_LOCLINEAR:
         o["hcoef"] = ctx.last_hcorr().reshape(B, nt, A + 1, P)
+    if ridge is not None and method == _lib.POSTERIOR_LOCLINEAR:
+        _ridge_out(ctx, o, ridge, (B, nt))
     o.update(post_mean=pm, coef=coef, alpha=coef[:, :, 0], rank=rank, status=status, h=h, Ks=ks.astype(np.int64), idx=idx, dist=dist,
              ncomp=ncomp.value, probs=keep[0])
     return o
 
 
 def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx,
-                     transf=None, bounds=None, hcorr=False):
+                     transf=None, bounds=None, hcorr=False, ridge=None):
     """The call of particle_ranking_PLS_targets_{summary,density,joint,draws}.  make(lead, P) -> (the product's struct, its outputs as a
     dict, what must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and ncomp added.  transf /
     bounds: the parameter transforms of particle_ranking_PLS_targets_adjust around the call ("loclinear" only; "rejection" does
     not regress and ignores them).  The product itself works on the parameter's own scale, after the back-transform: a density
     grid or a smoothed draw may still pass a bound, as in R.  hcorr=True: the heteroscedastic variance correction of
     particle_ranking_PLS_targets_adjust around the call: under "loclinear" the product is of the corrected rows; "rejection"
-    ignores it."""
+    ignores it.  ridge: the ridge adjustment of particle_ranking_PLS_targets_adjust around the call: under "loclinear" the product
+    is of the rows adjusted with the ridge fit and the outputs gain ridge_lambda, ridge_pick (B, P) and ridge_press (B, L, P);
+    "rejection" ignores it."""
     ctx = _ctx(ctx)
     method, kernel = _choice("method", method, _METHODS), _choice("kernel", kernel, _KERNELS)
     X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
@@ -346,10 +383,12 @@ def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, 
     dist = np.empty((B, K))
     ncomp = C.c_int32(0)
     entry = getattr(lib(), "abc_particle_ranking_pls_targets_" + product)
-    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, call=lambda: ctx.check(entry(
+    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, call=lambda: ctx.check(entry(
         ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K, method, kernel,
         _p(idx), _p(dist), None, C.byref(d), C.addressof(ncomp))))
     o.update(idx=idx, dist=dist, ncomp=ncomp.value)
+    if ridge is not None and method == _lib.POSTERIOR_LOCLINEAR:
+        _ridge_out(ctx, o, ridge, (B,))
     return o
 
 
@@ -379,7 +418,7 @@ def _summary_arg(probs, truth, lead, P):
 
 def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fraction, K, probs=(0.025, 0.5, 0.975), truth=None,
                                          method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                         rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False):
+                                         rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
     """particle_ranking_PLS_targets followed by weighted posterior quantiles of every target's K retained rows and, with truth
     (B, P), the posterior CDF at the truth (abc_particle_ranking_pls_targets_summary; the definition is in the header).
     method "rejection": the rows' parameters, equal weights; "loclinear": the local-linear adjusted rows with the kernel's weights
@@ -393,7 +432,7 @@ def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fract
         o["probs"] = keep[0]
         return s, o, keep
     return _targets_product("summary", make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule,
-                            ctx, transf, bounds, hcorr)
+                            ctx, transf, bounds, hcorr, ridge)
 
 
 def weighted_summary(values, weights=None, probs=(0.025, 0.5, 0.975), truth=None, ctx=None):
@@ -425,7 +464,7 @@ def _grid_points(grid, G):
 
 def particle_ranking_PLS_targets_density(X_orig, Y_orig, targets, training_fraction, K, G=512, cut=3.0, bw=None, bw_scale=1.0,
                                          method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                         rule=_lib.RULE_DEFAULT, dens=True, ctx=None, transf=None, bounds=None, hcorr=False):
+                                         rule=_lib.RULE_DEFAULT, dens=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
     """particle_ranking_PLS_targets followed by the weighted Gaussian kernel density of every (target, parameter) on a grid of G
     points and the mode taken from it (abc_particle_ranking_pls_targets_density; the definition is in the header: R's density()
     with bw.nrd0, cut and adjust = bw_scale).  method and kernel as particle_ranking_PLS_targets_summary; bw: given bandwidths
@@ -433,7 +472,7 @@ def particle_ranking_PLS_targets_density(X_orig, Y_orig, targets, training_fract
     grid (B, P, 2): lo_x and step, bw (B, P): the bandwidths used, mode (B, P), mode_dens (B, P), idx (B, K), dist (B, K),
     ncomp)."""
     o = _targets_product("density", lambda lead, P: _density_arg(G, cut, bw_scale, bw, lead, P, dens), X_orig, Y_orig, targets,
-                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr)
+                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
 
@@ -465,7 +504,7 @@ def _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens):
 
 def particle_ranking_PLS_targets_joint(X_orig, Y_orig, targets, training_fraction, K, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None,
                                        method="rejection", kernel="epanechnikov", exclude=None, max_comp=0, rule=_lib.RULE_DEFAULT,
-                                       dens=True, ctx=None, transf=None, bounds=None, hcorr=False):
+                                       dens=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
     """particle_ranking_PLS_targets followed by the joint posterior of every target, what a pairs plot draws
     (abc_particle_ranking_pls_targets_joint; the definition is in the header): the weighted means, the covariance matrix
     (numpy.cov with aweights) and the Pearson correlations of the P parameters, and for every pair of parameters in pairs (rows
@@ -476,7 +515,7 @@ def particle_ranking_PLS_targets_joint(X_orig, Y_orig, targets, training_fractio
     x (B, P, G): every parameter's grid points, grid (B, P, 2), bw (B, P), mode (B, npairs, 2), mode_dens (B, npairs), pairs
     (npairs, 2), idx (B, K), dist (B, K), ncomp)."""
     o = _targets_product("joint", lambda lead, P: _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens), X_orig, Y_orig, targets,
-                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr)
+                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
 
@@ -505,7 +544,7 @@ def _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P):
 
 def particle_ranking_PLS_targets_draws(X_orig, Y_orig, targets, training_fraction, K, S, smooth=False, seed=0, method="rejection",
                                        kernel="epanechnikov", bw=None, bw_scale=1.0, stream=None, exclude=None, max_comp=0,
-                                       rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False):
+                                       rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
     """particle_ranking_PLS_targets followed by S posterior draws of every target, made on the device
     (abc_particle_ranking_pls_targets_draws; the definition is in the header): rows of the target's K retained rows resampled with
     their weights (method and kernel as particle_ranking_PLS_targets_summary), as they are (smooth=False, the weighted bootstrap)
@@ -516,7 +555,7 @@ def particle_ranking_PLS_targets_draws(X_orig, Y_orig, targets, training_fractio
     each draw came from (idx[b, src[b, s]] is its row of the set), ess (B,): the effective sample size W^2 / sum w^2, bw (B, P):
     the bandwidths used (NaN with smooth=False), idx (B, K), dist (B, K), ncomp)."""
     return _targets_product("draws", lambda lead, P: _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P), X_orig, Y_orig,
-                            targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr)
+                            targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge)
 
 
 def weighted_draws(values, weights=None, S=1000, smooth=False, seed=0, bw=None, bw_scale=1.0, stream=None, ctx=None):
@@ -545,7 +584,7 @@ def hpd_levels(dens, step_x, step_y, probs=(0.5, 0.9, 0.95)):
 
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
                        ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False, transf=None,
-                       bounds=None, hcorr=False):
+                       bounds=None, hcorr=False, ridge=None):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
     without replacement (numpy Generator seeded with `seed`) serve as pseudo-observed data, each ranked against the set with
     itself excluded (the fit is shared: the row stays in it), and the posterior mean of its K nearest rows estimates its
@@ -561,7 +600,8 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
     "loclinear" calls (and only when given); the estimate under statistic="mean" is then its post_mean, the fitted value at the
     observation carried back.  hcorr=True: the heteroscedastic variance correction, handed on likewise and ignored under
     "rejection".  It rescales the adjusted rows about alpha and leaves alpha itself alone, so statistic="mean" under "loclinear"
-    is unaffected; the median, the mode, truth_cdf and ci95 do change."""
+    is unaffected; the median, the mode, truth_cdf and ci95 do change.  ridge: the penalties of the ridge adjustment, handed on
+    likewise and ignored under "rejection"; alpha is then the ridge fit's, so every statistic under "loclinear" changes."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -573,7 +613,7 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
         raise ValueError("statistic must be 'mean', 'median' or 'mode'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
     theta = np.ascontiguousarray(Y[rows])
-    tkw = _tf_kw(transf, bounds, hcorr)
+    tkw = _tf_kw(transf, bounds, hcorr, ridge)
     sm = None
     if statistic == "median" or coverage:
         sm = particle_ranking_PLS_targets_summary(X, Y, X[rows], training_fraction, K, probs=(0.5, 0.025, 0.975),
@@ -605,7 +645,7 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
 
 def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
                             ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False, transf=None,
-                            bounds=None, hcorr=False):
+                            bounds=None, hcorr=False, ridge=None):
     """cross_validate_pls at every tolerance of the strictly ascending list Ks from ONE call of
     particle_ranking_PLS_targets_path: cv4abc with tols = c(...).  The left-out rows are drawn from `seed` exactly as
     cross_validate_pls draws them.  method: "rejection" (the mean of the Ks[t] nearest rows) or "loclinear" (alpha of the fit at
@@ -617,7 +657,8 @@ def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fracti
     coverage_ks (T, P): the Kolmogorov distance of the finite truth_cdf values from the uniform (coverage_ks below), and
     best_calibrated (P,): the index of the tolerance with the smallest coverage_ks (0 where all are NaN).  transf / bounds as
     cross_validate_pls (handed on only when given); the "loclinear" mean estimate is then alpha_back of the path.  hcorr=True as
-    cross_validate_pls: alpha and so statistic="mean" are unaffected; the median, truth_cdf, ci95 and coverage_ks do change."""
+    cross_validate_pls: alpha and so statistic="mean" are unaffected; the median, truth_cdf, ci95 and coverage_ks do change.  ridge as
+    cross_validate_pls."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -629,7 +670,7 @@ def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fracti
         raise ValueError("statistic must be 'mean' or 'median'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
     theta = np.ascontiguousarray(Y[rows])
-    tkw = _tf_kw(transf, bounds, hcorr)
+    tkw = _tf_kw(transf, bounds, hcorr, ridge)
     if statistic == "median" or coverage:
         r = particle_ranking_PLS_targets_path_summary(X, Y, X[rows], training_fraction, Ks, probs=(0.5, 0.025, 0.975),
                                                       truth=theta if coverage else None, method=method, kernel=kernel, exclude=rows,

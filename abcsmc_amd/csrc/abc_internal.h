@@ -123,6 +123,15 @@ struct abc_ctx {
     double* hc_buf;
     size_t hc_cap, hc_slots, hc_a1, hc_P;
     unsigned long long* hc_skipped_dev;
+    // ridge adjustment (abc_ctx_set_adjust_ridge): the penalties (rg_L == 0: off), the record of the last regressing call made
+    // under it (device; rg_pick rg_slots x rg_P, rg_press rg_slots x rg_Lrec x rg_P; allocated and grown only while the setting is on,
+    // the counts 0 while there is none) and the counter of unscored pairs (device, abc_adjust_ridge_unscored)
+    double rg_lambda[ABC_RIDGE_MAXL];
+    size_t rg_L;
+    int32_t* rg_pick;
+    double* rg_press;
+    size_t rg_cap_pick, rg_cap_press, rg_slots, rg_Lrec, rg_P;
+    unsigned long long* rg_unscored_dev;
     unsigned long long wx_moved_counts, generation_repeats;      // abc_generation_repeats
     bool wx_gather_rows;     // diagnostic (ABC_DIAG=1 ABC_WX_GATHER=1, set at context creation): the sharded generation's Wilcoxon rule by
                              // gathering the validation rows on every rank (rounds 1-4) instead of the sharded cascade
@@ -295,24 +304,26 @@ int launch_rank_targets(abc_ctx*, const double* X, size_t ldx, const double* Y, 
                         bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean, abc_tg_scores* keep = nullptr);
 // local-linear adjustment of the batched ranking (adjust.hip): the ranking of launch_rank_targets, then the regression of every
 // target's K retained rows on their scores; out: device pointers (abc_adjust_out), dist may be NULL
-size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K, bool hcorr = false);
+size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K, bool hcorr = false, size_t ridge = 0);
 int launch_rank_targets_adjust(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
                                struct abc_adj_keep* keep = nullptr, const struct AbcTf* tf = nullptr,
-                               const struct AbcHc* hc = nullptr);
+                               const struct AbcHc* hc = nullptr, const struct AbcRg* rg = nullptr);
 // tf (optional, transf_dev.h): Y is already forward(Y) (launch_param_transf); theta and keep's readers carry the adjusted rows back
 // hc (optional, adjust_dev.h): the heteroscedastic variance correction, its second fit written to hc->hcoef (B, or B x T on a path,
 // slots laid out as coef); the *_need functions count its moment blocks with hcorr = true
+// rg (optional, adjust_dev.h): the ridge adjustment, coef replaced by the fit of the penalty with the smallest leave-one-out PRESS,
+// pick and press written to rg's buffers (slots as hc's); the *_need functions count its arena pieces with ridge = L
 // tolerance path (adjust.hip): the ranking at K = path->Ks[T - 1], then the rejection mean and the regression at every tolerance;
 // path: Ks in host memory, the outputs device pointers; dist may be NULL.  keep (optional): the fit is made whatever outputs path
 // names, and keep receives what a reader of the adjusted rows needs, with coef B x T x (A + 1) x P and dist B x K_max
-size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T, bool hcorr = false);
+size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T, bool hcorr = false, size_t ridge = 0);
 int launch_rank_targets_path(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                              bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path,
                              struct abc_adj_keep* keep = nullptr, const double* Yt = nullptr, const struct AbcTf* tf = nullptr,
-                             const struct AbcHc* hc = nullptr);
+                             const struct AbcHc* hc = nullptr, const struct AbcRg* rg = nullptr);
 // Yt / tf (optional, both or neither): forward(Y) as N x P with ld = N, which the fit reads; post_mean stays the mean of the raw Y.
 // launch_param_transf: the context's parameter transforms over a column-major n x P matrix (adjust.hip: k_tf_apply); tf NULL: a copy; in place is
 // allowed; outside (optional, device): a forward pass adds the entries of transformed columns it found outside their domain

@@ -28,6 +28,13 @@
 //                   hcoef, the skip rule and its counter
 // and k_adj_apply<true> rescales the residual of every made value (aj_hcorr, as sm_value<.., true> of segment_dev.h).  All three are
 // instances of their own: calls without the setting launch the code they launched before it existed.
+// Under the ridge adjustment (abc_ctx_set_adjust_ridge) three kernels follow every k_adj_solve<false>, which still gives rank and
+// status, and replace its coef:
+//   k_adj_rsolve    grid (targets, penalties): the same sums and sweep with the diagonal of C penalised; alpha_l, beta_l and the
+//                   swept left block M_l to the arena
+//   k_adj_press     grid (row tiles, targets, penalties): the rows' leverages from M_l, the leave-one-out terms, one partial per
+//                   (tile, penalty, parameter)
+//   k_adj_pick      one work-group per target: PRESS per penalty, the pick, coef and the context's record
 // Chunk sizes depend on K only, tile sizes on (nc, P) only, and the gather paths copy the same bits: a target's outputs are the
 // same alone and in any batch.
 #include <math.h>
@@ -572,6 +579,285 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
     }
 }
 
+// ---- ridge adjustment with the penalty chosen by leave-one-out PRESS (abc_ctx_set_adjust_ridge; the definition is in the header) ----
+// the penalties of the setting, ascending (kernel argument)
+struct AjLam {
+    double v[ABC_RIDGE_MAXL];
+};
+
+// doubles of one (slot, penalty) fit in the arena: [0] W, [1 + k] xm_k (the weighted mean of the shifted scores), then the
+// (1 + nc) x P coefficients laid out as coef (row 0 alpha_l, row 1 + k beta_l[k]), then M_l (nc x nc)
+__host__ __device__ __forceinline__ size_t aj_rfit_dbl(int nc, int P) { return (size_t)1 + nc + (size_t)(1 + nc) * P + (size_t)nc * nc; }
+
+// the penalised sweep: one work-group per (target b0 + blockIdx.x, penalty blockIdx.y).  k_adj_solve<false> with T = 1 over
+// again (the same sums in the same order, so W, the means, C and c have its bits) except that the diagonal of C becomes
+// fma(lambda, C_kk, C_kk) before the sweep, the skip rule reading that diagonal; lambda == 0 leaves every bit.  The swept left
+// block is kept: M_l = the inverse over the kept pivots, rows and columns of skipped pivots 0.  rfit[(bl L + l) aj_rfit_dbl ..].
+__global__ __launch_bounds__(256) void k_adj_rsolve(AjSrc src, const uint64_t* __restrict__ idx, size_t ld, size_t K, size_t CH, int nc, int P,
+                                                    const double* __restrict__ O, int KCO, const double* __restrict__ part, int nchs,
+                                                    size_t b0, AjLam lam, double* __restrict__ rfit) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int t = threadIdx.x;
+    const int U = 1 + nc, D = 1 + nc + P, NB = nc + AJ_RHS, ncp = (nc + 1) & ~1;
+    double* C0 = sm;                        // nc x nc: the centred moments, the diagonal penalised
+    double* Wk = C0 + ((nc * nc + 1) & ~1); // nc x NB: [C | c] being swept
+    double* xs = Wk + nc * NB;
+    double* xm = xs + ncp;
+    double* xb = xm + ncp;
+    double* colk = xb + ncp;
+    double* kept = colk + ncp;
+    double* rowk = kept + ncp;              // NB
+    double* ts = rowk + NB;                 // AJ_RHS
+    double* tm = ts + AJ_RHS;
+    double* sW = tm + AJ_RHS;
+    const size_t bl = blockIdx.x, b = b0 + bl;
+    const int l = blockIdx.y, L = gridDim.y;
+    const double la = lam.v[l];
+    const int nch = (int)((K + CH - 1) / CH);
+    const size_t blk = (size_t)U * D;
+    const double* pb = part + bl * (size_t)nchs * blk;
+    const size_t i0 = (size_t)idx[b * ld];
+    double* rf = rfit + (bl * L + l) * aj_rfit_dbl(nc, P);
+    double* cb = rf + 1 + nc;               // (1 + nc) x P
+    double* Mo = cb + (size_t)U * P;        // nc x nc
+    for (int q = t; q < U; q += 256) {
+        double s = 0.0;
+        for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + q];
+        if (q == 0) sW[0] = s; else xs[q - 1] = s;
+    }
+    __syncthreads();
+    const double W = sW[0];
+    if (t == 0) rf[0] = W;
+    for (int k = t; k < nc; k += 256) {
+        xm[k] = xs[k] / W;
+        xb[k] = xm[k] + (aj_val(src, i0, k, nc) - O[b * KCO + k]);
+        rf[1 + k] = xm[k];
+    }
+    __syncthreads();
+    for (int q = t; q < nc * nc; q += 256) {
+        const int k = q / nc, m = q % nc, lo = k < m ? k : m, hi = k < m ? m : k;
+        double s = 0.0;
+        for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + (size_t)(1 + lo) * D + 1 + hi];
+        const double c = fma(-xm[lo], xs[hi], s);
+        C0[q] = (k == m) ? fma(la, c, c) : c;
+    }
+    for (int j0 = 0; j0 == 0 || j0 < P; j0 += AJ_RHS) {
+        const int nb = (P - j0 < AJ_RHS) ? P - j0 : AJ_RHS, NW = nc + nb;
+        __syncthreads();
+        for (int jj = t; jj < nb; jj += 256) {
+            double s = 0.0;
+            for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + 1 + nc + j0 + jj];
+            ts[jj] = s;
+            tm[jj] = aj_val(src, i0, nc + j0 + jj, nc) + s / W;
+        }
+        for (int q = t; q < nc * nc; q += 256) Wk[(q / nc) * NB + q % nc] = C0[q];
+        __syncthreads();
+        for (int q = t; q < nc * nb; q += 256) {
+            const int k = q / nb, jj = q % nb;
+            double s = 0.0;
+            for (int ch = 0; ch < nch; ch++) s += pb[ch * blk + (size_t)(1 + k) * D + 1 + nc + j0 + jj];
+            Wk[k * NB + nc + jj] = fma(-xm[k], ts[jj], s);
+        }
+        __syncthreads();
+        for (int k = 0; k < nc; k++) {
+            const double d = Wk[k * NB + k], c0 = C0[k * nc + k];
+            const bool keep = (c0 > 0.0) && (d > 1e-10 * c0);
+            if (t == 0) kept[k] = keep ? 1.0 : 0.0;
+            if (!keep) continue;                                // (uniform)
+            for (int q = t; q < NW; q += 256) rowk[q] = (q == k) ? 1.0 / d : Wk[k * NB + q] / d;
+            for (int i = t; i < nc; i += 256) colk[i] = Wk[i * NB + k];
+            __syncthreads();
+            for (int q = t; q < nc * NW; q += 256) {
+                const int i = q / NW, j = q % NW;
+                double v;
+                if (i == k) v = rowk[j];
+                else if (j == k) v = -colk[i] / d;
+                else v = fma(-colk[i], rowk[j], Wk[i * NB + j]);
+                Wk[i * NB + j] = v;
+            }
+            __syncthreads();
+        }
+        __syncthreads();
+        if (j0 == 0)                                            // the left block is the same in every batch of right-hand sides
+            for (int q = t; q < nc * nc; q += 256) {
+                const int i = q / nc, j = q % nc;
+                Mo[q] = (kept[i] != 0.0 && kept[j] != 0.0) ? Wk[i * NB + j] : 0.0;
+            }
+        for (int jj = t; jj < nb; jj += 256) {
+            const int j = j0 + jj;
+            double a = tm[jj];
+            for (int k = 0; k < nc; k++) {
+                const double be = (kept[k] != 0.0) ? Wk[k * NB + nc + jj] : 0.0;
+                a = fma(-be, xb[k], a);
+                cb[(size_t)(1 + k) * P + j] = be;
+            }
+            cb[j] = a;
+        }
+    }
+}
+
+// k_adj_press's tile: TR rows of [x (observation-centred) | theta] and, in one region used twice, M_l and then beta_l (when it
+// fits AJ_APPLY_DBL: k_adj_apply's beta_lds rule); (nc, P) only
+struct AjPlanR {
+    int TR, beta_lds, reg;      // rows of a tile; beta_l in LDS; doubles of the shared region
+    size_t lds;
+};
+constexpr int AJ_PRESS_DBL = 8192;                          // doubles of k_adj_press's LDS (64 KiB)
+
+__host__ __device__ __forceinline__ AjPlanR aj_plan_r(int nc, int P) {
+    AjPlanR r;
+    const int Wv = nc + P, ncp = (nc + 1) & ~1;
+    r.beta_lds = (nc * P <= AJ_APPLY_DBL) ? 1 : 0;
+    int reg = nc * nc;
+    if (r.beta_lds && nc * P > reg) reg = nc * P;
+    r.reg = (reg + 1) & ~1;
+    int tr = (AJ_PRESS_DBL - r.reg - 2 * ncp - 256 - 2) / (Wv + 2);
+    if (tr > 256) tr = 256;
+    r.TR = tr < 1 ? 1 : tr;
+    r.lds = (size_t)(r.reg + 2 * ncp + 256 + 2 + r.TR * (Wv + 2)) * 8;
+    return r;
+}
+
+// grid (tiles of TR rows, targets b0 + blockIdx.y, penalties): the leave-one-out terms of the tile's rows under penalty l.
+// A lane owns rows for the leverage: xt = (x_e - x_0) - xm, s_k = sum_m M[k][m] xt[m] (an fma chain from 0.0, m ascending),
+// q = sum_k xt[k] s_k (an fma chain from 0.0, k ascending), h_e = w_e (1 / W + q), den_e = 1 - h_e.  Then a thread owns (row,
+// parameter) pairs: v = aj_adjusted with beta_l, r = v - alpha_l, u = r / den_e, the term w_e (u u), 0 for a row of weight 0.
+// Then per parameter: NS = 256 / min(P, 256) threads, each the sum of every NS-th row's term ascending, those sums in thread
+// order.  pp[((bl L + l) tiles + tile) P + j]; +inf in every j when a row of positive weight has den_e <= 1e-10 or NaN.
+__global__ __launch_bounds__(256) void k_adj_press(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist, size_t ld,
+                                                   size_t K, int nc, int P, int kernel, const double* __restrict__ O, int KCO,
+                                                   const double* __restrict__ rfit, size_t b0, double* __restrict__ pp) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ int s_inf;
+    const AjPlanR pr = aj_plan_r(nc, P);
+    const int t = threadIdx.x, Wv = nc + P, ncp = (nc + 1) & ~1, TR = pr.TR;
+    double* reg = sm;                        // M_l, then beta_l
+    double* xm = reg + pr.reg;               // nc
+    double* x0 = xm + ncp;                   // nc: the first row's scores
+    double* red = x0 + ncp;                  // 256
+    double* wd = red + 256;                  // TR x 2: w_e, den_e
+    double* tv = wd + 2 * (size_t)TR + 2;    // TR x Wv
+    const size_t bl = blockIdx.y, b = b0 + bl, e0 = (size_t)blockIdx.x * TR;
+    const int l = blockIdx.z, L = gridDim.z;
+    const int nr = (K - e0 < (size_t)TR) ? (int)(K - e0) : TR;
+    const uint64_t* ix = idx + b * ld;
+    const double* dd = dist + b * ld;
+    const double* rf = rfit + (bl * L + l) * aj_rfit_dbl(nc, P);
+    const double* cf = rf + 1 + nc;          // alpha_l at [j], beta_l at [(1 + k) P + j]
+    const double* Mg = cf + (size_t)(1 + nc) * P;
+    const double W = rf[0];
+    const double h = dd[K - 1];
+    const bool rect = kernel == 1 || aj_fallback(dd, K);
+    const size_t i0 = (size_t)ix[0];
+    if (t == 0) s_inf = 0;
+    for (int q = t; q < nc * nc; q += 256) reg[q] = Mg[q];
+    for (int k = t; k < nc; k += 256) {
+        xm[k] = rf[1 + k];
+        x0[k] = aj_val(src, i0, k, nc);
+    }
+    for (int q = t; q < nr * Wv; q += 256) {
+        const int r = q / Wv, c = q % Wv;
+        tv[q] = aj_val(src, (size_t)ix[e0 + r], c, nc);     // raw: the scores are centred below
+    }
+    for (int r = t; r < nr; r += 256) wd[2 * r] = aj_weight(dd[e0 + r], h, rect);
+    __syncthreads();
+    for (int r = t; r < nr; r += 256) {
+        const double* x = tv + r * Wv;
+        double q = 0.0;
+        for (int k = 0; k < nc; k++) {
+            double s = 0.0;
+            for (int m = 0; m < nc; m++) s = fma(reg[k * nc + m], (x[m] - x0[m]) - xm[m], s);
+            q = fma((x[k] - x0[k]) - xm[k], s, q);
+        }
+        const double w = wd[2 * r], den = 1.0 - w * (1.0 / W + q);
+        wd[2 * r + 1] = den;
+        if (w > 0.0 && !(den > 1e-10)) s_inf = 1;
+    }
+    __syncthreads();
+    if (pr.beta_lds)
+        for (int q = t; q < nc * P; q += 256) reg[q] = cf[P + q];
+    for (int q = t; q < nr * nc; q += 256) {                    // x_e as k_adj_apply stages it
+        const int r = q / nc, k = q % nc;
+        tv[r * Wv + k] = tv[r * Wv + k] - O[b * KCO + k];
+    }
+    __syncthreads();
+    const double* bt = pr.beta_lds ? reg : cf + P;
+    for (int q = t; q < nr * P; q += 256) {                     // theta_e[j] -> its term (its own slot; the scores are only read)
+        const int r = q / P, j = q % P;
+        double* x = tv + r * Wv;
+        const double w = wd[2 * r];
+        double term = 0.0;
+        if (w > 0.0) {
+            const double v = aj_adjusted(x[nc + j], [&](int k) { return x[k]; }, bt + j, (size_t)P, nc);
+            const double u = (v - cf[j]) / wd[2 * r + 1];
+            term = w * (u * u);
+        }
+        x[nc + j] = term;
+    }
+    __syncthreads();
+    const bool inf = s_inf != 0;
+    double* po = pp + ((bl * L + l) * (size_t)gridDim.x + blockIdx.x) * (size_t)P;
+    const int PW = P < 256 ? P : 256, NS = 256 / PW;
+    const int j = t % PW, s = t / PW;
+    for (int j0 = 0; j0 < P; j0 += PW) {
+        const bool mine = s < NS && j0 + j < P;
+        double a = 0.0;
+        if (mine)
+            for (int r = s; r < nr; r += NS) a += tv[r * Wv + nc + j0 + j];
+        red[t] = a;
+        __syncthreads();
+        if (mine && s == 0) {
+            for (int q = 1; q < NS; q++) a += red[q * PW + j];
+            po[j0 + j] = inf ? __longlong_as_double(0x7ff0000000000000ll) : a;
+        }
+        __syncthreads();
+    }
+}
+
+// where a regressing call under the ridge setting writes its record (the context's buffers)
+struct AjRgOut {
+    int32_t* pick;                  // slots x P
+    double* press;                  // slots x L x P
+    unsigned long long* unscored;   // device counter
+    size_t rstride, roff;           // record slot = b rstride + roff (1, 0; a tolerance path, one tolerance per launch: T, t)
+};
+
+// one work-group per target b0 + blockIdx.x: PRESS_l[j] = the tiles' partials summed in tile order (NaN counts as +inf),
+// pick[j] = the smallest l with the smallest PRESS (L - 1 and counted when every l is +inf), coef[b][:, j] = (alpha, beta) of the
+// pick, rows above nc 0
+__global__ __launch_bounds__(256) void k_adj_pick(int nc, int P, int A, int L, int tiles, const double* __restrict__ rfit,
+                                                  const double* __restrict__ pp, size_t b0, double* __restrict__ coef, AjRgOut ro) {
+    __shared__ unsigned s_un;
+    const int t = threadIdx.x;
+    const size_t bl = blockIdx.x, b = b0 + bl, rs = b * ro.rstride + ro.roff;
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    if (t == 0) s_un = 0;
+    __syncthreads();
+    double* cb = coef + b * (size_t)(A + 1) * P;
+    for (int j = t; j < P; j += 256) {
+        int best = L - 1;
+        double pbest = inf;
+        for (int l = 0; l < L; l++) {
+            const double* q = pp + (bl * L + l) * (size_t)tiles * P + j;
+            double s = 0.0;
+            for (int tl = 0; tl < tiles; tl++) s += q[(size_t)tl * P];
+            if (!(s < inf)) s = inf;
+            ro.press[(rs * L + l) * (size_t)P + j] = s;
+            if (s < pbest) {
+                pbest = s;
+                best = l;
+            }
+        }
+        if (!(pbest < inf)) atomicAdd(&s_un, 1u);
+        ro.pick[rs * (size_t)P + j] = best;
+        const double* cf = rfit + (bl * L + best) * aj_rfit_dbl(nc, P) + 1 + nc;
+        for (int k = 0; k <= nc; k++) cb[(size_t)k * P + j] = cf[(size_t)k * P + j];
+        for (int k = nc; k < A; k++) cb[(size_t)(1 + k) * P + j] = 0.0;
+    }
+    __syncthreads();
+    if (t == 0 && s_un && ro.unscored) atomicAdd(ro.unscored, (unsigned long long)s_un);
+}
+
 // grid (tiles of TR rows, targets b0 + blockIdx.y): theta[(b K + e) P + j] = theta_e[j] - sum_k beta_kj x_e[k] (one fma chain in k
 // order), weight[b K + e] = w_e.  HC: the variance correction on top (aj_hcorr with the second fit hcoef, unless row 0 of the
 // parameter holds the skip flag), before the back-transform
@@ -717,22 +1003,55 @@ size_t aj_solve_lds(int nc) {
     return (size_t)(((nc * nc + 1) & ~1) + nc * NB + 5 * ncp + NB + 2 * AJ_RHS + 2) * 8;
 }
 
+// the ridge setting for a launch: the penalties and where the record goes (NULL pick: off)
+size_t aj_ridge_tiles(size_t K, int nc, int P) {
+    const AjPlanR pr = aj_plan_r(nc, P);
+    return (K + pr.TR - 1) / pr.TR;
+}
+
+size_t aj_ridge_bytes(size_t K, size_t A, size_t P, size_t L) {      // one target's fits and PRESS partials (bound over nc <= A)
+    return L * (aj_rfit_dbl((int)A, (int)P) + aj_ridge_tiles(K, (int)A, (int)P) * P) * 8;
+}
+
+// the penalised fits, their PRESS and the pick for the targets b0 .. b0 + nb - 1 from the moment blocks k_adj_moments left in
+// `part` (pl: that launch's plan); coef receives the picked fit at slot b (stride 1)
+int aj_ridge(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, const double* d, size_t ld, size_t K, int nc, int P, int A,
+             int kernel, const abc_tg_scores& sc, const double* part, const AjPlan& pl, size_t b0, size_t nb, const AbcRg& rg,
+             double* rfit, double* pp, double* coef, size_t rstride, size_t roff) {
+    AjLam lam = {};
+    for (int l = 0; l < rg.L; l++) lam.v[l] = rg.lambda[l];
+    const AjPlanR pr = aj_plan_r(nc, P);
+    const size_t tiles = (K + pr.TR - 1) / pr.TR, lds_s = aj_solve_lds(nc);
+    const AjRgOut ro = {rg.pick, rg.press, rg.unscored, rstride, roff};
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_rsolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_press, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pr.lds));
+    hipLaunchKernelGGL(k_adj_rsolve, dim3((unsigned)nb, (unsigned)rg.L), dim3(256), lds_s, ctx->stream, src, idx, ld, K, pl.CH, nc, P,
+                       sc.O, sc.KCO, part, (int)pl.nch, b0, lam, rfit);
+    hipLaunchKernelGGL(k_adj_press, dim3((unsigned)tiles, (unsigned)nb, (unsigned)rg.L), dim3(256), pr.lds, ctx->stream, src, idx, d, ld,
+                       K, nc, P, kernel, sc.O, sc.KCO, (const double*)rfit, b0, pp);
+    hipLaunchKernelGGL(k_adj_pick, dim3((unsigned)nb), dim3(256), 0, ctx->stream, nc, P, A, rg.L, (int)tiles, (const double*)rfit,
+                       (const double*)pp, b0, coef, ro);
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
 }  // namespace
 
-size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K, bool hcorr) {
+size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K, bool hcorr, size_t ridge) {
     size_t b = 0;
     b += B * K * 8;                                          // distances (the caller's may be NULL)
     b += B * (A + 1) * P * 8 + 2 * B * 4;                    // coefficients, rank, status
     if (aj_use_table(N, A, P, B, K)) b += N * (A + P) * 8;   // the row-major table
     b += aj_batch(K, A, P, B) * aj_part_bytes(K, A, P);      // moment blocks of one batch
     if (hcorr) b += aj_batch(K, A, P, B) * aj_part2_bytes(K, A, P) + 256;
+    if (ridge) b += aj_batch(K, A, P, B) * aj_ridge_bytes(K, A, P, ridge) + 2 * 256;
     return b + 16 * 256;
 }
 
 int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
-                               abc_adj_keep* keep, const AbcTf* tf, const AbcHc* hc) {
+                               abc_adj_keep* keep, const AbcTf* tf, const AbcHc* hc, const AbcRg* rg) {
     const AbcTf tfd = tf ? *tf : AbcTf{nullptr, nullptr, nullptr};
     double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
     if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
@@ -782,6 +1101,13 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
         if (!part2) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
         ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
     }
+    const bool ridge = rg && rg->L > 0 && Pi > 0;                      // the penalised fits replace coef before anything reads it
+    double *rfit = nullptr, *rpp = nullptr;
+    if (ridge) {
+        rfit = (double*)abc_ws_alloc(ctx, bb * rg->L * aj_rfit_dbl(nc, Pi) * 8);
+        rpp = (double*)abc_ws_alloc(ctx, bb * rg->L * aj_ridge_tiles(K, nc, Pi) * P * 8);
+        if (!rfit || !rpp) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
+    }
     const AjHcSolve hs0 = {nullptr, nullptr, nullptr, nullptr, 1, 0};
     const AjHcSolve hs1 = {part2, coef, hcoef, hcoef ? hc->skipped : nullptr, 1, 0};
     AjKs ks = {};
@@ -794,6 +1120,8 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
                            (const double*)d, K, ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0,
                            coef, out->rank, out->status, hs0);
         ABC_HIP(ctx, hipGetLastError());
+        if (ridge)
+            ABC_TRY(aj_ridge(ctx, src, idx, d, K, K, nc, Pi, (int)A, kernel, sc, part, pl, b0, nb, *rg, rfit, rpp, coef, 1, 0));
         if (!hcoef) continue;
         hipLaunchKernelGGL(k_adj_moments2, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src, (const uint64_t*)idx,
                            (const double*)d, K, K, nc, Pi, (int)A, kernel, pl.CH, p2.TR, b0, pl.nch, sc.O, sc.KCO, (const double*)coef, 1,
@@ -858,20 +1186,22 @@ int aj_launch_moments_path(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, 
 
 }  // namespace
 
-size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T, bool hcorr) {
+size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T, bool hcorr, size_t ridge) {
     size_t b = 0;
     b += B * K * 8;                                                  // distances (the caller's may be NULL)
     b += B * T * (A + 1) * P * 8 + 8;                                // coefficients (the caller's may be NULL)
     if (aj_use_table(N, A, P, B, K)) b += N * (A + P) * 8;           // the row-major table
     b += aj_path_batch(K, A, P, B, T) * T * aj_part_bytes(K, A, P);  // moment blocks of one batch, every tolerance
-    if (hcorr) b += aj_path_batch(K, A, P, B, T) * aj_part2_bytes(K, A, P) + B * (A + 1) * P * 8 + 3 * 256;   // + the refit's coef
+    if (hcorr) b += aj_path_batch(K, A, P, B, T) * aj_part2_bytes(K, A, P) + 256;
+    if (hcorr || ridge) b += B * (A + 1) * P * 8 + 2 * 256;          // the refit's coef
+    if (ridge) b += aj_path_batch(K, A, P, B, T) * aj_ridge_bytes(K, A, P, ridge) + 2 * 256;
     return b + 16 * 256;
 }
 
 int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                              bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path, abc_adj_keep* keep,
-                             const double* Yt, const AbcTf* tf, const AbcHc* hc) {
+                             const double* Yt, const AbcTf* tf, const AbcHc* hc, const AbcRg* rg) {
     const int T = (int)path->T, Pi = (int)P;
     AjKs ks = {};
     for (int t = 0; t < T; t++) ks.K[t] = path->Ks[t];
@@ -932,11 +1262,22 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
         // pass's blocks in `part` once the path's own solve has read it
         hcoef = (hc && Pi > 0) ? hc->hcoef : nullptr;
         const size_t blk2 = (size_t)(1 + nc) * P;
-        double *part2 = nullptr, *coef1 = nullptr;
+        // the ridge setting takes the same branch: the refit's coef1 is that call's picked fit, copied to slot (b, t) of the path's
+        // coef (rank and status stay the path's own), and the second fit under both settings models its residuals
+        const bool ridge = rg && rg->L > 0 && Pi > 0;
+        double *part2 = nullptr, *coef1 = nullptr, *rfit = nullptr, *rpp = nullptr;
+        if (hcoef || ridge) {
+            coef1 = (double*)abc_ws_alloc(ctx, B * (A + 1) * P * 8 + 8);
+            if (!coef1) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
+        }
+        if (ridge) {
+            rfit = (double*)abc_ws_alloc(ctx, bb * rg->L * aj_rfit_dbl(nc, Pi) * 8);
+            rpp = (double*)abc_ws_alloc(ctx, bb * rg->L * aj_ridge_tiles(K, nc, Pi) * P * 8);
+            if (!rfit || !rpp) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
+        }
         if (hcoef) {
             part2 = (double*)abc_ws_alloc(ctx, bb * pl.nch * blk2 * 8);
-            coef1 = (double*)abc_ws_alloc(ctx, B * (A + 1) * P * 8 + 8);
-            if (!part2 || !coef1) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
+            if (!part2) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
             ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
         }
         const AjHcSolve hs0 = {nullptr, nullptr, nullptr, nullptr, 1, 0};
@@ -966,7 +1307,7 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
                                (const uint64_t*)idx, (const double*)d, K, ks, T, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO,
                                (const double*)part, (int)pl.nch, b0, coef, path->rank, path->status, hs0);
             ABC_HIP(ctx, hipGetLastError());
-            if (!hcoef) continue;
+            if (!hcoef && !ridge) continue;
             for (int t = 0; t < T; t++) {
                 const size_t Kt = ks.K[t];
                 const AjPlan pt = aj_plan(Kt, nc, Pi);               // (pt.nch <= pl.nch: the chunk count does not fall with K)
@@ -974,12 +1315,20 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
                 const size_t lds_t = (size_t)(((D + 1) & ~1) + ((pt.TR + 1) & ~1) + pt.TR * aj_stride(nc, Pi)) * 8;
                 AjKs k1 = {};
                 k1.K[0] = Kt;
-                const AjHcSolve hs1 = {part2, coef1, hcoef, hc->skipped, (size_t)T, (size_t)t};
+                const AjHcSolve hs1 = {part2, coef1, hcoef, hcoef ? hc->skipped : nullptr, (size_t)T, (size_t)t};
                 hipLaunchKernelGGL(k_adj_moments, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), lds_t, ctx->stream, src,
                                    (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, kernel, pt.CH, pt.TR, b0, pt.nch, part);
                 hipLaunchKernelGGL(k_adj_solve<false>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
                                    (const double*)d, K, k1, 1, pt.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part,
                                    (int)pt.nch, b0, coef1, (int32_t*)nullptr, (int32_t*)nullptr, hs0);
+                if (ridge) {
+                    ABC_TRY(aj_ridge(ctx, src, idx, d, K, Kt, nc, Pi, (int)A, kernel, sc, part, pt, b0, nb, *rg, rfit, rpp, coef1,
+                                     (size_t)T, (size_t)t));
+                    const size_t cw = (A + 1) * P * 8;
+                    ABC_HIP(ctx, hipMemcpy2DAsync(coef + (b0 * T + t) * (A + 1) * P, (size_t)T * cw, coef1 + b0 * (A + 1) * P, cw, cw, nb,
+                                                  hipMemcpyDeviceToDevice, ctx->stream));
+                }
+                if (!hcoef) continue;
                 hipLaunchKernelGGL(k_adj_moments2, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src,
                                    (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, (int)A, kernel, pt.CH, p2.TR, b0, pt.nch,
                                    sc.O, sc.KCO, (const double*)coef1, 1, 0, p2.cf_lds, part2);
@@ -1031,3 +1380,4 @@ int launch_param_transf(abc_ctx* ctx, const AbcTf* tf, const double* V, size_t l
 }
 
 static_assert(AJ_MAXA == 64 && AJ_MAXP == 1024, "limits of abc_rank_targets_adjust_dev (api.hip checks them)");
+static_assert(sizeof(AbcRg::lambda) == ABC_RIDGE_MAXL * sizeof(double), "AbcRg holds ABC_RIDGE_MAXL penalties");

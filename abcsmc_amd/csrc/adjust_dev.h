@@ -65,6 +65,16 @@ struct AbcHc {
     unsigned long long* skipped;    // device counter
 };
 
+// ---- ridge adjustment (abc_ctx_set_adjust_ridge; the definition is in the header) ----
+// the penalties of a regressing call under the setting and where it writes its record (the context's buffers)
+struct AbcRg {
+    double lambda[8];               // ascending (ABC_RIDGE_MAXL entries at most)
+    int L;                          // 0: the setting is off
+    int32_t* pick;                  // slots x P: the chosen penalty's index
+    double* press;                  // slots x L x P: the leave-one-out PRESS of every penalty
+    unsigned long long* unscored;   // device counter: (slot, parameter) pairs with every penalty's PRESS +inf
+};
+
 // what launch_rank_targets_adjust leaves in the arena for a caller that reads the adjusted rows itself (summary.hip)
 struct abc_adj_keep {
     AjSrc src;

@@ -109,6 +109,9 @@ extern "C" void abc_ctx_destroy(abc_ctx* ctx) {
     if (ctx->tf_outside_dev) (void)hipFree(ctx->tf_outside_dev);
     if (ctx->hc_buf) (void)hipFree(ctx->hc_buf);
     if (ctx->hc_skipped_dev) (void)hipFree(ctx->hc_skipped_dev);
+    if (ctx->rg_pick) (void)hipFree(ctx->rg_pick);
+    if (ctx->rg_press) (void)hipFree(ctx->rg_press);
+    if (ctx->rg_unscored_dev) (void)hipFree(ctx->rg_unscored_dev);
     if (ctx->wx_rec_dev) (void)hipFree(ctx->wx_rec_dev);
     abc_comm_release(ctx);
     if (ctx->xbuf) (void)hipFree(ctx->xbuf);
@@ -454,6 +457,90 @@ extern "C" int abc_adjust_hcorr_skipped(abc_ctx* ctx, uint64_t* count, int reset
     if (ctx->hc_skipped_dev) {
         ABC_HIP(ctx, hipMemcpyAsync(&dev, ctx->hc_skipped_dev, sizeof(dev), hipMemcpyDeviceToHost, ctx->stream));
         if (reset) ABC_HIP(ctx, hipMemsetAsync(ctx->hc_skipped_dev, 0, sizeof(dev), ctx->stream));
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    *count = (uint64_t)dev;
+    return ABC_OK;
+}
+
+// ---- ridge adjustment with the penalty chosen by leave-one-out PRESS -------------------------------------------------------------
+
+extern "C" int abc_ctx_set_adjust_ridge(abc_ctx* ctx, const double* lambda, size_t L) {
+    CHECK_CTX(ctx);
+    if (!lambda || L == 0) {
+        ctx->rg_L = 0;
+        return ABC_OK;
+    }
+    if (L > ABC_RIDGE_MAXL) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_adjust_ridge: L = %zu (at most %d)", L, (int)ABC_RIDGE_MAXL);
+    for (size_t l = 0; l < L; l++) {
+        if (!isfinite(lambda[l]) || lambda[l] < 0.0)
+            ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_adjust_ridge: lambda[%zu] = %g (finite and >= 0)", l, lambda[l]);
+        if (l && !(lambda[l] > lambda[l - 1]))
+            ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_ctx_set_adjust_ridge: lambda[%zu] = %g after %g (strictly ascending)", l, lambda[l],
+                     lambda[l - 1]);
+    }
+    if (!ctx->rg_unscored_dev) {
+        ABC_HIP(ctx, hipMalloc((void**)&ctx->rg_unscored_dev, sizeof(unsigned long long)));
+        ABC_HIP(ctx, hipMemset(ctx->rg_unscored_dev, 0, sizeof(unsigned long long)));
+    }
+    for (size_t l = 0; l < L; l++) ctx->rg_lambda[l] = lambda[l];
+    ctx->rg_L = L;
+    return ABC_OK;
+}
+
+// the context's record for a regressing call of `slots` fits under the setting (hcorr_record's rules)
+static int ridge_record(abc_ctx* ctx, const char* fn, size_t slots, size_t P, AbcRg* rg) {
+    const size_t np = slots * P, nq = slots * ctx->rg_L * P;
+    if (np > ctx->rg_cap_pick || nq > ctx->rg_cap_press) {
+        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->rg_pick) { ABC_HIP(ctx, hipFree(ctx->rg_pick)); ctx->rg_pick = nullptr; ctx->rg_cap_pick = 0; }
+        if (ctx->rg_press) { ABC_HIP(ctx, hipFree(ctx->rg_press)); ctx->rg_press = nullptr; ctx->rg_cap_press = 0; }
+        ctx->rg_slots = ctx->rg_Lrec = ctx->rg_P = 0;
+        if (hipMalloc((void**)&ctx->rg_pick, np * sizeof(int32_t)) != hipSuccess ||
+            hipMalloc((void**)&ctx->rg_press, nq * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (ctx->rg_pick) (void)hipFree(ctx->rg_pick);
+            ctx->rg_pick = nullptr;
+            ctx->rg_press = nullptr;
+            ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: no memory for the ridge adjustment's record (%zu picks)", fn, np);
+        }
+        ctx->rg_cap_pick = np;
+        ctx->rg_cap_press = nq;
+    }
+    ctx->rg_slots = ctx->rg_Lrec = ctx->rg_P = 0;         // nothing recorded until the call has queued its fits (tg_run)
+    for (size_t l = 0; l < ctx->rg_L; l++) rg->lambda[l] = ctx->rg_lambda[l];
+    rg->L = (int)ctx->rg_L;
+    rg->pick = ctx->rg_pick;
+    rg->press = ctx->rg_press;
+    rg->unscored = ctx->rg_unscored_dev;
+    return ABC_OK;
+}
+
+extern "C" int abc_adjust_last_ridge(abc_ctx* ctx, int32_t* pick, size_t cap_pick, double* press, size_t cap_press, size_t* slots,
+                                     size_t* L, size_t* P) {
+    CHECK_CTX(ctx);
+    if (!slots || !L || !P) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_adjust_last_ridge: null argument (slots, L and P are required)");
+    *slots = ctx->rg_slots;
+    *L = ctx->rg_Lrec;
+    *P = ctx->rg_P;
+    size_t np = ctx->rg_slots * ctx->rg_P, nq = np * ctx->rg_Lrec;
+    if (np > cap_pick) np = cap_pick;
+    if (nq > cap_press) nq = cap_press;
+    if (np && !pick) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_adjust_last_ridge: null argument (pick with cap_pick = %zu)", cap_pick);
+    if (nq && !press) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_adjust_last_ridge: null argument (press with cap_press = %zu)", cap_press);
+    if (np) ABC_HIP(ctx, hipMemcpyAsync(pick, ctx->rg_pick, np * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (nq) ABC_HIP(ctx, hipMemcpyAsync(press, ctx->rg_press, nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ABC_OK;
+}
+
+extern "C" int abc_adjust_ridge_unscored(abc_ctx* ctx, uint64_t* count, int reset) {
+    CHECK_CTX(ctx);
+    if (!count) ABC_FAIL(ctx, ABC_ERR_INVALID, "abc_adjust_ridge_unscored: null argument (count is required)");
+    unsigned long long dev = 0;
+    if (ctx->rg_unscored_dev) {
+        ABC_HIP(ctx, hipMemcpyAsync(&dev, ctx->rg_unscored_dev, sizeof(dev), hipMemcpyDeviceToHost, ctx->stream));
+        if (reset) ABC_HIP(ctx, hipMemsetAsync(ctx->rg_unscored_dev, 0, sizeof(dev), ctx->stream));
         ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     *count = (uint64_t)dev;
@@ -1697,8 +1784,9 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     size_t b = abc_targets_need(N, A, B, K, r.any_excl);
     if (ctx->tf_buf && r.fits()) b += N * P * 8 + 256;                                      // forward(Y)
     const bool hc = ctx->hcorr && r.fits();
-    if (r.regress()) b += abc_adjust_need(N, A, P, B, K, hc);
-    if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T, hc);
+    const size_t rg = r.fits() ? ctx->rg_L : 0;
+    if (r.regress()) b += abc_adjust_need(N, A, P, B, K, hc, rg);
+    if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T, hc, rg);
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
     if (r.path_summary()) b += abc_path_summary_need(B, r.path->Ks, r.path->T, P, r.method) + (r.idx ? 0 : B * K * 8 + 256);
     else b += r.prod.need(B, K, P);
@@ -1714,7 +1802,7 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
 }
 
 // The ranking or (regress) the ranking with the adjustment, then the product if one is asked for; device pointers, the workspace reserved.
-static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const AbcHc* hc) {
+static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const AbcHc* hc, const AbcRg* rg) {
     const size_t B = r.B, K = r.K;
     const bool summary = r.segments();
     uint64_t* ix = r.idx;
@@ -1741,7 +1829,7 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
         }
         abc_adj_keep pk;
         ABC_TRY(launch_rank_targets_path(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr, Yt, Yt ? &tf : nullptr, hc));
+                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr, Yt, Yt ? &tf : nullptr, hc, rg));
         if (!ps) return ABC_OK;
         SmValues pv = {};
         pv.method = r.method;
@@ -1762,7 +1850,7 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
         if (r.adj) od = *r.adj;
         ABC_TRY(launch_rank_targets_adjust(ctx, r.X, r.ldx, Yt ? Yt : r.Y, Yt ? r.N : r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt,
                                            B, r.exclude, r.any_excl, K, r.kernel, ix, d, &od, summary ? &keep : nullptr,
-                                           Yt ? &tf : nullptr, hc));
+                                           Yt ? &tf : nullptr, hc, rg));
     }
     if (!summary) return ABC_OK;
     SmValues sv = {};
@@ -1776,14 +1864,22 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
     return r.prod.launch(ctx, sv, B, K, r.P, fn);
 }
 
-// tg_run_queued under the variance correction: the call's second fits go to the context's record, which names them only after
-// everything has been queued without an error
+// tg_run_queued under the variance correction and the ridge adjustment: the call's second fits, picks and PRESS go to the context's
+// records, which name them only after everything has been queued without an error
 static int tg_run(abc_ctx* ctx, const char* fn, const TgRequest& r) {
     AbcHc hcd = {nullptr, nullptr};
     const bool hcon = ctx->hcorr && r.fits() && r.P;
     const size_t slots = r.kind == TG_PATH ? r.B * r.path->T : r.B;
     if (hcon) ABC_TRY(hcorr_record(ctx, fn, slots, r.A, r.P, &hcd));
-    ABC_TRY(tg_run_queued(ctx, fn, r, hcon ? &hcd : nullptr));
+    AbcRg rgd = {};
+    const bool rgon = ctx->rg_L && r.fits() && r.P;
+    if (rgon) ABC_TRY(ridge_record(ctx, fn, slots, r.P, &rgd));
+    ABC_TRY(tg_run_queued(ctx, fn, r, hcon ? &hcd : nullptr, rgon ? &rgd : nullptr));
+    if (rgon) {
+        ctx->rg_slots = slots;
+        ctx->rg_Lrec = ctx->rg_L;
+        ctx->rg_P = r.P;
+    }
     if (hcon) {
         ctx->hc_slots = slots;
         ctx->hc_a1 = r.A + 1;

@@ -407,6 +407,13 @@ inline Mat2D param_transf(const Mat2D& V, bool inverse = false) {
 // on, every call that regresses rescales the residuals of its adjusted rows by a fitted model of the residual variance.
 inline void set_adjust_hcorr(bool on) { check(abc_ctx_set_adjust_hcorr(context(), on ? 1 : 0)); }
 
+// Ridge adjustment with the penalty chosen by leave-one-out PRESS (abc_ctx_set_adjust_ridge; the definition is in the header):
+// every call that regresses then returns, per parameter, the ridge fit of the penalty of `lambda` (strictly ascending, at most
+// ABC_RIDGE_MAXL entries) with the smallest PRESS.  An empty list turns the setting off.
+inline void set_adjust_ridge(const std::vector<double>& lambda) {
+    check(abc_ctx_set_adjust_ridge(context(), lambda.empty() ? nullptr : lambda.data(), lambda.size()));
+}
+
 // hcoef of the last regressing call made under the correction (abc_adjust_last_hcorr), slot after slot: (slots * (A + 1)) x P,
 // row s (A + 1) the log residual variance at the observation of slot s (NaN: skipped), the A rows after it its slopes
 inline Mat2D last_hcorr() {

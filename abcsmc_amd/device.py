@@ -178,6 +178,16 @@ def adjust_hcorr(on=True, ctx=None, device=0):
     return ctx.adjust_hcorr(on)
 
 
+def adjust_ridge(lambdas, ctx=None, device=0):
+    """Context manager: the ridge adjustment with the penalty chosen by leave-one-out PRESS (Context.adjust_ridge,
+    abc_ctx_set_adjust_ridge) on ctx, or on the default context of `device`, inside the block.  Every rank_targets_* call that
+    regresses then returns, per parameter, the ridge fit of the penalty of `lambdas` with the smallest PRESS as coef, and makes its
+    adjusted rows from it; their arguments and results are otherwise unchanged, and ctx.last_ridge() returns the call's picks and
+    PRESS values."""
+    ctx = ctx if ctx is not None else _lib.default_context(device)
+    return ctx.adjust_ridge(lambdas)
+
+
 def _path_ks(Ks):
     """The tolerance list as a uint64 array (it stays in host memory) and its largest entry."""
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))

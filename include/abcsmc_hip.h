@@ -521,6 +521,50 @@ int abc_adjust_last_hcorr(abc_ctx* ctx, double* hcoef, size_t cap, size_t* slots
 /* (slot, parameter) pairs skipped by rule 5 since the context was created or the last reset. */
 int abc_adjust_hcorr_skipped(abc_ctx* ctx, uint64_t* count, int reset);
 
+/* ---- ridge adjustment with the penalty chosen by leave-one-out PRESS (R abc: method = "ridge") ---------------------------------
+ * The local-linear fit breaks down where few rows are retained relative to the number of covariates, or where the covariates are
+ * nearly collinear inside the tolerance window (PLS scores are orthogonal over the training rows, not over one target's K nearest
+ * rows).  With this setting on, every call that regresses fits each slot once per penalty of an ascending list and keeps, per
+ * parameter, the fit whose exact leave-one-out prediction error (PRESS) is smallest.  Per slot (a target b, or (b, t) on a
+ * tolerance path with K = K_t) and per parameter j; w_e, x_e, the shift by the first retained row, W, xm, xbar, thetabar, C and c
+ * are the plain fit's, on the transformed scale when parameter transforms are set:
+ *   1. For every l, C^(l) = C except for the diagonal, C^(l)_kk = fma(lambda_l, C_kk, C_kk): lm.ridge's penalty, which scales
+ *      every covariate to unit variance, written on the unscaled moments.
+ *   2. beta_l = C^(l)^-1 c by the plain fit's sweep in component order; the skip rule is the plain fit's, applied to C^(l).
+ *   3. alpha_l = thetabar - beta_l' xbar by the plain fit's chain.  For lambda_l == 0 beta_l and alpha_l are the plain fit's bits.
+ *   4. M_l is the swept left block: the inverse over the kept pivots, the rows and columns of skipped pivots 0.
+ *   5. For a row with w_e > 0, r_e[j] = v_e[j] - alpha_l[j], v_e the plain adjusted value with beta_l (rule 1 of the variance
+ *      correction above, with the stored alpha_l).
+ *   6. The leverage h_e = w_e (1 / W + q_e), q_e = xt_e' M_l xt_e with xt_e[k] = (x_e[k] - x_0[k]) - xm[k], the shifted, centred
+ *      covariate of the moments: s_k = sum_m M_l[k][m] xt_e[m] (an fma chain from 0.0, m ascending), q_e = sum_k xt_e[k] s_k (an
+ *      fma chain from 0.0, k ascending).
+ *   7. PRESS_l[j] = sum over w_e > 0 of w_e (r_e[j] / (1 - h_e))^2, the exact leave-one-out residuals of the weighted ridge fit with
+ *      an unpenalised intercept and the penalty matrix held fixed.  Rows of weight 0 take no part.
+ *   8. If any contributing row has 1 - h_e <= 1e-10 (the fit interpolates), PRESS_l[j] = +inf for every j; a NaN counts as +inf.
+ *   9. pick[j] = the smallest l with the smallest PRESS_l[j]; if every l is +inf, pick[j] = L - 1 and the pair counts as unscored.
+ *  10. coef[:, j] = (alpha_pick, beta_pick); rows above nc are 0.
+ * With L = 1 the same pass runs, the pick is trivial and the record holds that penalty's PRESS.  rank and status are those of the
+ * call with the setting off (the pivots of the unpenalised C, the same bits), as are idx, dist and weight.  Everything that reads
+ * coef sees the ridge fit: the adjusted rows, every product under method 1, the path summary, the back-transform, and the variance
+ * correction, whose second fit stays unpenalised and models the residuals of the ridge fit.  On a tolerance path slot (b, t) of
+ * coef, pick and press is made as abc_rank_targets_adjust_dev with K = K_t makes it (that call's order of sums) and has that
+ * call's bits; the path's rank, status, post_mean and h keep theirs.  Every reduction's order depends on (K, nc, P, L) only: a
+ * slot's outputs are the same bits alone, in any batch and through either entry point.  With the setting off (the default) every
+ * output of every call keeps its bits.
+ * lambda: host memory, copied; strictly ascending, every entry finite and >= 0, 1 <= L <= ABC_RIDGE_MAXL, else ABC_ERR_INVALID and
+ * the setting stays as it was.  L = 0 or lambda = NULL turns the setting off.  Calls that do not regress ignore it.
+ * Workspace: per target of a batch, L fits of 1 + nc + (1 + nc) P + nc^2 doubles and L P doubles per row tile. */
+enum { ABC_RIDGE_MAXL = 8 };
+int abc_ctx_set_adjust_ridge(abc_ctx* ctx, const double* lambda, size_t L);
+/* The record of the last regressing call made under the setting, copied to host memory: pick (slots x P, at most cap_pick
+ * entries) and press (slots x L x P, at most cap_press doubles; +inf: rule 8); either may be NULL when its cap is 0.  *slots, *L
+ * and *P are always written, 0 / 0 / 0 while there is nothing.  Synchronises.  The record lives in device buffers of the context,
+ * allocated or grown only while the setting is on and freed with the context. */
+int abc_adjust_last_ridge(abc_ctx* ctx, int32_t* pick, size_t cap_pick, double* press, size_t cap_press,
+                          size_t* slots, size_t* L, size_t* P);
+/* (slot, parameter) pairs for which no penalty could be scored (rule 9) since the context was created or the last reset. */
+int abc_adjust_ridge_unscored(abc_ctx* ctx, uint64_t* count, int reset);
+
 /* ---- tolerance path: one batched ranking, the rejection estimate and the local-linear fit at several tolerances ------------
  * What cv4abc does with tols = c(.005, .01, .05): ONE ranking at K_max = Ks[T-1] (idx and dist, K_max x B, are the bits of
  * abc_rank_targets_dev with K = K_max; dist may be NULL), and from it an estimate at every tolerance K_t of an ascending list.
