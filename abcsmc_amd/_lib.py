@@ -233,6 +233,9 @@ SIGNATURES = {
     "abc_ctx_set_adjust_ridge": (_i, [_vp, _vp, _sz]),
     "abc_adjust_last_ridge": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "abc_adjust_ridge_unscored": (_i, [_vp, _vp, _i]),
+    "abc_ctx_set_row_weights": (_i, [_vp, _vp, _sz]),
+    "abc_ctx_set_row_weights_dev": (_i, [_vp, _vp, _sz]),
+    "abc_row_weights_info": (_i, [_vp, _vp, _vp, _vp]),
     "abc_rank_targets_adjust_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _i, _vp, _vp,
                                          _vp]),
     "abc_particle_ranking_pls_targets_adjust": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _i, _vp, _vp,
@@ -338,6 +341,7 @@ class Context:
         self.device = device
         self._hcorr = False          # the variance correction as set through this object (adjust_hcorr restores it)
         self._ridge = ()             # the ridge penalties as set through this object (adjust_ridge restores them)
+        self._row_weights = None     # the row weights as set through this object (row_weights restores them)
 
     @classmethod
     def from_handle(cls, handle, device):
@@ -347,6 +351,7 @@ class Context:
         self.device = int(device)
         self._hcorr = False
         self._ridge = ()
+        self._row_weights = None
         self._borrowed = True
         return self
 
@@ -579,6 +584,52 @@ class Context:
         n = C.c_uint64(0)
         self.check(lib().abc_adjust_ridge_unscored(self._h, C.byref(n), int(reset)))
         return n.value
+
+    def set_row_weights(self, w):
+        """Row importance weights of the batched ranking (abc_ctx_set_row_weights / _dev; the definition is in the header): one
+        finite weight >= 0 per row of the table, at least one positive, as a NumPy array / sequence (host) or a float64 torch tensor
+        (a device tensor is read on the device); None for off (the default).  The context keeps its own copy.  It applies to every
+        rank_targets_* / particle_ranking_PLS_targets* call of this context, whose N must equal the count."""
+        import numpy as np
+        if w is None:
+            self.check(lib().abc_ctx_set_row_weights(self._h, None, 0))
+            self._row_weights = None
+            return
+        if hasattr(w, "data_ptr"):                                   # a torch tensor
+            import torch
+            t = w.detach().reshape(-1).to(torch.float64).contiguous()
+            if t.is_cuda:
+                torch.cuda.synchronize(t.device)
+                self.check(lib().abc_ctx_set_row_weights_dev(self._h, t.data_ptr(), t.numel()))
+                self._row_weights = t.clone()
+                return
+            w = t.numpy()
+        a = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1))
+        if a.size == 0:
+            raise ValueError("row weights: an empty array (None turns the setting off)")
+        self.check(lib().abc_ctx_set_row_weights(self._h, a.ctypes.data, a.size))
+        self._row_weights = a.copy()
+
+    def row_weights(self, w):
+        """Context manager: set_row_weights(w) inside the block, what was set before (through this object) after it."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            before = self._row_weights
+            self.set_row_weights(w)
+            try:
+                yield self
+            finally:
+                self.set_row_weights(before)
+        return scope()
+
+    def row_weights_info(self):
+        """(N, positive, ess) of the row weights that are set (abc_row_weights_info): their count (0: off), the number of positive
+        ones and (sum w)^2 / sum w^2 of the whole table"""
+        n, pos, ess = C.c_size_t(0), C.c_size_t(0), C.c_double(0.0)
+        self.check(lib().abc_row_weights_info(self._h, C.byref(n), C.byref(pos), C.byref(ess)))
+        return n.value, pos.value, ess.value
 
     def set_alias_mode(self, mode):
         """ALIAS_DEVICE (default: the resampling table built on the GPU by verified prefix scans) or ALIAS_HOST: abc_ctx_set_alias_mode"""

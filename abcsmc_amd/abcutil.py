@@ -169,10 +169,14 @@ def _ridge_out(ctx, o, ridge, lead):
     return o
 
 
-def _with_transf(ctx, transf, bounds, P, call, hcorr=False, ridge=None):
+def _with_transf(ctx, transf, bounds, P, call, hcorr=False, ridge=None, row_weights=None):
     """call() under the context's parameter transforms transf / bounds (None: whatever the context holds), with hcorr under the
-    heteroscedastic variance correction (False: whatever the context holds) and with ridge under the ridge adjustment with those
-    penalties (None: whatever the context holds); all restored afterwards"""
+    heteroscedastic variance correction (False: whatever the context holds), with ridge under the ridge adjustment with those
+    penalties (None: whatever the context holds) and with row_weights under those row importance weights (None: whatever the
+    context holds); all restored afterwards"""
+    if row_weights is not None:
+        with ctx.row_weights(row_weights):
+            return _with_transf(ctx, transf, bounds, P, call, hcorr, ridge)
     if ridge is not None:
         with ctx.adjust_ridge(_ridge_list(ridge)):
             return _with_transf(ctx, transf, bounds, P, call, hcorr)
@@ -188,9 +192,11 @@ def _with_transf(ctx, transf, bounds, P, call, hcorr=False, ridge=None):
         return call()
 
 
-def _tf_kw(transf, bounds, hcorr=False, ridge=None):
-    """transf / bounds / hcorr / ridge as keywords for a wrapped call, only when they are given"""
+def _tf_kw(transf, bounds, hcorr=False, ridge=None, row_weights=None):
+    """transf / bounds / hcorr / ridge / row_weights as keywords for a wrapped call, only when they are given"""
     kw = {}
+    if row_weights is not None:
+        kw["row_weights"] = row_weights
     if hcorr:
         kw["hcorr"] = True
     if ridge is not None:
@@ -203,20 +209,32 @@ def _tf_kw(transf, bounds, hcorr=False, ridge=None):
 
 
 def particle_ranking_PLS_targets(X_orig, Y_orig, targets, training_fraction, K, exclude=None, max_comp=0,
-                                 rule=_lib.RULE_DEFAULT, details=False, ctx=None):
+                                 rule=_lib.RULE_DEFAULT, details=False, ctx=None, row_weights=None):
     """particle_ranking_PLS for B observed targets at once (abc_particle_ranking_pls_targets): ONE fit shared by all of
     them.  targets: (B, M); exclude: B row numbers (or None; -1 / 2**64 - 1 = none) never ranked for their target (the row
     still takes part in the fit).  Returns idx (B, K): row b = the first K of particle_ranking_PLS(X, Y, targets[b]).
-    details=True: dict(idx, dist (B, K), post_mean (B, P): mean parameter row of each target's K rows, ncomp)."""
+    details=True: dict(idx, dist (B, K), post_mean (B, P): mean parameter row of each target's K rows, ncomp).
+    row_weights: None or one importance weight per row of the table (N finite weights >= 0, at least one positive;
+    abc_ctx_set_row_weights, the definition is in the header), set in the context around this call, here and in every
+    particle_ranking_PLS_targets* function below.  A table whose rows are not draws from the prior needs them: the rows of an SMC
+    generation from set 1 on come from the previous set's perturbation kernel, and their weight prior / proposal is what
+    weight_predictive_prior returns for all N rows of the generation; it is accepted as is, any positive scale is fine:
+        w = weight_predictive_prior(priors, theta, theta_prev, w_prev, dv_prev)  # theta: the N rows of this generation
+        r = particle_ranking_PLS_targets(X, theta, targets, 0.5, K, details=True, row_weights=w)
+        r["post_mean"]                                                           # sum w_e theta_e / sum w_e of the K rows
+    idx and dist never depend on the weights.  post_mean becomes the weighted mean; under the adjustment a row weighs its kernel
+    weight times its row weight everywhere (weight, the fit, hcorr, ridge, every product under "loclinear"), and under
+    "rejection" the products are the weighted products of the retained rows.  A target whose retained rows all weigh 0 is not
+    fitted: status bit 2 (value 4), NaN in coef, theta and the products, ess 0."""
     ctx = _ctx(ctx)
     X, Y, T, N, M, P, B, K, ex = _targets_args(X_orig, Y_orig, targets, training_fraction, K, exclude)
     idx = np.empty((B, K), dtype=np.uint64)
     dist = np.empty((B, K))
     pm = np.empty((B, P))
     ncomp = C.c_int32(0)
-    ctx.check(lib().abc_particle_ranking_pls_targets(ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction),
-                                                     int(max_comp), int(rule), _p(ex), K, _p(idx), _p(dist), _p(pm),
-                                                     C.addressof(ncomp)))
+    _with_transf(ctx, None, None, P, row_weights=row_weights, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets(
+        ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K, _p(idx),
+        _p(dist), _p(pm), C.addressof(ncomp))))
     if details:
         return dict(idx=idx, dist=dist, post_mean=pm, ncomp=ncomp.value)
     return idx
@@ -226,7 +244,7 @@ _KERNELS = {"epanechnikov": _lib.KERNEL_EPANECHNIKOV, "rectangular": _lib.KERNEL
 
 
 def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fraction, K, exclude=None, kernel="epanechnikov",
-                                        max_comp=0, rule=_lib.RULE_DEFAULT, theta=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
+                                        max_comp=0, rule=_lib.RULE_DEFAULT, theta=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None, row_weights=None):
     """particle_ranking_PLS_targets followed by the local-linear regression adjustment of every target's K rows on their PLS
     scores (abc_particle_ranking_pls_targets_adjust; Beaumont, Zhang & Balding 2002; the definition is in the header).  kernel:
     "epanechnikov" (default) or "rectangular".  Returns dict(idx (B, K), dist (B, K), theta (B, K, P): the adjusted rows, or None
@@ -259,7 +277,7 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
     status = np.empty(B, dtype=np.int32)
     out = _lib.AdjustOut(_p(th), _p(w), _p(coef), _p(rank), _p(status))
     ncomp = C.c_int32(0)
-    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_adjust(
+    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, row_weights=row_weights, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_adjust(
         ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K, kernel, _p(idx),
         _p(dist), C.byref(out), C.addressof(ncomp))))
     pm = coef[:, 0] if transf is None else untransform_params(coef[:, 0], transf, bounds)
@@ -272,7 +290,7 @@ def particle_ranking_PLS_targets_adjust(X_orig, Y_orig, targets, training_fracti
 
 
 def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction, Ks, kernel="epanechnikov", exclude=None,
-                                      max_comp=0, rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
+                                      max_comp=0, rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None, row_weights=None):
     """Tolerance path (abc_particle_ranking_pls_targets_path): particle_ranking_PLS_targets ONCE at K_max = Ks[-1], then the
     rejection estimate and the local-linear fit of particle_ranking_PLS_targets_adjust at every tolerance of the strictly ascending
     list Ks (at most 16): what cv4abc computes for tols = c(...), without ranking once per tolerance.  Tolerance t uses the first
@@ -300,7 +318,7 @@ def particle_ranking_PLS_targets_path(X_orig, Y_orig, targets, training_fraction
     h = np.empty((B, nt))
     path = _lib.Path(_p(ks), nt, _p(pm), _p(coef), _p(rank), _p(status), _p(h))
     ncomp = C.c_int32(0)
-    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path(
+    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, row_weights=row_weights, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path(
         ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), kernel, _p(idx),
         _p(dist), C.byref(path), C.addressof(ncomp))))
     r = dict(post_mean=pm, coef=coef, alpha=coef[:, :, 0], rank=rank, status=status, h=h, Ks=ks.astype(np.int64), idx=idx,
@@ -319,7 +337,7 @@ _METHODS = {"rejection": _lib.POSTERIOR_REJECTION, "loclinear": _lib.POSTERIOR_L
 
 def particle_ranking_PLS_targets_path_summary(X_orig, Y_orig, targets, training_fraction, Ks, probs=(0.025, 0.5, 0.975), truth=None,
                                               method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                              rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
+                                              rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None, row_weights=None):
     """particle_ranking_PLS_targets_path with the summaries of particle_ranking_PLS_targets_summary at every tolerance
     (abc_particle_ranking_pls_targets_path_summary; the definition is in the header): the ranking, the fit and, under "rejection",
     the sort of every (target, parameter) are made once for all of Ks.  Tolerance t's quantiles and CDF are those of the summary
@@ -350,7 +368,7 @@ def particle_ranking_PLS_targets_path_summary(X_orig, Y_orig, targets, training_
         o["cdf"] = np.empty((B, nt, P))
         sm.truth, sm.cdf = tr.ctypes.data, o["cdf"].ctypes.data
     ncomp = C.c_int32(0)
-    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path_summary(
+    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, row_weights=row_weights, call=lambda: ctx.check(lib().abc_particle_ranking_pls_targets_path_summary(
         ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), method, kernel,
         _p(idx), _p(dist), C.byref(path), C.byref(sm), C.addressof(ncomp))))
     if transf is not None:
@@ -365,7 +383,7 @@ def particle_ranking_PLS_targets_path_summary(X_orig, Y_orig, targets, training_
 
 
 def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx,
-                     transf=None, bounds=None, hcorr=False, ridge=None):
+                     transf=None, bounds=None, hcorr=False, ridge=None, row_weights=None):
     """The call of particle_ranking_PLS_targets_{summary,density,joint,draws}.  make(lead, P) -> (the product's struct, its outputs as a
     dict, what must stay alive during the call) for lead = (B,).  Returns the outputs with idx, dist and ncomp added.  transf /
     bounds: the parameter transforms of particle_ranking_PLS_targets_adjust around the call ("loclinear" only; "rejection" does
@@ -383,7 +401,7 @@ def _targets_product(product, make, X_orig, Y_orig, targets, training_fraction, 
     dist = np.empty((B, K))
     ncomp = C.c_int32(0)
     entry = getattr(lib(), "abc_particle_ranking_pls_targets_" + product)
-    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, call=lambda: ctx.check(entry(
+    _with_transf(ctx, transf, bounds, P, hcorr=hcorr, ridge=ridge, row_weights=row_weights, call=lambda: ctx.check(entry(
         ctx.handle, _p(X), _p(Y), N, M, P, _p(T), B, float(training_fraction), int(max_comp), int(rule), _p(ex), K, method, kernel,
         _p(idx), _p(dist), None, C.byref(d), C.addressof(ncomp))))
     o.update(idx=idx, dist=dist, ncomp=ncomp.value)
@@ -418,7 +436,7 @@ def _summary_arg(probs, truth, lead, P):
 
 def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fraction, K, probs=(0.025, 0.5, 0.975), truth=None,
                                          method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                         rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
+                                         rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None, row_weights=None):
     """particle_ranking_PLS_targets followed by weighted posterior quantiles of every target's K retained rows and, with truth
     (B, P), the posterior CDF at the truth (abc_particle_ranking_pls_targets_summary; the definition is in the header).
     method "rejection": the rows' parameters, equal weights; "loclinear": the local-linear adjusted rows with the kernel's weights
@@ -432,7 +450,7 @@ def particle_ranking_PLS_targets_summary(X_orig, Y_orig, targets, training_fract
         o["probs"] = keep[0]
         return s, o, keep
     return _targets_product("summary", make, X_orig, Y_orig, targets, training_fraction, K, method, kernel, exclude, max_comp, rule,
-                            ctx, transf, bounds, hcorr, ridge)
+                            ctx, transf, bounds, hcorr, ridge, row_weights)
 
 
 def weighted_summary(values, weights=None, probs=(0.025, 0.5, 0.975), truth=None, ctx=None):
@@ -464,7 +482,7 @@ def _grid_points(grid, G):
 
 def particle_ranking_PLS_targets_density(X_orig, Y_orig, targets, training_fraction, K, G=512, cut=3.0, bw=None, bw_scale=1.0,
                                          method="rejection", kernel="epanechnikov", exclude=None, max_comp=0,
-                                         rule=_lib.RULE_DEFAULT, dens=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
+                                         rule=_lib.RULE_DEFAULT, dens=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None, row_weights=None):
     """particle_ranking_PLS_targets followed by the weighted Gaussian kernel density of every (target, parameter) on a grid of G
     points and the mode taken from it (abc_particle_ranking_pls_targets_density; the definition is in the header: R's density()
     with bw.nrd0, cut and adjust = bw_scale).  method and kernel as particle_ranking_PLS_targets_summary; bw: given bandwidths
@@ -472,7 +490,7 @@ def particle_ranking_PLS_targets_density(X_orig, Y_orig, targets, training_fract
     grid (B, P, 2): lo_x and step, bw (B, P): the bandwidths used, mode (B, P), mode_dens (B, P), idx (B, K), dist (B, K),
     ncomp)."""
     o = _targets_product("density", lambda lead, P: _density_arg(G, cut, bw_scale, bw, lead, P, dens), X_orig, Y_orig, targets,
-                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge)
+                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge, row_weights)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
 
@@ -504,7 +522,7 @@ def _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens):
 
 def particle_ranking_PLS_targets_joint(X_orig, Y_orig, targets, training_fraction, K, G=64, cut=3.0, bw=None, bw_scale=1.0, pairs=None,
                                        method="rejection", kernel="epanechnikov", exclude=None, max_comp=0, rule=_lib.RULE_DEFAULT,
-                                       dens=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
+                                       dens=True, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None, row_weights=None):
     """particle_ranking_PLS_targets followed by the joint posterior of every target, what a pairs plot draws
     (abc_particle_ranking_pls_targets_joint; the definition is in the header): the weighted means, the covariance matrix
     (numpy.cov with aweights) and the Pearson correlations of the P parameters, and for every pair of parameters in pairs (rows
@@ -515,7 +533,7 @@ def particle_ranking_PLS_targets_joint(X_orig, Y_orig, targets, training_fractio
     x (B, P, G): every parameter's grid points, grid (B, P, 2), bw (B, P), mode (B, npairs, 2), mode_dens (B, npairs), pairs
     (npairs, 2), idx (B, K), dist (B, K), ncomp)."""
     o = _targets_product("joint", lambda lead, P: _joint_arg(G, cut, bw_scale, bw, pairs, lead, P, dens), X_orig, Y_orig, targets,
-                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge)
+                         training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge, row_weights)
     o["x"] = _grid_points(o["grid"], int(G))
     return o
 
@@ -544,7 +562,7 @@ def _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P):
 
 def particle_ranking_PLS_targets_draws(X_orig, Y_orig, targets, training_fraction, K, S, smooth=False, seed=0, method="rejection",
                                        kernel="epanechnikov", bw=None, bw_scale=1.0, stream=None, exclude=None, max_comp=0,
-                                       rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None):
+                                       rule=_lib.RULE_DEFAULT, ctx=None, transf=None, bounds=None, hcorr=False, ridge=None, row_weights=None):
     """particle_ranking_PLS_targets followed by S posterior draws of every target, made on the device
     (abc_particle_ranking_pls_targets_draws; the definition is in the header): rows of the target's K retained rows resampled with
     their weights (method and kernel as particle_ranking_PLS_targets_summary), as they are (smooth=False, the weighted bootstrap)
@@ -555,7 +573,7 @@ def particle_ranking_PLS_targets_draws(X_orig, Y_orig, targets, training_fractio
     each draw came from (idx[b, src[b, s]] is its row of the set), ess (B,): the effective sample size W^2 / sum w^2, bw (B, P):
     the bandwidths used (NaN with smooth=False), idx (B, K), dist (B, K), ncomp)."""
     return _targets_product("draws", lambda lead, P: _draws_arg(S, smooth, seed, bw, bw_scale, stream, lead, P), X_orig, Y_orig,
-                            targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge)
+                            targets, training_fraction, K, method, kernel, exclude, max_comp, rule, ctx, transf, bounds, hcorr, ridge, row_weights)
 
 
 def weighted_draws(values, weights=None, S=1000, smooth=False, seed=0, bw=None, bw_scale=1.0, stream=None, ctx=None):
@@ -584,7 +602,7 @@ def hpd_levels(dens, step_x, step_y, probs=(0.5, 0.9, 0.95)):
 
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
                        ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False, transf=None,
-                       bounds=None, hcorr=False, ridge=None):
+                       bounds=None, hcorr=False, ridge=None, row_weights=None):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
     without replacement (numpy Generator seeded with `seed`) serve as pseudo-observed data, each ranked against the set with
     itself excluded (the fit is shared: the row stays in it), and the posterior mean of its K nearest rows estimates its
@@ -601,7 +619,9 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
     observation carried back.  hcorr=True: the heteroscedastic variance correction, handed on likewise and ignored under
     "rejection".  It rescales the adjusted rows about alpha and leaves alpha itself alone, so statistic="mean" under "loclinear"
     is unaffected; the median, the mode, truth_cdf and ci95 do change.  ridge: the penalties of the ridge adjustment, handed on
-    likewise and ignored under "rejection"; alpha is then the ridge fit's, so every statistic under "loclinear" changes."""
+    likewise and ignored under "rejection"; alpha is then the ridge fit's, so every statistic under "loclinear" changes.
+    row_weights: the row importance weights of particle_ranking_PLS_targets (one per row of the set), handed to every call, both
+    methods: what a table that is not drawn from the prior needs."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -613,7 +633,7 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
         raise ValueError("statistic must be 'mean', 'median' or 'mode'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
     theta = np.ascontiguousarray(Y[rows])
-    tkw = _tf_kw(transf, bounds, hcorr, ridge)
+    tkw = _tf_kw(transf, bounds, hcorr, ridge, row_weights)
     sm = None
     if statistic == "median" or coverage:
         sm = particle_ranking_PLS_targets_summary(X, Y, X[rows], training_fraction, K, probs=(0.5, 0.025, 0.975),
@@ -626,7 +646,7 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
                                                  max_comp=max_comp, rule=rule, dens=False, ctx=ctx, **tkw)
     elif method == "rejection":
         r = particle_ranking_PLS_targets(X, Y, X[rows], training_fraction, K, exclude=rows, max_comp=max_comp, rule=rule,
-                                         details=True, ctx=ctx)
+                                         details=True, ctx=ctx, **_tf_kw(None, None, row_weights=row_weights))
     else:
         r = particle_ranking_PLS_targets_adjust(X, Y, X[rows], training_fraction, K, exclude=rows, kernel=kernel,
                                                 max_comp=max_comp, rule=rule, theta=False, ctx=ctx, **tkw)
@@ -645,7 +665,7 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
 
 def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
                             ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False, transf=None,
-                            bounds=None, hcorr=False, ridge=None):
+                            bounds=None, hcorr=False, ridge=None, row_weights=None):
     """cross_validate_pls at every tolerance of the strictly ascending list Ks from ONE call of
     particle_ranking_PLS_targets_path: cv4abc with tols = c(...).  The left-out rows are drawn from `seed` exactly as
     cross_validate_pls draws them.  method: "rejection" (the mean of the Ks[t] nearest rows) or "loclinear" (alpha of the fit at
@@ -657,8 +677,8 @@ def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fracti
     coverage_ks (T, P): the Kolmogorov distance of the finite truth_cdf values from the uniform (coverage_ks below), and
     best_calibrated (P,): the index of the tolerance with the smallest coverage_ks (0 where all are NaN).  transf / bounds as
     cross_validate_pls (handed on only when given); the "loclinear" mean estimate is then alpha_back of the path.  hcorr=True as
-    cross_validate_pls: alpha and so statistic="mean" are unaffected; the median, truth_cdf, ci95 and coverage_ks do change.  ridge as
-    cross_validate_pls."""
+    cross_validate_pls: alpha and so statistic="mean" are unaffected; the median, truth_cdf, ci95 and coverage_ks do change.  ridge
+    and row_weights as cross_validate_pls."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -670,7 +690,7 @@ def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fracti
         raise ValueError("statistic must be 'mean' or 'median'")
     rows = np.sort(np.random.default_rng(seed).choice(N, size=n_targets, replace=False)).astype(np.int64)
     theta = np.ascontiguousarray(Y[rows])
-    tkw = _tf_kw(transf, bounds, hcorr, ridge)
+    tkw = _tf_kw(transf, bounds, hcorr, ridge, row_weights)
     if statistic == "median" or coverage:
         r = particle_ranking_PLS_targets_path_summary(X, Y, X[rows], training_fraction, Ks, probs=(0.5, 0.025, 0.975),
                                                       truth=theta if coverage else None, method=method, kernel=kernel, exclude=rows,

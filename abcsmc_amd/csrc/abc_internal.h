@@ -132,6 +132,11 @@ struct abc_ctx {
     double* rg_press;
     size_t rg_cap_pick, rg_cap_press, rg_slots, rg_Lrec, rg_P;
     unsigned long long* rg_unscored_dev;
+    // row importance weights of the batched ranking (abc_ctx_set_row_weights): the context's own copy of the rw_N weights (device;
+    // rw_N == 0: off), the number of positive ones and (sum w)^2 / sum w^2, from the check made when they were set
+    double* rw_dev;
+    size_t rw_N, rw_pos;
+    double rw_ess;
     unsigned long long wx_moved_counts, generation_repeats;      // abc_generation_repeats
     bool wx_gather_rows;     // diagnostic (ABC_DIAG=1 ABC_WX_GATHER=1, set at context creation): the sharded generation's Wilcoxon rule by
                              // gathering the validation rows on every rank (rounds 1-4) instead of the sharded cascade
@@ -301,7 +306,12 @@ size_t abc_targets_need(size_t N, size_t A, size_t B, size_t K, bool any_excl);
 struct abc_tg_scores { const double* S; size_t sld; const double* O; int KCO; };
 int launch_rank_targets(abc_ctx*, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                         const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean, abc_tg_scores* keep = nullptr);
+                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean, abc_tg_scores* keep = nullptr,
+                        const double* om = nullptr);
+// om (optional, here and below): the context's row importance weights (N, device): post_mean, the regression's weights and what
+// follows from them take the RW instances of their kernels; idx and dist never depend on it
+// the check of row weights (targets.hip): out4 (device) = bad entries, positive entries, sum, sum of squares
+int launch_row_weights_check(abc_ctx*, const double* w_dev, size_t N, double* out4_dev);
 // local-linear adjustment of the batched ranking (adjust.hip): the ranking of launch_rank_targets, then the regression of every
 // target's K retained rows on their scores; out: device pointers (abc_adjust_out), dist may be NULL
 size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K, bool hcorr = false, size_t ridge = 0);
@@ -309,7 +319,7 @@ int launch_rank_targets_adjust(abc_ctx*, const double* X, size_t ldx, const doub
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
                                struct abc_adj_keep* keep = nullptr, const struct AbcTf* tf = nullptr,
-                               const struct AbcHc* hc = nullptr, const struct AbcRg* rg = nullptr);
+                               const struct AbcHc* hc = nullptr, const struct AbcRg* rg = nullptr, const double* om = nullptr);
 // tf (optional, transf_dev.h): Y is already forward(Y) (launch_param_transf); theta and keep's readers carry the adjusted rows back
 // hc (optional, adjust_dev.h): the heteroscedastic variance correction, its second fit written to hc->hcoef (B, or B x T on a path,
 // slots laid out as coef); the *_need functions count its moment blocks with hcorr = true
@@ -323,7 +333,7 @@ int launch_rank_targets_path(abc_ctx*, const double* X, size_t ldx, const double
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                              bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path,
                              struct abc_adj_keep* keep = nullptr, const double* Yt = nullptr, const struct AbcTf* tf = nullptr,
-                             const struct AbcHc* hc = nullptr, const struct AbcRg* rg = nullptr);
+                             const struct AbcHc* hc = nullptr, const struct AbcRg* rg = nullptr, const double* om = nullptr);
 // Yt / tf (optional, both or neither): forward(Y) as N x P with ld = N, which the fit reads; post_mean stays the mean of the raw Y.
 // launch_param_transf: the context's parameter transforms over a column-major n x P matrix (adjust.hip: k_tf_apply); tf NULL: a copy; in place is
 // allowed; outside (optional, device): a forward pass adds the entries of transformed columns it found outside their domain
@@ -343,6 +353,7 @@ struct SmValues {
     const double* V;             // method 2: V[e + ldv j], w[e] (NULL: 1)
     size_t ldv;
     const double* w;
+    const double* om;            // methods 0 and 1: the row importance weights (N, device; NULL: none), entry e weighs k_e om[idx[e]]
 };
 size_t abc_summary_need(size_t B, size_t K, size_t P);
 int launch_summary(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_summary* sum);

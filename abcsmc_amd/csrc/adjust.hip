@@ -35,6 +35,10 @@
 //   k_adj_press     grid (row tiles, targets, penalties): the rows' leverages from M_l, the leave-one-out terms, one partial per
 //                   (tile, penalty, parameter)
 //   k_adj_pick      one work-group per target: PRESS per penalty, the pick, coef and the context's record
+// Under row importance weights (abc_ctx_set_row_weights) a row's weight is k_e omega[i_e]: the kernels that make a weight
+// (k_adj_moments, k_adj_moments_path, k_adj_moments2, k_adj_press, k_adj_apply) and k_path_mean have RW instances that read omega
+// where the weight is made (aj_weight_rw), and k_adj_solve / k_adj_pick have RW instances for the all-zero rule (a slot whose
+// weights sum to 0 is not swept).  Calls without the setting launch the RW = false instances, which never see omega.
 // Chunk sizes depend on K only, tile sizes on (nc, P) only, and the gather paths copy the same bits: a target's outputs are the
 // same alone and in any batch.
 #include <math.h>
@@ -187,10 +191,12 @@ __device__ __forceinline__ void aj_chain_from(int l0, const double* __restrict__
 // ranking at K_max = ld; blocks of at most 256 entry groups only.  Grid (chunks of K_max, targets b0 + blockIdx.y).  The chunk's rows are staged once, up to the largest
 // tolerance of the pass; lane l's chain runs over the rows e0 <= e < min(e1, K_l) with h = d_{K_l - 1} and its own fallback, and is
 // absent (nothing written) when e0 >= K_l.  part[(((blockIdx.y T + t) nchs + chunk) U + r) D + c].
-template <int TL>
+// RW: under row importance weights, w_e = k_e om[i_e] (aj_weight_rw; om is not read otherwise).
+template <int TL, bool RW>
 __global__ __launch_bounds__(256) void k_adj_moments_path(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
                                                           size_t ld, AjKs ks, int T, int t0, int nc, int P, int kernel, size_t CH,
-                                                          int TR, size_t b0, size_t nchs, double* __restrict__ part) {
+                                                          int TR, size_t b0, size_t nchs, double* __restrict__ part,
+                                                          const double* __restrict__ om) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x;
     const int U = 1 + nc, D = 1 + nc + P, Wv = nc + P, Ds = aj_stride(nc, P);
@@ -236,7 +242,8 @@ __global__ __launch_bounds__(256) void k_adj_moments_path(AjSrc src, const uint6
         aj_stage_rows(src, ix + r0, shift, tv, nr, nc, P, t);
 #pragma unroll
         for (int l = 0; l < TL; l++)
-            for (int r = t; r < nrl[l]; r += 256) tw[l * TRp + r] = aj_weight(dd[r0 + r], h[l], rect[l]);
+            for (int r = t; r < nrl[l]; r += 256)
+                tw[l * TRp + r] = aj_weight_rw<RW>(dd[r0 + r], h[l], rect[l], om, RW ? (size_t)ix[r0 + r] : 0);
         __syncthreads();
         if (t >= J) continue;
 #pragma unroll
@@ -258,10 +265,14 @@ __global__ __launch_bounds__(256) void k_adj_moments_path(AjSrc src, const uint6
 // grid (targets, tolerances): post_mean[(b T + t) P + j] = the fp64 mean of Y[i_e, j] over e < K_t (NS = 256 / min(P, 256) threads
 // per parameter, each the sum of every NS-th row in ascending order, then those sums in thread order: (K_t, P) only);
 // hout[b T + t] = d_{K_t - 1}.  src is read for the parameters only (columns nc ..).
+// RW (row importance weights): sum om_e Y_e / sum om_e instead, both sums in the order above (the numerator an fma chain, the
+// weights' sum a second chain over the same rows, added up in the same thread order); 0 / 0 = NaN when every om_e is 0.
+template <bool RW>
 __global__ __launch_bounds__(256) void k_path_mean(AjSrc src, int nc, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
                                                    size_t ld, AjKs ks, int T, int P, double* __restrict__ post_mean,
-                                                   double* __restrict__ hout) {
-    __shared__ double red[256];
+                                                   double* __restrict__ hout, const double* __restrict__ om) {
+    __shared__ double red[RW ? 512 : 256];                          // RW: the weights' sums behind the numerators
+    [[maybe_unused]] double* redw = red + 256;                                    // (RW instances only)
     const int t = threadIdx.x, tt = blockIdx.y;
     const size_t b = blockIdx.x, K = ks.K[tt];
     const uint64_t* ix = idx + b * ld;
@@ -271,14 +282,29 @@ __global__ __launch_bounds__(256) void k_path_mean(AjSrc src, int nc, const uint
     const int j = t % PW, s = t / PW;
     for (int j0 = 0; j0 < P; j0 += PW) {
         const bool mine = s < NS && j0 + j < P;
-        double a = 0.0;
-        if (mine)
-            for (size_t e = (size_t)s; e < K; e += (size_t)NS) a += aj_val(src, (size_t)ix[e], nc + j0 + j, nc);
+        double a = 0.0, sw = 0.0;
+        if (mine) {
+            if constexpr (RW) {
+                for (size_t e = (size_t)s; e < K; e += (size_t)NS) {
+                    const double w = om[(size_t)ix[e]];
+                    a = fma(w, aj_val(src, (size_t)ix[e], nc + j0 + j, nc), a);
+                    sw += w;
+                }
+            } else {
+                for (size_t e = (size_t)s; e < K; e += (size_t)NS) a += aj_val(src, (size_t)ix[e], nc + j0 + j, nc);
+            }
+        }
         red[t] = a;
+        if constexpr (RW) redw[t] = sw;
         __syncthreads();
         if (mine && s == 0) {
             for (int q = 1; q < NS; q++) a += red[q * PW + j];
-            post_mean[(b * T + tt) * (size_t)P + j0 + j] = a / (double)K;
+            if constexpr (RW) {
+                for (int q = 1; q < NS; q++) sw += redw[q * PW + j];
+                post_mean[(b * T + tt) * (size_t)P + j0 + j] = a / sw;
+            } else {
+                post_mean[(b * T + tt) * (size_t)P + j0 + j] = a / (double)K;
+            }
         }
         __syncthreads();
     }
@@ -290,9 +316,11 @@ __global__ __launch_bounds__(256) void k_path_mean(AjSrc src, int nc, const uint
 // registers; otherwise an entry's running sum passes between tiles through part.  The chain is the same either way and for every TR.
 // ld: a target's rows start at idx + b ld (K itself, or K_max when the rows are a prefix of a longer ranking); pstride: blocks
 // between two targets in part (the grid's chunk count, or more when other tolerances' blocks lie between).
+// RW: under row importance weights, w_e = k_e om[i_e]: one more scattered 8-byte read per staged row, where the weight is made.
+template <bool RW>
 __global__ __launch_bounds__(256) void k_adj_moments(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
                                                      size_t ld, size_t K, int nc, int P, int kernel, size_t CH, int TR, size_t b0,
-                                                     size_t pstride, double* __restrict__ part) {
+                                                     size_t pstride, double* __restrict__ part, const double* __restrict__ om) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x;
     const int U = 1 + nc, D = 1 + nc + P, Wv = nc + P, Ds = aj_stride(nc, P);
@@ -316,7 +344,7 @@ __global__ __launch_bounds__(256) void k_adj_moments(AjSrc src, const uint64_t* 
         const int nr = (e1 - r0 < (size_t)TR) ? (int)(e1 - r0) : TR;
         __syncthreads();                                        // the shift is written, the previous tile consumed
         aj_stage_rows(src, ix + r0, shift, tv, nr, nc, P, t);
-        for (int r = t; r < nr; r += 256) tw[r] = aj_weight(dd[r0 + r], h, rect);
+        for (int r = t; r < nr; r += 256) tw[r] = aj_weight_rw<RW>(dd[r0 + r], h, rect, om, RW ? (size_t)ix[r0 + r] : 0);
         __syncthreads();
         if (regs) {
             if (t < J) aj_chain(tv, tw, Ds, nr, t % D, 4 * (t / D), racc);
@@ -346,12 +374,13 @@ __global__ __launch_bounds__(256) void k_adj_moments(AjSrc src, const uint64_t* 
 // first pass, z'_j = z_e[j] - z_0[j], z = 2 log|v_e[j] - alpha_j| with v_e[j] = aj_adjusted of the raw row (the bits k_adj_apply gives).
 // A row with a zero or non-finite residual makes entry (0, j) non-finite for good (w u_0 = w >= 0: NaN from 0 x inf, or an
 // infinity that no finite term removes), which is how k_adj_solve sees the skip rule.  cf_lds: the slot's (1 + nc) x P
-// coefficients staged in LDS.
+// coefficients staged in LDS.  RW: w_e = k_e om[i_e], as the first pass.
+template <bool RW>
 __global__ __launch_bounds__(256) void k_adj_moments2(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
                                                       size_t ld, size_t K, int nc, int P, int A, int kernel, size_t CH, int TR, size_t b0,
                                                       size_t pstride, const double* __restrict__ O, int KCO,
                                                       const double* __restrict__ coef, int T, int tt, int cf_lds,
-                                                      double* __restrict__ part2) {
+                                                      double* __restrict__ part2, const double* __restrict__ om) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x;
     const int U = 1 + nc, D = 1 + nc + P, Wv = nc + P, Ds = aj_stride(nc, P);
@@ -393,7 +422,7 @@ __global__ __launch_bounds__(256) void k_adj_moments2(AjSrc src, const uint64_t*
         for (int r = t; r < nr; r += 256) {
             tv[r * Ds] = 1.0;
             for (int c = D; c < Ds; c++) tv[r * Ds + c] = 0.0;
-            tw[r] = aj_weight(dd[r0 + r], h, rect);
+            tw[r] = aj_weight_rw<RW>(dd[r0 + r], h, rect, om, RW ? (size_t)ix[r0 + r] : 0);
         }
         __syncthreads();
         for (int q = t; q < nr * P; q += 256) {                 // theta_e[j] -> z'_e[j] (its own slot; the scores are only read)
@@ -446,7 +475,10 @@ struct AjHcSolve {
 // HC (the variance correction's second fit): C, the means and so every pivot decision from the same blocks by the same operations;
 // the right-hand sides from hs.part2, shifted by the first row's z; hs.hcoef instead of coef (a = zbar - g' xbar in row 0); a
 // parameter is skipped (NaN in row 0, zeros below) when K <= nc + 2 or its moment sum w z' is not finite; rank and status stay.
-template <bool HC>
+// RW (row importance weights): the blocks are k_adj_moments<true>'s and the same code reads them; a slot whose weights' sum is not
+// positive (every w_e = 0) takes the all-zero rule instead of the sweep: coef rows 0 .. nc NaN, the rows above 0, rank 0, status
+// bit 2 beside the bits of their own rules; HC: every parameter of the slot skipped and counted.
+template <bool HC, bool RW>
 __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist,
                                                    size_t ld, AjKs ks, int T, size_t CH, int nc, int P, int A, int kernel,
                                                    const double* __restrict__ O, int KCO, const double* __restrict__ part, int nchs,
@@ -483,6 +515,24 @@ __global__ __launch_bounds__(256) void k_adj_solve(AjSrc src, const uint64_t* __
     }
     __syncthreads();
     const double W = sW[0];
+    if constexpr (RW) {
+        if (!(W > 0.0)) {                                           // (uniform) the all-zero rule
+            const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+            if constexpr (HC) {
+                double* cz = hs.hcoef + (b * hs.hstride + hs.hoff) * (size_t)(A + 1) * P;
+                for (int q = t; q < (A + 1) * P; q += 256) cz[q] = (q < P) ? qnan : 0.0;
+                if (t == 0 && P > 0 && hs.skipped) atomicAdd(hs.skipped, (unsigned long long)P);
+            } else {
+                double* cz = coef + slot * (size_t)(A + 1) * P;
+                for (int q = t; q < (A + 1) * P; q += 256) cz[q] = (q / P <= nc) ? qnan : 0.0;
+                if (t == 0) {
+                    if (rank) rank[slot] = 0;
+                    if (status) status[slot] = 4 | (nc > 0 ? 1 : 0) | ((kernel == 0 && aj_fallback(dist + b * ld, K)) ? 2 : 0);
+                }
+            }
+            return;
+        }
+    }
     for (int k = t; k < nc; k += 256) {
         xm[k] = xs[k] / W;
         xb[k] = xm[k] + (aj_val(src, i0, k, nc) - O[b * KCO + k]);
@@ -724,9 +774,12 @@ __host__ __device__ __forceinline__ AjPlanR aj_plan_r(int nc, int P) {
 // parameter) pairs: v = aj_adjusted with beta_l, r = v - alpha_l, u = r / den_e, the term w_e (u u), 0 for a row of weight 0.
 // Then per parameter: NS = 256 / min(P, 256) threads, each the sum of every NS-th row's term ascending, those sums in thread
 // order.  pp[((bl L + l) tiles + tile) P + j]; +inf in every j when a row of positive weight has den_e <= 1e-10 or NaN.
+// RW: w_e = k_e om[i_e], as the moments (a row of om = 0 takes no part, as the Epanechnikov row at distance h).
+template <bool RW>
 __global__ __launch_bounds__(256) void k_adj_press(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist, size_t ld,
                                                    size_t K, int nc, int P, int kernel, const double* __restrict__ O, int KCO,
-                                                   const double* __restrict__ rfit, size_t b0, double* __restrict__ pp) {
+                                                   const double* __restrict__ rfit, size_t b0, double* __restrict__ pp,
+                                                   const double* __restrict__ om) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     __shared__ int s_inf;
     const AjPlanR pr = aj_plan_r(nc, P);
@@ -759,7 +812,7 @@ __global__ __launch_bounds__(256) void k_adj_press(AjSrc src, const uint64_t* __
         const int r = q / Wv, c = q % Wv;
         tv[q] = aj_val(src, (size_t)ix[e0 + r], c, nc);     // raw: the scores are centred below
     }
-    for (int r = t; r < nr; r += 256) wd[2 * r] = aj_weight(dd[e0 + r], h, rect);
+    for (int r = t; r < nr; r += 256) wd[2 * r] = aj_weight_rw<RW>(dd[e0 + r], h, rect, om, RW ? (size_t)ix[e0 + r] : 0);
     __syncthreads();
     for (int r = t; r < nr; r += 256) {
         const double* x = tv + r * Wv;
@@ -824,7 +877,9 @@ struct AjRgOut {
 
 // one work-group per target b0 + blockIdx.x: PRESS_l[j] = the tiles' partials summed in tile order (NaN counts as +inf),
 // pick[j] = the smallest l with the smallest PRESS (L - 1 and counted when every l is +inf), coef[b][:, j] = (alpha, beta) of the
-// pick, rows above nc 0
+// pick, rows above nc 0.  RW: a slot under the all-zero rule (W of its fits not positive) has every PRESS +inf, pick L - 1, every
+// parameter counted as unscored, and keeps k_adj_solve's coef (NaN in rows 0 .. nc)
+template <bool RW>
 __global__ __launch_bounds__(256) void k_adj_pick(int nc, int P, int A, int L, int tiles, const double* __restrict__ rfit,
                                                   const double* __restrict__ pp, size_t b0, double* __restrict__ coef, AjRgOut ro) {
     __shared__ unsigned s_un;
@@ -834,6 +889,16 @@ __global__ __launch_bounds__(256) void k_adj_pick(int nc, int P, int A, int L, i
     if (t == 0) s_un = 0;
     __syncthreads();
     double* cb = coef + b * (size_t)(A + 1) * P;
+    if constexpr (RW) {
+        if (!(rfit[bl * L * aj_rfit_dbl(nc, P)] > 0.0)) {           // (uniform)
+            for (int j = t; j < P; j += 256) {
+                for (int l = 0; l < L; l++) ro.press[(rs * L + l) * (size_t)P + j] = inf;
+                ro.pick[rs * (size_t)P + j] = L - 1;
+            }
+            if (t == 0 && P > 0 && ro.unscored) atomicAdd(ro.unscored, (unsigned long long)P);
+            return;
+        }
+    }
     for (int j = t; j < P; j += 256) {
         int best = L - 1;
         double pbest = inf;
@@ -861,12 +926,13 @@ __global__ __launch_bounds__(256) void k_adj_pick(int nc, int P, int A, int L, i
 // grid (tiles of TR rows, targets b0 + blockIdx.y): theta[(b K + e) P + j] = theta_e[j] - sum_k beta_kj x_e[k] (one fma chain in k
 // order), weight[b K + e] = w_e.  HC: the variance correction on top (aj_hcorr with the second fit hcoef, unless row 0 of the
 // parameter holds the skip flag), before the back-transform
-template <bool HC>
+// RW: weight[b K + e] = k_e om[i_e]
+template <bool HC, bool RW>
 __global__ __launch_bounds__(256) void k_adj_apply(AjSrc src, const uint64_t* __restrict__ idx, const double* __restrict__ dist, size_t K,
                                                    int nc, int P, int A, int kernel, const double* __restrict__ O, int KCO,
                                                    const double* __restrict__ coef, int TR, int beta_lds, size_t b0, AbcTf tf,
                                                    double* __restrict__ theta, double* __restrict__ weight,
-                                                   const double* __restrict__ hcoef) {
+                                                   const double* __restrict__ hcoef, const double* __restrict__ om) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int t = threadIdx.x, Wv = nc + P;
     const size_t b = b0 + blockIdx.y, e0 = (size_t)blockIdx.x * TR;
@@ -877,9 +943,29 @@ __global__ __launch_bounds__(256) void k_adj_apply(AjSrc src, const uint64_t* __
     if (weight) {
         const double h = dd[K - 1];
         const bool rect = kernel == 1 || aj_fallback(dd, K);
-        for (int r = t; r < nr; r += 256) weight[b * K + e0 + r] = aj_weight(dd[e0 + r], h, rect);
+        for (int r = t; r < nr; r += 256)
+            weight[b * K + e0 + r] = aj_weight_rw<RW>(dd[e0 + r], h, rect, om, RW ? (size_t)ix[e0 + r] : 0);
     }
     if (!theta) return;
+    if constexpr (RW) {
+        // the all-zero rule without components: no NaN slope reaches the rows below, so the target's weights are looked at here
+        // (nc > 0: k_adj_solve's NaN slopes make every row NaN)
+        if (nc == 0) {                                              // (uniform)
+            __shared__ int s_any;
+            if (t == 0) s_any = 0;
+            __syncthreads();
+            const double h = dd[K - 1];
+            const bool rect = kernel == 1 || aj_fallback(dd, K);
+            int any = 0;
+            for (size_t e = t; e < K; e += 256) any |= aj_weight_rw<true>(dd[e], h, rect, om, (size_t)ix[e]) > 0.0;
+            if (any) s_any = 1;
+            __syncthreads();
+            if (!s_any) {
+                for (int q = t; q < nr * P; q += 256) theta[(b * K + e0) * (size_t)P + q] = __longlong_as_double(0x7ff8000000000000ll);
+                return;
+            }
+        }
+    }
     const double* beta = coef + b * (size_t)(A + 1) * P + P;   // beta_kj at beta[k P + j]
     double* tv = sm;                                           // TR x Wv: [x (observation-centred) | theta]
     double* bl = sm + (((size_t)TR * Wv + 1) & ~(size_t)1);    // nc x P coefficients (beta_lds)
@@ -1017,19 +1103,21 @@ size_t aj_ridge_bytes(size_t K, size_t A, size_t P, size_t L) {      // one targ
 // `part` (pl: that launch's plan); coef receives the picked fit at slot b (stride 1)
 int aj_ridge(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, const double* d, size_t ld, size_t K, int nc, int P, int A,
              int kernel, const abc_tg_scores& sc, const double* part, const AjPlan& pl, size_t b0, size_t nb, const AbcRg& rg,
-             double* rfit, double* pp, double* coef, size_t rstride, size_t roff) {
+             double* rfit, double* pp, double* coef, size_t rstride, size_t roff, const double* om) {
     AjLam lam = {};
     for (int l = 0; l < rg.L; l++) lam.v[l] = rg.lambda[l];
     const AjPlanR pr = aj_plan_r(nc, P);
     const size_t tiles = (K + pr.TR - 1) / pr.TR, lds_s = aj_solve_lds(nc);
     const AjRgOut ro = {rg.pick, rg.press, rg.unscored, rstride, roff};
     ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_rsolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_press, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pr.lds));
+    const auto press = om ? k_adj_press<true> : k_adj_press<false>;
+    const auto pick = om ? k_adj_pick<true> : k_adj_pick<false>;
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)press, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pr.lds));
     hipLaunchKernelGGL(k_adj_rsolve, dim3((unsigned)nb, (unsigned)rg.L), dim3(256), lds_s, ctx->stream, src, idx, ld, K, pl.CH, nc, P,
                        sc.O, sc.KCO, part, (int)pl.nch, b0, lam, rfit);
-    hipLaunchKernelGGL(k_adj_press, dim3((unsigned)tiles, (unsigned)nb, (unsigned)rg.L), dim3(256), pr.lds, ctx->stream, src, idx, d, ld,
-                       K, nc, P, kernel, sc.O, sc.KCO, (const double*)rfit, b0, pp);
-    hipLaunchKernelGGL(k_adj_pick, dim3((unsigned)nb), dim3(256), 0, ctx->stream, nc, P, A, rg.L, (int)tiles, (const double*)rfit,
+    hipLaunchKernelGGL(press, dim3((unsigned)tiles, (unsigned)nb, (unsigned)rg.L), dim3(256), pr.lds, ctx->stream, src, idx, d, ld,
+                       K, nc, P, kernel, sc.O, sc.KCO, (const double*)rfit, b0, pp, om);
+    hipLaunchKernelGGL(pick, dim3((unsigned)nb), dim3(256), 0, ctx->stream, nc, P, A, rg.L, (int)tiles, (const double*)rfit,
                        (const double*)pp, b0, coef, ro);
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
@@ -1051,7 +1139,7 @@ size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K, bool hc
 int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                                const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
-                               abc_adj_keep* keep, const AbcTf* tf, const AbcHc* hc, const AbcRg* rg) {
+                               abc_adj_keep* keep, const AbcTf* tf, const AbcHc* hc, const AbcRg* rg, const double* om) {
     const AbcTf tfd = tf ? *tf : AbcTf{nullptr, nullptr, nullptr};
     double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
     if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
@@ -1092,14 +1180,20 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
     const int D = 1 + nc + Pi;
     const size_t lds_m = (size_t)(((D + 1) & ~1) + ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, Pi)) * 8;
     const size_t lds_s = aj_solve_lds(nc);
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+    // under row importance weights (om) every kernel that makes or sums weights is its RW instance; without them, the instances
+    // that ran before the setting existed
+    const auto moments = om ? k_adj_moments<true> : k_adj_moments<false>;
+    const auto moments2 = om ? k_adj_moments2<true> : k_adj_moments2<false>;
+    const auto solve = om ? k_adj_solve<false, true> : k_adj_solve<false, false>;
+    const auto solve_hc = om ? k_adj_solve<true, true> : k_adj_solve<true, false>;
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
     double* hcoef = (hc && Pi > 0) ? hc->hcoef : nullptr;              // the variance correction: a second fit after every first
     const AjPlan2 p2 = aj_plan2(pl, nc, Pi);
     double* part2 = nullptr;
     if (hcoef) {
         part2 = (double*)abc_ws_alloc(ctx, bb * pl.nch * (size_t)(1 + nc) * P * 8);
         if (!part2) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)solve_hc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
     }
     const bool ridge = rg && rg->L > 0 && Pi > 0;                      // the penalised fits replace coef before anything reads it
     double *rfit = nullptr, *rpp = nullptr;
@@ -1114,19 +1208,19 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
     ks.K[0] = K;
     for (size_t b0 = 0; b0 < B; b0 += bb) {
         const size_t nb = (B - b0 < bb) ? B - b0 : bb;
-        hipLaunchKernelGGL(k_adj_moments, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds_m, ctx->stream, src, (const uint64_t*)idx,
-                           (const double*)d, K, K, nc, Pi, kernel, pl.CH, pl.TR, b0, pl.nch, part);
-        hipLaunchKernelGGL(k_adj_solve<false>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+        hipLaunchKernelGGL(moments, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds_m, ctx->stream, src, (const uint64_t*)idx,
+                           (const double*)d, K, K, nc, Pi, kernel, pl.CH, pl.TR, b0, pl.nch, part, om);
+        hipLaunchKernelGGL(solve, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
                            (const double*)d, K, ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0,
                            coef, out->rank, out->status, hs0);
         ABC_HIP(ctx, hipGetLastError());
         if (ridge)
-            ABC_TRY(aj_ridge(ctx, src, idx, d, K, K, nc, Pi, (int)A, kernel, sc, part, pl, b0, nb, *rg, rfit, rpp, coef, 1, 0));
+            ABC_TRY(aj_ridge(ctx, src, idx, d, K, K, nc, Pi, (int)A, kernel, sc, part, pl, b0, nb, *rg, rfit, rpp, coef, 1, 0, om));
         if (!hcoef) continue;
-        hipLaunchKernelGGL(k_adj_moments2, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src, (const uint64_t*)idx,
+        hipLaunchKernelGGL(moments2, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src, (const uint64_t*)idx,
                            (const double*)d, K, K, nc, Pi, (int)A, kernel, pl.CH, p2.TR, b0, pl.nch, sc.O, sc.KCO, (const double*)coef, 1,
-                           0, p2.cf_lds, part2);
-        hipLaunchKernelGGL(k_adj_solve<true>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+                           0, p2.cf_lds, part2, om);
+        hipLaunchKernelGGL(solve_hc, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
                            (const double*)d, K, ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0,
                            (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, hs1);
         ABC_HIP(ctx, hipGetLastError());
@@ -1149,14 +1243,15 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
         if (TR < 1) TR = 1;
         const int beta_lds = (nc * Pi <= AJ_APPLY_DBL) ? 1 : 0;
         const size_t lds_a = (size_t)((((size_t)TR * Wv + 1) & ~(size_t)1) + (beta_lds ? (size_t)nc * Pi : 0)) * 8;     // <= 64 KiB
-        const auto apply = hcoef ? k_adj_apply<true> : k_adj_apply<false>;
+        const auto apply = om ? (hcoef ? k_adj_apply<true, true> : k_adj_apply<false, true>)
+                              : (hcoef ? k_adj_apply<true, false> : k_adj_apply<false, false>);
         ABC_HIP(ctx, hipFuncSetAttribute((const void*)apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
         const size_t tiles = (K + TR - 1) / TR;
         for (size_t b0 = 0; b0 < B; b0 += AJ_MAX_GRID_Y) {
             const size_t nb = (B - b0 < AJ_MAX_GRID_Y) ? B - b0 : AJ_MAX_GRID_Y;
             hipLaunchKernelGGL(apply, dim3((unsigned)tiles, (unsigned)nb), dim3(256), lds_a, ctx->stream, src, (const uint64_t*)idx,
                                (const double*)d, K, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)coef, TR, beta_lds, b0,
-                               tfd, out->theta, out->weight, (const double*)hcoef);
+                               tfd, out->theta, out->weight, (const double*)hcoef, om);
             ABC_HIP(ctx, hipGetLastError());
         }
     }
@@ -1174,12 +1269,13 @@ size_t aj_path_batch(size_t K, size_t A, size_t P, size_t B, size_t T) {
 
 template <int TL>
 int aj_launch_moments_path(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, const double* d, size_t ld, const AjKs& ks, int T,
-                           int t0, int nc, int P, int kernel, const AjPlan& pl, size_t b0, size_t nb, double* part) {
+                           int t0, int nc, int P, int kernel, const AjPlan& pl, size_t b0, size_t nb, double* part, const double* om) {
     const int D = 1 + nc + P;
     const size_t lds = (size_t)(((D + 1) & ~1) + TL * ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, P)) * 8;       // <= 64.5 KiB
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_moments_path<TL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_adj_moments_path<TL>, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds, ctx->stream, src, idx, d, ld, ks, T,
-                       t0, nc, P, kernel, pl.CH, pl.TR, b0, pl.nch, part);
+    const auto mp = om ? k_adj_moments_path<TL, true> : k_adj_moments_path<TL, false>;
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(mp, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds, ctx->stream, src, idx, d, ld, ks, T,
+                       t0, nc, P, kernel, pl.CH, pl.TR, b0, pl.nch, part, om);
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
 }
@@ -1201,7 +1297,7 @@ size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T,
 int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                              const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
                              bool any_excl, int kernel, uint64_t* idx, double* dist, const abc_path* path, abc_adj_keep* keep,
-                             const double* Yt, const AbcTf* tf, const AbcHc* hc, const AbcRg* rg) {
+                             const double* Yt, const AbcTf* tf, const AbcHc* hc, const AbcRg* rg, const double* om) {
     const int T = (int)path->T, Pi = (int)P;
     AjKs ks = {};
     for (int t = 0; t < T; t++) ks.K[t] = path->Ks[t];
@@ -1255,7 +1351,11 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
         const bool wide = D * ((1 + nc + 3) / 4) > 256;              // more than 256 entry groups: k_adj_moments, once per tolerance
         const size_t lds_m = (size_t)(((D + 1) & ~1) + ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, Pi)) * 8;
         const size_t lds_s = aj_solve_lds(nc);
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+        const auto moments = om ? k_adj_moments<true> : k_adj_moments<false>;        // (the RW instances: as the adjustment)
+        const auto moments2 = om ? k_adj_moments2<true> : k_adj_moments2<false>;
+        const auto solve = om ? k_adj_solve<false, true> : k_adj_solve<false, false>;
+        const auto solve_hc = om ? k_adj_solve<true, true> : k_adj_solve<true, false>;
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
         // the variance correction: at every tolerance the fit of abc_rank_targets_adjust_dev with K = K_t over again, in that call's
         // own chunks (coef1: its first fit, which differs from the path's coef in the last bits where the chunks of K_max and of
         // K_t differ), then its second fit, so that slot (b, t) of hcoef has that call's bits; one tolerance at a time, the first
@@ -1278,7 +1378,7 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
         if (hcoef) {
             part2 = (double*)abc_ws_alloc(ctx, bb * pl.nch * blk2 * 8);
             if (!part2) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
-            ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
+            ABC_HIP(ctx, hipFuncSetAttribute((const void*)solve_hc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
         }
         const AjHcSolve hs0 = {nullptr, nullptr, nullptr, nullptr, 1, 0};
         for (size_t b0 = 0; b0 < B; b0 += bb) {
@@ -1286,9 +1386,9 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
             if (wide) {
                 for (int t = 0; t < T; t++) {
                     const size_t ncht = (ks.K[t] + pl.CH - 1) / pl.CH;
-                    hipLaunchKernelGGL(k_adj_moments, dim3((unsigned)ncht, (unsigned)nb), dim3(256), lds_m, ctx->stream, src,
+                    hipLaunchKernelGGL(moments, dim3((unsigned)ncht, (unsigned)nb), dim3(256), lds_m, ctx->stream, src,
                                        (const uint64_t*)idx, (const double*)d, K, ks.K[t], nc, Pi, kernel, pl.CH, pl.TR, b0,
-                                       (size_t)T * pl.nch, part + (size_t)t * pl.nch * blk);
+                                       (size_t)T * pl.nch, part + (size_t)t * pl.nch * blk, om);
                 }
                 ABC_HIP(ctx, hipGetLastError());
             } else {
@@ -1296,14 +1396,14 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
                 for (int hi = T; hi > 0;) {
                     const int n = hi < 4 ? hi : 4, TL = n > 2 ? 4 : n, t0 = hi - TL;
                     switch (TL) {
-                    case 1: ABC_TRY(aj_launch_moments_path<1>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part)); break;
-                    case 2: ABC_TRY(aj_launch_moments_path<2>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part)); break;
-                    default: ABC_TRY(aj_launch_moments_path<4>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part)); break;
+                    case 1: ABC_TRY(aj_launch_moments_path<1>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part, om)); break;
+                    case 2: ABC_TRY(aj_launch_moments_path<2>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part, om)); break;
+                    default: ABC_TRY(aj_launch_moments_path<4>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part, om)); break;
                     }
                     hi -= n;
                 }
             }
-            hipLaunchKernelGGL(k_adj_solve<false>, dim3((unsigned)nb, (unsigned)T), dim3(256), lds_s, ctx->stream, src,
+            hipLaunchKernelGGL(solve, dim3((unsigned)nb, (unsigned)T), dim3(256), lds_s, ctx->stream, src,
                                (const uint64_t*)idx, (const double*)d, K, ks, T, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO,
                                (const double*)part, (int)pl.nch, b0, coef, path->rank, path->status, hs0);
             ABC_HIP(ctx, hipGetLastError());
@@ -1316,23 +1416,23 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
                 AjKs k1 = {};
                 k1.K[0] = Kt;
                 const AjHcSolve hs1 = {part2, coef1, hcoef, hcoef ? hc->skipped : nullptr, (size_t)T, (size_t)t};
-                hipLaunchKernelGGL(k_adj_moments, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), lds_t, ctx->stream, src,
-                                   (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, kernel, pt.CH, pt.TR, b0, pt.nch, part);
-                hipLaunchKernelGGL(k_adj_solve<false>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+                hipLaunchKernelGGL(moments, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), lds_t, ctx->stream, src,
+                                   (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, kernel, pt.CH, pt.TR, b0, pt.nch, part, om);
+                hipLaunchKernelGGL(solve, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
                                    (const double*)d, K, k1, 1, pt.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part,
                                    (int)pt.nch, b0, coef1, (int32_t*)nullptr, (int32_t*)nullptr, hs0);
                 if (ridge) {
                     ABC_TRY(aj_ridge(ctx, src, idx, d, K, Kt, nc, Pi, (int)A, kernel, sc, part, pt, b0, nb, *rg, rfit, rpp, coef1,
-                                     (size_t)T, (size_t)t));
+                                     (size_t)T, (size_t)t, om));
                     const size_t cw = (A + 1) * P * 8;
                     ABC_HIP(ctx, hipMemcpy2DAsync(coef + (b0 * T + t) * (A + 1) * P, (size_t)T * cw, coef1 + b0 * (A + 1) * P, cw, cw, nb,
                                                   hipMemcpyDeviceToDevice, ctx->stream));
                 }
                 if (!hcoef) continue;
-                hipLaunchKernelGGL(k_adj_moments2, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src,
+                hipLaunchKernelGGL(moments2, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src,
                                    (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, (int)A, kernel, pt.CH, p2.TR, b0, pt.nch,
-                                   sc.O, sc.KCO, (const double*)coef1, 1, 0, p2.cf_lds, part2);
-                hipLaunchKernelGGL(k_adj_solve<true>, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
+                                   sc.O, sc.KCO, (const double*)coef1, 1, 0, p2.cf_lds, part2, om);
+                hipLaunchKernelGGL(solve_hc, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
                                    (const double*)d, K, k1, 1, pt.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part,
                                    (int)pt.nch, b0, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, hs1);
                 ABC_HIP(ctx, hipGetLastError());
@@ -1353,9 +1453,9 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
         const size_t step = (size_t)1 << 30;
         for (size_t b0 = 0; b0 < B; b0 += step) {
             const size_t nb = (B - b0 < step) ? B - b0 : step;
-            hipLaunchKernelGGL(k_path_mean, dim3((unsigned)nb, (unsigned)T), dim3(256), 0, ctx->stream, Yt ? raw : src, nc,
-                               (const uint64_t*)idx + b0 * K, (const double*)d + b0 * K, K, ks, T, Pi,
-                               path->post_mean ? path->post_mean + b0 * T * P : nullptr, path->h ? path->h + b0 * T : nullptr);
+            hipLaunchKernelGGL(om ? k_path_mean<true> : k_path_mean<false>, dim3((unsigned)nb, (unsigned)T), dim3(256), 0, ctx->stream,
+                               Yt ? raw : src, nc, (const uint64_t*)idx + b0 * K, (const double*)d + b0 * K, K, ks, T, Pi,
+                               path->post_mean ? path->post_mean + b0 * T * P : nullptr, path->h ? path->h + b0 * T : nullptr, om);
             ABC_HIP(ctx, hipGetLastError());
         }
     }

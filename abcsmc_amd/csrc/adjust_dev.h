@@ -36,6 +36,15 @@ __device__ __forceinline__ double aj_weight(double de, double h, bool rect) {
     return 1.0 - t * t;
 }
 
+// ---- row importance weights (abc_ctx_set_row_weights; the definition is in the header) ----
+// w_e = k_e omega[i_e], one fp64 multiplication, in the RW instances only: the others never see omega
+template <bool RW>
+__device__ __forceinline__ double aj_weight_rw(double de, double h, bool rect, const double* __restrict__ om, size_t i) {
+    const double k = aj_weight(de, h, rect);
+    if constexpr (RW) return k * om[i];
+    return k;
+}
+
 // theta*_e[j] = theta_e[j] - sum_k beta_kj x_e[k]: one fma chain in k order; x(k) = x_e[k] (observation-centred score),
 // beta[k ldb] = beta_kj
 template <class XF>

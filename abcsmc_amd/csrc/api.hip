@@ -112,6 +112,7 @@ extern "C" void abc_ctx_destroy(abc_ctx* ctx) {
     if (ctx->rg_pick) (void)hipFree(ctx->rg_pick);
     if (ctx->rg_press) (void)hipFree(ctx->rg_press);
     if (ctx->rg_unscored_dev) (void)hipFree(ctx->rg_unscored_dev);
+    if (ctx->rw_dev) (void)hipFree(ctx->rw_dev);
     if (ctx->wx_rec_dev) (void)hipFree(ctx->wx_rec_dev);
     abc_comm_release(ctx);
     if (ctx->xbuf) (void)hipFree(ctx->xbuf);
@@ -544,6 +545,74 @@ extern "C" int abc_adjust_ridge_unscored(abc_ctx* ctx, uint64_t* count, int rese
         ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     *count = (uint64_t)dev;
+    return ABC_OK;
+}
+
+// ---- row importance weights of the batched ranking ----------------------------------------------------------------------------
+
+// both setters: a copy of the caller's N weights in a buffer of the context's own, checked by one kernel whose four numbers the
+// host reads here; the setting changes only when the check passes
+static int row_weights_set(abc_ctx* ctx, const char* fn, const double* w, size_t N, bool host) {
+    if (!w || N == 0) {
+        if (ctx->rw_dev) {
+            ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            ABC_HIP(ctx, hipFree(ctx->rw_dev));
+        }
+        ctx->rw_dev = nullptr;
+        ctx->rw_N = ctx->rw_pos = 0;
+        ctx->rw_ess = 0.0;
+        return ABC_OK;
+    }
+    double* buf = nullptr;                                      // the weights and, behind them, the check's four numbers
+    if (hipMalloc((void**)&buf, (N + 4) * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: no memory for %zu row weights", fn, N);
+    }
+    double chk[4] = {0.0, 0.0, 0.0, 0.0};
+    int rc = ABC_OK;
+    if (hipMemcpyAsync(buf, w, N * sizeof(double), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        rc = ABC_ERR_HIP;
+    if (rc == ABC_OK) rc = launch_row_weights_check(ctx, buf, N, buf + N);
+    if (rc == ABC_OK && (hipMemcpyAsync(chk, buf + N, sizeof(chk), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                         hipStreamSynchronize(ctx->stream) != hipSuccess))
+        rc = ABC_ERR_HIP;
+    if (rc != ABC_OK) {
+        (void)hipGetLastError();
+        (void)hipFree(buf);
+        ABC_FAIL(ctx, rc, "%s: copying or checking the row weights failed", fn);
+    }
+    if (chk[0] > 0.0 || !(chk[1] > 0.0)) {
+        (void)hipFree(buf);
+        if (chk[0] > 0.0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: %.0f of the %zu row weights are negative or not finite", fn, chk[0], N);
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: none of the %zu row weights is positive", fn, N);
+    }
+    if (!isfinite(chk[2]) || !isfinite(chk[3])) {               // every weighted sum of a call would overflow as these do
+        (void)hipFree(buf);
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: the sum of the %zu row weights or of their squares is not finite (rescale them)", fn, N);
+    }
+    if (ctx->rw_dev) (void)hipFree(ctx->rw_dev);                // (the stream is idle: synchronised above)
+    ctx->rw_dev = buf;
+    ctx->rw_N = N;
+    ctx->rw_pos = (size_t)chk[1];
+    ctx->rw_ess = chk[2] * chk[2] / chk[3];
+    return ABC_OK;
+}
+
+extern "C" int abc_ctx_set_row_weights(abc_ctx* ctx, const double* w, size_t N) {
+    CHECK_CTX(ctx);
+    return row_weights_set(ctx, "abc_ctx_set_row_weights", w, N, true);
+}
+
+extern "C" int abc_ctx_set_row_weights_dev(abc_ctx* ctx, const double* w_dev, size_t N) {
+    CHECK_CTX(ctx);
+    return row_weights_set(ctx, "abc_ctx_set_row_weights_dev", w_dev, N, false);
+}
+
+extern "C" int abc_row_weights_info(abc_ctx* ctx, size_t* N, size_t* positive, double* ess) {
+    CHECK_CTX(ctx);
+    if (N) *N = ctx->rw_N;
+    if (positive) *positive = ctx->rw_pos;
+    if (ess) *ess = ctx->rw_ess;
     return ABC_OK;
 }
 
@@ -1726,6 +1795,8 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
         r.K = r.path->Ks[r.path->T - 1];
     }
     const size_t N = r.N, B = r.B, K = r.K;
+    if (ctx->rw_N && N != ctx->rw_N)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: N = %zu, but the row weights were set for %zu rows", fn, N, ctx->rw_N);
     if (ctx->tf_buf && r.fits() && r.P != ctx->tf_P)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: P = %zu, but the parameter transforms were set for %zu parameters", fn, r.P, ctx->tf_P);
     if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
@@ -1788,7 +1859,9 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     if (r.regress()) b += abc_adjust_need(N, A, P, B, K, hc, rg);
     if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T, hc, rg);
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
-    if (r.path_summary()) b += abc_path_summary_need(B, r.path->Ks, r.path->T, P, r.method) + (r.idx ? 0 : B * K * 8 + 256);
+    // (under row importance weights the rejection path's summaries take the loclinear path's route, one tolerance at a time)
+    if (r.path_summary())
+        b += abc_path_summary_need(B, r.path->Ks, r.path->T, P, ctx->rw_N ? 1 : r.method) + (r.idx ? 0 : B * K * 8 + 256);
     else b += r.prod.need(B, K, P);
     if (!host) return b + abc_ws_need(N, 1, 1, 1, K + 1, 0, 0);
     b += abc_ws_need(N, M, P, A, K + 1, 0, 0) + (rule == ABC_RULE_WILCOXON ? abc_wx_need(N, P, A) : 0);
@@ -1805,6 +1878,7 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
 static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const AbcHc* hc, const AbcRg* rg) {
     const size_t B = r.B, K = r.K;
     const bool summary = r.segments();
+    const double* om = ctx->rw_N ? ctx->rw_dev : nullptr;      // the row importance weights (tg_check: rw_N == N)
     uint64_t* ix = r.idx;
     double* d = r.dist;
     if (summary) {     // every product reads both
@@ -1829,7 +1903,7 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
         }
         abc_adj_keep pk;
         ABC_TRY(launch_rank_targets_path(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr, Yt, Yt ? &tf : nullptr, hc, rg));
+                                         r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr, Yt, Yt ? &tf : nullptr, hc, rg, om));
         if (!ps) return ABC_OK;
         SmValues pv = {};
         pv.method = r.method;
@@ -1839,18 +1913,19 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
         pv.adj = lin ? &pk : nullptr;
         pv.A = (int)r.A;
         pv.kernel = r.kernel;
+        pv.om = om;
         return launch_path_summary(ctx, pv, B, r.path->Ks, r.path->T, r.P, r.prod.sum);
     }
     abc_adj_keep keep;
     if (!r.regress()) {     // (post_mean: of the plain ranking only)
         ABC_TRY(launch_rank_targets(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
-                                    r.any_excl, K, ix, d, r.post_mean));
+                                    r.any_excl, K, ix, d, r.post_mean, nullptr, om));
     } else {                // (without keep nothing is regressed when every member of adj is NULL)
         abc_adjust_out od = {};
         if (r.adj) od = *r.adj;
         ABC_TRY(launch_rank_targets_adjust(ctx, r.X, r.ldx, Yt ? Yt : r.Y, Yt ? r.N : r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt,
                                            B, r.exclude, r.any_excl, K, r.kernel, ix, d, &od, summary ? &keep : nullptr,
-                                           Yt ? &tf : nullptr, hc, rg));
+                                           Yt ? &tf : nullptr, hc, rg, om));
     }
     if (!summary) return ABC_OK;
     SmValues sv = {};
@@ -1861,6 +1936,7 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
     sv.adj = r.regress() ? &keep : nullptr;
     sv.A = (int)r.A;
     sv.kernel = r.kernel;
+    sv.om = om;
     return r.prod.launch(ctx, sv, B, K, r.P, fn);
 }
 

@@ -11,7 +11,7 @@
 //               w_e == 0, whatever the rounding: the search below cannot stop at an entry of weight 0.  With equal weights every
 //               sum is an integer and c_e = e + 1.  S2 is every thread's fma chain over its entries ascending, then a fixed tree
 //               over the threads; ess = c_{K-1}^2 / S2.  The order depends on K only.  Segments with equal weights by
-//               construction (method 0, generic without w) are not scanned: ess = K.
+//               construction (method 0 without row importance weights, generic without w) are not scanned: ess = K.
 //   k_dr_draw   the hot path.  A work-group takes DR_DB consecutive draws of a target.  First a thread per draw makes the
 //               selection block, u and tau = u W, and finds src by binary search in the target's c (K doubles that every
 //               work-group of the target reads: L2 hits after the first); floor(u K) for the unscanned segments.  src goes to LDS.
@@ -188,6 +188,22 @@ __global__ __launch_bounds__(DR_BS) void k_dr_draw(SmArgs a, DrArgs d, size_t b0
     }
 }
 
+// under row importance weights only: a target whose weights are all 0 (its last cumulative weight is not positive) has nothing to
+// draw from: its draws become NaN, its src and ess 0.  Grid (blocks of 256 draws, targets b0 + blockIdx.y); the other targets are
+// not touched.
+__global__ __launch_bounds__(256) void k_dr_void(const double* __restrict__ c, size_t K, size_t S, int P, size_t b0,
+                                                 double* __restrict__ draws, uint64_t* __restrict__ src, double* __restrict__ ess) {
+    const size_t b = b0 + blockIdx.y;
+    if (c[b * K + K - 1] > 0.0) return;                        // (uniform)
+    const size_t s0 = (size_t)blockIdx.x * 256, s = s0 + threadIdx.x;
+    if (ess && blockIdx.x == 0 && threadIdx.x == 0) ess[b] = 0.0;
+    if (src && s < S) src[b * S + s] = 0;
+    if (draws) {
+        const size_t n = (S - s0 < 256 ? S - s0 : 256) * (size_t)P;
+        for (size_t i = threadIdx.x; i < n; i += 256) draws[(b * S + s0) * (size_t)P + i] = dn_nan();
+    }
+}
+
 __global__ __launch_bounds__(256) void k_dr_nan(double* __restrict__ x, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) x[i] = dn_nan();
@@ -214,7 +230,7 @@ int launch_draws(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P,
         hipLaunchKernelGGL(k_dr_nan, dim3((unsigned)((B * P + 255) / 256)), dim3(256), 0, ctx->stream, dr->bw_out, B * P);
         ABC_HIP(ctx, hipGetLastError());
     }
-    const bool weighted = sv.method == 1 || (sv.method == 2 && sv.w);
+    const bool weighted = sv.method == 1 || (sv.method == 2 && sv.w) || (sv.method == 0 && sv.om);   // (om: row importance weights)
     const bool select = dr->draws || dr->src;
     if (!select && !dr->ess) return ABC_OK;
     double* c = weighted ? (double*)abc_ws_alloc(ctx, B * K * 8) : nullptr;
@@ -240,9 +256,15 @@ int launch_draws(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P,
             hipLaunchKernelGGL(k_dr_cdf, dim3(1, (unsigned)nb), dim3(DR_BS), 0, ctx->stream, a, b0, c, d.ess);
             ABC_HIP(ctx, hipGetLastError());
         }
-        if (!select) continue;
-        hipLaunchKernelGGL(draw, dim3(nblk, (unsigned)nb), dim3(DR_BS), 0, ctx->stream, a, d, b0, sp);
-        ABC_HIP(ctx, hipGetLastError());
+        if (select) {
+            hipLaunchKernelGGL(draw, dim3(nblk, (unsigned)nb), dim3(DR_BS), 0, ctx->stream, a, d, b0, sp);
+            ABC_HIP(ctx, hipGetLastError());
+        }
+        if (a.om && c) {     // (the all-zero rule of the row weights)
+            hipLaunchKernelGGL(k_dr_void, dim3((unsigned)((d.S + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, (const double*)c,
+                               K, d.S, (int)P, b0, d.draws, d.src, d.ess);
+            ABC_HIP(ctx, hipGetLastError());
+        }
     }
     return ABC_OK;
 }

@@ -25,6 +25,7 @@ struct SmArgs {
     const double* V;            // method 2
     size_t ldv;
     const double* w;
+    const double* om;           // methods 0 and 1: row importance weights (NULL: none), the weight of entry e times om[idx[e]]
     size_t K;                   // entries of a segment (a tolerance path: K_t)
     size_t ld;                  // row stride of idx and dist (K; a tolerance path: K_max)
     int T, t;                   // tolerance t of T (1, 0 outside a path): coefficients and outputs at slot b T + t
@@ -71,6 +72,7 @@ static inline SmArgs sm_args(const SmValues& sv, size_t K, size_t P) {
     a.V = sv.V;
     a.ldv = sv.ldv;
     a.w = sv.w;
+    a.om = sv.method == 2 ? nullptr : sv.om;
     a.K = K;
     a.ld = K;
     a.T = 1;
@@ -134,8 +136,10 @@ __device__ __forceinline__ double sm_value(const SmArgs& a, const SmSeg& s, size
     return a.V[e + a.ldv * (size_t)s.j];
 }
 
+// under row importance weights (a.om, methods 0 and 1) the weight is k_e om[i_e], the product abc_adjust_out.weight holds (under
+// method 0 k_e = 1, so the bits of om[i_e]); a.om is a kernel argument, uniform over the launch, as a.method and a.w are
 __device__ __forceinline__ double sm_weight(const SmArgs& a, const SmSeg& s, size_t e) {
-    if (a.method == 1) return aj_weight(s.dd[e], s.h, s.rect);
-    if (a.method == 2 && a.w) return a.w[e];
-    return 1.0;
+    if (a.method == 2) return a.w ? a.w[e] : 1.0;
+    const double k = (a.method == 1) ? aj_weight(s.dd[e], s.h, s.rect) : 1.0;
+    return a.om ? k * a.om[(size_t)s.ix[e]] : k;
 }

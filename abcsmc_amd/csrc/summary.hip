@@ -578,7 +578,9 @@ int launch_path_summary(abc_ctx* ctx, const SmValues& sv, size_t B, const size_t
     a.cdf = sum->cdf;
     a.T = (int)T;
     const SmProbs pr = sm_probs(sum);
-    if (sv.method == 0) {
+    // under row importance weights the rejection path's segments are weighted too: the one-sort unit-weight walk does not apply,
+    // and every tolerance goes through the general kernels with K = K_t, as the loclinear path (slot (b, t) = the summary call at K_t)
+    if (sv.method == 0 && !sv.om) {
         SmKs ks = {};
         ks.T = (int)T;
         for (size_t t = 0; t < T; t++) ks.K[t] = Ks[t];

@@ -380,23 +380,67 @@ __global__ __launch_bounds__(256) void k_tg_drop(const uint64_t* __restrict__ si
 }
 
 // post_mean[b P + j] = mean of Y[idx[b K + e], j] over e < K (fp64)
+// RW (row importance weights, abc_ctx_set_row_weights): sum om_e Y_e / sum om_e.  Thread t takes the entries e = t, t + 256, ...
+// ascending (the numerator one fma chain, the weights' sum a second chain), then both go through the same halving tree: the order is
+// fixed by K alone.  0 / 0 = NaN when every om_e is 0.
+template <bool RW>
 __global__ __launch_bounds__(256) void k_tg_post_mean(const double* __restrict__ Y, size_t ldy, int P, const uint64_t* __restrict__ idx,
-                                                      size_t K, double* __restrict__ pm) {
-    __shared__ double red[256];
+                                                      size_t K, double* __restrict__ pm, const double* __restrict__ om) {
+    __shared__ double red[RW ? 512 : 256];                          // RW: the weights' sums behind the numerators
+    [[maybe_unused]] double* redw = red + 256;                                    // (RW instances only)
     const size_t b = blockIdx.x;
     const int t = threadIdx.x;
     for (int j = 0; j < P; j++) {
-        double s = 0.0;
-        for (size_t e = t; e < K; e += 256) s += Y[idx[b * K + e] + ldy * (size_t)j];
+        double s = 0.0, sw = 0.0;
+        if constexpr (RW) {
+            for (size_t e = t; e < K; e += 256) {
+                const size_t i = (size_t)idx[b * K + e];
+                const double w = om[i];
+                s = fma(w, Y[i + ldy * (size_t)j], s);
+                sw += w;
+            }
+            redw[t] = sw;
+        } else {
+            for (size_t e = t; e < K; e += 256) s += Y[idx[b * K + e] + ldy * (size_t)j];
+        }
         red[t] = s;
         __syncthreads();
         for (int w = 128; w > 0; w >>= 1) {
-            if (t < w) red[t] += red[t + w];
+            if (t < w) {
+                red[t] += red[t + w];
+                if constexpr (RW) redw[t] += redw[t + w];
+            }
             __syncthreads();
         }
-        if (t == 0) pm[b * P + j] = red[0] / (double)K;
+        if (t == 0) pm[b * P + j] = RW ? red[0] / redw[0] : red[0] / (double)K;
         __syncthreads();
     }
+}
+
+// the row weights' check: out[0] entries that are negative or not finite, out[1] positive entries, out[2] sum, out[3] sum of
+// squares (over the valid entries).  One work-group: thread t takes the entries t, t + 1024, ... ascending, then a halving tree, so
+// the sums depend on N only.
+__global__ __launch_bounds__(1024) void k_rw_check(const double* __restrict__ w, size_t N, double* __restrict__ out) {
+    __shared__ double r0[1024], r1[1024], r2[1024], r3[1024];
+    const int t = threadIdx.x;
+    double bad = 0.0, pos = 0.0, s1 = 0.0, s2 = 0.0;
+    for (size_t i = t; i < N; i += 1024) {
+        const double v = w[i];
+        if (!(v >= 0.0) || !isfinite(v)) {
+            bad += 1.0;
+            continue;
+        }
+        if (v > 0.0) pos += 1.0;
+        s1 += v;
+        s2 = fma(v, v, s2);
+    }
+    r0[t] = bad; r1[t] = pos; r2[t] = s1; r3[t] = s2;
+    __syncthreads();
+    for (int h = 512; h > 0; h >>= 1) {
+        if (t < h) { r0[t] += r0[t + h]; r1[t] += r1[t + h]; r2[t] += r2[t + h]; r3[t] += r3[t + h]; }
+        __syncthreads();
+    }
+    if (t == 0) { out[0] = r0[0]; out[1] = r1[0]; out[2] = r2[0]; out[3] = r3[0]; }
 }
 
 // rows per thread of the candidate pass: as many as 32 score registers hold, at most four
@@ -463,7 +507,7 @@ size_t abc_targets_need(size_t N, size_t A, size_t B, size_t K, bool any_excl) {
 
 int launch_rank_targets(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
                         const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
-                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean, abc_tg_scores* keep) {
+                        bool any_excl, size_t K, uint64_t* idx, double* dist, double* post_mean, abc_tg_scores* keep, const double* om) {
     const ModelLayout ML = model_layout(M, P, A);
     const int kc = tg_kc(A);
     const int KCO = kc ? kc : (int)A;
@@ -585,8 +629,15 @@ int launch_rank_targets(abc_ctx* ctx, const double* X, size_t ldx, const double*
         ctx->ws_off = fm;
     }
     if (post_mean && P) {
-        hipLaunchKernelGGL(k_tg_post_mean, dim3((unsigned)B), dim3(256), 0, ctx->stream, Y, ldy, (int)P, (const uint64_t*)idx, K, post_mean);
+        hipLaunchKernelGGL(om ? k_tg_post_mean<true> : k_tg_post_mean<false>, dim3((unsigned)B), dim3(256), 0, ctx->stream, Y, ldy, (int)P,
+                           (const uint64_t*)idx, K, post_mean, om);
         ABC_HIP(ctx, hipGetLastError());
     }
+    return ABC_OK;
+}
+
+int launch_row_weights_check(abc_ctx* ctx, const double* w_dev, size_t N, double* out4_dev) {
+    hipLaunchKernelGGL(k_rw_check, dim3(1), dim3(1024), 0, ctx->stream, w_dev, N, out4_dev);
+    ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
 }

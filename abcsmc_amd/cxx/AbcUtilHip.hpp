@@ -414,6 +414,16 @@ inline void set_adjust_ridge(const std::vector<double>& lambda) {
     check(abc_ctx_set_adjust_ridge(context(), lambda.empty() ? nullptr : lambda.data(), lambda.size()));
 }
 
+// Row importance weights of the batched ranking (abc_ctx_set_row_weights; the definition is in the header): one finite weight
+// >= 0 per row of the table (at least one positive), copied by the context.  While set, every particle_ranking_PLS_targets* call
+// on a table of that many rows weighs entry e of a target by its kernel weight times w[idx[e]]; the ranking itself does not
+// change.  weight_predictive_prior's output for the N rows of a generation is accepted as is.
+inline void set_row_weights(const std::vector<double>& w) {
+    if (w.empty()) throw HipError(ABC_ERR_INVALID, "set_row_weights: no weights (clear_row_weights turns the setting off)");
+    check(abc_ctx_set_row_weights(context(), w.data(), w.size()));
+}
+inline void clear_row_weights() { check(abc_ctx_set_row_weights(context(), nullptr, 0)); }
+
 // hcoef of the last regressing call made under the correction (abc_adjust_last_hcorr), slot after slot: (slots * (A + 1)) x P,
 // row s (A + 1) the log residual variance at the observation of slot s (NaN: skipped), the A rows after it its slopes
 inline Mat2D last_hcorr() {

@@ -80,6 +80,16 @@ int main() {
         std::printf("path: %zu rows, h %.3g %.3g %.3g, alpha[0] %.3f %.3f %.3f\n", tp[0].idx.size(), tp[0].h[0], tp[0].h[1], tp[0].h[2],
                     tp[0].alpha(0, 0), tp[0].alpha(1, 0), tp[0].alpha(2, 0));
         if (tp[0].idx.size() != K || !(tp[0].h[0] <= tp[0].h[1] && tp[0].h[1] <= tp[0].h[2])) return 5;
+        // row importance weights: the table's rows weighted as draws that do not come from the prior (here: every other row twice
+        // as likely under the design as under the prior); the ranking stays, the rejection mean moves
+        std::vector<double> omega(X.rows());
+        for (size_t i = 0; i < omega.size(); i++) omega[i] = (i % 2) ? 0.5 : 1.0;
+        set_row_weights(omega);
+        const std::vector<TargetPath> tw = particle_ranking_PLS_targets_path(X, Y, tg, 0.5, {K / 4, K / 2, K});
+        clear_row_weights();
+        std::printf("row weights: post_mean[0] %.3f -> %.3f, same rows %d\n", tp[0].post_mean(2, 0), tw[0].post_mean(2, 0),
+                    (int)(tw[0].idx == tp[0].idx));
+        if (tw[0].idx != tp[0].idx || tw[0].post_mean(2, 0) == tp[0].post_mean(2, 0)) return 6;
     } catch (const HipError& e) {
         std::printf("HipError %d: %s\n", e.code, e.what());
         return 1;

@@ -188,6 +188,15 @@ def adjust_ridge(lambdas, ctx=None, device=0):
     return ctx.adjust_ridge(lambdas)
 
 
+def row_weights(w, ctx=None, device=0):
+    """Context manager: row importance weights of the batched ranking (Context.row_weights, abc_ctx_set_row_weights; the definition
+    is in the header) on ctx, or on the default context of `device`, inside the block.  w: one weight per row of the table, a
+    tensor (a device tensor is copied on the device) or an array.  Every rank_targets_* call inside the block weighs entry e of a
+    target by its kernel weight times w[idx[e]]; idx and dist do not change."""
+    ctx = ctx if ctx is not None else _lib.default_context(device)
+    return ctx.row_weights(w)
+
+
 def _path_ks(Ks):
     """The tolerance list as a uint64 array (it stays in host memory) and its largest entry."""
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))

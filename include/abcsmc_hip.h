@@ -430,7 +430,7 @@ typedef struct {            /* every pointer optional (NULL: not written); devic
     double*  weight;        /* B*K: w_e                                                                                       */
     double*  coef;          /* B x (A+1) x P row-major: [b][0][j] = alpha_j, [b][1+k][j] = beta_kj (0 for k >= nc or skipped) */
     int32_t* rank;          /* B: pivots kept                                                                                 */
-    int32_t* status;        /* B: bit 0 = some pivot skipped, bit 1 = rectangular fallback                                    */
+    int32_t* status;        /* B: bit 0 = some pivot skipped, bit 1 = rectangular fallback, bit 2 = every weight 0 (row weights) */
 } abc_adjust_out;
 enum { ABC_KERNEL_EPANECHNIKOV = 0, ABC_KERNEL_RECTANGULAR = 1 };
 /* Device pointers (as abc_rank_targets_dev; Y required), out's members in device memory. */
@@ -564,6 +564,56 @@ int abc_adjust_last_ridge(abc_ctx* ctx, int32_t* pick, size_t cap_pick, double* 
                           size_t* slots, size_t* L, size_t* P);
 /* (slot, parameter) pairs for which no penalty could be scored (rule 9) since the context was created or the last reset. */
 int abc_adjust_ridge_unscored(abc_ctx* ctx, uint64_t* count, int reset);
+
+/* ---- row importance weights of the batched ranking ------------------------------------------------------------------------------
+ * Everything built on the batched ranking takes the N rows of the table for draws from the prior, as R's abc does: every retained
+ * row counts the same, up to the kernel's factor.  The rows of an SMC generation from set 1 on are draws from the previous set's
+ * perturbation kernel instead, and a reference table may come from any design that is not the prior; every posterior product then
+ * estimates the wrong distribution, by an error that does not shrink with N or K.  The correction is the importance weight of the
+ * row, omega_i = prior(theta_i) / proposal(theta_i), which depends on the row only and not on the target: for a generation it is
+ * what abc_weight_predictive_prior / abc_weights_raw_dev compute for the N rows.  Any positive scale will do.
+ * The setting holds N finite weights omega >= 0 with at least one positive.  While it is set, for every abc_rank_targets_*_dev /
+ * abc_particle_ranking_pls_targets* entry:
+ *   1. A call whose N differs from the stored count is ABC_ERR_INVALID.
+ *   2. idx, dist, the fallback counter and the Epanechnikov fallback rule (distances only) keep every bit: the weights never
+ *      influence which rows are retained.
+ *   3. Entry e of a target weighs w_e = k_e * omega[i_e], one fp64 multiplication, k_e the kernel's weight as without the setting
+ *      (1 under rejection, the rectangular kernel and the fallback).  abc_adjust_out.weight holds w_e, and every place that uses a
+ *      weight uses w_e: the moments of the adjustment and of the path, the second fit of the variance correction, the leverages
+ *      and PRESS of the ridge fit, the weights of every product under either method, the draws' cumulative weights and ess.
+ *   4. post_mean of abc_rank_targets_dev and of the path is sum omega_e Y_e / sum omega_e.  abc_rank_targets_dev: thread t of 256
+ *      takes the entries e = t, t + 256, ... ascending (numerator: one fma chain from 0; the weights' sum: a chain of additions),
+ *      then both pass through the same halving tree.  The path: per parameter NS = 256 / min(P, 256) threads take every NS-th
+ *      entry below K_t the same way, and their sums are added in thread order.  The order is fixed by K (and P) alone.
+ *   5. Under method 0 the products are the weighted products of the retained rows with the weights omega[i_e]: the same kernels on
+ *      the same values and weights as the generic entries (abc_weighted_*) given V = Y[idx[b]] and w = omega[idx[b]].  The path's
+ *      summaries under method 0 take, per tolerance, the general kernels with K = K_t, as under method 1, so slot (b, t) has the
+ *      bits of the summary call at K_t.
+ *   6. A row with omega = 0 is an ordinary zero-weight row, as the Epanechnikov row at distance h is.  The variance correction's
+ *      skip rule keeps its meaning: a zero or non-finite residual skips the parameter whatever the row's weight.
+ *   7. The all-zero rule.  A slot whose retained rows all have w_e = 0 (W = 0) is not fitted: status gets bit 2 (value 4) beside
+ *      the bits of their own rules (bit 0 when nc > 0: rank < nc), rank = 0, coef rows 0 .. nc and the target's theta rows are
+ *      NaN, coef's rows beyond nc stay 0, weight is the zeros it is.  Under the variance correction every parameter of the slot is
+ *      skipped and counted, and its hcoef record holds what a skipped parameter's holds: NaN in row 0, zeros below.  Under ridge
+ *      every (slot, parameter) is unscored and counted, and the record holds pick = L - 1 and press = +inf for every penalty.
+ *      post_mean of such a target is NaN.  In the products every floating-point output of the target is NaN (quantiles, cdf,
+ *      grid, bandwidths, densities, modes, means, covariances, correlations, draws), its ess is 0 and its src entries are 0.  The
+ *      other targets of the batch keep the bits they have in a batch without it.
+ *   8. A target's outputs are the same bits alone, in any batch and through either entry point; reduction orders still depend on
+ *      (K, nc, P) only.  omega[i_e] is one more 8-byte read per staged row, made where the row's weight is made.
+ * Without the setting (the default) every call launches the kernel instances it launched before the setting existed and returns
+ * the same bits.  The abc_weighted_* entries, the single-target rankings and the generation and sharded drivers are not affected.
+ * R's abc has no such argument: it is this library's addition for tables that are not prior draws.
+ * w (host memory) / w_dev (device memory): N doubles, copied, so the caller's buffer may be freed after the call.  One small kernel
+ * counts the negative or non-finite and the positive entries and takes sum w and sum w^2, which the host reads here (the call
+ * synchronises): a negative or non-finite weight, none positive, or weights so large that sum w or sum w^2 is not finite in fp64
+ * (any positive scale will do short of that: rescale them) is ABC_ERR_INVALID and the setting stays as it was.  w = NULL or
+ * N = 0 clears the setting. */
+int abc_ctx_set_row_weights(abc_ctx* ctx, const double* w, size_t N);
+int abc_ctx_set_row_weights_dev(abc_ctx* ctx, const double* w_dev, size_t N);
+/* The setting: *N its count (0: off), *positive the number of positive weights, *ess = (sum w)^2 / sum w^2 of the whole table.
+ * Any pointer may be NULL. */
+int abc_row_weights_info(abc_ctx* ctx, size_t* N, size_t* positive, double* ess);
 
 /* ---- tolerance path: one batched ranking, the rejection estimate and the local-linear fit at several tolerances ------------
  * What cv4abc does with tols = c(.005, .01, .05): ONE ranking at K_max = Ks[T-1] (idx and dist, K_max x B, are the bits of
