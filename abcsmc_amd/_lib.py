@@ -210,6 +210,7 @@ SIGNATURES = {
     "abc_generation_repeats": (_i, [_vp, _vp, _vp, _i]),
     "abc_ctx_set_alias_mode": (_i, [_vp, _i]),
     "abc_alias_stats": (_i, [_vp, _vp, _vp, _i]),
+    "abc_select_stats": (_i, [_vp, _vp, _vp, _i]),
     "abc_alias_table": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "abc_ctx_synchronize": (_i, [_vp]),
     "abc_version": (_i, []),
@@ -369,6 +370,13 @@ class Context:
         component count has cost (abc_generation_repeats)"""
         a, b = C.c_uint64(0), C.c_uint64(0)
         self.check(lib().abc_generation_repeats(self._h, C.byref(a), C.byref(b), int(reset)))
+        return a.value, b.value
+
+    def select_stats(self, reset=False):
+        """(bin selections, bin give-ups) since the context was created / the last reset: selections queued on the sampled-range
+        bin path, and those of them the selection's own check repeated with the radix select (abc_select_stats)"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self.check(lib().abc_select_stats(self._h, C.byref(a), C.byref(b), int(reset)))
         return a.value, b.value
 
     def generation_giveups(self):

@@ -110,6 +110,7 @@ struct abc_ctx {
     int* sel_fail_dev;       // device: the sampled-range bin selection gave up (select.hip); read by abc_select_check
     bool sel_bins_ran;       // the last launch_select_smallest took the bin path and has not been checked yet
     bool sel_force_radix;    // set by a caller that repeats its work after a failed bin selection
+    unsigned long long sel_bin_selections, sel_bin_giveups;   // bin selections queued / found failed by launch_select_smallest's own check (abc_select_stats)
     unsigned long long targets_fallbacks;   // targets of abc_rank_targets_dev that took the exact single-target path
     // parameter transforms of the local-linear adjustment (abc_ctx_set_param_transf): one device allocation [lo | hi | kind] of tf_P
     // entries each, NULL / 0 while nothing is set; the forward passes' out-of-domain counter (device, abc_param_transf_outside)

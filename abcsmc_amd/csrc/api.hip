@@ -186,6 +186,14 @@ extern "C" int abc_alias_stats(abc_ctx* ctx, uint64_t* device_builds, uint64_t* 
     return ABC_OK;
 }
 
+extern "C" int abc_select_stats(abc_ctx* ctx, uint64_t* bin_selections, uint64_t* bin_giveups, int reset) {
+    if (!ctx) return ABC_ERR_INVALID;
+    if (bin_selections) *bin_selections = (uint64_t)ctx->sel_bin_selections;
+    if (bin_giveups) *bin_giveups = (uint64_t)ctx->sel_bin_giveups;
+    if (reset) { ctx->sel_bin_selections = 0; ctx->sel_bin_giveups = 0; }
+    return ABC_OK;
+}
+
 extern "C" int abc_perturb_giveups(abc_ctx* ctx, uint64_t* count, int reset) {
     if (!ctx || !count) return ABC_ERR_INVALID;
     if (hipSetDevice(ctx->device) != hipSuccess) ABC_FAIL(ctx, ABC_ERR_HIP, "hipSetDevice failed");
@@ -668,6 +676,16 @@ static size_t default_A(size_t M, size_t P, int max_comp) {
         if ((M) == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: the statistics record needs at least one metric (M == 0)", fn); \
     } while (0)
 
+// the chunk sort behind up to 2^18 winners carries an element's position in the top 16 bits of its index word (select.hip:
+// k_sort_chunks): row indices idx_base .. idx_base + n - 1 must stay below 2^48, whichever selection path answers
+#define CHECK_IDX48(ctx, fn, idx_base, n)                                                                               \
+    do {                                                                                                                \
+        const uint64_t lim48_ = (uint64_t)1 << 48;                                                                      \
+        if ((uint64_t)(idx_base) > lim48_ || (uint64_t)(n) > lim48_ - (uint64_t)(idx_base))                             \
+            ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: idx_base %llu + n %zu exceeds 2^48", fn,                            \
+                     (unsigned long long)(idx_base), (size_t)(n));                                                      \
+    } while (0)
+
 extern "C" size_t abc_stats_len(size_t M, size_t P) { return stats_layout(M, P).len; }
 extern "C" size_t abc_model_len(size_t M, size_t P, size_t A) { return model_layout(M, P, A).len; }
 
@@ -732,6 +750,7 @@ extern "C" int abc_project_distance_dev(abc_ctx* ctx, const double* X, size_t n,
 extern "C" int abc_select_smallest_dev(abc_ctx* ctx, const double* dist, size_t n, size_t K, uint64_t idx_base,
                                        uint64_t* idx, double* dist_out) {
     CHECK_CTX(ctx);
+    CHECK_IDX48(ctx, "abc_select_smallest_dev", idx_base, n);
     ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(n, 1, 1, 1, K, 0, 0)));
     return launch_select_smallest(ctx, dist, n, K, idx_base, idx, dist_out);
 }
@@ -757,6 +776,7 @@ extern "C" int abc_select_count_dev(abc_ctx* ctx, const double* dist, size_t n, 
 extern "C" int abc_select_compact_dev(abc_ctx* ctx, const double* dist, size_t n, const int64_t* state, uint64_t n_less,
                                       uint64_t ties_take, uint64_t idx_base, uint64_t* idx_out, double* dist_out) {
     CHECK_CTX(ctx);
+    CHECK_IDX48(ctx, "abc_select_compact_dev", idx_base, n);
     ABC_TRY(abc_ws_reserve(ctx, abc_ws_need(n, 1, 1, 1, n_less + ties_take, 0, 0)));
     return launch_select_compact(ctx, dist, n, (const long long*)state, n_less, ties_take, idx_base, idx_out, dist_out);
 }

@@ -926,11 +926,13 @@ int launch_select_smallest(abc_ctx* ctx, const double* dist, size_t n, size_t K,
     ctx->sel_bins_ran = bins;
     if (!bins) return select_by_radix(ctx, dist, n, K, idx_base, idx, dist_out);
     const size_t mark = ctx->ws_off;
+    ctx->sel_bin_selections++;
     ABC_TRY(select_by_bins(ctx, dist, n, K, idx_base, idx, dist_out));
-    if (defer_check) return ABC_OK;
+    if (defer_check) return ABC_OK;          // (a deferred give-up is the caller's repeat: abc_generation_repeats)
     int failed = 0;
     ABC_TRY(abc_select_check(ctx, &failed));
     if (!failed) return ABC_OK;
+    ctx->sel_bin_giveups++;
     ctx->ws_off = mark;
     return select_by_radix(ctx, dist, n, K, idx_base, idx, dist_out);
 }

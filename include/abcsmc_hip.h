@@ -186,6 +186,14 @@ int  abc_generation_giveups(const abc_ctx* ctx, uint64_t* count);
  * degenerate selection has to be redone by radix select, the generation starts over (*generation_repeats).  Both 0 on clean
  * responses; neither changes a result.  No synchronisation. */
 int  abc_generation_repeats(abc_ctx* ctx, uint64_t* ranking_repeats, uint64_t* generation_repeats, int reset);
+/* Which path the selection of the K smallest distances took since the context was created (or the last reset).  *bin_selections:
+ * selections queued on the sampled-range bin path, by any caller (abc_select_smallest_dev, a generation, a rank of the sharded
+ * driver, the exact single-target path of abc_rank_targets_dev); every other selection is a radix select.  *bin_giveups: of those,
+ * the ones whose give-up flag (a bin of more than 1024 keys at or below the K-th key's bin, or fewer than K keys at or below the
+ * sampled bound) was read by the selection's own check, which then repeated it with the radix select: abc_select_smallest_dev
+ * and the single-target path.  The generation drivers read the flag at a later synchronisation of their own and report their
+ * repeat through abc_generation_repeats, not here.  Host-side counters; neither changes a result.  No synchronisation. */
+int  abc_select_stats(abc_ctx* ctx, uint64_t* bin_selections, uint64_t* bin_giveups, int reset);
 /* Optional per-stage timing: HIP events recorded on the context's stream around each stage
  * (and around the k_gram / k_kde kernels alone).  abc_timing_read synchronises, then returns the
  * number of stages; names[i] is a static string, ms[i] the accumulated device time, host_ms[i]
@@ -333,21 +341,25 @@ int abc_simple_model_dev(abc_ctx* ctx, const double* stats, const double* obs, s
 /* per-row distance to the observed scores (AbcUtil.cpp:453-455, or :419 when simple != 0) */
 int abc_project_distance_dev(abc_ctx* ctx, const double* X, size_t n, size_t ldx, size_t M, size_t P,
                              size_t A, const double* model, int simple, double* dist);
-/* K smallest of dist[n] in ascending (dist, index) order: idx[K] (local row + idx_base), dist[K] */
+/* K smallest of dist[n] in ascending (dist, index) order: idx[K] (local row + idx_base), dist[K] (dist_out may be NULL).
+ * Limit: idx_base + n <= 2^48 (ABC_ERR_UNSUPPORTED beyond: the sort of up to 2^18 winners keeps 48 bits of an index). */
 int abc_select_smallest_dev(abc_ctx* ctx, const double* dist, size_t n, size_t K, uint64_t idx_base,
                             uint64_t* idx, double* dist_out);
 /* Distributed exact selection: every shard histograms its keys for pass p = 0..5 (digits of the
  * IEEE bit pattern, high to low), the caller all-reduces hist (2048 x int32) over the shards, then every shard
  * picks the same digit; after pass 5 `state` holds the global K-th smallest key.  count -> {#below, #equal} per
  * shard (the caller decides how many ties each shard takes, lowest global rows first); compact -> that shard's
- * winners (dist, row + idx_base) in row order.  state: 8 x int64, hist: 2048 x int32 (zeroed by begin / pick). */
+ * winners (dist, row + idx_base) in row order.  state: 8 x int64, hist: 2048 x int32 (zeroed by begin / pick).
+ * Limit of compact: idx_base + n <= 2^48 (ABC_ERR_UNSUPPORTED beyond), as what sorts its output keeps 48 bits of an index. */
 int abc_select_begin_dev(abc_ctx* ctx, uint64_t K, int64_t* state, int32_t* hist);
 int abc_select_hist_dev(abc_ctx* ctx, const double* dist, size_t n, const int64_t* state, int pass, int32_t* hist);
 int abc_select_pick_dev(abc_ctx* ctx, int64_t* state, int pass, int32_t* hist, uint64_t K);
 int abc_select_count_dev(abc_ctx* ctx, const double* dist, size_t n, const int64_t* state, int64_t* counts);
 int abc_select_compact_dev(abc_ctx* ctx, const double* dist, size_t n, const int64_t* state, uint64_t n_less,
                            uint64_t ties_take, uint64_t idx_base, uint64_t* idx_out, double* dist_out);
-/* sort n (key, idx) pairs by (key, idx); used to merge per-shard winners */
+/* stable sort of n (key, idx) pairs by key alone: equal keys keep their input order, whatever their idx; used to merge per-shard
+ * winners.  Limit: every idx below 2^48 -- up to 2^18 pairs the sort keeps 48 bits of idx and returns the rest as zeros, without
+ * an error (the values are on the device, the host cannot see them). */
 int abc_sort_pairs_dev(abc_ctx* ctx, double* key, uint64_t* idx, size_t n);
 /* merge n_runs runs of run_len pairs, each sorted by (key, idx), laid out back to back, into one sorted
  * sequence (ties: lower run first = a stable sort of the concatenation).  Out-of-place. */

@@ -255,9 +255,14 @@ def test_generation_with_massive_distance_ties_repeats_with_the_radix_select(gpu
     dev = "cuda:0"
     gen = device.Generation(N, M, P, K, 0, Nn, 0.5, A, multivariate=False, device=dev)
     r = abcutil.rng(99)
+    sel0, rep0 = gen.ctx.select_stats(), gen.ctx.generation_repeats()
     gen.run(device.colmajor(X, dev), device.colmajor(Y, dev), device.colmajor(obs, dev),
             device.priors_to_device(_lib.make_priors(spec), dev), r)
     torch.cuda.synchronize()
+    # the bin path did answer first (a selection counted), its give-up was the generation's to find (none counted by the selection
+    # itself) and cost exactly one repeat of the generation
+    sel1, rep1 = gen.ctx.select_stats(), gen.ctx.generation_repeats()
+    assert sel1[0] - sel0[0] >= 1 and sel1[1] == sel0[1] and rep1[1] - rep0[1] == 1
     o = oracle.rng(99)
     ref = oracle.generation(X, Y, obs, oracle.make_priors(spec), K, Nn, o, None, None, None, train_frac=0.5, max_comp=A,
                             multivariate=False)
@@ -2127,17 +2132,16 @@ def test_generation_tiny(gpu_ctx, oracle):
     assert np.array_equal(gen.parent.cpu().numpy()[:Nn].astype(np.uint64), ref["parent"])
 
 
-def test_distributed_select_protocol_with_ties(gpu_ctx, oracle):
+def _distributed_select_replay(gpu_ctx, oracle, d, n_loc, W, Ks):
     """The sharded driver's exact selection (6 all-reduced radix histograms, tie hand-out by global row, padded
-    gather, stable merge sort) replayed in one process over 3 emulated shards, on tie-heavy keys."""
+    gather, stable merge sort) replayed in one process over W emulated shards of n_loc rows, for every K of Ks; checked against
+    the oracle's order -> {K: (per shard [#below, #equal], per shard ties taken)}"""
     import torch
     from abcsmc_amd import sharded
     be = sharded.HipBackend("cuda:0", gpu_ctx)
-    rng = np.random.default_rng(12)
-    n_loc, W = 5000, 3
-    d = np.round(np.abs(rng.normal(size=n_loc * W)) * 20) / 20.0          # ~80 distinct values: massive ties
     shards = [torch.from_numpy(d[q * n_loc:(q + 1) * n_loc].copy()).cuda() for q in range(W)]
-    for K in (1, 37, 4999, 5000, 7501, 14999):
+    seen = {}
+    for K in Ks:
         st = [be.zeros(8, torch.int64) for _ in range(W)]
         hs = [be.zeros(2048, torch.int32) for _ in range(W)]
         for q in range(W):
@@ -2193,6 +2197,16 @@ def test_distributed_select_protocol_with_ties(gpu_ctx, oracle):
         assert np.array_equal(mi[:K].cpu().numpy().astype(np.uint64), ref), K
         assert np.array_equal(md[:K].cpu().numpy(), d[ref.astype(np.int64)])
         assert bool(torch.all(mi[K:] == (1 << 62))) and bool(torch.all(torch.isinf(md[K:])))
+        seen[K] = (cnt, take)
+    return seen
+
+
+def test_distributed_select_protocol_with_ties(gpu_ctx, oracle):
+    """the replay over 3 emulated shards, on tie-heavy keys"""
+    rng = np.random.default_rng(12)
+    n_loc, W = 5000, 3
+    d = np.round(np.abs(rng.normal(size=n_loc * W)) * 20) / 20.0          # ~80 distinct values: massive ties
+    _distributed_select_replay(gpu_ctx, oracle, d, n_loc, W, (1, 37, 4999, 5000, 7501, 14999))
 
 
 # ---------------------------------------------------------------------------------------------------
