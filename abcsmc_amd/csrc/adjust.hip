@@ -21,9 +21,7 @@
 // Under the heteroscedastic variance correction (abc_ctx_set_adjust_hcorr) a second fit follows every first one:
 //   k_adj_moments2  grid (row chunks, targets): the chunk's rows staged raw, the parameter columns turned into z = 2 log|v - alpha|
 //                   (v with aj_adjusted's bits) minus the first row's z, the scores shifted as in the first pass; the same ascending
-//                   fma chains for the (1 + nc) x P block [1 x'] w z' only.  The tolerance path runs, per tolerance, the whole
-//                   chain of the adjustment with K = K_t (k_adj_moments, k_adj_solve, k_adj_moments2, k_adj_solve<true> in that
-//                   call's chunks), so that a slot of hcoef has that call's bits
+//                   fma chains for the (1 + nc) x P block [1 x'] w z' only
 //   k_adj_solve<true>  the first fit's C from the first pass's blocks (the same sums, so the same pivots), the new right-hand sides;
 //                   hcoef, the skip rule and its counter
 // and k_adj_apply<true> rescales the residual of every made value (aj_hcorr, as sm_value<.., true> of segment_dev.h).  All three are
@@ -39,6 +37,12 @@
 // (k_adj_moments, k_adj_moments_path, k_adj_moments2, k_adj_press, k_adj_apply) and k_path_mean have RW instances that read omega
 // where the weight is made (aj_weight_rw), and k_adj_solve / k_adj_pick have RW instances for the all-zero rule (a slot whose
 // weights sum to 0 is not swept).  Calls without the setting launch the RW = false instances, which never see omega.
+// On the host one function queues a fit, aj_fit_chain: k_adj_moments, k_adj_solve, the ridge kernels, k_adj_moments2 and
+// k_adj_solve<true> for a batch of targets at one K, in the chunks of aj_plan(K, ..).  The adjust call runs it once per batch.  The
+// tolerance path, under the variance correction or ridge, calls it once per (batch, tolerance) with K = K_t behind its own
+// solve, so slot (b, t) of hcoef, pick and press, and of coef under ridge, has the bits of the adjust call with K = K_t because
+// it is that call's code with that call's arguments.  aj_call_setup is the set-up of both entries, and every arena block has one
+// byte count (aj_*_bytes) that the allocation and abc_adjust_need / abc_path_need share.
 // Chunk sizes depend on K only, tile sizes on (nc, P) only, and the gather paths copy the same bits: a target's outputs are the
 // same alone and in any batch.
 #include <math.h>
@@ -1037,14 +1041,11 @@ AjPlan aj_plan(size_t K, int nc, int P) {
     return p;
 }
 
-size_t aj_part_bytes(size_t K, size_t A, size_t P) {     // one target's moment blocks (bound over nc <= A)
-    const AjPlan p = aj_plan(K, 0, 0);
-    return p.nch * (1 + A) * (1 + A + P) * 8;
-}
-
-size_t aj_part2_bytes(size_t K, size_t A, size_t P) {    // ... and its second-stage blocks (the variance correction)
-    const AjPlan p = aj_plan(K, 0, 0);
-    return p.nch * (1 + A) * P * 8;
+// LDS bytes of k_adj_moments (TL = 1) and of k_adj_moments_path<TL> at tiles of TR rows: the first row, one weight column per
+// tolerance lane, the rows (<= 60 KiB at TL = 1, <= 64.5 KiB at TL = 4)
+size_t aj_moments_lds(int TR, int nc, int P, int TL) {
+    const int D = 1 + nc + P;
+    return (size_t)(((D + 1) & ~1) + TL * ((TR + 1) & ~1) + TR * aj_stride(nc, P)) * 8;
 }
 
 // k_adj_moments2's tile: the slot's coefficients in LDS up to AJ_APPLY_DBL doubles, the rows in what is left of AJ_TILE_DBL (the
@@ -1066,8 +1067,36 @@ AjPlan2 aj_plan2(const AjPlan& pl, int nc, int P) {
     return q;
 }
 
-size_t aj_batch(size_t K, size_t A, size_t P, size_t B) {
-    size_t bb = AJ_PART_BYTES / aj_part_bytes(K, A, P);
+size_t aj_solve_lds(int nc) {
+    const int NB = nc + AJ_RHS, ncp = (nc + 1) & ~1;
+    return (size_t)(((nc * nc + 1) & ~1) + nc * NB + 5 * ncp + NB + 2 * AJ_RHS + 2) * 8;
+}
+
+size_t aj_ridge_tiles(size_t K, int nc, int P) {
+    const AjPlanR pr = aj_plan_r(nc, P);
+    return (K + pr.TR - 1) / pr.TR;
+}
+
+// The arena blocks of a regressing call, each with one byte count: aj_call_setup allocates with the fit's nc, aj_need counts with
+// nc = A, its bound.
+size_t aj_dist_bytes(size_t B, size_t K) { return B * K * 8; }                                        // (the caller's may be NULL)
+size_t aj_coef_bytes(size_t slots, size_t A, size_t P) { return slots * (A + 1) * P * 8 + 8; }       // (the caller's may be NULL)
+size_t aj_table_bytes(size_t N, size_t nc, size_t P) { return N * (nc + P) * 8; }                     // the row-major table
+size_t aj_part_bytes(size_t K, size_t nc, size_t P) {    // one target's moment blocks
+    return aj_plan(K, 0, 0).nch * (1 + nc) * (1 + nc + P) * 8;
+}
+size_t aj_part2_bytes(size_t K, size_t nc, size_t P) {   // ... its second-stage blocks (the variance correction)
+    return aj_plan(K, 0, 0).nch * (1 + nc) * P * 8;
+}
+size_t aj_rfit_bytes(size_t nc, size_t P, size_t L) { return L * aj_rfit_dbl((int)nc, (int)P) * 8; }  // ... its penalised fits
+size_t aj_rpp_bytes(size_t K, size_t nc, size_t P, size_t L) {                                        // ... and their PRESS partials
+    return L * aj_ridge_tiles(K, (int)nc, (int)P) * P * 8;
+}
+
+// targets per batch: the moment blocks of a batch, T sets of them on a tolerance path, within AJ_PART_BYTES (from A, an upper
+// bound of nc, so that the arena bound does not depend on the fit)
+size_t aj_batch(size_t K, size_t A, size_t P, size_t B, size_t T) {
+    size_t bb = AJ_PART_BYTES / (T * aj_part_bytes(K, A, P));
     if (bb < 1) bb = 1;
     if (bb > AJ_MAX_GRID_Y) bb = AJ_MAX_GRID_Y;
     return bb < B ? bb : B;
@@ -1084,41 +1113,163 @@ bool aj_use_table(size_t N, size_t A, size_t P, size_t B, size_t K) {
     return 4 * B * K >= N;
 }
 
-size_t aj_solve_lds(int nc) {
-    const int NB = nc + AJ_RHS, ncp = (nc + 1) & ~1;
-    return (size_t)(((nc * nc + 1) & ~1) + nc * NB + 5 * ncp + NB + 2 * AJ_RHS + 2) * 8;
+// the bound of what aj_call_setup takes from the arena, block for block (T = 1: the adjust call; 256 per block for the alignment)
+size_t aj_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T, bool hcorr, size_t ridge) {
+    const size_t bb = aj_batch(K, A, P, B, T);
+    size_t b = aj_dist_bytes(B, K) + aj_coef_bytes(B * T, A, P);
+    if (aj_use_table(N, A, P, B, K)) b += aj_table_bytes(N, A, P);
+    b += bb * T * aj_part_bytes(K, A, P);
+    if (hcorr) b += bb * aj_part2_bytes(K, A, P) + 256;
+    if (ridge) b += bb * (aj_rfit_bytes(A, P, ridge) + aj_rpp_bytes(K, A, P, ridge)) + 2 * 256;
+    return b + 16 * 256;
 }
 
-// the ridge setting for a launch: the penalties and where the record goes (NULL pick: off)
-size_t aj_ridge_tiles(size_t K, int nc, int P) {
-    const AjPlanR pr = aj_plan_r(nc, P);
-    return (K + pr.TR - 1) / pr.TR;
+// What does not change within a regressing call: everything the fit chain takes besides the tolerance, the targets and the slot
+struct AjCall {
+    AjSrc src;
+    const uint64_t* idx;
+    const double* d;                        // the retained rows' distances, laid out as idx
+    int nc, P, A, kernel;
+    const double* O;                        // the targets' scores, O[b KCO + k]
+    int KCO;
+    const double* om;                       // row importance weights (NULL: none, and the instances below are the RW = false ones,
+                                            // which ran before the setting existed)
+    decltype(&k_adj_moments<false>) moments;
+    decltype(&k_adj_moments2<false>) moments2;
+    decltype(&k_adj_solve<false, false>) solve, solve_hc;
+    decltype(&k_adj_press<false>) press;
+    decltype(&k_adj_pick<false>) pick;
+    size_t lds_s;                           // LDS bytes of k_adj_solve and k_adj_rsolve
+    double* coef;                           // the call's coef, slots x (A + 1) x P
+    double* part;                           // moment blocks of one batch
+    double *hcoef, *part2;                  // the variance correction: its record (NULL: off), second-stage blocks of one batch
+    unsigned long long* skipped;
+    AbcRg rg;                               // ridge: the penalties and the record (L == 0: off)
+    AjLam lam;
+    double *rfit, *rpp;                     // ... the penalised fits and PRESS partials of one batch
+};
+
+// The set-up of a regressing call, after its ranking: nc from the model header (the call's one stream synchronisation), coef, the
+// rows' source with the table when aj_use_table says so, the kernel instances, and the blocks of one batch of bb targets (T sets
+// of moment blocks on a path) with those of the settings that are on; keep (if given) is filled for the products.
+int aj_call_setup(abc_ctx* ctx, const char* fn, const abc_tg_scores& sc, const double* Y, size_t ldy, size_t N, size_t P,
+                  const double* model, size_t A, size_t B, size_t K, size_t T, size_t bb, int kernel, const uint64_t* idx, const double* d,
+                  double* coef, const AbcTf& tf, const AbcHc* hc, const AbcRg* rg, const double* om, abc_adj_keep* keep, AjCall* c) {
+    double hdr = 0.0;
+    ABC_HIP(ctx, hipMemcpyAsync(&hdr, model, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int nc = hdr < 0.0 ? 0 : (hdr > (double)A ? (int)A : (int)hdr);      // the ranking's tg_ncomp
+    const int Pi = (int)P;
+    *c = AjCall{};
+    c->idx = idx;
+    c->d = d;
+    c->nc = nc;
+    c->P = Pi;
+    c->A = (int)A;
+    c->kernel = kernel;
+    c->O = sc.O;
+    c->KCO = sc.KCO;
+    c->om = om;
+    c->coef = coef ? coef : (double*)abc_ws_alloc(ctx, aj_coef_bytes(B * T, A, P));
+    if (!c->coef) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+
+    c->src = AjSrc{nullptr, (size_t)nc + P, sc.S, sc.sld, Y, ldy};
+    if (aj_use_table(N, A, P, B, K) && c->src.W > 0) {
+        double* Tb = (double*)abc_ws_alloc(ctx, aj_table_bytes(N, (size_t)nc, P));
+        if (!Tb) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+        size_t blocks = (N + 63) / 64;
+        if (blocks > 8192) blocks = 8192;
+        hipLaunchKernelGGL(k_adj_table, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sc.S, sc.sld, Y, ldy, N, nc, Pi, Tb);
+        ABC_HIP(ctx, hipGetLastError());
+        c->src.T = Tb;
+    }
+
+    // under row importance weights every kernel that makes or sums weights is its RW instance
+    c->moments = om ? k_adj_moments<true> : k_adj_moments<false>;
+    c->moments2 = om ? k_adj_moments2<true> : k_adj_moments2<false>;
+    c->solve = om ? k_adj_solve<false, true> : k_adj_solve<false, false>;
+    c->solve_hc = om ? k_adj_solve<true, true> : k_adj_solve<true, false>;
+    c->press = om ? k_adj_press<true> : k_adj_press<false>;
+    c->pick = om ? k_adj_pick<true> : k_adj_pick<false>;
+    c->lds_s = aj_solve_lds(nc);
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)c->solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_s));
+    c->part = (double*)abc_ws_alloc(ctx, bb * T * aj_part_bytes(K, (size_t)nc, P));
+    if (!c->part) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    if (hc && Pi > 0) {                                                // the variance correction: a second fit after every first
+        c->hcoef = hc->hcoef;
+        c->skipped = hc->skipped;
+        c->part2 = (double*)abc_ws_alloc(ctx, bb * aj_part2_bytes(K, (size_t)nc, P));
+        if (!c->part2) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)c->solve_hc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_s));
+    }
+    if (rg && rg->L > 0 && Pi > 0) {                                   // ridge: the penalised fits replace every first fit's coef
+        c->rg = *rg;
+        for (int l = 0; l < rg->L; l++) c->lam.v[l] = rg->lambda[l];
+        c->rfit = (double*)abc_ws_alloc(ctx, bb * aj_rfit_bytes((size_t)nc, P, (size_t)rg->L));
+        c->rpp = (double*)abc_ws_alloc(ctx, bb * aj_rpp_bytes(K, (size_t)nc, P, (size_t)rg->L));
+        if (!c->rfit || !c->rpp) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_rsolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_s));
+        ABC_HIP(ctx, hipFuncSetAttribute((const void*)c->press, hipFuncAttributeMaxDynamicSharedMemorySize, (int)aj_plan_r(nc, Pi).lds));
+    }
+    if (keep) *keep = abc_adj_keep{c->src, sc.O, sc.KCO, nc, c->coef, d, tf, c->hcoef};
+    return ABC_OK;
 }
 
-size_t aj_ridge_bytes(size_t K, size_t A, size_t P, size_t L) {      // one target's fits and PRESS partials (bound over nc <= A)
-    return L * (aj_rfit_dbl((int)A, (int)P) + aj_ridge_tiles(K, (int)A, (int)P) * P) * 8;
+// The fit of abc_rank_targets_adjust_dev at one tolerance for the targets b0 .. b0 + nb - 1: the first K of a target's ld retained
+// rows, in the chunks of pl = aj_plan(K, ..).  k_adj_moments and k_adj_solve give coef (and rank / status where given) at slot
+// b; under ridge k_adj_rsolve, k_adj_press and k_adj_pick replace that coef before anything reads it; under the variance
+// correction k_adj_moments2 and k_adj_solve<true> fit its residuals.  The settings' records (pick, press, hcoef) go to slot
+// b sstride + soff: (1, 0) for the adjust call, (T, t) for tolerance t of a path, whose coef is not laid out as the chain's;
+// for it the picked fit is also copied to that slot of slot_coef, right behind the pick (NULL: no copy).
+// Both entries fit through this one function, so a path's records at (b, t) have the bits of the adjust call with K = K_t.
+int aj_fit_chain(abc_ctx* ctx, const AjCall& c, const AjPlan& pl, size_t ld, size_t K, size_t b0, size_t nb, size_t sstride,
+                 size_t soff, double* coef, int32_t* rank, int32_t* status, double* slot_coef) {
+    AjKs ks = {};
+    ks.K[0] = K;
+    const AjHcSolve hs0 = {nullptr, nullptr, nullptr, nullptr, 1, 0};
+    hipLaunchKernelGGL(c.moments, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), aj_moments_lds(pl.TR, c.nc, c.P, 1), ctx->stream,
+                       c.src, c.idx, c.d, ld, K, c.nc, c.P, c.kernel, pl.CH, pl.TR, b0, pl.nch, c.part, c.om);
+    hipLaunchKernelGGL(c.solve, dim3((unsigned)nb), dim3(256), c.lds_s, ctx->stream, c.src, c.idx, c.d, ld, ks, 1, pl.CH, c.nc, c.P,
+                       c.A, c.kernel, c.O, c.KCO, (const double*)c.part, (int)pl.nch, b0, coef, rank, status, hs0);
+    ABC_HIP(ctx, hipGetLastError());
+    if (c.rg.L > 0) {
+        const AjPlanR pr = aj_plan_r(c.nc, c.P);
+        const size_t tiles = aj_ridge_tiles(K, c.nc, c.P);
+        const AjRgOut ro = {c.rg.pick, c.rg.press, c.rg.unscored, sstride, soff};
+        hipLaunchKernelGGL(k_adj_rsolve, dim3((unsigned)nb, (unsigned)c.rg.L), dim3(256), c.lds_s, ctx->stream, c.src, c.idx, ld, K,
+                           pl.CH, c.nc, c.P, c.O, c.KCO, (const double*)c.part, (int)pl.nch, b0, c.lam, c.rfit);
+        hipLaunchKernelGGL(c.press, dim3((unsigned)tiles, (unsigned)nb, (unsigned)c.rg.L), dim3(256), pr.lds, ctx->stream, c.src,
+                           c.idx, c.d, ld, K, c.nc, c.P, c.kernel, c.O, c.KCO, (const double*)c.rfit, b0, c.rpp, c.om);
+        hipLaunchKernelGGL(c.pick, dim3((unsigned)nb), dim3(256), 0, ctx->stream, c.nc, c.P, c.A, c.rg.L, (int)tiles,
+                           (const double*)c.rfit, (const double*)c.rpp, b0, coef, ro);
+        ABC_HIP(ctx, hipGetLastError());
+        if (slot_coef) {
+            const size_t cn = (size_t)(c.A + 1) * c.P, cw = cn * 8;
+            ABC_HIP(ctx, hipMemcpy2DAsync(slot_coef + (b0 * sstride + soff) * cn, sstride * cw, coef + b0 * cn, cw, cw, nb,
+                                          hipMemcpyDeviceToDevice, ctx->stream));
+        }
+    }
+    if (!c.hcoef) return ABC_OK;
+    const AjPlan2 p2 = aj_plan2(pl, c.nc, c.P);
+    const AjHcSolve hs1 = {c.part2, coef, c.hcoef, c.skipped, sstride, soff};
+    hipLaunchKernelGGL(c.moments2, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, c.src, c.idx, c.d, ld, K,
+                       c.nc, c.P, c.A, c.kernel, pl.CH, p2.TR, b0, pl.nch, c.O, c.KCO, (const double*)coef, 1, 0, p2.cf_lds, c.part2,
+                       c.om);
+    hipLaunchKernelGGL(c.solve_hc, dim3((unsigned)nb), dim3(256), c.lds_s, ctx->stream, c.src, c.idx, c.d, ld, ks, 1, pl.CH, c.nc,
+                       c.P, c.A, c.kernel, c.O, c.KCO, (const double*)c.part, (int)pl.nch, b0, (double*)nullptr, (int32_t*)nullptr,
+                       (int32_t*)nullptr, hs1);
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
 }
 
-// the penalised fits, their PRESS and the pick for the targets b0 .. b0 + nb - 1 from the moment blocks k_adj_moments left in
-// `part` (pl: that launch's plan); coef receives the picked fit at slot b (stride 1)
-int aj_ridge(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, const double* d, size_t ld, size_t K, int nc, int P, int A,
-             int kernel, const abc_tg_scores& sc, const double* part, const AjPlan& pl, size_t b0, size_t nb, const AbcRg& rg,
-             double* rfit, double* pp, double* coef, size_t rstride, size_t roff, const double* om) {
-    AjLam lam = {};
-    for (int l = 0; l < rg.L; l++) lam.v[l] = rg.lambda[l];
-    const AjPlanR pr = aj_plan_r(nc, P);
-    const size_t tiles = (K + pr.TR - 1) / pr.TR, lds_s = aj_solve_lds(nc);
-    const AjRgOut ro = {rg.pick, rg.press, rg.unscored, rstride, roff};
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_adj_rsolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-    const auto press = om ? k_adj_press<true> : k_adj_press<false>;
-    const auto pick = om ? k_adj_pick<true> : k_adj_pick<false>;
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)press, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pr.lds));
-    hipLaunchKernelGGL(k_adj_rsolve, dim3((unsigned)nb, (unsigned)rg.L), dim3(256), lds_s, ctx->stream, src, idx, ld, K, pl.CH, nc, P,
-                       sc.O, sc.KCO, part, (int)pl.nch, b0, lam, rfit);
-    hipLaunchKernelGGL(press, dim3((unsigned)tiles, (unsigned)nb, (unsigned)rg.L), dim3(256), pr.lds, ctx->stream, src, idx, d, ld,
-                       K, nc, P, kernel, sc.O, sc.KCO, (const double*)rfit, b0, pp, om);
-    hipLaunchKernelGGL(pick, dim3((unsigned)nb), dim3(256), 0, ctx->stream, nc, P, A, rg.L, (int)tiles, (const double*)rfit,
-                       (const double*)pp, b0, coef, ro);
+template <int TL>
+int aj_launch_moments_path(abc_ctx* ctx, const AjCall& c, size_t ld, const AjKs& ks, int T, int t0, const AjPlan& pl, size_t b0,
+                           size_t nb) {
+    const size_t lds = aj_moments_lds(pl.TR, c.nc, c.P, TL);
+    const auto mp = c.om ? k_adj_moments_path<TL, true> : k_adj_moments_path<TL, false>;
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(mp, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds, ctx->stream, c.src, c.idx, c.d, ld, ks, T, t0, c.nc,
+                       c.P, c.kernel, pl.CH, pl.TR, b0, pl.nch, c.part, c.om);
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
 }
@@ -1126,14 +1277,7 @@ int aj_ridge(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, const double* 
 }  // namespace
 
 size_t abc_adjust_need(size_t N, size_t A, size_t P, size_t B, size_t K, bool hcorr, size_t ridge) {
-    size_t b = 0;
-    b += B * K * 8;                                          // distances (the caller's may be NULL)
-    b += B * (A + 1) * P * 8 + 2 * B * 4;                    // coefficients, rank, status
-    if (aj_use_table(N, A, P, B, K)) b += N * (A + P) * 8;   // the row-major table
-    b += aj_batch(K, A, P, B) * aj_part_bytes(K, A, P);      // moment blocks of one batch
-    if (hcorr) b += aj_batch(K, A, P, B) * aj_part2_bytes(K, A, P) + 256;
-    if (ridge) b += aj_batch(K, A, P, B) * aj_ridge_bytes(K, A, P, ridge) + 2 * 256;
-    return b + 16 * 256;
+    return aj_need(N, A, P, B, K, 1, hcorr, ridge) + 2 * B * 4;      // (rank, status: the caller's; kept in the bound)
 }
 
 int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
@@ -1141,101 +1285,21 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
                                bool any_excl, size_t K, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* out,
                                abc_adj_keep* keep, const AbcTf* tf, const AbcHc* hc, const AbcRg* rg, const double* om) {
     const AbcTf tfd = tf ? *tf : AbcTf{nullptr, nullptr, nullptr};
-    double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
+    double* d = dist ? dist : (double*)abc_ws_alloc(ctx, aj_dist_bytes(B, K));
     if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
     abc_tg_scores sc;
     ABC_TRY(launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, idx, d, nullptr, &sc));
     if (!keep && !out->theta && !out->weight && !out->coef && !out->rank && !out->status) return ABC_OK;
 
-    double hdr = 0.0;
-    ABC_HIP(ctx, hipMemcpyAsync(&hdr, model, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int nc = hdr < 0.0 ? 0 : (hdr > (double)A ? (int)A : (int)hdr);      // the ranking's tg_ncomp
-    const int Pi = (int)P;
-    double* coef = out->coef ? out->coef : (double*)abc_ws_alloc(ctx, B * (A + 1) * P * 8 + 8);
-    if (!coef) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
-
-    AjSrc src;
-    src.T = nullptr;
-    src.W = (size_t)nc + P;
-    src.S = sc.S;
-    src.sld = sc.sld;
-    src.Y = Y;
-    src.ldy = ldy;
-    if (aj_use_table(N, A, P, B, K) && src.W > 0) {
-        double* T = (double*)abc_ws_alloc(ctx, N * src.W * 8);
-        if (!T) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
-        size_t blocks = (N + 63) / 64;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(k_adj_table, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sc.S, sc.sld, Y, ldy, N, nc, Pi, T);
-        ABC_HIP(ctx, hipGetLastError());
-        src.T = T;
-    }
-
+    const size_t bb = aj_batch(K, A, P, B, 1);
+    AjCall c;
+    ABC_TRY(aj_call_setup(ctx, "rank_targets_adjust", sc, Y, ldy, N, P, model, A, B, K, 1, bb, kernel, idx, d, out->coef, tfd, hc, rg,
+                          om, keep, &c));
+    const int nc = c.nc, Pi = c.P;
     const AjPlan pl = aj_plan(K, nc, Pi);
-    const size_t bb = aj_batch(K, A, P, B);
-    const size_t blk = (size_t)(1 + nc) * (1 + nc + P);
-    double* part = (double*)abc_ws_alloc(ctx, bb * pl.nch * blk * 8);
-    if (!part) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
-    const int D = 1 + nc + Pi;
-    const size_t lds_m = (size_t)(((D + 1) & ~1) + ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, Pi)) * 8;
-    const size_t lds_s = aj_solve_lds(nc);
-    // under row importance weights (om) every kernel that makes or sums weights is its RW instance; without them, the instances
-    // that ran before the setting existed
-    const auto moments = om ? k_adj_moments<true> : k_adj_moments<false>;
-    const auto moments2 = om ? k_adj_moments2<true> : k_adj_moments2<false>;
-    const auto solve = om ? k_adj_solve<false, true> : k_adj_solve<false, false>;
-    const auto solve_hc = om ? k_adj_solve<true, true> : k_adj_solve<true, false>;
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-    double* hcoef = (hc && Pi > 0) ? hc->hcoef : nullptr;              // the variance correction: a second fit after every first
-    const AjPlan2 p2 = aj_plan2(pl, nc, Pi);
-    double* part2 = nullptr;
-    if (hcoef) {
-        part2 = (double*)abc_ws_alloc(ctx, bb * pl.nch * (size_t)(1 + nc) * P * 8);
-        if (!part2) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)solve_hc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-    }
-    const bool ridge = rg && rg->L > 0 && Pi > 0;                      // the penalised fits replace coef before anything reads it
-    double *rfit = nullptr, *rpp = nullptr;
-    if (ridge) {
-        rfit = (double*)abc_ws_alloc(ctx, bb * rg->L * aj_rfit_dbl(nc, Pi) * 8);
-        rpp = (double*)abc_ws_alloc(ctx, bb * rg->L * aj_ridge_tiles(K, nc, Pi) * P * 8);
-        if (!rfit || !rpp) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_adjust: workspace exhausted");
-    }
-    const AjHcSolve hs0 = {nullptr, nullptr, nullptr, nullptr, 1, 0};
-    const AjHcSolve hs1 = {part2, coef, hcoef, hcoef ? hc->skipped : nullptr, 1, 0};
-    AjKs ks = {};
-    ks.K[0] = K;
-    for (size_t b0 = 0; b0 < B; b0 += bb) {
-        const size_t nb = (B - b0 < bb) ? B - b0 : bb;
-        hipLaunchKernelGGL(moments, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds_m, ctx->stream, src, (const uint64_t*)idx,
-                           (const double*)d, K, K, nc, Pi, kernel, pl.CH, pl.TR, b0, pl.nch, part, om);
-        hipLaunchKernelGGL(solve, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
-                           (const double*)d, K, ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0,
-                           coef, out->rank, out->status, hs0);
-        ABC_HIP(ctx, hipGetLastError());
-        if (ridge)
-            ABC_TRY(aj_ridge(ctx, src, idx, d, K, K, nc, Pi, (int)A, kernel, sc, part, pl, b0, nb, *rg, rfit, rpp, coef, 1, 0, om));
-        if (!hcoef) continue;
-        hipLaunchKernelGGL(moments2, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src, (const uint64_t*)idx,
-                           (const double*)d, K, K, nc, Pi, (int)A, kernel, pl.CH, p2.TR, b0, pl.nch, sc.O, sc.KCO, (const double*)coef, 1,
-                           0, p2.cf_lds, part2, om);
-        hipLaunchKernelGGL(solve_hc, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
-                           (const double*)d, K, ks, 1, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part, (int)pl.nch, b0,
-                           (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, hs1);
-        ABC_HIP(ctx, hipGetLastError());
-    }
+    for (size_t b0 = 0; b0 < B; b0 += bb)
+        ABC_TRY(aj_fit_chain(ctx, c, pl, K, K, b0, (B - b0 < bb) ? B - b0 : bb, 1, 0, c.coef, out->rank, out->status, nullptr));
 
-    if (keep) {
-        keep->src = src;
-        keep->O = sc.O;
-        keep->KCO = sc.KCO;
-        keep->nc = nc;
-        keep->coef = coef;
-        keep->dist = d;
-        keep->tf = tfd;
-        keep->hcoef = hcoef;
-    }
     if (out->theta || out->weight) {
         const int Wv = nc + Pi;
         int TR = Wv > 0 ? AJ_APPLY_DBL / Wv : 64;
@@ -1243,55 +1307,25 @@ int launch_rank_targets_adjust(abc_ctx* ctx, const double* X, size_t ldx, const 
         if (TR < 1) TR = 1;
         const int beta_lds = (nc * Pi <= AJ_APPLY_DBL) ? 1 : 0;
         const size_t lds_a = (size_t)((((size_t)TR * Wv + 1) & ~(size_t)1) + (beta_lds ? (size_t)nc * Pi : 0)) * 8;     // <= 64 KiB
-        const auto apply = om ? (hcoef ? k_adj_apply<true, true> : k_adj_apply<false, true>)
-                              : (hcoef ? k_adj_apply<true, false> : k_adj_apply<false, false>);
+        const auto apply = om ? (c.hcoef ? k_adj_apply<true, true> : k_adj_apply<false, true>)
+                              : (c.hcoef ? k_adj_apply<true, false> : k_adj_apply<false, false>);
         ABC_HIP(ctx, hipFuncSetAttribute((const void*)apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
         const size_t tiles = (K + TR - 1) / TR;
         for (size_t b0 = 0; b0 < B; b0 += AJ_MAX_GRID_Y) {
             const size_t nb = (B - b0 < AJ_MAX_GRID_Y) ? B - b0 : AJ_MAX_GRID_Y;
-            hipLaunchKernelGGL(apply, dim3((unsigned)tiles, (unsigned)nb), dim3(256), lds_a, ctx->stream, src, (const uint64_t*)idx,
-                               (const double*)d, K, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)coef, TR, beta_lds, b0,
-                               tfd, out->theta, out->weight, (const double*)hcoef, om);
+            hipLaunchKernelGGL(apply, dim3((unsigned)tiles, (unsigned)nb), dim3(256), lds_a, ctx->stream, c.src, (const uint64_t*)idx,
+                               (const double*)d, K, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)c.coef, TR, beta_lds, b0,
+                               tfd, out->theta, out->weight, (const double*)c.hcoef, om);
             ABC_HIP(ctx, hipGetLastError());
         }
     }
     return ABC_OK;
 }
 
-namespace {
-
-size_t aj_path_batch(size_t K, size_t A, size_t P, size_t B, size_t T) {
-    size_t bb = AJ_PART_BYTES / (T * aj_part_bytes(K, A, P));
-    if (bb < 1) bb = 1;
-    if (bb > AJ_MAX_GRID_Y) bb = AJ_MAX_GRID_Y;
-    return bb < B ? bb : B;
-}
-
-template <int TL>
-int aj_launch_moments_path(abc_ctx* ctx, const AjSrc& src, const uint64_t* idx, const double* d, size_t ld, const AjKs& ks, int T,
-                           int t0, int nc, int P, int kernel, const AjPlan& pl, size_t b0, size_t nb, double* part, const double* om) {
-    const int D = 1 + nc + P;
-    const size_t lds = (size_t)(((D + 1) & ~1) + TL * ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, P)) * 8;       // <= 64.5 KiB
-    const auto mp = om ? k_adj_moments_path<TL, true> : k_adj_moments_path<TL, false>;
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(mp, dim3((unsigned)pl.nch, (unsigned)nb), dim3(256), lds, ctx->stream, src, idx, d, ld, ks, T,
-                       t0, nc, P, kernel, pl.CH, pl.TR, b0, pl.nch, part, om);
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
-}
-
-}  // namespace
-
 size_t abc_path_need(size_t N, size_t A, size_t P, size_t B, size_t K, size_t T, bool hcorr, size_t ridge) {
-    size_t b = 0;
-    b += B * K * 8;                                                  // distances (the caller's may be NULL)
-    b += B * T * (A + 1) * P * 8 + 8;                                // coefficients (the caller's may be NULL)
-    if (aj_use_table(N, A, P, B, K)) b += N * (A + P) * 8;           // the row-major table
-    b += aj_path_batch(K, A, P, B, T) * T * aj_part_bytes(K, A, P);  // moment blocks of one batch, every tolerance
-    if (hcorr) b += aj_path_batch(K, A, P, B, T) * aj_part2_bytes(K, A, P) + 256;
-    if (hcorr || ridge) b += B * (A + 1) * P * 8 + 2 * 256;          // the refit's coef
-    if (ridge) b += aj_path_batch(K, A, P, B, T) * aj_ridge_bytes(K, A, P, ridge) + 2 * 256;
-    return b + 16 * 256;
+    size_t b = aj_need(N, A, P, B, K, T, hcorr, ridge);
+    if (hcorr || ridge) b += aj_coef_bytes(B, A, P) + 2 * 256;       // the refits' coef
+    return b;
 }
 
 int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
@@ -1302,93 +1336,37 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
     AjKs ks = {};
     for (int t = 0; t < T; t++) ks.K[t] = path->Ks[t];
     const size_t K = ks.K[T - 1];                                    // K_max: the ranking's K and the rows' stride
-    double* d = dist ? dist : (double*)abc_ws_alloc(ctx, B * K * 8);
+    double* d = dist ? dist : (double*)abc_ws_alloc(ctx, aj_dist_bytes(B, K));
     if (!d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
     abc_tg_scores sc;
     ABC_TRY(launch_rank_targets(ctx, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, any_excl, K, idx, d, nullptr, &sc));
     const bool fit = path->coef || path->rank || path->status || keep;
     if (!fit && !path->post_mean && !path->h) return ABC_OK;
 
-    AjSrc src;                                                       // without the fit: the parameters only
-    src.T = nullptr;
-    src.W = P;
-    src.S = nullptr;
-    src.sld = 0;
-    src.Y = Y;
-    src.ldy = ldy;
-    const AjSrc raw = src;                                           // post_mean is of the raw Y under transforms too
-    int nc = 0;
-    double* hcoef = nullptr;
+    const AjSrc raw = {nullptr, P, nullptr, 0, Y, ldy};              // the parameters only: post_mean is of the raw Y under transforms too
+    AjCall c = {};
+    c.src = raw;                                                     // (all k_path_mean reads without the fit)
     if (fit) {
-        double hdr = 0.0;
-        ABC_HIP(ctx, hipMemcpyAsync(&hdr, model, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        nc = hdr < 0.0 ? 0 : (hdr > (double)A ? (int)A : (int)hdr);  // the ranking's tg_ncomp
-        double* coef = path->coef ? path->coef : (double*)abc_ws_alloc(ctx, B * T * (A + 1) * P * 8 + 8);
-        if (!coef) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
-        src.W = (size_t)nc + P;
-        src.S = sc.S;
-        src.sld = sc.sld;
-        if (Yt) {                                                    // the fit on the transformed scale (N x P, ld = N)
-            src.Y = Yt;
-            src.ldy = N;
-        }
-        if (aj_use_table(N, A, P, B, K) && src.W > 0) {              // the adjustment's rule with K = K_max
-            double* Tb = (double*)abc_ws_alloc(ctx, N * src.W * 8);
-            if (!Tb) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
-            size_t blocks = (N + 63) / 64;
-            if (blocks > 8192) blocks = 8192;
-            hipLaunchKernelGGL(k_adj_table, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, sc.S, sc.sld, src.Y, src.ldy, N, nc, Pi, Tb);
-            ABC_HIP(ctx, hipGetLastError());
-            src.T = Tb;
-        }
+        // the fit on the transformed scale reads Yt (N x P, ld = N); the table by the adjustment's rule with K = K_max
+        const size_t bb = aj_batch(K, A, P, B, (size_t)T);
+        ABC_TRY(aj_call_setup(ctx, "rank_targets_path", sc, Yt ? Yt : Y, Yt ? N : ldy, N, P, model, A, B, K, (size_t)T, bb, kernel, idx,
+                              d, path->coef, (Yt && tf) ? *tf : AbcTf{nullptr, nullptr, nullptr}, hc, rg, om, keep, &c));
+        const int nc = c.nc;
+        const bool refit = c.hcoef || c.rg.L > 0;
+        double* coef1 = refit ? (double*)abc_ws_alloc(ctx, aj_coef_bytes(B, A, P)) : nullptr;
+        if (refit && !coef1) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
         const AjPlan pl = aj_plan(K, nc, Pi);
-        const size_t bb = aj_path_batch(K, A, P, B, (size_t)T);
         const size_t blk = (size_t)(1 + nc) * (1 + nc + P);
-        double* part = (double*)abc_ws_alloc(ctx, bb * T * pl.nch * blk * 8);
-        if (!part) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
-        const int D = 1 + nc + Pi;
-        const bool wide = D * ((1 + nc + 3) / 4) > 256;              // more than 256 entry groups: k_adj_moments, once per tolerance
-        const size_t lds_m = (size_t)(((D + 1) & ~1) + ((pl.TR + 1) & ~1) + pl.TR * aj_stride(nc, Pi)) * 8;
-        const size_t lds_s = aj_solve_lds(nc);
-        const auto moments = om ? k_adj_moments<true> : k_adj_moments<false>;        // (the RW instances: as the adjustment)
-        const auto moments2 = om ? k_adj_moments2<true> : k_adj_moments2<false>;
-        const auto solve = om ? k_adj_solve<false, true> : k_adj_solve<false, false>;
-        const auto solve_hc = om ? k_adj_solve<true, true> : k_adj_solve<true, false>;
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-        // the variance correction: at every tolerance the fit of abc_rank_targets_adjust_dev with K = K_t over again, in that call's
-        // own chunks (coef1: its first fit, which differs from the path's coef in the last bits where the chunks of K_max and of
-        // K_t differ), then its second fit, so that slot (b, t) of hcoef has that call's bits; one tolerance at a time, the first
-        // pass's blocks in `part` once the path's own solve has read it
-        hcoef = (hc && Pi > 0) ? hc->hcoef : nullptr;
-        const size_t blk2 = (size_t)(1 + nc) * P;
-        // the ridge setting takes the same branch: the refit's coef1 is that call's picked fit, copied to slot (b, t) of the path's
-        // coef (rank and status stay the path's own), and the second fit under both settings models its residuals
-        const bool ridge = rg && rg->L > 0 && Pi > 0;
-        double *part2 = nullptr, *coef1 = nullptr, *rfit = nullptr, *rpp = nullptr;
-        if (hcoef || ridge) {
-            coef1 = (double*)abc_ws_alloc(ctx, B * (A + 1) * P * 8 + 8);
-            if (!coef1) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
-        }
-        if (ridge) {
-            rfit = (double*)abc_ws_alloc(ctx, bb * rg->L * aj_rfit_dbl(nc, Pi) * 8);
-            rpp = (double*)abc_ws_alloc(ctx, bb * rg->L * aj_ridge_tiles(K, nc, Pi) * P * 8);
-            if (!rfit || !rpp) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
-        }
-        if (hcoef) {
-            part2 = (double*)abc_ws_alloc(ctx, bb * pl.nch * blk2 * 8);
-            if (!part2) ABC_FAIL(ctx, ABC_ERR_NOMEM, "rank_targets_path: workspace exhausted");
-            ABC_HIP(ctx, hipFuncSetAttribute((const void*)solve_hc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-        }
+        const bool wide = (1 + nc + Pi) * ((1 + nc + 3) / 4) > 256;  // more than 256 entry groups: k_adj_moments, once per tolerance
         const AjHcSolve hs0 = {nullptr, nullptr, nullptr, nullptr, 1, 0};
         for (size_t b0 = 0; b0 < B; b0 += bb) {
             const size_t nb = (B - b0 < bb) ? B - b0 : bb;
             if (wide) {
                 for (int t = 0; t < T; t++) {
                     const size_t ncht = (ks.K[t] + pl.CH - 1) / pl.CH;
-                    hipLaunchKernelGGL(moments, dim3((unsigned)ncht, (unsigned)nb), dim3(256), lds_m, ctx->stream, src,
-                                       (const uint64_t*)idx, (const double*)d, K, ks.K[t], nc, Pi, kernel, pl.CH, pl.TR, b0,
-                                       (size_t)T * pl.nch, part + (size_t)t * pl.nch * blk, om);
+                    hipLaunchKernelGGL(c.moments, dim3((unsigned)ncht, (unsigned)nb), dim3(256), aj_moments_lds(pl.TR, nc, Pi, 1),
+                                       ctx->stream, c.src, (const uint64_t*)idx, (const double*)d, K, ks.K[t], nc, Pi, kernel, pl.CH,
+                                       pl.TR, b0, (size_t)T * pl.nch, c.part + (size_t)t * pl.nch * blk, om);
                 }
                 ABC_HIP(ctx, hipGetLastError());
             } else {
@@ -1396,57 +1374,26 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
                 for (int hi = T; hi > 0;) {
                     const int n = hi < 4 ? hi : 4, TL = n > 2 ? 4 : n, t0 = hi - TL;
                     switch (TL) {
-                    case 1: ABC_TRY(aj_launch_moments_path<1>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part, om)); break;
-                    case 2: ABC_TRY(aj_launch_moments_path<2>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part, om)); break;
-                    default: ABC_TRY(aj_launch_moments_path<4>(ctx, src, idx, d, K, ks, T, t0, nc, Pi, kernel, pl, b0, nb, part, om)); break;
+                    case 1: ABC_TRY(aj_launch_moments_path<1>(ctx, c, K, ks, T, t0, pl, b0, nb)); break;
+                    case 2: ABC_TRY(aj_launch_moments_path<2>(ctx, c, K, ks, T, t0, pl, b0, nb)); break;
+                    default: ABC_TRY(aj_launch_moments_path<4>(ctx, c, K, ks, T, t0, pl, b0, nb)); break;
                     }
                     hi -= n;
                 }
             }
-            hipLaunchKernelGGL(solve, dim3((unsigned)nb, (unsigned)T), dim3(256), lds_s, ctx->stream, src,
-                               (const uint64_t*)idx, (const double*)d, K, ks, T, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO,
-                               (const double*)part, (int)pl.nch, b0, coef, path->rank, path->status, hs0);
+            hipLaunchKernelGGL(c.solve, dim3((unsigned)nb, (unsigned)T), dim3(256), c.lds_s, ctx->stream, c.src, (const uint64_t*)idx,
+                               (const double*)d, K, ks, T, pl.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)c.part,
+                               (int)pl.nch, b0, c.coef, path->rank, path->status, hs0);
             ABC_HIP(ctx, hipGetLastError());
-            if (!hcoef && !ridge) continue;
-            for (int t = 0; t < T; t++) {
-                const size_t Kt = ks.K[t];
-                const AjPlan pt = aj_plan(Kt, nc, Pi);               // (pt.nch <= pl.nch: the chunk count does not fall with K)
-                const AjPlan2 p2 = aj_plan2(pt, nc, Pi);
-                const size_t lds_t = (size_t)(((D + 1) & ~1) + ((pt.TR + 1) & ~1) + pt.TR * aj_stride(nc, Pi)) * 8;
-                AjKs k1 = {};
-                k1.K[0] = Kt;
-                const AjHcSolve hs1 = {part2, coef1, hcoef, hcoef ? hc->skipped : nullptr, (size_t)T, (size_t)t};
-                hipLaunchKernelGGL(moments, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), lds_t, ctx->stream, src,
-                                   (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, kernel, pt.CH, pt.TR, b0, pt.nch, part, om);
-                hipLaunchKernelGGL(solve, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
-                                   (const double*)d, K, k1, 1, pt.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part,
-                                   (int)pt.nch, b0, coef1, (int32_t*)nullptr, (int32_t*)nullptr, hs0);
-                if (ridge) {
-                    ABC_TRY(aj_ridge(ctx, src, idx, d, K, Kt, nc, Pi, (int)A, kernel, sc, part, pt, b0, nb, *rg, rfit, rpp, coef1,
-                                     (size_t)T, (size_t)t, om));
-                    const size_t cw = (A + 1) * P * 8;
-                    ABC_HIP(ctx, hipMemcpy2DAsync(coef + (b0 * T + t) * (A + 1) * P, (size_t)T * cw, coef1 + b0 * (A + 1) * P, cw, cw, nb,
-                                                  hipMemcpyDeviceToDevice, ctx->stream));
-                }
-                if (!hcoef) continue;
-                hipLaunchKernelGGL(moments2, dim3((unsigned)pt.nch, (unsigned)nb), dim3(256), p2.lds, ctx->stream, src,
-                                   (const uint64_t*)idx, (const double*)d, K, Kt, nc, Pi, (int)A, kernel, pt.CH, p2.TR, b0, pt.nch,
-                                   sc.O, sc.KCO, (const double*)coef1, 1, 0, p2.cf_lds, part2, om);
-                hipLaunchKernelGGL(solve_hc, dim3((unsigned)nb), dim3(256), lds_s, ctx->stream, src, (const uint64_t*)idx,
-                                   (const double*)d, K, k1, 1, pt.CH, nc, Pi, (int)A, kernel, sc.O, sc.KCO, (const double*)part,
-                                   (int)pt.nch, b0, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, hs1);
-                ABC_HIP(ctx, hipGetLastError());
-            }
-        }
-        if (keep) {
-            keep->src = src;
-            keep->O = sc.O;
-            keep->KCO = sc.KCO;
-            keep->nc = nc;
-            keep->coef = coef;
-            keep->dist = d;
-            keep->tf = (Yt && tf) ? *tf : AbcTf{nullptr, nullptr, nullptr};
-            keep->hcoef = hcoef;
+            // Under the variance correction or ridge, tolerance t then goes through the adjust call's own chain with K = K_t, in
+            // that call's chunks (aj_plan(K_t, ..): never more chunks than pl's, so `part` holds them once the solve above has
+            // read it), one tolerance at a time.  coef1 is that call's coef: it differs from the path's in the last bits where the
+            // chunks of K_max and of K_t differ.  Under ridge it is the picked fit, which the chain copies to slot (b, t) of the
+            // path's coef (rank and status stay the path's own); the second fit models coef1's residuals, and slot (b, t) of
+            // hcoef, pick and press is the chain's record at (T, t).
+            for (int t = 0; refit && t < T; t++)
+                ABC_TRY(aj_fit_chain(ctx, c, aj_plan(ks.K[t], nc, Pi), K, ks.K[t], b0, nb, (size_t)T, (size_t)t, coef1, nullptr, nullptr,
+                                     c.rg.L > 0 ? c.coef : nullptr));
         }
     }
     if (path->post_mean || path->h) {
@@ -1454,7 +1401,7 @@ int launch_rank_targets_path(abc_ctx* ctx, const double* X, size_t ldx, const do
         for (size_t b0 = 0; b0 < B; b0 += step) {
             const size_t nb = (B - b0 < step) ? B - b0 : step;
             hipLaunchKernelGGL(om ? k_path_mean<true> : k_path_mean<false>, dim3((unsigned)nb, (unsigned)T), dim3(256), 0, ctx->stream,
-                               Yt ? raw : src, nc, (const uint64_t*)idx + b0 * K, (const double*)d + b0 * K, K, ks, T, Pi,
+                               Yt ? raw : c.src, c.nc, (const uint64_t*)idx + b0 * K, (const double*)d + b0 * K, K, ks, T, Pi,
                                path->post_mean ? path->post_mean + b0 * T * P : nullptr, path->h ? path->h + b0 * T : nullptr, om);
             ABC_HIP(ctx, hipGetLastError());
         }

@@ -1894,6 +1894,20 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     return b + r.prod.stage_bytes(B, P);
 }
 
+// the values a product of the request reads: the retained rows ix of its Y (raw: the transforms are in adj), adjusted under adj
+static SmValues tg_values(const TgRequest& r, const uint64_t* ix, const abc_adj_keep* adj, const double* om) {
+    SmValues sv = {};
+    sv.method = r.method;
+    sv.idx = ix;
+    sv.Y = r.Y;
+    sv.ldy = r.ldy;
+    sv.adj = adj;
+    sv.A = (int)r.A;
+    sv.kernel = r.kernel;
+    sv.om = om;
+    return sv;
+}
+
 // The ranking or (regress) the ranking with the adjustment, then the product if one is asked for; device pointers, the workspace reserved.
 static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const AbcHc* hc, const AbcRg* rg) {
     const size_t B = r.B, K = r.K;
@@ -1925,16 +1939,7 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
         ABC_TRY(launch_rank_targets_path(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
                                          r.any_excl, r.kernel, ix, d, r.path, lin ? &pk : nullptr, Yt, Yt ? &tf : nullptr, hc, rg, om));
         if (!ps) return ABC_OK;
-        SmValues pv = {};
-        pv.method = r.method;
-        pv.idx = ix;
-        pv.Y = r.Y;
-        pv.ldy = r.ldy;
-        pv.adj = lin ? &pk : nullptr;
-        pv.A = (int)r.A;
-        pv.kernel = r.kernel;
-        pv.om = om;
-        return launch_path_summary(ctx, pv, B, r.path->Ks, r.path->T, r.P, r.prod.sum);
+        return launch_path_summary(ctx, tg_values(r, ix, lin ? &pk : nullptr, om), B, r.path->Ks, r.path->T, r.P, r.prod.sum);
     }
     abc_adj_keep keep;
     if (!r.regress()) {     // (post_mean: of the plain ranking only)
@@ -1948,16 +1953,7 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
                                            Yt ? &tf : nullptr, hc, rg, om));
     }
     if (!summary) return ABC_OK;
-    SmValues sv = {};
-    sv.method = r.method;
-    sv.idx = ix;
-    sv.Y = r.Y;
-    sv.ldy = r.ldy;
-    sv.adj = r.regress() ? &keep : nullptr;
-    sv.A = (int)r.A;
-    sv.kernel = r.kernel;
-    sv.om = om;
-    return r.prod.launch(ctx, sv, B, K, r.P, fn);
+    return r.prod.launch(ctx, tg_values(r, ix, r.regress() ? &keep : nullptr, om), B, K, r.P, fn);
 }
 
 // tg_run_queued under the variance correction and the ridge adjustment: the call's second fits, picks and PRESS go to the context's
