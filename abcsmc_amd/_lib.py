@@ -26,6 +26,8 @@ ADJ_STATUS_SKIPPED, ADJ_STATUS_RECTANGULAR = 1, 2
 POSTERIOR_REJECTION, POSTERIOR_LOCLINEAR = 0, 1
 TRANSF_NONE, TRANSF_LOG, TRANSF_LOGIT = 0, 1, 2
 TRANSF_KINDS = {"none": TRANSF_NONE, "log": TRANSF_LOG, "logit": TRANSF_LOGIT}
+BOX_COX_MAXL = 512
+BOX_COX_BAD, BOX_COX_CONSTANT, BOX_COX_SKIPPED = 1, 2, 4
 
 
 class LibraryMissing(ImportError):
@@ -109,6 +111,39 @@ class AdjustOut(C.Structure):
     """abc_adjust_out: every pointer optional (None: not written)"""
     _fields_ = [("theta", C.c_void_p), ("weight", C.c_void_p), ("coef", C.c_void_p), ("rank", C.c_void_p),
                 ("status", C.c_void_p)]
+
+
+class BoxCoxOut(C.Structure):
+    """abc_box_cox_out: every pointer optional (None: not written) except lambda"""
+    _fields_ = [("lam", C.c_void_p), ("best_skew", C.c_void_p), ("skew", C.c_void_p), ("pick", C.c_void_p), ("status", C.c_void_p)]
+
+
+def box_cox_grid(lambda_min=-5.0, lambda_max=5.0, step=0.1):
+    """The search grid of ABC::optimize_box_cox as float64 (L,) (abc_box_cox_grid): the reference's loop over its three float
+    arguments, so the defaults give 100 values and never 0 exactly.  ValueError for what the library refuses."""
+    import numpy as np
+    g = np.empty(BOX_COX_MAXL)
+    n = C.c_size_t(0)
+    with np.errstate(over="ignore"):
+        a, b, st = (float(np.float32(v)) for v in (lambda_min, lambda_max, step))
+    if lib().abc_box_cox_grid(a, b, st, g.ctypes.data, g.size, C.byref(n)):
+        raise ValueError("box_cox_grid(%r, %r, %r): bounds and step must be finite, step > 0, and the grid must have 1 to %d values"
+                         % (lambda_min, lambda_max, step, BOX_COX_MAXL))
+    return g[:n.value].copy()
+
+
+def _host_doubles(a, n, what):
+    """a as a C-contiguous float64 host array of n entries (a scalar is broadcast), or None"""
+    import numpy as np
+    if a is None:
+        return None
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    v = np.asarray(a, dtype=np.float64)
+    v = np.full(n, float(v)) if v.ndim == 0 else np.ascontiguousarray(v.reshape(-1))
+    if v.size != n:
+        raise ValueError("%s needs one entry per column" % what)
+    return v
 
 
 class Summary(C.Structure):
@@ -228,6 +263,11 @@ SIGNATURES = {
     "abc_param_transf_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _sz]),
     "abc_param_transf": (_i, [_vp, _vp, _sz, _sz, _i, _vp]),
     "abc_param_transf_outside": (_i, [_vp, _vp, _i]),
+    "abc_box_cox_grid": (_i, [C.c_float, C.c_float, C.c_float, _vp, _sz, _vp]),
+    "abc_optimize_box_cox_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp]),
+    "abc_optimize_box_cox": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp]),
+    "abc_box_cox_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _sz]),
+    "abc_box_cox": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "abc_ctx_set_adjust_hcorr": (_i, [_vp, _i]),
     "abc_adjust_last_hcorr": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "abc_adjust_hcorr_skipped": (_i, [_vp, _vp, _i]),
@@ -511,6 +551,29 @@ class Context:
         n = C.c_uint64(0)
         self.check(lib().abc_param_transf_outside(self._h, C.byref(n), int(reset)))
         return n.value
+
+    def optimize_box_cox(self, X, grid, shift=None, skew=False):
+        """The Box-Cox skewness search over the columns of a host table (abc_optimize_box_cox; the definition is in the header):
+        X float64 (N, M) Fortran-ordered, grid float64 (L,), shift float64 (M,) or None.  Returns dict(lam (M,), skew_best (M,),
+        pick (M,) int32, status (M,) int32, skew (M, L) or None)."""
+        import numpy as np
+        N, M = X.shape
+        r = dict(lam=np.empty(M), skew_best=np.empty(M), pick=np.empty(M, dtype=np.int32), status=np.empty(M, dtype=np.int32),
+                 skew=np.empty((M, grid.size)) if skew else None)
+        out = BoxCoxOut(*(r[k].ctypes.data if r[k] is not None else None for k in ("lam", "skew_best", "skew", "pick", "status")))
+        self.check(lib().abc_optimize_box_cox(self._h, X.ctypes.data, N, M, shift.ctypes.data if shift is not None else None,
+                                              grid.ctypes.data, grid.size, C.byref(out)))
+        return r
+
+    def box_cox(self, X, lam, shift=None):
+        """The Box-Cox transform of a host table (abc_box_cox): X float64 (n, M) Fortran-ordered, lam float64 (M,), shift float64
+        (M,) or None.  Returns a new (n, M) Fortran-ordered array."""
+        import numpy as np
+        n, M = X.shape
+        out = np.empty((n, M), order="F")
+        self.check(lib().abc_box_cox(self._h, X.ctypes.data, n, M, lam.ctypes.data, shift.ctypes.data if shift is not None else None,
+                                     out.ctypes.data))
+        return out
 
     def set_adjust_hcorr(self, on):
         """The heteroscedastic variance correction of the local-linear adjustment (abc_ctx_set_adjust_hcorr; the definition is

@@ -735,6 +735,84 @@ def coverage_ks(truth_cdf):
     return out.reshape(u.shape[1:])
 
 
+def _box_cox_table(X, what="X"):
+    """A table of metrics as column-major float64 (n, M); a 1-D array is one column (the reference's Col)"""
+    a = np.asarray(X, dtype=np.float64)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    if a.ndim != 2 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("%s must be a non-empty (n, M) table or a column" % what)
+    return np.asfortranarray(a)
+
+
+def _box_cox_shift(shift, X):
+    """shift= as float64 (M,) or None; "auto": 1 - min_j for the columns whose minimum is <= 0, else 0 (minima taken here, on the host)"""
+    M = X.shape[1]
+    if isinstance(shift, str):
+        if shift != "auto":
+            raise ValueError("shift must be None, 'auto', a number or one number per column")
+        mn = X.min(axis=0)
+        if not np.isfinite(mn).all():
+            raise ValueError("shift='auto' needs finite columns")
+        return np.where(mn <= 0, 1.0 - mn, 0.0)
+    sh = _lib._host_doubles(shift, M, "shift")
+    if sh is not None and not np.isfinite(sh).all():
+        raise ValueError("shift must be finite")
+    return sh
+
+
+def optimize_box_cox(X, lambda_min=-5, lambda_max=5, step=0.1, shift=None, skew=False, details=False, ctx=None):
+    """ABC::optimize_box_cox (AbcUtil.cpp:89-109) for every column of X at once: the lambda of the reference's grid whose Box-Cox
+    transform has the smallest |skewness| (the definition, the status bits and the one deviation are in the header).  X: (N, M), or
+    a column (N,) as the reference takes it; shift: None, "auto", a number or one per column, added before the logarithm.  Returns
+    lam (M,), or a float for a column; details=True: dict(lam, skew_best, pick, status, skew (M, L) if skew else None, grid,
+    shift)."""
+    Xf = _box_cox_table(X)
+    sh = _box_cox_shift(shift, Xf)
+    grid = _lib.box_cox_grid(lambda_min, lambda_max, step)
+    r = _ctx(ctx).optimize_box_cox(Xf, grid, sh, skew=skew)
+    if details:
+        r.update(grid=grid, shift=sh)
+        return r
+    return float(r["lam"][0]) if np.ndim(X) == 1 else r["lam"]
+
+
+def box_cox(X, lam, shift=None, ctx=None):
+    """The Box-Cox transform y = ((x + shift)^lam - 1) / lam (lam == 0: log(x + shift)) of the columns of X (n, M), or of a
+    column (n,): lam and shift a number or one per column (abc_box_cox).  Returns an array of X's shape."""
+    Xf = _box_cox_table(X)
+    if lam is None:
+        raise ValueError("lam is required")
+    la = _lib._host_doubles(lam, Xf.shape[1], "lam")
+    if not np.isfinite(la).all():
+        raise ValueError("lam must be finite")
+    sh = _box_cox_shift(shift, Xf)
+    out = _ctx(ctx).box_cox(Xf, la, sh)
+    return out[:, 0] if np.ndim(X) == 1 else out
+
+
+def box_cox_metrics(X, targets=None, lambda_min=-5, lambda_max=5, step=0.1, shift=None, ctx=None):
+    """The metrics' pre-pass of a ranking: the search on the table X (N, M), then the transform of the table and of the targets
+    (B, M) or (M,) with the table's lambda and shift.  Returns dict(lam, shift, pick, skew_best, status, X, targets): X and targets
+    are what every later call must be given in place of the raw ones (targets None if none were given).  A column with status bit
+    0 (an entry <= 0 after the shift) keeps lambda = 1: x - 1 + shift, an affine map."""
+    Xf = _box_cox_table(X)
+    T = None
+    if targets is not None:
+        T = np.asarray(targets, dtype=np.float64)
+        if T.ndim not in (1, 2) or T.shape[-1] != Xf.shape[1]:
+            raise ValueError("targets must be (B, M) or (M,)")
+    sh = _box_cox_shift(shift, Xf)
+    grid = _lib.box_cox_grid(lambda_min, lambda_max, step)
+    ctx = _ctx(ctx)
+    r = ctx.optimize_box_cox(Xf, grid, sh)
+    out = dict(lam=r["lam"], shift=sh if sh is not None else np.zeros(Xf.shape[1]), pick=r["pick"], skew_best=r["skew_best"],
+               status=r["status"], X=ctx.box_cox(Xf, r["lam"], sh), targets=None)
+    if T is not None:
+        out["targets"] = ctx.box_cox(np.asfortranarray(np.atleast_2d(T)), r["lam"], sh).reshape(T.shape)
+    return out
+
+
 def particle_ranking_simple(X_orig, Y_orig, target_values, K=None, details=False, ctx=None):
     """ABC::particle_ranking_simple (AbcUtil.cpp:408-421); Y_orig is unused, as in the reference."""
     ctx = _ctx(ctx)

@@ -340,6 +340,14 @@ int launch_rank_targets_path(abc_ctx*, const double* X, size_t ldx, const double
 // allowed; outside (optional, device): a forward pass adds the entries of transformed columns it found outside their domain
 int launch_param_transf(abc_ctx*, const struct AbcTf* tf, const double* V, size_t ldv, size_t n, size_t P, int inverse, double* out,
                         size_t ldo, unsigned long long* outside);
+// Box-Cox transform of the metrics (boxcox.hip).  Search: shift (M, or NULL) and grid (L) in device memory, out's members device
+// pointers (lambda required); abc_box_cox_need: its arena pieces.  Apply: lambda (M) and shift (M, or NULL) in device memory; in
+// place is allowed.  The callers have checked the sizes.
+size_t abc_box_cox_need(size_t N, size_t M, size_t L);
+int launch_box_cox_search(abc_ctx*, const double* X, size_t ldx, size_t N, size_t M, const double* shift, const double* grid, size_t L,
+                          const abc_box_cox_out* out);
+int launch_box_cox_apply(abc_ctx*, const double* X, size_t ldx, size_t n, size_t M, const double* lambda, const double* shift, double* out,
+                         size_t ldo);
 // weighted posterior quantiles and CDF (summary.hip).  abc_summary_need: workspace of launch_summary for B segment groups of P
 // segments of K values.  SmValues: how the values and weights of segment (b, j) are made (method 0 / 1: the ranking's rows,
 // method 2: V and w); sum: probs in host memory, truth / quant / cdf in device memory.

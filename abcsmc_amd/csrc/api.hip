@@ -2347,6 +2347,128 @@ extern "C" int abc_param_transf(abc_ctx* ctx, const double* V, size_t n, size_t 
     return ABC_OK;
 }
 
+// ---- Box-Cox transform of the metrics (boxcox.hip) ---------------------------------------------------------------------------------
+extern "C" int abc_box_cox_grid(float lambda_min, float lambda_max, float step, double* grid, size_t cap, size_t* L) {
+    if (!L) return ABC_ERR_INVALID;
+    *L = 0;
+    const double lo = (double)lambda_min, hi = (double)lambda_max, st = (double)step;
+    if (!isfinite(lo) || !isfinite(hi) || !isfinite(st) || !(st > 0.0)) return ABC_ERR_INVALID;
+    size_t n = 0;
+    for (double lam = lo; lam <= hi; lam += st) {            // the reference's loop (AbcUtil.cpp:93) with its float arguments widened
+        if (n == ABC_BOX_COX_MAXL) return ABC_ERR_INVALID;
+        if (grid && n < cap) grid[n] = lam;
+        n++;
+    }
+    if (n == 0) return ABC_ERR_INVALID;
+    *L = n;
+    return (grid && cap < n) ? ABC_ERR_INVALID : ABC_OK;
+}
+
+static int box_cox_check(abc_ctx* ctx, const char* fn, const char* rows_name, size_t ldx, size_t rows, size_t M, const double* shift) {
+    if (rows == 0 || M == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: %s = %zu, M = %zu (both must be positive)", fn, rows_name, rows, M);
+    if (ldx < rows) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldx %zu < %s %zu", fn, ldx, rows_name, rows);
+    if (rows >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: %s = %zu, 2^32 rows or more are not supported", fn, rows_name, rows);
+    if (shift)
+        for (size_t j = 0; j < M; ++j)
+            if (!isfinite(shift[j])) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: shift[%zu] is not finite", fn, j);
+    return ABC_OK;
+}
+
+static int box_cox_search_check(abc_ctx* ctx, const char* fn, const double* X, size_t ldx, size_t N, size_t M, const double* shift,
+                                const double* grid, size_t L, const abc_box_cox_out* out) {
+    if (!X || !grid || !out || !out->lambda)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, grid, out and out->lambda are required)", fn);
+    if (L < 1 || L > ABC_BOX_COX_MAXL) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: L = %zu is outside 1..%d", fn, L, (int)ABC_BOX_COX_MAXL);
+    ABC_TRY(box_cox_check(ctx, fn, "N", ldx, N, M, shift));
+    for (size_t k = 0; k < L; ++k)
+        if (!isfinite(grid[k])) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: grid[%zu] is not finite", fn, k);
+    return ABC_OK;
+}
+
+static int box_cox_apply_check(abc_ctx* ctx, const char* fn, const double* X, size_t ldx, size_t n, size_t M, const double* lambda,
+                               const double* shift, const double* out, size_t ldo) {
+    if (!X || !lambda || !out) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X, lambda and out are required)", fn);
+    ABC_TRY(box_cox_check(ctx, fn, "n", ldx, n, M, shift));
+    if (ldo < n) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldo %zu < n %zu", fn, ldo, n);
+    for (size_t j = 0; j < M; ++j)
+        if (!isfinite(lambda[j])) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: lambda[%zu] is not finite", fn, j);
+    return ABC_OK;
+}
+
+extern "C" int abc_optimize_box_cox_dev(abc_ctx* ctx, const double* X, size_t ldx, size_t N, size_t M, const double* shift,
+                                        const double* grid, size_t L, const abc_box_cox_out* out) {
+    CHECK_CTX(ctx);
+    ABC_TRY(box_cox_search_check(ctx, "abc_optimize_box_cox_dev", X, ldx, N, M, shift, grid, L, out));
+    ABC_TRY(abc_ws_reserve(ctx, abc_box_cox_need(N, M, L) + (L + M) * 8 + 4 * 256));
+    Stage s{ctx};
+    const double* grid_d = s.up(grid, L);
+    const double* shift_d = shift ? s.up(shift, M) : nullptr;
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "abc_optimize_box_cox_dev: workspace exhausted");
+    const int rc = launch_box_cox_search(ctx, X, ldx, N, M, shift_d, grid_d, L, out);
+    if (rc == ABC_ERR_NOMEM) ABC_FAIL(ctx, ABC_ERR_NOMEM, "abc_optimize_box_cox_dev: workspace exhausted");
+    ABC_TRY(rc);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+extern "C" int abc_optimize_box_cox(abc_ctx* ctx, const double* X, size_t N, size_t M, const double* shift, const double* grid, size_t L,
+                                    const abc_box_cox_out* out) {
+    CHECK_CTX(ctx);
+    ABC_TRY(box_cox_search_check(ctx, "abc_optimize_box_cox", X, N, N, M, shift, grid, L, out));
+    ABC_TRY(abc_ws_reserve(ctx, abc_box_cox_need(N, M, L) + (N * M + L + 4 * M + M * L) * 8 + 10 * 256));
+    Stage s{ctx};
+    const double* X_d = s.up(X, N * M);
+    const double* grid_d = s.up(grid, L);
+    const double* shift_d = shift ? s.up(shift, M) : nullptr;
+    abc_box_cox_out d;
+    d.lambda = s.dev<double>(M);
+    d.best_skew = out->best_skew ? s.dev<double>(M) : nullptr;
+    d.skew = out->skew ? s.dev<double>(M * L) : nullptr;
+    d.pick = out->pick ? s.dev<int32_t>(M) : nullptr;
+    d.status = out->status ? s.dev<int32_t>(M) : nullptr;
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "abc_optimize_box_cox: workspace exhausted");
+    const int rc = launch_box_cox_search(ctx, X_d, N, N, M, shift_d, grid_d, L, &d);
+    if (rc == ABC_ERR_NOMEM) ABC_FAIL(ctx, ABC_ERR_NOMEM, "abc_optimize_box_cox: workspace exhausted");
+    ABC_TRY(rc);
+    s.down(out->lambda, (const double*)d.lambda, M);
+    s.down(out->best_skew, (const double*)d.best_skew, M);
+    s.down(out->skew, (const double*)d.skew, M * L);
+    s.down(out->pick, (const int32_t*)d.pick, M);
+    s.down(out->status, (const int32_t*)d.status, M);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+extern "C" int abc_box_cox_dev(abc_ctx* ctx, const double* X, size_t ldx, size_t n, size_t M, const double* lambda, const double* shift,
+                               double* out, size_t ldo) {
+    CHECK_CTX(ctx);
+    ABC_TRY(box_cox_apply_check(ctx, "abc_box_cox_dev", X, ldx, n, M, lambda, shift, out, ldo));
+    ABC_TRY(abc_ws_reserve(ctx, 2 * M * 8 + 4 * 256));
+    Stage s{ctx};
+    const double* lambda_d = s.up(lambda, M);
+    const double* shift_d = shift ? s.up(shift, M) : nullptr;
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "abc_box_cox_dev: workspace exhausted");
+    return launch_box_cox_apply(ctx, X, ldx, n, M, lambda_d, shift_d, out, ldo);
+}
+
+extern "C" int abc_box_cox(abc_ctx* ctx, const double* X, size_t n, size_t M, const double* lambda, const double* shift, double* out) {
+    CHECK_CTX(ctx);
+    ABC_TRY(box_cox_apply_check(ctx, "abc_box_cox", X, n, n, M, lambda, shift, out, n));
+    ABC_TRY(abc_ws_reserve(ctx, (n * M + 2 * M) * 8 + 6 * 256));
+    Stage s{ctx};
+    const double* X_d = s.up(X, n * M);
+    const double* lambda_d = s.up(lambda, M);
+    const double* shift_d = shift ? s.up(shift, M) : nullptr;
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "abc_box_cox: workspace exhausted");
+    ABC_TRY(launch_box_cox_apply(ctx, X_d, n, n, M, lambda_d, shift_d, (double*)X_d, n));
+    s.down(out, X_d, n * M);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
 extern "C" int abc_targets_fallbacks(abc_ctx* ctx, uint64_t* count, int reset) {
     if (!ctx || !count) return ABC_ERR_INVALID;
     *count = (uint64_t)ctx->targets_fallbacks;

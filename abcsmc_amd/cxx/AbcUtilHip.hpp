@@ -403,6 +403,37 @@ inline Mat2D param_transf(const Mat2D& V, bool inverse = false) {
     return out;
 }
 
+// Box-Cox transform of the metrics (AbcUtil.h:60-62, AbcUtil.cpp:89-109; the definition is in the C header).  The reference's two
+// signatures over one column, the same search over every column of a table, and the transform itself.  A column with an entry
+// <= 0 returns lambda = 1 (the reference would return lambda_min).  Transform the table AND the observed metrics with the same
+// lambda (and shift), then hand both to any ranking call.
+inline Row optimize_box_cox(const Mat2D& data, const float lambda_min = -5, const float lambda_max = 5, const float step = 0.1f,
+                            const Row& shift = {}) {
+    if (!shift.empty() && shift.size() != data.cols()) throw HipError(ABC_ERR_INVALID, "optimize_box_cox: shift needs one entry per column");
+    double grid[ABC_BOX_COX_MAXL];
+    size_t L = 0;
+    if (abc_box_cox_grid(lambda_min, lambda_max, step, grid, ABC_BOX_COX_MAXL, &L) != ABC_OK)
+        throw HipError(ABC_ERR_INVALID, "optimize_box_cox: the grid needs finite bounds, a step > 0 and 1 to 512 values");
+    Row lambda(data.cols());
+    abc_box_cox_out out = {lambda.data(), nullptr, nullptr, nullptr, nullptr};
+    check(abc_optimize_box_cox(context(), data.data(), data.rows(), data.cols(), shift.empty() ? nullptr : shift.data(), grid, L, &out));
+    return lambda;
+}
+inline float_type optimize_box_cox(const Col& data, const float lambda_min, const float lambda_max, const float step) {
+    Mat2D one(data.size(), 1);
+    std::copy(data.begin(), data.end(), one.data());
+    return optimize_box_cox(one, lambda_min, lambda_max, step)[0];
+}
+inline float_type optimize_box_cox(const Col& data) { return optimize_box_cox(data, -5, 5, 0.1f); }
+// y = ((x + shift)^lambda - 1) / lambda per column (lambda == 0: log(x + shift)); shift empty: zeros
+inline Mat2D box_cox(const Mat2D& data, const Row& lambda, const Row& shift = {}) {
+    if (lambda.size() != data.cols() || (!shift.empty() && shift.size() != data.cols()))
+        throw HipError(ABC_ERR_INVALID, "box_cox: lambda and shift need one entry per column");
+    Mat2D out(data.rows(), data.cols());
+    check(abc_box_cox(context(), data.data(), data.rows(), data.cols(), lambda.data(), shift.empty() ? nullptr : shift.data(), out.data()));
+    return out;
+}
+
 // Heteroscedastic variance correction of the local-linear adjustment (abc_ctx_set_adjust_hcorr; the definition is in the header):
 // on, every call that regresses rescales the residuals of its adjusted rows by a fitted model of the residual variance.
 inline void set_adjust_hcorr(bool on) { check(abc_ctx_set_adjust_hcorr(context(), on ? 1 : 0)); }

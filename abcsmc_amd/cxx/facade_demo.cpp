@@ -90,6 +90,21 @@ int main() {
         std::printf("row weights: post_mean[0] %.3f -> %.3f, same rows %d\n", tp[0].post_mean(2, 0), tw[0].post_mean(2, 0),
                     (int)(tw[0].idx == tp[0].idx));
         if (tw[0].idx != tp[0].idx || tw[0].post_mean(2, 0) == tp[0].post_mean(2, 0)) return 6;
+        // Box-Cox pre-pass of the metrics (AbcUtil.cpp:430's TODO): right-skewed metrics exp(x / scale), the search per column, then
+        // the table and the observed metrics through the same lambdas and on into the ranking
+        Mat2D Xs(N, M);
+        Mat2D os(1, M);
+        for (size_t m = 0; m < M; m++) {
+            for (size_t i = 0; i < N; i++) Xs(i, m) = std::exp(X(i, m) / (10.0 * (1.0 + m)));
+            os(0, m) = std::exp(obs[m] / (10.0 * (1.0 + m)));
+        }
+        const Row lam = optimize_box_cox(Xs);
+        Col first(N);
+        for (size_t i = 0; i < N; i++) first[i] = Xs(i, 0);
+        const Mat2D Xt = box_cox(Xs, lam), ot = box_cox(os, lam);
+        const std::vector<size_t> r_bc = particle_ranking_PLS(Xt, Y, Row(ot.v), 0.5);
+        std::printf("box-cox: lambda[0] %.2f (column alone %.2f), best particle %zu\n", lam[0], optimize_box_cox(first), r_bc[0]);
+        if (optimize_box_cox(first) != lam[0] || !(std::fabs(lam[0]) < 1.0)) return 7;
     } catch (const HipError& e) {
         std::printf("HipError %d: %s\n", e.code, e.what());
         return 1;

@@ -197,6 +197,53 @@ def row_weights(w, ctx=None, device=0):
     return ctx.row_weights(w)
 
 
+def _box_cox_holder(X, ctx):
+    """What the two Box-Cox calls share: the (M, n) holder's layout assert, its sizes and leading dimension, the context on the
+    current stream."""
+    assert X.dim() == 2 and X.dtype == torch.float64 and (X.stride(1) == 1 or X.shape[1] == 1)
+    M, n = X.shape
+    dev = X.device
+    ctx = ctx if ctx is not None else _lib.default_context(dev.index or 0)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    return M, n, (X.stride(0) if M > 1 else n), dev, ctx
+
+
+def optimize_box_cox(X, lambda_min=-5, lambda_max=5, step=0.1, shift=None, skew=False, ctx=None):
+    """The Box-Cox skewness search over the metrics (abc_optimize_box_cox_dev; the definition is in the header).  X: (M, N)
+    column-major holder (a view with a row stride >= N is fine); the grid is the reference's (_lib.box_cox_grid); shift: one
+    value per metric added before the logarithm (a scalar, a sequence, a tensor, or None).  Returns dict(lam (M,), skew_best (M,),
+    pick (M,) int32, status (M,) int32, skew (M, L) or None) as device tensors and grid (L,) as a host array.  Synchronises."""
+    M, N, ldx, dev, ctx = _box_cox_holder(X, ctx)
+    grid = _lib.box_cox_grid(lambda_min, lambda_max, step)
+    sh = _lib._host_doubles(shift, M, "shift")
+    f64, i32 = torch.float64, torch.int32
+    r = dict(lam=torch.empty(M, dtype=f64, device=dev), skew_best=torch.empty(M, dtype=f64, device=dev),
+             pick=torch.empty(M, dtype=i32, device=dev), status=torch.empty(M, dtype=i32, device=dev),
+             skew=torch.empty((M, grid.size), dtype=f64, device=dev) if skew else None)
+    out = _lib.BoxCoxOut(r["lam"].data_ptr(), r["skew_best"].data_ptr(), _ptr(r["skew"]), r["pick"].data_ptr(), r["status"].data_ptr())
+    ctx.check(lib().abc_optimize_box_cox_dev(ctx.handle, X.data_ptr(), ldx, N, M, sh.ctypes.data if sh is not None else None,
+                                             grid.ctypes.data, grid.size, C.byref(out)))
+    r["grid"] = grid
+    return r
+
+
+def box_cox(X, lam, shift=None, out=None, ctx=None):
+    """The Box-Cox transform (abc_box_cox_dev) of X, an (M, n) column-major holder: the table, or a block of targets held the same
+    way.  lam: one exponent per metric (a sequence or a tensor, read on the host); shift as in optimize_box_cox; out: None for a
+    new contiguous (M, n) tensor, or a holder of X's shape (X itself: in place).  Stream-ordered.  Returns out."""
+    M, n, ldx, dev, ctx = _box_cox_holder(X, ctx)
+    if lam is None:
+        raise ValueError("lam is required")
+    la = _lib._host_doubles(lam, M, "lam")
+    sh = _lib._host_doubles(shift, M, "shift")
+    if out is None:
+        out = torch.empty((M, n), dtype=torch.float64, device=dev)
+    assert out.shape == X.shape and out.dtype == torch.float64 and out.device == dev and (out.stride(1) == 1 or n == 1)
+    ctx.check(lib().abc_box_cox_dev(ctx.handle, X.data_ptr(), ldx, n, M, la.ctypes.data, sh.ctypes.data if sh is not None else None,
+                                    out.data_ptr(), out.stride(0) if M > 1 else n))
+    return out
+
+
 def _path_ks(Ks):
     """The tolerance list as a uint64 array (it stays in host memory) and its largest entry."""
     ks = np.ascontiguousarray(np.asarray(Ks, dtype=np.int64).reshape(-1).astype(np.uint64))

@@ -927,6 +927,66 @@ int abc_weighted_draws_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, 
 /* HOST-pointer form: V is K x P column-major (ldv = K); w and dr's arrays in host memory. */
 int abc_weighted_draws(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_draws* dr);
 
+/* ---- Box-Cox transform of the metrics: the skewness search and the transform (ABC::optimize_box_cox, AbcUtil.cpp:89-109) ---------
+ * PLS is linear; simulated metrics (counts, sizes, durations) are positive and right-skewed.  The reference searches, per metric, a
+ * grid of exponents for the lambda whose transform (x^lambda - 1) / lambda has the smallest |skewness| (its ranking carries the
+ * call as a TODO, AbcUtil.cpp:430).  This is that search for every column of a table at once, and the transform.  It is a pre-pass:
+ * transform the table AND the targets, then hand both to any ranking call; no other entry point changes.
+ * All arrays are fp64; matrices are column-major with a leading dimension, as in abc_param_transf_dev.
+ * Grid (abc_box_cox_grid): the reference's loop, quirks included.  The three float arguments are widened to double; then
+ *   lambda_0 = min, lambda_{k+1} = lambda_k + step in fp64, for as long as lambda_k <= max.  So the defaults (-5, 5, 0.1f) give 100
+ *   values, not 101 (the last is 4.9000001475...), and never hit 0 (lambda_50 = 7.45e-8), because (double)0.1f != 0.1; (-2, 2, 0.5f)
+ *   gives 9 values and hits 0 exactly.  ABC_ERR_INVALID for a count outside 1..ABC_BOX_COX_MAXL, a step that is non-finite or <= 0,
+ *   non-finite bounds, NULL L, and a grid with cap below the count (grid may be NULL: the count alone).  The search calls take any
+ *   grid of finite values, this one or the caller's own.
+ * Per column j, with the caller's shifts c_j (NULL: zeros): z_i = x_ij + c_j, l_i = log z_i, lbar the mean of l.  For a grid value:
+ *   lambda != 0: t_i = exp(lambda (l_i - lbar));  lambda == 0: t_i = l_i - lbar;
+ *   skew(lambda) = sgn(lambda) (sum (t - tbar)^3 / N) / (sum (t - tbar)^2 / (N - 1))^(3/2), sgn(0) = +1.
+ *   This is the reference's quantity, skewness((x^lambda - 1) / lambda): skewness does not change under a positive affine map and
+ *   flips sign under a negative one.  The form above is evaluated where it is well conditioned (the reference's own double formula
+ *   loses everything on a column of 1000 +- 50 at the far lambda, where x^-5 - 1 cancels).  The kernels take l_i - lbar as
+ *   v_i - vbar with v_i = log1p((z_i - z_min) / z_min), which keeps the differences of the logs of a narrow column to full relative
+ *   precision, and sum the moments in one sweep about the pilot t = 1 (d = expm1(lambda (l - lbar))), centred at the end.
+ * Pick: ascending k, strict |skew_k| < |best| starting from +inf; a non-finite skew is never taken; if none is finite the pick is
+ *   0 (all the reference's behaviour).  lambda_j = grid[pick_j], best_skew_j = skew[j][pick_j].
+ * Status bits per column:
+ *   bit 0  some z_i is non-finite or <= 0: lambda_j = 1, pick_j = -1, every skew NaN.  DEVIATION: the reference would return
+ *          lambda_min, a destructive transform
+ *   bit 1  min == max, a constant column (N = 1 lands here): every skew 0, pick 0 (the reference's `_v == 0` rule)
+ *   bit 2  some skew of the grid was non-finite (an overflow at the far lambda) and was skipped
+ * Apply: y = expm1(lambda l) / lambda for lambda != 0, y = l for lambda == 0, with l = log(x + c) in IEEE arithmetic: z == 0 gives
+ *   -1 / lambda (lambda > 0) or -inf, z < 0 or NaN gives NaN.  Elementwise: element (i, j) depends on x_ij, lambda_j and c_j only.
+ *   out may be X itself (same pointer and ld); it must not overlap otherwise.
+ * Bits: every reduction order depends on N only and no floating-point atomics are used, so a column's outputs are the same bits on
+ *   a repeat run, alone (M = 1) and among other columns, for any ldx, through the device and the host entry, and whichever
+ *   optional outputs are asked for.
+ * ABC_ERR_INVALID, with a message naming the entry point, for N, n or M equal to 0, ld < rows, NULL X / grid / out / out->lambda /
+ * lambda, L outside 1..ABC_BOX_COX_MAXL and a non-finite grid value, lambda or shift; ABC_ERR_UNSUPPORTED for N or n >= 2^32;
+ * ABC_ERR_NOMEM from the workspace (3 N M L / 2048 doubles of partial sums).  Nothing is launched by a refused call.  Both search
+ * calls synchronise; abc_box_cox_dev is stream-ordered like abc_param_transf_dev (its host arrays are read before it returns).
+ * Cost: N x M x L exponentials, fp64 vector work; the search is compute-bound, unlike everything else here. */
+enum { ABC_BOX_COX_MAXL = 512 };
+typedef struct {            /* every member optional except lambda; device or host memory per the entry point */
+    double*  lambda;        /* M */
+    double*  best_skew;     /* M */
+    double*  skew;          /* M x L row-major: [j][k] */
+    int32_t* pick;          /* M */
+    int32_t* status;        /* M */
+} abc_box_cox_out;
+enum { ABC_BOX_COX_BAD = 1, ABC_BOX_COX_CONSTANT = 2, ABC_BOX_COX_SKIPPED = 4 };
+int abc_box_cox_grid(float lambda_min, float lambda_max, float step, double* grid, size_t cap, size_t* L);   /* host only */
+/* X in device memory (X[i + ldx j]); shift (M, or NULL) and grid (L) in HOST memory; out's members in device memory. */
+int abc_optimize_box_cox_dev(abc_ctx* ctx, const double* X, size_t ldx, size_t N, size_t M, const double* shift, const double* grid,
+                             size_t L, const abc_box_cox_out* out);
+/* HOST-pointer form: X is N x M column-major (ld = N); out's members in host memory. */
+int abc_optimize_box_cox(abc_ctx* ctx, const double* X, size_t N, size_t M, const double* shift, const double* grid, size_t L,
+                         const abc_box_cox_out* out);
+/* The transform of an n x M matrix (X[i + ldx j] -> out[i + ldo j]) in device memory; lambda (M) and shift (M, or NULL) in HOST
+ * memory.  A B x M block of targets is transformed by the same call with n = B. */
+int abc_box_cox_dev(abc_ctx* ctx, const double* X, size_t ldx, size_t n, size_t M, const double* lambda, const double* shift, double* out,
+                    size_t ldo);
+int abc_box_cox(abc_ctx* ctx, const double* X, size_t n, size_t M, const double* lambda, const double* shift, double* out);   /* host pointers, ld = n */
+
 /* ======================================================================================== */
 /* Multi-GPU: rows (particles) sharded over several GPUs of one node             */
 /* ======================================================================================== */
