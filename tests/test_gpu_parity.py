@@ -624,10 +624,14 @@ def test_weight_split_kernel_staging_does_not_change_the_sums():
 
 @pytest.mark.parametrize("P", [16, 11])
 def test_weight_split_kernel_range_edges(gpu_ctx, oracle, P):
-    """edges of the range the split-operand kernel is exact on: particles up to ~9.5 scaled units from the centre and
-    previous weights down to 1e-150 are inside it; one coordinate past 10 units, or a weight of 1e-200, makes that ROW
-    'far': it leaves the matrix work and its pairs are added in fp64 by the fix-up kernels -- the call stays on the split
-    kernel and still matches the oracle"""
+    """rows OUTSIDE the range the split-operand kernel is exact on (a scaled coordinate above 8, a squared norm above 400, a
+    previous weight outside [2^-300, 2^100]: weights.hip, KS_BOUND, KS_NORM2, KS_LW_CAP, KS_LW_MIN), written when the range was
+    wider: every row moved here -- 9.0 to 9.5 scaled units from the centre, then one coordinate 10.6 units out --, and the
+    previous weights 1e-150 (-log2: 498) and 1e-200, are 'far' under today's bounds.  Such a ROW leaves the matrix work and its
+    pairs are added in fp64 by the fix-up kernels: the call stays on the split kernel and still matches the oracle, with more
+    and more far rows from step to step.  The edges themselves, from both sides and through the kernel word, are in
+    tests/test_gpu_weights_branches.py (test_range_edges_of_the_new_rows, test_range_edges_of_the_previous_weights,
+    test_whole_range_shifted_to_its_edges)"""
     from abcsmc_amd import abcutil, _lib
     K, Kp = 400, 600
     wl, th, tp, wp, dv = _weights_case(P, K, Kp, 99)
