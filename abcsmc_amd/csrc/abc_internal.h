@@ -401,23 +401,8 @@ int abc_select_check(abc_ctx* ctx, int* failed);
 // synchronisation, abc_select_check_done reads it
 int abc_select_check_queue(abc_ctx* ctx, int* slot);
 int abc_select_check_done(abc_ctx* ctx, const int* slot);
-// column slices of the weight kernel (weights.hip) and the bytes of partial sums they need; shared with the
-// workspace sizing in api.hip
-inline size_t abc_kde_slices(size_t kn, size_t Kp, int PP) {
-    if (kn == 0 || Kp == 0) return 1;
-    size_t rows_per_slice = 24576 / (size_t)PP;            // ~190 KB of scaled previous-set rows per slice
-    if (rows_per_slice < 256) rows_per_slice = 256;
-    size_t s = (Kp + rows_per_slice - 1) / rows_per_slice;
-    const size_t rb = (kn + 255) / 256;
-    if (s * rb < 4096) s = (4096 + rb - 1) / rb;           // small sets: still a few work-groups per resident slot
-    size_t cap = ((size_t)64 << 20) / (8 * kn);            // partial sums: slices x kn doubles <= 64 MB ...
-    if (cap < 8) cap = 8;                                  // ... but at least 8 slices
-    if (s > cap) s = cap;
-    if (s > Kp / 64) s = Kp / 64;
-    if (s < 1) s = 1;
-    if (s > 1024) s = 1024;
-    return s;
-}
+// the weight stage's plan and its column slices (abc_kde_slices; shared with the workspace sizing in api.hip)
+#include "weights_plan.h"
 // osrc (optional): for every output position the flat input position q * len + i it came from
 int launch_merge_runs(abc_ctx* ctx, const double* key, const uint64_t* idx, int W, size_t len, double* okey, uint64_t* oidx,
                       uint64_t* osrc = nullptr);

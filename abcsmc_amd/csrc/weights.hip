@@ -329,7 +329,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-constexpr int KS_NL = 4;                       // f16 operands per 16-parameter chunk and side
+// (KS_NL = 4 f16 operands per 16-parameter chunk and side: weights_plan.h)
 constexpr int KS_NP = 6;                       // limb products per chunk
 // Exact range of the split kernel (rows outside are "far": fp64 fix-ups).  X = sum h0.h0' - hbTop counts in units of 2^-14 and
 // must stay below 2^10 in every partial sum: with |a|^2, |b|^2 <= KS_NORM2 the products of any number of chunks sum to at most
@@ -678,24 +678,7 @@ struct KsRef { float p0, p1, p2, p3; };        // the four running f32 sums of a
 // parameters).  Error of a batch sum (emulation, scripts/split_precision.py): rms 4.8e-8 / max 2.0e-7 (4.6e-8 / 2.0e-7 with two
 // accumulators).  Measured at 1e10 pairs, P = 16: 2.38 -> 2.24 ms -- the chip clocks 6 % lower under the ninth MFMA (1.78 against
 // 1.90 GHz, PMC), which eats most of what the 26 % shorter instruction stream buys.
-// The kernel's variants, by their first template argument: 1, 2, 4 = 16-parameter chunks; KS_FOLD + 1, 2, 4 = as many chunks
-// holding at most 13 / 29 / 61 parameters with the norm pieces in the three spare K-slots of the LAST chunk's limb operands -- hbTop (three f16 pieces against -1) in the
-// exact h0.h0' step, hbLow (scaled by 2^24, three f16 pieces against -2^-24: f16 has no exponent for it otherwise) in the
-// (h0 2^-11).(r2' 2^11) step, which only ever meets its own partner operand: 7 / 13 / 25 MFMAs per 1024 pairs instead of 9 / 15 / 27 (the -n
-// step stays an instruction of its own: scripts/mfma_merge_probe.hip), and no norm operand to stream (the -1 entries the -n step
-// needs are a per-lane constant).  The matrix pipe's energy is what bounds this kernel.
-constexpr int KS_FOLD = 100;               // variant tag KS_FOLD + chunks: 101, 102, 104
-// KS_TOPN + 1, 2, 4 = full chunks (14..16, 30..32, 62..64 parameters: no spare K-slot) with ONE MFMA less than the plain variants:
-// the norm top is not subtracted by a step of its own in front of the batch reference but TOGETHER with the reference, in one
-// bf16 step (-1 against the top pieces, the pieces of n against the -1 entries): X' - top - n is exact for every result within
-// 2^-128 of the batch's largest (scripts/mfma_topn_probe.hip: 0 of 2 048 000 such results inexact), the others flush to zero
-// anyway.  The reference has to come from X' = h0.h0' alone then: n = floor(max X' - tmin) with tmin the smallest top of the
-// tile, which is only close to the largest X' - top if the tile's tops are close to one another -- so the previous set's tiles
-// are filled in the ORDER OF THE ROWS' TOPS (launch_weights_prev: k_whb, a stable sort, k_wrows writing every row to its rank;
-// pair sums do not care about the order of their terms): the spread inside a tile is the set's range / its tiles.  Taking the
-// maximum of X' - top row by row instead (16 subtractions per lane and tile) cost more than the MFMA saved (+5.7 % at 16
-// parameters); this way the vector pipe gets one subtraction per batch.
-constexpr int KS_TOPN = 200;
+// The kernel's variants, by their first template argument: the plain, KS_FOLD and KS_TOPN families (weights_plan.h)
 template <int V> __host__ __device__ constexpr int kz_nch() { return V > KS_TOPN ? V - KS_TOPN : V > KS_FOLD ? V - KS_FOLD : V; }
 template <int V> __host__ __device__ constexpr bool kz_fold() { return V > KS_FOLD && V < KS_TOPN; }
 template <int V> __host__ __device__ constexpr bool kz_topn() { return V > KS_TOPN; }
@@ -1378,21 +1361,63 @@ __global__ __launch_bounds__(256) void k_tile_tmin(const float* __restrict__ top
     const bool wide = !(mx - mn <= KS_TOPN_SPREAD);
     tinfo[t] = wide ? make_uint2(0u, 0u) : make_uint2(__float_as_uint(mn), 0xffffffffu);
 }
-// full chunks (no spare K-slot) and enough pairs for the sort to pay (it runs on the side stream of the fused drivers, in front of a
-// stage-level call): the variants with one MFMA less
-static bool ks_topn_on(size_t P, bool split, bool fold, size_t pairs) {
-    if (!split || fold) return false;
+// the pair count from which the top-order variants run (ks_topn_on, weights_plan.h); read on every call
+static double ks_topn_min_pairs() {
     const char* e = abc_diag_env("ABC_KDE_TOPN_MIN_PAIRS");                       // (tests: 0 = always; A/B: a huge number = never)
     const double minp = e ? atof(e) : 4.0e9;
-    return (double)pairs >= minp;
+    return minp;
 }
 
-// 33..64 parameters: the previous tiles staged in LDS (k_kde_split_lds), and with it three stored chunks instead of four at 33..48
-// parameters
-static int ks_chunks(size_t P) { return (P <= 16) ? 1 : (P <= 32) ? 2 : (P <= 48) ? 3 : 4; }
-// up to 13 / 17..29 / 33..45 / 49..61 parameters: the variants of the split kernel with two MFMAs fewer (norm pieces in the spare K-slots: KS_FOLD)
-static bool ks_fold_on(size_t P, bool split) {
-    return split && P + 3 <= (size_t)16 * ks_chunks(P);                       // three spare K-slots in the last chunk
+// ---- the stage's kernel tables: which instance a plan (abc_weights_plan, weights_plan.h) gets -------------------------------------
+// k_wrows by chunks, [NCH - 1], with the rows one wave takes (four waves a work-group: grid = (rows_pad / div + 3) / 4)
+using WrowsFn = decltype(&k_wrows<1>);
+struct WrowsEntry { WrowsFn fn; int div; };
+static const WrowsEntry WROWS[4] = {{k_wrows<1>, 32}, {k_wrows<2>, 16}, {k_wrows<4, 3>, 8}, {k_wrows<4>, 8}};
+
+// the split kernels, [plain | fold | top-order][NCH - 1]:
+// three waves per SIMD at 16 parameters (129 VGPRs; four, with two spills: no faster), two at 32 (192)
+// ... one at 64 on this kernel (more than 256 registers: the two resident column operand sets alone are 128) -- which is
+// why 33..64 parameters go to k_kde_split_lds since round 6: the previous tiles in LDS, two waves per SIMD at four chunks
+// (194-205 registers), three at three chunks (up to 48 parameters; 163-168): 7.2-7.9 -> 4.2-6.3 ms per 1e10 pairs
+// (16 parameters: the sixteen-slot interleave, reference one slot behind the exact steps: 2.244 -> 2.220 ms per 1e10 pairs,
+// and ON TOP of it the operand sets trading places instead of being copied: -> 2.13-2.17 ms (without the finer interleave
+// the same loop was 2 % slower than the copying one, rounds 2 and 3); at 32 parameters either change and both together are
+// 0.7-2 % slower than the eight-slot copying loop, at 64 -- one wave per SIMD -- the finer interleave costs 50 %: they keep
+// kz_slots; four waves per SIMD, the reference two slots behind: +0.5 %)
+using SplitFn = decltype(&k_kde_split<1, 3, true, 1>);
+static const SplitFn KDE_SPLIT[3][4] = {
+    {k_kde_split<1, 3, true, 1>,
+     k_kde_split<2, 2>,
+     k_kde_split_lds<3, KDE_LDS_W3, KDE_LDS_F4>,
+     k_kde_split_lds<4, 2, KDE_LDS_F4>},
+    {k_kde_split<KS_FOLD + 1, 3, true, 1>,                     // (up to 13 parameters: seven MFMAs per 1024 pairs, no norm operand)
+     k_kde_split<KS_FOLD + 2, 2, false, 0>,                    // (17..29: thirteen instead of fifteen)
+     k_kde_split_lds<KS_FOLD + 3, KDE_LDS_W3, KDE_LDS_F4>,     // (33..45: three chunks, nineteen MFMAs per 1024 pairs; previous tiles in LDS, two waves per SIMD)
+     k_kde_split_lds<KS_FOLD + 4, 2, KDE_LDS_F4>},             // (49..61 with the previous tiles in LDS: twenty-five)
+    {k_kde_split<KS_TOPN + 1, 3, true, 1>,                     // (14..16 parameters, tiles in the order of the norm tops: eight MFMAs instead of nine)
+     k_kde_split<KS_TOPN + 2, 2, false, 0>,                    // (30..32: fourteen instead of fifteen)
+     k_kde_split_lds<KS_TOPN + 3, KDE_LDS_W3, KDE_LDS_F4>,     // (46..48: twenty)
+     k_kde_split_lds<KS_TOPN + 4, 2, KDE_LDS_F4>},             // (62..64: twenty-six)
+};
+
+// the fp64 kernels by padded width, [log2 PP] (ks_lg): k_kde and k_epan from 2 columns on, the split kernel's fix-ups from 8
+using KdeFn = decltype(&k_kde<2>);
+using EpanFn = decltype(&k_epan<2>);
+using FixupsFn = decltype(&k_kde_fixups<8>);
+static const KdeFn KDE_FP64[7] = {nullptr, k_kde<2>, k_kde<4>, k_kde<8>, k_kde<16>, k_kde<32>, k_kde<64>};
+static const EpanFn KDE_EPAN[7] = {nullptr, k_epan<2>, k_epan<4>, k_epan<8>, k_epan<16>, k_epan<32>, k_epan<64>};
+static const FixupsFn KDE_FIXUPS[7] = {nullptr, nullptr, nullptr, k_kde_fixups<8>, k_kde_fixups<16>, k_kde_fixups<32>, k_kde_fixups<64>};
+static int ks_lg(int PP) { return __builtin_ctz((unsigned)PP); }                  // (PP <= 64: a power of two)
+
+// scaled copy and the limb tiles of one set in one pass (k_wrows): the previous set's (is_prev: with hb, in rank order where
+// `rank` is given) or the new rows' (with the far flags and ha_int / ha_frac)
+static void launch_wrows(const abc_wplan& pl, hipStream_t s, int is_prev, const double* in, size_t rows, size_t ld, size_t P, WConst* wc,
+                         const double* w, double* out, double* hb, unsigned short* tiles, unsigned char* far_flag, unsigned* far_list,
+                         int* ha_int, double* ha_frac, const unsigned* rank, float* topf) {
+    const WrowsEntry& e = WROWS[pl.NCH - 1];
+    const size_t rows_pad = (is_prev ? pl.nbt : pl.nat) * 32;
+    hipLaunchKernelGGL(e.fn, dim3((unsigned)((rows_pad / e.div + 3) / 4)), dim3(256), 0, s, in, rows, ld, (int)P, pl.PP, rows_pad, wc,
+                       w, is_prev, out, hb, tiles, is_prev ? pl.opb : pl.opa, far_flag, far_list, ha_int, ha_frac, pl.fold ? 1 : 0, rank, topf);
 }
 
 int launch_weights_prev(abc_ctx* ctx, size_t P, size_t kn_max, const double* theta_prev, size_t Kp, const double* w_prev,
@@ -1401,29 +1426,23 @@ int launch_weights_prev(abc_ctx* ctx, size_t P, size_t kn_max, const double* the
     if (P > (size_t)W_MAXP) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "weights: P = %zu > %d parameters", P, W_MAXP);
     if (Kp > 0xffffffffull) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "weights: K' = %zu >= 2^32", Kp);
     hipStream_t s = st ? st : ctx->stream;
-    int PP = 2;
-    while (PP < (int)P) PP *= 2;
-    if (P > 64) PP = (int)((P + 63) / 64 * 64);
-    const int NCH = ks_chunks(P);                                   // (3: dealt out as four, three stored)
-    const bool epan = ctx->weight_kernel == ABC_WEIGHT_EPANECHNIKOV;
-    const bool split = (PP >= 8 && P <= 64 && ctx->kde_mode != ABC_KDE_FP64 && !epan);
-    const size_t nbt = (Kp + 31) / 32;
-    const bool fold = ks_fold_on(P, split);
-    const int opb = NCH * KS_NL + (fold ? 0 : 1);
+    const abc_wplan pl = abc_weights_plan(P, kn_max, Kp, ctx->kde_mode, ctx->weight_kernel, ks_topn_min_pairs());
+    const int PP = pl.PP;
+    const bool split = pl.split, topn = pl.topn;
+    const size_t nbt = pl.nbt;
     WConst* wc = (WConst*)abc_ws_alloc(ctx, sizeof(WConst));
     double* b = (double*)abc_ws_alloc(ctx, Kp * PP * sizeof(double));
     double* hb = (double*)abc_ws_alloc(ctx, Kp * sizeof(double));
     double* cpart = (double*)abc_ws_alloc(ctx, (P > 64 ? P : 64) * WC_NB * sizeof(double));
     unsigned short* bt = nullptr;
     unsigned* far_list = nullptr;
-    const bool topn = ks_topn_on(P, split, fold, Kp * kn_max);
     unsigned* rank = nullptr;
     uint2* tmin = nullptr;
     float* topf = nullptr;
     double* hbk = nullptr;
     unsigned* qh = nullptr;
     if (split) {
-        bt = (unsigned short*)abc_ws_alloc(ctx, nbt * opb * 1024);
+        bt = (unsigned short*)abc_ws_alloc(ctx, nbt * pl.opb * 1024);
         far_list = (unsigned*)abc_ws_alloc(ctx, KS_MAX_FAR_J * sizeof(unsigned));
         if (!bt || !far_list) ABC_FAIL(ctx, ABC_ERR_NOMEM, "weights: workspace exhausted");
         if (topn) {
@@ -1437,7 +1456,7 @@ int launch_weights_prev(abc_ctx* ctx, size_t P, size_t kn_max, const double* the
     }
     if (!wc || !b || !hb || !cpart) ABC_FAIL(ctx, ABC_ERR_NOMEM, "weights: workspace exhausted");
     const double* centre = (const double*)((const char*)wc + offsetof(WConst, centre));
-    hipLaunchKernelGGL(k_wprep, dim3(1), dim3(64), 0, s, dv_prev, (int)P, wc, (int)(kn_max / 16 + 32));
+    hipLaunchKernelGGL(k_wprep, dim3(1), dim3(64), 0, s, dv_prev, (int)P, wc, pl.lim_i);
     hipLaunchKernelGGL(k_wcentre, dim3((unsigned)P, WC_NB), dim3(256), 0, s, theta_prev, Kp, wc, cpart);
     hipLaunchKernelGGL(k_wcentre_finish, dim3(1), dim3(P > 64 ? 1024 : 64), 0, s, theta_prev, Kp, (int)P, cpart, wc);
     if (topn) {          // the rows' ranks by norm top (KS_TOPN): keys, a stable sort, the inverse permutation
@@ -1449,19 +1468,7 @@ int launch_weights_prev(abc_ctx* ctx, size_t P, size_t kn_max, const double* the
         ABC_HIP(ctx, hipGetLastError());
     }
     if (split) {         // scaled copy, hb and the limb tiles in one pass (k_wrows)
-        const size_t rbp = nbt * 32;
-        if (NCH == 1)
-            hipLaunchKernelGGL(k_wrows<1>, dim3((unsigned)((rbp / 32 + 3) / 4)), dim3(256), 0, s, theta_prev, Kp, Kp, (int)P, PP, rbp, wc,
-                               w_prev, 1, b, hb, bt, opb, (unsigned char*)nullptr, far_list, (int*)nullptr, (double*)nullptr, fold ? 1 : 0, (const unsigned*)rank, topf);
-        else if (NCH == 2)
-            hipLaunchKernelGGL(k_wrows<2>, dim3((unsigned)((rbp / 16 + 3) / 4)), dim3(256), 0, s, theta_prev, Kp, Kp, (int)P, PP, rbp, wc,
-                               w_prev, 1, b, hb, bt, opb, (unsigned char*)nullptr, far_list, (int*)nullptr, (double*)nullptr, fold ? 1 : 0, (const unsigned*)rank, topf);
-        else if (NCH == 3)
-            hipLaunchKernelGGL((k_wrows<4, 3>), dim3((unsigned)((rbp / 8 + 3) / 4)), dim3(256), 0, s, theta_prev, Kp, Kp, (int)P, PP, rbp, wc,
-                               w_prev, 1, b, hb, bt, opb, (unsigned char*)nullptr, far_list, (int*)nullptr, (double*)nullptr, fold ? 1 : 0, (const unsigned*)rank, topf);
-        else
-            hipLaunchKernelGGL(k_wrows<4>, dim3((unsigned)((rbp / 8 + 3) / 4)), dim3(256), 0, s, theta_prev, Kp, Kp, (int)P, PP, rbp, wc,
-                               w_prev, 1, b, hb, bt, opb, (unsigned char*)nullptr, far_list, (int*)nullptr, (double*)nullptr, fold ? 1 : 0, (const unsigned*)rank, topf);
+        launch_wrows(pl, s, 1, theta_prev, Kp, Kp, P, wc, w_prev, b, hb, bt, nullptr, far_list, nullptr, nullptr, rank, topf);
     } else {
         hipLaunchKernelGGL(k_wscale, dim3((unsigned)((Kp + 255) / 256)), dim3(256), 0, s, theta_prev, Kp, Kp,
                            (int)P, PP, wc, centre, (size_t)1, w_prev, b, hb);
@@ -1482,34 +1489,10 @@ int launch_weights_raw(abc_ctx* ctx, const abc_prior* priors, const double* thet
     ABC_TRY(abc_kde_words(ctx));
     if (Kp > 0xffffffffull) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "weights: K' = %zu >= 2^32", Kp);
     if (k0 + kn > K) ABC_FAIL(ctx, ABC_ERR_INVALID, "weights: row range [%zu,%zu) outside K=%zu", k0, k0 + kn, K);
-    int PP = 2;
-    while (PP < (int)P) PP *= 2;
-    if (P > 64) PP = (int)((P + 63) / 64 * 64);
-    const size_t rb = (kn + 255) / 256;
-    // Column slices: many short ones.  Work-groups are dispatched slice by slice, so the ~2000 resident groups all
-    // stream the same few hundred KB of the previous set through the scalar cache / L2; with 6 slices of 2 MB each
-    // (one residency) the same kernel was 25 % slower, waiting on scalar loads (measured: 6 -> 12.0 ms, 16 -> 10.0,
-    // 64 -> 9.1, 128 -> 9.05 at K = K' = 1e5).  Bounded by the partial-sum buffer (slices x kn doubles <= 64 MB).
-    size_t slices = abc_kde_slices(kn, Kp, PP);
-    if (slices > Kp / 64) slices = Kp / 64;
-    if (slices < 1) slices = 1;
-    if (slices > 1024) slices = 1024;
-    // split-operand kernel: 5 <= P <= 64 parameters (padded width 8, 16, 32 or 64: one, two or four 16-parameter chunks; below
-    // that the fp64 body is as short), unless the caller asked for fp64
-    const int NCH = ks_chunks(P);
-    const bool epan = ctx->weight_kernel == ABC_WEIGHT_EPANECHNIKOV;
-    const bool split = (PP >= 8 && P <= 64 && ctx->kde_mode != ABC_KDE_FP64 && !epan);
-    const size_t nbt = (Kp + 31) / 32, nat = rb * 8;
-    const int opa = NCH * KS_NL;
-    const bool fold = ks_fold_on(P, split);
-    if (split) {
-        // Every work-group of the split kernel loads its 32-64 KB of resident operands once per slice: with the 65 slices
-        // the fp64 kernel likes that was 1.2 GB of fabric traffic per launch at K = K' = 1e5 (PMC).  Its time is flat between
-        // 24 and 130 slices, so it gets about 12k work-groups (16 residencies of the chip) and no more.
-        size_t cap = 12288 / rb;
-        if (cap < 8) cap = 8;
-        if (slices > cap) slices = cap;
-    }
+    abc_wplan pl = abc_weights_plan(P, kn, Kp, ctx->kde_mode, ctx->weight_kernel, ks_topn_min_pairs());
+    const int PP = pl.PP;
+    const bool epan = pl.epan, split = pl.split;
+    const size_t rb = pl.rb, slices = pl.slices, nbt = pl.nbt, nat = pl.nat;
     // the previous set's share: prepared by the caller (side stream, already joined) or here
     abc_wprev own;
     if (!prev || !prev->ready) {
@@ -1518,6 +1501,7 @@ int launch_weights_raw(abc_ctx* ctx, const abc_prior* priors, const double* thet
     }
     if (prev->Kp != Kp || prev->P != P || prev->kn_max < kn || (prev->split != 0) != split)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "weights: the prepared previous set does not match this call");
+    abc_weights_plan_topn(&pl, prev->tmin != nullptr);          // tiles in top order or not: as the set was prepared, whatever kn is
     WConst* wc = (WConst*)prev->wc;
     double* b = prev->b;
     double* hb = prev->hb;
@@ -1530,7 +1514,7 @@ int launch_weights_raw(abc_ctx* ctx, const abc_prior* priors, const double* thet
     double *fix_i = nullptr, *fix_j = nullptr, *ha_frac = nullptr;
     int* ha_int = nullptr;
     if (split) {
-        at = (unsigned short*)abc_ws_alloc(ctx, nat * opa * 1024);
+        at = (unsigned short*)abc_ws_alloc(ctx, nat * pl.opa * 1024);
         far_flag = (unsigned char*)abc_ws_alloc(ctx, nat * 32);
         fix_i = (double*)abc_ws_alloc(ctx, kn * sizeof(double));
         fix_j = (double*)abc_ws_alloc(ctx, kn * sizeof(double));
@@ -1542,116 +1526,34 @@ int launch_weights_raw(abc_ctx* ctx, const abc_prior* priors, const double* thet
     const double* centre = (const double*)((const char*)wc + offsetof(WConst, centre));
     StageTimer tm(ctx, ST_WEIGHTS_MISC);
     if (split) {
-        const size_t ra = nat * 32;
-        if (NCH == 1)
-            hipLaunchKernelGGL(k_wrows<1>, dim3((unsigned)((ra / 32 + 3) / 4)), dim3(256), 0, ctx->stream, theta + k0, kn, K, (int)P, PP, ra,
-                               wc, (const double*)nullptr, 0, a, (double*)nullptr, at, opa, far_flag, far_list, ha_int, ha_frac, fold ? 1 : 0, (const unsigned*)nullptr, (float*)nullptr);
-        else if (NCH == 2)
-            hipLaunchKernelGGL(k_wrows<2>, dim3((unsigned)((ra / 16 + 3) / 4)), dim3(256), 0, ctx->stream, theta + k0, kn, K, (int)P, PP, ra,
-                               wc, (const double*)nullptr, 0, a, (double*)nullptr, at, opa, far_flag, far_list, ha_int, ha_frac, fold ? 1 : 0, (const unsigned*)nullptr, (float*)nullptr);
-        else if (NCH == 3)
-            hipLaunchKernelGGL((k_wrows<4, 3>), dim3((unsigned)((ra / 8 + 3) / 4)), dim3(256), 0, ctx->stream, theta + k0, kn, K, (int)P, PP, ra,
-                               wc, (const double*)nullptr, 0, a, (double*)nullptr, at, opa, far_flag, far_list, ha_int, ha_frac, fold ? 1 : 0, (const unsigned*)nullptr, (float*)nullptr);
-        else
-            hipLaunchKernelGGL(k_wrows<4>, dim3((unsigned)((ra / 8 + 3) / 4)), dim3(256), 0, ctx->stream, theta + k0, kn, K, (int)P, PP, ra,
-                               wc, (const double*)nullptr, 0, a, (double*)nullptr, at, opa, far_flag, far_list, ha_int, ha_frac, fold ? 1 : 0, (const unsigned*)nullptr, (float*)nullptr);
+        launch_wrows(pl, ctx->stream, 0, theta + k0, kn, K, P, wc, nullptr, a, nullptr, at, far_flag, far_list, ha_int, ha_frac, nullptr, nullptr);
     } else {
         hipLaunchKernelGGL(k_wscale, dim3((unsigned)((kn + 255) / 256)), dim3(256), 0, ctx->stream, theta + k0, kn, K,
                            (int)P, PP, wc, centre, (size_t)1, (const double*)nullptr, a, (double*)nullptr);
     }
-#define LAUNCH_KDE(PPV)                                                                                        \
-    hipLaunchKernelGGL(k_kde<PPV>, dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream, a, kn, b, \
-                       Kp, hb, wc, theta, K, k0, theta_prev, part, split ? 1 : 0)
+    const dim3 grid((unsigned)rb, (unsigned)slices);
     if (epan) {
         StageTimer tk(ctx, ST_KDE);
-#define LAUNCH_EPAN(PPV) hipLaunchKernelGGL(k_epan<PPV>, dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream, a, kn, b, Kp, w_prev, wc, (int)P, part)
         if (PP > 64)
-            hipLaunchKernelGGL(k_kde_gen, dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream, a, kn, b, Kp, hb, wc, theta, K, k0,
+            hipLaunchKernelGGL(k_kde_gen, grid, dim3(256), 0, ctx->stream, a, kn, b, Kp, hb, wc, theta, K, k0,
                                theta_prev, part, PP, 1, (int)P, w_prev);
         else
-        switch (PP) {
-            case 2: LAUNCH_EPAN(2); break;
-            case 4: LAUNCH_EPAN(4); break;
-            case 8: LAUNCH_EPAN(8); break;
-            case 16: LAUNCH_EPAN(16); break;
-            case 32: LAUNCH_EPAN(32); break;
-            default: LAUNCH_EPAN(64); break;
-        }
-#undef LAUNCH_EPAN
+            hipLaunchKernelGGL(KDE_EPAN[ks_lg(PP)], grid, dim3(256), 0, ctx->stream, a, kn, b, Kp, w_prev, wc, (int)P, part);
     } else {
         StageTimer tk(ctx, ST_KDE);
-        if (split) {
-            // three waves per SIMD at 16 parameters (129 VGPRs; four, with two spills: no faster), two at 32 (192)
-            // ... one at 64 on this kernel (more than 256 registers: the two resident column operand sets alone are 128) -- which is
-            // why 33..64 parameters go to k_kde_split_lds since round 6: the previous tiles in LDS, two waves per SIMD at four chunks
-            // (194-205 registers), three at three chunks (up to 48 parameters; 163-168): 7.2-7.9 -> 4.2-6.3 ms per 1e10 pairs
-            // (16 parameters: the sixteen-slot interleave, reference one slot behind the exact steps: 2.244 -> 2.220 ms per 1e10 pairs,
-            // and ON TOP of it the operand sets trading places instead of being copied: -> 2.13-2.17 ms (without the finer interleave
-            // the same loop was 2 % slower than the copying one, rounds 2 and 3); at 32 parameters either change and both together are
-            // 0.7-2 % slower than the eight-slot copying loop, at 64 -- one wave per SIMD -- the finer interleave costs 50 %: they keep
-            // kz_slots; four waves per SIMD, the reference two slots behind: +0.5 %)
-            if (fold && NCH == 1)           // (up to 13 parameters: seven MFMAs per 1024 pairs, no norm operand)
-                hipLaunchKernelGGL((k_kde_split<KS_FOLD + 1, 3, true, 1>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (fold && NCH == 2)      // (17..29: thirteen instead of fifteen)
-                hipLaunchKernelGGL((k_kde_split<KS_FOLD + 2, 2, false, 0>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (fold && NCH == 3)      // (33..45: three chunks, nineteen MFMAs per 1024 pairs; previous tiles in LDS, two waves per SIMD)
-                hipLaunchKernelGGL((k_kde_split_lds<KS_FOLD + 3, KDE_LDS_W3, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (fold)                  // (49..61 with the previous tiles in LDS: twenty-five)
-                hipLaunchKernelGGL((k_kde_split_lds<KS_FOLD + 4, 2, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (prev->tmin && NCH == 1)      // (14..16 parameters, tiles in the order of the norm tops: eight MFMAs instead of nine)
-                hipLaunchKernelGGL((k_kde_split<KS_TOPN + 1, 3, true, 1>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (prev->tmin && NCH == 2)      // (30..32: fourteen instead of fifteen)
-                hipLaunchKernelGGL((k_kde_split<KS_TOPN + 2, 2, false, 0>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (prev->tmin && NCH == 3)      // (46..48: twenty)
-                hipLaunchKernelGGL((k_kde_split_lds<KS_TOPN + 3, KDE_LDS_W3, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (prev->tmin)                  // (62..64: twenty-six)
-                hipLaunchKernelGGL((k_kde_split_lds<KS_TOPN + 4, 2, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (NCH == 1)
-                hipLaunchKernelGGL((k_kde_split<1, 3, true, 1>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (NCH == 2)
-                hipLaunchKernelGGL((k_kde_split<2, 2>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else if (NCH == 3)
-                hipLaunchKernelGGL((k_kde_split_lds<3, KDE_LDS_W3, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-            else
-                hipLaunchKernelGGL((k_kde_split_lds<4, 2, KDE_LDS_F4>), dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream,
-                                   (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
-        }
+        if (split)
+            hipLaunchKernelGGL(KDE_SPLIT[pl.fold ? 1 : pl.topn ? 2 : 0][pl.NCH - 1], grid, dim3(256), 0, ctx->stream,
+                               (const uint4*)at, kn, (const uint4*)bt, (unsigned)nbt, wc, (const int*)ha_int, part, (const uint2*)prev->tmin);
         if (PP > 64)
-            hipLaunchKernelGGL(k_kde_gen, dim3((unsigned)rb, (unsigned)slices), dim3(256), 0, ctx->stream, a, kn, b, Kp, hb, wc, theta, K, k0,
+            hipLaunchKernelGGL(k_kde_gen, grid, dim3(256), 0, ctx->stream, a, kn, b, Kp, hb, wc, theta, K, k0,
                                theta_prev, part, PP, 0, (int)P, w_prev);
-        else if (split) {       // far rows + the fp64 kernel as the split kernel's stand-in: one launch, returns at once when not needed
-#define LAUNCH_FIX(PPV)                                                                                                       \
-    hipLaunchKernelGGL(k_kde_fixups<PPV>, dim3((unsigned)(nat + rb + rb * slices)), dim3(256), 0, ctx->stream, a, kn, b, Kp, hb, wc, \
-                       far_flag, far_list, (unsigned)nat, (unsigned)rb, (unsigned)slices, fix_i, fix_j, theta, K, k0, theta_prev, part)
-            switch (PP) {
-                case 8: LAUNCH_FIX(8); break;
-                case 16: LAUNCH_FIX(16); break;
-                case 32: LAUNCH_FIX(32); break;
-                default: LAUNCH_FIX(64); break;
-            }
-#undef LAUNCH_FIX
-        } else
-        switch (PP) {
-            case 2: LAUNCH_KDE(2); break;
-            case 4: LAUNCH_KDE(4); break;
-            case 8: LAUNCH_KDE(8); break;
-            case 16: LAUNCH_KDE(16); break;
-            case 32: LAUNCH_KDE(32); break;
-            default: LAUNCH_KDE(64); break;
-        }
+        else if (split)         // far rows + the fp64 kernel as the split kernel's stand-in: one launch, returns at once when not needed
+            hipLaunchKernelGGL(KDE_FIXUPS[ks_lg(PP)], dim3((unsigned)(nat + rb + rb * slices)), dim3(256), 0, ctx->stream, a, kn, b, Kp, hb, wc,
+                               far_flag, far_list, (unsigned)nat, (unsigned)rb, (unsigned)slices, fix_i, fix_j, theta, K, k0, theta_prev, part);
+        else
+            hipLaunchKernelGGL(KDE_FP64[ks_lg(PP)], grid, dim3(256), 0, ctx->stream, a, kn, b, Kp, hb, wc, theta, K, k0, theta_prev, part,
+                               0 /* not as the split kernel's stand-in */);
     }
-#undef LAUNCH_KDE
     // the whole set in one call (k0 = 0, kn = K) and a caller that normalises next: the sum of squares comes out of k_wfinish
     const unsigned fb = (unsigned)((kn + 63) / 64);
     double* sq_part = nullptr;

@@ -1,7 +1,8 @@
-"""Which kernels the weight stage runs: a copy of the decisions of launch_weights_prev() and launch_weights_raw() in
-abcsmc_amd/csrc/weights.hip, so that a test can state the kernel and branch it means to reach and check that it does.
-tests/test_weights_dispatch.py holds this copy against the launch sites of weights.hip; tests/test_gpu_weights_branches.py
-asserts through it that its cases reach every instance.
+"""Which kernels the weight stage runs: a copy of the plan (abcsmc_amd/csrc/weights_plan.h: abc_weights_plan) and of the kernel
+tables behind launch_weights_prev() and launch_weights_raw() in abcsmc_amd/csrc/weights.hip, so that a test can state the kernel
+and branch it means to reach and check that it does.  tests/test_weights_dispatch.py holds this copy against the plan function
+itself (tests/cxx/weights_plan_probe.cpp) and the tables of weights.hip; tests/test_gpu_weights_branches.py asserts through it
+that its cases reach every instance.
 
 Pair kernels (the `pair` of plan), as the tuple that names the template instance:
     ("split", V, WPS)       k_kde_split<V, WPS, ...>: V = chunks (1, 2), KS_FOLD + chunks (101, 102: the norm pieces in spare
@@ -44,7 +45,7 @@ def chunks(P):
 
 
 def kde_slices(kn, Kp, PP):
-    """abc_internal.h: abc_kde_slices"""
+    """weights_plan.h: abc_kde_slices"""
     if kn == 0 or Kp == 0:
         return 1
     rows_per_slice = max(24576 // PP, 256)
@@ -74,9 +75,6 @@ def plan(P, kn, Kp, kde_mode="auto", weight_kernel="gauss", topn_min_pairs=TOPN_
     topn = split and not fold and float(Kp * kn) >= topn_min_pairs
     rb = (kn + 255) // 256
     slices = kde_slices(kn, Kp, PP)
-    slices = min(slices, Kp // 64)
-    slices = max(slices, 1)
-    slices = min(slices, 1024)
     if split:
         slices = min(slices, max(12288 // rb, 8))
     if epan:

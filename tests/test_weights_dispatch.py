@@ -1,18 +1,23 @@
-"""CPU checks of tests/_weights_dispatch.py, the tests' copy of the weight stage's kernel choice (weights.hip:
-launch_weights_prev, launch_weights_raw): the instances it can reach are exactly the launch sites of the two launchers, so
-the copy and the source cannot drift apart unseen, and the decisions on both sides of every threshold are pinned."""
+"""CPU checks of tests/_weights_dispatch.py, the tests' copy of the weight stage's kernel choice (weights_plan.h:
+abc_weights_plan; weights.hip: the kernel tables behind launch_weights_prev and launch_weights_raw): it gives what the plan
+function itself gives on every case of tests/cxx/weights_plan_probe.cpp, the instances it can reach are exactly the entries of
+the tables the two launchers launch through, so the copy and the source cannot drift apart unseen, and the decisions on both
+sides of every threshold are pinned."""
+import itertools
 import os
 import re
+import subprocess
 
 import numpy as np
 
 import _weights_dispatch as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TABLES = ("WROWS", "KDE_SPLIT", "KDE_FP64", "KDE_EPAN", "KDE_FIXUPS")
 
 
-def _source():
-    return open(os.path.join(ROOT, "abcsmc_amd", "csrc", "weights.hip")).read()
+def _source(name="weights.hip"):
+    return open(os.path.join(ROOT, "abcsmc_amd", "csrc", name)).read()
 
 
 def _launchers():
@@ -22,42 +27,116 @@ def _launchers():
     return body[:body.index("int launch_weights_raw(")], body[body.index("int launch_weights_raw("):]
 
 
+def _helper(name):
+    """the text of a static helper of the two launchers"""
+    src = _source()
+    body = src[src.index("static void %s(" % name):]
+    return body[:body.index("\n}\n")]
+
+
+def _table(name):
+    """the initialiser of one of the static const kernel tables, as text"""
+    return re.search(r"static const \w+ %s(?:\[\d+\])+ = \{(.*?)\};" % name, _source(), re.S).group(1)
+
+
 def _int(expr, names):
     return int(eval(expr, {"__builtins__": {}}, names))
 
 
-def _launch_table():
-    """-> (pair kernels, k_wrows instances of the previous set, ... of the new set, fix-up widths) named at the launch sites"""
-    src = _source()
-    names = {k: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1)) for k in ("KS_FOLD", "KS_TOPN")}
-    names["KDE_LDS_W3"] = int(re.search(r"#define KDE_LDS_W3 (\d+)", src).group(1))
+def _tables():
+    """-> the kernel tables of weights.hip in the order of their entries: split[plain | fold | top-order][NCH - 1] as the tuples of
+    _weights_dispatch, wrows[NCH - 1] as (instance, rows-per-group divisor), and kde / epan / fixups[log2 PP] as widths (None: no entry)"""
+    plan_h = _source("weights_plan.h")
+    names = {k: int(re.search(r"constexpr int %s = (\d+);" % k, plan_h).group(1)) for k in ("KS_FOLD", "KS_TOPN")}
+    names["KDE_LDS_W3"] = int(re.search(r"#define KDE_LDS_W3 (\d+)", _source()).group(1))
     assert names == {"KS_FOLD": D.KS_FOLD, "KS_TOPN": D.KS_TOPN, "KDE_LDS_W3": D.KDE_LDS_W3}
-    prev, raw = _launchers()
-    # what the three macros launch
-    for macro, kernel in (("LAUNCH_KDE", "k_kde"), ("LAUNCH_EPAN", "k_epan"), ("LAUNCH_FIX", "k_kde_fixups")):
-        m = re.search(r"#define %s\(PPV\)\s*\\?\s*hipLaunchKernelGGL\((\w+)<PPV>" % macro, raw)
-        assert m and m.group(1) == kernel, macro
-    pairs, fix = set(), set()
-    for lds, args in re.findall(r"hipLaunchKernelGGL\(\(k_kde_split(_lds)?<([^>]*)>\)", raw):
+    flat = []
+    for lds, args in re.findall(r"\bk_kde_split(_lds)?<([^>]*)>", _table("KDE_SPLIT")):
         a = [s.strip() for s in args.split(",")]
-        pairs.add(("split_lds" if lds else "split", _int(a[0], names), _int(a[1], names)))
-    for pp in re.findall(r"LAUNCH_KDE\((\d+)\)", raw):
-        pairs.add(("kde", int(pp)))
-    for pp in re.findall(r"LAUNCH_EPAN\((\d+)\)", raw):
-        pairs.add(("epan", int(pp)))
+        flat.append(("split_lds" if lds else "split", _int(a[0], names), _int(a[1], names)))
+    assert len(flat) == 12
+    split = [flat[0:4], flat[4:8], flat[8:12]]
+    wrows = [(tuple(int(x) for x in a.split(",")), int(d)) for a, d in re.findall(r"\{k_wrows<([\d, ]+)>, (\d+)\}", _table("WROWS"))]
+    width = lambda tab, kernel: [int(pp) if pp else None for pp in re.findall(r"nullptr|%s<(\d+)>" % kernel, _table(tab))]
+    return split, wrows, width("KDE_FP64", "k_kde"), width("KDE_EPAN", "k_epan"), width("KDE_FIXUPS", "k_kde_fixups")
+
+
+def _named(text):
+    """the kernels a piece of host code launches: by name, through a kernel table, or through a helper that does"""
+    direct = re.findall(r"hipLaunchKernelGGL\(\(?(k_[a-z0-9_]+)", text)
+    tabs = [t for t in TABLES if re.search(r"\b%s\[" % t, text)]
+    via = re.findall(r"hipLaunchKernelGGL\((?:%s)\[|hipLaunchKernelGGL\(e\.fn," % "|".join(TABLES), text)
+    assert len(direct) + len(via) == text.count("hipLaunchKernelGGL("), "a launch this reader does not understand"
+    assert len(via) == len(tabs), "one launch per table"
+    names = set(direct)
+    for t in tabs:
+        names |= set(re.findall(r"\b(k_[a-z0-9_]+)<", _table(t)))
+    if "launch_wrows(" in text and not text.startswith("static void launch_wrows("):
+        names |= _named(_helper("launch_wrows"))
+    return names
+
+
+def _launch_table():
+    """-> (pair kernels, k_wrows instances of the previous set, ... of the new set, fix-up widths) the two launchers launch"""
+    prev, raw = _launchers()
+    split, wrows, kde, epan, fixups = _tables()
+    # the width tables are indexed by log2 PP; k_wrows' by chunks with the rows a wave takes
+    assert kde == epan == [None, 2, 4, 8, 16, 32, 64] and fixups == [None, None, None, 8, 16, 32, 64]
+    assert [d for _, d in wrows] == [32, 16, 8, 8]
+    for tab in ("KDE_SPLIT", "KDE_FP64", "KDE_EPAN", "KDE_FIXUPS"):
+        assert len(re.findall(r"hipLaunchKernelGGL\(%s\[" % tab, raw)) == 1 and tab not in prev, tab
+    assert "KDE_EPAN[ks_lg(PP)]" in raw and "KDE_FIXUPS[ks_lg(PP)]" in raw and "KDE_FP64[ks_lg(PP)]" in raw
+    assert "KDE_SPLIT[pl.fold ? 1 : pl.topn ? 2 : 0][pl.NCH - 1]" in raw and "WROWS[pl.NCH - 1]" in _helper("launch_wrows")
+    pairs = {k for row in split for k in row} | {("kde", w) for w in kde if w} | {("epan", w) for w in epan if w}
     gen = re.findall(r"hipLaunchKernelGGL\(k_kde_gen,.*?part, PP, (\d), \(int\)P, w_prev\);", raw, re.S)
     assert sorted(gen) == ["0", "1"], gen
     pairs |= {("gen", False), ("gen", True)}
-    for pp in re.findall(r"LAUNCH_FIX\((\d+)\)", raw):
-        fix.add(int(pp))
-    rows = lambda text: {tuple(int(x) for x in a.split(",")) for a in re.findall(r"hipLaunchKernelGGL\(\(?k_wrows<([\d, ]+)>", text)}
-    # nothing else is launched from the two
-    named = lambda text: set(re.findall(r"hipLaunchKernelGGL\(\(?(k_[a-z0-9_]+)", text))
-    assert named(prev) == {"k_wprep", "k_wcentre", "k_wcentre_finish", "k_whb", "k_wq_hist", "k_wq_scan", "k_wq_rank", "k_wrows",
-                           "k_wscale", "k_tile_tmin"}, named(prev)
-    assert named(raw) == {"k_wrows", "k_wscale", "k_kde", "k_epan", "k_kde_gen", "k_kde_split", "k_kde_split_lds", "k_kde_fixups",
-                          "k_wfinish"}, named(raw)
-    return pairs, rows(prev), rows(raw), fix
+    # both launchers reach k_wrows through the one helper and its table
+    rows = lambda text: {inst for inst, _ in wrows} if len(re.findall(r"\blaunch_wrows\(pl, ", text)) == 1 else set()
+    assert "k_wrows<" not in prev and "k_wrows<" not in raw
+    # nothing else is launched from the two, the helper they call included
+    assert _named(prev) == {"k_wprep", "k_wcentre", "k_wcentre_finish", "k_whb", "k_wq_hist", "k_wq_scan", "k_wq_rank", "k_wrows",
+                            "k_wscale", "k_tile_tmin"}, _named(prev)
+    assert _named(raw) == {"k_wrows", "k_wscale", "k_kde", "k_epan", "k_kde_gen", "k_kde_split", "k_kde_split_lds", "k_kde_fixups",
+                           "k_wfinish"}, _named(raw)
+    return pairs, rows(prev), rows(raw), {w for w in fixups if w}
+
+
+def test_mirror_agrees_with_the_plan_function(tmp_path):
+    """abc_weights_plan itself (tests/cxx/weights_plan_probe.cpp prints it) and the kernel tables of weights.hip, indexed as
+    launch_weights_raw indexes them, against _weights_dispatch.plan on every case of the probe"""
+    exe = str(tmp_path / "weights_plan_probe")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", os.path.join(ROOT, "tests", "cxx", "weights_plan_probe.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr
+    split_tab, wrows_tab, kde_tab, epan_tab, fix_tab = _tables()
+    shapes = [(300, 700), (150, 700), (300, 1300), (300, 2049), (1, 700), (255, 700), (256, 700), (257, 700), (40000, 100000),
+              (39999, 100000), (100000, 100000), (600000, 100000), (256, 10 ** 6), (3084, 10 ** 6), (100000, 10 ** 7)]
+    shapes += [(300, Kp) for Kp in (1, 31, 32, 33, 63, 64, 65, 127, 128, 129)]
+    want = set(itertools.product(list(range(1, 201)) + [1024], (0, 1), (0, 1), (4.0e9, 0.0), shapes))
+    seen = set()
+    for line in out.stdout.splitlines():
+        f = dict(kv.split("=") for kv in line.split())
+        minp = float(f.pop("minp"))
+        f = {k: int(v) for k, v in f.items()}
+        P, kn, Kp, PP, NCH = f["P"], f["kn"], f["Kp"], f["PP"], f["NCH"]
+        seen.add((P, f["fp64"], f["epan_in"], minp, (kn, Kp)))
+        lg = PP.bit_length() - 1
+        if f["epan"]:
+            pair = ("gen", True) if PP > 64 else ("epan", epan_tab[lg])
+        elif f["split"]:
+            pair = split_tab[1 if f["fold"] else 2 if f["topn"] else 0][NCH - 1]
+            assert pair[1] == f["V"], line
+        else:
+            pair = ("gen", False) if PP > 64 else ("kde", kde_tab[lg])
+        got = {"width": PP, "chunks": NCH, "split": bool(f["split"]), "fold": bool(f["fold"]), "topn": bool(f["topn"]), "pair": pair,
+               "wrows": wrows_tab[NCH - 1][0] if f["split"] else None, "fixup": fix_tab[lg] if f["split"] else None,
+               "slices": f["slices"], "tiles": f["nbt"], "lim_i": f["lim_i"]}
+        assert got == D.plan(P, kn, Kp, "fp64" if f["fp64"] else "auto", "epan" if f["epan_in"] else "gauss", minp), line
+        assert f["epan"] == f["epan_in"] and f["V"] == NCH + (D.KS_FOLD if f["fold"] else D.KS_TOPN if f["topn"] else 0), line
+        assert f["rb"] == (kn + 255) // 256 and f["nat"] == 8 * f["rb"] and f["opa"] == 4 * NCH, line
+        assert f["opb"] == f["opa"] + (0 if f["fold"] else 1), line
+    assert seen == want and len(out.stdout.splitlines()) == len(want) == 201 * 2 * 2 * 2 * 25
 
 
 def test_mirror_reaches_exactly_the_launch_sites():
@@ -82,7 +161,9 @@ def test_the_far_bounds_are_the_kernels():
     assert (val("KS_BOUND"), val("KS_NORM2"), val("KS_LW_CAP"), val("KS_LW_MIN")) == (D.KS_BOUND, D.KS_NORM2, D.KS_LW_CAP, D.KS_LW_MIN)
     assert val("KS_MAX_FAR_J") == D.KS_MAX_FAR_J and val("W_COORD_BOUND") == D.W_COORD_BOUND
     assert "const double minp = e ? atof(e) : 4.0e9;" in src and D.TOPN_MIN_PAIRS == 4.0e9
-    assert "(int)(kn_max / 16 + 32)" in src
+    # the far-row budget of the plan; launch_weights_prev plans for kn_max rows and hands it to k_wprep
+    assert "pl.lim_i = (int)(kn / 16 + 32);" in _source("weights_plan.h")
+    assert "abc_weights_plan(P, kn_max, Kp, " in src and "(int)P, wc, pl.lim_i);" in src
 
 
 def _p(P, kn=300, Kp=700, **kw):
