@@ -8,10 +8,16 @@
 // The operation order is FIXED and shared with the oracle (orc_project_distance): for each
 // metric m ascending, z = (x - mean)/sd (true division), s_k = fma(z, R[m,k], s_k); then
 // d2 = fma(s_k - o_k, s_k - o_k, d2) for k ascending; dist = sqrt(d2).  HBM-bound: 8*M B/particle.
+//
+// Which kernel a call gets is decided in ONE place, abc_project_plan (project_plan.h: host-only, printed by
+// tests/cxx/project_plan_probe.cpp); the three launchers below -- distances, the Wilcoxon rule's scores, both in one pass --
+// ask it and launch through the kernel tables PROJECT_DIST2, PROJECT_DIST2_LDS and PROJECT_DIST and the two helpers
+// launch_pair_lds and launch_mfma.
 #include <stdlib.h>
 
 #include <hip/hip_ext.h>
 #include "abc_internal.h"
+#include "project_plan.h"
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
@@ -56,8 +62,7 @@ __global__ __launch_bounds__(256) void k_project_dist2(const double* __restrict_
     }
 }
 
-// 16 / 32 components: the scalar-register operands of k_project_dist2 no longer fit (32 components x 8 metrics in flight = 256
-// SGPR pairs: hipcc spilled 488 of them to VGPR lanes and the kernel ran at a sixth of its memory time); here the padded loadings
+// 8 / 16 components: the scalar-register operands of k_project_dist2 run out (its table row below); here the padded loadings
 // live in LDS (M x KC doubles, every work-group copies them once) and are read with wave-uniform 16-byte reads (broadcast), the
 // metric columns of a row pair are fetched PF metrics ahead.  Same per-particle operation order as k_project_dist -> same bits.
 template <int KC>
@@ -374,187 +379,105 @@ __global__ void k_pad_model(const double* __restrict__ model, int M, int P, int 
 
 }  // namespace
 
+// ---- the stage's kernel tables: which instance a plan (abc_project_plan, project_plan.h) gets, by log2 of its width (pj_lg) ----------
+using Dist2Fn = decltype(&k_project_dist2<1>);
+using Dist2LdsFn = decltype(&k_project_dist2_lds<8>);
+using DistFn = decltype(&k_project_dist<1>);
+// row pairs, scalar operands.  At 32 components they no longer fit (32 components x 8 metrics in flight = 256 SGPR pairs: hipcc
+// spills 488 of them to VGPR lanes and the kernel runs at a sixth of its memory time): the plan gives that entry only the sets
+// whose loadings are beyond the matrix-pipe kernel's LDS
+static const Dist2Fn PROJECT_DIST2[6] = {k_project_dist2<1>, k_project_dist2<2>, k_project_dist2<4>, k_project_dist2<8>, k_project_dist2<16>, k_project_dist2<32>};
+static const Dist2LdsFn PROJECT_DIST2_LDS[6] = {nullptr, nullptr, nullptr, k_project_dist2_lds<8>, k_project_dist2_lds<16>, nullptr};
+// one row per lane: the tail of every pair kernel and of k_project_mfma<2>
+static const DistFn PROJECT_DIST[6] = {k_project_dist<1>, k_project_dist<2>, k_project_dist<4>, k_project_dist<8>, k_project_dist<16>, k_project_dist<32>};
+static int pj_lg(int KC) { return __builtin_ctz((unsigned)KC); }                  // (KC <= 32: a power of two)
+static bool pj_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The plan's main kernel, one of the two that also write scores (S != NULL: the first nc_force scores of the rows from row_split
+// on, leading dimension sld; dist == NULL: scores only).  A call through a kernel pointer does not see the kernels' default
+// arguments: every argument is passed.  done: an event bound to the kernel's own completion signal (as launch_gather_rows' -- a
+// hipEventRecord behind the launch is one more packet the selection's first kernel would wait for: ~7 us of the critical path)
+template <typename F, typename... Args>
+static void pj_launch(F fn, const abc_pj_plan& pl, hipStream_t st, hipEvent_t done, Args... args) {
+    if (done) hipExtLaunchKernelGGL(fn, dim3(pl.grid), dim3(256), pl.lds, st, nullptr, done, 0, args...);
+    else hipLaunchKernelGGL(fn, dim3(pl.grid), dim3(256), pl.lds, st, args...);
+}
+static void launch_pair_lds(abc_ctx* ctx, const abc_pj_plan& pl, const double* X, size_t ldx, size_t M, const double* model,
+                            const ModelLayout& ML, double* dist, double* S, size_t sld, int nc_force, size_t row_split, hipEvent_t done) {
+    pj_launch(PROJECT_DIST2_LDS[pj_lg(pl.KC)], pl, ctx->stream, done, X, pl.rows / 2, ldx, (int)M, model + ML.off_mean, model + ML.off_sd,
+              model, ML.off_R, ML.off_oscore, dist, S, sld, nc_force, row_split);
+}
+// (-> what hipFuncSetAttribute says: the callers differ in what they do about it)
+static hipError_t launch_mfma(abc_ctx* ctx, const abc_pj_plan& pl, const double* X, size_t ldx, size_t M, const double* model,
+                              const ModelLayout& ML, double* dist, double* S, size_t sld, int nc_force, size_t row_split, hipEvent_t done) {
+    const hipError_t e = hipFuncSetAttribute((const void*)k_project_mfma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+    if (e == hipSuccess)
+        pj_launch(k_project_mfma<2>, pl, ctx->stream, done, X, pl.rows, ldx, (int)M, model + ML.off_mean, model + ML.off_sd, model, ML.off_R,
+                  ML.off_oscore, dist, (int)pl.lds_main, S, sld, nc_force, row_split);
+    return e;
+}
+
 int launch_project_distance(abc_ctx* ctx, const double* X, size_t n, size_t ldx, size_t M, size_t P, size_t A,
                             const double* model, int simple, double* dist) {
     if (n == 0) return ABC_OK;
     StageTimer tm(ctx, ST_PROJECT);
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (simple) {
-        const ModelLayout ML = model_layout(M, P, 0);
-        hipLaunchKernelGGL(k_simple_dist, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, X, n, ldx, (int)M,
-                           model + ML.off_mean, model + ML.off_sd, model + ML.off_zobs, dist);
+    const abc_pj_plan pl = abc_project_plan({PJ_DISTANCE, n, ldx, M, A, simple != 0, 0, 0, pj_aligned(X), pj_aligned(dist), true});
+    const ModelLayout ML = model_layout(M, P, simple ? 0 : A);
+    const double *mean = model + ML.off_mean, *sd = model + ML.off_sd;
+    if (pl.main == PJ_SIMPLE) {
+        hipLaunchKernelGGL(k_simple_dist, dim3(pl.grid), dim3(256), 0, ctx->stream, X, n, ldx, (int)M, mean, sd, model + ML.off_zobs, dist);
         ABC_HIP(ctx, hipGetLastError());
         return ABC_OK;
     }
-    const ModelLayout ML = model_layout(M, P, A);
-    // ncomp lives on the device; the kernel is compiled for the next power-of-two >= A and the
-    // unused components are zero-padded (exact, see k_pad_model).
-    int KC = 1;
-    while (KC < (int)A) KC *= 2;
-    if (KC > 32) KC = (int)((A + 31) / 32) * 32;
+    // the padded copy k_pad_model leaves for the kernels that do not pad the loadings themselves (allocated on every path: the
+    // arena's offsets behind this call do not depend on the plan)
+    const int KC = pl.KC;
     double* Rpad = (double*)abc_ws_alloc(ctx, (M * KC + KC) * sizeof(double));
     if (!Rpad) ABC_FAIL(ctx, ABC_ERR_NOMEM, "project: workspace exhausted");
     double* opad = Rpad + M * KC;
-    if (KC > 32) {
-        hipLaunchKernelGGL(k_pad_model, dim3(1), dim3(256), 0, ctx->stream, model, (int)M, (int)P, (int)A, KC, Rpad, opad);
+    auto pad_model = [&] { hipLaunchKernelGGL(k_pad_model, dim3(1), dim3(256), 0, ctx->stream, model, (int)M, (int)P, (int)A, KC, Rpad, opad); };
+    if (pl.pad && pl.main != PJ_MFMA) { pad_model(); ABC_HIP(ctx, hipGetLastError()); }
+    if (pl.main == PJ_WIDE)
+        hipLaunchKernelGGL(k_project_dist_wide, dim3(pl.grid), dim3(256), 0, ctx->stream, X, n, ldx, (int)M, KC, mean, sd, Rpad, opad, dist);
+    else if (pl.main == PJ_MFMA) {
+        ABC_HIP(ctx, launch_mfma(ctx, pl, X, ldx, M, model, ML, dist, nullptr, 0, 0, 0, nullptr));
         ABC_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_project_dist_wide, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, X, n, ldx, (int)M, KC,
-                           model + ML.off_mean, model + ML.off_sd, Rpad, opad, dist);
-        ABC_HIP(ctx, hipGetLastError());
-        return ABC_OK;
-    }
-    // fast path: row pairs with 16-B loads/stores; the odd last row (if any) goes through the scalar kernel
-    const bool vec_ok = (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)dist & 15) == 0) && n >= 2;
-    const size_t npairs = vec_ok ? n / 2 : 0;
-    const size_t ntail = n - 2 * npairs;
-    size_t pblocks = (npairs + 255) / 256;
-    if (pblocks > 256 * 16) pblocks = 256 * 16;
-    blocks = (ntail + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    // 17..32 components: the score contraction on the fp64 matrix pipe, while its LDS fits (aligned row pairs; an odd last row
-    // goes through the scalar kernel below)
-    bool mfma_kernel = false;
-    size_t mfma_lb = 0, mfma_main = 0;
-    if (KC == 32 && npairs) {       // (16 components: the vector kernel is 5-10 % faster, measured)
-        const size_t M4 = (M + 3) & ~(size_t)3;
-        mfma_main = (M4 * KC + 2 * M4 > (size_t)4 * 64 * (KC + 1)) ? M4 * KC + 2 * M4 : (size_t)4 * 64 * (KC + 1);
-        mfma_lb = (mfma_main + KC) * sizeof(double);
-        mfma_kernel = mfma_lb <= 150 * 1024;
-    }
-    if (mfma_kernel) {
-        const unsigned gb = (unsigned)((2 * npairs + 255) / 256);
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_project_mfma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mfma_lb));
-        hipLaunchKernelGGL(k_project_mfma<2>, dim3(gb), dim3(256), mfma_lb, ctx->stream, X, 2 * npairs, ldx, (int)M, model + ML.off_mean,
-                           model + ML.off_sd, model, ML.off_R, ML.off_oscore, dist, (int)mfma_main);
-        ABC_HIP(ctx, hipGetLastError());
-        if (ntail) {
-            hipLaunchKernelGGL(k_pad_model, dim3(1), dim3(256), 0, ctx->stream, model, (int)M, (int)P, (int)A, KC, Rpad, opad);
-            hipLaunchKernelGGL(k_project_dist<32>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, X + 2 * npairs, ntail, ldx, (int)M,
-                                   model + ML.off_mean, model + ML.off_sd, Rpad, opad, dist + 2 * npairs);
-            ABC_HIP(ctx, hipGetLastError());
-        }
-        return ABC_OK;
-    }
-    // the LDS kernel pads the loadings itself; the others read the padded copy k_pad_model leaves in the workspace
-    const bool lds_kernel = (KC == 8 || KC == 16) && (M * KC + KC) * sizeof(double) <= 64 * 1024 && npairs;
-    if (!lds_kernel || ntail) {
-        hipLaunchKernelGGL(k_pad_model, dim3(1), dim3(256), 0, ctx->stream, model, (int)M, (int)P, (int)A, KC, Rpad, opad);
-        ABC_HIP(ctx, hipGetLastError());
-    }
-    // (8 / 16 components with the loadings in LDS; beyond 64 KB of them, and at 32 components beyond the matrix-pipe kernel's LDS,
-    // the scalar-operand kernel)
-#define LAUNCH_PD_LDS(KCV)                                                                                             \
-    do {                                                                                                               \
-        const int lb = (int)((M * KCV + KCV) * sizeof(double));                                                        \
-        if (npairs) {                                                                                                  \
-            if (pblocks > 1024) pblocks = 1024;                                                                        \
-            hipLaunchKernelGGL(k_project_dist2_lds<KCV>, dim3((unsigned)pblocks), dim3(256), lb, ctx->stream, X,       \
-                               npairs, ldx, (int)M, model + ML.off_mean, model + ML.off_sd, model, ML.off_R,           \
-                               ML.off_oscore, dist);                                                                   \
-        }                                                                                                              \
-        if (ntail)                                                                                                     \
-            hipLaunchKernelGGL(k_project_dist<KCV>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,                 \
-                               X + 2 * npairs, ntail, ldx, (int)M, model + ML.off_mean, model + ML.off_sd, Rpad, opad, \
-                               dist + 2 * npairs);                                                                     \
-    } while (0)
-#define LAUNCH_PD(KCV)                                                                                                 \
-    do {                                                                                                               \
-        if (npairs)                                                                                                    \
-            hipLaunchKernelGGL(k_project_dist2<KCV>, dim3((unsigned)pblocks), dim3(256), 0, ctx->stream, X, npairs,    \
-                               ldx, (int)M, model + ML.off_mean, model + ML.off_sd, Rpad, opad, dist);                 \
-        if (ntail)                                                                                                     \
-            hipLaunchKernelGGL(k_project_dist<KCV>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,                 \
-                               X + 2 * npairs, ntail, ldx, (int)M, model + ML.off_mean, model + ML.off_sd, Rpad, opad, \
-                               dist + 2 * npairs);                                                                     \
-    } while (0)
-    switch (KC) {
-        case 1: LAUNCH_PD(1); break;
-        case 2: LAUNCH_PD(2); break;
-        case 4: LAUNCH_PD(4); break;
-        case 8: if (lds_kernel) LAUNCH_PD_LDS(8); else LAUNCH_PD(8); break;
-        case 16: if (lds_kernel) LAUNCH_PD_LDS(16); else LAUNCH_PD(16); break;
-        default: LAUNCH_PD(32); break;      // (32 components with row pairs and the loadings within LDS: the matrix-pipe kernel above)
-    }
-#undef LAUNCH_PD
-#undef LAUNCH_PD_LDS
+        if (pl.pad) pad_model();                      // (only its tail reads the padded copy)
+    } else if (pl.main == PJ_DIST2_LDS)
+        launch_pair_lds(ctx, pl, X, ldx, M, model, ML, dist, nullptr, 0, 0, 0, nullptr);
+    else if (pl.main == PJ_DIST2)
+        hipLaunchKernelGGL(PROJECT_DIST2[pj_lg(KC)], dim3(pl.grid), dim3(256), 0, ctx->stream, X, pl.rows / 2, ldx, (int)M, mean, sd, Rpad, opad, dist);
+    if (pl.tail == PJ_DIST)
+        hipLaunchKernelGGL(PROJECT_DIST[pj_lg(KC)], dim3(pl.tail_grid), dim3(256), 0, ctx->stream, X + pl.rows, pl.tail_rows, ldx, (int)M, mean, sd,
+                           Rpad, opad, dist + pl.rows);
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
 }
 
 // The validation scores of the Wilcoxon reduction (wilcoxon.hip): S[i + n k] = score k of row i of X (n rows from X on), all A components, by
-// the projection kernels above (row pairs with 16-byte loads; 8 / 16 components with the loadings in LDS, 17..32 on the fp64 matrix
-// pipe).  Returns the number of rows it took (an even number; 0: the shape or the alignment is not theirs) -- the caller scores the rest.
+// the projection kernels above.  Returns the number of rows it took (an even number; 0: the shape or the alignment is not theirs) -- the
+// caller scores the rest.
 size_t launch_project_scores(abc_ctx* ctx, const double* X, size_t n, size_t ldx, size_t M, size_t P, size_t A, const double* model, double* S) {
+    const abc_pj_plan pl = abc_project_plan({PJ_SCORES, n, ldx, M, A, false, 0, n, pj_aligned(X), true, pj_aligned(S)});
+    if (pl.declined) return 0;
     const ModelLayout ML = model_layout(M, P, A);
-    int KC = 1;
-    while (KC < (int)A) KC *= 2;
-    if (KC < 8) KC = 8;
-    const bool vec_ok = (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)S & 15) == 0) && n >= 2;
-    if (!vec_ok || KC > 32) return 0;
-    const size_t npairs = n / 2;
-    if (KC == 32) {
-        const size_t M4 = (M + 3) & ~(size_t)3;
-        const size_t mfma_main = (M4 * KC + 2 * M4 > (size_t)4 * 64 * (KC + 1)) ? M4 * KC + 2 * M4 : (size_t)4 * 64 * (KC + 1);
-        const size_t lb = (mfma_main + KC) * sizeof(double);
-        if (lb > 150 * 1024) return 0;
-        const unsigned gb = (unsigned)((2 * npairs + 255) / 256);
-        if (hipFuncSetAttribute((const void*)k_project_mfma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb) != hipSuccess) return 0;
-        hipLaunchKernelGGL(k_project_mfma<2>, dim3(gb), dim3(256), lb, ctx->stream, X, 2 * npairs, ldx, (int)M, model + ML.off_mean, model + ML.off_sd,
-                           model, ML.off_R, ML.off_oscore, (double*)nullptr, (int)mfma_main, S, n, (int)A);
-        return 2 * npairs;
-    }
-    if ((M * KC + KC) * sizeof(double) > 64 * 1024 || (n & 1)) return 0;      // (16-byte stores into columns of n rows: an even n)
-    size_t pblocks = (npairs + 255) / 256;
-    if (pblocks > 1024) pblocks = 1024;
-    const int lb = (int)((M * KC + KC) * sizeof(double));
-    if (KC == 8)
-        hipLaunchKernelGGL(k_project_dist2_lds<8>, dim3((unsigned)pblocks), dim3(256), lb, ctx->stream, X, npairs, ldx, (int)M, model + ML.off_mean,
-                           model + ML.off_sd, model, ML.off_R, ML.off_oscore, (double*)nullptr, S, n, (int)A);
-    else
-        hipLaunchKernelGGL(k_project_dist2_lds<16>, dim3((unsigned)pblocks), dim3(256), lb, ctx->stream, X, npairs, ldx, (int)M, model + ML.off_mean,
-                           model + ML.off_sd, model, ML.off_R, ML.off_oscore, (double*)nullptr, S, n, (int)A);
-    return 2 * npairs;
+    if (pl.main != PJ_MFMA) launch_pair_lds(ctx, pl, X, ldx, M, model, ML, nullptr, S, n, (int)A, 0, nullptr);
+    else if (launch_mfma(ctx, pl, X, ldx, M, model, ML, nullptr, S, n, (int)A, 0, nullptr) != hipSuccess) return 0;
+    return pl.rows;
 }
 
 // The ranking's projection AND the Wilcoxon reduction's validation scores in ONE pass over X (round 5: as two launches the
 // validation half of X was read twice, and the second read competed with the selection for the chip): dist as
 // launch_project_distance, S[i - row_test + sld k] = score k (all A components) of the rows from row_test on.
-// 0: done; 1: not a shape for it (nothing queued: the caller launches the two separately).
-// done: an event bound to the kernel's own completion signal (as launch_gather_rows' -- a hipEventRecord behind the launch is one more
-// packet the selection's first kernel would wait for: ~7 us of the critical path)
+// 0: done; 1: not a shape for it (nothing queued: the caller launches the two separately).  done: pj_launch.
 int launch_project_distance_scores(abc_ctx* ctx, const double* X, size_t n, size_t ldx, size_t M, size_t P, size_t A, const double* model,
                                    double* dist, double* S, size_t sld, size_t row_test, hipEvent_t done) {
-    const ModelLayout ML = model_layout(M, P, A);
-    int KC = 1;
-    while (KC < (int)A) KC *= 2;
-    const bool vec_ok = (ldx % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)dist & 15) == 0) && (((uintptr_t)S & 15) == 0) &&
-                        n >= 2 && !(n & 1) && !(row_test & 1) && !(sld & 1) && row_test < n;
-    if (!vec_ok || (KC != 8 && KC != 16 && KC != 32)) return 1;
+    const abc_pj_plan pl = abc_project_plan({PJ_FUSED, n, ldx, M, A, false, row_test, sld, pj_aligned(X), pj_aligned(dist), pj_aligned(S)});
+    if (pl.declined) return 1;
     StageTimer tm(ctx, ST_PROJECT);
-    const size_t npairs = n / 2;
-    if (KC == 32) {
-        const size_t M4 = (M + 3) & ~(size_t)3;
-        const size_t mfma_main = (M4 * KC + 2 * M4 > (size_t)4 * 64 * (KC + 1)) ? M4 * KC + 2 * M4 : (size_t)4 * 64 * (KC + 1);
-        const size_t lb = (mfma_main + KC) * sizeof(double);
-        if (lb > 150 * 1024) return 1;
-        const unsigned gb = (unsigned)((n + 255) / 256);
-        ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_project_mfma<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-        hipExtLaunchKernelGGL(k_project_mfma<2>, dim3(gb), dim3(256), lb, ctx->stream, nullptr, done, 0, X, n, ldx, (int)M, model + ML.off_mean,
-                              model + ML.off_sd, model, ML.off_R, ML.off_oscore, dist, (int)mfma_main, S, sld, (int)A, row_test);
-        ABC_HIP(ctx, hipGetLastError());
-        return 0;
-    }
-    if ((M * KC + KC) * sizeof(double) > 64 * 1024) return 1;
-    size_t pblocks = (npairs + 255) / 256;
-    if (pblocks > 1024) pblocks = 1024;
-    const int lb = (int)((M * KC + KC) * sizeof(double));
-    if (KC == 8)
-        hipExtLaunchKernelGGL(k_project_dist2_lds<8>, dim3((unsigned)pblocks), dim3(256), lb, ctx->stream, nullptr, done, 0, X, npairs, ldx, (int)M,
-                              model + ML.off_mean, model + ML.off_sd, model, ML.off_R, ML.off_oscore, dist, S, sld, (int)A, row_test);
-    else
-        hipExtLaunchKernelGGL(k_project_dist2_lds<16>, dim3((unsigned)pblocks), dim3(256), lb, ctx->stream, nullptr, done, 0, X, npairs, ldx, (int)M,
-                              model + ML.off_mean, model + ML.off_sd, model, ML.off_R, ML.off_oscore, dist, S, sld, (int)A, row_test);
+    const ModelLayout ML = model_layout(M, P, A);
+    if (pl.main != PJ_MFMA) launch_pair_lds(ctx, pl, X, ldx, M, model, ML, dist, S, sld, (int)A, row_test, done);
+    else ABC_HIP(ctx, launch_mfma(ctx, pl, X, ldx, M, model, ML, dist, S, sld, (int)A, row_test, done));
     ABC_HIP(ctx, hipGetLastError());
     return 0;
 }

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "abc_internal.h"
+#include "project_plan.h"
 
 namespace {
 
@@ -448,10 +449,8 @@ constexpr int tg_rpt(int kc) { return (kc == 0 || kc >= 32) ? 1 : (32 / kc > 4 ?
 
 // the padded component count the candidate pass holds in registers (0: more than 32, read as needed)
 int tg_kc(size_t A) {
-    if (A > 32) return 0;
-    int kc = 1;
-    while (kc < (int)A) kc *= 2;
-    return kc;
+    const int kc = abc_project_kc(A);
+    return kc > 32 ? 0 : kc;
 }
 
 struct TgPlan {

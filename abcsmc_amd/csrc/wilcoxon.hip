@@ -34,6 +34,7 @@
 // The SORTED path of rounds 1-3 (one stable LSD radix sort of all (key, test) pairs) stays for small sets, for more than
 // 32 components and as the fallback when a bin of the exact step outgrows LDS (massive ties).
 #include "abc_internal.h"
+#include "project_plan.h"
 #include <chrono>
 #include <sched.h>
 #include <time.h>
@@ -270,6 +271,21 @@ __global__ __launch_bounds__(256) void k_wx_scores_wide(const double* __restrict
         for (int k = 0; k < 32; k++)
             if (k0 + k < A) S[i + nt * (k0 + k)] = s[k];
     }
+}
+
+// the vector score kernel by log2 of the padded component count (abc_project_kc, project_plan.h), and the one place that launches
+// it: the scores of nt rows from row_test on into S, leading dimension sld (the wide kernel, above 32 components: sld == nt)
+using WxScoresFn = decltype(&k_wx_scores<1>);
+static const WxScoresFn WX_SCORES[6] = {k_wx_scores<1>, k_wx_scores<2>, k_wx_scores<4>, k_wx_scores<8>, k_wx_scores<16>, k_wx_scores<32>};
+static void launch_wx_scores(abc_ctx* ctx, const double* X, size_t ldx, size_t row_test, size_t nt, size_t M, size_t P, size_t A,
+                             const double* model, double* S, size_t sld) {
+    const unsigned rb = (unsigned)((nt + 255) / 256);
+    const int KC = abc_project_kc(A);
+    if (KC > 32)
+        hipLaunchKernelGGL(k_wx_scores_wide, dim3(rb), dim3(256), 0, ctx->stream, X, ldx, row_test, nt, (int)M, (int)P, (int)A, model, S);
+    else
+        hipLaunchKernelGGL(WX_SCORES[__builtin_ctz((unsigned)KC)], dim3(rb), dim3(256), 0, ctx->stream, X, ldx, row_test, nt, (int)M, (int)P,
+                           (int)A, model, S, sld);
 }
 
 // one thread per (validation row, segment): key / payload of the paired difference
@@ -1356,24 +1372,7 @@ static int launch_wilcoxon_sorted(abc_ctx* ctx, const double* X, const double* Y
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (nseg_host == 0) return ABC_OK;
     const unsigned rb = (unsigned)((nt + 255) / 256);
-    int KC = 1;
-    while (KC < (int)A) KC *= 2;
-    if (A > 32) {
-        hipLaunchKernelGGL(k_wx_scores_wide, dim3(rb), dim3(256), 0, ctx->stream, X, ldx, row_test, nt, (int)M, (int)P, (int)A, model, S);
-        KC = 0;
-    }
-#define LAUNCH_SC(KCV) hipLaunchKernelGGL(k_wx_scores<KCV>, dim3(rb), dim3(256), 0, ctx->stream, X, ldx, row_test, nt, \
-                                          (int)M, (int)P, (int)A, model, S, nt)
-    switch (KC) {
-        case 0: break;
-        case 1: LAUNCH_SC(1); break;
-        case 2: LAUNCH_SC(2); break;
-        case 4: LAUNCH_SC(4); break;
-        case 8: LAUNCH_SC(8); break;
-        case 16: LAUNCH_SC(16); break;
-        default: LAUNCH_SC(32); break;
-    }
-#undef LAUNCH_SC
+    launch_wx_scores(ctx, X, ldx, row_test, nt, M, P, A, model, S, nt);
     hipLaunchKernelGGL(k_wx_diffs, dim3(rb, nseg_host), dim3(256), 0, ctx->stream, Y, ldy, row_test, nt, (int)M, (int)P,
                        (int)A, model, S, plan, key0, val0, nz);
     ABC_HIP(ctx, hipGetLastError());
@@ -1590,21 +1589,7 @@ static void wx_scores(abc_ctx* ctx, const double* X, size_t ldx, size_t row_test
     // vector kernel for what they leave (an odd last row, unaligned or narrow sets)
     const size_t took = launch_project_scores(ctx, X + row_test, nt, ldx, M, P, A, model, S);
     if (took >= nt) return;
-    const size_t nt_all = nt;
-    X += took; S += took; nt -= took;
-    const unsigned rb = (unsigned)((nt + 255) / 256);
-    int KC = 1;
-    while (KC < (int)A) KC *= 2;
-#define LAUNCH_SC(KCV) hipLaunchKernelGGL(k_wx_scores<KCV>, dim3(rb), dim3(256), 0, ctx->stream, X, ldx, row_test, nt, (int)M, (int)P, (int)A, model, S, nt_all)
-    switch (KC) {
-        case 1: LAUNCH_SC(1); break;
-        case 2: LAUNCH_SC(2); break;
-        case 4: LAUNCH_SC(4); break;
-        case 8: LAUNCH_SC(8); break;
-        case 16: LAUNCH_SC(16); break;
-        default: LAUNCH_SC(32); break;
-    }
-#undef LAUNCH_SC
+    launch_wx_scores(ctx, X + took, ldx, row_test, nt - took, M, P, A, model, S + took, nt);
 }
 
 // The cascade, in two halves: begin() queues everything up to level 0's bounds and returns; finish() waits for the host's first

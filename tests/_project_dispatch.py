@@ -1,6 +1,8 @@
-"""Which projection kernels abc_project_distance_dev runs: a copy of launch_project_distance()'s decisions in
-abcsmc_amd/csrc/project.hip, so that a test can state the kernel and branch it means to reach and check that it does.
-tests/test_project_dispatch.py holds this copy against the launch sites of project.hip; tests/test_gpu_project.py asserts through
+"""Which projection kernels abc_project_distance_dev runs: a copy of the decisions of abc_project_plan
+(abcsmc_amd/csrc/project_plan.h), the one plan behind the three launchers of abcsmc_amd/csrc/project.hip, so that a test can state
+the kernel and branch it means to reach and check that it does.  tests/test_project_dispatch.py holds this copy against the plan
+function itself, line by line over the cases tests/cxx/project_plan_probe.cpp prints, and against the kernel tables
+(PROJECT_DIST2, PROJECT_DIST2_LDS, PROJECT_DIST) the launchers launch through; tests/test_gpu_project.py asserts through
 it that its cases reach every kernel, every tail, both matrix-pipe layouts and the second trip of every grid-stride loop.
 
 Kernels (the `main` and `tail` of plan):
@@ -112,9 +114,7 @@ def fused_plan(n, ldx, aligned, M, A, row_test, sld):
     """the kernel launch_project_distance_scores runs -- ("dist2_lds", 8 | 16) or ("mfma", 2, layout) -- or NOT_A_SHAPE (it
     returns 1 and queues nothing: the caller scores the rows with a kernel of its own).  aligned: X, dist and S all on 16-byte
     boundaries; sld: the leading dimension of S."""
-    KC = 1
-    while KC < A:
-        KC *= 2
+    KC = kc_of(A)
     vec_ok = (ldx % 2 == 0 and aligned and n >= 2 and n % 2 == 0 and row_test % 2 == 0 and sld % 2 == 0 and row_test < n)
     if not vec_ok or KC not in (8, 16, 32):
         return NOT_A_SHAPE
@@ -124,6 +124,22 @@ def fused_plan(n, ldx, aligned, M, A, row_test, sld):
     if (M * KC + KC) * 8 > LDS_PAIR:
         return NOT_A_SHAPE
     return ("dist2_lds", KC)
+
+
+def scores_plan(n, ldx, aligned, M, A):
+    """what launch_project_scores runs for the n validation rows of the Wilcoxon rule -- (kernel, rows it takes), the kernel
+    ("dist2_lds", 8 | 16) or ("mfma", 2, layout) -- or NOT_A_SHAPE (it returns 0 rows: the caller scores them all).  aligned: X and
+    S both on 16-byte boundaries; S has n rows.  Unlike the fused pass it has a kernel for up to 4 components (the 8-wide one),
+    and its matrix-pipe kernel takes the even part of an odd n."""
+    KC = max(kc_of(A), 8)
+    if not (ldx % 2 == 0 and aligned and n >= 2) or KC > 32:
+        return NOT_A_SHAPE
+    if KC == 32:
+        main, lb, layout = mfma_lds(M)
+        return (("mfma", 2, layout), n // 2 * 2) if lb <= LDS_MFMA else NOT_A_SHAPE
+    if (M * KC + KC) * 8 > LDS_PAIR or n % 2:
+        return NOT_A_SHAPE
+    return ("dist2_lds", KC), n
 
 
 def family(kernel):

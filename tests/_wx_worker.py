@@ -46,6 +46,9 @@ CASES_CASCADE = {
     "c32_pairs": (32768, 36, 2, 32, "pairs", 18, 1.5),
     "c8_const": (32782, 12, 6, 8, "const", 19, 1.5),
     "c8_zeros": (32778, 12, 6, 8, "zeros", 20, 1.5),
+    # the validation scores from k_project_mfma<2> with the loadings in front of the observed scores in LDS (from 249 metrics on;
+    # an even first validation row, so launch_project_scores takes them: tests/_project_dispatch.py, scores_plan)
+    "c32_loadings": (32768, 249, 2, 17, "plain", 33, 1.5),
 }
 # many open tests (every test kept open: ABC_WX_NOBOUNDS), so that a fine level has enough groups of tests for two and four rows
 # per thread at 65 537 validation rows (tests/_wx_dispatch.py)

@@ -53,9 +53,22 @@ def test_thresholds_are_the_source_s():
     assert "first_r = 32 / (int)(A - 1);" in SRC and "first_r = first_r < 2 ? 2 : (first_r > 4 ? 4 : first_r);" in SRC
     assert "if (stop_at_max && P <= 1024 && A >= 2) {" in SRC and "if ((size_t)first_r >= P) first_r = 0;" in SRC
     assert "if (f == 1 && (NBX <= NBX_last || left > 32)) break;" in SRC
-    # the score kernels: the power of two at or above A; the wide kernel above 32 components on the sorted path only
-    assert SRC.count("while (KC < (int)A) KC *= 2;") == 2 and "if (A > 32) {\n        hipLaunchKernelGGL(k_wx_scores_wide" in SRC
-    assert sorted(set(int(v) for v in re.findall(r"LAUNCH_SC\((\d+)\)", SRC))) == [1, 2, 4, 8, 16, 32]
+    # the score kernels: one helper, the power of two at or above A (the projection's rounding, project_plan.h) through one table
+    # by its log2; the wide kernel above 32 components only -- which is the sorted path only (abc_wx_cascade_applies above)
+    plan_h = open(os.path.join(ROOT, "abcsmc_amd", "csrc", "project_plan.h")).read()
+    kc = re.search(r"inline int abc_project_kc\(size_t A\) \{(.*?)\n\}", plan_h, re.S).group(1)
+    assert "int KC = 1;\n    while (KC < (int)A) KC *= 2;\n    if (KC > 32) KC = (int)((A + 31) / 32) * 32;\n    return KC;" in kc
+    assert "while (KC < (int)A)" not in SRC and "LAUNCH_SC" not in SRC
+    table = re.search(r"static const WxScoresFn WX_SCORES\[6\] = \{(.*?)\};", SRC, re.S).group(1)
+    assert [s.strip() for s in table.split(",")] == ["k_wx_scores<%d>" % v for v in (1, 2, 4, 8, 16, 32)]
+    helper = _body("static void launch_wx_scores(", "\n}\n")
+    assert "const int KC = abc_project_kc(A);\n    if (KC > 32)\n        hipLaunchKernelGGL(k_wx_scores_wide," in helper
+    assert "    else\n        hipLaunchKernelGGL(WX_SCORES[__builtin_ctz((unsigned)KC)]," in helper and helper.count("LaunchKernelGGL(") == 2
+    # both call sites go through it, and nothing else launches a score kernel
+    assert len(re.findall(r"LaunchKernelGGL\(\(?(?:k_wx_scores|WX_SCORES)", SRC)) == 2
+    assert len(re.findall(r"\blaunch_wx_scores\(ctx, ", SRC)) == 2
+    assert "launch_wx_scores(ctx, X, ldx, row_test, nt, M, P, A, model, S, nt);" in _body("int launch_wilcoxon_sorted(", "\n}\n")
+    assert "launch_wx_scores(ctx, X + took, ldx, row_test, nt - took, M, P, A, model, S + took, nt);" in _body("static void wx_scores(", "\n}\n")
 
 
 def test_sweep_instantiations_are_the_launch_macros():
