@@ -173,6 +173,12 @@ class Draws(C.Structure):
                 ("stream", C.c_void_p), ("draws", C.c_void_p), ("src", C.c_void_p), ("bw_out", C.c_void_p), ("ess", C.c_void_p)]
 
 
+class Entropy(C.Structure):
+    """abc_entropy: k (1..8), scale (optional, HOST float64, one value per parameter), then the optional outputs H / knn / zeros
+    (memory as the entry point's other arrays)"""
+    _fields_ = [("k", C.c_int), ("scale", C.c_void_p), ("H", C.c_void_p), ("knn", C.c_void_p), ("zeros", C.c_void_p)]
+
+
 def _draws_stream(stream, n):
     """The stream ids of an abc_draws as a C-contiguous uint64 host array of n entries, or None (target b takes id b)"""
     import numpy as np
@@ -341,7 +347,9 @@ _PRODUCT_ARGS = {
     "abc_weighted_%s": [_vp, _vp, _sz, _sz, _vp, _vp],
 }
 PRODUCTS = ("summary", "density", "joint", "draws")
-SIGNATURES.update((entry % product, (_i, args)) for product in PRODUCTS for entry, args in _PRODUCT_ARGS.items())
+# products of an unweighted sample: the same four argument lists; the entries refuse weights that are not all equal
+UNWEIGHTED_PRODUCTS = ("entropy",)
+SIGNATURES.update((entry % product, (_i, args)) for product in PRODUCTS + UNWEIGHTED_PRODUCTS for entry, args in _PRODUCT_ARGS.items())
 
 _LIB = None
 

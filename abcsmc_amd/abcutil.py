@@ -584,6 +584,19 @@ def weighted_draws(values, weights=None, S=1000, smooth=False, seed=0, bw=None, 
                              ctx)
 
 
+# The products of an unweighted sample (entropy.py) answer under this module's names too.  They are forwarded, not defined here: the
+# functions this module defines under the name particle_ranking_PLS_targets* are the family that works under row importance
+# weights, every member of it, and the entropy is refused under them.
+_UNWEIGHTED = ("particle_ranking_PLS_targets_entropy", "knn_entropy")
+
+
+def __getattr__(name):
+    if name in _UNWEIGHTED:
+        from . import entropy
+        return getattr(entropy, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 def hpd_levels(dens, step_x, step_y, probs=(0.5, 0.9, 0.95)):
     """Contour heights of highest-density regions of one gridded pair density (host only, pure NumPy).  dens: (G, G') values of f on
     a grid with cell area step_x * step_y.  The cells are sorted by descending f and their masses f * step_x * step_y accumulated;
@@ -602,7 +615,7 @@ def hpd_levels(dens, step_x, step_y, probs=(0.5, 0.9, 0.95)):
 
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
                        ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False, transf=None,
-                       bounds=None, hcorr=False, ridge=None, row_weights=None):
+                       bounds=None, hcorr=False, ridge=None, row_weights=None, entropy=False, entropy_k=4, entropy_scale="sd"):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
     without replacement (numpy Generator seeded with `seed`) serve as pseudo-observed data, each ranked against the set with
     itself excluded (the fit is shared: the row stays in it), and the posterior mean of its K nearest rows estimates its
@@ -621,7 +634,10 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
     is unaffected; the median, the mode, truth_cdf and ci95 do change.  ridge: the penalties of the ridge adjustment, handed on
     likewise and ignored under "rejection"; alpha is then the ridge fit's, so every statistic under "loclinear" changes.
     row_weights: the row importance weights of particle_ranking_PLS_targets (one per row of the set), handed to every call, both
-    methods: what a table that is not drawn from the prior needs."""
+    methods: what a table that is not drawn from the prior needs.  entropy=True adds entropy (n_targets,): the k-nearest-neighbour
+    entropy of each left-out row's posterior (particle_ranking_PLS_targets_entropy with k = entropy_k and scale = entropy_scale,
+    same method, kernel and adjustment settings), and mean_entropy: their mean, what min_entropy_components compares.  The estimator
+    takes entries of equal weight only: "loclinear" then needs kernel="rectangular", and the library refuses row_weights."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -660,7 +676,36 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
     if coverage:
         out["truth_cdf"] = sm["cdf"]
         out["ci95"] = ((sm["quant"][:, 1, :] <= theta) & (theta <= sm["quant"][:, 2, :])).mean(axis=0)
+    if entropy:
+        from .entropy import particle_ranking_PLS_targets_entropy
+        en = particle_ranking_PLS_targets_entropy(X, Y, X[rows], training_fraction, K, k=entropy_k, scale=entropy_scale, method=method,
+                                                  kernel=kernel, exclude=rows, max_comp=max_comp, rule=rule, ctx=ctx,
+                                                  **tkw)
+        out["entropy"] = en["H"]
+        out["mean_entropy"] = float(np.mean(en["H"]))
     return out
+
+
+def min_entropy_components(X_orig, Y_orig, n_targets, K, seed, max_comps, entropy_k=4, entropy_scale="sd", **cv_kw):
+    """The number of PLS components by the minimum-entropy criterion of Nunes & Balding (2010), with the components in the place
+    of their summary statistics: cross_validate_pls(..., entropy=True) once per cap in max_comps (a sequence of caps, or an int c
+    for 1..c; the same pseudo-observed rows every time, by seed), and the cap whose posteriors have the lowest mean entropy.
+    Where the two existing rules judge how well the metrics predict the parameters, this one looks at the posterior the ranking
+    produces.  cv_kw: further arguments of cross_validate_pls (training_fraction, rule, method, kernel, ...).  Returns
+    dict(max_comp (C,): the caps; ncomp (C,): the count actually used under each; mean_entropy (C,); pred_error (C, P);
+    best: the cap with the smallest mean entropy (NaN counts as largest; ties go to the smaller cap), best_ncomp: its count)."""
+    caps = list(range(1, int(max_comps) + 1)) if np.ndim(max_comps) == 0 else [int(c) for c in max_comps]
+    if not caps or min(caps) < 1:
+        raise ValueError("max_comps must name at least one cap >= 1")
+    for name in ("max_comp", "entropy"):
+        if name in cv_kw:
+            raise ValueError("%s is set by min_entropy_components" % name)
+    cvs = [cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, max_comp=c, entropy=True, entropy_k=entropy_k,
+                              entropy_scale=entropy_scale, **cv_kw) for c in caps]
+    me = np.array([cv["mean_entropy"] for cv in cvs])
+    at = int(np.argmin(np.where(np.isnan(me), np.inf, me)))
+    return dict(max_comp=np.array(caps), ncomp=np.array([cv["ncomp"] for cv in cvs]), mean_entropy=me,
+                pred_error=np.stack([cv["pred_error"] for cv in cvs]), best=caps[at], best_ncomp=int(cvs[at]["ncomp"]))
 
 
 def cross_validate_pls_path(X_orig, Y_orig, n_targets, Ks, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,

@@ -394,6 +394,10 @@ int launch_joint(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, con
 // checked as launch_density's
 size_t abc_draws_need(size_t B, size_t K, size_t P, int smooth);
 int launch_draws(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_draws* dr, const char* fn);
+// posterior entropy of the same segments (entropy.hip): the k-nearest-neighbour estimate over a target's entries, whose weights are
+// all equal (the entries refuse the rest).  en: scale in host memory, every other array in device memory
+size_t abc_entropy_need(size_t B, size_t K, size_t P);
+int launch_entropy(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_entropy* en, const char* fn);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

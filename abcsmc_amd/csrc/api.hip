@@ -1542,9 +1542,9 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
 
 // ---- batched ranking of many observed targets against one fitted set (targets.hip), optionally followed by the local-linear
 // adjustment (adjust.hip) or by a posterior product of every target's retained rows: the weighted quantiles and CDF (summary.hip),
-// the densities and modes (density.hip), the joint moments and pair densities (joint.hip) or the posterior draws (draws.hip).  One
-// pipeline (tg_*) behind the fourteen entry points of the family and one pair of paths (weighted_dev, weighted_host) behind the eight
-// abc_weighted_* entries, which
+// the densities and modes (density.hip), the joint moments and pair densities (joint.hip), the posterior draws (draws.hip) or the
+// posterior entropy (entropy.hip).  One pipeline (tg_*) behind the sixteen entry points of the family and one pair of paths
+// (weighted_dev, weighted_host) behind the ten abc_weighted_* entries, which
 // compute the same products from given values; what differs between the products is in Product ----
 static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
     if (!sum) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (sum is required)", fn);
@@ -1597,6 +1597,17 @@ static int draws_check(abc_ctx* ctx, const char* fn, const abc_draws* dr) {
     if (dr->smooth && (!(dr->bw_scale > 0.0) || !std::isfinite(dr->bw_scale)))
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: bw_scale = %g (finite, > 0)", fn, dr->bw_scale);
     if (!dr->draws && !dr->src && !dr->bw_out && !dr->ess) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of dr is NULL", fn);
+    return ABC_OK;
+}
+
+static int entropy_check(abc_ctx* ctx, const char* fn, const abc_entropy* en, size_t P) {
+    if (!en) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (en is required)", fn);
+    if (en->k < 1 || en->k > 8) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: k = %d neighbours (1 to 8)", fn, en->k);
+    if (!en->H && !en->knn && !en->zeros) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of en is NULL", fn);
+    if (en->scale)
+        for (size_t j = 0; j < P; j++)
+            if (!(en->scale[j] > 0.0) || !std::isfinite(en->scale[j]))
+                ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: scale[%zu] = %g (finite, > 0)", fn, j, en->scale[j]);
     return ABC_OK;
 }
 
@@ -1680,25 +1691,41 @@ static void draws_down(Stage& s, const abc_draws* h, const abc_draws& d, size_t 
     s.down(h->ess, d.ess, B);
 }
 
+// an abc_entropy's arrays for B targets of K entries, host (h) <-> arena: scale stays where it is, NULL members stay NULL
+static abc_entropy entropy_stage(Stage& s, const abc_entropy* h, size_t B, size_t K) {
+    abc_entropy d = *h;
+    d.H = h->H ? s.dev<double>(B) : nullptr;
+    d.knn = h->knn ? s.dev<double>(B * K) : nullptr;
+    d.zeros = h->zeros ? s.dev<uint64_t>(B) : nullptr;
+    return d;
+}
+static void entropy_down(Stage& s, const abc_entropy* h, const abc_entropy& d, size_t B, size_t K) {
+    s.down(h->H, d.H, B);
+    s.down(h->knn, d.knn, B * K);
+    s.down(h->zeros, d.zeros, B);
+}
+
 namespace {
 // A posterior product: what is computed from the segments' values and weights, described by the caller's abc_summary, abc_density,
-// abc_joint or abc_draws.  Every member below has one row per kind, and nothing else in this file tells the kinds apart: a new
-// product adds
-// its constructor and its six rows here.
+// abc_joint, abc_draws or abc_entropy.  Every member below has one row per kind, and nothing else in this file tells the kinds
+// apart: a new product adds its constructor and its six rows here (and a seventh where it has a demand of its own on the segments,
+// as equal_weights()).
 struct Product {
-    enum Kind { NONE, SUMMARY, DENSITY, JOINT, DRAWS } kind = NONE;
+    enum Kind { NONE, SUMMARY, DENSITY, JOINT, DRAWS, ENTROPY } kind = NONE;
     union {
         const abc_summary* sum = nullptr;
         const abc_density* den;
         const abc_joint* jnt;
         const abc_draws* drw;
+        const abc_entropy* ent;
     };
-    union { abc_summary sum; abc_density den; abc_joint jnt; abc_draws drw; } staged;      // stage()'s copy of the descriptor
+    union { abc_summary sum; abc_density den; abc_joint jnt; abc_draws drw; abc_entropy ent; } staged;      // stage()'s copy of the descriptor
     Product() {}
     explicit Product(const abc_summary* s) : kind(SUMMARY), sum(s) {}
     explicit Product(const abc_density* d) : kind(DENSITY), den(d) {}
     explicit Product(const abc_joint* j) : kind(JOINT), jnt(j) {}
     explicit Product(const abc_draws* d) : kind(DRAWS), drw(d) {}
+    explicit Product(const abc_entropy* e) : kind(ENTROPY), ent(e) {}
 
     // the descriptor's own argument checks (a NULL descriptor among them)
     int check(abc_ctx* ctx, const char* fn, size_t P) const {
@@ -1707,6 +1734,7 @@ struct Product {
         case DENSITY: return density_check(ctx, fn, den);
         case JOINT: return joint_check(ctx, fn, jnt, P);
         case DRAWS: return draws_check(ctx, fn, drw);
+        case ENTROPY: return entropy_check(ctx, fn, ent, P);
         default: return ABC_OK;
         }
     }
@@ -1717,37 +1745,41 @@ struct Product {
         case DENSITY: return abc_density_need(B, K, P, den->G);
         case JOINT: return abc_joint_need(B, K, P, jnt->G, abc_joint_pairs(jnt, P));
         case DRAWS: return abc_draws_need(B, K, P, drw->smooth);
+        case ENTROPY: return abc_entropy_need(B, K, P);
         default: return 0;
         }
     }
     // arena bytes of stage(): what the host entries reserve beyond need()
-    size_t stage_bytes(size_t B, size_t P) const {
+    size_t stage_bytes(size_t B, size_t K, size_t P) const {
         switch (kind) {
         case SUMMARY: return B * P * (sum->nq + 2) * 8 + 16 * 256;         // truth, quant, cdf
         case DENSITY: return B * P * (den->G + 6) * 8 + 32 * 256;          // bw, dens, grid, bw_out, mode, mode_dens
         case JOINT: return joint_stage_bytes(jnt, B, P);
         case DRAWS: return B * (drw->S * (P + 1) + 2 * P + 1) * 8 + 20 * 256;  // draws, src, bw, bw_out, ess
+        case ENTROPY: return B * (K + 2) * 8 + 12 * 256;                   // H, knn, zeros
         default: return 0;
         }
     }
     // A host descriptor's arrays in the arena (inputs uploaded, NULL members stay NULL): the product on those copies.  It points
     // into this object, which has to outlive it.
-    Product stage(Stage& s, size_t B, size_t P) {
+    Product stage(Stage& s, size_t B, size_t K, size_t P) {
         switch (kind) {
         case SUMMARY: staged.sum = summary_stage(s, sum, B, P); return Product(&staged.sum);
         case DENSITY: staged.den = density_stage(s, den, B * P); return Product(&staged.den);
         case JOINT: staged.jnt = joint_stage(s, jnt, B, P); return Product(&staged.jnt);
         case DRAWS: staged.drw = draws_stage(s, drw, B, P); return Product(&staged.drw);
+        case ENTROPY: staged.ent = entropy_stage(s, ent, B, K); return Product(&staged.ent);
         default: return Product();
         }
     }
     // stage()'s outputs back into the host descriptor's arrays
-    void down(Stage& s, size_t B, size_t P) const {
+    void down(Stage& s, size_t B, size_t K, size_t P) const {
         switch (kind) {
         case SUMMARY: summary_down(s, sum, staged.sum, B, P); break;
         case DENSITY: density_down(s, den, staged.den, B * P); break;
         case JOINT: joint_down(s, jnt, staged.jnt, B, P); break;
         case DRAWS: draws_down(s, drw, staged.drw, B, P); break;
+        case ENTROPY: entropy_down(s, ent, staged.ent, B, K); break;
         default: break;
         }
     }
@@ -1758,9 +1790,12 @@ struct Product {
         case DENSITY: return launch_density(ctx, sv, B, K, P, den, fn);
         case JOINT: return launch_joint(ctx, sv, B, K, P, jnt, fn);
         case DRAWS: return launch_draws(ctx, sv, B, K, P, drw, fn);
+        case ENTROPY: return launch_entropy(ctx, sv, B, K, P, ent, fn);
         default: return ABC_OK;
         }
     }
+    // the product is of an unweighted sample: the entries refuse segments whose weights are not all equal
+    bool equal_weights() const { return kind == ENTROPY; }
 };
 
 // what follows the ranking: nothing, the adjustment, a posterior product, the tolerance path
@@ -1841,6 +1876,12 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
         if (r.P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, r.P);
     }
     ABC_TRY(r.prod.check(ctx, fn, r.P));
+    if (summary && r.prod.equal_weights()) {     // (an estimator for an unweighted sample: ignoring weights would give a wrong number)
+        if (ctx->rw_N)
+            ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: row importance weights are set on the context, and the estimate is for entries of equal weight", fn);
+        if (r.method == ABC_POSTERIOR_LOCLINEAR && r.kernel != ABC_KERNEL_RECTANGULAR)
+            ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: the Epanechnikov kernel weights the entries, and the estimate is for entries of equal weight (pass the rectangular kernel)", fn);
+    }
     if (r.path_summary() && !r.prod.sum->quant && !r.prod.sum->cdf)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: quant and cdf of sum are both NULL", fn);
     if (B == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: no targets (B == 0)", fn);
@@ -1891,7 +1932,7 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     else if (r.kind == TG_PATH) b += B * r.path->T * ((A + 2) * P + 2) * 8 + 8 * 256;      // abc_path: post_mean, coef, rank + status, h
     else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
     if (r.path_summary()) return b + B * P * (r.path->T * (r.prod.sum->nq + 1) + 1) * 8 + 16 * 256;     // truth, quant, cdf
-    return b + r.prod.stage_bytes(B, P);
+    return b + r.prod.stage_bytes(B, K, P);
 }
 
 // the values a product of the request reads: the retained rows ix of its Y (raw: the transforms are in adj), adjusted under adj
@@ -2049,7 +2090,7 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         psd.cdf = sh->cdf ? s.dev<double>(B * T * P) : nullptr;
         r.prod = Product(&psd);
     } else {
-        r.prod = h.prod.stage(s, B, P);
+        r.prod = h.prod.stage(s, B, K, P);
     }
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_TRY(tg_run(ctx, fn, r));
@@ -2075,7 +2116,7 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         s.down(h.prod.sum->quant, psd.quant, B * h.path->T * h.prod.sum->nq * P);
         s.down(h.prod.sum->cdf, psd.cdf, B * h.path->T * P);
     } else {
-        h.prod.down(s, B, P);
+        h.prod.down(s, B, K, P);
     }
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
@@ -2229,6 +2270,26 @@ extern "C" int abc_rank_targets_draws_dev(abc_ctx* ctx, const double* X, size_t 
     return tg_dev(ctx, "abc_rank_targets_draws_dev", r);
 }
 
+extern "C" int abc_rank_targets_entropy_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                            size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                            const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                            const abc_adjust_out* adj, const abc_entropy* en) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_PRODUCT, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(en)};
+    return tg_dev(ctx, "abc_rank_targets_entropy_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_entropy(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                        const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                        const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                                        double* dist, const abc_adjust_out* adj, const abc_entropy* en, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_PRODUCT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(en)};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_entropy", h, train_frac, max_comp, rule, ncomp);
+}
+
 extern "C" int abc_particle_ranking_pls_targets_draws(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
                                                       const double* targets, size_t B, double train_frac, int max_comp, int rule,
                                                       const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
@@ -2259,11 +2320,19 @@ static SmValues weighted_values(const double* V, size_t ldv, const double* w) {
     return sv;
 }
 
+// a product of an unweighted sample takes no weights
+static int weighted_equal_check(abc_ctx* ctx, const char* fn, const double* w, const Product& p) {
+    if (w && p.equal_weights())
+        ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: weights w are given, and the estimate is for entries of equal weight (pass w = NULL)", fn);
+    return ABC_OK;
+}
+
 // device pointers (p's arrays too)
 static int weighted_dev(abc_ctx* ctx, const char* fn, const double* V, size_t ldv, size_t K, size_t P, const double* w,
                         const Product& p) {
     ABC_TRY(weighted_values_check(ctx, fn, V, ldv, K, P));
     ABC_TRY(p.check(ctx, fn, P));
+    ABC_TRY(weighted_equal_check(ctx, fn, w, p));
     ABC_TRY(abc_ws_reserve(ctx, p.need(1, K, P) + 16 * 256));
     if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
     return p.launch(ctx, weighted_values(V, ldv, w), 1, K, P, fn);
@@ -2273,15 +2342,16 @@ static int weighted_dev(abc_ctx* ctx, const char* fn, const double* V, size_t ld
 static int weighted_host(abc_ctx* ctx, const char* fn, const double* V, size_t K, size_t P, const double* w, Product p) {
     ABC_TRY(weighted_values_check(ctx, fn, V, K, K, P));
     ABC_TRY(p.check(ctx, fn, P));
-    ABC_TRY(abc_ws_reserve(ctx, p.need(1, K, P) + (K * P + K) * 8 + p.stage_bytes(1, P) + 16 * 256));
+    ABC_TRY(weighted_equal_check(ctx, fn, w, p));
+    ABC_TRY(abc_ws_reserve(ctx, p.need(1, K, P) + (K * P + K) * 8 + p.stage_bytes(1, K, P) + 16 * 256));
     Stage s{ctx};
     const double* V_d = s.up(V, K * P);
     const double* w_d = w ? s.up(w, K) : nullptr;
-    const Product d = p.stage(s, 1, P);
+    const Product d = p.stage(s, 1, K, P);
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
     ABC_TRY(d.launch(ctx, weighted_values(V_d, K, w_d), 1, K, P, fn));
-    p.down(s, 1, P);
+    p.down(s, 1, K, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;
@@ -2329,6 +2399,17 @@ extern "C" int abc_weighted_draws_dev(abc_ctx* ctx, const double* V, size_t ldv,
 extern "C" int abc_weighted_draws(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_draws* dr) {
     CHECK_CTX(ctx);
     return weighted_host(ctx, "abc_weighted_draws", V, K, P, w, Product(dr));
+}
+
+extern "C" int abc_weighted_entropy_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w,
+                                        const abc_entropy* en) {
+    CHECK_CTX(ctx);
+    return weighted_dev(ctx, "abc_weighted_entropy_dev", V, ldv, K, P, w, Product(en));
+}
+
+extern "C" int abc_weighted_entropy(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_entropy* en) {
+    CHECK_CTX(ctx);
+    return weighted_host(ctx, "abc_weighted_entropy", V, K, P, w, Product(en));
 }
 
 extern "C" int abc_param_transf(abc_ctx* ctx, const double* V, size_t n, size_t P, int inverse, double* out) {

@@ -808,6 +808,45 @@ inline TargetDraws weighted_draws(const Mat2D& values, const std::vector<double>
     check(abc_weighted_draws(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &dr));
     return detail::target_draws(draws.data(), src.data(), bw.data(), ess, S, P);
 }
+// The same ranking followed by the k-nearest-neighbour entropy of every target's posterior in all P parameters at once
+// (abc_particle_ranking_pls_targets_entropy; the definition is in the header): the lower, the more concentrated.  k: 1..8; scale:
+// empty, or P positive values the parameters are divided by.  The estimate is for entries of equal weight: method 1 needs the
+// rectangular kernel (1, the default here).  Per target: H (NaN when K <= k or a value is not finite, -inf when zeros > 0), knn
+// (K: each entry's distance to its k-th nearest neighbour) and zeros (entries with k or more exact duplicates).
+struct TargetEntropy {
+    double H;
+    std::vector<double> knn;
+    size_t zeros;
+};
+inline std::vector<TargetEntropy> particle_ranking_PLS_targets_entropy(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                       const float_type train_frac, size_t K, int k = 4,
+                                                                       const std::vector<double>& scale = {}, int method = 0,
+                                                                       int kernel = 1) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols();
+    if (!scale.empty() && scale.size() != P) throw HipError(ABC_ERR_INVALID, "scale needs one entry per parameter");
+    std::vector<double> H(B), knn(B * K);
+    std::vector<uint64_t> zeros(B);
+    abc_entropy en = {k, scale.empty() ? nullptr : scale.data(), H.data(), knn.data(), zeros.data()};
+    check(abc_particle_ranking_pls_targets_entropy(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac,
+                                                   max_components_ref(), component_rule(), nullptr, K, method, kernel, nullptr,
+                                                   nullptr, nullptr, &en, nullptr));
+    std::vector<TargetEntropy> res(B);
+    for (size_t b = 0; b < B; b++)
+        res[b] = TargetEntropy{H[b], std::vector<double>(knn.begin() + b * K, knn.begin() + (b + 1) * K), (size_t)zeros[b]};
+    return res;
+}
+// The k-nearest-neighbour entropy of the rows of values (K x P) as one unweighted sample (abc_weighted_entropy).
+inline TargetEntropy knn_entropy(const Mat2D& values, int k = 4, const std::vector<double>& scale = {}) {
+    const size_t K = values.rows(), P = values.cols();
+    if (!scale.empty() && scale.size() != P) throw HipError(ABC_ERR_INVALID, "scale needs one entry per parameter");
+    TargetEntropy r{0.0, std::vector<double>(K), 0};
+    uint64_t zeros = 0;
+    abc_entropy en = {k, scale.empty() ? nullptr : scale.data(), &r.H, r.knn.data(), &zeros};
+    check(abc_weighted_entropy(context(), values.data(), K, P, nullptr, &en));
+    r.zeros = (size_t)zeros;
+    return r;
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

@@ -480,3 +480,32 @@ def weighted_draws(V, w=None, S=1000, smooth=False, seed=0, bw=None, bw_scale=1.
     None, src (S,) int64 or None, ess (0-d), bw (P,)) as device tensors."""
     return _weighted_product("draws", lambda lead, P, dev: _draws(S, smooth, seed, bw, bw_scale, stream, lead, P, dev, draws, src),
                              V, w, ctx)
+
+
+def _entropy(k, scale, lead, K, P, dev, knn):
+    """Device tensors for the entropy of prod(lead) targets with K entries of P parameters and the abc_entropy pointing at them
+    (scale: P host values or None)"""
+    sc = _lib._host_doubles(scale, P, "scale")
+    r = dict(H=torch.empty(lead, dtype=torch.float64, device=dev),
+             knn=torch.empty(lead + (K,), dtype=torch.float64, device=dev) if knn else None,
+             zeros=torch.empty(lead, dtype=torch.int64, device=dev))
+    d = _lib.Entropy(int(k), sc.ctypes.data if sc is not None else None, _ptr(r["H"]), _ptr(r["knn"]), _ptr(r["zeros"]))
+    return d, r, (sc,)
+
+
+def rank_targets_entropy(X, model, A, targets, K, Y, k=4, scale=None, method=_lib.POSTERIOR_REJECTION,
+                         kernel=_lib.KERNEL_RECTANGULAR, exclude=None, dist=False, adjust=(), knn=True, ctx=None):
+    """rank_targets followed by the k-nearest-neighbour entropy of every target's posterior in all P parameters at once
+    (abc_rank_targets_entropy_dev; method 0 rejection, 1 loclinear; the definition is in the header).  k: 1..8; scale: P positive
+    host values the parameters are divided by, or None.  The estimate is for entries of equal weight: method 1 needs the
+    rectangular kernel (the default here), and the context may hold no row importance weights.  Returns dict(idx (B, K) int64,
+    dist (B, K) or None, H (B,), knn (B, K) or None, zeros (B,) int64, and the adjust members)."""
+    return _rank_targets_product("entropy", lambda lead, P, dev: _entropy(k, scale, lead, K, P, dev, knn), X, model, A, targets, K, Y,
+                                 method, kernel, exclude, dist, adjust, ctx)
+
+
+def weighted_entropy(V, w=None, k=4, scale=None, knn=True, ctx=None):
+    """The k-nearest-neighbour entropy of the K rows of P columns as one unweighted sample (abc_weighted_entropy_dev).  V: (P, K)
+    holder as weighted_summary's; w must be None (the library refuses weights); the other arguments as rank_targets_entropy.
+    Returns dict(H (0-d), knn (K,) or None, zeros (0-d) int64) as device tensors."""
+    return _weighted_product("entropy", lambda lead, P, dev: _entropy(k, scale, lead, V.shape[1], P, dev, knn), V, w, ctx)

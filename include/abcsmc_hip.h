@@ -927,6 +927,61 @@ int abc_weighted_draws_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, 
 /* HOST-pointer form: V is K x P column-major (ldv = K); w and dr's arrays in host memory. */
 int abc_weighted_draws(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_draws* dr);
 
+/* ---- posterior entropy of the batched ranking: the k-nearest-neighbour estimate ------------------------------------------------
+ * One number per target that says how concentrated its posterior is in all P parameters at once: the Kozachenko-Leonenko
+ * k-nearest-neighbour entropy of the target's K entries, in the form of Singh et al. (2003) that the minimum-entropy criterion
+ * of Nunes & Balding (2010) uses to choose summary statistics (abctools: AS.select, nn.ent).  It has NOT been checked against
+ * abctools.  A Gaussian entropy from the joint product's covariance is no substitute for skewed, bounded or multimodal posteriors.
+ * For one target the entries are e = 0..K-1 in the ranking's row order and their values v_e[j] are those of the products above,
+ * bit for bit (method 0 rejection: the Y rows; method 1 loclinear: theta*_e, with the transforms, the variance correction and
+ * the ridge adjustment when set; generic: V[e + ldv j]).  With n = K:
+ *   scaled value  u_e[j] = v_e[j] / scale[j], a division (a generic call on a matrix divided beforehand gives the same bits);
+ *                 without scale u_e[j] = v_e[j].
+ *   distance      d2(e, f): acc = 0, then acc = fma(dl_j, dl_j, acc) for j ascending, dl_j = u_e[j] - u_f[j].
+ *   neighbour     rho2_e = the k-th smallest of d2(e, f) over f != e; f != e is decided by position, not by value.
+ *                 knn[e] = sqrt(rho2_e).
+ *   entropy       H = c + coef S, S = sum_e log rho2_e, coef = P / (2 n) (one rounding) and
+ *                 c = (P / 2) log pi - lgamma(P / 2 + 1) - psi(k) + log n, psi(k) = -gamma + sum_{m < k} 1 / m, made on the host in
+ *                 double.  S is taken in a fixed order that depends on K only (entry e belongs to e mod 256; each class is summed
+ *                 with e ascending, then the 256 class sums by a binary tree).
+ *   zeros         the number of entries with rho2_e == 0, that is k or more exact duplicates; when zeros > 0, H = -inf.
+ *   too few       K <= k: H = NaN, the target's knn NaN, zeros 0.
+ *   bad           a non-finite scaled value among a target's entries makes that target's H and knn NaN and its zeros 0.  The
+ *                 other targets are unaffected.  (Finite values whose distance overflows give rho2 = +inf the ordinary way.)
+ * No floating-point atomics are used.  A target's outputs are the same bits on a repeat run, alone (B = 1) and in any batch,
+ * through the device and host entry points, and whichever output members are asked for.  knn of a row-permuted generic V is the
+ * permuted knn, bit for bit; H is not, because the order of its sum moves.
+ * The estimator is for an unweighted sample, so the entries' weights must all be equal: ABC_ERR_UNSUPPORTED, with a message that
+ * says which, for method 1 with the Epanechnikov kernel (pass the rectangular kernel), for a ranking call while row importance
+ * weights are set on the context, and for a generic call with w non-NULL.  There is no entry for tolerance paths: a smaller
+ * tolerance lowers the entropy almost by construction.
+ * Layout: H [b], knn [b][e], zeros [b]; the generic entries have one b.  Limits as the summaries': A <= 64, P <= 1024; K is
+ * limited by the workspace alone (B K (P + 1) doubles). */
+typedef struct {
+    int k;                 /* 1..8; abctools uses 4                                              */
+    const double* scale;   /* optional, P finite values > 0, HOST memory in every entry          */
+    double* H;             /* [b]                                                                */
+    double* knn;           /* [b][e], B x K: distance to the k-th nearest neighbour              */
+    uint64_t* zeros;       /* [b]                                                                */
+} abc_entropy;             /* at least one output required; memory as the entry's other arrays   */
+/* Device pointers; the arguments of abc_rank_targets_draws_dev with en in place of dr.  idx, dist and adj are optional and
+ * receive the bits of the plain calls.  Besides the ranking's, the adjustment's and the method / kernel checks, ABC_ERR_INVALID
+ * for NULL en, k outside 1..8, every output member NULL and a scale entry that is <= 0 or non-finite; ABC_ERR_UNSUPPORTED as
+ * above. */
+int abc_rank_targets_entropy_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M,
+                                 size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                 const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                 const abc_adjust_out* adj, const abc_entropy* en);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_draws); every array of adj and en in host memory. */
+int abc_particle_ranking_pls_targets_entropy(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                             const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                             const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                             double* dist, const abc_adjust_out* adj, const abc_entropy* en, int32_t* ncomp);
+/* The same of P given columns of K values (as abc_weighted_draws_dev, with its checks of V, ldv, K and P); w must be NULL. */
+int abc_weighted_entropy_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w, const abc_entropy* en);
+/* HOST-pointer form: V is K x P column-major (ldv = K); en's arrays in host memory. */
+int abc_weighted_entropy(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_entropy* en);
+
 /* ---- Box-Cox transform of the metrics: the skewness search and the transform (ABC::optimize_box_cox, AbcUtil.cpp:89-109) ---------
  * PLS is linear; simulated metrics (counts, sizes, durations) are positive and right-skewed.  The reference searches, per metric, a
  * grid of exponents for the lambda whose transform (x^lambda - 1) / lambda has the smallest |skewness| (its ranking carries the
