@@ -12,14 +12,15 @@
 #include <stdlib.h>
 
 #include "abc_internal.h"
+#include "gram_plan.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-constexpr int TR = 128;      // rows per tile
-constexpr int TRP = TR + 2;  // LDS column stride in doubles (== 2 mod 32 -> conflict-free b64 reads)
+constexpr int TR = GRAM_TR;    // rows per tile
+constexpr int TRP = GRAM_TRP;  // LDS column stride in doubles (== 2 mod 32 -> conflict-free b64 reads)
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -36,12 +37,12 @@ __device__ __forceinline__ double wave_sum(double v) {
 template <int C, int CY>
 struct GramDims {
     static constexpr int C16 = 16 * C;
-    static constexpr int NBLK = C * (C + 1) / 2 - CY * (CY + 1) / 2;
-    static constexpr int NW = (C <= 3) ? 8 : 4;
+    static constexpr int NBLK = gram_nblk(C, CY);
+    static constexpr int NW = gram_vgpr_nw(C);
     static constexpr int NT = 64 * NW;
     static constexpr int NI = 16 * C / NW;             // 16-byte vectors per thread per tile
-    static constexpr int PSZ = NBLK * 256 + 2 * C16;   // doubles per work-group partial record
-    static constexpr int LDS_D = (C16 * TRP > PSZ) ? C16 * TRP : PSZ;
+    static constexpr int PSZ = gram_psz(C, CY);        // doubles per work-group partial record
+    static constexpr int LDS_D = gram_vgpr_lds_d(C, CY);
     static constexpr int EPT = (NBLK * 256 + NT - 1) / NT;   // partial-record elements per thread
     static constexpr int IQ = 16 * (C - CY) / NW;            // staged columns i >= IQ may lie in a skipped Y'Y block
 };
@@ -213,10 +214,10 @@ __global__ __launch_bounds__((GramDims<C, CY>::NT)) void k_gram(const double* __
 template <int C, int CY, int NW, int R = 3>
 struct GramDimsDma {
     static constexpr int C16 = 16 * C;
-    static constexpr int NBLK = C * (C + 1) / 2 - CY * (CY + 1) / 2;
+    static constexpr int NBLK = gram_nblk(C, CY);
     static constexpr int NT = 64 * NW;
     static constexpr int NI = C16 / NW;                 // DMA instructions (one column x 128 rows) per wave per tile
-    static constexpr int PSZ = NBLK * 256 + 2 * C16;    // same partial record as k_gram
+    static constexpr int PSZ = gram_psz(C, CY);         // same partial record as k_gram
     static constexpr int BUF = C16 * TRP;
     static constexpr int EPT = (NBLK * 256 + NT - 1) / NT;
     static constexpr int LDS_D = R * BUF;               // ring of R tiles: R - 1 DMAs in flight behind the one being read
@@ -423,7 +424,7 @@ __global__ __launch_bounds__((GramDimsDma<C, CY, NW>::NT)) void k_gram_dma(
 // waves per SIMD need rings of at most 18 KB per wave: wave-private chunks of EIGHT rows (64-row tiles, three-chunk rings of
 // 6 KB per wave at 96 columns).  DMA instruction i of a chunk brings the 16 columns of MFMA block i: lane l fetches rows
 // 2 (l >> 4), +1 of column 16 i + (l & 15), 64-byte pieces of a column (the other half of the 128-byte line goes to the
-// neighbouring wave of the same work-group at the same time: the loads are therefore NOT non-temporal, see run_gram_dma8); in LDS that is element (column c, row r) of block i at
+// neighbouring wave of the same work-group at the same time: the loads are therefore NOT non-temporal, see GRAM_DMA8_K); in LDS that is element (column c, row r) of block i at
 // 128 i + 2 c + 32 (r >> 1) + (r & 1), so the operand read of k-step s (lane (cl, q) -> row 4 s + q) covers 64 consecutive
 // doubles: conflict-free without a swizzle.  Everything else (shift at operand read, masks, column sums, epilogue) as above.
 template <int C, int CY>
@@ -570,12 +571,12 @@ __global__ __launch_bounds__(512) void k_gram_dma8(const double* __restrict__ X,
 template <int C, int CY>
 struct GramWide {
     static constexpr int C16 = 16 * C;
-    static constexpr int NBLK = C * (C + 1) / 2 - CY * (CY + 1) / 2;
-    static constexpr int NW = 8, NT = 512, TRW = 64, TRPW = TRW + 2;
+    static constexpr int NBLK = gram_nblk(C, CY);
+    static constexpr int NW = 8, NT = 512, TRW = GRAM_TRW, TRPW = TRW + 2;
     static constexpr int NI = C;                          // one column of every 16-column block per thread and tile
-    static constexpr int PSZ = NBLK * 256 + 2 * C16;      // same partial record as k_gram
+    static constexpr int PSZ = gram_psz(C, CY);           // same partial record as k_gram
     static constexpr int NBW = (NBLK + NW - 1) / NW;      // blocks per wave
-    static constexpr int LDS_D = C16 * TRPW;
+    static constexpr int LDS_D = gram_wide_lds_d(C);
 };
 template <int C, int CY>
 __global__ __launch_bounds__(512) void k_gram_wide(const double* __restrict__ X, const double* __restrict__ Y, size_t ldx, size_t ldy,
@@ -710,27 +711,21 @@ template <int C, int CY>
 struct GramI8 {
     static constexpr int C16 = 16 * C;
     static constexpr int CB = (C + 1) / 2;                       // 32-column super-blocks
-    static constexpr int C32 = 32 * CB;
-    static constexpr int NBLK = C * (C + 1) / 2 - CY * (CY + 1) / 2;
-    static constexpr int PSZ = NBLK * 256 + 2 * C16;             // the partial record of k_gram
-    static constexpr int NT = 512, NW = 8, TRW = 32;             // a tile = one 32-row step of the i8 MFMA
+    static constexpr int C32 = gram_i8_c32(C);
+    static constexpr int NBLK = gram_nblk(C, CY);
+    static constexpr int PSZ = gram_psz(C, CY);                  // the partial record of k_gram
+    static constexpr int NT = 512, NW = 8, TRW = GRAM_TRI;       // a tile = one 32-row step of the i8 MFMA
     static constexpr int NR = (C32 + 63) / 64;                   // conversion rounds per tile: a thread takes (column 64 r + t / 8, rows 4 (t % 8) .. + 3)
     static constexpr int DPW = (C32 / 4 + NW - 1) / NW;          // LDS-DMA instructions (1 KB each: 4 columns x 16 row pairs) per wave and tile, at most
     static constexpr int CS = 32;                                // bytes of a (byte plane, column) in LDS: 32 rows, the two 16-byte halves swapped
     //                                                              in columns 4..7 mod 8 (b128 operand reads and the conversion's b32 stores conflict-free)
-    static constexpr int PLANE = C32 * CS;
+    static constexpr int PLANE = gram_i8_plane(C);
     static constexpr bool skip_last = (2 * (CB - 1) >= C - CY);  // the last diagonal tile holds Y'Y / padding only
     static constexpr int NTILE = CB * (CB + 1) / 2 - (skip_last ? 1 : 0);
     static constexpr int TPW = (NTILE + NW - 1) / NW;            // tiles per wave
-    // two or three raw tiles (LDS-DMA targets: the real columns only, [column][16 row pairs]), TWO sets of byte planes, a 16-byte
-    // record per column (shift, high words of magic and limit), three sets of far flags (32 rows + any); the running column sums
-    // and sums of squares live in registers (a thread's (column, four rows) slots are the same in every tile) and pass through
-    // the raw tiles' space once, at the end
-    static constexpr int FIXED_B = 8 * PLANE + C32 * 16 + 3 * 48 + 256;         // (+ 256 zero bytes: the "raw column" of the padding columns)
-    static constexpr int LDS_MAX = 160 * 1024;
-    static int raw_bytes(int cols) { return ((cols + 3) / 4) * 1024; }
-    static int raw_tiles(int cols) { return FIXED_B + 3 * raw_bytes(cols) <= LDS_MAX ? 3 : 2; }          // (two: 157..160 columns)
-    static int lds_bytes(int cols) { return FIXED_B + raw_tiles(cols) * raw_bytes(cols); }
+    // the LDS: two or three raw tiles, two sets of byte planes, the columns' records, the far flags (gram_plan.h: gram_i8_lds_bytes)
+    static constexpr int FIXED_B = gram_i8_fixed_b(C);
+    static_assert(C32 == 32 * CB && PLANE == C32 * CS, "gram_plan.h has the byte planes of this kernel");
     static_assert(2 * C32 * 8 * 8 <= 2 * ((C16 - 15 + 3) / 4) * 1024, "the final sums fit the raw tiles");
     static constexpr int FLUSH = 512;                            // tiles (32-row steps) between two flushes of the i32 accumulators
 };
@@ -1218,179 +1213,138 @@ __global__ void k_pilot_shift(const double* __restrict__ X, const double* __rest
     if (lane == 0) shift[c] = (c < M + P && m > 0) ? s / (double)m : 0.0;
 }
 
-template <int C, int CY>
-int run_gram(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M,
-             size_t P, long long split, double* stats) {
-    using D = GramDims<C, CY>;
-    const StatsLayout L = stats_layout(M, P);
-    const long long ntr = split, nte = (long long)n - split;
-    const long long tiles = ((ntr > nte ? ntr : nte) + TR - 1) / TR + 1;
-    long long G = tiles / 2;           // >= 2 tiles per work-group amortise its prologue / epilogue
-    if (G < 1) G = 1;
-    const long long gmax = (D::NW == 8) ? 256 : 384;   // resident work-groups: 2 x 8 waves or 3 x 4 waves per CU
-    if (G > gmax) G = gmax;
-    const size_t pbytes = (size_t)2 * G * D::PSZ * sizeof(double);
-    double* partial = (double*)abc_ws_alloc(ctx, pbytes);
-    if (!partial) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted (%zu B)", pbytes);
-    const int vec_ok = (ldx % 2 == 0) && (ldy % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)Y & 15) == 0);
-    const size_t lds_bytes = (size_t)D::LDS_D * sizeof(double);
+// ---- the stage's kernel tables: which instance a plan (abc_gram_plan_of, gram_plan.h) gets, by [C][CY]; nullptr: no such instance ----
+using GramFn = decltype(&k_gram<1, 0>);               // k_gram and k_gram_wide: (.., partial, vec_ok)
+using GramDmaFn = decltype(&k_gram_dma8<4, 0>);       // k_gram_dma8 and k_gram_dma: (.., partial)
+using GramI8Fn = decltype(&k_gram_i8<6, 1>);
+using GramFarFn = decltype(&k_gram_far<6, 1>);
+using StatsReduceFn = decltype(&k_stats_reduce<1, 0>);
+static const GramFn GRAM_VGPR_K[11][3] = {
+    {},
+    {k_gram<1, 0>},
+    {k_gram<2, 0>, k_gram<2, 1>},
+    {k_gram<3, 0>, k_gram<3, 1>, k_gram<3, 2>},
+    {k_gram<4, 0>, k_gram<4, 1>, k_gram<4, 2>},
+    {k_gram<5, 0>, k_gram<5, 1>, k_gram<5, 2>},
+    {k_gram<6, 0>, k_gram<6, 1>, k_gram<6, 2>},
+};
+// k_gram_dma8's loads go WITHOUT the non-temporal hint (round 4).  Its DMA pieces are 64 bytes of a column -- half a 128-byte
+// line, the other half going to the neighbouring wave at about the same time --, and a line fetched with the hint is not kept
+// for the neighbour: FETCH_SIZE showed 13.5 GB for the 7.68 GB of configs[3]'s set (1.76 x), 8.25 GB without the hint, and the
+// kernel 2.25 -> 2.09 ms (it is bound by the fp64 matrix pipe first, so the doubled traffic cost 7 %, not 76 %).  The kernels
+// whose pieces are whole lines (k_gram_dma: 16 rows, k_gram_i8: 32 rows of a column) keep the hint.
+// (6, 0) needs 172 KB for its epilogue: no instance
+static const GramDmaFn GRAM_DMA8_K[11][3] = {
+    {}, {}, {}, {},
+    {k_gram_dma8<4, 0>, k_gram_dma8<4, 1>, k_gram_dma8<4, 2>},
+    {k_gram_dma8<5, 0>, k_gram_dma8<5, 1>, k_gram_dma8<5, 2>},
+    {nullptr, k_gram_dma8<6, 1>, k_gram_dma8<6, 2>},
+};
+static const GramFn GRAM_WIDE_K[11][3] = {
+    {}, {}, {}, {}, {}, {}, {}, {},
+    {k_gram_wide<8, 0>, k_gram_wide<8, 1>, k_gram_wide<8, 2>},
+    {k_gram_wide<9, 0>, k_gram_wide<9, 1>, k_gram_wide<9, 2>},
+    {k_gram_wide<10, 0>, k_gram_wide<10, 1>, k_gram_wide<10, 2>},
+};
+static const GramI8Fn GRAM_I8_K[11][3] = {
+    {}, {}, {}, {}, {}, {},
+    {nullptr, k_gram_i8<6, 1>, k_gram_i8<6, 2>},
+    {k_gram_i8<7, 0>, k_gram_i8<7, 1>, k_gram_i8<7, 2>},
+    {k_gram_i8<8, 0>, k_gram_i8<8, 1>, k_gram_i8<8, 2>},
+    {k_gram_i8<9, 0>, k_gram_i8<9, 1>, k_gram_i8<9, 2>},
+    {k_gram_i8<10, 0>, k_gram_i8<10, 1>, k_gram_i8<10, 2>},
+};
+static const GramFarFn GRAM_FAR_K[11][3] = {
+    {}, {}, {}, {}, {}, {},
+    {nullptr, k_gram_far<6, 1>, k_gram_far<6, 2>},
+    {k_gram_far<7, 0>, k_gram_far<7, 1>, k_gram_far<7, 2>},
+    {k_gram_far<8, 0>, k_gram_far<8, 1>, k_gram_far<8, 2>},
+    {k_gram_far<9, 0>, k_gram_far<9, 1>, k_gram_far<9, 2>},
+    {k_gram_far<10, 0>, k_gram_far<10, 1>, k_gram_far<10, 2>},
+};
+// the reduce of every instance above (the grouped kernels': (6, 0))
+static const StatsReduceFn STATS_REDUCE_K[11][3] = {
+    {},
+    {k_stats_reduce<1, 0>},
+    {k_stats_reduce<2, 0>, k_stats_reduce<2, 1>},
+    {k_stats_reduce<3, 0>, k_stats_reduce<3, 1>, k_stats_reduce<3, 2>},
+    {k_stats_reduce<4, 0>, k_stats_reduce<4, 1>, k_stats_reduce<4, 2>},
+    {k_stats_reduce<5, 0>, k_stats_reduce<5, 1>, k_stats_reduce<5, 2>},
+    {k_stats_reduce<6, 0>, k_stats_reduce<6, 1>, k_stats_reduce<6, 2>},
+    {k_stats_reduce<7, 0>, k_stats_reduce<7, 1>, k_stats_reduce<7, 2>},
+    {k_stats_reduce<8, 0>, k_stats_reduce<8, 1>, k_stats_reduce<8, 2>},
+    {k_stats_reduce<9, 0>, k_stats_reduce<9, 1>, k_stats_reduce<9, 2>},
+    {k_stats_reduce<10, 0>, k_stats_reduce<10, 1>, k_stats_reduce<10, 2>},
+};
+// the grouped path's two: a pair's 96 columns through a column-pointer table instead of X / Y
+static const GramDmaFn GRAM_GROUPED_DMA_K = k_gram_dma<6, 0, 4, true, 3, true>;
+static const GramFn GRAM_GROUPED_VGPR_K = k_gram<6, 0, true>;
+template <typename F>
+static F gram_slot(const F (&tab)[11][3], const abc_gram_plan& pl) { return pl.kC <= 10 ? tab[pl.kC][pl.kCY] : nullptr; }
+// (a plan that names an empty slot: abc_gram_plan_of never gives one -- tests/cxx/gram_plan_probe.cpp against the tables)
+static int gram_no_instance(abc_ctx* ctx, const abc_gram_plan& pl) {
+    ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "gram: no instance (%d, %d) of kernel family %d", pl.kC, pl.kCY, (int)pl.kernel);
+}
+
+// the plan's k_stats_reduce over the partial records: the sums of both partitions into the record
+static int run_stats_reduce(abc_ctx* ctx, const abc_gram_plan& pl, StatsReduceFn reduce, const double* partial, double* stats, size_t n) {
+    StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_STATS_REDUCE);
+    hipLaunchKernelGGL(reduce, dim3((pl.psz + 63) / 64, 2), dim3(64 * SR_SL), 0, ctx->stream, partial, pl.nrec, stats, pl.split,
+                       (long long)n - pl.split);
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+// The ONE launch body of the fp64 families: the plan's Gram kernel over the M + P columns of X and Y -- the grouped kernels: over the
+// 96 of a pair's column-pointer table, which X then is --, then the reduce of its partial records into `stats` (whose shift it reads)
+static int run_gram_fp64(abc_ctx* ctx, const abc_gram_plan& pl, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, int M,
+                         int P, double* stats) {
+    const GramFn with_vec = pl.kernel == GRAM_VGPR ? gram_slot(GRAM_VGPR_K, pl) : pl.kernel == GRAM_WIDE ? gram_slot(GRAM_WIDE_K, pl)
+                            : pl.kernel == GRAM_GROUPED_VGPR ? GRAM_GROUPED_VGPR_K : nullptr;
+    const GramDmaFn dma = pl.kernel == GRAM_DMA8 ? gram_slot(GRAM_DMA8_K, pl) : pl.kernel == GRAM_GROUPED_DMA ? GRAM_GROUPED_DMA_K : nullptr;
+    const StatsReduceFn reduce = gram_slot(STATS_REDUCE_K, pl);
+    if ((!with_vec && !dma) || !reduce) return gram_no_instance(ctx, pl);
+    double* partial = (double*)abc_ws_alloc(ctx, pl.partial_bytes);
+    if (!partial) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted (%zu B)", pl.partial_bytes);
+    const double* shift = stats + stats_layout(M, P).off_shift;
     // per device and cheap: set on every launch (a function-level flag would be wrong for a second device)
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram<C, CY>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_bytes));
+    ABC_HIP(ctx, hipFuncSetAttribute(with_vec ? (const void*)with_vec : (const void*)dma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
     {
         StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_GRAM);
-        hipLaunchKernelGGL((k_gram<C, CY>), dim3((unsigned)G, 2), dim3(D::NT), lds_bytes, ctx->stream, X, Y, ldx, ldy, (int)M,
-                           (int)P, (long long)n, split, stats + L.off_shift, partial, vec_ok);
+        const dim3 grid((unsigned)pl.G, 2), block(pl.threads);
+        if (with_vec)
+            hipLaunchKernelGGL(with_vec, grid, block, pl.lds, ctx->stream, X, Y, ldx, ldy, M, P, (long long)n, pl.split, shift, partial, (int)pl.vec_ok);
+        else
+            hipLaunchKernelGGL(dma, grid, block, pl.lds, ctx->stream, X, Y, ldx, ldy, M, P, (long long)n, pl.split, shift, partial);
     }
     ABC_HIP(ctx, hipGetLastError());
-    StageTimer tm2(ctx, ctx->in_mvn ? -1 : ST_STATS_REDUCE);
-    hipLaunchKernelGGL((k_stats_reduce<C, CY>), dim3((D::PSZ + 63) / 64, 2), dim3(64 * SR_SL), 0, ctx->stream, partial, (int)G,
-                       stats, ntr, nte);
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
+    return run_stats_reduce(ctx, pl, reduce, partial, stats, n);
 }
 
-template <int C, int CY, int NW, bool PRIV, int R = 3, bool TABLE = false>
-int run_gram_dma(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M,
-                 size_t P, long long split, double* stats) {
-    using D = GramDimsDma<C, CY, NW, R>;
-    const StatsLayout L = stats_layout(M, P);
-    const long long ntr = split, nte = (long long)n - split;
-    constexpr int TRK = PRIV ? 16 * NW : TR;          // rows per tile (k_gram_dma)
-    const long long tiles = ((ntr > nte ? ntr : nte) + TRK - 1) / TRK + 1;
-    long long G = tiles / 2;
-    if (G < 1) G = 1;
-    if (G > 128) G = 128;              // 150 KB of LDS: one work-group per CU, 2 partitions x 128
-    const size_t pbytes = (size_t)2 * G * D::PSZ * sizeof(double);
-    double* partial = (double*)abc_ws_alloc(ctx, pbytes);
-    if (!partial) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted (%zu B)", pbytes);
-    // wave-private staging: NW rings of R chunks of 16 rows x C16 columns; the epilogue stages four waves' accumulators
-    constexpr size_t epi4 = (size_t)4 * D::NBLK * 256;          // the epilogue stages four waves' accumulators (two if that is too much)
-    constexpr size_t lds_priv = (size_t)NW * R * D::C16 * 16, lds_epi = (epi4 * sizeof(double) <= 160 * 1024) ? epi4 : epi4 / 2,
-                     lds_cs = (size_t)C * D::NT;
-    constexpr size_t lds_pmax = lds_priv > lds_epi ? (lds_priv > lds_cs ? lds_priv : lds_cs) : (lds_epi > lds_cs ? lds_epi : lds_cs);
-    const size_t lds_bytes = (PRIV ? lds_pmax : (size_t)D::LDS_D) * sizeof(double);
-    static_assert(!PRIV || lds_pmax * sizeof(double) <= 160 * 1024, "k_gram_dma: ring + epilogue exceed the 160 KB of LDS");
-    // per device and cheap: set on every launch (a function-level flag would be wrong for a second device)
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram_dma<C, CY, NW, PRIV, R, TABLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds_bytes));
+static int run_gram_i8(abc_ctx* ctx, const abc_gram_plan& pl, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, int M,
+                       int P, double* stats) {
+    const GramI8Fn limbs = gram_slot(GRAM_I8_K, pl);
+    const GramFarFn far = gram_slot(GRAM_FAR_K, pl);
+    const StatsReduceFn reduce = gram_slot(STATS_REDUCE_K, pl);
+    if (!limbs || !far || !reduce) return gram_no_instance(ctx, pl);
+    double* partial = (double*)abc_ws_alloc(ctx, pl.partial_bytes);
+    int* escale = (int*)abc_ws_alloc(ctx, pl.escale_bytes);
+    unsigned long long* far_mask = (unsigned long long*)abc_ws_alloc(ctx, pl.far_mask_bytes);
+    unsigned long long* far_sum = (unsigned long long*)abc_ws_alloc(ctx, pl.far_sum_bytes);
+    if (!partial || !escale || !far_mask || !far_sum) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted (%zu B)", pl.partial_bytes);
+    const double* shift = stats + stats_layout(M, P).off_shift;
+    ABC_HIP(ctx, hipFuncSetAttribute((const void*)limbs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
     {
         StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_GRAM);
-        hipLaunchKernelGGL((k_gram_dma<C, CY, NW, PRIV, R, TABLE>), dim3((unsigned)G, 2), dim3(D::NT), lds_bytes, ctx->stream, X, Y, ldx,
-                           ldy, (int)M, (int)P, (long long)n, split, stats + L.off_shift, partial);
+        hipLaunchKernelGGL(k_pilot_scale, dim3((unsigned)(16 * pl.C)), dim3(1024), 0, ctx->stream, X, Y, ldx, ldy, M, P, (long long)n, shift, escale);
+        ABC_HIP(ctx, hipMemsetAsync(far_sum, 0, pl.far_sum_bytes, ctx->stream));
+        hipLaunchKernelGGL(limbs, dim3((unsigned)pl.G, 2), dim3(pl.threads), pl.lds, ctx->stream, X, Y, ldx, ldy, M, P, (long long)n, pl.split, shift,
+                           (const int*)escale, partial, far_mask, far_sum, pl.tmax, pl.nraw);
+        hipLaunchKernelGGL(far, dim3((unsigned)(pl.nblk + 1), 2), dim3(256), 0, ctx->stream, X, Y, ldx, ldy, M, P, (long long)n, pl.split, shift,
+                           partial, pl.G, (const unsigned long long*)far_mask, (const unsigned long long*)far_sum, pl.tmax);
     }
     ABC_HIP(ctx, hipGetLastError());
-    StageTimer tm2(ctx, ctx->in_mvn ? -1 : ST_STATS_REDUCE);
-    hipLaunchKernelGGL((k_stats_reduce<C, CY>), dim3((D::PSZ + 63) / 64, 2), dim3(64 * SR_SL), 0, ctx->stream, partial, (int)G,
-                       stats, ntr, nte);
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
-}
-
-template <int C, int CY>
-int run_gram_dma8(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
-                  long long split, double* stats) {
-    using D = GramDimsDma<C, CY, 8, 3>;
-    const StatsLayout L = stats_layout(M, P);
-    const long long ntr = split, nte = (long long)n - split;
-    const long long tiles = ((ntr > nte ? ntr : nte) + 63) / 64 + 1;
-    long long G = tiles / 2;
-    if (G < 1) G = 1;
-    if (G > 128) G = 128;              // ~150 KB of LDS: one work-group (eight waves) per CU, 2 partitions x 128
-    const size_t pbytes = (size_t)2 * G * D::PSZ * sizeof(double);
-    double* partial = (double*)abc_ws_alloc(ctx, pbytes);
-    if (!partial) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted (%zu B)", pbytes);
-    constexpr size_t epi4 = (size_t)4 * D::NBLK * 256;
-    constexpr size_t lds_ring = (size_t)8 * 3 * D::C16 * 8, lds_epi = (epi4 * sizeof(double) <= 160 * 1024) ? epi4 : epi4 / 2,
-                     lds_cs = (size_t)C * 512;
-    constexpr size_t lds_max = lds_ring > lds_epi ? (lds_ring > lds_cs ? lds_ring : lds_cs) : (lds_epi > lds_cs ? lds_epi : lds_cs);
-    static_assert(lds_max * sizeof(double) <= 160 * 1024, "k_gram_dma8: ring / epilogue exceed the 160 KB of LDS");
-    const size_t lds_bytes = lds_max * sizeof(double);
-    // This kernel's loads go WITHOUT the non-temporal hint (round 4).  Its DMA pieces are 64 bytes of a column -- half a 128-byte
-    // line, the other half going to the neighbouring wave at about the same time --, and a line fetched with the hint is not kept
-    // for the neighbour: FETCH_SIZE showed 13.5 GB for the 7.68 GB of configs[3]'s set (1.76 x), 8.25 GB without the hint, and the
-    // kernel 2.25 -> 2.09 ms (it is bound by the fp64 matrix pipe first, so the doubled traffic cost 7 %, not 76 %).  The kernels
-    // whose pieces are whole lines (k_gram_dma: 16 rows, k_gram_i8: 32 rows of a column) keep the hint.
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram_dma8<C, CY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    {
-        StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_GRAM);
-        hipLaunchKernelGGL((k_gram_dma8<C, CY>), dim3((unsigned)G, 2), dim3(512), lds_bytes, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P,
-                           (long long)n, split, stats + L.off_shift, partial);
-    }
-    ABC_HIP(ctx, hipGetLastError());
-    StageTimer tm2(ctx, ctx->in_mvn ? -1 : ST_STATS_REDUCE);
-    hipLaunchKernelGGL((k_stats_reduce<C, CY>), dim3((D::PSZ + 63) / 64, 2), dim3(64 * SR_SL), 0, ctx->stream, partial, (int)G, stats, ntr,
-                       nte);
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
-}
-
-template <int C, int CY>
-int run_gram_wide(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
-                  long long split, double* stats) {
-    using D = GramWide<C, CY>;
-    const StatsLayout L = stats_layout(M, P);
-    const long long ntr = split, nte = (long long)n - split;
-    const long long tiles = ((ntr > nte ? ntr : nte) + D::TRW - 1) / D::TRW + 1;
-    long long G = tiles / 2;
-    if (G < 1) G = 1;
-    if (G > 128) G = 128;              // 84 KB of LDS and 512 threads: one work-group per CU, 2 partitions x 128
-    const size_t pbytes = (size_t)2 * G * D::PSZ * sizeof(double);
-    double* partial = (double*)abc_ws_alloc(ctx, pbytes);
-    if (!partial) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted (%zu B)", pbytes);
-    const int vec_ok = (ldx % 2 == 0) && (ldy % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)Y & 15) == 0);
-    const size_t lds_bytes = (size_t)D::LDS_D * sizeof(double);
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram_wide<C, CY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    {
-        StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_GRAM);
-        hipLaunchKernelGGL((k_gram_wide<C, CY>), dim3((unsigned)G, 2), dim3(D::NT), lds_bytes, ctx->stream, X, Y, ldx, ldy, (int)M,
-                           (int)P, (long long)n, split, stats + L.off_shift, partial, vec_ok);
-    }
-    ABC_HIP(ctx, hipGetLastError());
-    StageTimer tm2(ctx, ctx->in_mvn ? -1 : ST_STATS_REDUCE);
-    hipLaunchKernelGGL((k_stats_reduce<C, CY>), dim3((D::PSZ + 63) / 64, 2), dim3(64 * SR_SL), 0, ctx->stream, partial, (int)G,
-                       stats, ntr, nte);
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
-}
-
-template <int C, int CY>
-int run_gram_i8(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
-                long long split, double* stats) {
-    using D = GramI8<C, CY>;
-    const StatsLayout L = stats_layout(M, P);
-    const long long ntr = split, nte = (long long)n - split;
-    const long long tmax = ((ntr > nte ? ntr : nte) + D::TRW - 1) / D::TRW + 2;      // tiles of a partition (t0 may start a row early)
-    long long G = tmax / 2;
-    if (G < 1) G = 1;
-    if (G > 127) G = 127;              // 154 KB of LDS, 512 threads with ~250 registers: one work-group per CU; with k_gram_far's record
-                                       // 128 records per partition (k_stats_reduce splits them evenly over its 16 slices)
-    const size_t pbytes = (size_t)2 * (G + 1) * D::PSZ * sizeof(double);
-    double* partial = (double*)abc_ws_alloc(ctx, pbytes);
-    int* escale = (int*)abc_ws_alloc(ctx, (size_t)D::C32 * sizeof(int));
-    const size_t sumw = (size_t)((tmax + 63) / 64);
-    unsigned long long* far_mask = (unsigned long long*)abc_ws_alloc(ctx, (size_t)2 * tmax * 8);
-    unsigned long long* far_sum = (unsigned long long*)abc_ws_alloc(ctx, (2 * sumw + 1) * 8);
-    if (!partial || !escale || !far_mask || !far_sum) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted (%zu B)", pbytes);
-    const int lds_b = D::lds_bytes((int)(M + P)), nraw = D::raw_tiles((int)(M + P));
-    ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram_i8<C, CY>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b));
-    {
-        StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_GRAM);
-        hipLaunchKernelGGL(k_pilot_scale, dim3((unsigned)D::C16), dim3(1024), 0, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P, (long long)n,
-                           (const double*)(stats + L.off_shift), escale);
-        ABC_HIP(ctx, hipMemsetAsync(far_sum, 0, (2 * sumw + 1) * 8, ctx->stream));
-        hipLaunchKernelGGL((k_gram_i8<C, CY>), dim3((unsigned)G, 2), dim3(D::NT), (size_t)lds_b, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P,
-                           (long long)n, split, (const double*)(stats + L.off_shift), (const int*)escale, partial, far_mask, far_sum, tmax, nraw);
-        hipLaunchKernelGGL((k_gram_far<C, CY>), dim3((unsigned)(D::NBLK + 1), 2), dim3(256), 0, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P,
-                           (long long)n, split, (const double*)(stats + L.off_shift), partial, (int)G, (const unsigned long long*)far_mask,
-                           (const unsigned long long*)far_sum, tmax);
-    }
-    ABC_HIP(ctx, hipGetLastError());
-    StageTimer tm2(ctx, ctx->in_mvn ? -1 : ST_STATS_REDUCE);
-    hipLaunchKernelGGL((k_stats_reduce<C, CY>), dim3((D::PSZ + 63) / 64, 2), dim3(64 * SR_SL), 0, ctx->stream, partial, (int)(G + 1),
-                       stats, ntr, nte);
-    ABC_HIP(ctx, hipGetLastError());
-    return ABC_OK;
+    return run_stats_reduce(ctx, pl, reduce, partial, stats, n);
 }
 
 // ---- wide sets (M+P > 96): column groups of <= 48, one k_gram<.,0,TABLE> launch per pair of groups ------------
@@ -1422,11 +1376,10 @@ __global__ __launch_bounds__(256) void k_group_scatter(const double* __restrict_
     }
 }
 
-int run_gram_grouped(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M,
-                     size_t P, long long split, double* stats) {
+static int run_gram_grouped(abc_ctx* ctx, const abc_gram_plan& pl, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy,
+                            size_t M, size_t P, double* stats) {
     const StatsLayout LB = stats_layout(M, P);
     const int ncol = (int)(M + P);
-    const int ng = (ncol + 47) / 48;
     const StatsLayout LL = stats_layout(96, 0);
     double* loc = (double*)abc_ws_alloc(ctx, LL.len * sizeof(double));
     const double** tab = (const double**)abc_ws_alloc(ctx, 96 * sizeof(double*));
@@ -1436,41 +1389,15 @@ int run_gram_grouped(abc_ctx* ctx, const double* X, const double* Y, size_t n, s
     // as every single-launch path leaves them (tests/test_gpu_stats.py fills the record with NaN first)
     ABC_HIP(ctx, hipMemsetAsync(stats + LB.off_sum[0], 0, (LB.len - LB.off_sum[0]) * sizeof(double), ctx->stream));
     const size_t ws_mark = ctx->ws_off;
-    for (int ga = 0; ga < ng; ga++)
-        for (int gb = ga + 1; gb < ng; gb++) {
+    for (int ga = 0; ga < pl.groups; ga++)
+        for (int gb = ga + 1; gb < pl.groups; gb++) {
             ctx->ws_off = ws_mark;                       // the per-launch partial records reuse the same arena space
             const int ga0 = 48 * ga, gan = ncol - ga0 < 48 ? ncol - ga0 : 48;
             const int gb0 = 48 * gb, gbn = ncol - gb0 < 48 ? ncol - gb0 : 48;
             hipLaunchKernelGGL(k_group_table, dim3(1), dim3(128), 0, ctx->stream, X, Y, ldx, ldy, (int)M, (int)P, ga0, gan,
                                gb0, gbn, stats + LB.off_shift, tab, loc + LL.off_shift, gmap, 96);
-            const bool dma_ok = (ldx % 2 == 0) && (ldy % 2 == 0) && (n % 2 == 0) && (((uintptr_t)X & 15) == 0) &&
-                                (((uintptr_t)Y & 15) == 0) && n >= 2;
-            if (dma_ok) {
-                // the pair's 96 columns through the four-wave LDS-DMA kernel (column-pointer table instead of X / Y)
-                ABC_TRY((run_gram_dma<6, 0, 4, true, 3, true>(ctx, (const double*)tab, nullptr, n, ldx, ldy, 96, 0, split, loc)));
-            } else {
-            using D = GramDims<6, 0>;
-            const long long ntr = split, nte = (long long)n - split;
-            const long long tiles = ((ntr > nte ? ntr : nte) + TR - 1) / TR + 1;
-            long long G = tiles / 2;
-            if (G < 1) G = 1;
-            if (G > 128) G = 128;                        // 100 KB of LDS: one work-group per CU
-            double* partial = (double*)abc_ws_alloc(ctx, (size_t)2 * G * D::PSZ * sizeof(double));
-            if (!partial) ABC_FAIL(ctx, ABC_ERR_NOMEM, "gram: workspace exhausted");
-            const int vec_ok = (ldx % 2 == 0) && (ldy % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)Y & 15) == 0);
-            const size_t lds_bytes = (size_t)D::LDS_D * sizeof(double);
-            // per device and cheap: set on every launch (a function-level flag would be wrong for a second device)
-            ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_gram<6, 0, true>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            {
-                StageTimer tm(ctx, ctx->in_mvn ? -1 : ST_GRAM);
-                hipLaunchKernelGGL((k_gram<6, 0, true>), dim3((unsigned)G, 2), dim3(D::NT), lds_bytes, ctx->stream,
-                                   (const double*)tab, (const double*)nullptr, ldx, ldy, 96, 0, (long long)n, split,
-                                   loc + LL.off_shift, partial, vec_ok);
-            }
-            hipLaunchKernelGGL((k_stats_reduce<6, 0>), dim3((D::PSZ + 63) / 64, 2), dim3(64 * SR_SL), 0, ctx->stream, partial,
-                               (int)G, loc, ntr, nte);
-            }
+            // the pair's 96 columns (column-pointer table instead of X / Y) through the plan's kernel: the four-wave LDS-DMA one, or k_gram
+            ABC_TRY(run_gram_fp64(ctx, pl, (const double*)tab, nullptr, n, ldx, ldy, 96, 0, loc));
             hipLaunchKernelGGL(k_group_scatter, dim3((96 * 96 + 255) / 256), dim3(256), 0, ctx->stream, loc, 96, gmap, stats,
                                (int)LB.C16);
             ABC_HIP(ctx, hipGetLastError());
@@ -1489,103 +1416,25 @@ int launch_stats_shift(abc_ctx* ctx, const double* X, const double* Y, size_t n,
     return ABC_OK;
 }
 
-// ---- which statistics kernel a set takes ------------------------------------------------------------------------------------------
-// ONE decision, for launch_stats_accumulate and for a caller that arranges its streams around the byte-limb kernel (abc_gram_takes_i8).
-// Up to 48 columns (C <= 3) the VGPR-staged k_gram is the default since its loads carry the non-temporal policy: 75 us against 84 us
-// for the LDS-DMA kernel at N = 1e6, M = 32, P = 16 (0.68 against 0.60 of the HBM peak inside a generation); 49..96 columns run the
-// eight-wave LDS-DMA variant (0.29 against 0.68 ms on the configs[3] shape).  LDS-DMA staging (dma_ok) needs 16-B aligned columns and
-// an even row count (row pairs never straddle the array end).
-// 4..6 column blocks (49..96 columns, e.g. BASELINE configs[3]: 64 metrics + 32 parameters): k_gram_dma8, EIGHT waves of
-// wave-private staging in 8-row chunks (two waves per SIMD keep the fp64 matrix pipe busy: 0.36 -> 0.29 ms on the configs[3]
-// shard against the four-wave, 16-row-chunk variant, which stays for the column-pointer-table mode of the grouped path).
-// (6, 0) needs 172 KB for its epilogue and stays on the VGPR-staged kernel.
-// 81..96 columns of a LARGE set (configs[3]: 64 metrics + 32 parameters, 1e7 rows) go through the byte-limb kernel of the wide
-// sets (k_gram_i8): 1.59 ms against k_gram_dma8's 1.99 at 1e7 rows x 96 columns (0.60 against 0.48 of HBM: the fp64
-// matrix pipe is 0.62 busy there), the same statistics to the byte products' error (section 4).  From 2e6 rows: where it was measured.
-// WHERE THE BYTE-LIMB KERNEL IS THE DEFAULT (round 6).  Its noise -- every value rounded to a 32-bit grid -- is harmless at the
-// Gram's own scale (4e-11 of sqrt(G_aa G_bb)) but not always at the LOADINGS: a component that fits noise works on cross
-// products sqrt(rows) below that scale, with close eigenvalues, and tests/fuzz/wide_model_fuzz.py found a used loading column
-// 4.3e-6 off the oracle's (fp64 kernels: 4e-10) at 66 000 training rows x 29 responses x 30 components -- BASELINE.json allows
-// 1e-6.  The error falls faster than 1 / rows: 64 fuzzed sets whose partitions hold 450 000 rows and more stay within 2.6e-7
-// (profiles/r06_wide_model_fuzz_big.json).  So ABC_GRAM_AUTO takes the kernel only where EVERY non-empty partition of the
-// WHOLE set (training / validation rows: ntr_set, nte_set) has at least 400 000 rows -- configs[4] (5e5 + 5e5), configs[3]
-// (5e6 + 5e6) -- and the fp64 kernels below that; ABC_GRAM_I8 is round 5's rule (200 000 rows in the whole set) for A/B runs and tests.
-// 8..10 column blocks: one launch, the Gram blocks dealt out to the waves of a work-group -- large sets on the byte-limb kernel on the
-// i8 matrix pipe (sums and the diagonal exact, off-diagonal products to ~1e-10 of sqrt(G_aa G_bb)); small ones, and all with
-// ABC_GRAM_FP64 (A/B runs, tests), on the fp64 matrix pipe (k_gram_wide).  (LDS-DMA staging: 16-byte aligned columns, an even row
-// count; from 200000 rows: the values are rounded to a 32-bit grid of 10 .. 19 sigma, noise of 3e-9 sigma per value that averages
-// out with the square root of the rows -- 1e-10 of sqrt(G_aa G_bb) at 35000 rows per partition, which the 32nd loading of a
-// 128-metric model amplifies to 2e-7; 4e-8 at 1e6 rows.)  7 blocks, 97..112 columns: the byte-limb kernel where it applies -- round
-// 5; the fp64 one-launch kernel spills at that width, so small sets of it stay on the grouped path, which reads every column twice.
-// (A rank whose shard the byte-limb kernel cannot take -- an odd row count, columns that are not 16-byte aligned, fewer than 4096
-// rows -- runs the fp64 kernel on ITS rows: the rows' rule is the same on every rank, dma_ok and n are about what can run.)
-// Wider sets, and the shapes without an instantiation ((1, 1), (2, 2): sets without metrics): column groups of 48, one launch per
-// pair of groups (every column is read ceil(columns / 48) - 1 times).
-enum GramKernel { GRAM_VGPR, GRAM_DMA8, GRAM_WIDE, GRAM_I8, GRAM_GROUPED };
-static GramKernel gram_kernel(size_t C, size_t CY, bool dma_ok, size_t n, size_t ntr_set, size_t nte_set, int gram_mode) {
-    const size_t rows_set = ntr_set + nte_set;
-    const size_t part_min = (ntr_set && nte_set) ? (ntr_set < nte_set ? ntr_set : nte_set) : (ntr_set ? ntr_set : nte_set);
-    const bool i8_rows = gram_mode == ABC_GRAM_I8 ? rows_set >= 200000 : (gram_mode == ABC_GRAM_AUTO && part_min >= 400000);
-    const bool i8_ok = i8_rows && dma_ok && n >= 4096;
-    if (C >= 7) return C > 10 ? GRAM_GROUPED : i8_ok ? GRAM_I8 : C == 7 ? GRAM_GROUPED : GRAM_WIDE;
-    if (C == 6 && CY >= 1 && i8_ok && rows_set >= 2000000) return GRAM_I8;
-    if (C >= 4 && dma_ok && !(C == 6 && CY == 0)) return GRAM_DMA8;
-    return (C >= 3 || (C >= 1 && CY < C)) ? GRAM_VGPR : GRAM_GROUPED;
+// Which statistics kernel a set takes, and everything its launch needs: abc_gram_plan_of (gram_plan.h), the one owner of the decision
+static abc_gram_plan gram_plan_for(const abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
+                                   uint64_t row0, uint64_t n_train_global, size_t n_set) {
+    return abc_gram_plan_of({n, ldx, ldy, M, P, ((uintptr_t)X & 15) == 0, ((uintptr_t)Y & 15) == 0, row0, n_train_global, n_set, ctx->gram_mode});
 }
 
 // n_set (0: n): the rows of the whole set these n are a shard of; n_train_global: its training rows
-static GramKernel gram_kernel_for(const abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
-                                  uint64_t n_train_global, size_t n_set, size_t* C, size_t* CY) {
-    *C = (M + P + 15) / 16;
-    *CY = *C - (M + 15) / 16;           // trailing blocks without any metric column
-    if (*CY > 2) *CY = 2;
-    const bool dma_ok = (ldx % 2 == 0) && (ldy % 2 == 0) && (n % 2 == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)Y & 15) == 0) && n >= 2;
-    const size_t rows_set = n_set ? n_set : n;
-    const size_t ntr_set = n_train_global < rows_set ? (size_t)n_train_global : rows_set;
-    return gram_kernel(*C, *CY, dma_ok, n, ntr_set, rows_set - ntr_set, ctx->gram_mode);
-}
-
 bool abc_gram_takes_i8(const abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy, size_t M, size_t P,
                        uint64_t n_train_global, size_t n_set) {
-    size_t C, CY;
-    return gram_kernel_for(ctx, X, Y, n, ldx, ldy, M, P, n_train_global, n_set, &C, &CY) == GRAM_I8;
+    return gram_plan_for(ctx, X, Y, n, ldx, ldy, M, P, 0, n_train_global, n_set).kernel == GRAM_I8;
 }
 
 int launch_stats_accumulate(abc_ctx* ctx, const double* X, const double* Y, size_t n, size_t ldx, size_t ldy,
                             size_t M, size_t P, uint64_t row0, uint64_t n_train_global, double* stats, size_t n_set) {
-    long long split = 0;
-    if (n_train_global > row0) split = (long long)((n_train_global - row0) < n ? (n_train_global - row0) : n);
-    size_t C, CY;
-    const GramKernel kind = gram_kernel_for(ctx, X, Y, n, ldx, ldy, M, P, n_train_global, n_set, &C, &CY);
-#define GRAM_RUN(run, c, cy) if (C == c && CY == cy) return run<c, cy>(ctx, X, Y, n, ldx, ldy, M, P, split, stats)
-    switch (kind) {
-        case GRAM_I8:
-            GRAM_RUN(run_gram_i8, 6, 1); GRAM_RUN(run_gram_i8, 6, 2);
-            GRAM_RUN(run_gram_i8, 7, 0); GRAM_RUN(run_gram_i8, 7, 1); GRAM_RUN(run_gram_i8, 7, 2);
-            GRAM_RUN(run_gram_i8, 8, 0); GRAM_RUN(run_gram_i8, 8, 1); GRAM_RUN(run_gram_i8, 8, 2);
-            GRAM_RUN(run_gram_i8, 9, 0); GRAM_RUN(run_gram_i8, 9, 1); GRAM_RUN(run_gram_i8, 9, 2);
-            GRAM_RUN(run_gram_i8, 10, 0); GRAM_RUN(run_gram_i8, 10, 1); GRAM_RUN(run_gram_i8, 10, 2);
-            break;
-        case GRAM_DMA8:
-            GRAM_RUN(run_gram_dma8, 4, 0); GRAM_RUN(run_gram_dma8, 4, 1); GRAM_RUN(run_gram_dma8, 4, 2);
-            GRAM_RUN(run_gram_dma8, 5, 0); GRAM_RUN(run_gram_dma8, 5, 1); GRAM_RUN(run_gram_dma8, 5, 2);
-            GRAM_RUN(run_gram_dma8, 6, 1); GRAM_RUN(run_gram_dma8, 6, 2);
-            break;
-        case GRAM_WIDE:
-            GRAM_RUN(run_gram_wide, 8, 0); GRAM_RUN(run_gram_wide, 8, 1); GRAM_RUN(run_gram_wide, 8, 2);
-            GRAM_RUN(run_gram_wide, 9, 0); GRAM_RUN(run_gram_wide, 9, 1); GRAM_RUN(run_gram_wide, 9, 2);
-            GRAM_RUN(run_gram_wide, 10, 0); GRAM_RUN(run_gram_wide, 10, 1); GRAM_RUN(run_gram_wide, 10, 2);
-            break;
-        case GRAM_VGPR:
-            GRAM_RUN(run_gram, 1, 0); GRAM_RUN(run_gram, 2, 0); GRAM_RUN(run_gram, 2, 1);
-            GRAM_RUN(run_gram, 3, 0); GRAM_RUN(run_gram, 3, 1); GRAM_RUN(run_gram, 3, 2);
-            GRAM_RUN(run_gram, 4, 0); GRAM_RUN(run_gram, 4, 1); GRAM_RUN(run_gram, 4, 2);
-            GRAM_RUN(run_gram, 5, 0); GRAM_RUN(run_gram, 5, 1); GRAM_RUN(run_gram, 5, 2);
-            GRAM_RUN(run_gram, 6, 0); GRAM_RUN(run_gram, 6, 1); GRAM_RUN(run_gram, 6, 2);
-            break;
-        case GRAM_GROUPED:
-            break;
+    const abc_gram_plan pl = gram_plan_for(ctx, X, Y, n, ldx, ldy, M, P, row0, n_train_global, n_set);
+    switch (pl.kernel) {
+        case GRAM_I8: return run_gram_i8(ctx, pl, X, Y, n, ldx, ldy, (int)M, (int)P, stats);
+        case GRAM_GROUPED_DMA:
+        case GRAM_GROUPED_VGPR: return run_gram_grouped(ctx, pl, X, Y, n, ldx, ldy, M, P, stats);
+        default: return run_gram_fp64(ctx, pl, X, Y, n, ldx, ldy, (int)M, (int)P, stats);
     }
-#undef GRAM_RUN
-    return run_gram_grouped(ctx, X, Y, n, ldx, ldy, M, P, split, stats);
 }

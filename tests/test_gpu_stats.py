@@ -17,7 +17,7 @@ import math
 import numpy as np
 import pytest
 
-from _gram_dispatch import kernel_for, work_groups
+from _gram_dispatch import kernel_for, plan, work_groups
 
 pytestmark = pytest.mark.gpu
 
@@ -387,3 +387,28 @@ def test_stats_record_with_an_unrepresentative_pilot(gpu_ctx, M, P, n, fam):
         worst_amp = max(worst_amp, float(amp.max()))
     assert worst_amp > 10, worst_amp          # the pilot really is unrepresentative
     print("unrepresentative pilot, %s: the record's scale is %.0f x the centred one" % (fam, worst_amp))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# stage timing: the same record, and a bracket around every launch of every launch body
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("M,P,n,fam", [(32, 16, 1000, "vgpr"), (40, 20, 1000, "dma8"), (128, 16, 1000, "wide"),
+                                       (100, 8, 1000, "grouped_dma"), (100, 8, 1001, "grouped_vgpr"), (170, 10, 1000, "grouped_dma")])
+def test_stats_record_under_stage_timing(gpu_ctx, M, P, n, fam):
+    """abc_timing_enable does not change a byte of the record, and the k_gram and stats_reduce stages are counted once per launch
+    of the plan: once, on the grouped path once per pair of column groups (the smallest shapes that reach each launch body; the
+    byte-limb kernel needs 200 000 rows: tests/test_gpu_parity.py::test_wide_gram_on_the_i8_matrix_pipe)"""
+    split = n // 2
+    p = plan(M, P, n, split)
+    assert p["kernel"] == fam and p["launches"] == (1 if not fam.startswith("grouped") else p["pairs"]) >= 1, p
+    X, Y = _data(n, M, P, 3)
+    plain = _record(gpu_ctx, X, Y, split)
+    gpu_ctx.timing_enable(True)
+    try:
+        gpu_ctx.timing_read(reset=True)
+        timed = _record(gpu_ctx, X, Y, split)
+        stages = gpu_ctx.timing_read(reset=True)
+    finally:
+        gpu_ctx.timing_enable(False)
+    assert timed.tobytes() == plain.tobytes()
+    assert stages["k_gram"][2] == p["launches"] and stages["stats_reduce"][2] == p["launches"], (stages["k_gram"], stages["stats_reduce"])
