@@ -22,18 +22,19 @@
 //     raises a flag; the caller then builds the table on the host as before.
 // scripts/alias_scan_proto.py is the same algorithm in exact Python integers (900 random weight vectors of six kinds, tie-heavy
 // and nearly uniform ones included: bit-exact, no flag); tests/test_gpu_parity.py::test_device_alias_table_* compare the device
-// table with the oracle's entry by entry.
+// table with the oracle's entry by entry, tests/test_gpu_alias_branches.py at every work-group edge and chain shape, the fallbacks
+// held to that model.  The map algebra itself (rne_map, rapply, inv_min, compose, to_grid, from_grid) is alias_maps.h, host and
+// device alike: tests/cxx/alias_maps_probe.cpp holds it to brute force on the CPU.
 // Ten launches (the verdict is published by the caller's next kernel), no host involvement, no device-scope fences (reductions across work-groups go through kernel boundaries: every
 // "apply" kernel re-derives its block's prefix from the per-block aggregates of the launch before).
 #include <stdlib.h>
 
 #include "abc_internal.h"
+#include "alias_maps.h"
 
 namespace {
 
-typedef __int128 i128;
-typedef unsigned __int128 u128;
-typedef unsigned long long u64;
+using namespace abc_al;     // i128 / u128 / u64, RMap and the step-map algebra (alias_maps.h)
 
 // Elements per thread: this file is compiled TWICE (Makefile: alias_dev.o with four, alias_dev_i2.o with -DABC_AL_I=2).  Every
 // kernel of the build is latency-bound on a nearly empty chip, a thread's serial work (compositions of 128-bit step maps) grows
@@ -50,68 +51,6 @@ constexpr int AL_I = ABC_AL_I;            // consecutive elements per thread
 constexpr int AL_B = AL_T * AL_I;         // elements per work-group
 constexpr int AL_MAXBLK = 8192;           // work-groups whose aggregates one work-group re-scans in its prologue (K <= 4.19e6 / 2.1e6)
 constexpr int AL_SUM_BITS = 44;           // the total's grid lies this many bits below its ulp
-
-struct RMap { i128 t0, t1, b; int k; int pad_[3]; };      // 64 bytes
-
-__device__ __forceinline__ i128 shl(i128 v, int s) { return (i128)((u128)v << s); }
-__device__ __forceinline__ int bitlen(i128 v) {           // v >= 0
-    const u64 hi = (u64)((u128)v >> 64), lo = (u64)v;
-    return hi ? 128 - __clzll((long long)hi) : (lo ? 64 - __clzll((long long)lo) : 0);
-}
-__device__ __forceinline__ int level_of(i128 v) { const int b = bitlen(v); return b > 53 ? b - 53 : 0; }
-
-// y -> round-to-nearest-even at level k of (y + c); sticky: c stands for a real number slightly above the integer c
-__device__ __forceinline__ RMap rne_map(int k, i128 c, bool sticky) {
-    RMap m;
-    m.k = k; m.b = 0; m.pad_[0] = m.pad_[1] = m.pad_[2] = 0;
-    if (k == 0) { m.t0 = -c - 1; m.t1 = -c; return m; }
-    const i128 P = shl(1, k + 1), h = shl(1, k - 1);
-    const i128 t_even = -c - shl(1, k) + h;                // reaching an EVEN multiple of 2^k: a tie rounds up to it
-    const i128 t_odd = -c + h + (sticky ? 0 : 1);          // reaching an ODD multiple: a tie stays below
-    m.t0 = t_odd - P; m.t1 = t_even;
-    return m;
-}
-__device__ __forceinline__ RMap rmap_identity() { RMap m; m.k = 0; m.t0 = -1; m.t1 = 0; m.b = 0; m.pad_[0] = m.pad_[1] = m.pad_[2] = 0; return m; }
-__device__ __forceinline__ i128 rapply(const RMap& m, i128 y) {
-    return shl(((y - m.t0) >> (m.k + 1)) + ((y - m.t1) >> (m.k + 1)), m.k) + m.b;
-}
-// min { y : m(y) >= v }
-__device__ __forceinline__ i128 inv_min(const RMap& m, i128 v) {
-    const i128 a = -((-(v - m.b)) >> m.k);                 // ceil((v - b) / 2^k): the step count that must be reached
-    if (a & 1) return m.t0 + shl((a + 1) >> 1, m.k + 1);
-    return m.t1 + shl(a >> 1, m.k + 1);
-}
-// first m1, then m2
-__device__ __forceinline__ RMap compose(const RMap& m1, const RMap& m2) {
-    RMap r;
-    if (m2.k < m1.k) { r = m1; r.b = rapply(m2, m1.b); return r; }     // 2^k1 N is a multiple of m2's period
-    r.k = m2.k; r.t0 = inv_min(m1, m2.t0); r.t1 = inv_min(m1, m2.t1); r.b = m2.b;
-    r.pad_[0] = r.pad_[1] = r.pad_[2] = 0;
-    return r;
-}
-
-// x (>= 0, finite) as an integer multiple of 2^e0; *inexact is set when bits fall below the grid (the result is then the floor)
-__device__ __forceinline__ i128 to_grid(double x, int e0, bool* inexact) {
-    const u64 bits = (u64)__double_as_longlong(x);
-    const int be = (int)((bits >> 52) & 0x7ff);
-    u64 mant = bits & 0xfffffffffffffull;
-    int e;
-    if (be == 0) { if (mant == 0) return 0; e = -1074; } else { mant |= 1ull << 52; e = be - 1075; }
-    const int sh = e - e0;
-    if (sh >= 0) return (sh < 70) ? shl((i128)mant, sh) : (i128)0;       // (sh >= 70 cannot happen for values the callers admit)
-    if (sh <= -64) { *inexact = true; return 0; }
-    if (mant & ((1ull << -sh) - 1)) *inexact = true;
-    return (i128)(mant >> -sh);
-}
-// the double with value v 2^e0, if v has at most 53 significant bits (else *ok = false)
-__device__ __forceinline__ double from_grid(i128 v, int e0, bool* ok) {
-    if (v < 0) { *ok = false; return 0.0; }
-    if (v == 0) return 0.0;
-    const int bl = bitlen(v), sh = bl > 53 ? bl - 53 : 0;
-    const u64 top = (u64)(v >> sh);
-    if (shl((i128)top, sh) != v) { *ok = false; return 0.0; }
-    return ldexp((double)top, sh + e0);
-}
 
 __device__ __forceinline__ i128 shfl_up_i128(i128 v, int d) {
     const u64 lo = (u64)__shfl_up((long long)(u64)v, d, 64), hi = (u64)__shfl_up((long long)(u64)((u128)v >> 64), d, 64);
@@ -653,6 +592,12 @@ size_t abc_alias_dev_need(size_t K) {       // (the larger of the two variants' 
 }
 int launch_alias_build_dev(abc_ctx* ctx, const double* w, size_t K, double* F, uint32_t* A, int* fail_dev, int* fail_pin,
                            const int** verdict_src) {
+    // ABC_ALIAS_ELEMS=2 / 4 (tests): that variant whatever K says, where it can take K (AL_MAXBLK * AL_B / 2 of its own AL_B)
+    if (const char* e = abc_diag_env("ABC_ALIAS_ELEMS")) {
+        const int elems = atoi(e);
+        if (elems == 2 && K <= (size_t)AL_MAXBLK * (AL_T * 2) / 2) return launch_alias_build_dev_i2(ctx, w, K, F, A, fail_dev, fail_pin, verdict_src);
+        if (elems == 4 && K <= (size_t)AL_MAXBLK * (AL_T * 4) / 2) return launch_alias_build_dev_i4(ctx, w, K, F, A, fail_dev, fail_pin, verdict_src);
+    }
     if (K <= ABC_ALIAS_DEV_SMALL_K) return launch_alias_build_dev_i2(ctx, w, K, F, A, fail_dev, fail_pin, verdict_src);
     return launch_alias_build_dev_i4(ctx, w, K, F, A, fail_dev, fail_pin, verdict_src);
 }

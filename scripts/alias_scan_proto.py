@@ -134,10 +134,12 @@ class Fallback(Exception):
     pass
 
 
-def total_by_scan(w, fast_scan=False):
-    """the sequential sum s = fl(s + w_k) as a verified scan"""
+def total_by_scan(w, fast_scan=False, approx=None):
+    """the sequential sum s = fl(s + w_k) as a verified scan; approx: the approximate prefix sums that place every partial sum
+    in its binade (default: np.cumsum; the device accumulates inside a block of elements, then across the blocks)"""
     K = len(w)
-    approx = np.cumsum(np.asarray(w, dtype=np.float64))        # (any parallel prefix sum: only the binades matter)
+    if approx is None:
+        approx = np.cumsum(np.asarray(w, dtype=np.float64))    # (any parallel prefix sum: only the binades matter)
     tot_a = float(approx[-1])
     if not (tot_a > 0 and math.isfinite(tot_a)):
         raise Fallback("total")
@@ -183,9 +185,10 @@ def total_by_scan(w, fast_scan=False):
     return prev
 
 
-def alias_by_scan(w, tree_scan=False):
+def alias_by_scan(w, tree_scan=False, approx=None, info=None):
+    """approx: see total_by_scan; info: a dict that receives ns, nb (smalls, bigs) and nsteps (steps of the serving chain)"""
     K = len(w)
-    total = total_by_scan(w)
+    total = total_by_scan(w, approx=approx)
     mean = 1.0 / K
     dK = float(K)
     E = [x / total for x in w]
@@ -194,6 +197,8 @@ def alias_by_scan(w, tree_scan=False):
     F = [1.0] * K
     A = list(range(K))
     ns, nb = len(smalls), len(bigs)
+    if info is not None:
+        info.update(ns=ns, nb=nb, nsteps=0)
     if ns == 0 or nb == 0:
         return total, F, A
     e0 = math.frexp(mean)[1] - 53 - 1                           # g0 = ulp(mean) / 2
@@ -227,6 +232,8 @@ def alias_by_scan(w, tree_scan=False):
             order[z[j - 1] + j] = ("h", j)
     Tn = len(order)
     assert sorted(order) == list(range(1, Tn + 1)), "positions are not a permutation"
+    if info is not None:
+        info["nsteps"] = Tn
     maps = []
     meta = []
     for t in range(1, Tn + 1):
