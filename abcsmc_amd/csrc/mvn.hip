@@ -3,7 +3,11 @@
 // (n-1 covariance), diagonal doubled (:475-479), [GSL] gsl_linalg_cholesky_decomp1 (lower factor in
 // place, strict upper triangle keeps the covariance entries).
 // The K x P cross-products come from the same one-pass MFMA Gram kernel as the PLS statistics
-// (gram.hip, theta treated as a P-column matrix); the P x P factorisation is one wavefront in LDS.
+// (gram.hip, theta treated as a P-column matrix); the P x P factorisation is one wavefront: in registers up to 32 parameters
+// (k_post_tail), in LDS up to 138, in the arena beyond.
+// Pinned by tests/test_gpu_moments.py: every kernel here, at both sides of each of those edges and from both call sites of
+// k_post_tail, against the long-double reference and the derived bounds of tests/_moments_ref.py (covariance entries, dv, factor,
+// the not-positive-definite status), and the fused tail bit for bit against the stand-alone entries.
 #include <stdlib.h>
 
 #include "abc_internal.h"

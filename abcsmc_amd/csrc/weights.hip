@@ -56,16 +56,22 @@ __global__ __launch_bounds__(256) void k_gather_rows(const double* __restrict__ 
     if (g >= idx_base && g - idx_base < n_local) theta[i + ldt * p] = Y[(g - idx_base) + ldy * p];
 }
 
-// one work-group per parameter: dv_p = 2 * sum (x - mean)^2 / (K - 1)
+// one work-group per parameter: dv_p = 2 * sum (x - mean)^2 / (K - 1), both passes on the values centred on the column's first row.
+// A constant column (a converged parameter: the reference's running statistic gives exactly 0 there, and the weight stage branches
+// on dv_p == 0) then has x - x0 == 0.0 in every row, exactly: the sum, its mean, every deviation and every square are 0.0, so
+// dv_p is 0.0 whatever the summation order.  (The mean of the raw values can miss the constant c by an ulp, e: dv_p = 2 K e^2 /
+// (K - 1) > 0 then, and the converged-parameter rule does not fire.)  Elsewhere the centring only helps: the mean's error enters
+// squared, and relative to |x - x0|, not to |x|.
 __global__ __launch_bounds__(256) void k_doubled_variance(const double* __restrict__ theta, size_t K,
                                                           double* __restrict__ dv) {
     __shared__ double sm[4];
     const double* col = theta + K * (size_t)blockIdx.x;
+    const double x0 = K ? col[0] : 0.0;
     double s = 0.0;
-    for (size_t i = threadIdx.x; i < K; i += 256) s += col[i];
+    for (size_t i = threadIdx.x; i < K; i += 256) s += col[i] - x0;
     const double mean = block_sum_256(s, sm) / (double)K;
     double ss = 0.0;
-    for (size_t i = threadIdx.x; i < K; i += 256) { const double d = col[i] - mean; ss = fma(d, d, ss); }
+    for (size_t i = threadIdx.x; i < K; i += 256) { const double d = (col[i] - x0) - mean; ss = fma(d, d, ss); }
     ss = block_sum_256(ss, sm);
     if (threadIdx.x == 0) dv[blockIdx.x] = (K > 1) ? 2.0 * (ss / (double)(K - 1)) : 0.0;
 }

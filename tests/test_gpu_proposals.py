@@ -5,6 +5,10 @@ The model reproduces the Philox words exactly and the deviates up to the f32 tra
 sum_b |L_ab| zbound_b (+ roundings) of the model's, integer coordinates must be equal.  A wrong counter word, key, column, row
 group, padded-factor layout or slice offset moves a proposal by O(1) in units of its noise.
 
+The factor and the doubled variance k_post_tail computes are held to the long-double reference and the derived bounds of
+tests/_moments_ref.py here at one shape per width (test_generation_factor_and_proposals); tests/test_gpu_moments.py pins them at
+every width, both call sites and the stand-alone kernels.
+
 zbound (tests/_philox_ref.py: ZB_MULT x the first-order error of one unit in each hardware step) was set from one measured run of
 test_hardware_deviates_against_the_model on gfx950: over 1.6e6 deviates the largest |z_dev - z_ref| was 6.1e-4, 0.999 units of
 the model (ZB_MULT = 16: 16x headroom).  That worst case is one ulp of v_log_f32 near 32 (u close to 1, a small radius); for
@@ -14,6 +18,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import _moments_ref as MR
 import _philox_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -254,36 +259,6 @@ def test_column_prefix_of_a_wider_call(gpu_ctx, multivariate):
 
 
 # ---- the fused generation: k_post_tail's factor, padded factor and parent table ---------------------------------------------
-def _chol_ld(A):
-    A = A.astype(np.longdouble)
-    P = A.shape[0]
-    L = np.zeros_like(A)
-    for j in range(P):
-        s = A[j, j] - np.sum(L[j, :j] ** 2)
-        L[j, j] = np.sqrt(s)
-        for i in range(j + 1, P):
-            L[i, j] = (A[i, j] - np.sum(L[i, :j] * L[j, :j])) / L[j, j]
-    return L
-
-
-def _factor_bounds(th, Lr):
-    """(E, B): entrywise bounds on the device's doubled covariance and on its factor.  E: fp64 sums of K products of
-    pilot-shifted values (the shift lies within the data, a few sd from the mean at most), every shifted value carrying eps |theta|,
-    then the mean's share subtracted.  B: the first-order perturbation of the factor, dL = L Phi(L^-1 dC L^-T) (Phi: the lower
-    triangle, half the diagonal), taken entrywise in absolute values, with the factorisation's own backward error
-    (P + 1) eps |L| |L|^T added to dC, and a factor 2 for the second order"""
-    K, P = th.shape
-    eps = 2.0 ** -53
-    m = np.abs(th.mean(axis=0))
-    s = th.std(axis=0, ddof=1)
-    E = (K + 4) * eps * (64.0 * np.outer(s, s) + 8.0 * (np.outer(m, s) + np.outer(s, m)))
-    E[np.diag_indices(P)] *= 2
-    aL = np.abs(Lr)
-    Li = np.abs(np.linalg.inv(Lr))
-    B = 2.0 * aL @ np.tril(Li @ (E + (P + 1) * eps * aL @ aL.T) @ Li.T)
-    return E, B
-
-
 @pytest.mark.parametrize("P", [2, 3, 5, 8, 9, 17, 32, 33, 64])
 def test_generation_factor_and_proposals(gpu_ctx, P):
     """(d) a small weighted multivariate generation: gen.L and gen.dv against a long-double reference from gen.theta (the doubled
@@ -292,7 +267,8 @@ def test_generation_factor_and_proposals(gpu_ctx, P):
 
     The statistics of a set this small come from the fp64 Gram kernels (the byte-limb kernel of tests/_gram_model.py needs
     >= 400000 rows): the covariance is bounded by the fp64 rounding of sums of K products, the factor by that error times
-    the condition number -- far below the rtol 1e-7 of the oracle comparisons"""
+    the condition number (E and B of tests/_moments_ref.py; B stays below 1e-10 of the largest factor entry here, where the
+    oracle comparisons ask for rtol 1e-7)"""
     import torch
     from abcsmc_amd import abcutil, device, synthetic, _lib
     N, M, K, Kp, Nn, A = 3000, 8, 600, 300, 4001, 4
@@ -308,21 +284,19 @@ def test_generation_factor_and_proposals(gpu_ctx, P):
             device.priors_to_device(_lib.make_priors(spec), dev), r, *(device.colmajor(a, dev) for a in prev))
     torch.cuda.synchronize()
     th = device.to_numpy(gen.theta)
-    L = np.tril(device.to_numpy(gen.L))
+    Lg = device.to_numpy(gen.L)
+    L = np.tril(Lg)
     dv = gen.dv.cpu().numpy()
-    # long-double reference: covariance with n - 1, its diagonal doubled (AbcUtil.cpp:475-479), then the factor
-    t = th.astype(np.longdouble)
-    d = t - t.mean(axis=0)
-    cov = (d.T @ d) / (K - 1)
-    cov[np.diag_indices(P)] *= 2
-    Lr = _chol_ld(cov).astype(np.float64)
-    E, B = _factor_bounds(th, Lr)
+    # long-double reference and derived bounds (tests/_moments_ref.py): covariance with n - 1, its diagonal doubled
+    # (AbcUtil.cpp:475-479), then the factor; the strict upper triangle keeps the covariance entries
+    sB, sE, E, B, mref = MR.check_factor(Lg, th)
+    Lr = mref["L"]
     err = np.abs(L - Lr)
-    dv_ref = np.diag(cov).astype(np.float64)
-    print("P=%d: |L - L_ref| %.3g, worst share of the bound %.3g, bound / max|L| %.3g, |dv - dv_ref| / dv %.3g" % (
-        P, err.max(), np.max(err / np.maximum(B, 1e-300)), B.max() / np.abs(Lr).max(), np.max(np.abs(dv - dv_ref) / dv)))
-    assert np.all(err <= B) and B.max() < 1e-7 * np.abs(Lr).max()
-    assert np.all(np.abs(dv - dv_ref) <= np.diag(E))
+    dv_ref = mref["dv"]
+    print("P=%d: |L - L_ref| %.3g, worst share of B %.3g, of E (strict upper triangle) %.3g, bound / max|L| %.3g, |dv - dv_ref| / dv %.3g" % (
+        P, err.max(), sB, sE, B.max() / np.abs(Lr).max(), np.max(np.abs(dv - dv_ref) / dv)))
+    assert sB <= 1.0 and sE <= 1.0 and B.max() < 1e-10 * np.abs(Lr).max()
+    assert np.all(np.abs(dv.astype(MR.LD) - np.diag(mref["cov"])).astype(np.float64) <= np.diag(E))
     par = gen.parent.cpu().numpy().astype(np.int64)
     x = device.to_numpy(gen.next)
     ref = R.proposals_ref(key, th, par, spec, L, True, 0, Nn)
