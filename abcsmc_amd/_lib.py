@@ -179,6 +179,13 @@ class Entropy(C.Structure):
     _fields_ = [("k", C.c_int), ("scale", C.c_void_p), ("H", C.c_void_p), ("knn", C.c_void_p), ("zeros", C.c_void_p)]
 
 
+class Hpd(C.Structure):
+    """abc_hpd: mass (host, nm masses inside (0, 1)), then the optional outputs lo / hi / plo / phi (memory as the entry point's
+    other arrays)"""
+    _fields_ = [("mass", C.c_void_p), ("nm", C.c_size_t), ("lo", C.c_void_p), ("hi", C.c_void_p), ("plo", C.c_void_p),
+                ("phi", C.c_void_p)]
+
+
 def _draws_stream(stream, n):
     """The stream ids of an abc_draws as a C-contiguous uint64 host array of n entries, or None (target b takes id b)"""
     import numpy as np
@@ -349,7 +356,10 @@ _PRODUCT_ARGS = {
 PRODUCTS = ("summary", "density", "joint", "draws")
 # products of an unweighted sample: the same four argument lists; the entries refuse weights that are not all equal
 UNWEIGHTED_PRODUCTS = ("entropy",)
-SIGNATURES.update((entry % product, (_i, args)) for product in PRODUCTS + UNWEIGHTED_PRODUCTS for entry, args in _PRODUCT_ARGS.items())
+# products of the summaries' sort that came after the four above: the same argument lists, any weights
+INTERVAL_PRODUCTS = ("hpd",)
+SIGNATURES.update((entry % product, (_i, args)) for product in PRODUCTS + UNWEIGHTED_PRODUCTS + INTERVAL_PRODUCTS
+                  for entry, args in _PRODUCT_ARGS.items())
 
 _LIB = None
 

@@ -588,12 +588,17 @@ def weighted_draws(values, weights=None, S=1000, smooth=False, seed=0, bw=None, 
 # functions this module defines under the name particle_ranking_PLS_targets* are the family that works under row importance
 # weights, every member of it, and the entropy is refused under them.
 _UNWEIGHTED = ("particle_ranking_PLS_targets_entropy", "knn_entropy")
+# The highest-density intervals (hpd.py) are forwarded the same way; they do work under row importance weights and any others.
+_INTERVALS = ("particle_ranking_PLS_targets_hpd", "weighted_hpd")
 
 
 def __getattr__(name):
     if name in _UNWEIGHTED:
         from . import entropy
         return getattr(entropy, name)
+    if name in _INTERVALS:
+        from . import hpd
+        return getattr(hpd, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -615,7 +620,8 @@ def hpd_levels(dens, step_x, step_y, probs=(0.5, 0.9, 0.95)):
 
 def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5, max_comp=0, rule=_lib.RULE_DEFAULT,
                        ctx=None, method="rejection", kernel="epanechnikov", statistic="mean", coverage=False, transf=None,
-                       bounds=None, hcorr=False, ridge=None, row_weights=None, entropy=False, entropy_k=4, entropy_scale="sd"):
+                       bounds=None, hcorr=False, ridge=None, row_weights=None, entropy=False, entropy_k=4, entropy_scale="sd",
+                       hpd=None):
     """Leave-one-out cross-validation of the PLS rejection step, as cv4abc of the R package abc: n_targets rows drawn
     without replacement (numpy Generator seeded with `seed`) serve as pseudo-observed data, each ranked against the set with
     itself excluded (the fit is shared: the row stays in it), and the posterior mean of its K nearest rows estimates its
@@ -637,7 +643,10 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
     methods: what a table that is not drawn from the prior needs.  entropy=True adds entropy (n_targets,): the k-nearest-neighbour
     entropy of each left-out row's posterior (particle_ranking_PLS_targets_entropy with k = entropy_k and scale = entropy_scale,
     same method, kernel and adjustment settings), and mean_entropy: their mean, what min_entropy_components compares.  The estimator
-    takes entries of equal weight only: "loclinear" then needs kernel="rectangular", and the library refuses row_weights."""
+    takes entries of equal weight only: "loclinear" then needs kernel="rectangular", and the library refuses row_weights.
+    hpd: None, or masses inside (0, 1); adds hpd (n_targets, nm, 2, P): the highest-density interval [lo, hi] of each left-out row's
+    posterior for every mass (particle_ranking_PLS_targets_hpd, same method, kernel and adjustment settings), and hpd_coverage
+    (nm, P): the share of the left-out rows whose true parameter lies in its interval, about the mass for a calibrated posterior."""
     X, Y = _f(X_orig), _f(Y_orig)
     N = X.shape[0]
     n_targets = int(n_targets)
@@ -683,6 +692,12 @@ def cross_validate_pls(X_orig, Y_orig, n_targets, K, seed, training_fraction=0.5
                                                   **tkw)
         out["entropy"] = en["H"]
         out["mean_entropy"] = float(np.mean(en["H"]))
+    if hpd is not None:
+        from .hpd import particle_ranking_PLS_targets_hpd
+        hd = particle_ranking_PLS_targets_hpd(X, Y, X[rows], training_fraction, K, mass=hpd, method=method, kernel=kernel,
+                                              exclude=rows, max_comp=max_comp, rule=rule, ctx=ctx, outputs=("lo", "hi"), **tkw)
+        out["hpd"] = np.stack([hd["lo"], hd["hi"]], axis=2)
+        out["hpd_coverage"] = ((hd["lo"] <= theta[:, None, :]) & (theta[:, None, :] <= hd["hi"])).mean(axis=0)
     return out
 
 

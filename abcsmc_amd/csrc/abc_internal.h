@@ -398,6 +398,10 @@ int launch_draws(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, con
 // all equal (the entries refuse the rest).  en: scale in host memory, every other array in device memory
 size_t abc_entropy_need(size_t B, size_t K, size_t P);
 int launch_entropy(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_entropy* en, const char* fn);
+// highest-density intervals of the same segments (summary.hip): the summary's sort and knots, then the shortest interval of every
+// mass.  hd: mass in host memory, every other array in device memory
+size_t abc_hpd_need(size_t B, size_t K, size_t P);
+int launch_hpd(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const abc_hpd* hd);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

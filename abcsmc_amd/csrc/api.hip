@@ -1542,9 +1542,9 @@ extern "C" int abc_sample_predictive_priors(abc_ctx* ctx, abc_rng* rng, size_t n
 
 // ---- batched ranking of many observed targets against one fitted set (targets.hip), optionally followed by the local-linear
 // adjustment (adjust.hip) or by a posterior product of every target's retained rows: the weighted quantiles and CDF (summary.hip),
-// the densities and modes (density.hip), the joint moments and pair densities (joint.hip), the posterior draws (draws.hip) or the
-// posterior entropy (entropy.hip).  One pipeline (tg_*) behind the sixteen entry points of the family and one pair of paths
-// (weighted_dev, weighted_host) behind the ten abc_weighted_* entries, which
+// the densities and modes (density.hip), the joint moments and pair densities (joint.hip), the posterior draws (draws.hip), the
+// posterior entropy (entropy.hip) or the highest-density intervals (summary.hip).  One pipeline (tg_*) behind the eighteen entry
+// points of the family and one pair of paths (weighted_dev, weighted_host) behind the twelve abc_weighted_* entries, which
 // compute the same products from given values; what differs between the products is in Product ----
 static int summary_check(abc_ctx* ctx, const char* fn, const abc_summary* sum) {
     if (!sum) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (sum is required)", fn);
@@ -1608,6 +1608,17 @@ static int entropy_check(abc_ctx* ctx, const char* fn, const abc_entropy* en, si
         for (size_t j = 0; j < P; j++)
             if (!(en->scale[j] > 0.0) || !std::isfinite(en->scale[j]))
                 ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: scale[%zu] = %g (finite, > 0)", fn, j, en->scale[j]);
+    return ABC_OK;
+}
+
+static int hpd_check(abc_ctx* ctx, const char* fn, const abc_hpd* hd) {
+    if (!hd) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (hd is required)", fn);
+    if (hd->nm == 0 || hd->nm > 16) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: nm = %zu masses (1 to 16)", fn, hd->nm);
+    if (!hd->mass) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (mass is required)", fn);
+    for (size_t i = 0; i < hd->nm; i++)
+        if (!(hd->mass[i] > 0.0 && hd->mass[i] < 1.0))
+            ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: mass[%zu] = %g is not a mass inside (0, 1)", fn, i, hd->mass[i]);
+    if (!hd->lo && !hd->hi && !hd->plo && !hd->phi) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of hd is NULL", fn);
     return ABC_OK;
 }
 
@@ -1705,27 +1716,47 @@ static void entropy_down(Stage& s, const abc_entropy* h, const abc_entropy& d, s
     s.down(h->zeros, d.zeros, B);
 }
 
+// an abc_hpd's arrays for B targets of P segments, host (h) <-> arena: mass stays where it is, NULL members stay NULL
+static abc_hpd hpd_stage(Stage& s, const abc_hpd* h, size_t B, size_t P) {
+    abc_hpd d = *h;
+    const size_t n = B * h->nm * P;
+    d.lo = h->lo ? s.dev<double>(n) : nullptr;
+    d.hi = h->hi ? s.dev<double>(n) : nullptr;
+    d.plo = h->plo ? s.dev<double>(n) : nullptr;
+    d.phi = h->phi ? s.dev<double>(n) : nullptr;
+    return d;
+}
+static void hpd_down(Stage& s, const abc_hpd* h, const abc_hpd& d, size_t B, size_t P) {
+    const size_t n = B * h->nm * P;
+    s.down(h->lo, d.lo, n);
+    s.down(h->hi, d.hi, n);
+    s.down(h->plo, d.plo, n);
+    s.down(h->phi, d.phi, n);
+}
+
 namespace {
 // A posterior product: what is computed from the segments' values and weights, described by the caller's abc_summary, abc_density,
-// abc_joint, abc_draws or abc_entropy.  Every member below has one row per kind, and nothing else in this file tells the kinds
+// abc_joint, abc_draws, abc_entropy or abc_hpd.  Every member below has one row per kind, and nothing else in this file tells the kinds
 // apart: a new product adds its constructor and its six rows here (and a seventh where it has a demand of its own on the segments,
 // as equal_weights()).
 struct Product {
-    enum Kind { NONE, SUMMARY, DENSITY, JOINT, DRAWS, ENTROPY } kind = NONE;
+    enum Kind { NONE, SUMMARY, DENSITY, JOINT, DRAWS, ENTROPY, HPD } kind = NONE;
     union {
         const abc_summary* sum = nullptr;
         const abc_density* den;
         const abc_joint* jnt;
         const abc_draws* drw;
         const abc_entropy* ent;
+        const abc_hpd* hpd;
     };
-    union { abc_summary sum; abc_density den; abc_joint jnt; abc_draws drw; abc_entropy ent; } staged;      // stage()'s copy of the descriptor
+    union { abc_summary sum; abc_density den; abc_joint jnt; abc_draws drw; abc_entropy ent; abc_hpd hpd; } staged;      // stage()'s copy of the descriptor
     Product() {}
     explicit Product(const abc_summary* s) : kind(SUMMARY), sum(s) {}
     explicit Product(const abc_density* d) : kind(DENSITY), den(d) {}
     explicit Product(const abc_joint* j) : kind(JOINT), jnt(j) {}
     explicit Product(const abc_draws* d) : kind(DRAWS), drw(d) {}
     explicit Product(const abc_entropy* e) : kind(ENTROPY), ent(e) {}
+    explicit Product(const abc_hpd* h) : kind(HPD), hpd(h) {}
 
     // the descriptor's own argument checks (a NULL descriptor among them)
     int check(abc_ctx* ctx, const char* fn, size_t P) const {
@@ -1735,6 +1766,7 @@ struct Product {
         case JOINT: return joint_check(ctx, fn, jnt, P);
         case DRAWS: return draws_check(ctx, fn, drw);
         case ENTROPY: return entropy_check(ctx, fn, ent, P);
+        case HPD: return hpd_check(ctx, fn, hpd);
         default: return ABC_OK;
         }
     }
@@ -1746,6 +1778,7 @@ struct Product {
         case JOINT: return abc_joint_need(B, K, P, jnt->G, abc_joint_pairs(jnt, P));
         case DRAWS: return abc_draws_need(B, K, P, drw->smooth);
         case ENTROPY: return abc_entropy_need(B, K, P);
+        case HPD: return abc_hpd_need(B, K, P);
         default: return 0;
         }
     }
@@ -1757,6 +1790,7 @@ struct Product {
         case JOINT: return joint_stage_bytes(jnt, B, P);
         case DRAWS: return B * (drw->S * (P + 1) + 2 * P + 1) * 8 + 20 * 256;  // draws, src, bw, bw_out, ess
         case ENTROPY: return B * (K + 2) * 8 + 12 * 256;                   // H, knn, zeros
+        case HPD: return B * P * hpd->nm * 4 * 8 + 16 * 256;               // lo, hi, plo, phi
         default: return 0;
         }
     }
@@ -1769,6 +1803,7 @@ struct Product {
         case JOINT: staged.jnt = joint_stage(s, jnt, B, P); return Product(&staged.jnt);
         case DRAWS: staged.drw = draws_stage(s, drw, B, P); return Product(&staged.drw);
         case ENTROPY: staged.ent = entropy_stage(s, ent, B, K); return Product(&staged.ent);
+        case HPD: staged.hpd = hpd_stage(s, hpd, B, P); return Product(&staged.hpd);
         default: return Product();
         }
     }
@@ -1780,6 +1815,7 @@ struct Product {
         case JOINT: joint_down(s, jnt, staged.jnt, B, P); break;
         case DRAWS: draws_down(s, drw, staged.drw, B, P); break;
         case ENTROPY: entropy_down(s, ent, staged.ent, B, K); break;
+        case HPD: hpd_down(s, hpd, staged.hpd, B, P); break;
         default: break;
         }
     }
@@ -1791,6 +1827,7 @@ struct Product {
         case JOINT: return launch_joint(ctx, sv, B, K, P, jnt, fn);
         case DRAWS: return launch_draws(ctx, sv, B, K, P, drw, fn);
         case ENTROPY: return launch_entropy(ctx, sv, B, K, P, ent, fn);
+        case HPD: return launch_hpd(ctx, sv, B, K, P, hpd);
         default: return ABC_OK;
         }
     }
@@ -2290,6 +2327,26 @@ extern "C" int abc_particle_ranking_pls_targets_entropy(abc_ctx* ctx, const doub
     return tg_host(ctx, "abc_particle_ranking_pls_targets_entropy", h, train_frac, max_comp, rule, ncomp);
 }
 
+extern "C" int abc_rank_targets_hpd_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
+                                        const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                                        const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                        const abc_adjust_out* adj, const abc_hpd* hd) {
+    CHECK_CTX(ctx);
+    const TgRequest r{TG_PRODUCT, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(hd)};
+    return tg_dev(ctx, "abc_rank_targets_hpd_dev", r);
+}
+
+extern "C" int abc_particle_ranking_pls_targets_hpd(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                                    const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                                    const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
+                                                    double* dist, const abc_adjust_out* adj, const abc_hpd* hd, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    const TgRequest h{TG_PRODUCT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
+                      adj, Product(hd)};
+    return tg_host(ctx, "abc_particle_ranking_pls_targets_hpd", h, train_frac, max_comp, rule, ncomp);
+}
+
 extern "C" int abc_particle_ranking_pls_targets_draws(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
                                                       const double* targets, size_t B, double train_frac, int max_comp, int rule,
                                                       const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx,
@@ -2410,6 +2467,16 @@ extern "C" int abc_weighted_entropy_dev(abc_ctx* ctx, const double* V, size_t ld
 extern "C" int abc_weighted_entropy(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_entropy* en) {
     CHECK_CTX(ctx);
     return weighted_host(ctx, "abc_weighted_entropy", V, K, P, w, Product(en));
+}
+
+extern "C" int abc_weighted_hpd_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w, const abc_hpd* hd) {
+    CHECK_CTX(ctx);
+    return weighted_dev(ctx, "abc_weighted_hpd_dev", V, ldv, K, P, w, Product(hd));
+}
+
+extern "C" int abc_weighted_hpd(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_hpd* hd) {
+    CHECK_CTX(ctx);
+    return weighted_host(ctx, "abc_weighted_hpd", V, K, P, w, Product(hd));
 }
 
 extern "C" int abc_param_transf(abc_ctx* ctx, const double* V, size_t n, size_t P, int inverse, double* out) {

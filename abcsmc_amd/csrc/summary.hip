@@ -21,6 +21,9 @@
 // of rank r is exactly r + 0.5 and W = n, so no H array is kept; the expressions are sm_eval's.  Under loclinear the values change
 // with the tolerance (its own beta): segment (b, t, j) goes through the kernels above with K = K_t, the row stride K_max and the
 // coefficient and output slot b T + t (SmArgs ld, T, t).
+//
+// Highest-density intervals (abc_rank_targets_hpd_dev, abc_weighted_hpd_dev): the same sort and the same knots, then per mass the
+// shortest of the 2 n candidate intervals that end on a knot (k_hp_lds; k_hp_knots_global, k_hp_search_global, k_hp_final_global).
 #include <math.h>
 
 #include "abc_internal.h"
@@ -258,6 +261,241 @@ __global__ __launch_bounds__(SM_BS) void k_sm_eval_global(SmArgs a, SmProbs pr, 
     sm_eval(a, s, pr, gkey + seg * a.K, gid + seg * a.K, gH + seg * a.K, (size_t)cnt[seg], bad[seg] != 0, red);
 }
 
+// ---- highest-density intervals (abc_rank_targets_hpd_dev, abc_weighted_hpd_dev; the definition is in the header) ----
+// The sort is the summary's and so are the knots: hp_knots repeats sm_eval's tile pass expression for expression (without the CDF's
+// sums, which do not enter H), then p_r = H_r / W is stored once over H, the bits sm_eval compares.  Every mass is one sweep of the
+// work-group over the 2 n candidates (one binary search over p each) and one reduction of the pair (width, c), whose order is
+// total: the winner does not depend on the reduction's shape (on the global path the candidates are split over work-groups).
+constexpr int HP_MAXM = 16;
+constexpr unsigned long long HP_NONE = ~0ull;               // the candidate number of "no valid candidate"
+
+struct HpMass {
+    double m[HP_MAXM];
+    int nm;
+};
+struct HpOut {
+    double *lo, *hi, *plo, *phi;                            // B x nm x P each, NULL: not asked for
+};
+
+// sm_eval's tile pass: H[r] = fma(-0.5, om_r, W_r) for the n sorted entries, the same per-thread order, scan and carry; returns W.
+// H may overlay id from byte 0 of id (the LDS path; only one tile there).  scan: SM_BS doubles of LDS.
+__device__ double hp_knots(const SmArgs& a, const SmSeg& s, const unsigned* id, double* H, size_t n, double* scan) {
+    const int t = threadIdx.x;
+    double carry = 0.0;
+    for (size_t base = 0; base < n; base += SM_TILE) {
+        const size_t r0 = base + (size_t)t * SM_PER;
+        double om[SM_PER], inc[SM_PER];
+        double acc = 0.0;
+#pragma unroll
+        for (int q = 0; q < SM_PER; q++) {
+            const size_t r = r0 + q;
+            om[q] = 0.0;
+            if (r < n) om[q] = sm_weight(a, s, (size_t)id[r]);
+            acc += om[q];
+            inc[q] = acc;
+        }
+        scan[t] = acc;
+        __syncthreads();                                       // (also: every id of the tile is read before H is written)
+        for (int off = 1; off < SM_BS; off <<= 1) {
+            const double v = (t >= off) ? scan[t - off] : 0.0;
+            __syncthreads();
+            scan[t] += v;
+            __syncthreads();
+        }
+        const double off = carry + ((t > 0) ? scan[t - 1] : 0.0);
+#pragma unroll
+        for (int q = 0; q < SM_PER; q++) {
+            const size_t r = r0 + q;
+            if (r < n) H[r] = fma(-0.5, om[q], off + inc[q]);
+        }
+        carry += scan[SM_BS - 1];
+        __syncthreads();                                       // scan read before the next tile writes it
+    }
+    __syncthreads();                                           // H complete
+    return carry;
+}
+
+// the summary's quantile function over the stored knots p (sm_eval's expressions with p[r] for H[r] / W), n >= 1
+__device__ __forceinline__ double hp_quantile(const double* p, const unsigned long long* key, size_t n, double q) {
+    if (q <= p[0]) return sm_unkey(key[0]);
+    if (q >= p[n - 1]) return sm_unkey(key[n - 1]);
+    size_t lo = 0, hi = n - 1;                                 // p_lo <= q < p_hi
+    while (hi - lo > 1) {
+        const size_t mid = lo + (hi - lo) / 2;
+        if (p[mid] <= q) lo = mid; else hi = mid;
+    }
+    const double plo = p[lo], phi = p[hi];
+    const double tt = (q - plo) / (phi - plo);
+    const double ulo = sm_unkey(key[lo]), uhi = sm_unkey(key[hi]);
+    return fma(tt, uhi - ulo, ulo);
+}
+
+// candidate c = 2 r + kind of mass m; false: not valid (the outputs are then not set)
+__device__ __forceinline__ bool hp_cand(const double* p, const unsigned long long* key, size_t n, double m, unsigned long long c,
+                                        double p0, double pl, double* lo, double* hi, double* plo, double* phi) {
+    const size_t r = (size_t)(c >> 1);
+    const double pr = p[r], ur = sm_unkey(key[r]);
+    if ((c & 1) == 0) {                                        // lower end on knot r
+        const double q = pr + m;
+        if (!(q <= pl)) return false;
+        *plo = pr; *phi = q;
+        *lo = ur; *hi = hp_quantile(p, key, n, q);
+    } else {                                                   // upper end on knot r
+        const double q = pr - m;
+        if (!(q >= p0)) return false;
+        *plo = q; *phi = pr;
+        *lo = hp_quantile(p, key, n, q); *hi = ur;
+    }
+    return true;
+}
+
+// the best (width, c) over the candidates c0 <= c < c1 of mass m, the work-group's threads striding over them; the result is
+// thread 0's alone.  rw / rc: SM_BS / 64 entries of LDS each, free again after the return
+__device__ void hp_sweep(const double* p, const unsigned long long* key, size_t n, double m, unsigned long long c0, unsigned long long c1,
+                         double p0, double pl, double* rw, unsigned long long* rc, double* bw_out, unsigned long long* bc_out) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    double bw = __longlong_as_double(0x7ff0000000000000ll);
+    unsigned long long bc = HP_NONE;
+    double lo, hi, plo, phi;
+    for (unsigned long long c = c0 + (unsigned long long)t; c < c1; c += SM_BS)
+        if (hp_cand(p, key, n, m, c, p0, pl, &lo, &hi, &plo, &phi)) {
+            const double w = hi - lo;
+            if (w < bw || (w == bw && c < bc)) { bw = w; bc = c; }
+        }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double w2 = __shfl_down(bw, off, 64);
+        const unsigned long long c2 = __shfl_down(bc, off, 64);
+        if (w2 < bw || (w2 == bw && c2 < bc)) { bw = w2; bc = c2; }
+    }
+    if (lane == 0) { rw[wave] = bw; rc[wave] = bc; }
+    __syncthreads();
+    if (t == 0)
+        for (int v = 1; v < SM_BS / 64; v++)
+            if (rw[v] < bw || (rw[v] == bw && rc[v] < bc)) { bw = rw[v]; bc = rc[v]; }
+    __syncthreads();                                           // rw / rc read before the next sweep writes them
+    *bw_out = bw;
+    *bc_out = bc;
+}
+
+// one thread: the four outputs of (slot, mass mi, parameter j) from the winner bc (HP_NONE: none was valid); none: all NaN
+__device__ void hp_store(const HpOut& o, size_t at, const double* p, const unsigned long long* key, size_t n, double m,
+                         unsigned long long bc, bool none, double p0, double pl) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double lo = nan, hi = nan, plo = nan, phi = nan;
+    if (!none) {
+        if (bc == HP_NONE) {                                   // n = 1, or m at least the knots' span
+            lo = sm_unkey(key[0]); hi = sm_unkey(key[n - 1]);
+            plo = p0; phi = pl;
+        } else {
+            hp_cand(p, key, n, m, bc, p0, pl, &lo, &hi, &plo, &phi);
+        }
+    }
+    if (o.lo) o.lo[at] = lo;
+    if (o.hi) o.hi[at] = hi;
+    if (o.plo) o.plo[at] = plo;
+    if (o.phi) o.phi[at] = phi;
+}
+
+// the knots of one segment over H: p_r = H_r / W.  scan: SM_BS doubles of LDS
+__device__ void hp_make_knots(const SmArgs& a, const SmSeg& s, const unsigned* id, double* H, size_t n, double* scan) {
+    const double W = hp_knots(a, s, id, H, n, scan);
+    for (size_t r = threadIdx.x; r < n; r += SM_BS) H[r] = H[r] / W;
+    __syncthreads();
+}
+
+// LDS path: k_sm_lds's grid and dynamic LDS
+template <bool HC>
+__global__ __launch_bounds__(SM_BS) void k_hp_lds(SmArgs a, HpMass hm, HpOut o, int n2, size_t b0) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long smk[];
+    __shared__ double red[3 * SM_BS];
+    __shared__ unsigned s_cnt;
+    __shared__ int s_bad;
+    unsigned long long* key = smk;
+    unsigned* id = (unsigned*)(smk + n2);
+    double* H = (double*)(smk + n2);
+    if (threadIdx.x == 0) { s_cnt = 0; s_bad = 0; }
+    __syncthreads();
+    const SmSeg s = sm_seg<HC>(a, b0 + blockIdx.y, (int)blockIdx.x);
+    sm_build_sort<true, HC>(a, s, 0, (int)a.K, n2, key, id, &s_cnt, &s_bad);
+    const size_t n = (size_t)s_cnt;
+    const bool none = s_bad != 0 || n == 0;
+    hp_make_knots(a, s, id, H, n, red);
+    const double p0 = none ? 0.0 : H[0], pl = none ? 0.0 : H[n - 1];
+    for (int mi = 0; mi < hm.nm; mi++) {                       // (red: the scan is done, the sweeps' pairs take its place)
+        double bw = 0.0;
+        unsigned long long bc = HP_NONE;
+        if (!none) hp_sweep(H, key, n, hm.m[mi], 0, 2ull * n, p0, pl, red, (unsigned long long*)(red + SM_BS), &bw, &bc);
+        if (threadIdx.x == 0) hp_store(o, (s.slot * (size_t)hm.nm + (size_t)mi) * a.P + s.j, H, key, n, hm.m[mi], bc, none, p0, pl);
+    }
+}
+
+// global path, 3: three kernels in the place of k_sm_eval_global, because a segment's 2 n candidates are n log n dependent reads of
+// global memory: too long a chain for the one work-group a segment has there, and a batch holds few segments.  The order of
+// (width, c) is total, so the split changes no bit.
+//   k_hp_knots_global   grid (P, batch targets): the knots p into the other key buffer
+//   k_hp_search_global  grid (P x HP_SPLIT, batch targets): slice sp of every mass's candidates, its best pair to
+//                       pw / pc[(seg nm + mi) HP_SPLIT + sp]
+//   k_hp_final_global   one thread per (segment, mass): the best of the slices' pairs, the winner evaluated again and written
+constexpr int HP_SPLIT = 8;
+
+__global__ __launch_bounds__(SM_BS) void k_hp_knots_global(SmArgs a, size_t b0, const unsigned* __restrict__ gid, double* gH,
+                                                           const unsigned* __restrict__ cnt) {
+    __shared__ double scan[SM_BS];
+    const int j = (int)blockIdx.x;
+    const size_t bl = blockIdx.y, seg = bl * a.P + j;
+    const SmSeg s = sm_seg(a, b0 + bl, j);
+    hp_make_knots(a, s, gid + seg * a.K, gH + seg * a.K, (size_t)cnt[seg], scan);
+}
+
+__global__ __launch_bounds__(SM_BS) void k_hp_search_global(SmArgs a, HpMass hm, const unsigned long long* __restrict__ gkey,
+                                                            const double* __restrict__ gp, const unsigned* __restrict__ cnt,
+                                                            const int* __restrict__ bad, double* __restrict__ pw,
+                                                            unsigned long long* __restrict__ pc) {
+    __shared__ double rw[SM_BS / 64];
+    __shared__ unsigned long long rc[SM_BS / 64];
+    const int j = (int)(blockIdx.x % (unsigned)a.P), sp = (int)(blockIdx.x / (unsigned)a.P);
+    const size_t seg = (size_t)blockIdx.y * a.P + j, n = (size_t)cnt[seg];
+    if (bad[seg] != 0 || n == 0) return;                       // (uniform; k_hp_final_global does not read the pairs then)
+    const unsigned long long* key = gkey + seg * a.K;
+    const double* p = gp + seg * a.K;
+    const double p0 = p[0], pl = p[n - 1];
+    const unsigned long long total = 2ull * n, per = (total + HP_SPLIT - 1) / HP_SPLIT;
+    const unsigned long long c0 = (unsigned long long)sp * per, c1 = (c0 + per < total) ? c0 + per : total;
+    for (int mi = 0; mi < hm.nm; mi++) {
+        double bw;
+        unsigned long long bc;
+        hp_sweep(p, key, n, hm.m[mi], c0, c1, p0, pl, rw, rc, &bw, &bc);     // (c0 >= c1: no candidate, the pair of none)
+        if (threadIdx.x == 0) {
+            const size_t at = (seg * (size_t)hm.nm + (size_t)mi) * HP_SPLIT + (size_t)sp;
+            pw[at] = bw;
+            pc[at] = bc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hp_final_global(SmArgs a, HpMass hm, HpOut o, size_t b0, size_t nseg,
+                                                         const unsigned long long* __restrict__ gkey, const double* __restrict__ gp,
+                                                         const unsigned* __restrict__ cnt, const int* __restrict__ bad,
+                                                         const double* __restrict__ pw, const unsigned long long* __restrict__ pc) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nseg * (size_t)hm.nm) return;
+    const size_t seg = g / (size_t)hm.nm, mi = g % (size_t)hm.nm, bl = seg / (size_t)a.P, j = seg % (size_t)a.P;
+    const size_t n = (size_t)cnt[seg];
+    const bool none = bad[seg] != 0 || n == 0;
+    const unsigned long long* key = gkey + seg * a.K;
+    const double* p = gp + seg * a.K;
+    double bw = __longlong_as_double(0x7ff0000000000000ll);
+    unsigned long long bc = HP_NONE;
+    if (!none)
+        for (int sp = 0; sp < HP_SPLIT; sp++) {
+            const double w2 = pw[g * HP_SPLIT + sp];
+            const unsigned long long c2 = pc[g * HP_SPLIT + sp];
+            if (w2 < bw || (w2 == bw && c2 < bc)) { bw = w2; bc = c2; }
+        }
+    hp_store(o, ((b0 + bl) * (size_t)hm.nm + mi) * a.P + j, p, key, n, hm.m[mi], bc, none, none ? 0.0 : p[0], none ? 0.0 : p[n - 1]);
+}
+
 // ---- tolerance path, rejection: one sort at K_max, every tolerance from it ----
 constexpr int SM_MAXT = 16;
 struct SmKs {
@@ -490,19 +728,25 @@ SmProbs sm_probs(const abc_summary* sum) {
 }
 
 // the B x a.P segments of a.K entries: sort and evaluation; ks: the tolerances of a rejection path (every one evaluated from the one
-// sort at a.K = K_max), NULL otherwise
-int sm_launch(abc_ctx* ctx, const SmArgs& a, const SmProbs& pr, size_t B, const SmKs* ks) {
+// sort at a.K = K_max), NULL otherwise; hp: the highest-density intervals in the place of the summary (pr is then not read)
+struct HpReq {
+    HpMass hm;
+    HpOut o;
+};
+int sm_launch(abc_ctx* ctx, const SmArgs& a, const SmProbs& pr, size_t B, const SmKs* ks, const HpReq* hp = nullptr) {
     const size_t K = a.K, P = (size_t)a.P;
     if (sm_use_lds(K)) {
         int n2 = 1;
         while ((size_t)n2 < K) n2 <<= 1;
         const size_t lds = (size_t)n2 * (ks ? 12 : 16);
         const auto lds_k = a.hcoef ? k_sm_lds<true> : k_sm_lds<false>;
-        ABC_HIP(ctx, hipFuncSetAttribute(ks ? (const void*)k_smp_lds : (const void*)lds_k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
+        const auto lds_h = a.hcoef ? k_hp_lds<true> : k_hp_lds<false>;
+        ABC_HIP(ctx, hipFuncSetAttribute(hp ? (const void*)lds_h : ks ? (const void*)k_smp_lds : (const void*)lds_k,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         for (size_t b0 = 0; b0 < B; b0 += SM_MAX_GRID_Y) {
             const size_t nb = (B - b0 < SM_MAX_GRID_Y) ? B - b0 : SM_MAX_GRID_Y;
-            if (ks) hipLaunchKernelGGL(k_smp_lds, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, *ks, n2, b0);
+            if (hp) hipLaunchKernelGGL(lds_h, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, hp->hm, hp->o, n2, b0);
+            else if (ks) hipLaunchKernelGGL(k_smp_lds, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, *ks, n2, b0);
             else hipLaunchKernelGGL(lds_k, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), lds, ctx->stream, a, pr, n2, b0);
             ABC_HIP(ctx, hipGetLastError());
         }
@@ -517,6 +761,13 @@ int sm_launch(abc_ctx* ctx, const SmArgs& a, const SmProbs& pr, size_t B, const 
     unsigned* cnt = (unsigned*)abc_ws_alloc(ctx, ns * 4);
     int* bad = (int*)abc_ws_alloc(ctx, ns * 4);
     if (!k0 || !k1 || !i0 || !i1 || !cnt || !bad) ABC_FAIL(ctx, ABC_ERR_NOMEM, "summary: workspace exhausted");
+    double* hpw = nullptr;
+    unsigned long long* hpc = nullptr;
+    if (hp) {                                                  // the slices' pairs of one batch
+        hpw = (double*)abc_ws_alloc(ctx, ns * HP_MAXM * HP_SPLIT * 8);
+        hpc = (unsigned long long*)abc_ws_alloc(ctx, ns * HP_MAXM * HP_SPLIT * 8);
+        if (!hpw || !hpc) ABC_FAIL(ctx, ABC_ERR_NOMEM, "hpd: workspace exhausted");
+    }
     const size_t nch = (K + SM_LDS_MAX - 1) / SM_LDS_MAX;
     const size_t lds_c = (size_t)SM_LDS_MAX * 12;
     const auto chunk_k = a.hcoef ? k_sm_chunk<true> : k_sm_chunk<false>;
@@ -538,7 +789,17 @@ int sm_launch(abc_ctx* ctx, const SmArgs& a, const SmProbs& pr, size_t B, const 
             unsigned long long* tk = ka; ka = kb; kb = tk;
             unsigned* ti = ia; ia = ib; ib = ti;
         }
-        if (ks)
+        if (hp) {
+            hipLaunchKernelGGL(k_hp_knots_global, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), 0, ctx->stream, a, b0, (const unsigned*)ia,
+                               (double*)kb, (const unsigned*)cnt);
+            ABC_HIP(ctx, hipGetLastError());
+            hipLaunchKernelGGL(k_hp_search_global, dim3((unsigned)(P * HP_SPLIT), (unsigned)nb), dim3(SM_BS), 0, ctx->stream, a, hp->hm,
+                               (const unsigned long long*)ka, (const double*)kb, (const unsigned*)cnt, (const int*)bad, hpw, hpc);
+            ABC_HIP(ctx, hipGetLastError());
+            hipLaunchKernelGGL(k_hp_final_global, dim3((unsigned)((nseg * hp->hm.nm + 255) / 256)), dim3(256), 0, ctx->stream, a, hp->hm,
+                               hp->o, b0, nseg, (const unsigned long long*)ka, (const double*)kb, (const unsigned*)cnt, (const int*)bad,
+                               (const double*)hpw, (const unsigned long long*)hpc);
+        } else if (ks)
             hipLaunchKernelGGL(k_smp_eval_global, dim3((unsigned)P, (unsigned)nb), dim3(SM_BS), 0, ctx->stream, a, pr, *ks, b0, ka, ia, kb,
                                ib);
         else
@@ -558,6 +819,26 @@ int launch_summary(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t 
     a.quant = sum->quant;
     a.cdf = sum->cdf;
     return sm_launch(ctx, a, sm_probs(sum), B, nullptr);
+}
+
+// the summary's sort, buffers and batches (the knots lie in the spare key buffer), and on the global path the slices' pairs
+size_t abc_hpd_need(size_t B, size_t K, size_t P) {
+    size_t b = abc_summary_need(B, K, P);
+    if (!sm_use_lds(K)) b += 2 * sm_batch(B, K, P) * P * HP_MAXM * HP_SPLIT * 8 + 2 * 256;
+    return b;
+}
+
+int launch_hpd(abc_ctx* ctx, const SmValues& sv, size_t B, size_t K, size_t P, const abc_hpd* hd) {
+    if (B == 0 || K == 0 || P == 0) return ABC_OK;
+    const SmArgs a = sm_args(sv, K, P);
+    HpReq hp;
+    memset(&hp, 0, sizeof(hp));
+    hp.hm.nm = (int)hd->nm;
+    for (size_t i = 0; i < hd->nm; i++) hp.hm.m[i] = hd->mass[i];
+    hp.o = HpOut{hd->lo, hd->hi, hd->plo, hd->phi};
+    SmProbs pr;
+    memset(&pr, 0, sizeof(pr));
+    return sm_launch(ctx, a, pr, B, nullptr, &hp);
 }
 
 size_t abc_path_summary_need(size_t B, const size_t* Ks, size_t T, size_t P, int method) {

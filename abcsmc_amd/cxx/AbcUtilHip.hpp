@@ -847,6 +847,52 @@ inline TargetEntropy knn_entropy(const Mat2D& values, int k = 4, const std::vect
     r.zeros = (size_t)zeros;
     return r;
 }
+// The same ranking followed by the highest-density interval of every target's posterior in every parameter: the shortest interval
+// that holds each mass (abc_particle_ranking_pls_targets_hpd; the definition is in the header; method and kernel as
+// particle_ranking_PLS_targets_summary).  Per target: lo, hi (nm x P, row m = mass[m]) and the probabilities plo, phi of the two
+// ends, so that (lo, hi) are the summary's quantiles at (plo, phi).
+struct TargetHpd {
+    Mat2D lo, hi, plo, phi;
+};
+namespace detail {
+inline TargetHpd target_hpd(const double* lo, const double* hi, const double* plo, const double* phi, size_t nm, size_t P) {
+    TargetHpd r{Mat2D(nm, P), Mat2D(nm, P), Mat2D(nm, P), Mat2D(nm, P)};
+    for (size_t k = 0; k < nm; k++)
+        for (size_t j = 0; j < P; j++) {
+            r.lo(k, j) = lo[k * P + j];
+            r.hi(k, j) = hi[k * P + j];
+            r.plo(k, j) = plo[k * P + j];
+            r.phi(k, j) = phi[k * P + j];
+        }
+    return r;
+}
+}  // namespace detail
+inline std::vector<TargetHpd> particle_ranking_PLS_targets_hpd(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                               const float_type train_frac, size_t K,
+                                                               const std::vector<double>& mass = {0.5, 0.95}, int method = 0,
+                                                               int kernel = 0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols(), nm = mass.size(), n = B * nm * P;
+    std::vector<double> lo(n), hi(n), plo(n), phi(n);
+    abc_hpd hd = {mass.data(), nm, lo.data(), hi.data(), plo.data(), phi.data()};
+    check(abc_particle_ranking_pls_targets_hpd(context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac,
+                                               max_components_ref(), component_rule(), nullptr, K, method, kernel, nullptr, nullptr,
+                                               nullptr, &hd, nullptr));
+    std::vector<TargetHpd> res(B);
+    for (size_t b = 0; b < B; b++)
+        res[b] = detail::target_hpd(lo.data() + b * nm * P, hi.data() + b * nm * P, plo.data() + b * nm * P, phi.data() + b * nm * P,
+                                    nm, P);
+    return res;
+}
+// The highest-density intervals of every column of values (K x P) with the given weights (empty: equal) (abc_weighted_hpd).
+inline TargetHpd weighted_hpd(const Mat2D& values, const std::vector<double>& weights = {}, const std::vector<double>& mass = {0.95}) {
+    const size_t K = values.rows(), P = values.cols(), nm = mass.size(), n = nm * P;
+    if (!weights.empty() && weights.size() != K) throw HipError(ABC_ERR_INVALID, "weights needs one entry per row");
+    std::vector<double> lo(n), hi(n), plo(n), phi(n);
+    abc_hpd hd = {mass.data(), nm, lo.data(), hi.data(), plo.data(), phi.data()};
+    check(abc_weighted_hpd(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &hd));
+    return detail::target_hpd(lo.data(), hi.data(), plo.data(), phi.data(), nm, P);
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

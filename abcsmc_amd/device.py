@@ -509,3 +509,27 @@ def weighted_entropy(V, w=None, k=4, scale=None, knn=True, ctx=None):
     holder as weighted_summary's; w must be None (the library refuses weights); the other arguments as rank_targets_entropy.
     Returns dict(H (0-d), knn (K,) or None, zeros (0-d) int64) as device tensors."""
     return _weighted_product("entropy", lambda lead, P, dev: _entropy(k, scale, lead, V.shape[1], P, dev, knn), V, w, ctx)
+
+
+def _hpd(mass, lead, P, dev, outputs):
+    """Device tensors for the highest-density intervals of prod(lead) targets with P parameters and the abc_hpd pointing at them"""
+    ms = np.ascontiguousarray(np.asarray(mass, dtype=np.float64).reshape(-1))
+    r = {k: (torch.empty(lead + (ms.size, P), dtype=torch.float64, device=dev) if k in outputs else None)
+         for k in ("lo", "hi", "plo", "phi")}
+    return _lib.Hpd(ms.ctypes.data, ms.size, _ptr(r["lo"]), _ptr(r["hi"]), _ptr(r["plo"]), _ptr(r["phi"])), r, (ms,)
+
+
+def rank_targets_hpd(X, model, A, targets, K, Y, mass=(0.5, 0.95), method=_lib.POSTERIOR_REJECTION, kernel=_lib.KERNEL_EPANECHNIKOV,
+                     exclude=None, dist=False, adjust=(), outputs=("lo", "hi", "plo", "phi"), ctx=None):
+    """rank_targets followed by the highest-density interval of every (target, parameter): the shortest interval that holds each
+    mass (abc_rank_targets_hpd_dev; method 0 rejection, 1 loclinear; the definition is in the header).  mass: 1 to 16 host values
+    inside (0, 1).  outputs: the members to compute, the others are None.  Returns dict(idx (B, K) int64, dist (B, K) or None, lo,
+    hi, plo, phi (B, nm, P), and the adjust members); (lo, hi) are rank_targets_summary's quantiles at probs = (plo, phi)."""
+    return _rank_targets_product("hpd", lambda lead, P, dev: _hpd(mass, lead, P, dev, outputs), X, model, A, targets, K, Y, method,
+                                 kernel, exclude, dist, adjust, ctx)
+
+
+def weighted_hpd(V, w=None, mass=(0.95,), outputs=("lo", "hi", "plo", "phi"), ctx=None):
+    """The highest-density intervals of P columns of K values (abc_weighted_hpd_dev).  V: (P, K) holder as weighted_summary's; w: K
+    weights or None (equal).  Returns dict(lo, hi, plo, phi (nm, P)) as device tensors."""
+    return _weighted_product("hpd", lambda lead, P, dev: _hpd(mass, lead, P, dev, outputs), V, w, ctx)

@@ -982,6 +982,55 @@ int abc_weighted_entropy_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K
 /* HOST-pointer form: V is K x P column-major (ldv = K); en's arrays in host memory. */
 int abc_weighted_entropy(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_entropy* en);
 
+/* ---- highest-density intervals of the batched ranking: the shortest interval that holds a given mass --------------------------
+ * The interval an analyst reports as "the 95 % credible interval" of a skewed, bounded posterior (the HPD interval or HDI, as
+ * coda::HPDinterval), where the summaries' quantiles give equal-tailed intervals only.  A segment, its sorted entries
+ * u_0 .. u_{n-1}, its knots p_r = fma(-0.5, om_r, W_r) / W and the quantile function Q(q) are the summaries' above; the device
+ * takes the same sums in the same fixed order as the summaries, so p_r and W are the summary call's bits for the same segment.
+ * For a mass m, 0 < m < 1, the candidates are numbered c = 2 r + kind, r = 0..n-1 (fl: one fp64 rounding):
+ *   kind 0 (lower end on knot r):  plo = p_r,          phi = fl(p_r + m),  lo = u_r,     hi = Q(phi),  valid iff phi <= p_{n-1}
+ *   kind 1 (upper end on knot r):  plo = fl(p_r - m),  phi = p_r,          lo = Q(plo),  hi = u_r,     valid iff plo >= p_0
+ * with Q evaluated by the summaries' expressions (the largest r with p_r <= q, then t, then fma(t, u_{r+1} - u_r, u_r)).  The
+ * result is the valid candidate with the smallest (hi - lo, c) in lexicographic order, the width in fp64: a total order, so the
+ * answer does not depend on the shape of the reduction.  If no candidate is valid (n = 1, or m at least the knots' span):
+ * lo = u_0, hi = u_{n-1}, plo = p_0, phi = p_{n-1}.  A non-finite value in the segment, or n = 0, makes all four outputs of that
+ * segment NaN and affects nothing else.
+ * Why: between the first and the last knot Q is piecewise linear, so Q(p + m) - Q(p) is piecewise linear in p with its breakpoints
+ * exactly at these candidates, and a minimum lies on one of them; the search is restricted to [p_0, p_{n-1} - m] so that the flat
+ * tails of Q cannot donate free mass.  The result is the exact minimiser for the project's own quantile convention, not a grid
+ * approximation.  With equal weights and integer n m it is coda::HPDinterval's interval [x_i, x_{i + n m}]; a NumPy prototype
+ * agreed with coda's rule on gamma-distributed samples, but it has NOT been compared with R itself.
+ * Guarantees.  With equal weights (as the summaries': method 0; method 1 with kernel 1 or the fallback; generic with w NULL) the
+ * outputs are the reference's bits.  A target gives the same bits on a repeat run, alone (B = 1) and in any batch, through the
+ * device and host entries, and whichever outputs are requested.  (lo, hi) are the bits that the summary call on the same segment
+ * returns for probs = {plo, phi}, as long as the knot at the winning end is not tied with a later knot (two neighbouring weights
+ * both below the rounding of W can tie knots; the summary then answers from the last of them).  With unequal weights the knots
+ * differ from the reference's by the rounding of the other summation order, as the summaries' do.
+ * Layout: lo, hi, plo, phi B x nm x P row-major ([b][m][j]); generic entry nm x P.  Limits are the summaries': A <= 64,
+ * P <= 1024 (ABC_ERR_UNSUPPORTED beyond), any K <= N.  There is no form for tolerance paths (abc_rank_targets_path_*) and none in
+ * the sharded driver. */
+typedef struct {
+    const double* mass;  size_t nm;   /* 1..16 finite masses strictly inside (0, 1), any order; host memory in every entry */
+    double* lo;  double* hi;          /* optional; B x nm x P ([b][m][j]); generic entry nm x P                           */
+    double* plo; double* phi;         /* optional; the probabilities of the two ends, same layout                         */
+} abc_hpd;                            /* at least one output required                                                      */
+/* Device pointers; the arguments of abc_rank_targets_summary_dev with hd in place of sum.  idx, dist and adj are optional and
+ * receive the bits of the plain calls.  Besides the ranking's, the adjustment's and the method / kernel checks, ABC_ERR_INVALID
+ * for NULL hd, nm = 0 or > 16, NULL mass, a mass that is NaN or outside (0, 1), and all four outputs NULL. */
+int abc_rank_targets_hpd_dev(abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
+                             const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
+                             size_t K, int method, int kernel, uint64_t* idx, double* dist, const abc_adjust_out* adj,
+                             const abc_hpd* hd);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_summary); every array of adj and hd in host memory. */
+int abc_particle_ranking_pls_targets_hpd(abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M, size_t P,
+                                         const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                         const uint64_t* exclude, size_t K, int method, int kernel, uint64_t* idx, double* dist,
+                                         const abc_adjust_out* adj, const abc_hpd* hd, int32_t* ncomp);
+/* The same of P given columns of K values (as abc_weighted_summary_dev, with its checks of V, ldv, K, P and w). */
+int abc_weighted_hpd_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, size_t P, const double* w, const abc_hpd* hd);
+/* HOST-pointer form: V is K x P column-major (ldv = K); w and hd's arrays in host memory. */
+int abc_weighted_hpd(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_hpd* hd);
+
 /* ---- Box-Cox transform of the metrics: the skewness search and the transform (ABC::optimize_box_cox, AbcUtil.cpp:89-109) ---------
  * PLS is linear; simulated metrics (counts, sizes, durations) are positive and right-skewed.  The reference searches, per metric, a
  * grid of exponents for the lambda whose transform (x^lambda - 1) / lambda has the smallest |skewness| (its ranking carries the
