@@ -259,6 +259,7 @@ SIGNATURES = {
     "abc_ctx_set_alias_mode": (_i, [_vp, _i]),
     "abc_alias_stats": (_i, [_vp, _vp, _vp, _i]),
     "abc_select_stats": (_i, [_vp, _vp, _vp, _i]),
+    "abc_ws_info": (_i, [_vp, _vp, _vp, _vp]),
     "abc_alias_table": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "abc_ctx_synchronize": (_i, [_vp]),
     "abc_version": (_i, []),
@@ -436,6 +437,13 @@ class Context:
         a, b = C.c_uint64(0), C.c_uint64(0)
         self.check(lib().abc_select_stats(self._h, C.byref(a), C.byref(b), int(reset)))
         return a.value, b.value
+
+    def ws_info(self):
+        """(reserved, asked, peak) of the scratch arena after the most recent call (abc_ws_info): the arena's bytes, the bound that
+        call reserved before the rounding to 1 MiB, and the highest offset its allocations reached"""
+        r, a, p = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self.check(lib().abc_ws_info(self._h, C.byref(r), C.byref(a), C.byref(p)))
+        return r.value, a.value, p.value
 
     def generation_giveups(self):
         """proposals the most recent generation call gave up on (abc_generation_giveups); no synchronisation"""

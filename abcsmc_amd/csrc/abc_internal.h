@@ -65,6 +65,8 @@ struct abc_ctx {
     char* ws;
     size_t ws_bytes;
     size_t ws_off;
+    size_t ws_asked;       // bytes the entry point passed to the last abc_ws_reserve, before the rounding (abc_ws_info)
+    size_t ws_peak;        // largest ws_off an abc_ws_alloc has reached since then: the hand rewinds of ws_off do not lower it
     // pinned host scratch
     char* pin;
     size_t pin_bytes;

@@ -10,6 +10,8 @@
 
 // ---- workspace -------------------------------------------------------------------------------
 int abc_ws_reserve(abc_ctx* ctx, size_t bytes) {
+    ctx->ws_asked = bytes;
+    ctx->ws_peak = 0;
     bytes = abc_align(bytes, 1 << 20);
     if (bytes > ctx->ws_bytes) {
         ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -29,6 +31,7 @@ void* abc_ws_alloc(abc_ctx* ctx, size_t bytes) {
     const size_t off = abc_align(ctx->ws_off, 256);
     if (off + bytes > ctx->ws_bytes) return nullptr;
     ctx->ws_off = off + bytes;
+    if (ctx->ws_off > ctx->ws_peak) ctx->ws_peak = ctx->ws_off;
     return ctx->ws + off;
 }
 int abc_pin_reserve(abc_ctx* ctx, size_t bytes) {
@@ -126,6 +129,14 @@ extern "C" void abc_ctx_destroy(abc_ctx* ctx) {
 }
 
 extern "C" const char* abc_last_error(const abc_ctx* ctx) { return ctx ? ctx->err : "null context"; }
+
+extern "C" int abc_ws_info(const abc_ctx* ctx, size_t* reserved, size_t* asked, size_t* peak) {
+    if (!ctx) return ABC_ERR_INVALID;
+    if (reserved) *reserved = ctx->ws_bytes;
+    if (asked) *asked = ctx->ws_asked;
+    if (peak) *peak = ctx->ws_peak;
+    return ABC_OK;
+}
 
 extern "C" int abc_ctx_set_stream(abc_ctx* ctx, void* hip_stream) {
     if (!ctx) return ABC_ERR_INVALID;

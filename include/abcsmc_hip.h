@@ -194,6 +194,16 @@ int  abc_generation_repeats(abc_ctx* ctx, uint64_t* ranking_repeats, uint64_t* g
  * and the single-target path.  The generation drivers read the flag at a later synchronisation of their own and report their
  * repeat through abc_generation_repeats, not here.  Host-side counters; neither changes a result.  No synchronisation. */
 int  abc_select_stats(abc_ctx* ctx, uint64_t* bin_selections, uint64_t* bin_giveups, int reset);
+/* The context's scratch arena as the most recent entry point left it.  Every call first reserves an upper bound of the device
+ * scratch it will take and then allocates from it block by block; the arena only grows.  *reserved: the arena's size in bytes;
+ * *asked: the bound that call reserved, before it is rounded up to 1 MiB; *peak: the highest offset any allocation of that call
+ * reached, counted at every allocation, so that space a call hands back and takes again counts once.  peak <= asked <= reserved
+ * after every call that returned ABC_OK; the tests hold every entry point to it (tests/test_gpu_arena.py).  Where the Wilcoxon
+ * reduction repeats itself on its sorted path it works in a temporary arena of its own: peak then keeps counting against that
+ * arena, and may pass asked, which bounds the context's own arena only.  An entry point that takes nothing from the arena (the
+ * setters and getters, abc_stats_shift_dev, abc_gather_rows_dev, ...) leaves the three values as the call before it did; all are 0
+ * on a new context.  Any pointer may be NULL.  Host-side values, no synchronisation; nothing about a result depends on them. */
+int  abc_ws_info(const abc_ctx* ctx, size_t* reserved, size_t* asked, size_t* peak);
 /* Optional per-stage timing: HIP events recorded on the context's stream around each stage
  * (and around the k_gram / k_kde kernels alone).  abc_timing_read synchronises, then returns the
  * number of stages; names[i] is a static string, ms[i] the accumulated device time, host_ms[i]
