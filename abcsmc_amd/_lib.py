@@ -186,6 +186,26 @@ class Hpd(C.Structure):
                 ("phi", C.c_void_p)]
 
 
+GLM_MAX = 32
+GLM_OUTPUTS = ("dens", "lo_x", "step", "mode", "mode_dens", "mean", "var", "ess", "log_md", "C", "c0", "sigma_s", "T", "peaks", "c",
+               "status")
+
+
+class Glm(C.Structure):
+    """abc_glm: G, cut, bw_scale, then bw (optional input) and the optional outputs in GLM_OUTPUTS' order (memory as the entry
+    point's other arrays)"""
+    _fields_ = ([("G", C.c_size_t), ("cut", C.c_double), ("bw_scale", C.c_double), ("bw", C.c_void_p)] +
+                [(name, C.c_void_p) for name in GLM_OUTPUTS])
+
+
+def glm_shapes(lead, K, P, n, G):
+    """The shape of every output of an abc_glm for targets of shape lead (() for the generic entry) with n components"""
+    lead = tuple(lead)
+    return {"dens": lead + (P, G), "lo_x": lead + (P,), "step": lead + (P,), "mode": lead + (P,), "mode_dens": lead + (P,),
+            "mean": lead + (P,), "var": lead + (P,), "ess": lead, "log_md": lead, "C": lead + (n, P), "c0": lead + (n,),
+            "sigma_s": lead + (n, n), "T": lead + (P, P), "peaks": lead + (K, P), "c": lead + (K,), "status": lead}
+
+
 def _draws_stream(stream, n):
     """The stream ids of an abc_draws as a C-contiguous uint64 host array of n entries, or None (target b takes id b)"""
     import numpy as np
@@ -343,6 +363,11 @@ SIGNATURES = {
     "abc_ctx_create_multi": (_i, [_vp, _i, _vp]),
     "abc_generation_sharded_dev": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "abc_generation_multi": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    # ABC-GLM: the descriptor first, the context second
+    "abc_glm_rank_targets_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp]),
+    "abc_glm_particle_ranking_pls_targets": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "abc_glm_weighted_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "abc_glm_weighted": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
 }
 
 # The posterior products (abc_summary, abc_density, abc_joint, abc_draws) share their four argument lists, each ending in the product's

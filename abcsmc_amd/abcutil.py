@@ -590,6 +590,8 @@ def weighted_draws(values, weights=None, S=1000, smooth=False, seed=0, bw=None, 
 _UNWEIGHTED = ("particle_ranking_PLS_targets_entropy", "knn_entropy")
 # The highest-density intervals (hpd.py) are forwarded the same way; they do work under row importance weights and any others.
 _INTERVALS = ("particle_ranking_PLS_targets_hpd", "weighted_hpd")
+# The ABC-GLM posterior (glm.py) likewise: an estimator of its own on the ranking's rows, under row importance weights too.
+_GLM = ("particle_ranking_PLS_targets_glm", "weighted_glm", "cross_validate_pls_glm")
 
 
 def __getattr__(name):
@@ -599,6 +601,9 @@ def __getattr__(name):
     if name in _INTERVALS:
         from . import hpd
         return getattr(hpd, name)
+    if name in _GLM:
+        from . import glm
+        return getattr(glm, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

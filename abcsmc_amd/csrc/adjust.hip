@@ -1029,10 +1029,9 @@ struct AjPlan {
 
 AjPlan aj_plan(size_t K, int nc, int P) {
     AjPlan p;
-    p.nch = (K + 255) / 256;
-    if (p.nch > 64) p.nch = 64;
-    p.CH = (K + p.nch - 1) / p.nch;
-    p.nch = (K + p.CH - 1) / p.CH;
+    const AjChunks ck = aj_chunks(K);
+    p.nch = ck.nch;
+    p.CH = ck.CH;
     const int D = 1 + nc + P, Ds = aj_stride(nc, P);
     int tr = (AJ_TILE_DBL - (D + 1) - 2) / (Ds + 1);
     if (tr > 128) tr = 128;                                 // (LDS for several work-groups per CU)

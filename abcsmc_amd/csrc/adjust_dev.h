@@ -23,6 +23,20 @@ __device__ __forceinline__ double aj_val(const AjSrc& s, size_t i, int c, int nc
     return (c < nc) ? s.S[i + s.sld * (size_t)c] : s.Y[i + s.ldy * (size_t)(c - nc)];
 }
 
+// chunks of a target's K retained rows for the chunked moment passes (adjust.hip, glm.hip): about 256 rows each, 64 chunks at
+// most; from K alone, so that a target's sums do not depend on the batch or on the fit
+struct AjChunks {
+    size_t nch, CH;          // chunks and their size
+};
+static inline AjChunks aj_chunks(size_t K) {
+    AjChunks p;
+    p.nch = (K + 255) / 256;
+    if (p.nch > 64) p.nch = 64;
+    p.CH = (K + p.nch - 1) / p.nch;
+    p.nch = (K + p.CH - 1) / p.CH;
+    return p;
+}
+
 // the Epanechnikov weights of a target are all 0 exactly when its first one is (d ascending, w non-increasing in d)
 __device__ __forceinline__ bool aj_fallback(const double* d, size_t K) {
     const double h = d[K - 1];

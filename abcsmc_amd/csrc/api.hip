@@ -1846,8 +1846,8 @@ struct Product {
     bool equal_weights() const { return kind == ENTROPY; }
 };
 
-// what follows the ranking: nothing, the adjustment, a posterior product, the tolerance path
-enum { TG_PLAIN, TG_ADJUST, TG_PRODUCT, TG_PATH };
+// what follows the ranking: nothing, the adjustment, a posterior product, the tolerance path, the ABC-GLM posterior (glm.hip)
+enum { TG_PLAIN, TG_ADJUST, TG_PRODUCT, TG_PATH, TG_GLM };
 struct TgRequest {                             // (members in the order of the entries' arguments)
     int kind;
     const double* X;  size_t ldx;
@@ -1865,6 +1865,8 @@ struct TgRequest {                             // (members in the order of the e
     Product prod;                              // TG_PRODUCT; TG_PATH: none or the summaries (method: of those)
     bool any_excl = false;                     // exclude names a row for some target: set by tg_check
     const abc_path* path = nullptr;            // TG_PATH only: required; Ks in host memory
+    const abc_glm* glm = nullptr;              // TG_GLM only: required
+    int* glm_nc = nullptr;                     // TG_GLM, optional: receives the model's ncomp once the run has read it (host)
     bool segments() const { return kind == TG_PRODUCT; }      // the rows' values are read after the ranking
     bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
     bool path_summary() const { return kind == TG_PATH && prod.kind == Product::SUMMARY; }      // prod: the summaries at every tolerance
@@ -1875,6 +1877,78 @@ struct TgRequest {                             // (members in the order of the e
     }
 };
 }  // namespace
+
+// the descriptor of an ABC-GLM request, its limits and the context's settings it refuses (A: 0 where the caller has none)
+static int glm_check(abc_ctx* ctx, const char* fn, const abc_glm* m, size_t P, size_t A) {
+    if (!m) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (glm is required)", fn);
+    if (ctx->tf_buf) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: parameter transforms are set on the context, and ABC-GLM is not an adjustment", fn);
+    if (ctx->hcorr) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: the variance correction is set on the context, and ABC-GLM is not an adjustment", fn);
+    if (ctx->rg_L) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: ridge is set on the context, and ABC-GLM is not an adjustment", fn);
+    if (P == 0 || P > ABC_GLM_MAX) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: P = %zu parameters (1 to %d)", fn, P, ABC_GLM_MAX);
+    if (A > 64) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: A = %zu components (at most 64)", fn, A);
+    if (m->G < 2 || m->G > 4096) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: G = %zu grid points (2 to 4096)", fn, m->G);
+    if (!(m->cut >= 0.0) || !std::isfinite(m->cut)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: cut = %g (finite, >= 0)", fn, m->cut);
+    if (!(m->bw_scale > 0.0) || !std::isfinite(m->bw_scale))
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: bw_scale = %g (finite, > 0)", fn, m->bw_scale);
+    if (!m->dens && !m->lo_x && !m->step && !m->mode && !m->mode_dens && !m->mean && !m->var && !m->ess && !m->log_md && !m->C &&
+        !m->c0 && !m->sigma_s && !m->T && !m->peaks && !m->c && !m->status)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of glm is NULL", fn);
+    return ABC_OK;
+}
+// the model's ncomp of a device model record (synchronises), within ABC-GLM's limit
+static int glm_ncomp(abc_ctx* ctx, const char* fn, const double* model, size_t A, size_t* n) {
+    double hdr = 0.0;
+    ABC_HIP(ctx, hipMemcpyAsync(&hdr, model, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n = hdr < 0.0 ? 0 : (hdr > (double)A ? A : (size_t)hdr);      // the ranking's tg_ncomp
+    if (*n == 0 || *n > ABC_GLM_MAX) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: the model has %zu components (1 to %d)", fn, *n, ABC_GLM_MAX);
+    return ABC_OK;
+}
+// an abc_glm's arrays for B targets, host (h) <-> arena: NULL members stay NULL; C, c0 and sigma_s with room for nA components
+static size_t glm_stage_bytes(const abc_glm* h, size_t B, size_t K, size_t P, size_t nA) {
+    if (nA > ABC_GLM_MAX) nA = ABC_GLM_MAX;
+    return B * (P * (h->G + 8) + 2 + nA * (P + 1 + nA) + P * P + K * (P + 1) + 1) * 8 + 40 * 256;
+}
+static abc_glm glm_stage(Stage& s, const abc_glm* h, size_t B, size_t K, size_t P, size_t nA) {
+    if (nA > ABC_GLM_MAX) nA = ABC_GLM_MAX;
+    abc_glm d = *h;
+    d.bw = h->bw ? s.up(h->bw, B * P) : nullptr;
+    d.dens = h->dens ? s.dev<double>(B * P * h->G) : nullptr;
+    d.lo_x = h->lo_x ? s.dev<double>(B * P) : nullptr;
+    d.step = h->step ? s.dev<double>(B * P) : nullptr;
+    d.mode = h->mode ? s.dev<double>(B * P) : nullptr;
+    d.mode_dens = h->mode_dens ? s.dev<double>(B * P) : nullptr;
+    d.mean = h->mean ? s.dev<double>(B * P) : nullptr;
+    d.var = h->var ? s.dev<double>(B * P) : nullptr;
+    d.ess = h->ess ? s.dev<double>(B) : nullptr;
+    d.log_md = h->log_md ? s.dev<double>(B) : nullptr;
+    d.C = h->C ? s.dev<double>(B * nA * P) : nullptr;
+    d.c0 = h->c0 ? s.dev<double>(B * nA) : nullptr;
+    d.sigma_s = h->sigma_s ? s.dev<double>(B * nA * nA) : nullptr;
+    d.T = h->T ? s.dev<double>(B * P * P) : nullptr;
+    d.peaks = h->peaks ? s.dev<double>(B * K * P) : nullptr;
+    d.c = h->c ? s.dev<double>(B * K) : nullptr;
+    d.status = h->status ? s.dev<int32_t>(B) : nullptr;
+    return d;
+}
+static void glm_down(Stage& s, const abc_glm* h, const abc_glm& d, size_t B, size_t K, size_t P, size_t n) {
+    s.down(h->dens, d.dens, B * P * h->G);
+    s.down(h->lo_x, d.lo_x, B * P);
+    s.down(h->step, d.step, B * P);
+    s.down(h->mode, d.mode, B * P);
+    s.down(h->mode_dens, d.mode_dens, B * P);
+    s.down(h->mean, d.mean, B * P);
+    s.down(h->var, d.var, B * P);
+    s.down(h->ess, d.ess, B);
+    s.down(h->log_md, d.log_md, B);
+    s.down(h->C, d.C, B * n * P);
+    s.down(h->c0, d.c0, B * n);
+    s.down(h->sigma_s, d.sigma_s, B * n * n);
+    s.down(h->T, d.T, B * P * P);
+    s.down(h->peaks, d.peaks, B * K * P);
+    s.down(h->c, d.c, B * K);
+    s.down(h->status, d.status, B);
+}
 
 // the tolerance list of a path request
 static int path_check(abc_ctx* ctx, const char* fn, const abc_path* path) {
@@ -1904,7 +1978,8 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: P = %zu, but the parameter transforms were set for %zu parameters", fn, r.P, ctx->tf_P);
     if (!r.X) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (X is required)", fn);
     if (!r.targets) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (targets is required)", fn);
-    if (!r.idx && !summary && !r.path_summary()) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (idx is required)", fn);
+    if (!r.idx && !summary && !r.path_summary() && r.kind != TG_GLM)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (idx is required)", fn);
     if (!r.Y && (host || !plain)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (Y is required)", fn);
     if (!r.Y && r.post_mean && r.P) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: post_mean needs Y", fn);
     if (!host) {
@@ -1919,6 +1994,7 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
     if (!plain && r.kernel != ABC_KERNEL_EPANECHNIKOV && r.kernel != ABC_KERNEL_RECTANGULAR)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: kernel %d (0 = Epanechnikov, 1 = rectangular)", fn, r.kernel);
     if ((!plain || r.post_mean) && r.P && r.ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, r.ldy, N);
+    if (r.kind == TG_GLM) ABC_TRY(glm_check(ctx, fn, r.glm, r.P, r.A));
     if (!plain) {     // the adjustment's limits, for both of a product's methods too
         if (r.A > 64) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: A = %zu components (at most 64)", fn, r.A);
         if (r.P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, r.P);
@@ -1968,6 +2044,7 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     if (r.regress()) b += abc_adjust_need(N, A, P, B, K, hc, rg);
     if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T, hc, rg);
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
+    if (r.kind == TG_GLM) b += 2 * B * K * 8 + 16 * 256 + abc_glm_need(B, K, P, A, r.glm->G);
     // (under row importance weights the rejection path's summaries take the loclinear path's route, one tolerance at a time)
     if (r.path_summary())
         b += abc_path_summary_need(B, r.path->Ks, r.path->T, P, ctx->rw_N ? 1 : r.method) + (r.idx ? 0 : B * K * 8 + 256);
@@ -1978,8 +2055,9 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     b += (B * M + B + 2 * B * K) * 8 + 8 * 256;                                   // targets, exclude, idx, dist
     if (r.kind == TG_PLAIN) b += B * P * 8;                                       // post_mean
     else if (r.kind == TG_PATH) b += B * r.path->T * ((A + 2) * P + 2) * 8 + 8 * 256;      // abc_path: post_mean, coef, rank + status, h
-    else b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;            // abc_adjust_out: theta, weight, coef, rank + status
+    else if (r.kind != TG_GLM) b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;      // abc_adjust_out: theta, weight, coef, rank + status
     if (r.path_summary()) return b + B * P * (r.path->T * (r.prod.sum->nq + 1) + 1) * 8 + 16 * 256;     // truth, quant, cdf
+    if (r.kind == TG_GLM) b += glm_stage_bytes(r.glm, B, K, P, A);
     return b + r.prod.stage_bytes(B, K, P);
 }
 
@@ -2017,6 +2095,19 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
         Yt = (double*)abc_ws_alloc(ctx, r.N * r.P * 8);
         if (!Yt) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
         ABC_TRY(launch_param_transf(ctx, &tf, r.Y, r.ldy, r.N, r.P, 0, Yt, r.N, ctx->tf_outside_dev));
+    }
+    if (r.kind == TG_GLM) {     // the ranking with its scores kept, the model's ncomp, the GLM on the retained rows
+        if (!ix) ix = (uint64_t*)abc_ws_alloc(ctx, B * K * 8);
+        if (!d) d = (double*)abc_ws_alloc(ctx, B * K * 8);
+        if (!ix || !d) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+        size_t n = 0;
+        ABC_TRY(glm_ncomp(ctx, fn, r.model, r.A, &n));      // (before the ranking: a model beyond the limit runs nothing)
+        if (r.glm_nc) *r.glm_nc = (int)n;
+        abc_tg_scores sc;
+        ABC_TRY(launch_rank_targets(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
+                                    r.any_excl, K, ix, d, nullptr, &sc));
+        return launch_glm(ctx, tg_values(r, ix, nullptr, om), sc.S, sc.sld, r.Y, r.ldy, ix, om, nullptr, sc.O, sc.KCO, B, K, r.P, n,
+                          r.A, r.glm, fn);
     }
     if (r.kind == TG_PATH) {
         const bool ps = r.path_summary(), lin = ps && r.method == ABC_POSTERIOR_LOCLINEAR;
@@ -2140,8 +2231,16 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
     } else {
         r.prod = h.prod.stage(s, B, K, P);
     }
+    abc_glm gd = {};
+    int gnc = 0;
+    if (h.kind == TG_GLM) {
+        gd = glm_stage(s, h.glm, B, K, P, A);
+        r.glm = &gd;
+        r.glm_nc = &gnc;
+    }
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_TRY(tg_run(ctx, fn, r));
+    if (h.kind == TG_GLM) glm_down(s, h.glm, gd, B, K, P, (size_t)gnc);
     s.down(h.idx, r.idx, B * K);
     s.down(h.dist, r.dist, B * K);
     s.down(h.post_mean, r.post_mean, B * P);
@@ -2366,6 +2465,81 @@ extern "C" int abc_particle_ranking_pls_targets_draws(abc_ctx* ctx, const double
     const TgRequest h{TG_PRODUCT, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist, nullptr, method, kernel,
                       adj, Product(dr)};
     return tg_host(ctx, "abc_particle_ranking_pls_targets_draws", h, train_frac, max_comp, rule, ncomp);
+}
+
+// ---- ABC-GLM posterior of the batched ranking (glm.hip): the descriptor first, the call is a method of the request ----
+static TgRequest glm_request(const abc_glm* glm, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N, size_t M, size_t P,
+                             const double* model, size_t A, const double* targets, size_t ldt, size_t B, const uint64_t* exclude,
+                             size_t K, uint64_t* idx, double* dist) {
+    TgRequest r{TG_GLM, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist};
+    r.glm = glm;
+    return r;
+}
+
+extern "C" int abc_glm_rank_targets_dev(const abc_glm* glm, abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy,
+                                        size_t N, size_t M, size_t P, const double* model, size_t A, const double* targets, size_t ldt,
+                                        size_t B, const uint64_t* exclude, size_t K, uint64_t* idx, double* dist) {
+    CHECK_CTX(ctx);
+    return tg_dev(ctx, "abc_glm_rank_targets_dev",
+                  glm_request(glm, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist));
+}
+
+extern "C" int abc_glm_particle_ranking_pls_targets(const abc_glm* glm, abc_ctx* ctx, const double* X, const double* Y, size_t N,
+                                                    size_t M, size_t P, const double* targets, size_t B, double train_frac,
+                                                    int max_comp, int rule, const uint64_t* exclude, size_t K, uint64_t* idx,
+                                                    double* dist, int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    return tg_host(ctx, "abc_glm_particle_ranking_pls_targets",
+                   glm_request(glm, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist), train_frac, max_comp, rule,
+                   ncomp);
+}
+
+// the generic form: any retained sample with any statistics, B = 1
+static int glm_weighted_check(abc_ctx* ctx, const char* fn, const abc_glm* glm, const double* theta, size_t ldv, const double* stats,
+                              size_t lds, size_t K, size_t P, size_t n, const double* obs) {
+    ABC_TRY(glm_check(ctx, fn, glm, P, 0));
+    if (!theta) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (theta is required)", fn);
+    if (!stats) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (stats is required)", fn);
+    if (!obs) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (obs is required)", fn);
+    if (K == 0) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: K == 0", fn);
+    if (n == 0 || n > ABC_GLM_MAX) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: n = %zu statistics (1 to %d)", fn, n, ABC_GLM_MAX);
+    if (ldv < K) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldv %zu < K %zu", fn, ldv, K);
+    if (lds < K) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: lds %zu < K %zu", fn, lds, K);
+    if (K >= ((size_t)1 << 32)) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: K = %zu rows (at most 2^32 - 1)", fn, K);
+    return ABC_OK;
+}
+
+static SmValues weighted_values(const double* V, size_t ldv, const double* w);
+
+extern "C" int abc_glm_weighted_dev(const abc_glm* glm, abc_ctx* ctx, const double* theta, size_t ldv, const double* stats, size_t lds,
+                                    size_t K, size_t P, size_t n, const double* obs, const double* w) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_glm_weighted_dev";
+    ABC_TRY(glm_weighted_check(ctx, fn, glm, theta, ldv, stats, lds, K, P, n, obs));
+    ABC_TRY(abc_ws_reserve(ctx, abc_glm_need(1, K, P, n, glm->G) + 16 * 256));
+    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
+    return launch_glm(ctx, weighted_values(theta, ldv, w), stats, lds, theta, ldv, nullptr, nullptr, w, obs, (int)n, 1, K, P, n, n, glm, fn);
+}
+
+extern "C" int abc_glm_weighted(const abc_glm* glm, abc_ctx* ctx, const double* theta, const double* stats, size_t K, size_t P, size_t n,
+                                const double* obs, const double* w) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_glm_weighted";
+    ABC_TRY(glm_weighted_check(ctx, fn, glm, theta, K, stats, K, K, P, n, obs));
+    ABC_TRY(abc_ws_reserve(ctx, abc_glm_need(1, K, P, n, glm->G) + (K * (P + n + 1) + n) * 8 + glm_stage_bytes(glm, 1, K, P, n) + 16 * 256));
+    Stage s{ctx};
+    const double* th_d = s.up(theta, K * P);
+    const double* st_d = s.up(stats, K * n);
+    const double* ob_d = s.up(obs, n);
+    const double* w_d = w ? s.up(w, K) : nullptr;
+    const abc_glm d = glm_stage(s, glm, 1, K, P, n);
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
+    ABC_TRY(launch_glm(ctx, weighted_values(th_d, K, w_d), st_d, K, th_d, K, nullptr, nullptr, w_d, ob_d, (int)n, 1, K, P, n, n, &d, fn));
+    glm_down(s, glm, d, 1, K, P, n);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
 }
 
 // ---- the same products of P given columns of K values (V[e + ldv j], weights w or NULL): one segment group ----

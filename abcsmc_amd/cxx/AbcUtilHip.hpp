@@ -893,6 +893,65 @@ inline TargetHpd weighted_hpd(const Mat2D& values, const std::vector<double>& we
     check(abc_weighted_hpd(context(), values.data(), K, P, weights.empty() ? nullptr : weights.data(), &hd));
     return detail::target_hpd(lo.data(), hi.data(), plo.data(), phi.data(), nm, P);
 }
+// The same ranking followed by the ABC-GLM posterior of every target (abc_glm_particle_ranking_pls_targets; Leuenberger & Wegmann
+// 2010; the definition is in the header).  Per target: mean, var, mode, mode_dens, lo_x, step (P), dens (P x G, row j at
+// x_g = fma(g, step[j], lo_x[j])), ess, log_md (the evidence) and status (0: fitted; otherwise everything else is NaN).
+struct TargetGlm {
+    Row mean, var, mode, mode_dens, lo_x, step;
+    Mat2D dens;
+    double ess, log_md;
+    int32_t status;
+};
+namespace detail {
+struct GlmBuffers {
+    size_t P, G;
+    std::vector<double> mean, var, mode, mode_dens, lo_x, step, dens, ess, log_md;
+    std::vector<int32_t> status;
+    GlmBuffers(size_t B, size_t P_, size_t G_)
+        : P(P_), G(G_), mean(B * P_), var(B * P_), mode(B * P_), mode_dens(B * P_), lo_x(B * P_), step(B * P_), dens(B * P_ * G_),
+          ess(B), log_md(B), status(B) {}
+    abc_glm descriptor(double cut, double bw_scale) {
+        abc_glm g = {};
+        g.G = G; g.cut = cut; g.bw_scale = bw_scale;
+        g.dens = dens.data(); g.lo_x = lo_x.data(); g.step = step.data(); g.mode = mode.data(); g.mode_dens = mode_dens.data();
+        g.mean = mean.data(); g.var = var.data(); g.ess = ess.data(); g.log_md = log_md.data(); g.status = status.data();
+        return g;
+    }
+    TargetGlm target(size_t b) const {
+        TargetGlm r{Row(P), Row(P), Row(P), Row(P), Row(P), Row(P), Mat2D(P, G), ess[b], log_md[b], status[b]};
+        for (size_t j = 0; j < P; j++) {
+            r.mean[j] = mean[b * P + j]; r.var[j] = var[b * P + j]; r.mode[j] = mode[b * P + j];
+            r.mode_dens[j] = mode_dens[b * P + j]; r.lo_x[j] = lo_x[b * P + j]; r.step[j] = step[b * P + j];
+            for (size_t g = 0; g < G; g++) r.dens(j, g) = dens[(b * P + j) * G + g];
+        }
+        return r;
+    }
+};
+}  // namespace detail
+inline std::vector<TargetGlm> particle_ranking_PLS_targets_glm(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                               const float_type train_frac, size_t K, size_t G = 512,
+                                                               double cut = 3.0, double bw_scale = 1.0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols();
+    detail::GlmBuffers buf(B, P, G);
+    const abc_glm g = buf.descriptor(cut, bw_scale);
+    check(abc_glm_particle_ranking_pls_targets(&g, context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac,
+                                               max_components_ref(), component_rule(), nullptr, K, nullptr, nullptr, nullptr));
+    std::vector<TargetGlm> res(B);
+    for (size_t b = 0; b < B; b++) res[b] = buf.target(b);
+    return res;
+}
+// The ABC-GLM posterior of any retained sample: theta (K x P), stats (K x n), obs (n), weights (empty: equal) (abc_glm_weighted).
+inline TargetGlm weighted_glm(const Mat2D& theta, const Mat2D& stats, const Row& obs, const std::vector<double>& weights = {},
+                              size_t G = 512, double cut = 3.0, double bw_scale = 1.0) {
+    const size_t K = theta.rows(), P = theta.cols(), n = stats.cols();
+    if (stats.rows() != K || obs.size() != n) throw HipError(ABC_ERR_INVALID, "stats needs one row per row of theta, obs one entry per statistic");
+    if (!weights.empty() && weights.size() != K) throw HipError(ABC_ERR_INVALID, "weights needs one entry per row");
+    detail::GlmBuffers buf(1, P, G);
+    const abc_glm g = buf.descriptor(cut, bw_scale);
+    check(abc_glm_weighted(&g, context(), theta.data(), stats.data(), K, P, n, obs.data(), weights.empty() ? nullptr : weights.data()));
+    return buf.target(0);
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

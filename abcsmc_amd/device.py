@@ -533,3 +533,34 @@ def weighted_hpd(V, w=None, mass=(0.95,), outputs=("lo", "hi", "plo", "phi"), ct
     """The highest-density intervals of P columns of K values (abc_weighted_hpd_dev).  V: (P, K) holder as weighted_summary's; w: K
     weights or None (equal).  Returns dict(lo, hi, plo, phi (nm, P)) as device tensors."""
     return _weighted_product("hpd", lambda lead, P, dev: _hpd(mass, lead, P, dev, outputs), V, w, ctx)
+
+
+def rank_targets_glm(X, model, A, targets, K, Y, G=512, cut=3.0, bw=None, bw_scale=1.0, exclude=None, dist=False,
+                     outputs=("dens", "lo_x", "step", "mode", "mode_dens", "mean", "var", "ess", "log_md", "status"), ctx=None):
+    """rank_targets followed by the ABC-GLM posterior of every target (abc_glm_rank_targets_dev; the definition is in the header).
+    bw: given bandwidths (B, P) or None (the marginal density's rule times bw_scale).  outputs: names among _lib.GLM_OUTPUTS.
+    Works on device tensors; the one copy is the model's ncomp, read back after the call (a synchronisation).  Returns dict(idx (B, K)
+    int64, dist (B, K) or None, ncomp, and the outputs asked
+    for (None for the rest): dens (B, P, G), lo_x, step, mode, mode_dens, mean, var (B, P), ess, log_md (B,), status (B,) int32,
+    C (B, n, P), c0 (B, n), sigma_s (B, n, n) at the model's n = ncomp, T (B, P, P), peaks (B, K, P), c (B, K))."""
+    N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
+    unknown = set(outputs) - set(_lib.GLM_OUTPUTS)
+    if unknown:
+        raise ValueError("unknown outputs %s" % sorted(unknown))
+    f64 = torch.float64
+    nA = min(int(A), _lib.GLM_MAX)
+    sh = _lib.glm_shapes((B,), K, P, nA, int(G))
+    r = {k: (torch.empty(sh[k], dtype=torch.int32 if k == "status" else f64, device=dev) if k in outputs else None)
+         for k in _lib.GLM_OUTPUTS}
+    if bw is not None:
+        bw = torch.as_tensor(bw, dtype=f64).to(dev).expand((B, P)).contiguous()
+    d = _lib.Glm(int(G), float(cut), float(bw_scale), _ptr(bw), *[_ptr(r[k]) for k in _lib.GLM_OUTPUTS])
+    r.update(idx=torch.empty((B, K), dtype=torch.int64, device=dev), dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None)
+    ctx.check(lib().abc_glm_rank_targets_dev(C.byref(d), ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
+                                             targets.data_ptr(), ldt, B, _ptr(exclude), K, r["idx"].data_ptr(), _ptr(r["dist"])))
+    n = min(max(int(model[0].item()), 0), int(A))
+    for k, tail in (("C", (n, P)), ("c0", (n,)), ("sigma_s", (n, n))):      # packed at the model's n components
+        if r[k] is not None:
+            r[k] = r[k].reshape(-1)[:B * int(np.prod(tail))].reshape((B,) + tail)
+    r["ncomp"] = n
+    return r

@@ -1041,6 +1041,80 @@ int abc_weighted_hpd_dev(abc_ctx* ctx, const double* V, size_t ldv, size_t K, si
 /* HOST-pointer form: V is K x P column-major (ldv = K); w and hd's arrays in host memory. */
 int abc_weighted_hpd(abc_ctx* ctx, const double* V, size_t K, size_t P, const double* w, const abc_hpd* hd);
 
+/* ---- ABC-GLM posterior of the batched ranking (Leuenberger & Wegmann 2010): densities, moments and the evidence ---------------
+ * ABCtoolbox's estimator on top of PLS.  On the retained rows a general linear model of the scores on the parameters is fitted;
+ * the retained sample is taken as a mixture of sharp Gaussian peaks (the truncated prior) and multiplied analytically by the
+ * Gaussian likelihood of the observation.  That gives smooth marginal posterior densities, posterior means and variances that
+ * rest on no regression of parameters on statistics, and the marginal density of the observation (the evidence of model choice).
+ * Inputs, per target b.  The ranking's rows e = 0..K-1 carry the parameter rows theta_e (P) = Y[i_e, :], the scores x_e (n = the
+ * model's ncomp) and the observed scores o, exactly the covariates of abc_rank_targets_adjust_dev, and the weights w_e: the row
+ * importance weight of i_e when row weights are set on the context, else 1.  Only entries with w_e > 0 count.  W = sum w,
+ * S2 = sum w^2, n_eff = W^2 / S2.  Any non-finite theta or x among the counted rows makes every output of that target NaN and sets
+ * status bit 2 (so does a non-finite theta in an uncounted row, with or without a given bw: abc_density's rule reads every
+ * entry of a parameter's column before it looks at the weights).
+ * Step 1, moments.  The weighted means thbar and xbar; in a second pass the centred weighted moments divided by W: M_thth (P x P),
+ *   M_thx (P x n), M_xx (n x n).
+ * Step 2, the GLM s = C theta + c0 + eps.  M_thth is factored by Cholesky in parameter order; a pivot <= 1e-10 of its own diagonal
+ *   entry makes the target degenerate: status bit 0 and NaN outputs (the pivot is not skipped).  C = (M_thth^-1 M_thx)', n x P;
+ *   c0 = xbar - C thbar; R = M_xx - M_xth M_thth^-1 M_thx; Sigma_s = R n_eff / (n_eff - P - 1).  n_eff <= P + 1, or a Cholesky
+ *   pivot of Sigma_s <= 1e-10 of its diagonal entry, sets status bit 1 and writes NaN outputs.
+ * Step 3, peaks.  Sigma_theta = diag(h_j^2), h_j the bandwidth of parameter j by abc_density's rule (bw.nrd0 on the weighted
+ *   sample, times bw_scale); a given bw array (B x P) replaces the rule, as there.
+ * Step 4, the posterior mixture, every theta taken relative to thbar (an exact reparametrisation that keeps the exponents small).
+ *   Q = C' Sigma_s^-1 C + Sigma_theta^-1; T = Q^-1 by Cholesky; u = C' Sigma_s^-1 (o - xbar); v_e = u + Sigma_theta^-1 (theta_e - thbar);
+ *   t_e = thbar + T v_e; log c_e = log w_e - [(theta_e - thbar)' Sigma_theta^-1 (theta_e - thbar) - v_e' T v_e] / 2;
+ *   c^_e = exp(log c_e - max log c) / (the sum of that over the counted rows).
+ * Step 5, products.  mean[j] = sum c^_e t_e[j]; var[j] = T_jj + sum c^_e (t_e[j] - mean[j])^2; ess = 1 / sum c^_e^2.
+ *   Grid, per (b, j): lo_x = min_e t_e[j] - cut sqrt(T_jj); step = ((max_e t_e[j] + cut sqrt(T_jj)) - lo_x) / (G - 1);
+ *   x_g = fma(g, step, lo_x).  Marginal density f_j(x_g) = sum_e c^_e exp(-(x_g - t_e[j])^2 / (2 T_jj)) / sqrt(2 pi T_jj), the
+ *   term evaluated as abc_density's (fp64 argument; relative error of a term about 1e-7).  mode is the x_g of the smallest g at
+ *   which the device's own f is largest, mode_dens that f.  Evidence: S = Sigma_s + C Sigma_theta C';
+ *   log_md = log sum_e w_e N(o; c0 + C theta_e, S) - log W, by log-sum-exp with the Cholesky factor of S.
+ *   Model outputs (optional): C (B x n x P), c0 (B x n), sigma_s (B x n x n), T (B x P x P), peaks t_e (B x K x P, [b][e][j]) and
+ *   c = c^_e (B x K); peaks and c are written only when asked for.  C, c0 and sigma_s are packed at the model's n = ncomp; the
+ *   caller's arrays hold room for n = min(A, 32).
+ * Reduction order.  The order of every reduction depends on (K, n, P, G) only: a target's outputs are the same bits on a repeat,
+ * alone or in any batch, through the device or the host entry, and with or without dens / peaks.
+ * Limits: 1 <= P <= 32, 1 <= ncomp <= 32, A <= 64, G in 2..4096, cut >= 0 and finite, bw_scale > 0 and finite, at least one output;
+ * each violation is ABC_ERR_INVALID with a message (ncomp is read from the model before anything is ranked).  A parameter
+ * transform, the variance correction or ridge set on the context is ABC_ERR_UNSUPPORTED: ABC-GLM is not an adjustment, so those
+ * settings have no meaning for it.
+ * Deviations from ABCtoolbox: the peak widths come from abc_density's bandwidth rule instead of diracPeakWidth, the statistics are
+ * the PLS scores instead of raw statistics, and all targets share one PLS fit.  NOT checked against ABCtoolbox itself. */
+#define ABC_GLM_MAX 32
+typedef struct {
+    size_t G;                          /* grid points per parameter, 2..4096                                              */
+    double cut, bw_scale;              /* as abc_density                                                                  */
+    const double* bw;                  /* optional: given bandwidths h_j, B x P, finite and positive                      */
+    double *dens;                      /* optional; B x P x G ([b][j][g])                                                 */
+    double *lo_x, *step;               /* optional; B x P                                                                 */
+    double *mode, *mode_dens;          /* optional; B x P                                                                 */
+    double *mean, *var;                /* optional; B x P                                                                 */
+    double *ess, *log_md;              /* optional; B                                                                     */
+    double *C, *c0, *sigma_s, *T;      /* optional; B x n x P, B x n, B x n x n, B x P x P (row-major per target)         */
+    double *peaks, *c;                 /* optional; B x K x P, B x K                                                      */
+    int32_t* status;                   /* optional; B: bit 0 degenerate M_thth, bit 1 n_eff or Sigma_s, bit 2 non-finite; */
+                                       /* one bit at most, the first of: non-finite input, n_eff <= P + 1 (also: no       */
+                                       /* counted row), a pivot of M_thth, a pivot of Sigma_s                              */
+} abc_glm;                             /* memory of every array as the entry point's other arrays                         */
+/* Device pointers; the remaining arguments are those of abc_rank_targets_density_dev without method and kernel.  idx and dist are
+ * optional and receive the bits of abc_rank_targets_dev.  The descriptor comes first: the call is a method of the request. */
+int abc_glm_rank_targets_dev(const abc_glm* glm, abc_ctx* ctx, const double* X, size_t ldx, const double* Y, size_t ldy, size_t N,
+                             size_t M, size_t P, const double* model, size_t A, const double* targets, size_t ldt, size_t B,
+                             const uint64_t* exclude, size_t K, uint64_t* idx, double* dist);
+/* HOST-pointer drop-in (as abc_particle_ranking_pls_targets_density); every array of glm in host memory. */
+int abc_glm_particle_ranking_pls_targets(const abc_glm* glm, abc_ctx* ctx, const double* X, const double* Y, size_t N, size_t M,
+                                         size_t P, const double* targets, size_t B, double train_frac, int max_comp, int rule,
+                                         const uint64_t* exclude, size_t K, uint64_t* idx, double* dist, int32_t* ncomp);
+/* The generic form for any retained sample with any statistics (B = 1): theta K x P (theta[e + ldv j]), stats K x n
+ * (stats[e + lds k]), obs the n observed statistics, w the K weights (NULL: all 1; checked as abc_weighted_density_dev's).
+ * ABC_ERR_INVALID for a NULL theta, stats or obs, K = 0, P or n outside 1..32, ldv < K or lds < K. */
+int abc_glm_weighted_dev(const abc_glm* glm, abc_ctx* ctx, const double* theta, size_t ldv, const double* stats, size_t lds, size_t K,
+                         size_t P, size_t n, const double* obs, const double* w);
+/* HOST-pointer form: theta and stats column-major with ldv = lds = K; every array in host memory. */
+int abc_glm_weighted(const abc_glm* glm, abc_ctx* ctx, const double* theta, const double* stats, size_t K, size_t P, size_t n,
+                     const double* obs, const double* w);
+
 /* ---- Box-Cox transform of the metrics: the skewness search and the transform (ABC::optimize_box_cox, AbcUtil.cpp:89-109) ---------
  * PLS is linear; simulated metrics (counts, sizes, durations) are positive and right-skewed.  The reference searches, per metric, a
  * grid of exponents for the lambda whose transform (x^lambda - 1) / lambda has the smallest |skewness| (its ranking carries the
