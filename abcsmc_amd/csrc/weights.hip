@@ -340,6 +340,11 @@ constexpr int KS_NP = 6;                       // limb products per chunk
 // Exact range of the split kernel (rows outside are "far": fp64 fix-ups).  X = sum h0.h0' - hbTop counts in units of 2^-14 and
 // must stay below 2^10 in every partial sum: with |a|^2, |b|^2 <= KS_NORM2 the products of any number of chunks sum to at most
 // |a||b| <= 400 in absolute value (Cauchy-Schwarz), hbTop = 1/2|b|^2 - log2 w' lies in [-100, 500]: at most 900.
+// The batch reference n (the floor of the largest X of the values that share it: the 16 a lane owns of a tile, or the 32 it owns
+// of two consecutive tiles in kz_pair_sums) lies in the same range, so X - n is a multiple of 2^-14 below 2^11 in magnitude; it is
+// exact in f32 -- below 2^10 -- for every value less than 1024 below its batch's largest, and a value further down than that is
+// more than 2^126 below it and flushes to zero in v_exp_f32 whatever its last bits were.  How many values share a reference does
+// not enter: the flush rule reads "more than 2^126 below the largest of the batch", of 16 or of 32.
 constexpr double KS_BOUND = 8.0;               // |scaled coordinate| (h0 <= 1024 units of 2^-7: one f16)
 constexpr double KS_NORM2 = 400.0;             // |scaled row|^2  (typical: 0.7 x parameters)
 constexpr double KS_LW_CAP = 300.0, KS_LW_MIN = -100.0;   // -log2 w' of a non-zero weight (w' = 0: an all-zero row with hb = KS_HB_ZERO)
@@ -432,6 +437,7 @@ constexpr unsigned KS_MONE = 0xBF80u;                       // bf16 -1
 // The new set's 1/2|a_i|^2 is common to every term of row i and stays OUT of the sums: its integer part goes to ha_int
 // (subtracted from the exponent of every batch's power of two), its fraction to ha_frac (k_wfinish, fp64).
 // Rows >= rows are padding: zero limbs; a padded previous row has hb = KS_HB_ZERO (a term of exactly 0).
+// (KS_TOPN: k_tile_tmin afterwards moves the hbTop pieces of a WIDE tile from K-slots 0..2 to 8..10)
 
 // f16 bits of n 2^-s for an integer |n| <= 1024 whose value lies on f16's grid (the exact limbs h0 = n0 2^-7, h1 = n1 2^-18,
 // h0 2^-11 = n0 2^-18): integer arithmetic only -- f16_bits does the same through ilogb / ldexp / rint in fp64
@@ -682,7 +688,9 @@ struct KsRef { float p0, p1, p2, p3; };        // the four running f32 sums of a
 // vector side: 14.5 fp64 instructions per pair (round 1) -> 8 slots (floor / fract split of an exact X, per-pair ldexp) -> 5.75
 // (one power of two per batch, two accumulators: subtract, add, exp, add) -> 4.1, for one MFMA more (9 per 1024 pairs at 16
 // parameters).  Error of a batch sum (emulation, scripts/split_precision.py): rms 4.8e-8 / max 2.0e-7 (4.6e-8 / 2.0e-7 with two
-// accumulators).  Measured at 1e10 pairs, P = 16: 2.38 -> 2.24 ms -- the chip clocks 6 % lower under the ninth MFMA (1.78 against
+// accumulators); of the two-tile batch of kz_pair_sums -- 32 terms, eight chains of four, a tree of seven -- rms 4.8e-8 / max 2.2e-7
+// beside 4.9e-8 / 2.2e-7 for 16 terms on the same 1500 x 1500 pairs (`split_precision.py 16 1500 pairs`): the longer tree adds one
+// rounding to a sum whose error the exponentials dominate.  Measured at 1e10 pairs, P = 16: 2.38 -> 2.24 ms -- the chip clocks 6 % lower under the ninth MFMA (1.78 against
 // 1.90 GHz, PMC), which eats most of what the 26 % shorter instruction stream buys.
 // The kernel's variants, by their first template argument: the plain, KS_FOLD and KS_TOPN families (weights_plan.h)
 template <int V> __host__ __device__ constexpr int kz_nch() { return V > KS_TOPN ? V - KS_TOPN : V > KS_FOLD ? V - KS_FOLD : V; }
@@ -718,7 +726,12 @@ __device__ __forceinline__ void kz_mfma(const AT A, const uint4* B, const uint4 
             // route -- the norm top in a step of its own, in front of everything -- so that its reference is the maximum of X' - top
             // itself; the tile's info word says so (mask 0), and the reference step below then leaves the top out of its operand
             if (__builtin_amdgcn_readfirstlane(A[C * KS_NL + 1].y) == 0u) {
-                Z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A[C * KS_NL]), __builtin_bit_cast(bf16x8, NB[0]), Z0, 0, 0, 0);
+                // (a wide tile keeps its top pieces in K-slots 8..10, k_tile_tmin; the -1 pattern against them is put together HERE, from
+                // the lane number read afresh: held in registers across the loop for the sparse tail's sake it would cost the two-tile
+                // kernel four registers it does not have)
+                const bool hi = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >= 32u;
+                const uint4 NT = make_uint4(hi ? (KS_MONE | (KS_MONE << 16)) : 0u, hi ? KS_MONE : 0u, 0u, 0u);
+                Z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A[C * KS_NL]), __builtin_bit_cast(bf16x8, NT), Z0, 0, 0, 0);
                 Z = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A[0]), __builtin_bit_cast(f16x8, B[0]), Z, 0, 0, 0);
             } else {
                 Z = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A[0]), __builtin_bit_cast(f16x8, B[0]), Z0, 0, 0, 0);
@@ -726,6 +739,9 @@ __device__ __forceinline__ void kz_mfma(const AT A, const uint4* B, const uint4 
         } else if constexpr (S < C) {
             Z = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A[S * KS_NL]), __builtin_bit_cast(f16x8, B[S * KS_NL]), Z, 0, 0, 0);
         } else if constexpr (S == C) {          // - top - n
+            // BN carries the -1 entries against the top pieces (K-slots 0..2) for good, beside the batch's n (slots 6,7).  A wide tile,
+            // whose top is in the accumulator already, has nothing in those slots (k_tile_tmin moved its pieces to 8..10): the same
+            // instruction subtracts n alone there -- no mask on the operand (until round 6: two vector ANDs in every batch), no branch
             Z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A[C * KS_NL]), __builtin_bit_cast(bf16x8, BN), Z, 0, 0, 0);
         } else if constexpr (S == C + 1) {      // - low
             Z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A[C * KS_NL]), __builtin_bit_cast(bf16x8, NB[1]), Z, 0, 0, 0);
@@ -749,6 +765,11 @@ __device__ __forceinline__ void kz_mfma(const AT A, const uint4* B, const uint4 
                                                    __builtin_bit_cast(f16x8, B[c * KS_NL + KS_LB[l]]), Z, 0, 0, 0);
     }
 }
+// the B operand of the -n step before any reference is in it: KS_TOPN -- the -1 entries against the top pieces; otherwise nothing
+template <int V>
+__device__ __forceinline__ uint4 kz_bn_init(const uint4& NB0) {
+    return kz_topn<V>() ? make_uint4(NB0.x, NB0.y, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
+}
 template <int NCH, int S0, int S1, typename AT>
 __device__ __forceinline__ void kz_mfma_range(const AT A, const uint4* B, const uint4 (&NB)[2], const uint4& BN, f32x16& Z) {
     if constexpr (S0 < S1) {
@@ -756,9 +777,19 @@ __device__ __forceinline__ void kz_mfma_range(const AT A, const uint4* B, const 
         kz_mfma_range<NCH, S0 + 1, S1>(A, B, NB, BN, Z);
     }
 }
-// n = floor(max of the lane's 16 values) and the B operand that subtracts it (see above); |n| < 2048: two bf16 pieces
-template <int V, typename AT>
-__device__ __forceinline__ void kz_reference(const f32x16& Z, const AT A, const uint4& NB0, unsigned lane, int& n, uint4& BN) {
+// n = floor(m), m the batch's maximum, and the B operand that subtracts it (see above); |n| < 2048: two bf16 pieces against the -1
+// entries of the previous set's norm operand.  p1 = the float's top 16 bits (n cut to eight significant bits: a mask), p2 = n - p1
+// (at most three bits, exact, a bf16 value as it stands); v_perm_b32 packs the two upper halves.  (Until round 6: p1 = n ROUNDED to
+// bf16 -- convert, shift, subtract, convert.  p1 + p2 = n either way and the step adds both in exact arithmetic: same accumulator.)
+__device__ __forceinline__ void kz_nsplit(float m, int& n, uint4& BN) {
+    const float nf = __builtin_floorf(m);
+    n = (int)nf;
+    const unsigned nb = __float_as_uint(nf);
+    const float p2 = nf - __uint_as_float(nb & 0xffff0000u);
+    BN.w = __builtin_amdgcn_perm(__float_as_uint(p2), nb, 0x07060302u);   // K-slots 6,7 (lanes 0..31) / 14,15 (lanes 32..63): see k_wrows
+}
+// the maximum of the 16 values a lane owns of one tile (eight v_max3_f32)
+__device__ __forceinline__ float kz_max16(const f32x16& Z) {
     // The first read of the freshly written accumulator is an instruction the compiler knows (it places the wait states a VALU
     // read of an MFMA result needs; it does not look inside inline assembly): ONE v_max_f32 of Z[0] with itself (fmaxf of two
     // accumulator values is three instructions: each input is quieted first); the v_max3_f32 tree follows.
@@ -767,26 +798,16 @@ __device__ __forceinline__ void kz_reference(const f32x16& Z, const AT A, const 
     const float m0 = ks_max3(f0, Z[1], Z[2]), m1 = ks_max3(Z[3], Z[4], Z[5]), m2 = ks_max3(Z[6], Z[7], Z[8]),
                 m3 = ks_max3(Z[9], Z[10], Z[11]), m4 = ks_max3(Z[12], Z[13], Z[14]);
     const float ma = ks_max3(m0, m1, m2), mb = ks_max3(m3, m4, Z[15]);
-    float m = ks_max3(ma, mb, mb);
-    if constexpr (kz_topn<V>()) {
-        // the tile's info words (behind its operands): its smallest top and an all-ones mask, or 0 and 0 for a wide tile (whose
-        // top is in the accumulator already: kz_mfma, step 0)
-        const uint4 ti = A[kz_nch<V>() * KS_NL + 1];
-        m -= __uint_as_float(ti.x);
-        BN.x = NB0.x & ti.y;
-        BN.y = NB0.y & ti.y;
-    }
-    const float nf = __builtin_floorf(m);
-    n = (int)nf;
-    // n = p1 + p2, two bf16 pieces against the -1 entries of the previous set's norm operand: p1 = n rounded to bf16 (eight
-    // significant bits), p2 = n - p1 (|n| < 2048: at most three bits, exact); v_cvt_pk_bf16_f32 packs both
-    typedef __attribute__((ext_vector_type(2))) float f32x2_;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
-    const bf16x2_ h1 = __builtin_convertvector((f32x2_){nf, 0.f}, bf16x2_);
-    const float p1 = __uint_as_float(__builtin_bit_cast(unsigned, h1) << 16);
-    const bf16x2_ pk = __builtin_convertvector((f32x2_){nf, nf - p1}, bf16x2_);
+    return ks_max3(ma, mb, mb);
+}
+// the reference of a one-tile batch.  KS_TOPN: the tile's info words (behind its operands) hold its smallest top, or 0 for a wide
+// tile (whose top is in the accumulator already: kz_mfma, step 0)
+template <int V, typename AT>
+__device__ __forceinline__ void kz_reference(const f32x16& Z, const AT A, unsigned lane, int& n, uint4& BN) {
+    float m = kz_max16(Z);
+    if constexpr (kz_topn<V>()) m -= __uint_as_float(A[kz_nch<V>() * KS_NL + 1].x);
     (void)lane;
-    BN.w = __builtin_bit_cast(unsigned, pk);      // K-slots 6,7 (lanes 0..31) / 14,15 (lanes 32..63), the rest stays zero: see k_wrows
+    kz_nsplit(m, n, BN);
 }
 // One step of a wave: the vector work of the finished batch (Zc, reference nc) interleaved with the whole chain of the next one
 // (An x Bn -> Zn, reference nn).  Eight slots of two exponentials; the next batch's exact part goes first, its reference is taken
@@ -798,7 +819,7 @@ __device__ __forceinline__ void kz_slots(const AT An, const uint4* Bn, const uin
         constexpr int NS = kz_nsteps<NCH>(), NA = kz_nexact<NCH>();   // NA exact steps, then the reference, then NS - NA more
         if constexpr (R == 0) kz_mfma_range<NCH, 0, NA>(An, Bn, NB, BN, Zn);
         if constexpr (R == 3) {
-            kz_reference<NCH>(Zn, An, NB[0], lane, nn, BN);
+            kz_reference<NCH>(Zn, An, lane, nn, BN);
         }
         if constexpr (R >= 3 && R < 7) {
             constexpr int r = R - 3, M = NS - NA;                        // spread the remaining M steps over slots 3..6
@@ -837,7 +858,7 @@ __device__ __forceinline__ void kz_fine(const AT An, const uint4* Bn, const uint
     if constexpr (R < 16) {
         constexpr int NS = kz_nsteps<NCH>(), NA = kz_nexact<NCH>(), R0 = NA + RO, M = NS - NA, L = 16 - R0;
         if constexpr (R < NA) kz_mfma_range<NCH, R, R + 1>(An, Bn, NB, BN, Zn);
-        if constexpr (R == R0) kz_reference<NCH>(Zn, An, NB[0], lane, nn, BN);
+        if constexpr (R == R0) kz_reference<NCH>(Zn, An, lane, nn, BN);
         if constexpr (R >= R0) {
             constexpr int r = R - R0;
             constexpr int s0 = NA + (r * M) / L, s1 = NA + ((r + 1) * M) / L;
@@ -869,12 +890,20 @@ __device__ __forceinline__ void kz_step(const AT An, const uint4* Bn, const uint
     else kz_slots<NCH, 0>(An, Bn, NB, Zn, nn, lane, Zc, nc, hsub, s, q, BN);
 }
 
-template <int NCH, int WPS, bool PING = (NCH >= 4), int FINE = 0>
+template <int V>
+__device__ __forceinline__ void kz_pair_sums(const uint4* __restrict__ at, size_t kn, const uint4* __restrict__ bt, unsigned nbt,
+                                             const int* __restrict__ ha_int, double* __restrict__ part, const uint2* __restrict__ tmin);
+// (TPB: tiles per batch -- 1: this loop; 2, one chunk: kz_pair_sums below, the same grid and arguments)
+template <int NCH, int WPS, bool PING = (NCH >= 4), int FINE = 0, int TPB = 1>
 __global__ __launch_bounds__(256, WPS) void k_kde_split(const uint4* __restrict__ at, size_t kn,
                                                       const uint4* __restrict__ bt, unsigned nbt,
                                                       const WConst* __restrict__ wc, const int* __restrict__ ha_int,
                                                       double* __restrict__ part, const uint2* __restrict__ tmin /* KS_TOPN: two info words per tile */) {
     if (!ks_split_on(wc)) return;                             // the fp64 kernel's turn
+    if constexpr (TPB == 2) {
+        kz_pair_sums<NCH>(at, kn, bt, nbt, ha_int, part, tmin);
+        return;
+    }
     constexpr int OPA = kz_nch<NCH>() * KS_NL, OPB = OPA + (kz_fold<NCH>() ? 0 : 1);
     constexpr int OPT = kz_topn<NCH>() ? 1 : 0;            // one more register behind a tile's operands: its smallest top (KS_TOPN)
     const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -906,11 +935,11 @@ __global__ __launch_bounds__(256, WPS) void k_kde_split(const uint4* __restrict_
         if constexpr (OPT) { const uint2 ti = tmin[t0]; A[OPB] = make_uint4(ti.x, ti.y, 0u, 0u); }
         f32x16 Z0, Z1;
         int n0 = 0, n1 = 0;
-        uint4 BN = make_uint4(0u, 0u, 0u, 0u);                   // (kz_reference only ever writes its last component)
+        uint4 BN = kz_bn_init<NCH>(NB[0]);                       // (kz_reference only ever writes its last component)
         {   // (t0, columns 0): the whole chain up front
             constexpr int NA = kz_nexact<NCH>();
             kz_mfma_range<NCH, 0, NA>(A, B0, NB, BN, Z0);
-            kz_reference<NCH>(Z0, A, NB[0], lane, n0, BN);
+            kz_reference<NCH>(Z0, A, lane, n0, BN);
             kz_mfma_range<NCH, NA, kz_nsteps<NCH>()>(A, B0, NB, BN, Z0);
         }
         if constexpr (!PING) {
@@ -960,6 +989,224 @@ __global__ __launch_bounds__(256, WPS) void k_kde_split(const uint4* __restrict_
     {
         const double v0 = acc0 + __shfl_xor(acc0, 32, 64);          // the two halves hold different previous rows
         const double v1 = acc1 + __shfl_xor(acc1, 32, 64);
+        const size_t i0 = (it0 + 0) * 32 + (lane & 31), i1 = (it0 + 1) * 32 + (lane & 31);
+        if (lane < 32 && i0 < kn) part[(size_t)sl * kn + i0] = v0;
+        if (lane < 32 && i1 < kn) part[(size_t)sl * kn + i1] = v1;
+    }
+}
+
+// ---- two tiles per batch (one chunk: up to 16 parameters) -----------------------------------------------------------------------
+// A batch is the 2 x 16 values a lane owns of the previous tiles t and t + 1 against ONE resident column set, under ONE reference
+// n = floor(max of the 32) (KS_TOPN: each tile's values less its own smallest top first; a wide tile keeps its own route, kz_mfma):
+// what the reference has to be is the floor of the maximum of every value that shares it -- X - n exact, Z small for the terms that
+// carry the batch, every exponent at most 1 + the small products -- and nothing ties it to 16 values.  The matrix side is the
+// one-tile kernel's: every tile still takes its kz_nsteps MFMAs, with the same operands and in the same order within its chain; the
+// exact steps of both tiles go first, then the reference, then the remaining steps of tile t, then those of tile t + 1.  The vector
+// side pays the tail of the reference (floor, convert, the split of n) and the close of the batch (convert, v_ldexp_f64, fp64 add)
+// once per 32 values instead of once per 16: 32 exponentials into EIGHT running sums (chains of four, as before), a tree of seven.
+// A term more than 2^126 below the largest of its 32 flushes to zero (before: of its 16); the terms that decide a weight lie within
+// a few units of the largest of their row, whichever tile holds it.
+// the steps behind the reference, J0 <= j < J1: tile t's H = kz_nsteps - kz_nexact first, then tile t + 1's
+template <int V, int J0, int J1>
+__device__ __forceinline__ void kz_rest(const uint4* A0, const uint4* A1, const uint4* B, const uint4 (&NB)[2], const uint4& BN,
+                                        f32x16& Z0, f32x16& Z1) {
+    if constexpr (J0 < J1) {
+        constexpr int NA = kz_nexact<V>(), H = kz_nsteps<V>() - NA;
+        if constexpr (J0 < H) {
+            asm volatile("" : "+v"(Z0));
+            kz_mfma<V, NA + J0>(A0, B, NB, BN, Z0);
+        } else {
+            asm volatile("" : "+v"(Z1));
+            kz_mfma<V, NA + J0 - H>(A1, B, NB, BN, Z1);
+        }
+        kz_rest<V, J0 + 1, J1>(A0, A1, B, NB, BN, Z0, Z1);
+    }
+}
+// the reference of a two-tile batch: sixteen v_max3_f32 over the 32 values (KS_TOPN: two trees of eight, a subtraction each, one more)
+template <int V>
+__device__ __forceinline__ void kz_reference2(const f32x16& Z0, const f32x16& Z1, const uint4* A0, const uint4* A1, int& n, uint4& BN) {
+    float m;
+    if constexpr (kz_topn<V>()) {
+        constexpr int I = kz_nch<V>() * KS_NL + 1;
+        const float ma = kz_max16(Z0) - __uint_as_float(A0[I].x), mb = kz_max16(Z1) - __uint_as_float(A1[I].x);
+        m = ks_max3(ma, mb, mb);
+    } else {
+        const float f0 = __builtin_canonicalizef(Z0[0]), g0 = __builtin_canonicalizef(Z1[0]);     // (kz_max16: the first reads)
+        __builtin_amdgcn_sched_barrier(0);
+        const float a0 = ks_max3(f0, Z0[1], Z0[2]), a1 = ks_max3(Z0[3], Z0[4], Z0[5]), a2 = ks_max3(Z0[6], Z0[7], Z0[8]),
+                    a3 = ks_max3(Z0[9], Z0[10], Z0[11]), a4 = ks_max3(Z0[12], Z0[13], Z0[14]);
+        const float b0 = ks_max3(g0, Z1[1], Z1[2]), b1 = ks_max3(Z1[3], Z1[4], Z1[5]), b2 = ks_max3(Z1[6], Z1[7], Z1[8]),
+                    b3 = ks_max3(Z1[9], Z1[10], Z1[11]), b4 = ks_max3(Z1[12], Z1[13], Z1[14]);
+        const float c0 = ks_max3(a0, a1, a2), c1 = ks_max3(a3, a4, Z0[15]), c2 = ks_max3(b0, b1, b2), c3 = ks_max3(b3, b4, Z1[15]);
+        const float d = ks_max3(c0, c1, c2);
+        m = ks_max3(d, c3, c3);
+    }
+    kz_nsplit(m, n, BN);
+}
+// the whole chain of a batch of MT tiles, nothing beside it (the first batch of a slice)
+template <int V, int MT>
+__device__ __forceinline__ void kz_chain(const uint4* A0, const uint4* A1, const uint4* B, const uint4 (&NB)[2], uint4& BN,
+                                         f32x16& Z0, f32x16& Z1, int& n, unsigned lane) {
+    constexpr int NA = kz_nexact<V>(), H = kz_nsteps<V>() - NA;
+    kz_mfma_range<V, 0, NA>(A0, B, NB, BN, Z0);
+    if constexpr (MT == 2) {
+        kz_mfma_range<V, 0, NA>(A1, B, NB, BN, Z1);
+        kz_reference2<V>(Z0, Z1, A0, A1, n, BN);
+    } else {
+        kz_reference<V>(Z0, A0, lane, n, BN);
+    }
+    kz_rest<V, 0, MT * H>(A0, A1, B, NB, BN, Z0, Z1);
+}
+// One step of a wave: the vector work of the finished batch of VT tiles (Zc0, Zc1; reference nc) in 16 VT slots of one exponential,
+// interleaved with the whole chain of the next batch of MT tiles (A0, A1 x Bn -> Zn0, Zn1; reference nn; MT = 0: none).  kz_fine's
+// discipline: the exact steps first, one per slot; the reference one slot behind the last of them; the remaining steps evenly over
+// the slots that are left -- never more than one MFMA between two exponentials here.  <MT 1, VT 1> IS kz_fine<.., 1, ..>: the
+// one-tile batch that ends a slice with an odd number of tiles.  LD: the operands of the tiles after these two are fetched into A0
+// behind tile t's last step and into A1 behind the last step of all (nx0, nx1: their bases, ni0, ni1: their info words).
+template <int V, int MT, int VT, bool LD, int R, int NOP>
+__device__ __forceinline__ void kz_pstep(uint4 (&A0)[NOP], uint4 (&A1)[NOP], const uint4* Bn, const uint4 (&NB)[2], f32x16& Zn0,
+                                         f32x16& Zn1, int& nn, unsigned lane, const f32x16& Zc0, const f32x16& Zc1, int nc,
+                                         double& s, float (&p)[8], uint4& BN, const uint4* nx0, const uint4* nx1, const uint2* ni0,
+                                         const uint2* ni1) {
+    constexpr int SL = 16 * VT;
+    if constexpr (R < SL) {
+        constexpr int NA = kz_nexact<V>(), H = kz_nsteps<V>() - NA, E = MT * NA, R0 = E + 1, M = MT * H, L = SL - R0;
+        constexpr int OPN = NOP - (kz_topn<V>() ? 1 : 0);                 // operands to fetch; KS_TOPN: the info words behind them
+        if constexpr (R < E) {
+            if constexpr (R < NA) kz_mfma<V, R>(A0, Bn, NB, BN, Zn0);
+            else kz_mfma<V, R - NA>(A1, Bn, NB, BN, Zn1);
+        }
+        if constexpr (MT == 2 && R == R0) kz_reference2<V>(Zn0, Zn1, A0, A1, nn, BN);
+        if constexpr (MT == 1 && R == R0) kz_reference<V>(Zn0, A0, lane, nn, BN);
+        if constexpr (MT > 0 && R >= R0) {
+            constexpr int r = R - R0, j0 = (r * M) / L, j1 = ((r + 1) * M) / L;
+            kz_rest<V, j0, j1>(A0, A1, Bn, NB, BN, Zn0, Zn1);
+            if constexpr (LD && j0 < H && j1 >= H) {
+#pragma unroll
+                for (int q = 0; q < OPN; q++) A0[q] = nx0[q * 64 + lane];
+                if constexpr (kz_topn<V>()) { const uint2 ti = *ni0; A0[OPN] = make_uint4(ti.x, ti.y, 0u, 0u); }
+            }
+            if constexpr (LD && R == SL - 1) {
+#pragma unroll
+                for (int q = 0; q < OPN; q++) A1[q] = nx1[q * 64 + lane];
+                if constexpr (kz_topn<V>()) { const uint2 ti = *ni1; A1[OPN] = make_uint4(ti.x, ti.y, 0u, 0u); }
+            }
+        }
+        {
+            const float e = __builtin_amdgcn_exp2f(R < 16 ? Zc0[R & 15] : Zc1[R & 15]);
+            constexpr int c = (R & 3) + (R < 16 ? 0 : 4);
+            if constexpr ((R & 15) < 4) p[c] = e; else p[c] += e;
+        }
+        if constexpr (R == SL - 1) {
+            float t = p[0] + p[1];
+            asm volatile("" : "+v"(t));
+            t += p[2] + p[3];
+            if constexpr (VT == 2) {
+                float u = p[4] + p[5];
+                asm volatile("" : "+v"(u));
+                u += p[6] + p[7];
+                asm volatile("" : "+v"(t), "+v"(u));
+                t += u;
+            }
+            s += ldexp((double)t, nc);
+            asm volatile("" : "+v"(s));
+        } else if constexpr (R < 16) {
+            asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]));
+        } else {
+            asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        kz_pstep<V, MT, VT, LD, R + 1>(A0, A1, Bn, NB, Zn0, Zn1, nn, lane, Zc0, Zc1, nc, s, p, BN, nx0, nx1, ni0, ni1);
+    }
+}
+
+// The pair sums of the one-chunk families with two tiles per batch (k_kde_split<.., TPB 2>).  Grid, slices and tiles are k_kde_split's (abc_weights_plan); a
+// slice of an odd number of tiles ends with a one-tile batch per column set, a slice of one tile is that alone.  Per pair of tiles
+// (t, t + 1), with the two column sets as matrix and vector partners:
+//   matrix (t, t + 1; columns 1)      beside  vector (t, t + 1; columns 0)      -- and the fetch of the tiles t + 2, t + 3
+//   matrix (t + 2, t + 3; columns 0)  beside  vector (t, t + 1; columns 1)
+// (the last pair: the one-tile chain of the odd tile, or no chain at all, beside the second vector half -- k_kde_split ran one
+// chain for nothing there).
+template <int V>
+__device__ __forceinline__ void kz_pair_sums(const uint4* __restrict__ at, size_t kn, const uint4* __restrict__ bt, unsigned nbt,
+                                             const int* __restrict__ ha_int, double* __restrict__ part, const uint2* __restrict__ tmin) {
+    static_assert(kz_nch<V>() == 1, "one chunk");
+    constexpr int OPA = KS_NL, OPB = OPA + (kz_fold<V>() ? 0 : 1);
+    constexpr int OPT = kz_topn<V>() ? 1 : 0;
+    constexpr size_t TS = (size_t)OPB * 64;
+    const unsigned lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (the wave's columns: scalar)
+    const size_t it0 = ((size_t)blockIdx.x * 4 + wv) * 2;
+    const unsigned slices = gridDim.y, sl = blockIdx.y;
+    const unsigned t0 = __builtin_amdgcn_readfirstlane((unsigned)((size_t)nbt * sl / slices));
+    const unsigned t1 = __builtin_amdgcn_readfirstlane((unsigned)((size_t)nbt * (sl + 1) / slices));
+    uint4 B0[OPA], B1[OPA];
+#pragma unroll
+    for (int q = 0; q < OPA; q++) {
+        B0[q] = at[((it0 + 0) * OPA + q) * 64 + lane];
+        B1[q] = at[((it0 + 1) * OPA + q) * 64 + lane];
+    }
+    uint4 NB[2];
+    NB[0] = (lane < 32) ? make_uint4(KS_MONE | (KS_MONE << 16), KS_MONE, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
+    NB[1] = (lane < 32) ? make_uint4(0u, KS_MONE << 16, KS_MONE | (KS_MONE << 16), 0u) : make_uint4(0u, 0u, 0u, 0u);
+    uint4 BN = kz_bn_init<V>(NB[0]);
+    if constexpr (kz_fold<V>()) {                              // (k_kde_split: the A operand of the -n step)
+        const bool mine = (lane < 32) == (((lane & 31u) & 4u) == 0u);
+        NB[0] = make_uint4(0u, 0u, 0u, mine ? (KS_MONE | (KS_MONE << 16)) : 0u);
+    }
+    // (the integer part of the new row's 1/2|a_i|^2, ha_int, scales the row's whole sum here, once, at the end -- k_kde_split takes it
+    // off every batch's exponent: a subtraction per batch and two registers.  A batch's 2^n t with |n| <= 901 and a slice's sum of
+    // them stay well inside the range of a double, and a scaling by a power of two commutes with every rounding of the sum.)
+    double acc0 = 0.0, acc1 = 0.0;
+    if (t0 < t1) {
+        const unsigned np = (t1 - t0) >> 1;                    // whole pairs; then one more tile or none
+        const bool odd = ((t1 - t0) & 1u) != 0u;
+        const uint4* tb = bt + (size_t)t0 * TS;                // the pair in hand: its first tile's operands and info words
+        const uint2* ib = OPT ? tmin + t0 : tmin;
+        uint4 A0[OPB + OPT], A1[OPB + OPT];
+        f32x16 Za0, Za1, Zb0, Zb1;                             // columns 0 / columns 1, tile t / tile t + 1
+        int na = 0, nb = 0;
+        float p[8];
+#pragma unroll
+        for (int q = 0; q < OPB; q++) A0[q] = tb[q * 64 + lane];
+        if constexpr (OPT) { const uint2 ti = ib[0]; A0[OPB] = make_uint4(ti.x, ti.y, 0u, 0u); }
+        if (np > 0) {
+#pragma unroll
+            for (int q = 0; q < OPB; q++) A1[q] = tb[TS + q * 64 + lane];
+            if constexpr (OPT) { const uint2 ti = ib[1]; A1[OPB] = make_uint4(ti.x, ti.y, 0u, 0u); }
+            kz_chain<V, 2>(A0, A1, B0, NB, BN, Za0, Za1, na, lane);   // (t0, t0 + 1; columns 0): the whole chain up front
+        } else {
+            kz_chain<V, 1>(A0, A1, B0, NB, BN, Za0, Za1, na, lane);
+        }
+        for (unsigned k = 1; k < np; k++) {                    // every pair but the last: the tiles behind it are a pair too
+            const uint4 *nx0 = tb + 2 * TS, *nx1 = tb + 3 * TS;
+            const uint2 *ni0 = ib + (OPT ? 2 : 0), *ni1 = ib + (OPT ? 3 : 0);
+            __builtin_amdgcn_sched_barrier(0);
+            kz_pstep<V, 2, 2, true, 0>(A0, A1, B1, NB, Zb0, Zb1, nb, lane, Za0, Za1, na, acc0, p, BN, nx0, nx1, ni0, ni1);
+            kz_pstep<V, 2, 2, false, 0>(A0, A1, B0, NB, Za0, Za1, na, lane, Zb0, Zb1, nb, acc1, p, BN, nx0, nx1, ni0, ni1);
+            tb = nx0;
+            ib = ni0;
+        }
+        if (np > 0) {                                          // the last pair: behind it the odd tile (fetched into A0), or nothing
+            const uint4* nx0 = tb + (odd ? 2 * TS : 0);        // (nothing: the pair's first tile once more, no branch; unused)
+            const uint2* ni0 = ib + ((OPT && odd) ? 2 : 0);
+            kz_pstep<V, 2, 2, true, 0>(A0, A1, B1, NB, Zb0, Zb1, nb, lane, Za0, Za1, na, acc0, p, BN, nx0, tb, ni0, ib);
+            if (odd) {                                         // (wave-uniform)
+                kz_pstep<V, 1, 2, false, 0>(A0, A1, B0, NB, Za0, Za1, na, lane, Zb0, Zb1, nb, acc1, p, BN, nx0, tb, ni0, ib);
+            } else {
+                kz_pstep<V, 0, 2, false, 0>(A0, A1, B0, NB, Za0, Za1, na, lane, Zb0, Zb1, nb, acc1, p, BN, nx0, tb, ni0, ib);
+            }
+            tb = nx0;
+            ib = ni0;
+        }
+        if (odd) {                                             // the one-tile batch (A0 holds the tile, Za0 its chain against columns 0)
+            kz_pstep<V, 1, 1, false, 0>(A0, A1, B1, NB, Zb0, Zb1, nb, lane, Za0, Za1, na, acc0, p, BN, tb, tb, ib, ib);
+            kz_pstep<V, 0, 1, false, 0>(A0, A1, B0, NB, Za0, Za1, na, lane, Zb0, Zb1, nb, acc1, p, BN, tb, tb, ib, ib);
+        }
+    }
+    {
+        const int hs0 = ha_int[(it0 + 0) * 32 + (lane & 31)], hs1 = ha_int[(it0 + 1) * 32 + (lane & 31)];
+        const double v0 = ldexp(acc0 + __shfl_xor(acc0, 32, 64), -hs0);          // the two halves hold different previous rows
+        const double v1 = ldexp(acc1 + __shfl_xor(acc1, 32, 64), -hs1);
         const size_t i0 = (it0 + 0) * 32 + (lane & 31), i1 = (it0 + 1) * 32 + (lane & 31);
         if (lane < 32 && i0 < kn) part[(size_t)sl * kn + i0] = v0;
         if (lane < 32 && i1 < kn) part[(size_t)sl * kn + i1] = v1;
@@ -1044,14 +1291,14 @@ __global__ __launch_bounds__(256, WPS) void k_kde_split_lds(const uint4* __restr
         __syncthreads();
         f32x16 Z0, Z1;
         int n0 = 0, n1 = 0;
-        uint4 BN = make_uint4(0u, 0u, 0u, 0u);
+        uint4 BN = kz_bn_init<NCH>(NB[0]);
         unsigned cur = 0;
         {   // (t0, columns 0): the whole chain up front
             constexpr int NA = kz_nexact<NCH>();
             KsLdsOps<OPT ? OPB : -1> A{sA + lane, make_uint4(0u, 0u, 0u, 0u)};
             if constexpr (OPT) { const uint2 ti = tmin[t0]; A.info = make_uint4(ti.x, ti.y, 0u, 0u); }
             kz_mfma_range<NCH, 0, NA>(A, B0, NB, BN, Z0);
-            kz_reference<NCH>(Z0, A, NB[0], lane, n0, BN);
+            kz_reference<NCH>(Z0, A, lane, n0, BN);
             kz_mfma_range<NCH, NA, kz_nsteps<NCH>()>(A, B0, NB, BN, Z0);
         }
         for (unsigned t = t0; t < t1; t++) {
@@ -1355,7 +1602,11 @@ __global__ __launch_bounds__(256) void k_wq_rank(const double* __restrict__ hbk,
 // a tile's info words: (smallest top, all ones), or (0, 0) if the tops of its rows that take part (below KS_HB_ZERO) spread over
 // more than KS_TOPN_SPREAD -- then the kernel handles the tile as the plain variant would
 constexpr float KS_TOPN_SPREAD = 0.75f;
-__global__ __launch_bounds__(256) void k_tile_tmin(const float* __restrict__ topf, size_t ntiles, uint2* __restrict__ tinfo) {
+// A wide tile's top pieces move from K-slots 0..2 of its norm operand to 8..10 (the other half's first words, empty otherwise): the
+// kernel subtracts its top in a step of its own, against a pattern for those slots, and the -top - n step, whose operand addresses
+// slots 0..2, then finds nothing there.
+__global__ __launch_bounds__(256) void k_tile_tmin(const float* __restrict__ topf, size_t ntiles, uint2* __restrict__ tinfo,
+                                                   unsigned short* __restrict__ tiles, int ops) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= ntiles) return;
     float mn = 3.0e38f, mx = -3.0e38f;
@@ -1366,6 +1617,18 @@ __global__ __launch_bounds__(256) void k_tile_tmin(const float* __restrict__ top
     if (mx < mn) { mn = (float)KS_HB_ZERO; mx = mn; }              // no row of the tile takes part
     const bool wide = !(mx - mn <= KS_TOPN_SPREAD);
     tinfo[t] = wide ? make_uint2(0u, 0u) : make_uint2(__float_as_uint(mn), 0xffffffffu);
+    if (wide) {
+        uint4* ob = (uint4*)(tiles + (t * (size_t)ops + (size_t)(ops - 1)) * 512);     // the norm operand: the tile's last
+        for (int j = 0; j < 32; j++) {
+            uint4 lo = ob[j], hi = ob[32 + j];
+            hi.x = lo.x;
+            hi.y = lo.y & 0xffffu;
+            lo.x = 0u;
+            lo.y &= 0xffff0000u;
+            ob[j] = lo;
+            ob[32 + j] = hi;
+        }
+    }
 }
 // the pair count from which the top-order variants run (ks_topn_on, weights_plan.h); read on every call
 static double ks_topn_min_pairs() {
@@ -1381,10 +1644,13 @@ struct WrowsEntry { WrowsFn fn; int div; };
 static const WrowsEntry WROWS[4] = {{k_wrows<1>, 32}, {k_wrows<2>, 16}, {k_wrows<4, 3>, 8}, {k_wrows<4>, 8}};
 
 // the split kernels, [plain | fold | top-order][NCH - 1]:
-// three waves per SIMD at 16 parameters (129 VGPRs; four, with two spills: no faster), two at 32 (192)
+// three waves per SIMD at 16 parameters (132 VGPRs; four, with two spills: no faster), two at 32 (192)
 // ... one at 64 on this kernel (more than 256 registers: the two resident column operand sets alone are 128) -- which is
 // why 33..64 parameters go to k_kde_split_lds since round 6: the previous tiles in LDS, two waves per SIMD at four chunks
 // (194-205 registers), three at three chunks (up to 48 parameters; 163-168): 7.2-7.9 -> 4.2-6.3 ms per 1e10 pairs
+// (one chunk, folded and top-order families: TWO tiles per batch, kz_pair_sums -- 158 / 167 registers, no scratch: 2.10-2.12 -> 2.04-2.06 ms
+// per 1e10 pairs at 16 parameters, 1.85-1.88 -> 1.80-1.82 at 13, 1.70 -> 1.65 at 5 (profiles/kde_tile_pairs.txt); the plain family
+// would need 172 registers, four of them spilled, and keeps the one-tile loop)
 // (16 parameters: the sixteen-slot interleave, reference one slot behind the exact steps: 2.244 -> 2.220 ms per 1e10 pairs,
 // and ON TOP of it the operand sets trading places instead of being copied: -> 2.13-2.17 ms (without the finer interleave
 // the same loop was 2 % slower than the copying one, rounds 2 and 3); at 32 parameters either change and both together are
@@ -1392,15 +1658,15 @@ static const WrowsEntry WROWS[4] = {{k_wrows<1>, 32}, {k_wrows<2>, 16}, {k_wrows
 // kz_slots; four waves per SIMD, the reference two slots behind: +0.5 %)
 using SplitFn = decltype(&k_kde_split<1, 3, true, 1>);
 static const SplitFn KDE_SPLIT[3][4] = {
-    {k_kde_split<1, 3, true, 1>,
+    {k_kde_split<1, 3, true, 1>,                              // (the two-tile kernel needs 172 registers here: four spilled; not built)
      k_kde_split<2, 2>,
      k_kde_split_lds<3, KDE_LDS_W3, KDE_LDS_F4>,
      k_kde_split_lds<4, 2, KDE_LDS_F4>},
-    {k_kde_split<KS_FOLD + 1, 3, true, 1>,                     // (up to 13 parameters: seven MFMAs per 1024 pairs, no norm operand)
+    {k_kde_split<KS_FOLD + 1, 3, true, 1, 2>,                     // (up to 13 parameters: seven MFMAs per 1024 pairs, no norm operand)
      k_kde_split<KS_FOLD + 2, 2, false, 0>,                    // (17..29: thirteen instead of fifteen)
      k_kde_split_lds<KS_FOLD + 3, KDE_LDS_W3, KDE_LDS_F4>,     // (33..45: three chunks, nineteen MFMAs per 1024 pairs; previous tiles in LDS, two waves per SIMD)
      k_kde_split_lds<KS_FOLD + 4, 2, KDE_LDS_F4>},             // (49..61 with the previous tiles in LDS: twenty-five)
-    {k_kde_split<KS_TOPN + 1, 3, true, 1>,                     // (14..16 parameters, tiles in the order of the norm tops: eight MFMAs instead of nine)
+    {k_kde_split<KS_TOPN + 1, 3, true, 1, 2>,                     // (14..16 parameters, tiles in the order of the norm tops: eight MFMAs instead of nine)
      k_kde_split<KS_TOPN + 2, 2, false, 0>,                    // (30..32: fourteen instead of fifteen)
      k_kde_split_lds<KS_TOPN + 3, KDE_LDS_W3, KDE_LDS_F4>,     // (46..48: twenty)
      k_kde_split_lds<KS_TOPN + 4, 2, KDE_LDS_F4>},             // (62..64: twenty-six)
@@ -1479,7 +1745,7 @@ int launch_weights_prev(abc_ctx* ctx, size_t P, size_t kn_max, const double* the
         hipLaunchKernelGGL(k_wscale, dim3((unsigned)((Kp + 255) / 256)), dim3(256), 0, s, theta_prev, Kp, Kp,
                            (int)P, PP, wc, centre, (size_t)1, w_prev, b, hb);
     }
-    if (topn) hipLaunchKernelGGL(k_tile_tmin, dim3((unsigned)((nbt + 255) / 256)), dim3(256), 0, s, (const float*)topf, nbt, tmin);
+    if (topn) hipLaunchKernelGGL(k_tile_tmin, dim3((unsigned)((nbt + 255) / 256)), dim3(256), 0, s, (const float*)topf, nbt, tmin, bt, pl.opb);
     ABC_HIP(ctx, hipGetLastError());
     out->wc = wc; out->b = b; out->hb = hb; out->bt = bt; out->far_list = far_list; out->tmin = (unsigned*)tmin;
     out->Kp = Kp; out->P = P; out->kn_max = kn_max; out->split = split ? 1 : 0; out->ready = 1;

@@ -25,6 +25,14 @@ constexpr int KS_FOLD = 100;               // variant tag KS_FOLD + chunks: 101,
 // pair sums do not care about the order of their terms): the spread inside a tile is the set's range / its tiles.  Taking the
 // maximum of X' - top row by row instead (16 subtractions per lane and tile) cost more than the MFMA saved (+5.7 % at 16
 // parameters); this way the vector pipe gets one subtraction per batch.
+// The one-chunk kernel takes its batch over TWO consecutive tiles (weights.hip: kz_pair_sums): n = floor(max over both of max X' -
+// tmin, each tile with its own tmin).  Every top of either tile is at least its tile's tmin, so X' - top - n <= 1 still holds for
+// all 32 values, the largest of them is at least -KS_TOPN_SPREAD, and the partial sums of X' - top - n stay below 2^10 in units of
+// 2^-14 for every result within 2^-126 of the largest of the 32 -- the operand ranges of the bf16 step are those of one tile
+// (mfma_topn_probe); what lies further down flushes as before.  A tile whose tops spread over more than KS_TOPN_SPREAD (a "wide"
+// tile of the sparse tail) has its top subtracted in a step of its own in front of the reference, from K-slots 8..10 where
+// k_tile_tmin puts its pieces, so that the -top - n step -- the same instruction and operand for every tile -- finds slots 0..2 empty.
+// The plan below does not know about any of this: a slice of an odd number of tiles ends with a one-tile batch inside the kernel.
 constexpr int KS_TOPN = 200;
 
 // 33..64 parameters: the previous tiles staged in LDS (k_kde_split_lds), and with it three stored chunks instead of four at 33..48

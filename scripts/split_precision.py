@@ -7,14 +7,17 @@ h0.h1' + h1.h0' + h1.h1' + h0.r2' + r2.h0' goes through an f32 accumulator, emul
 For the shipped split the f32 evaluation of the terms (kz_slots: the 16 terms of a lane's batch share n = floor(max X),
 X - n exact, the small products accumulated on top of it in the same f32 accumulator, 2^Z in f32, an f32 sum of the 16, then an
 exact scaling by 2^n) is emulated as well and the RELATIVE error of the batch sums reported: that, not the exponent error, is
-what a weight inherits.
-    python scripts/split_precision.py [P] [n]"""
+what a weight inherits.  With `pairs` the same for the two-tile batch of the one-chunk kernels (kz_pair_sums): 32 terms -- the 16
+a lane owns of each of two consecutive tiles (here: 32 consecutive columns of the random set, the same thing for its i.i.d. rows)
+-- under one n = floor(max of the 32), eight chains of four and a tree of seven.
+    python scripts/split_precision.py [P] [n] [pairs]"""
 import sys
 
 import numpy as np
 
 P = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 1500
+TILES = 2 if "pairs" in sys.argv[3:] else 1                   # tiles per batch
 rng = np.random.default_rng(1)
 # scaled coordinates of a posterior against the previous one: N(0, 0.85) (sqrt(log2 e) / sqrt(2) proposal sigmas)
 a = rng.normal(0, 0.85, (n, P))
@@ -48,30 +51,36 @@ base = [(0, 1), (1, 0), (1, 1), (2, 3), (3, 2)]                  # (operand of a
 cases = [("shipped: 3 limbs, 6 products", base),
          ("cross: + h1.r2' + r2.h1'", base + [(4, 5), (5, 4)]),
          ("without h1.h1'", [p for p in base if p != (1, 1)])]
-def term_f32(X, A, B, pairs):
+def term_f32(X, A, B, pairs, tiles=1):
     """kz_slots of weights.hip: the 16 terms a lane owns of one 32 x 32 block share n = floor(max X); X - n is exact, the
     small products are then added INTO THE SAME f32 accumulator -- emulated with one rounding per product and 16-parameter
     chunk (what an MFMA step does at most) --, 2^Z from the hardware's v_exp_f32 -- emulated by the correctly rounded float of
     exp2(Z); the hardware adds at most one more ulp (measured 8.2e-8 max / 2.6e-8 rms relative on [-0.3, 1.3],
     scripts/exp2_hw_accuracy.hip) --, the 16 terms are added in f32 (four chains of four, then (p0 + p1) + (p2 + p3)) and the
-    batch sum is scaled by 2^n exactly.  Returns the batch sums (rows x columns / 16) and Z."""
+    batch sum is scaled by 2^n exactly.  tiles = 2 (kz_pair_sums): batches of 32 -- two groups of 16 --, eight chains of four
+    (four per group), ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)).  Returns the batch sums (rows x columns / (16 tiles))
+    and Z."""
     Xf = X.astype(np.float32)
     assert np.array_equal(Xf.astype(np.float64), X)
     r, c = Xf.shape
-    c16 = c // 16 * 16
-    Xb = Xf[:, :c16].reshape(r, -1, 16)
+    nb = 16 * tiles
+    c16 = c // nb * nb
+    Xb = Xf[:, :c16].reshape(r, -1, nb)
     nfl = np.floor(Xb.max(axis=2, keepdims=True)).astype(np.float32)
     Z = (Xb - nfl).astype(np.float32)
     assert np.array_equal(Z.astype(np.float64), Xb.astype(np.float64) - nfl.astype(np.float64)), "X - n is not exact in f32"
     for i, j in pairs:
         for c0 in range(0, P, 16):
-            ch = (A[i][:, c0:c0 + 16] @ B[j][:, c0:c0 + 16].T)[:, :c16].reshape(r, -1, 16)
+            ch = (A[i][:, c0:c0 + 16] @ B[j][:, c0:c0 + 16].T)[:, :c16].reshape(r, -1, nb)
             Z = (Z.astype(np.float64) + ch).astype(np.float32)
     e = np.exp2(Z.astype(np.float64)).astype(np.float32)
-    p = [e[:, :, k] for k in range(4)]
-    for i in range(4, 16):
-        p[i & 3] = (p[i & 3] + e[:, :, i]).astype(np.float32)
-    t = ((p[0] + p[1]).astype(np.float32) + (p[2] + p[3]).astype(np.float32)).astype(np.float32)
+    t = None
+    for g in range(tiles):
+        p = [e[:, :, 16 * g + k] for k in range(4)]
+        for i in range(4, 16):
+            p[i & 3] = (p[i & 3] + e[:, :, 16 * g + i]).astype(np.float32)
+        u = ((p[0] + p[1]).astype(np.float32) + (p[2] + p[3]).astype(np.float32)).astype(np.float32)
+        t = u if t is None else (t + u).astype(np.float32)
     return np.ldexp(t.astype(np.float64), nfl[:, :, 0].astype(np.int64)), Z
 
 
@@ -89,8 +98,9 @@ for name, pairs in cases:
     print("%-32s MFMAs %2d   truncation only: rms %.2e max %.2e   with the f32 accumulator: rms %.2e max %.2e" % (
         name, (1 + len(pairs)) * ((P + 15) // 16) + 3, np.sqrt((e_tr ** 2).mean()), e_tr.max(), np.sqrt((e_all ** 2).mean()), e_all.max()))
     if name.startswith("shipped"):
-        t, g = term_f32(X, A, B, pairs)
-        exact = np.exp2(ref)[:, :t.shape[1] * 16].reshape(n, -1, 16).sum(axis=2)
+        t, g = term_f32(X, A, B, pairs, TILES)
+        nb = 16 * TILES
+        exact = np.exp2(ref)[:, :t.shape[1] * nb].reshape(n, -1, nb).sum(axis=2)
         rel = np.abs(t / exact - 1.0)
-        print("   f32 term sums (16 terms 2^(a.b) per batch) of the shipped split: relative error rms %.2e max %.2e mean %.2e;  Z = X - n + Y in [%.3f, %.3f]" % (
-            np.sqrt((rel ** 2).mean()), rel.max(), (t / exact - 1.0).mean(), g.min(), g.max()))
+        print("   f32 term sums (%d terms 2^(a.b) per batch) of the shipped split: relative error rms %.2e max %.2e mean %.2e;  Z = X - n + Y in [%.3f, %.3f]" % (
+            nb, np.sqrt((rel ** 2).mean()), rel.max(), (t / exact - 1.0).mean(), g.min(), g.max()))
