@@ -368,6 +368,13 @@ SIGNATURES = {
     "abc_glm_particle_ranking_pls_targets": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "abc_glm_weighted_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
     "abc_glm_weighted": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    # the same with the exact quantiles and CDF: glm, then the abc_summary, then the context
+    "abc_glm_rank_targets_summary_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp,
+                                              _vp]),
+    "abc_glm_particle_ranking_pls_targets_summary": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _d, _i, _i, _vp, _sz, _vp,
+                                                          _vp, _vp]),
+    "abc_glm_weighted_summary_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "abc_glm_weighted_summary": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
 }
 
 # The posterior products (abc_summary, abc_density, abc_joint, abc_draws) share their four argument lists, each ending in the product's

@@ -408,10 +408,11 @@ int launch_hpd(abc_ctx*, const SmValues& sv, size_t B, size_t K, size_t P, const
 // the row of entry e of target b, idx[b K + e] (NULL: e itself, B = 1); weights om[i] or w[e] (one of them at most, NULL: 1); the
 // observed scores O[b KCO + k].  sv: the parameters' values and weights as launch_density_segs reads them (the bandwidths).
 // nA >= n: the bound abc_glm_need was asked with (A of the model).  glm: every array in device memory, checked by the caller
-size_t abc_glm_need(size_t B, size_t K, size_t P, size_t nA, size_t G);
+// sum: NULL, or the exact quantiles and CDF of the marginal mixtures (the *_summary entries; abc_glm_need's sum says which)
+size_t abc_glm_need(size_t B, size_t K, size_t P, size_t nA, size_t G, bool sum = false);
 int launch_glm(abc_ctx*, const SmValues& sv, const double* S, size_t sld, const double* Y, size_t ldy, const uint64_t* idx,
                const double* om, const double* w, const double* O, int KCO, size_t B, size_t K, size_t P, size_t n, size_t nA,
-               const abc_glm* glm, const char* fn);
+               const abc_glm* glm, const abc_summary* sum, const char* fn);
 int launch_select_smallest(abc_ctx*, const double* dist, size_t n, size_t K, uint64_t idx_base,
                            uint64_t* idx, double* dist_out, bool defer_check = false);
 int abc_select_check(abc_ctx* ctx, int* failed);

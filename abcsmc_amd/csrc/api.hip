@@ -1866,6 +1866,8 @@ struct TgRequest {                             // (members in the order of the e
     bool any_excl = false;                     // exclude names a row for some target: set by tg_check
     const abc_path* path = nullptr;            // TG_PATH only: required; Ks in host memory
     const abc_glm* glm = nullptr;              // TG_GLM only: required
+    bool glm_summary = false;                  // TG_GLM: a *_summary entry; glm_sum is then required and every output of glm optional
+    const abc_summary* glm_sum = nullptr;
     int* glm_nc = nullptr;                     // TG_GLM, optional: receives the model's ncomp once the run has read it (host)
     bool segments() const { return kind == TG_PRODUCT; }      // the rows' values are read after the ranking
     bool regress() const { return kind == TG_ADJUST || (segments() && method == ABC_POSTERIOR_LOCLINEAR); }
@@ -1879,7 +1881,9 @@ struct TgRequest {                             // (members in the order of the e
 }  // namespace
 
 // the descriptor of an ABC-GLM request, its limits and the context's settings it refuses (A: 0 where the caller has none)
-static int glm_check(abc_ctx* ctx, const char* fn, const abc_glm* m, size_t P, size_t A) {
+// (summary: a *_summary entry, whose sum is required; every level strictly inside (0, 1), the mixture's quantile at 0 or 1 being infinite)
+static int glm_check(abc_ctx* ctx, const char* fn, const abc_glm* m, size_t P, size_t A, bool summary = false,
+                     const abc_summary* sum = nullptr) {
     if (!m) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (glm is required)", fn);
     if (ctx->tf_buf) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: parameter transforms are set on the context, and ABC-GLM is not an adjustment", fn);
     if (ctx->hcorr) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: the variance correction is set on the context, and ABC-GLM is not an adjustment", fn);
@@ -1890,9 +1894,23 @@ static int glm_check(abc_ctx* ctx, const char* fn, const abc_glm* m, size_t P, s
     if (!(m->cut >= 0.0) || !std::isfinite(m->cut)) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: cut = %g (finite, >= 0)", fn, m->cut);
     if (!(m->bw_scale > 0.0) || !std::isfinite(m->bw_scale))
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: bw_scale = %g (finite, > 0)", fn, m->bw_scale);
-    if (!m->dens && !m->lo_x && !m->step && !m->mode && !m->mode_dens && !m->mean && !m->var && !m->ess && !m->log_md && !m->C &&
-        !m->c0 && !m->sigma_s && !m->T && !m->peaks && !m->c && !m->status)
-        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of glm is NULL", fn);
+    const bool none = !m->dens && !m->lo_x && !m->step && !m->mode && !m->mode_dens && !m->mean && !m->var && !m->ess && !m->log_md &&
+                      !m->C && !m->c0 && !m->sigma_s && !m->T && !m->peaks && !m->c && !m->status;
+    if (!summary) {
+        if (none) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: every output member of glm is NULL", fn);
+        return ABC_OK;
+    }
+    if (!sum) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (sum is required)", fn);
+    if (sum->quant) {
+        if (sum->nq == 0 || sum->nq > 64) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: nq = %zu levels (1 to 64)", fn, sum->nq);
+        if (!sum->probs) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (probs is required)", fn);
+        for (size_t q = 0; q < sum->nq; q++)
+            if (!(sum->probs[q] > 0.0 && sum->probs[q] < 1.0))
+                ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: probs[%zu] = %g is not a level strictly inside (0, 1)", fn, q, sum->probs[q]);
+    }
+    if (sum->cdf && !sum->truth) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: cdf requires truth", fn);
+    if (none && !sum->quant && !sum->cdf)
+        ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: quant and cdf of sum and every output member of glm are NULL", fn);
     return ABC_OK;
 }
 // the model's ncomp of a device model record (synchronises), within ABC-GLM's limit
@@ -1950,6 +1968,19 @@ static void glm_down(Stage& s, const abc_glm* h, const abc_glm& d, size_t B, siz
     s.down(h->status, d.status, B);
 }
 
+// the abc_summary of a *_summary entry of ABC-GLM for B targets, host (h) <-> arena: quant only with levels (nq is not read without)
+static abc_summary glm_summary_stage(Stage& s, const abc_summary* h, size_t B, size_t P) {
+    abc_summary d = *h;
+    d.truth = h->truth ? s.up(h->truth, B * P) : nullptr;
+    d.quant = h->quant ? s.dev<double>(B * h->nq * P) : nullptr;
+    d.cdf = h->cdf ? s.dev<double>(B * P) : nullptr;
+    return d;
+}
+static void glm_summary_down(Stage& s, const abc_summary* h, const abc_summary& d, size_t B, size_t P) {
+    if (h->quant) s.down(h->quant, d.quant, B * h->nq * P);
+    s.down(h->cdf, d.cdf, B * P);
+}
+
 // the tolerance list of a path request
 static int path_check(abc_ctx* ctx, const char* fn, const abc_path* path) {
     if (!path) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (path is required)", fn);
@@ -1994,7 +2025,7 @@ static int tg_check(abc_ctx* ctx, const char* fn, TgRequest& r, bool host) {
     if (!plain && r.kernel != ABC_KERNEL_EPANECHNIKOV && r.kernel != ABC_KERNEL_RECTANGULAR)
         ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: kernel %d (0 = Epanechnikov, 1 = rectangular)", fn, r.kernel);
     if ((!plain || r.post_mean) && r.P && r.ldy < N) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: ldy %zu < N %zu", fn, r.ldy, N);
-    if (r.kind == TG_GLM) ABC_TRY(glm_check(ctx, fn, r.glm, r.P, r.A));
+    if (r.kind == TG_GLM) ABC_TRY(glm_check(ctx, fn, r.glm, r.P, r.A, r.glm_summary, r.glm_sum));
     if (!plain) {     // the adjustment's limits, for both of a product's methods too
         if (r.A > 64) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: A = %zu components (at most 64)", fn, r.A);
         if (r.P > 1024) ABC_FAIL(ctx, ABC_ERR_UNSUPPORTED, "%s: P = %zu parameters (at most 1024)", fn, r.P);
@@ -2044,7 +2075,7 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     if (r.regress()) b += abc_adjust_need(N, A, P, B, K, hc, rg);
     if (r.kind == TG_PATH) b += abc_path_need(N, A, P, B, K, r.path->T, hc, rg);
     if (r.segments()) b += 2 * B * K * 8 + 16 * 256;                                         // (tg_run's own idx and dist)
-    if (r.kind == TG_GLM) b += 2 * B * K * 8 + 16 * 256 + abc_glm_need(B, K, P, A, r.glm->G);
+    if (r.kind == TG_GLM) b += 2 * B * K * 8 + 16 * 256 + abc_glm_need(B, K, P, A, r.glm->G, r.glm_summary);
     // (under row importance weights the rejection path's summaries take the loclinear path's route, one tolerance at a time)
     if (r.path_summary())
         b += abc_path_summary_need(B, r.path->Ks, r.path->T, P, ctx->rw_N ? 1 : r.method) + (r.idx ? 0 : B * K * 8 + 256);
@@ -2058,6 +2089,7 @@ static size_t tg_need(const abc_ctx* ctx, const TgRequest& r, bool host, int rul
     else if (r.kind != TG_GLM) b += (B * K * P + B * K + B * (A + 1) * P + B) * 8 + 8 * 256;      // abc_adjust_out: theta, weight, coef, rank + status
     if (r.path_summary()) return b + B * P * (r.path->T * (r.prod.sum->nq + 1) + 1) * 8 + 16 * 256;     // truth, quant, cdf
     if (r.kind == TG_GLM) b += glm_stage_bytes(r.glm, B, K, P, A);
+    if (r.kind == TG_GLM && r.glm_summary) b += B * P * (r.glm_sum->quant ? r.glm_sum->nq + 2 : 2) * 8 + 4 * 256;      // truth, quant, cdf
     return b + r.prod.stage_bytes(B, K, P);
 }
 
@@ -2107,7 +2139,7 @@ static int tg_run_queued(abc_ctx* ctx, const char* fn, const TgRequest& r, const
         ABC_TRY(launch_rank_targets(ctx, r.X, r.ldx, r.Y, r.ldy, r.N, r.M, r.P, r.model, r.A, r.targets, r.ldt, B, r.exclude,
                                     r.any_excl, K, ix, d, nullptr, &sc));
         return launch_glm(ctx, tg_values(r, ix, nullptr, om), sc.S, sc.sld, r.Y, r.ldy, ix, om, nullptr, sc.O, sc.KCO, B, K, r.P, n,
-                          r.A, r.glm, fn);
+                          r.A, r.glm, r.glm_summary ? r.glm_sum : nullptr, fn);
     }
     if (r.kind == TG_PATH) {
         const bool ps = r.path_summary(), lin = ps && r.method == ABC_POSTERIOR_LOCLINEAR;
@@ -2238,9 +2270,15 @@ static int tg_host(abc_ctx* ctx, const char* fn, TgRequest h, double train_frac,
         r.glm = &gd;
         r.glm_nc = &gnc;
     }
+    abc_summary gsd = {};
+    if (h.kind == TG_GLM && h.glm_summary) {
+        gsd = glm_summary_stage(s, h.glm_sum, B, P);
+        r.glm_sum = &gsd;
+    }
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_TRY(tg_run(ctx, fn, r));
     if (h.kind == TG_GLM) glm_down(s, h.glm, gd, B, K, P, (size_t)gnc);
+    if (h.kind == TG_GLM && h.glm_summary) glm_summary_down(s, h.glm_sum, gsd, B, P);
     s.down(h.idx, r.idx, B * K);
     s.down(h.dist, r.dist, B * K);
     s.down(h.post_mean, r.post_mean, B * P);
@@ -2494,10 +2532,35 @@ extern "C" int abc_glm_particle_ranking_pls_targets(const abc_glm* glm, abc_ctx*
                    ncomp);
 }
 
+// the same with the exact quantiles and CDF of the marginal mixtures: the summary's descriptor second, every output of glm optional
+extern "C" int abc_glm_rank_targets_summary_dev(const abc_glm* glm, const abc_summary* sum, abc_ctx* ctx, const double* X, size_t ldx,
+                                                const double* Y, size_t ldy, size_t N, size_t M, size_t P, const double* model, size_t A,
+                                                const double* targets, size_t ldt, size_t B, const uint64_t* exclude, size_t K,
+                                                uint64_t* idx, double* dist) {
+    CHECK_CTX(ctx);
+    TgRequest r = glm_request(glm, X, ldx, Y, ldy, N, M, P, model, A, targets, ldt, B, exclude, K, idx, dist);
+    r.glm_summary = true;
+    r.glm_sum = sum;
+    return tg_dev(ctx, "abc_glm_rank_targets_summary_dev", r);
+}
+
+extern "C" int abc_glm_particle_ranking_pls_targets_summary(const abc_glm* glm, const abc_summary* sum, abc_ctx* ctx, const double* X,
+                                                            const double* Y, size_t N, size_t M, size_t P, const double* targets,
+                                                            size_t B, double train_frac, int max_comp, int rule,
+                                                            const uint64_t* exclude, size_t K, uint64_t* idx, double* dist,
+                                                            int32_t* ncomp) {
+    CHECK_CTX(ctx);
+    TgRequest r = glm_request(glm, X, N, Y, N, N, M, P, nullptr, 0, targets, B, B, exclude, K, idx, dist);
+    r.glm_summary = true;
+    r.glm_sum = sum;
+    return tg_host(ctx, "abc_glm_particle_ranking_pls_targets_summary", r, train_frac, max_comp, rule, ncomp);
+}
+
 // the generic form: any retained sample with any statistics, B = 1
 static int glm_weighted_check(abc_ctx* ctx, const char* fn, const abc_glm* glm, const double* theta, size_t ldv, const double* stats,
-                              size_t lds, size_t K, size_t P, size_t n, const double* obs) {
-    ABC_TRY(glm_check(ctx, fn, glm, P, 0));
+                              size_t lds, size_t K, size_t P, size_t n, const double* obs, bool summary = false,
+                              const abc_summary* sum = nullptr) {
+    ABC_TRY(glm_check(ctx, fn, glm, P, 0, summary, sum));
     if (!theta) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (theta is required)", fn);
     if (!stats) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (stats is required)", fn);
     if (!obs) ABC_FAIL(ctx, ABC_ERR_INVALID, "%s: null argument (obs is required)", fn);
@@ -2518,7 +2581,20 @@ extern "C" int abc_glm_weighted_dev(const abc_glm* glm, abc_ctx* ctx, const doub
     ABC_TRY(glm_weighted_check(ctx, fn, glm, theta, ldv, stats, lds, K, P, n, obs));
     ABC_TRY(abc_ws_reserve(ctx, abc_glm_need(1, K, P, n, glm->G) + 16 * 256));
     if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
-    return launch_glm(ctx, weighted_values(theta, ldv, w), stats, lds, theta, ldv, nullptr, nullptr, w, obs, (int)n, 1, K, P, n, n, glm, fn);
+    return launch_glm(ctx, weighted_values(theta, ldv, w), stats, lds, theta, ldv, nullptr, nullptr, w, obs, (int)n, 1, K, P, n, n, glm,
+                      nullptr, fn);
+}
+
+extern "C" int abc_glm_weighted_summary_dev(const abc_glm* glm, const abc_summary* sum, abc_ctx* ctx, const double* theta, size_t ldv,
+                                            const double* stats, size_t lds, size_t K, size_t P, size_t n, const double* obs,
+                                            const double* w) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_glm_weighted_summary_dev";
+    ABC_TRY(glm_weighted_check(ctx, fn, glm, theta, ldv, stats, lds, K, P, n, obs, true, sum));
+    ABC_TRY(abc_ws_reserve(ctx, abc_glm_need(1, K, P, n, glm->G, true) + 16 * 256));
+    if (w) ABC_TRY(abc_summary_check_weights(ctx, w, K, fn));
+    return launch_glm(ctx, weighted_values(theta, ldv, w), stats, lds, theta, ldv, nullptr, nullptr, w, obs, (int)n, 1, K, P, n, n, glm,
+                      sum, fn);
 }
 
 extern "C" int abc_glm_weighted(const abc_glm* glm, abc_ctx* ctx, const double* theta, const double* stats, size_t K, size_t P, size_t n,
@@ -2535,8 +2611,33 @@ extern "C" int abc_glm_weighted(const abc_glm* glm, abc_ctx* ctx, const double* 
     const abc_glm d = glm_stage(s, glm, 1, K, P, n);
     if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
-    ABC_TRY(launch_glm(ctx, weighted_values(th_d, K, w_d), st_d, K, th_d, K, nullptr, nullptr, w_d, ob_d, (int)n, 1, K, P, n, n, &d, fn));
+    ABC_TRY(launch_glm(ctx, weighted_values(th_d, K, w_d), st_d, K, th_d, K, nullptr, nullptr, w_d, ob_d, (int)n, 1, K, P, n, n, &d, nullptr,
+                       fn));
     glm_down(s, glm, d, 1, K, P, n);
+    ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ABC_HIP(ctx, hipGetLastError());
+    return ABC_OK;
+}
+
+extern "C" int abc_glm_weighted_summary(const abc_glm* glm, const abc_summary* sum, abc_ctx* ctx, const double* theta, const double* stats,
+                                        size_t K, size_t P, size_t n, const double* obs, const double* w) {
+    CHECK_CTX(ctx);
+    const char* fn = "abc_glm_weighted_summary";
+    ABC_TRY(glm_weighted_check(ctx, fn, glm, theta, K, stats, K, K, P, n, obs, true, sum));
+    ABC_TRY(abc_ws_reserve(ctx, abc_glm_need(1, K, P, n, glm->G, true) + (K * (P + n + 1) + n) * 8 + glm_stage_bytes(glm, 1, K, P, n) +
+                                    P * (sum->quant ? sum->nq + 2 : 2) * 8 + 20 * 256));
+    Stage s{ctx};
+    const double* th_d = s.up(theta, K * P);
+    const double* st_d = s.up(stats, K * n);
+    const double* ob_d = s.up(obs, n);
+    const double* w_d = w ? s.up(w, K) : nullptr;
+    const abc_glm d = glm_stage(s, glm, 1, K, P, n);
+    const abc_summary sd = glm_summary_stage(s, sum, 1, P);
+    if (s.full) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    if (w_d) ABC_TRY(abc_summary_check_weights(ctx, w_d, K, fn));
+    ABC_TRY(launch_glm(ctx, weighted_values(th_d, K, w_d), st_d, K, th_d, K, nullptr, nullptr, w_d, ob_d, (int)n, 1, K, P, n, n, &d, &sd, fn));
+    glm_down(s, glm, d, 1, K, P, n);
+    glm_summary_down(s, sum, sd, 1, P);
     ABC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ABC_HIP(ctx, hipGetLastError());
     return ABC_OK;

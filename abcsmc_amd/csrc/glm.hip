@@ -19,6 +19,14 @@
 //                  points), GL_R grid points per thread, (t_e[j], c^_e) staged in LDS in tiles, every lane reads the same entry, one
 //                  fma chain per grid point over e ascending; the term is dn_kern (density_dev.h: fp64 argument, 2^r split)
 //   k_glm_mode     the chunks' candidates in chunk order (G > GL_GC)
+// and, for the *_summary entries only (abc_glm_rank_targets_summary_dev and its kin; the four older entries launch none of them):
+//   k_glm_cdf      one work-group per (target, parameter): F_j(truth), a thread's fma chain over e = t (mod 256) of c^_e erfc(.),
+//                  then the fixed tree
+//   k_glm_quant    work-groups over (target, parameter, group of GL_QL levels): the root of F_j(x) = q for every level of the group
+//                  in lockstep, a safeguarded Newton iteration (with Halley's correction) inside the guaranteed bracket
+//                  [t_min + sigma z_q, t_max + sigma z_q]; one iteration is one pass over K, every thread summing its own entries
+//                  e = t (mod 256) of c^_e erfc(.), c^_e exp(.) and c^_e a_e exp(.) for every level, a fixed shuffle tree per wave and
+//                  the four waves' sums in order
 // Chunk sizes depend on K only and tile sizes on nothing, every sum is a fixed chain or a fixed tree, and there are no floating-
 // point atomics: a target's outputs are the same bits alone and in any batch, and whatever outputs are asked for.
 // The bandwidths h_j are the marginal density's (launch_density_segs: bw.nrd0 on the weighted sample, or the given ones).
@@ -42,6 +50,9 @@ constexpr int GL_GC = GL_BS * GL_R;                         // grid points per w
 constexpr int GL_TILE = 1024;                               // entries staged in LDS at a time
 constexpr size_t GL_BATCH_BYTES = (size_t)256 << 20;        // workspace of one batch of targets
 constexpr unsigned GL_MAX_GRID_Y = 65535;
+constexpr int GL_QL = 8;                                    // levels of a k_glm_quant work-group
+constexpr int GL_QSLACK = 24;                               // steps of a level that may fail to halve its bracket
+constexpr int GL_QCAP = 64 + GL_QSLACK + 2;                 // iterations at most (see k_glm_quant)
 constexpr double GL_PIVOT = 1e-10;
 
 // a target's record, made by k_glm_solve (doubles; matrices at row stride GL_MAX)
@@ -59,6 +70,20 @@ constexpr int GR_LEN = GR_ST + 2;
 
 struct GlSeg {                                              // per (target, parameter), made by k_glm_stats (all NaN: a bad target)
     double lo_x, step, den, c;                              // den = sqrt(2 pi T_jj), c = sqrt(log2(e) / 2) / sqrt(T_jj)
+};
+
+struct GlQs {                                               // per (target, parameter), made by k_glm_stats for the summaries
+    double tlo, thi, mean, sd;                              // the smallest and largest peak of the counted rows, mean and sqrt(var)
+};
+
+struct GlLev {                                              // the levels of a summary (a kernel argument)
+    double q[64], z[64];                                    // z = Phi^-1(q), from the host
+    int nq;
+};
+
+struct GlSum {                                              // the caller's abc_summary, device pointers
+    const double* truth;
+    double *quant, *cdf;
 };
 
 struct GlSrc {
@@ -90,6 +115,7 @@ struct GlWs {                   // one batch's blocks; b below is the target's p
     GlSeg* seg;                 // [b][j]
     double* pf;                 // [b][j][chunk of the grid]
     int* pg;
+    GlQs* qs;                   // [b][j]; NULL without a summary
 };
 
 typedef AjChunks GlPlan;        // the adjustment's chunks of a target's rows (adjust_dev.h): from K alone
@@ -581,6 +607,11 @@ __global__ __launch_bounds__(256) void k_glm_stats(size_t K, int P, size_t b0, G
         p.c = 0.8493218002880191 / sd;                         // sqrt(log2(e) / 2)
     }
     ws.seg[bl * P + j] = p;
+    if (ws.qs) {
+        GlQs s;
+        s.tlo = lo; s.thi = hi; s.mean = m; s.sd = sqrt(Tjj + v);
+        ws.qs[bl * P + j] = s;
+    }
     if (o.mean) o.mean[sg] = bad ? dn_nan() : m;
     if (o.var) o.var[sg] = bad ? dn_nan() : Tjj + v;
     if (o.lo_x) o.lo_x[sg] = p.lo_x;
@@ -667,12 +698,153 @@ __global__ __launch_bounds__(256) void k_glm_mode(size_t nseg, size_t sg0, int n
     if (o.mode_dens) o.mode_dens[sg0 + s] = none ? dn_nan() : bf;
 }
 
+// ---- the exact CDF and quantiles of the marginal mixture (the *_summary entries) ----
+// F_j(x) = sum_e c^_e Phi((x - t_e[j]) / sigma) = sum_e c^_e erfc(a_e) / 2 with a_e = (t_e[j] - x) / (sigma sqrt 2).  An uncounted row
+// has c^_e = 0 exactly and a finite t_e (its row of Z is zero), so its term is an exact zero and the sums run over every e.
+
+// grid (P, targets of the batch)
+__global__ __launch_bounds__(256) void k_glm_cdf(size_t K, int P, size_t b0, GlSum sm, GlWs ws) {
+    __shared__ double r[256];
+    const int t = threadIdx.x, j = (int)blockIdx.x;
+    const size_t bl = blockIdx.y, sg = (b0 + bl) * P + j;
+    const double* rec = ws.rec + bl * GR_LEN;
+    const double* tp = ws.tpk + (bl * P + j) * K;
+    const double* ch = ws.chat + bl * K;
+    const double x = sm.truth[sg];
+    const double ri = 1.0 / (sqrt(rec[GR_T + j * GL_MAX + j]) * 1.4142135623730951);
+    double s = 0.0;
+    for (size_t e = t; e < K; e += 256) s = fma(ch[e], erfc((tp[e] - x) * ri), s);
+    s = gl_tree_sum(s, r);
+    if (t != 0) return;
+    double F = 0.5 * s;
+    if (x == INFINITY) F = 1.0;
+    if (x == -INFINITY) F = 0.0;
+    sm.cdf[sg] = rec[GR_ST] != 0.0 ? dn_nan() : F;             // (a NaN truth: every term is NaN)
+}
+
+// the doubles in ascending order as unsigned integers (-0.0 right below +0.0), and back
+__device__ __forceinline__ uint64_t gl_ord(double x) {
+    const uint64_t u = (uint64_t)__double_as_longlong(x);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double gl_unord(uint64_t k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+// a fixed tree over the 64 lanes of a wave; lane 0 holds the sum
+__device__ __forceinline__ double gl_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// grid (P x groups of GL_QL levels, targets of the batch).  Level l of the group belongs to thread l, which keeps its bracket
+// (lo, hi), the values F found at its ends (NaN: not evaluated), the next point x and its allowance; the work-group reads x and
+// the activity flags from LDS, and every thread sums its own entries for every active level.
+// The bracket.  Every peak lies in [t_min, t_max], so Phi((x - t_max) / sigma) <= F(x) <= Phi((x - t_min) / sigma) and the root lies
+// in [t_min + sigma z, t_max + sigma z]; the ends are widened by 2^-49 of their terms and four doubles for the rounding of z, sigma
+// and the two operations.  They are not evaluated: an end moves only to a point the device has evaluated, F < q to lo, else to hi.
+// A step.  s = r / f with r = F - q, Halley's correction s / (1 - s f' / (2 f)) where that factor is within [1/2, 2]; a point equal
+// to x moves one double towards the root.  The point is taken if it lies strictly inside the bracket and the level's allowance is
+// not spent; otherwise the next point is the middle of the bracket counted in doubles.
+// The cap.  W = the doubles from lo to hi.  A step either leaves W' <= ceil(W / 2) (every middle point does) or it costs one of the
+// GL_QSLACK allowances; W < 2^64, so after at most 64 + GL_QSLACK steps W <= 1: no double lies strictly inside.  GL_QCAP is that
+// plus two.  The result is the end whose evaluated F is nearer q (hi on a tie; the evaluated one where only one is).
+__global__ __launch_bounds__(256) void k_glm_quant(size_t K, int P, size_t b0, GlLev lv, GlSum sm, GlWs ws) {
+    __shared__ double part[3][GL_QL][4], xs[GL_QL];
+    __shared__ int act[GL_QL], nact;
+    const int t = threadIdx.x, j = (int)(blockIdx.x % (unsigned)P), l0 = (int)(blockIdx.x / (unsigned)P) * GL_QL;
+    const int nl = lv.nq - l0 < GL_QL ? lv.nq - l0 : GL_QL, lane = t & 63, wave = t >> 6;
+    const size_t bl = blockIdx.y, b = b0 + bl;
+    const double* rec = ws.rec + bl * GR_LEN;
+    const double* tp = ws.tpk + (bl * P + j) * K;
+    const double* ch = ws.chat + bl * K;
+    double* out = sm.quant + (b * lv.nq + l0) * (size_t)P + j;       // level l at out[l P]
+    if (rec[GR_ST] != 0.0) {
+        if (t < nl) out[(size_t)t * P] = dn_nan();
+        return;
+    }
+    const double sd = sqrt(rec[GR_T + j * GL_MAX + j]), ri = 1.0 / (sd * 1.4142135623730951);
+    const double kf = ri * 0.5641895835477563, kd = 2.0 * ri;    // f = kf sum c exp(-a^2), f' / f = kd sum c a exp(-a^2) / sum c exp(-a^2)
+    double q = 0.0, lo = 0.0, hi = 0.0, Flo = dn_nan(), Fhi = dn_nan(), x = 0.0;
+    int slack = GL_QSLACK, it = 0;
+    if (t < nl) {
+        const GlQs s = ws.qs[bl * P + j];
+        const double z = lv.z[l0 + t], sz = sd * z, eps = 1.7763568394002505e-15;      // 2^-49
+        q = lv.q[l0 + t];
+        lo = gl_unord(gl_ord((s.tlo + sz) - eps * (fabs(s.tlo) + fabs(sz))) - 4);
+        hi = gl_unord(gl_ord((s.thi + sz) + eps * (fabs(s.thi) + fabs(sz))) + 4);
+        x = fma(s.sd, z, s.mean);                                 // the quantile of a Gaussian of the mixture's mean and variance
+        if (!(x > lo && x < hi)) x = gl_unord(gl_ord(lo) + (gl_ord(hi) - gl_ord(lo)) / 2);
+        xs[t] = x;
+        act[t] = 1;
+    }
+    if (t == 0) nact = nl;
+    __syncthreads();
+    while (nact > 0 && it < GL_QCAP) {                             // (uniform: nact is read between two barriers)
+        double xl[GL_QL], a0[GL_QL], a1[GL_QL], a2[GL_QL];
+        bool on[GL_QL];
+#pragma unroll
+        for (int l = 0; l < GL_QL; l++) {
+            on[l] = l < nl && act[l] != 0;
+            xl[l] = on[l] ? xs[l] : 0.0;
+            a0[l] = a1[l] = a2[l] = 0.0;
+        }
+        for (size_t e = t; e < K; e += 256) {
+            const double te = tp[e], ce = ch[e];
+#pragma unroll
+            for (int l = 0; l < GL_QL; l++)
+                if (on[l]) {                                       // (uniform over the work-group)
+                    const double a = (te - xl[l]) * ri, ex = ce * exp(-(a * a));
+                    a0[l] = fma(ce, erfc(a), a0[l]);
+                    a1[l] += ex;
+                    a2[l] = fma(a, ex, a2[l]);
+                }
+        }
+#pragma unroll
+        for (int l = 0; l < GL_QL; l++)
+            if (on[l]) {
+                const double s0 = gl_wave_sum(a0[l]), s1 = gl_wave_sum(a1[l]), s2 = gl_wave_sum(a2[l]);
+                if (lane == 0) { part[0][l][wave] = s0; part[1][l][wave] = s1; part[2][l][wave] = s2; }
+            }
+        __syncthreads();
+        it++;
+        if (t < nl && act[t]) {
+            const double F = 0.5 * (((part[0][t][0] + part[0][t][1]) + part[0][t][2]) + part[0][t][3]);
+            const double E = ((part[1][t][0] + part[1][t][1]) + part[1][t][2]) + part[1][t][3];
+            const double A = ((part[2][t][0] + part[2][t][1]) + part[2][t][2]) + part[2][t][3];
+            const double r = F - q;
+            const uint64_t W = gl_ord(hi) - gl_ord(lo);
+            if (r < 0.0) { lo = x; Flo = F; } else { hi = x; Fhi = F; }
+            const uint64_t W2 = gl_ord(hi) - gl_ord(lo);
+            if (W2 <= 1) {
+                act[t] = 0;
+                atomicSub(&nact, 1);
+            } else {
+                if (W2 > W - W / 2) slack--;
+                double s = r / (kf * E);
+                const double h = 1.0 - 0.5 * s * (kd * (A / E));
+                if (h >= 0.5 && h <= 2.0) s /= h;
+                double xn = x - s;
+                if (xn == x) xn = gl_unord(r < 0.0 ? gl_ord(x) + 1 : gl_ord(x) - 1);
+                x = (slack > 0 && xn > lo && xn < hi) ? xn : gl_unord(gl_ord(lo) + W2 / 2);
+                xs[t] = x;
+            }
+        }
+        __syncthreads();
+    }
+    if (t < nl) {
+        const bool up = !isnan(Fhi) && (isnan(Flo) || Fhi - q <= q - Flo);
+        out[(size_t)t * P] = up ? hi : lo;
+    }
+}
+
 // the blocks of one batch of bb targets, each with one byte count that the allocation and abc_glm_need share
 struct GlBytes {
-    size_t Z, wv, part1, part2, rec, tpk, row, seg, pf, pg;
-    size_t per_target() const { return Z + wv + part1 + part2 + rec + tpk + 3 * row + seg + pf + pg; }
+    size_t Z, wv, part1, part2, rec, tpk, row, seg, pf, pg, qs;
+    size_t per_target() const { return Z + wv + part1 + part2 + rec + tpk + 3 * row + seg + pf + pg + qs; }
 };
-GlBytes gl_bytes(size_t K, size_t n, size_t P, size_t G) {
+// sum: the call computes a summary (the four older entries: never, and their bytes are what they were)
+GlBytes gl_bytes(size_t K, size_t n, size_t P, size_t G, bool sum) {
     const GlPlan pl = gl_plan(K);
     const size_t D = n + P, nchunk = (G + GL_GC - 1) / GL_GC;
     GlBytes y;
@@ -686,11 +858,12 @@ GlBytes gl_bytes(size_t K, size_t n, size_t P, size_t G) {
     y.seg = P * sizeof(GlSeg);
     y.pf = P * nchunk * 8;
     y.pg = P * nchunk * 4;
+    y.qs = sum ? P * sizeof(GlQs) : 0;
     return y;
 }
 // targets per batch, from the bound nA of n so that the arena bound does not depend on the fit
-size_t gl_batch(size_t K, size_t nA, size_t P, size_t G, size_t B) {
-    size_t bb = GL_BATCH_BYTES / gl_bytes(K, nA, P, G).per_target();
+size_t gl_batch(size_t K, size_t nA, size_t P, size_t G, size_t B, bool sum) {
+    size_t bb = GL_BATCH_BYTES / gl_bytes(K, nA, P, G, sum).per_target();
     if (bb < 1) bb = 1;
     if (bb > GL_MAX_GRID_Y) bb = GL_MAX_GRID_Y;
     return bb < B ? bb : B;
@@ -707,19 +880,47 @@ GlOut gl_out(const abc_glm* m) {
     return o;
 }
 
+// Phi^-1(p), 0 < p < 1: Acklam's rational approximation (relative error 1.2e-9) and two of Halley's steps on erfc, in the lower half
+// (p > 1/2: -Phi^-1(1 - p), whose argument is exact)
+double gl_norm_inv(double p) {
+    if (p > 0.5) return -gl_norm_inv(1.0 - p);
+    static const double a[6] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02,
+                                1.383577518672690e+02, -3.066479806614716e+01, 2.506628277459239e+00};
+    static const double b[5] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02,
+                                6.680131188771972e+01, -1.328068155288572e+01};
+    static const double c[6] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00,
+                                -2.549732539343734e+00, 4.374664141464968e+00, 2.938163982698783e+00};
+    static const double d[4] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00};
+    double x;
+    if (p < 0.02425) {
+        const double q = sqrt(-2.0 * log(p));
+        x = (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
+    } else {
+        const double q = p - 0.5, r = q * q;
+        x = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
+            (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
+    }
+    for (int i = 0; i < 2; i++) {
+        const double e = 0.5 * erfc(-x * 0.7071067811865476) - p, u = e * 2.5066282746310002 * exp(0.5 * x * x);
+        x -= u / (1.0 + 0.5 * x * u);
+    }
+    return x;
+}
+
 }  // namespace
 
-size_t abc_glm_need(size_t B, size_t K, size_t P, size_t nA, size_t G) {
+size_t abc_glm_need(size_t B, size_t K, size_t P, size_t nA, size_t G, bool sum) {
     if (nA > GL_MAX) nA = GL_MAX;
-    const size_t bb = gl_batch(K, nA, P, G, B);
-    return abc_density_segs_need(B, K, P) + bb * gl_bytes(K, nA, P, G).per_target() + 16 * 256;
+    const size_t bb = gl_batch(K, nA, P, G, B, sum);
+    return abc_density_segs_need(B, K, P) + bb * gl_bytes(K, nA, P, G, sum).per_target() + 16 * 256 + (sum ? 256 : 0);
 }
 
 // sv: the parameters' values and weights as the marginal density reads them (the bandwidths' rule); S, sld, Y, ldy, idx, om, w, O, KCO:
-// as GlSrc; n <= 32 components, P <= 32; nA: the bound of n that abc_glm_need was asked with
+// as GlSrc; n <= 32 components, P <= 32; nA: the bound of n that abc_glm_need was asked with; sum: NULL, or the summary of a
+// *_summary entry (checked by the caller: probs in host memory, every level strictly inside (0, 1))
 int launch_glm(abc_ctx* ctx, const SmValues& sv, const double* S, size_t sld, const double* Y, size_t ldy, const uint64_t* idx,
                const double* om, const double* w, const double* O, int KCO, size_t B, size_t K, size_t P, size_t n, size_t nA,
-               const abc_glm* glm, const char* fn) {
+               const abc_glm* glm, const abc_summary* sum, const char* fn) {
     if (nA > GL_MAX) nA = GL_MAX;
     const GlOut o = gl_out(glm);
     abc_density dn;
@@ -731,8 +932,8 @@ int launch_glm(abc_ctx* ctx, const SmValues& sv, const double* S, size_t sld, co
     const DnSeg* hseg = nullptr;
     ABC_TRY(launch_density_segs(ctx, sv, B, K, P, &dn, &hseg, fn));
 
-    const size_t bb = gl_batch(K, nA, P, glm->G, B);
-    const GlBytes y = gl_bytes(K, n, P, glm->G);
+    const size_t bb = gl_batch(K, nA, P, glm->G, B, sum != nullptr);
+    const GlBytes y = gl_bytes(K, n, P, glm->G, sum != nullptr);
     const GlPlan pl = gl_plan(K);
     const int ni = (int)n, Pi = (int)P, D = ni + Pi, nchunk = (int)((glm->G + GL_GC - 1) / GL_GC);
     GlWs ws;
@@ -748,6 +949,21 @@ int launch_glm(abc_ctx* ctx, const SmValues& sv, const double* S, size_t sld, co
     ws.seg = (GlSeg*)abc_ws_alloc(ctx, bb * y.seg);
     ws.pf = (double*)abc_ws_alloc(ctx, bb * y.pf);
     ws.pg = (int*)abc_ws_alloc(ctx, bb * y.pg);
+    ws.qs = sum ? (GlQs*)abc_ws_alloc(ctx, bb * y.qs) : nullptr;
+    if (sum && !ws.qs) ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
+    GlSum sm = {nullptr, nullptr, nullptr};
+    GlLev lv;
+    memset(&lv, 0, sizeof(lv));
+    if (sum) {
+        sm.truth = sum->truth; sm.quant = sum->quant; sm.cdf = sum->cdf;
+        if (sum->quant) {
+            lv.nq = (int)sum->nq;
+            for (int q = 0; q < lv.nq; q++) {
+                lv.q[q] = sum->probs[q];
+                lv.z[q] = gl_norm_inv(sum->probs[q]);
+            }
+        }
+    }
     if (!ws.Z || !ws.wv || !ws.part1 || !ws.part2 || !ws.rec || !ws.tpk || !ws.logc || !ws.logn || !ws.chat || !ws.seg || !ws.pf || !ws.pg)
         ABC_FAIL(ctx, ABC_ERR_NOMEM, "%s: workspace exhausted", fn);
     ABC_HIP(ctx, hipFuncSetAttribute((const void*)k_glm_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GL_SOLVE_LDS));
@@ -771,6 +987,11 @@ int launch_glm(abc_ctx* ctx, const SmValues& sv, const double* S, size_t sld, co
         hipLaunchKernelGGL(k_glm_weights, dim3(nb), dim3(256), 0, ctx->stream, K, ni, b0, o, ws);
         hipLaunchKernelGGL(k_glm_stats, dim3((unsigned)P, nb), dim3(256), 0, ctx->stream, K, Pi, b0, o, ws);
         ABC_HIP(ctx, hipGetLastError());
+        if (sm.cdf) hipLaunchKernelGGL(k_glm_cdf, dim3((unsigned)P, nb), dim3(256), 0, ctx->stream, K, Pi, b0, sm, ws);
+        if (sm.quant)
+            hipLaunchKernelGGL(k_glm_quant, dim3((unsigned)(P * ((lv.nq + GL_QL - 1) / GL_QL)), nb), dim3(256), 0, ctx->stream, K, Pi, b0,
+                               lv, sm, ws);
+        if (sum) ABC_HIP(ctx, hipGetLastError());
         if (!dens) continue;
         hipLaunchKernelGGL(k_glm_dens, dim3((unsigned)(P * nchunk), nb), dim3(GL_BS), 0, ctx->stream, K, Pi, b0, nchunk, o, ws);
         if (nchunk > 1)

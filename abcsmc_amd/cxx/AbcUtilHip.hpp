@@ -952,6 +952,60 @@ inline TargetGlm weighted_glm(const Mat2D& theta, const Mat2D& stats, const Row&
     check(abc_glm_weighted(&g, context(), theta.data(), stats.data(), K, P, n, obs.data(), weights.empty() ? nullptr : weights.data()));
     return buf.target(0);
 }
+// The same two with the exact quantiles of the marginal mixtures at the levels probs (each strictly inside (0, 1)) and their CDF at a
+// truth (abc_glm_particle_ranking_pls_targets_summary, abc_glm_weighted_summary): quant (nq x P), cdf (P; empty without a truth).
+// truth: one row per target (B x P), or no rows; the generic form takes one row or an empty one.
+struct TargetGlmSummary {
+    TargetGlm glm;
+    Mat2D quant;
+    Row cdf;
+};
+namespace detail {
+inline TargetGlmSummary glm_summary_target(const GlmBuffers& buf, size_t b, const std::vector<double>& quant, const std::vector<double>& cdf,
+                                           size_t nq) {
+    TargetGlmSummary r{buf.target(b), Mat2D(nq, buf.P), Row(cdf.empty() ? 0 : buf.P)};
+    for (size_t q = 0; q < nq; q++)
+        for (size_t j = 0; j < buf.P; j++) r.quant(q, j) = quant[(b * nq + q) * buf.P + j];
+    for (size_t j = 0; j < r.cdf.size(); j++) r.cdf[j] = cdf[b * buf.P + j];
+    return r;
+}
+}  // namespace detail
+inline std::vector<TargetGlmSummary> particle_ranking_PLS_targets_glm_summary(const Mat2D& X, const Mat2D& Y, const Mat2D& targets,
+                                                                              const float_type train_frac, size_t K,
+                                                                              const std::vector<double>& probs, const Mat2D& truth = Mat2D(0, 0),
+                                                                              size_t G = 512, double cut = 3.0, double bw_scale = 1.0) {
+    if (!((0 < train_frac) && (train_frac <= 1))) throw HipError(ABC_ERR_INVALID, "training_fraction");
+    const size_t B = targets.rows(), P = Y.cols(), M = X.cols(), nq = probs.size();
+    const bool tr = truth.rows() != 0;
+    if (tr && (truth.rows() != B || truth.cols() != P)) throw HipError(ABC_ERR_INVALID, "truth needs one row of P values per target");
+    detail::GlmBuffers buf(B, P, G);
+    const abc_glm g = buf.descriptor(cut, bw_scale);
+    std::vector<double> tv(tr ? B * P : 0), quant(B * nq * P), cdf(tr ? B * P : 0);
+    for (size_t b = 0; tr && b < B; b++)
+        for (size_t j = 0; j < P; j++) tv[b * P + j] = truth(b, j);
+    const abc_summary sm = {probs.data(), nq, tr ? tv.data() : nullptr, nq ? quant.data() : nullptr, tr ? cdf.data() : nullptr};
+    check(abc_glm_particle_ranking_pls_targets_summary(&g, &sm, context(), X.data(), Y.data(), X.rows(), M, P, targets.data(), B, train_frac,
+                                                       max_components_ref(), component_rule(), nullptr, K, nullptr, nullptr, nullptr));
+    std::vector<TargetGlmSummary> res;
+    for (size_t b = 0; b < B; b++) res.push_back(detail::glm_summary_target(buf, b, quant, cdf, nq));
+    return res;
+}
+inline TargetGlmSummary weighted_glm_summary(const Mat2D& theta, const Mat2D& stats, const Row& obs, const std::vector<double>& probs,
+                                             const Row& truth = Row(0), const std::vector<double>& weights = {}, size_t G = 512,
+                                             double cut = 3.0, double bw_scale = 1.0) {
+    const size_t K = theta.rows(), P = theta.cols(), n = stats.cols(), nq = probs.size();
+    if (stats.rows() != K || obs.size() != n) throw HipError(ABC_ERR_INVALID, "stats needs one row per row of theta, obs one entry per statistic");
+    if (!weights.empty() && weights.size() != K) throw HipError(ABC_ERR_INVALID, "weights needs one entry per row");
+    const bool tr = truth.size() != 0;
+    if (tr && truth.size() != P) throw HipError(ABC_ERR_INVALID, "truth needs one value per parameter");
+    detail::GlmBuffers buf(1, P, G);
+    const abc_glm g = buf.descriptor(cut, bw_scale);
+    std::vector<double> quant(nq * P), cdf(tr ? P : 0);
+    const abc_summary sm = {probs.data(), nq, tr ? truth.data() : nullptr, nq ? quant.data() : nullptr, tr ? cdf.data() : nullptr};
+    check(abc_glm_weighted_summary(&g, &sm, context(), theta.data(), stats.data(), K, P, n, obs.data(),
+                                   weights.empty() ? nullptr : weights.data()));
+    return detail::glm_summary_target(buf, 0, quant, cdf, nq);
+}
 inline std::vector<size_t> particle_ranking_simple(const Mat2D& X_orig, const Mat2D& /* Y_orig */,
                                                    const Row& target_values) {
     const size_t N = X_orig.rows();

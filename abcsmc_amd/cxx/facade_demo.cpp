@@ -105,6 +105,9 @@ int main() {
         const std::vector<size_t> r_bc = particle_ranking_PLS(Xt, Y, Row(ot.v), 0.5);
         std::printf("box-cox: lambda[0] %.2f (column alone %.2f), best particle %zu\n", lam[0], optimize_box_cox(first), r_bc[0]);
         if (optimize_box_cox(first) != lam[0] || !(std::fabs(lam[0]) < 1.0)) return 7;
+        // the ABC-GLM posterior of the two targets with its exact 95 % interval and median
+        const std::vector<TargetGlmSummary> gs = particle_ranking_PLS_targets_glm_summary(X, Y, tg, 0.5, K, {0.025, 0.5, 0.975});
+        std::printf("glm: mean %.3f, median %.3f in [%.3f, %.3f]\n", gs[0].glm.mean[0], gs[0].quant(1, 0), gs[0].quant(0, 0), gs[0].quant(2, 0));
     } catch (const HipError& e) {
         std::printf("HipError %d: %s\n", e.code, e.what());
         return 1;

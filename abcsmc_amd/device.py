@@ -536,13 +536,17 @@ def weighted_hpd(V, w=None, mass=(0.95,), outputs=("lo", "hi", "plo", "phi"), ct
 
 
 def rank_targets_glm(X, model, A, targets, K, Y, G=512, cut=3.0, bw=None, bw_scale=1.0, exclude=None, dist=False,
-                     outputs=("dens", "lo_x", "step", "mode", "mode_dens", "mean", "var", "ess", "log_md", "status"), ctx=None):
+                     outputs=("dens", "lo_x", "step", "mode", "mode_dens", "mean", "var", "ess", "log_md", "status"), ctx=None,
+                     probs=None, truth=None):
     """rank_targets followed by the ABC-GLM posterior of every target (abc_glm_rank_targets_dev; the definition is in the header).
     bw: given bandwidths (B, P) or None (the marginal density's rule times bw_scale).  outputs: names among _lib.GLM_OUTPUTS.
     Works on device tensors; the one copy is the model's ncomp, read back after the call (a synchronisation).  Returns dict(idx (B, K)
     int64, dist (B, K) or None, ncomp, and the outputs asked
     for (None for the rest): dens (B, P, G), lo_x, step, mode, mode_dens, mean, var (B, P), ess, log_md (B,), status (B,) int32,
-    C (B, n, P), c0 (B, n), sigma_s (B, n, n) at the model's n = ncomp, T (B, P, P), peaks (B, K, P), c (B, K))."""
+    C (B, n, P), c0 (B, n), sigma_s (B, n, n) at the model's n = ncomp, T (B, P, P), peaks (B, K, P), c (B, K)).
+    probs (host: 1 to 64 levels strictly inside (0, 1)) and truth (a (B, P) device tensor): the exact quantiles quant (B, nq, P) of the
+    marginal mixtures and their CDF at the truth, cdf (B, P) (abc_glm_rank_targets_summary_dev; outputs may then be empty); with
+    both None the call and its result are those without."""
     N, M, P, B, dev, ctx, exclude, (ldx, ldy, ldt) = _targets_holders(X, targets, Y, exclude, ctx)
     unknown = set(outputs) - set(_lib.GLM_OUTPUTS)
     if unknown:
@@ -556,8 +560,22 @@ def rank_targets_glm(X, model, A, targets, K, Y, G=512, cut=3.0, bw=None, bw_sca
         bw = torch.as_tensor(bw, dtype=f64).to(dev).expand((B, P)).contiguous()
     d = _lib.Glm(int(G), float(cut), float(bw_scale), _ptr(bw), *[_ptr(r[k]) for k in _lib.GLM_OUTPUTS])
     r.update(idx=torch.empty((B, K), dtype=torch.int64, device=dev), dist=torch.empty((B, K), dtype=f64, device=dev) if dist else None)
-    ctx.check(lib().abc_glm_rank_targets_dev(C.byref(d), ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A,
-                                             targets.data_ptr(), ldt, B, _ptr(exclude), K, r["idx"].data_ptr(), _ptr(r["dist"])))
+    tail = (ctx.handle, X.data_ptr(), ldx, Y.data_ptr(), ldy, N, M, P, model.data_ptr(), A, targets.data_ptr(), ldt, B, _ptr(exclude), K,
+            r["idx"].data_ptr(), _ptr(r["dist"]))
+    if probs is None and truth is None:
+        ctx.check(lib().abc_glm_rank_targets_dev(C.byref(d), *tail))
+    else:
+        from .glm import _levels
+        pr = _levels(probs)
+        if truth is not None:
+            if tuple(truth.shape) != (B, P):
+                raise ValueError("truth must have shape %s" % ((B, P),))
+            truth = truth.to(device=dev, dtype=f64).contiguous()
+        r["quant"] = torch.empty((B, pr.size, P), dtype=f64, device=dev) if pr is not None else None
+        r["cdf"] = torch.empty((B, P), dtype=f64, device=dev) if truth is not None else None
+        sm = _lib.Summary(pr.ctypes.data if pr is not None else None, 0 if pr is None else pr.size, _ptr(truth), _ptr(r["quant"]),
+                          _ptr(r["cdf"]))
+        ctx.check(lib().abc_glm_rank_targets_summary_dev(C.byref(d), C.byref(sm), *tail))
     n = min(max(int(model[0].item()), 0), int(A))
     for k, tail in (("C", (n, P)), ("c0", (n,)), ("sigma_s", (n, n))):      # packed at the model's n components
         if r[k] is not None:

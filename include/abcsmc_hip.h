@@ -1115,6 +1115,51 @@ int abc_glm_weighted_dev(const abc_glm* glm, abc_ctx* ctx, const double* theta, 
 int abc_glm_weighted(const abc_glm* glm, abc_ctx* ctx, const double* theta, const double* stats, size_t K, size_t P, size_t n,
                      const double* obs, const double* w);
 
+/* ---- ABC-GLM posterior: exact quantiles and the CDF at a truth ---------------------------------------------------------------
+ * The four ABC-GLM entries with one more descriptor, an abc_summary (probs, nq, truth, quant, cdf) right after glm; both come in
+ * front of the context.  ABCtoolbox validates this estimator by the posterior quantile of the true parameter over many
+ * pseudo-observed sets (Wegmann et al. 2010); cdf is that quantile.
+ * Definition.  Every peak of parameter j has the one variance T_jj, so with sigma = sqrt(T_jj) the marginal CDF of step 4's mixture is
+ *   F_j(x) = sum over the counted rows e (w_e > 0), in the ranking's order, of c^_e Phi((x - t_e[j]) / sigma),
+ *   Phi(z) = erfc(-z / sqrt 2) / 2.
+ * For a target of status 0:
+ *   cdf[b][j] = F_j(truth[b][j]); a NaN truth gives NaN, -inf gives 0 and +inf gives 1.
+ *   quant[b][q][j] = the x with F_j(x) = probs[q].  F_j is strictly increasing, so the root is unique.  It lies in
+ *     [min_e t_e[j] + sigma z_q, max_e t_e[j] + sigma z_q], z_q = Phi^-1(probs[q]), because every peak lies between the two
+ *     extremes.  The device closes that bracket (widened by 2^-49 of its terms and four doubles) with a safeguarded Newton
+ *     iteration on its own evaluation of F_j until no double lies strictly between the ends, and returns the end whose F_j is
+ *     nearer probs[q]: |F_j(quant) - probs[q]| is within the rounding of a K-term fp64 sum plus what one spacing of quant is
+ *     worth in F_j (the density there times that spacing).
+ * For a target whose status is not 0 every quant and cdf entry of that target is NaN; other targets are unaffected.
+ * Phi is evaluated with the device library's fp64 erfc, not with the density's term (whose relative error is about 1e-7).
+ * No sort, no knots and no interpolation convention enter: this is not abc_rank_targets_summary_dev's weighted sample quantile.
+ * Reduction order.  The order of every sum depends on (K, n, P, nq) only, and there are no floating-point atomics.  A target's
+ * quant and cdf are the same bits on a repeat, alone (B = 1) or in any batch, through the device and the host entry, whatever glm
+ * outputs are asked for beside them, and for each level whatever other levels are in probs.  The glm outputs written by these
+ * entries are bit for bit those of the corresponding entry above for the same arguments.
+ * Arguments.  sum is required (NULL: ABC_ERR_INVALID).  Every output member of glm is optional here and all may be NULL; G, cut,
+ * bw_scale and bw keep their meaning and their checks (G also when no grid output is asked for).  At least one of sum->quant,
+ * sum->cdf and the outputs of glm is required.  probs in host memory in every entry, nq in 1..64, every level finite and STRICTLY
+ * inside (0, 1) (the mixture's quantile at 0 or 1 is infinite; ABC_ERR_INVALID, although abc_summary allows both elsewhere), any
+ * order, repeats allowed; probs and nq are read only when quant is given.  cdf without truth is ABC_ERR_INVALID.
+ * Shapes as abc_summary's: quant B x nq x P ([b][q][j]), cdf and truth B x P; the generic entries nq x P and P.  Memory as the
+ * entry point's other arrays.  Every other check, limit and refusal is that of the entry above that the new one extends, with
+ * the same message, before anything is ranked.  Like the ABC-GLM posterior itself this is NOT checked against ABCtoolbox. */
+int abc_glm_rank_targets_summary_dev(const abc_glm* glm, const abc_summary* sum, abc_ctx* ctx, const double* X, size_t ldx,
+                                     const double* Y, size_t ldy, size_t N, size_t M, size_t P, const double* model, size_t A,
+                                     const double* targets, size_t ldt, size_t B, const uint64_t* exclude, size_t K, uint64_t* idx,
+                                     double* dist);
+/* HOST-pointer drop-in: every array of glm and sum in host memory. */
+int abc_glm_particle_ranking_pls_targets_summary(const abc_glm* glm, const abc_summary* sum, abc_ctx* ctx, const double* X,
+                                                 const double* Y, size_t N, size_t M, size_t P, const double* targets, size_t B,
+                                                 double train_frac, int max_comp, int rule, const uint64_t* exclude, size_t K,
+                                                 uint64_t* idx, double* dist, int32_t* ncomp);
+/* The generic forms (B = 1), as abc_glm_weighted_dev and abc_glm_weighted. */
+int abc_glm_weighted_summary_dev(const abc_glm* glm, const abc_summary* sum, abc_ctx* ctx, const double* theta, size_t ldv,
+                                 const double* stats, size_t lds, size_t K, size_t P, size_t n, const double* obs, const double* w);
+int abc_glm_weighted_summary(const abc_glm* glm, const abc_summary* sum, abc_ctx* ctx, const double* theta, const double* stats,
+                             size_t K, size_t P, size_t n, const double* obs, const double* w);
+
 /* ---- Box-Cox transform of the metrics: the skewness search and the transform (ABC::optimize_box_cox, AbcUtil.cpp:89-109) ---------
  * PLS is linear; simulated metrics (counts, sizes, durations) are positive and right-skewed.  The reference searches, per metric, a
  * grid of exponents for the lambda whose transform (x^lambda - 1) / lambda has the smallest |skewness| (its ranking carries the
